@@ -8,7 +8,16 @@ sampler scan, log-densities, MH accept.  Inputs are resident in HBM before the t
 seconds (independent chains: weak scaling, no data-path collective; torch.distributed (RCCL) is used only for the barrier, the
 max-over-ranks and the final chain-gather).
 
-On the same JSON line:
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, W warm-up steps, EXACTLY N timed steps, the
+result line (`value`, `ms_per_step` = milliseconds of one timed step).  Its `roofline` and `cpu_baseline` are null and `kernels` is
+empty: everything below is measured only with `--full` (`--secondary`, `--small-secondary` require it).
+
+--dump-outputs DIR  after the timed steps, writes what the timed path's last step returned to its caller as DIR/<name>.npy (float32 /
+                    float64): C2 -> x (chains, T, d), accepted (chains,), logs (chains, 5); --workload csmc -> x (chains, T, 1), ancestors
+                    (chains, T).  Above DUMP_BYTES in all, the per-chain trajectories keep a fixed seeded sample of time steps (t_index.npy).
+                    Inputs and keys are seeded: the same arguments give the same inputs on every run.
+
+With --full, on the same JSON line:
   roofline      the filter's scan (the parallel-in-time scan of the metric; the largest chain pass of the step), timed LIVE with HIP events on the library's stream inside the timed region
                 (auxssm_prof_*, one event pair per launch of that group); `achieved` = the bytes THAT group has to move (its per-chain
                 inputs read once + its outputs written once + chain-shared tables once; DESIGN.md section 4 lists the per-step reals of
@@ -44,6 +53,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0       # MI355X_MICROARCH.md: HBM3E ~8 TB/s
 MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32 / 32x32x2_f32 dense peak
+DUMP_BYTES = 60_000_000       # --dump-outputs: array bytes in all, over every rank (under 64 MB with the .npy headers)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -64,8 +74,12 @@ def parse_args(argv=None):
                     help="headline on the general per-chain path (AUXSSM_OPT_SHARE_MODEL = 0)")
     ap.add_argument("--no-general-leg", action="store_true", help="skip the extra run of the general per-chain path")
     ap.add_argument("--no-secondary", action="store_true", help="skip the C3 / C4 / C5 legs")
-    ap.add_argument("--secondary", default="c3,c4,c5,sv", help="comma list of secondary legs to run")
+    ap.add_argument("--secondary", default=None, help="comma list of secondary legs to run (--full; default c3,c4,c5,sv)")
     ap.add_argument("--small-secondary", action="store_true", help="shrink the secondary legs (contract tests): not the BASELINE sizes")
+    ap.add_argument("--full", action="store_true",
+                    help="also the profile pass (kernels, roofline), the general-path leg, the secondary legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path's last step returned as DIR/<name>.npy")
     ap.add_argument("--workload", default="kalman", choices=["kalman", "csmc"],
                     help="kalman = BASELINE configs[1] (C2, the headline); csmc = configs[2] (C3) as the only workload")
     ap.add_argument("--N", type=int, default=1024, help="particles (csmc workload)")
@@ -76,6 +90,13 @@ def parse_args(argv=None):
         args.dtype = "f32" if args.workload == "csmc" else "f64"
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
         ap.error("--gpus >= 1, --steps >= 1, --warmup >= 0")
+    if not args.full:
+        if args.secondary is not None or args.small_secondary:
+            ap.error("--secondary / --small-secondary run legs that only --full measures: add --full")
+        # a plain run: the headline's own steps and nothing else
+        args.no_prof = args.no_general_leg = args.no_secondary = args.no_cpu_baseline = True
+    if args.secondary is None:
+        args.secondary = "c3,c4,c5,sv"
     return args
 
 
@@ -406,8 +427,9 @@ def leg_c2(ctx, args, share, steps, warmup, chains_obj=None):
     return out
 
 
-def leg_c3_csmc(ctx, T, N, Cn, steps, warmup, dtype=np.float32, cpu=False):
-    """BASELINE configs[2] = C3: SV d=1, auxiliary cSMC with independent proposals, backward sampling, in-kernel Threefry noise."""
+def leg_c3_csmc(ctx, T, N, Cn, steps, warmup, dtype=np.float32, cpu=False, prof=True, outputs=False):
+    """BASELINE configs[2] = C3: SV d=1, auxiliary cSMC with independent proposals, backward sampling, in-kernel Threefry noise.
+    outputs: also return the last step's trajectories and ancestors (host arrays) under "outputs"."""
     import ctypes as C
     from aux_ssm_samplers_amd import random as R
     from aux_ssm_samplers_amd.csmc import _device, GaussianInit, LinearGaussianDynamics, SVPotential
@@ -431,12 +453,15 @@ def leg_c3_csmc(ctx, T, N, Cn, steps, warmup, dtype=np.float32, cpu=False):
         _lib.check(handle.lib.auxssm_csmc_sweep(handle.h, _lib.dtype_code(dtype), C.byref(m), Cn, T, N, 1, shd.ptr, xd.ptr,
                                                 C.byref(nz), anc.ptr, None, None, None))
 
-    el, groups = ctx.timed(step, steps, warmup)
-    moved = float((anc.to_host() != 0).mean())
+    el, groups = ctx.timed(step, steps, warmup, prof=prof)
+    anc_h = anc.to_host()
+    moved = float((anc_h != 0).mean())
     s = np.dtype(dtype).itemsize
     out = dict(workload=f"C3: stochastic volatility d=1 T={T}, auxiliary cSMC N={N}, independent proposals, backward sampling",
                chains_per_gpu=Cn, steps=steps, value=round(Cn * ctx.world * steps / el, 2), unit="sweeps/s", ms_per_step=round(el / steps * 1e3, 3),
                dtype="f32" if s == 4 else "f64", updated_fraction=moved)
+    if outputs:
+        out["outputs"] = dict(x=xd.to_host().reshape(Cn, T, 1), ancestors=anc_h)
     kern = {}
     alg = {"csmc_fwd": Cn * T * N * (1 * s + s),   # forward pass writes xs + log_ws (As is not stored with backward sampling)
            "csmc_bwd": Cn * T * N * (1 * s + s)}   # backward sampling re-reads them
@@ -754,6 +779,32 @@ def cpu_baseline_c2(T, d, budget_s=12.0):
                         f"on {nthr} OpenMP threads in {en:.1f} s; 1 thread: {r1} sweep(s) in {e1:.1f} s; same T={T} d={d} fp64 workload"))
 
 
+def dump_outputs(outdir, per_chain, other, rank, world, budget=DUMP_BYTES):
+    """--dump-outputs: np.save every array as float32 / float64 (integers -> float64, exact).  per_chain: {name: (chains, T, ...)} trajectories;
+    other: small arrays, written whole.  Above `budget / world` bytes the trajectories keep the same seeded sample of time steps, written as
+    t_index.npy.  With more than one rank every file name carries the rank."""
+    def real(a):
+        a = np.asarray(a)
+        return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+
+    per_chain = {k: real(v) for k, v in per_chain.items()}
+    other = {k: real(v) for k, v in other.items()}
+    budget //= world
+    small = sum(a.nbytes for a in other.values())
+    big = sum(a.nbytes for a in per_chain.values())
+    if small + big > budget:
+        T = next(iter(per_chain.values())).shape[1]
+        per_t = big // T + 8  # (+ its t_index entry)
+        nt = max(1, (budget - small) // per_t)
+        t_index = np.sort(np.random.default_rng(0).choice(T, size=min(nt, T), replace=False))
+        per_chain = {k: np.ascontiguousarray(a[:, t_index]) for k, a in per_chain.items()}
+        other["t_index"] = t_index.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for k, a in {**per_chain, **other}.items():
+        np.save(os.path.join(outdir, f"{k}{sfx}.npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
@@ -773,7 +824,10 @@ def main(argv=None):
 
     if args.workload == "csmc":
         r = leg_c3_csmc(ctx, args.T, args.N, args.chains, args.steps, args.warmup, np.float32 if args.dtype == "f32" else np.float64,
-                        cpu=not args.no_cpu_baseline and world == 1 and rank == 0)
+                        cpu=not args.no_cpu_baseline and world == 1 and rank == 0, prof=args.full, outputs=args.dump_outputs is not None)
+        if args.dump_outputs is not None:
+            o = r.pop("outputs")
+            dump_outputs(args.dump_outputs, o, {}, rank, world)
         if rank == 0:
             print(json.dumps({
                 "metric": "Gibbs sweeps/sec (auxiliary cSMC, backward sampling)", "value": r["value"], "unit": "sweeps/s", "n_gpus": world,
@@ -787,6 +841,9 @@ def main(argv=None):
     share = not args.no_share_model
     main_leg = leg_c2(ctx, args, share, args.steps, args.warmup)
     chains, kernel = main_leg["chains_obj"]
+    if args.dump_outputs is not None:
+        # the state a caller of the sweep receives (KalmanSampler(x=chains, updated=chains.accepted)), before any other leg sweeps these chains again
+        dump_outputs(args.dump_outputs, dict(x=chains.to_host()), dict(accepted=chains.accepted.to_host(), logs=chains.logs.to_host()), rank, world)
 
     general = None
     if share and not args.no_general_leg and not args.no_prof and main_leg["mode"] in ("shared", "fused"):

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,3 +62,44 @@ def test_spawn_passes_the_childs_exit_code_on(tmp_path):
     import json
     argv = json.loads(rec.read_text())
     assert "--nproc-per-node=2" in argv and argv[-4:] == ["--gpus", "2", "--steps", "2"]
+
+
+def test_plain_run_measures_the_headline_only_and_full_keeps_the_rest():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.steps == 7 and a.warmup == 2
+    assert a.no_prof and a.no_general_leg and a.no_secondary and a.no_cpu_baseline
+    f = bench.parse_args(["--gpus", "1", "--full"])
+    assert not (f.no_prof or f.no_general_leg or f.no_secondary or f.no_cpu_baseline) and f.secondary == "c3,c4,c5,sv"
+    assert bench.parse_args(["--full", "--secondary", "c3", "--small-secondary"]).secondary == "c3"
+    for extra in (["--secondary", "c3"], ["--small-secondary"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(extra)
+
+
+def test_dump_outputs_writes_reals_within_the_budget(tmp_path):
+    rng = np.random.default_rng(3)
+    x = rng.standard_normal((8, 1000, 4))
+    anc = rng.integers(0, 100, (8, 1000)).astype(np.int32)
+    acc = np.array([1, 0, 1, 1, 0, 0, 1, 0], np.int32)
+    bench.dump_outputs(str(tmp_path / "all"), dict(x=x, ancestors=anc), dict(accepted=acc), rank=0, world=1)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert set(got) == {"x", "ancestors", "accepted"} and all(a.dtype in (np.float32, np.float64) for a in got.values())
+    np.testing.assert_array_equal(got["x"], x)
+    np.testing.assert_array_equal(got["ancestors"], anc)
+    np.testing.assert_array_equal(got["accepted"], acc)
+    # over the budget: the same seeded time steps of every trajectory, and their indices
+    budget = 100_000
+    for rep in ("s0", "s1"):
+        bench.dump_outputs(str(tmp_path / rep), dict(x=x, ancestors=anc), dict(accepted=acc), rank=0, world=1, budget=budget)
+    s0 = {f[:-4]: np.load(tmp_path / "s0" / f) for f in os.listdir(tmp_path / "s0")}
+    s1 = {f[:-4]: np.load(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")}
+    assert set(s0) == {"x", "ancestors", "accepted", "t_index"} and sum(a.nbytes for a in s0.values()) <= budget
+    ti = s0["t_index"].astype(np.int64)
+    assert np.all(np.diff(ti) > 0) and ti[-1] < 1000
+    np.testing.assert_array_equal(s0["x"], x[:, ti])
+    np.testing.assert_array_equal(s0["ancestors"], anc[:, ti])
+    for k in s0:
+        np.testing.assert_array_equal(s0[k], s1[k])
+    # more than one rank: the files carry the rank
+    bench.dump_outputs(str(tmp_path / "r"), dict(x=x), {}, rank=1, world=2)
+    assert os.listdir(tmp_path / "r") == ["x_rank1.npy"]

@@ -10,11 +10,12 @@ if [ "$1" = build ]; then
   done
 else
   cd ../..
+  OUT=${OUT:-bench_logs}; mkdir -p "$OUT"
   for m in $2; do
-    AUXSSM_LIB=$PWD/aux_ssm_samplers_amd/libauxssm_abl$m.so timeout -k 10 200 python bench.py --secondary c3 --no-cpu-baseline --steps 2 --warmup 1 --T 1024 --chains 4 > gpurun_out/c3_abl$m.log 2>&1 || { tail -3 gpurun_out/c3_abl$m.log; exit 1; }
+    AUXSSM_LIB=$PWD/aux_ssm_samplers_amd/libauxssm_abl$m.so timeout -k 10 200 python bench.py --full --secondary c3 --no-cpu-baseline --steps 2 --warmup 1 --T 1024 --chains 4 > "$OUT/c3_abl$m.log" 2>&1 || { tail -3 "$OUT/c3_abl$m.log"; exit 1; }
     python - <<PY
 import json
-for l in open("gpurun_out/c3_abl$m.log"):
+for l in open("$OUT/c3_abl$m.log"):
     if l.startswith("{"):
         d = json.loads(l)["secondary"]["C3_csmc"]
         print("ablate $m:", d["value"], {k: v["ms_per_step"] for k, v in d["kernels"].items()})

@@ -6,9 +6,9 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_${1:-x}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-C2="$R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary"
-C5="$R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --secondary c5 --T 1024 --chains 4"
-C3="$R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --secondary c3 --T 1024 --chains 4"
+C2="$R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary"
+C5="$R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --secondary c5 --T 1024 --chains 4"
+C3="$R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --secondary c3 --T 1024 --chains 4"
 run() { name=$1; shift; echo "== $name"; timeout -k 10 500 rocprofv3 "$@" > $OUT/$name.log 2>&1 || { tail -5 $OUT/$name.log; exit 1; }; }
 run stats_c2 --kernel-trace --stats --output-format csv -d $OUT/stats_c2 -- python3 $C2
 run pmc_fetch_c2 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_c2 -- python3 $C2

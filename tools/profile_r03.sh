@@ -8,10 +8,10 @@ shift || true
 WHAT=${@:-c2}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-C2="$R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-general-leg"
-C2G="$R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-share-model"
-C5="$R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --secondary c5 --T 1024 --chains 4"
-C3="$R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --secondary c3 --T 1024 --chains 4"
+C2="$R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-general-leg"
+C2G="$R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-share-model"
+C5="$R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --secondary c5 --T 1024 --chains 4"
+C3="$R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --secondary c3 --T 1024 --chains 4"
 run() { name=$1; shift; echo "== $name"; timeout -k 10 500 rocprofv3 "$@" > $OUT/$name.log 2>&1 || { tail -5 $OUT/$name.log; exit 1; }; }
 for w in $WHAT; do
   case $w in
