@@ -58,11 +58,10 @@ int side_open(auxssm_ctx* h, size_t need) {
     if (!s.streams[0]) {
         // lowest priority: the stage has whole sweeps of slack, the chain passes it overlaps do not
         int lo = 0, hi = 0;
-        static const int prio = [] { const char* e = getenv("AUXSSM_SIDE_PRIO"); return e ? atoi(e) : 1; }();  // 0 default priority, 1 lowest, 2 highest
-        const bool prio_on = prio != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess;
+        const bool prio_on = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess;
         bool ok = true;
         for (int p = 0; ok && p < NS; ++p) {
-            if (!prio_on || hipStreamCreateWithPriority(&s.streams[p], hipStreamNonBlocking, prio == 2 ? hi : lo) != hipSuccess)
+            if (!prio_on || hipStreamCreateWithPriority(&s.streams[p], hipStreamNonBlocking, lo) != hipSuccess)
                 ok = hipStreamCreateWithFlags(&s.streams[p], hipStreamNonBlocking) == hipSuccess;
             ok = ok && hipEventCreateWithFlags(&s.done[p], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s.sweep_end[p], hipEventDisableTiming) == hipSuccess &&
                  hipEventCreateWithFlags(&s.begun[p], hipEventDisableTiming) == hipSuccess;
@@ -148,10 +147,6 @@ AffPlan plan_aff(const auxssm_ctx* h, int S, int N, int parallel, int waves) {
     long long E = (N + want - 1) / want;
     if (E < 16) E = 16;
     if (E > 1024) E = 1024;
-    if (const char* ev = getenv("AUXSSM_AFF_E")) {  // tuning/debug override
-        const long long v = atoll(ev);
-        if (v >= 1 && v <= 65536) E = v;
-    }
     p.E = (int)E;
     p.nchunk = (int)((N + E - 1) / E);
     return p;
@@ -176,10 +171,6 @@ ScanPlan plan_scan(const auxssm_ctx* h, int S, int n, int parallel, int waves) {
     if (E < 32) E = (4 * E + 2) / 3;  // a chip that is only just full of one-chunk lanes: slightly longer chunks win (24 sequences: E = 32 beats 24 by 9 %)
     if (E < emin) E = emin;
     if (E > 512) E = 512;
-    if (const char* ev = getenv("AUXSSM_SCAN_E")) {  // tuning/debug override
-        const long long v = atoll(ev);
-        if (v >= 1 && v <= 4096) E = v;
-    }
     p.E = (int)E;
     p.nchunk = (int)((n + E - 1) / E);
     return p;
@@ -250,11 +241,6 @@ const SweepLogpdfEntry* sweep_logpdf_entry(int dtype, int D, int PO) {
 }
 
 static inline Arr cv(const auxssm_arr& a) { return Arr{a.ptr, (long long)a.sc, (long long)a.st, (long long)a.sb, 1}; }
-// AUXSSM_AUX_FLY=0 (debug / comparison runs): materialise the concatenated observations and the scan elements instead
-static bool aux_fly_enabled() {
-    static const bool on = [] { const char* e = getenv("AUXSSM_AUX_FLY"); return e ? atoi(e) != 0 : true; }();
-    return on;
-}
 
 static int check_dims(const auxssm_dims* d, bool need_dy) {
     if (!d) {
@@ -615,7 +601,7 @@ static int sweep_lg_concat(auxssm_ctx* h, int dtype, const auxssm_dims* dims, co
     const size_t mark = h->ws_off;
     // chain-shared parameters: the filtered covariances do not depend on the chain and are stored once, (T, D, D) dense with chain stride 0
     const bool shared_mode = !wide && chain_shared_mode(h, cm, C, T, model->Fs.sc == 0 && model->Qs.sc == 0 && model->bs.sc == 0 && model->P0.sc == 0);
-    const bool aux_fly = cm && T > 1 && !wide && aux_fly_enabled();  // u and the concatenated observations of t >= 1 are formed inside the filter
+    const bool aux_fly = cm && T > 1 && !wide;  // u and the concatenated observations of t >= 1 are formed inside the filter
     // a time-invariant real observation model (time stride 0 on Hs, Rs, cs: the broadcast views of a constant model) gives a time-invariant concatenated one: ONE
     // record with time stride 0 instead of T of them (C2 at one chain: 54 MB written and read back per sweep, 27 of its 240 us)
     const bool tinv = model->Hs.st == 0 && model->Rs.st == 0 && model->cs.st == 0;
@@ -649,9 +635,7 @@ static int sweep_lg_concat(auxssm_ctx* h, int dtype, const auxssm_dims* dims, co
     const Arr msA = cm ? cm_arr(ms, kd, D) : dense_arr(ms, kd, D);
     // general chain-minor sweep: the filtered covariances are an internal buffer the sampler reads twice -- kept symmetric-packed (10 instead of 16
     // reals at d = 4)
-    static const bool ps_pack_on = [] { const char* e = getenv("AUXSSM_PS_PACK"); return e ? atoi(e) != 0 : true; }();
-    static const bool samp_fly_on = [] { const char* e = getenv("AUXSSM_SAMPLE_FLY"); return e ? atoi(e) != 0 : true; }();
-    const bool ps_pack = ps_pack_on && samp_fly_on && cm && !shared_mode && !wide;
+    const bool ps_pack = cm && !shared_mode && !wide;
     // wide states, several chains on one model: ONE copy of the filtered covariances (chain stride 0) -- the chain-shared wide filter then skips its broadcast to
     // the chains' slots and the sampler builds its gain / factor tables once (wide.hip::run_sample_shared); the pattern carrier below replaces the filter's read-back
     const bool wide_shared = wide && C >= 2 && h->share_model && model->Fs.sc == 0 && model->Qs.sc == 0 && model->bs.sc == 0 && model->P0.sc == 0 &&
@@ -673,8 +657,7 @@ static int sweep_lg_concat(auxssm_ctx* h, int dtype, const auxssm_dims* dims, co
     // only draws row t = 0 and the acceptance uniforms); everywhere else the fill kernel draws all of it first.  Same values either way.
     bool gen = false;
     if (keys) {
-        static const bool gen_on = !getenv("AUXSSM_NO_GEN");
-        gen = gen_on && aux_fly && shared_mode && parallel && (C % 2 == 0) && plan_aff(h, C, T - 1, 1).nchunk > 1 && plan_aff(h, C, T, 1).nchunk > 1;
+        gen = aux_fly && shared_mode && parallel && (C % 2 == 0) && plan_aff(h, C, T - 1, 1).nchunk > 1 && plan_aff(h, C, T, 1).nchunk > 1;
         launch_rng_sweep<R>(h, keys, gen ? (long long)D * C : (long long)C * T * D, C, const_cast<void*>(eps_aux), const_cast<void*>(eps_samp), const_cast<void*>(u_acc));
     }
     {
@@ -810,8 +793,6 @@ __global__ void __launch_bounds__(256) k_fs_stats(int C, const int32_t* __restri
 // whether (and why not) a sweep can run the fused passes
 static const char* fused_refusal(const auxssm_ctx* h, const auxssm_dims* dims, const auxssm_lgssm* model, int parallel, int layout) {
     const int C = dims->C, T = dims->T, D = dims->dx, PO = dims->dy;
-    static const bool off = [] { const char* e = getenv("AUXSSM_FUSED"); return e && atoi(e) == 0; }();
-    if (off) return "AUXSSM_FUSED=0";
     if (layout != AUXSSM_LAYOUT_CHAIN_MINOR) return "the fused sweep takes the chain-minor layout";
     if (D > MAX_D || PO < 1 || PO > 4) return "the fused sweep is instantiated for dx <= 4, 1 <= dy <= 4";
     if (!parallel) return "the fused sweep is the parallel-in-time one";
@@ -873,7 +854,6 @@ static int sweep_lg_concat_fused(auxssm_ctx* h, int dtype, const auxssm_dims* di
     } memo_guard{h};
     if (overlap) {
         // MODEL-STAGE MEMO (ctx.h::SideStage): the head of the slab holds the `rebuild` word and a snapshot of the stage's inputs
-        static const bool memo_on = [] { const char* e = getenv("AUXSSM_STAGE_MEMO"); return !(e && atoi(e) == 0); }();
         SideScope sc(h);
         auxssm_ctx::SideStage& sd = h->side;
         const int p = sd.parity;
@@ -883,7 +863,7 @@ static int sweep_lg_concat_fused(auxssm_ctx* h, int dtype, const auxssm_dims* di
         const int nts[9] = {1, 1, T - 1, T - 1, T - 1, T, T, T, T};
         md.n = 9;
         md.off[0] = 0;
-        bool plain = memo_on;
+        bool plain = true;
         for (int q = 0; q < 9; ++q) {
             md.a[q] = cv(*srcs[q]);
             md.rec[q] = recs[q];
@@ -898,7 +878,7 @@ static int sweep_lg_concat_fused(auxssm_ctx* h, int dtype, const auxssm_dims* di
             // host key: everything the tables depend on besides the arrays' contents
             std::vector<unsigned char> key;
             auto put = [&](const void* v, size_t nb) { key.insert(key.end(), (const unsigned char*)v, (const unsigned char*)v + nb); };
-            const int hdr[8] = {(int)sR, C, T, D, PO, nan_policy, 0, 0};  // (the chunk length is a function of C, T and the process's environment)
+            const int hdr[8] = {(int)sR, C, T, D, PO, nan_policy, 0, 0};  // (the chunk length is a function of C and T)
             put(hdr, sizeof(hdr));
             put(&delta, sizeof(delta));
             for (int q = 0; q < 9; ++q) put(srcs[q], sizeof(auxssm_arr));
@@ -1139,9 +1119,8 @@ static int sweep_sv(auxssm_ctx* h, int dtype, int order, const auxssm_dims* dims
     const size_t sR = sizeof(R), CT = (size_t)C * T;
     const bool second = order == 2;
     // Per-chain observation model in the chain-minor layout (second order, or first order without chain-shared dynamics): no observation arrays -- the
-    // scan passes and the log-density pass re-form the pseudo-observations from (x, u, y) (FilterArgs::sv_order; AUXSSM_SV_FLY=0: the array path)
-    static const bool sv_fly_on = [] { const char* e = getenv("AUXSSM_SV_FLY"); return e ? atoi(e) != 0 : true; }();
-    const bool fly = sv_fly_on && cm && !wide && T > 1 &&
+    // scan passes and the log-density pass re-form the pseudo-observations from (x, u, y) (FilterArgs::sv_order)
+    const bool fly = cm && !wide && T > 1 &&
                      !(!second && chain_shared_mode(h, cm, C, T, model->Fs.sc == 0 && model->Qs.sc == 0 && model->bs.sc == 0 && model->P0.sc == 0));
     size_t need = 0;
     auto add = [&](size_t b) { need += b + 256; };
@@ -1440,7 +1419,7 @@ static int sweep_lorenz(auxssm_ctx* h, int dtype, const auxssm_dims* dims, const
     const long long psc = model->Fs.sc;
     auto arr = [&](const void* p, long long rec) { return cm ? cm_arr(p, kd, rec) : dense_arr(p, kd, rec); };
     const Arr xA = arr(x, D), xpA = arr(xp, D), uA = arr(u, D), yscA = arr(ysc, P);
-    const bool aux_fly = cm && T > 1 && aux_fly_enabled();  // u and the concatenated observations of t >= 1 are formed inside the filter
+    const bool aux_fly = cm && T > 1;  // u and the concatenated observations of t >= 1 are formed inside the filter
     // per-chain transition arrays have n = T - 1 rows: same strides as a T-row array of that record size
     const Arr F1A = arr(Fs1, 9), b1A = arr(bs1, 3), F2A = arr(Fs2, 9), b2A = arr(bs2, 3);
     {
@@ -1625,7 +1604,6 @@ int auxssm_create(int device, auxssm_handle* out) {
     AX_HIP(hipGetDeviceProperties(&prop, device));
     h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     AX_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    if (const char* e = getenv("AUXSSM_SHARED")) h->share_model = atoi(e) != 0;  // default of AUXSSM_OPT_SHARE_MODEL
     if (const char* e = getenv("AUXSSM_OVERLAP_TAB")) h->overlap_model_stage = atoi(e) != 0;  // default of AUXSSM_OPT_OVERLAP_MODEL_STAGE
     *out = h;
     return AUXSSM_OK;
@@ -1841,8 +1819,7 @@ int auxssm_kalman_filter(auxssm_handle h, int dtype, const auxssm_dims* dims, co
     fill_filter_args(a, dims, lgssm, ys, ms, Ps);
     // a wide batch axis (the reference's spatial example: B = 64 scalar LGSSMs side by side, examples/spatial/model.py:103-112): lanes <-> (c, b) sequences, which
     // are contiguous along b in every (C, T, B, .) array -- no element buffer, the sequential recursion inside each time chunk (kernels.hip.h::run_filter)
-    static const int lanes_b = [] { const char* e = getenv("AUXSSM_FILTER_BATCH_LANES"); return e ? atoi(e) : 32; }();
-    if (!is_wide(dims->dx, dims->dy) && lanes_b > 0 && dims->B >= lanes_b && (long long)dims->C * dims->B >= 256) a.lay.cm = 1;
+    if (!is_wide(dims->dx, dims->dy) && dims->B >= 32 && (long long)dims->C * dims->B >= 256) a.lay.cm = 1;
     return e->filter(h, a, parallel, ell);
 }
 

@@ -40,14 +40,6 @@ template <typename R, int D> __global__ void k_csmc_potbound(int T, FkDev<R> m, 
     }
     gb[t] = b;
 }
-// Diagnostic builds only (tools/csmc_ablate.sh): -DAUXSSM_CSMC_ABLATE=<mask> removes one phase of the forward step at a time (wrong results, right
-// shape) to attribute its time: 1 search, 2 in-kernel draws, 4 potential / transition log-density, 8 max + exp, 16 cumsum; 32: max + exp of the
-// BACKWARD pass.  0 in the product.
-#ifndef AUXSSM_CSMC_ABLATE
-#define AUXSSM_CSMC_ABLATE 0
-#endif
-constexpr int CSMC_ABL = AUXSSM_CSMC_ABLATE;
-
 // ---- forward pass (_csmc, csmc.py:69-107) -------------------------------------------------------------------------------
 // NW = 8 / 16: exactly NW full waves (N = blockDim = 64 NW: the C4 / C3 shapes): no liveness / group-bound selects (csmc_dev.h); NW = 0: any N
 // SP = 1: the instantiation of config C3's shape -- auxiliary independent proposals, the stochastic-volatility potential, a time-invariant linear transition, draws
@@ -158,10 +150,6 @@ template <typename R, int D, bool TV, bool GRAD, int NW, int SP = 0> __global__ 
 #pragma unroll
             for (int k = 0; k < D; ++k) eps[k] = live ? ((const R*)a.eps_prop)[eps_base + ((long long)t * N + tid) * D + k] : (R)0;
             if (live) un = ((const R*)a.u_res)[ures_base + (long long)(t - 1) * N + tid];
-        } else if (CSMC_ABL & 2) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) eps[k] = (R)0.25;
-            un = (R)0.37;
         } else if (t & 1) {  // normals cached by step t - 1; uniforms of steps t and t + 1
 #pragma unroll
             for (int k = 0; k < D; ++k) eps[k] = eps_nx[k];
@@ -182,12 +170,7 @@ template <typename R, int D, bool TV, bool GRAD, int NW, int SP = 0> __global__ 
 #pragma unroll
         for (int k = 0; k < D; ++k) xprev[tid * D + k] = x[k];
         R tot;
-        if (CSMC_ABL & 16) {
-            tot = (R)N;
-            c[cpad(tid)] = w;
-            __syncthreads();
-        } else
-            block_cumsum_dpp<R, NW, true>(w, c, red, tid, nw, tot);  // trailing barrier also publishes xprev; tot = c[N - 1]
+        block_cumsum_dpp<R, NW, true>(w, c, red, tid, nw, tot);  // trailing barrier also publishes xprev; tot = c[N - 1]
         if (used_bound && !(tot > (R)0)) {  // every weight of step t - 1 underflowed under its bound: the exact maximum after all (uniform)
             __syncthreads();                // (every lane is past its reads of the step's images before they are rewritten)
             w = block_expmax<R, NW>(lw, red, tid, nw, &mstep);
@@ -195,8 +178,7 @@ template <typename R, int D, bool TV, bool GRAD, int NW, int SP = 0> __global__ 
             block_cumsum_dpp<R, NW, true>(w, c, red, tid, nw, tot);
         }
         int idx = 0;
-        if (CSMC_ABL & 1) idx = (tid * 7) & (N - 1);
-        else if (live && tid > 0) idx = search2<R, NW, true>(c, N, tot * ((R)1 - un));
+        if (live && tid > 0) idx = search2<R, NW, true>(c, N, tot * ((R)1 - un));
         R xp[D];
 #pragma unroll
         for (int k = 0; k < D; ++k) xp[k] = xprev[idx * D + k];
@@ -225,21 +207,18 @@ template <typename R, int D, bool TV, bool GRAD, int NW, int SP = 0> __global__ 
             for (int k = 0; k < D; ++k) x[k] = xstar[(long long)t * D + k];
         }
         // weights (csmc.py:95-96)
-        if (CSMC_ABL & 4) lw = x[0] * (R)0.01;
-        else {
-            R g = potential<R, D>(m, x, ycur);
-            if (m.proposal == 1) {  // AuxiliaryGt = Mt.logpdf + Gt (independent.py:238-248)
-                R mu[D];
-                trans_mean_t<R, D>(m, tr, xp, mu);
-                g = gauss_chol_logpdf<R, D>(x, mu, tr.LQ, tr.iL, tr.c_trans, tr.ld) + g;
-                // GradientAuxiliaryGt (:252-268): in the reference the correction is summed over all particles, i.e. a constant of the
-                // step (AUXSSM_GRAD_REFERENCE: nothing to add); AUXSSM_GRAD_EXACT applies it per particle
-                if constexpr (GRAD) {
-                    if (m.gradient == 2) g = g + grad_correction<R, D>(x, uaux + (long long)t * D, pm, ((const R*)a.shd)[t]);
-                }
+        R g = potential<R, D>(m, x, ycur);
+        if (m.proposal == 1) {  // AuxiliaryGt = Mt.logpdf + Gt (independent.py:238-248)
+            R mu[D];
+            trans_mean_t<R, D>(m, tr, xp, mu);
+            g = gauss_chol_logpdf<R, D>(x, mu, tr.LQ, tr.iL, tr.c_trans, tr.ld) + g;
+            // GradientAuxiliaryGt (:252-268): in the reference the correction is summed over all particles, i.e. a constant of the
+            // step (AUXSSM_GRAD_REFERENCE: nothing to add); AUXSSM_GRAD_EXACT applies it per particle
+            if constexpr (GRAD) {
+                if (m.gradient == 2) g = g + grad_correction<R, D>(x, uaux + (long long)t * D, pm, ((const R*)a.shd)[t]);
             }
-            lw = live ? g : ninf;
         }
+        lw = live ? g : ninf;
         if (live) {
             const long long o = (long long)t * N + tid;
 #pragma unroll
@@ -247,19 +226,16 @@ template <typename R, int D, bool TV, bool GRAD, int NW, int SP = 0> __global__ 
             lws[o] = lw;
             if (As) As[(long long)(t - 1) * N + tid] = idx;
         }
-        if (CSMC_ABL & 8) w = lw * (R)0.001 + (R)1;
-        else {
-            // the shift of this step's weights (sweep contract): a reduction-free bound where there is one, else the block maximum
-            R Mb = gbt + (m.proposal == 1 ? tr.c_trans : (R)0);
-            used_bound = bmode && t < T - 1 && (Mb - Mb == 0);
-            if (used_bound) {
-                w = det_exp(lw - Mb);
-                mstep = Mb;
-            } else {
-                w = block_expmax<R, NW>(lw, red, tid, nw, &mstep);
-            }
-            if (fmax && tid == 0) fmax[t] = mstep;
+        // the shift of this step's weights (sweep contract): a reduction-free bound where there is one, else the block maximum
+        R Mb = gbt + (m.proposal == 1 ? tr.c_trans : (R)0);
+        used_bound = bmode && t < T - 1 && (Mb - Mb == 0);
+        if (used_bound) {
+            w = det_exp(lw - Mb);
+            mstep = Mb;
+        } else {
+            w = block_expmax<R, NW>(lw, red, tid, nw, &mstep);
         }
+        if (fmax && tid == 0) fmax[t] = mstep;
     }
     if (live) ((R*)a.wT)[(long long)ch * N + tid] = w;
 }
@@ -366,8 +342,7 @@ template <typename R, int D, bool TV, int NW> __global__ void __launch_bounds__(
         // log_ws[t] plus the transition's log-normaliser; the exact maximum only if everything underflowed
         R Mb = fm_t + tr.c_trans;
         if (!(Mb - Mb == 0)) Mb = 0;
-        if (CSMC_ABL & 32) w = lw * (R)0.001 + (R)1;  // (diagnostic build: the backward pass without its exp)
-        else w = det_exp(lw - Mb);
+        w = det_exp(lw - Mb);
         {   // ONE barrier per step: local scan values and wave totals of this parity are published together with xpub / ubuf; every wave then finds the
             // group and counts inside it on its own (csmc_dev.h::draw_two_level)
             const int lane = tid & 63, wv = tid >> 6;
@@ -526,8 +501,7 @@ static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, const double* host
         else if (fullw == 8) AX_FWD1(TVv, GRv, 8); \
         else AX_FWD1(TVv, GRv, 0);      \
     } while (0)
-        static const bool spec_on = [] { const char* e = getenv("AUXSSM_CSMC_SPEC"); return !(e && atoi(e) == 0); }();   // 0: the generic instantiation (measurement, tests)
-        const bool c3_shape = spec_on && D == 1 && sizeof(R) == 4 && fullw == 16 && !tv && !gr && fk->proposal == 1 && fk->potential == 2 && m.transition == 0 &&
+        const bool c3_shape = D == 1 && sizeof(R) == 4 && fullw == 16 && !tv && !gr && fk->proposal == 1 && fk->potential == 2 && m.transition == 0 &&
                               ab.As == nullptr && ab.noise_mode != 0 && !ab.pregen;
         if (c3_shape) {
             if constexpr (D == 1 && sizeof(R) == 4) {
@@ -756,7 +730,7 @@ extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_mod
                 if (cb > h->num_cu) cb -= cb % h->num_cu;  // one workgroup per chain and CU: whole rounds of the chip per batch
             }
         }
-        if (const char* ev = getenv("AUXSSM_CSMC_BATCH")) {  // tests: force small batches
+        if (const char* ev = getenv("AUXSSM_CSMC_BATCH")) {  // test hook: tests/test_gpu_csmc.py and tests/test_gpu_full_size.py force small batches
             const int v = atoi(ev);
             if (v >= 1 && v < cb) cb = v;
         }
@@ -772,7 +746,8 @@ extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_mod
     need += 2 * (CT * D * sR + 256) + (size_t)T * (1 + D) * sR + 256;
     // fewer chains than CUs: the forward pass's draws are generated up front by the whole chip (csmc_dev.h::k_csmc_pregen) when the two arrays fit
     const size_t pre_eps = CT * N * D * sR + 256, pre_u = (size_t)C * (T > 1 ? T - 1 : 1) * N * sR + 256;
-    bool pregen = noise->mode == AUXSSM_NOISE_THREEFRY && !wide && T > 1 && C < h->num_cu && cb == C && !getenv("AUXSSM_CSMC_NO_PREGEN");
+    bool pregen = noise->mode == AUXSSM_NOISE_THREEFRY && !wide && T > 1 && C < h->num_cu && cb == C &&
+                  !getenv("AUXSSM_CSMC_NO_PREGEN");  // test hook: tests/test_gpu_csmc.py and tests/test_gpu_full_size.py force the in-pass draws
     if (pregen) {
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess || (double)(need + pre_eps + pre_u) > 0.7 * (double)(fr + h->ws_bytes)) pregen = false;
@@ -794,8 +769,7 @@ extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_mod
     a.As = As_out ? As_out : (!backward ? (int32_t*)ws_take(h, (size_t)cb * (T > 1 ? T - 1 : 1) * N * 4) : nullptr);
     a.wT = ws_take(h, (size_t)C * N * sR);
     a.fmax = ws_take(h, (size_t)C * T * sR);
-    static const bool bound_on = !getenv("AUXSSM_CSMC_NO_BOUND");
-    a.gb = (bound_on && (fk->potential == 0 || fk->y)) ? ws_take(h, (size_t)T * sR) : nullptr;
+    a.gb = (fk->potential == 0 || fk->y) ? ws_take(h, (size_t)T * sR) : nullptr;
     a.anc = ancestors;
     a.noise_mode = noise->mode;
     a.key0 = noise->key0; a.key1 = noise->key1;

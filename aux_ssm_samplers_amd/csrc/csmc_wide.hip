@@ -167,10 +167,6 @@ template <typename R> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
 //   * the potential's sum over components is accumulated in component order from readlane broadcasts of the per-component terms;
 //   * weights, cumulative sums, searches and the single draw of the backward pass are done by wave 0 with one lane per particle, exactly as before.
 // Two workgroup barriers per time step in either pass.  In-kernel draws keep the natural flat indices (and use both normals of a Threefry block).
-#ifndef CW2_ABL
-#define CW2_ABL 0  // diagnostic builds: 1 no search, 2 no draws, 4 no substitution, 8 no potential sums, 16 no mean products (tools/cw2_ablate.sh)
-#endif
-
 template <typename R> struct Cw2Lds {
     int D, S;
     R *F, *LQ, *b, *iL, *c, *lwv, *xa, *xb, *eps, *blk;
@@ -274,7 +270,6 @@ template <typename R> __device__ __forceinline__ R grad_corr_half(int D, int k, 
 // element stride 1 (L[j] = L_kj), iLk = 1 / L_kk.  Every lane of the half-wave returns the same value.
 template <typename R> __device__ __forceinline__ R gauss_half(int D, int k, bool hi, R acc, const R* Lrow, R iLk, R cst) {
     R q = 0;
-    if (CW2_ABL & 4) return acc * cst;
     acc = k < D ? acc : (R)0;  // (components beyond D: z = 0, fma(0, 0, q) = q -- the 32 steps below are the D steps of the contract)
     R l[CSW_MAXD];
 #pragma unroll
@@ -292,7 +287,6 @@ template <typename R> __device__ __forceinline__ R gauss_half(int D, int k, bool
 // accumulator, in the same order, so the same bits -- and applies the four columns to its own accumulator in order.  Eight broadcast latencies per density instead of
 // thirty-two (profiles/r03_d_cw2_ablation.txt: the dependent broadcast chain was half of the sweep).  blk: Cw2Lds::blk (uniform reads).
 template <typename R> __device__ __forceinline__ R gauss_half_blk(int D, int k, R acc, const R* Lrow, const R* blk, R cst) {
-    if (CW2_ABL & 4) return acc * cst;
     R q = 0;
     acc = k < D ? acc : (R)0;
     R l[CSW_MAXD];
@@ -327,7 +321,6 @@ template <typename R> __device__ __forceinline__ R gauss_half_blk(int D, int k, 
 template <typename R> __device__ __forceinline__ R potential_half(const FkW<R>& m, int k, bool hi, R xk, R yk) {
     const int D = m.D;
     if (m.potential == 0) return (R)0;
-    if (CW2_ABL & 8) return xk * yk;
     if (m.potential == 1 || m.potential == 3) {
         const bool obs = m.potential == 1 || (yk - yk == 0);
         const R z = (k < D && obs) ? (yk - xk) * m.inv_sig_y : (R)0;
@@ -352,10 +345,6 @@ template <typename R> __device__ __forceinline__ R potential_half(const FkW<R>& 
 // this step's proposal noise into the LDS rows eps[n][k]: natural flat index ((ch T + t) N + n) D + k of stream 2, both normals of every Threefry block used
 template <typename R> __device__ __forceinline__ void cw2_draw(const CsmcArgs& a, Cw2Lds<R>& L, int ch, int t, int r, int nr) {
     const int N = a.N, D = L.D, S = L.S, ND = N * D;
-    if (CW2_ABL & 2) {
-        for (int e = r; e < N * S; e += nr) L.eps[e] = (R)0.25;
-        return;
-    }
     const long long base = (((long long)ch * a.T + t) * N) * D;
     if (a.noise_mode == 0) {
         for (int e = r; e < ND; e += nr) {
@@ -478,8 +467,7 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
             __builtin_amdgcn_wave_barrier();
             const R un = (live && lane > 0) ? noise_uniform<R>(a, a.u_res, STREAM_U_RES, ((long long)ch * (T - 1) + (t - 1)) * N + lane) : (R)0;
             int idx = 0;
-            if (CW2_ABL & 1) idx = (lane * 7) % N;
-            else if (live && lane > 0) idx = search_w<R>(L.c, N, tot * ((R)1 - un));
+            if (live && lane > 0) idx = search_w<R>(L.c, N, tot * ((R)1 - un));
             L.idx[lane] = idx;
             if (live && As) As[(long long)(t - 1) * N + lane] = idx;
             cw2_draw<R>(a, L, ch, t, lane, NT_);  // (its share of the draws: the other waves start with theirs)
@@ -495,10 +483,8 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
             const R* xp = xprev + L.idx[ir] * S;
             // the parent's transition mean, component k (csmc.py:91-92)
             R mu = bk;
-            if (!(CW2_ABL & 16)) {
 #pragma unroll
-                for (int j = 0; j < CSW_MAXD; ++j) mu = fma_(Frow[j], xp[j], mu);  // (columns beyond D are zeros on both sides: fma(0, 0, mu) = mu)
-            }
+            for (int j = 0; j < CSW_MAXD; ++j) mu = fma_(Frow[j], xp[j], mu);  // (columns beyond D are zeros on both sides: fma(0, 0, mu) = mu)
             R xk = 0, pmk = 0;
             if (k < D) {
                 if (m.proposal == 0) {
@@ -619,10 +605,8 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
             __builtin_amdgcn_wave_barrier();
             const R* xi = L.xa + ir * S;
             R mu = bk;
-            if (!(CW2_ABL & 16)) {
 #pragma unroll
-                for (int j = 0; j < CSW_MAXD; ++j) mu = fma_(Frow[j], xi[j], mu);
-            }
+            for (int j = 0; j < CSW_MAXD; ++j) mu = fma_(Frow[j], xi[j], mu);
             const R lwt = gauss_half_blk<R>(D, k, xn - mu, Lrow, L.blk, ctr) + lwik;  // Pt.logpdf(x_{t+1}, xs_t) + log_ws_t (csmc.py:136)
             if (pl && k == 0) L.lwv[i] = lwt;
         }
@@ -745,7 +729,7 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     const int cb = a.cb > 0 ? a.cb : a.C;
     // sixteen waves per chain (every particle of N <= 32 in its own half-wave at once: the shortest step) while the chains leave CUs to spare, eight (no idle
     // waves at N = 25, two passes) once there are more chains than CUs
-    const bool wide16 = sizeof(R) == 4 && (getenv("AUXSSM_CW_WAVES") ? atoi(getenv("AUXSSM_CW_WAVES")) == 16 : a.C <= h->num_cu);  // (fp64: the unrolled loops need more than the 128 registers of a 1024-lane workgroup)
+    const bool wide16 = sizeof(R) == 4 && a.C <= h->num_cu;  // (fp64: the unrolled loops need more than the 128 registers of a 1024-lane workgroup)
     for (int c0 = 0; c0 < a.C; c0 += cb) {
         CsmcArgs ab = a;
         ab.c0 = c0;

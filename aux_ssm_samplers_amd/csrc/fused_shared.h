@@ -423,12 +423,10 @@ __device__ __forceinline__ bool fs_terms_fast(const R* row, const R* v, const R*
 __device__ __forceinline__ bool fs_wave_any(bool flag) { return __builtin_amdgcn_ballot_w64(flag) != 0; }
 
 // ---- pass AC --------------------------------------------------------------------------------------------------------------------------
-#ifndef AUXSSM_FS_WPE_A
-#define AUXSSM_FS_WPE_A 2
-#endif
+constexpr int FS_WPE_A = 2;  // waves per EU of pass A (3 or 4: 200 VGPRs spill, 0.55 -> 1.2 / 2.1 ms)
 // PK (few chains, one wave per workgroup): lane = sub * cp + chain walks chunk blockIdx.x * pack + sub -- the time index is per lane, everything else is the same code
 template <typename R, int D, int PO, bool PK = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(AUXSSM_FS_WPE_A))) k_fs_ac(FusedArgs a, const R* __restrict__ rows) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_WPE_A))) k_fs_ac(FusedArgs a, const R* __restrict__ rows) {
     using F = FsRows<R, D, PO>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     R* lds = (R*)smem;
@@ -706,24 +704,21 @@ template <typename R> __global__ void __launch_bounds__(TB_ELEM) k_fs_accept(Fus
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-// few chains (<= 128): how many chunks one workgroup of up to 256 lanes walks side by side (lanes = pack x cp), 1 = the plain mapping.  AUXSSM_FS_PACK=0 switches it off, n > 1 caps it (measurement).
+// few chains (<= 128): how many chunks one workgroup of up to 256 lanes walks side by side (lanes = pack x cp), 1 = the plain mapping.
 // Measured at C2's sizes (profiles/r04_i_low_chain_layout.txt): 8 chains 18.2k -> 23.4k sweeps/s, 16 chains 40.7k -> 51.0k, 32 chains 78.0k -> 91.0k, 64 chains 133.7k -> 152.0k,
 // 128 chains 189.4k -> 218.4k (the chunks of a workgroup share one staging of the normal tables and one barrier).
 inline int fs_pack(int C, int* cp_out) {
-    static const int on = [] { const char* e = getenv("AUXSSM_FS_PACK"); return e ? atoi(e) : 1; }();
     int cp = 2;
     while (cp < C) cp <<= 1;
     *cp_out = cp;
-    static const int lanes = [] { const char* e = getenv("AUXSSM_FS_PACK_LANES"); const int v = e ? atoi(e) : 256; return v == 64 || v == 128 ? v : 256; }();   // lanes per packed workgroup (measured: 256 best from 32 chains on)
-    if (!on || cp > lanes / 2) return 1;
-    int pack = lanes / cp;
-    const int cap = on > 1 ? on : 8;   // (LDS: pack blocks of E coefficient rows)
+    constexpr int lanes = 256;   // lanes per packed workgroup (measured: 256 best from 32 chains on)
+    if (cp > lanes / 2) return 1;
+    const int pack = lanes / cp;
+    constexpr int cap = 8;   // (LDS: pack blocks of E coefficient rows)
     return pack > cap ? cap : pack;
 }
 inline int fs_chunk_len(const auxssm_ctx* h, int C, int T) {
-    static const int waves = [] { const char* e = getenv("AUXSSM_FS_WAVES"); const int v = e ? atoi(e) : 10; return v >= 1 && v <= 64 ? v : 10; }();
-    static const int fixedE = [] { const char* e = getenv("AUXSSM_FS_E"); return e ? atoi(e) : 0; }();
-    if (fixedE >= 2 && fixedE <= 64) return fixedE;
+    constexpr int waves = 10;
     const long long stiles = (C + TB_CM - 1) / TB_CM;
     long long want = (long long)h->num_cu * 4 * waves / stiles;
     if (want < 1) want = 1;
@@ -826,8 +821,7 @@ template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHo
     f.fa.t0_keep_ps = 1;
     hipLaunchKernelGGL((k_filter_t0<R, D, P>), dim3((C + TB_ELEM - 1) / TB_ELEM), dim3(TB_ELEM), 0, h->stream, f.fa);
     using F = FsRows<R, D, PO>;
-    static const int tbf_env = getenv("AUXSSM_FS_TBF") ? atoi(getenv("AUXSSM_FS_TBF")) : 0;
-    const int TBF = (tbf_env == 64 || tbf_env == 128 || tbf_env == 256) && C >= tbf_env ? tbf_env : (C >= 256 ? 256 : (C + 63) / 64 * 64);
+    const int TBF = C >= 256 ? 256 : (C + 63) / 64 * 64;
     const unsigned grid = (unsigned)a.nchunk * (unsigned)((C + TBF - 1) / TBF);
     const unsigned grid_pk = (unsigned)((a.nchunk + a.pack - 1) / a.pack);
     const size_t lds = (size_t)TB_AGGS * SampElem<R, D>::NPAD * sizeof(R);

@@ -280,16 +280,6 @@ template <typename R, int D> __global__ void __launch_bounds__(TB_ELEM) k_sample
     const int t = blockIdx.x * TB_ELEM + threadIdx.x;
     if (t < a.d.T) body_sample_shared_tab<R, D>(a, t);
 }
-template <typename R, int D> __global__ void __launch_bounds__(TB_CM) k_sample_init_cm(SampleArgs a, int TI) {
-    const CmTile c = decode_cm(a.d.S(), a.d.T - 1, TI);
-    if (!c.live) return;
-    DirectIO io;
-    if (c.tt == 0) body_sample_last<R, D>(a, c.s);
-#pragma unroll 1
-    for (int jp = c.i0; jp < c.i1; ++jp) {
-        body_sample_init<R, D>(a, io, c.s, opaque_uniform(jp), true);
-    }
-}
 template <typename R, int D, int PO>
 __global__ void __launch_bounds__(TB_CM) k_sweep_logpdf_cm(SweepLogpdfArgs a, Acc* __restrict__ part, int ntile, int TI) {
     resolve_step(a);
@@ -992,10 +982,9 @@ constexpr int TB_KS = 256;
 // `weight`: the operator's combine relative to the fp32 d = 3 filter combine (measured: that one still gains at four tiles per CU -- C4 at 16 chains 42.6k -> 55.8k
 // sweeps/s -- the fp64 d = 4 one, 4.2 times the record and twice the width, at one tile per CU (C2 at one chain 2.05k -> 4.3k) but not at 16: 14.0k -> 12.1k)
 inline bool use_ks_scan(const auxssm_ctx* h, int S, int n, int parallel, double weight) {
-    static const int mode = [] { const char* e = getenv("AUXSSM_KS_SCAN"); return e ? atoi(e) : 1; }();  // 0 off, 1 auto, 2 always (tests)
-    if (!parallel || mode == 0 || n < 2 * TB_KS) return false;
+    if (!parallel || n < 2 * TB_KS) return false;
     const long long tiles = (long long)S * ((n + TB_KS - 1) / TB_KS);
-    return mode == 2 || (double)tiles * weight <= 10.0 * h->num_cu;
+    return (double)tiles * weight <= 10.0 * h->num_cu;
 }
 template <class Op> inline bool use_ks(const auxssm_ctx* h, int S, int n, int parallel) {
     const double r = (double)Op::Full::NPAD / 28.0;
@@ -1076,26 +1065,17 @@ inline ScanLayout make_layout(const ScanPlan& pl, int cm, int S) {
     const int W = pl.nchunk < 64 ? pl.nchunk : 64;
     return ScanLayout{pl.E, pl.nchunk, (pl.nchunk + W - 1) / W, W, cm, S};
 }
-// time steps per wave in the chain-minor elementwise kernels (AUXSSM_TI overrides, for tuning)
-inline int ti_cm() {
-    static int v = [] { const char* e = getenv("AUXSSM_TI"); const int t = e ? atoi(e) : 16; return t >= 1 && t <= 1024 ? t : 16; }();
-    return v;
-}
-#define TI_CM ti_cm()
+// time steps per wave in the chain-minor elementwise kernels
+constexpr int TI_CM = 16;
 // ... of the per-chain log-density passes: longer runs once the grid holds ~32 waves per SIMD anyway (their per-tile costs -- the t - 1 reads, one logarithm per
 // sum -- amortise; SV second order, 1024 chains x 65536 steps: 244k -> 267k sweeps/s at 64 steps, Lorenz 256 chains x 16384: best at 16); never below TI_CM,
 // which sizes the partial-sum buffers
 inline int ti_cm_for(const auxssm_ctx* h, int C, int n) {
-    static const bool forced = getenv("AUXSSM_TI") != nullptr;
-    if (forced) return TI_CM;
     const long long t = (long long)C * n / ((long long)64 * h->num_cu * 4 * 32);
     return (int)std::min<long long>(64, std::max<long long>(TI_CM, t));
 }
-// ... and of the chain-shared log-density pass (run_sweep_logpdf; AUXSSM_TI_SHARED overrides)
-inline int ti_shared() {
-    static int v = [] { const char* e = getenv("AUXSSM_TI_SHARED"); const int t = e ? atoi(e) : 64; return t >= 1 && t <= 1024 ? t : 64; }();
-    return v;
-}
+// ... and of the chain-shared log-density pass (run_sweep_logpdf)
+constexpr int TI_SHARED = 64;
 
 // `a` must already carry the layout the element buffer was written with (make_layout(plan_scan(...)))
 // DownOp: the operator of the final pass (same element/prefix types as Op; e.g. SampleOpFly, which rebuilds its elements)
@@ -1250,8 +1230,7 @@ template <typename R, int D, int P> int run_filter(auxssm_ctx* h, const FilterAr
     const int S = a.d.S(), n = a.d.n();
     const int cm = a_in.lay.cm;  // the caller chose the layout of ms / Ps; the element buffer follows it
     // block-diagonal R with a leading dx x dx block (the concatenated auxiliary observations): information form
-    static const bool blk_on = [] { const char* e = getenv("AUXSSM_INFO_BLOCKS"); return e ? atoi(e) != 0 : true; }();
-    const bool blk = blk_on && P > D && a_in.pblk == D;
+    const bool blk = P > D && a_in.pblk == D;
     a.lay = make_layout(plan_scan(h, S, n, parallel, cm ? scan_waves<R, D>() : 1), cm, S);
     // chain-shared model parameters (the factories of a linear-Gaussian model): what jax.vmap leaves unbatched in the reference
     const bool shared_on = h->share_model != 0;
@@ -1316,9 +1295,8 @@ template <typename R, int D, int P> int run_filter(auxssm_ctx* h, const FilterAr
         }
     }
     // lanes <-> sequences on any model (the caller's arrays through their strides): no element buffer -- composites from elements built in registers, then the
-    // sequential recursion from each chunk's prefix (kalman_bodies.h::FilterOpBuildCm / FilterOpSeqWalk).  AUXSSM_CM_ELEM=1: the materialised-element passes.
-    static const bool cm_elem = [] { const char* e = getenv("AUXSSM_CM_ELEM"); return e && atoi(e) != 0; }();
-    if (cm && n > 0 && !cm_elem && !a.ps_packed) {
+    // sequential recursion from each chunk's prefix (kalman_bodies.h::FilterOpBuildCm / FilterOpSeqWalk).
+    if (cm && n > 0 && !a.ps_packed) {
         a.elem = nullptr;
         a.ellz = ws_take(h, (size_t)S * a.lay.nchunk * sizeof(R));
         if (!a.ellz) return AUXSSM_ERR_NOMEM;
@@ -1384,7 +1362,6 @@ template <typename R, int D> int run_sample(auxssm_ctx* h, const SampleArgs& a_i
     const int S = a.d.S(), T = a.d.T;
     const int cm = a_in.lay.cm;
     a.lay = make_layout(plan_scan(h, S, T, parallel, cm ? scan_waves<R, D>() : 1), cm, S);
-    static const bool fly = [] { const char* e = getenv("AUXSSM_SAMPLE_FLY"); return e ? atoi(e) != 0 : true; }();
     const bool shared_on = h->share_model != 0;
     if (cm && shared_on && a.ps_shared && a.d.B == 1 && a.Fs.sc == 0 && a.Qs.sc == 0 && a.bs.sc == 0) {
         // chain-shared covariances: gains and Cholesky factors once per time step, a chain's element is two small mat-vecs
@@ -1402,11 +1379,7 @@ template <typename R, int D> int run_sample(auxssm_ctx* h, const SampleArgs& a_i
         AX_HIP(hipGetLastError());
         return AUXSSM_OK;
     }
-    if (a.ps_packed && !(cm && fly)) {
-        set_error("internal: packed covariance records are read by the on-the-fly chain-minor sampler only");
-        return AUXSSM_ERR_UNSUPPORTED;
-    }
-    if (cm && fly) {
+    if (cm) {
         // chain-minor: elements are recomputed on the fly by both scan passes (SampleOpFly), nothing to initialise
         a.elem = nullptr;
         ProfScope ps(h, AUXSSM_K_SAMPLE_SCAN);
@@ -1415,7 +1388,11 @@ template <typename R, int D> int run_sample(auxssm_ctx* h, const SampleArgs& a_i
         AX_HIP(hipGetLastError());
         return AUXSSM_OK;
     }
-    if (!cm && !a.ps_packed && use_ks<SampleOp<R, D>>(h, S, T, a.lay.nchunk > 1)) {
+    if (a.ps_packed) {
+        set_error("internal: packed covariance records are read by the on-the-fly chain-minor sampler only");
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    if (use_ks<SampleOp<R, D>>(h, S, T, a.lay.nchunk > 1)) {
         // few sequences: the tile scan builds its own elements (SampleOpFly::load_elem): no k_sample_init launch, no element buffer
         a.elem = nullptr;
         ProfScope ps(h, AUXSSM_K_SAMPLE_SCAN);
@@ -1428,8 +1405,7 @@ template <typename R, int D> int run_sample(auxssm_ctx* h, const SampleArgs& a_i
     {
         ProfScope ps(h, AUXSSM_K_SAMPLE_INIT);
         const int nt = ntiles(T - 1) > 0 ? ntiles(T - 1) : 1;
-        if (cm) hipLaunchKernelGGL((k_sample_init_cm<R, D>), dim3(grid_cm(S, T - 1, TI_CM)), dim3(TB_CM), 0, h->stream, a, TI_CM);
-        else hipLaunchKernelGGL((k_sample_init<R, D>), dim3(grid_tile_seq(nt, S)), dim3(TB_ELEM), 0, h->stream, a);
+        hipLaunchKernelGGL((k_sample_init<R, D>), dim3(grid_tile_seq(nt, S)), dim3(TB_ELEM), 0, h->stream, a);
     }
     {
         ProfScope ps(h, AUXSSM_K_SAMPLE_SCAN);
@@ -1457,7 +1433,7 @@ template <typename R, int D, int P> int run_logpdf(auxssm_ctx* h, const LogpdfAr
 }
 
 template <typename R, int D, int PO> size_t sweep_logpdf_ws(const auxssm_ctx*, const KDims& d) {
-    const int ti = std::min(TI_CM, ti_shared());
+    const int ti = std::min(TI_CM, TI_SHARED);
     return (size_t)5 * d.C * (std::max(ntiles(d.T), (d.T + ti - 1) / ti) + 1) * sizeof(Acc) + 256 +
            (size_t)d.T * LogShared<R, D, PO>::NPAD * sizeof(R) + 256;
 }
@@ -1470,10 +1446,9 @@ template <typename R, int D, int PO> int run_sweep_logpdf(auxssm_ctx* h, const S
                         a.cs.sc == 0 && a.ys.sc == 0;
     // time steps per lane: the streamed shared pass (52 scalars per step from its table) likes longer runs than the per-chain pass -- measured at C2,
     // two runs each: 0.41-0.44 / 0.39 / 0.38-0.41 / 0.38-0.40 ms at 16 / 32 / 48 / 64 steps; the per-chain pass 1.28 / 1.31 / 1.37 / 1.34 ms
-    // the SEMI-shared form: covariances, observation model and data common to the chains (chain stride 0), whatever the transition's F, b (AUXSSM_LOGPDF_SEMI=0: off)
-    static const bool semi_on = [] { const char* e = getenv("AUXSSM_LOGPDF_SEMI"); return e ? atoi(e) != 0 : true; }();
-    const bool semi = semi_on && cm && !shared && n > 0 && a.d.C > 1 && a.Qs.sc == 0 && a.Hs.sc == 0 && a.Rs.sc == 0 && a.cs.sc == 0 && a.ys.sc == 0;
-    const int TI = shared ? ti_shared() : ti_cm_for(h, a.d.C, n);
+    // the SEMI-shared form: covariances, observation model and data common to the chains (chain stride 0), whatever the transition's F, b
+    const bool semi = cm && !shared && n > 0 && a.d.C > 1 && a.Qs.sc == 0 && a.Hs.sc == 0 && a.Rs.sc == 0 && a.cs.sc == 0 && a.ys.sc == 0;
+    const int TI = shared ? TI_SHARED : ti_cm_for(h, a.d.C, n);
     const int C = a.d.C, nt = cm ? ((n + TI - 1) / TI > 0 ? (n + TI - 1) / TI : 1) : (ntiles(n) > 0 ? ntiles(n) : 1);
     Acc* part = (Acc*)ws_take(h, (size_t)5 * C * nt * sizeof(Acc));
     ProfScope ps(h, AUXSSM_K_LOGPDF);
@@ -1530,8 +1505,7 @@ template <typename R, int PO> int run_lorenz_logpdf(auxssm_ctx* h, const SweepLo
     const int nt = cm ? ((n + TI - 1) / TI > 0 ? (n + TI - 1) / TI : 1) : (ntiles(n) > 0 ? ntiles(n) : 1);
     Acc* part = (Acc*)ws_take(h, (size_t)5 * C * nt * sizeof(Acc));
     ProfScope ps(h, AUXSSM_K_LOGPDF);
-    static const bool semi_on = [] { const char* e = getenv("AUXSSM_LOGPDF_SEMI"); return e ? atoi(e) != 0 : true; }();
-    const bool semi = semi_on && cm && n > 0 && C > 1 && a.Qs.sc == 0 && a.Hs.sc == 0 && a.Rs.sc == 0 && a.cs.sc == 0 && a.ys.sc == 0;
+    const bool semi = cm && n > 0 && C > 1 && a.Qs.sc == 0 && a.Hs.sc == 0 && a.Rs.sc == 0 && a.cs.sc == 0 && a.ys.sc == 0;
     if (semi) {
         SweepLogpdfArgs as = a;
         as.tab_semi = 1;

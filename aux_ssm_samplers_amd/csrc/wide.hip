@@ -20,10 +20,7 @@
 namespace ax {
 namespace wide {
 
-#ifndef AUXSSM_WIDE_NT
-#define AUXSSM_WIDE_NT 1024
-#endif
-constexpr int NT = AUXSSM_WIDE_NT;         // lanes per workgroup: 4 waves per SIMD hide the LDS latency of the dependent sweeps
+constexpr int NT = 1024;         // lanes per workgroup: 4 waves per SIMD hide the LDS latency of the dependent sweeps
 constexpr int NWV = NT / 64;     // waves per workgroup
 constexpr size_t LDS_BUDGET = 160 * 1024 - 512;
 
@@ -2298,17 +2295,12 @@ static WPlan plan(const auxssm_ctx* h, int S, int n, int parallel) {
     if (!parallel || n <= 3) return p;
     // one sequence: a chunk per CU; many sequences: two rounds of workgroups; never chunks shorter than ~sqrt(n / 2) steps
     long long nchunk = std::max(1ll, std::min(((long long)2 * h->num_cu + S - 1) / S, std::max((long long)std::sqrt(2.0 * n), (long long)h->num_cu / S)));
-    if (const char* ev = getenv("AUXSSM_WIDE_NCHUNK")) {  // tuning/debug override
-        const long long v = atoll(ev);
-        if (v >= 1 && v <= n) nchunk = v;
-    }
     nchunk = std::min<long long>(nchunk, n);
     p.E = (int)((n + nchunk - 1) / nchunk);
     p.nchunk = (n + p.E - 1) / p.E;
     p.cnt[0] = p.nchunk;
-    int group = 4;
-    if (const char* ev = getenv("AUXSSM_WIDE_GROUP")) group = std::max(2, atoi(ev));
-    while (p.nlev < WMAXLEV && p.cnt[p.nlev] > 2 * group && !getenv("AUXSSM_WIDE_ONE_LEVEL")) {
+    constexpr int group = 4;
+    while (p.nlev < WMAXLEV && p.cnt[p.nlev] > 2 * group) {
         p.El[p.nlev] = group;
         p.cnt[p.nlev + 1] = (p.cnt[p.nlev] + group - 1) / group;
         ++p.nlev;
@@ -2332,7 +2324,7 @@ template <typename K> static int set_lds(K kern, size_t bytes) {
     } while (0)
 
 static bool fold_enabled() {
-    static const bool on = !getenv("AUXSSM_WIDE_NO_FOLD");
+    static const bool on = !getenv("AUXSSM_WIDE_NO_FOLD");  // test hook: tests/test_gpu_wide.py runs the element path as the fold path's reference
     return on;
 }
 template <typename R> static bool use_fold(int d, int p) { return fold_enabled() && fold_fits(sizeof(R), d) && lds_obs_info(sizeof(R), d, p) <= LDS_BUDGET; }
@@ -2354,10 +2346,6 @@ static SPlan shared_plan(const auxssm_ctx* h, int S, int n, int d, int p, size_t
         sp.CB /= 2;
     sp.ncb = (S + sp.CB - 1) / sp.CB;
     long long nchunk = std::max(1, std::min(n, std::max(h->num_cu / sp.ncb, 32)));
-    if (const char* ev = getenv("AUXSSM_WIDE_SHARED_NCHUNK")) {
-        const long long v = atoll(ev);
-        if (v >= 1 && v <= n) nchunk = v;
-    }
     sp.E = (int)((n + nchunk - 1) / nchunk);
     sp.nchunk = (n + sp.E - 1) / sp.E;
     return sp;
@@ -2433,8 +2421,7 @@ template <typename R> int run_filter(auxssm_ctx* h, const FilterArgs& a, int par
 // returns 1 when the shared form does not apply (the caller runs the per-sequence path), else a status
 template <typename R> static int run_filter_shared(auxssm_ctx* h, const FilterArgs& a, void* ell_out) {
     const int S = a.d.S(), n = a.d.n(), d = a.dx, p = a.dy;
-    static const bool off = getenv("AUXSSM_WIDE_SHARED") && atoi(getenv("AUXSSM_WIDE_SHARED")) == 0;
-    if (off || !h->share_model || a.aux_on || a.tab || p < 1) return 1;
+    if (!h->share_model || a.aux_on || a.tab || p < 1) return 1;
     if (a.pc && a.tab_ready && !a.mask_ys.ptr) return 1;  // (a reused table was built on the carrier's pattern)
     for (const Arr* q : {&a.P0, &a.Fs, &a.Qs, &a.bs, &a.Hs, &a.Rs, &a.cs})
         if (q->sc != 0 || q->sb != 0) return 1;
@@ -2455,7 +2442,7 @@ template <typename R> static int run_filter_shared(auxssm_ctx* h, const FilterAr
     R* aggG = (R*)ws_take(h, (size_t)sp.nchunk * d * Spad * sizeof(R));
     R* pre = (R*)ws_take(h, (size_t)sp.nchunk * d * Spad * sizeof(R));
     // second level of the chunk-composite scan: groups of GRP composites (none below 2 GRP chunks)
-    static const int GRP = getenv("AUXSSM_WIDE_SHARED_GROUP") ? std::max(2, atoi(getenv("AUXSSM_WIDE_SHARED_GROUP"))) : 16;
+    constexpr int GRP = 16;
     const int nsup = sp.nchunk >= 2 * GRP ? (sp.nchunk + GRP - 1) / GRP : 1;
     const size_t l_grp = lds_mean_group(sizeof(R), d, sp.CB);
     R *supA = nullptr, *supG = nullptr, *presup = nullptr;
@@ -2511,7 +2498,7 @@ template <typename R> static int run_filter_shared(auxssm_ctx* h, const FilterAr
     const bool prof_all = h->prof.kernel_id == AUXSSM_K_ALL && h->prof.max_launches > 0;
     const bool ps_once = a.Ps.sc == 0 && a.Ps.sb == 0;  // the caller keeps ONE copy of the covariances (the matrix filter wrote it): nothing to broadcast
     if (ps_once) {
-    } else if (!prof_all && !getenv("AUXSSM_WIDE_NO_FORK")) {
+    } else if (!prof_all) {
         if (!h->fork_stream) {
             AX_HIP(hipStreamCreateWithFlags(&h->fork_stream, hipStreamNonBlocking));
             AX_HIP(hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
@@ -2563,10 +2550,6 @@ static WPlan samp_plan(int T, int parallel) {
     p.cnt[0] = 1;
     if (!parallel || T <= 3) return p;
     long long nchunk = std::max(1ll, (long long)std::sqrt(2.0 * T));
-    if (const char* ev = getenv("AUXSSM_WIDE_SAMP_NCHUNK")) {
-        const long long v = atoll(ev);
-        if (v >= 1 && v <= T) nchunk = v;
-    }
     p.E = (int)((T + nchunk - 1) / nchunk);
     p.nchunk = (T + p.E - 1) / p.E;
     p.cnt[0] = p.nchunk;
@@ -2582,8 +2565,7 @@ static int samp_cb(const auxssm_ctx* h, int S, int nchunk) {
 // the gain / factor tables once, the sequences as columns (wide_shared.h).  Returns 1 when not applicable.
 template <typename R> static int run_sample_shared(auxssm_ctx* h, const SampleArgs& a, int parallel) {
     const int S = a.d.S(), T = a.d.T, d = a.dx;
-    static const bool off = getenv("AUXSSM_WIDE_SHARED") && atoi(getenv("AUXSSM_WIDE_SHARED")) == 0;
-    if (off || !h->share_model || S < 2 || T < 2) return 1;
+    if (!h->share_model || S < 2 || T < 2) return 1;
     for (const Arr* q : {&a.Ps, &a.Fs, &a.Qs, &a.bs})
         if (q->sc != 0 || q->sb != 0) return 1;
     const WPlan pl = samp_plan(T, parallel);
@@ -2657,8 +2639,7 @@ template <typename R> int run_logpdf(auxssm_ctx* h, const LogpdfArgs& a, void* o
 // The observations may be per chain under the reference NaN policy (SweepLogpdfArgs::ys_x).  Returns 1 when the form does not apply (nothing enqueued).
 template <typename R> int run_sweep_logpdf_shared(auxssm_ctx* h, const SweepLogpdfArgs& a, void* out) {
     const int C = a.d.C, T = a.d.T;
-    static const bool sh_off = getenv("AUXSSM_WIDE_SHARED") && atoi(getenv("AUXSSM_WIDE_SHARED")) == 0;
-    if (sh_off || !h->share_model || C < 2 || a.u_fly || NT != 1024 || !spd_fits(std::max(a.dx, a.po), 2 * std::max(a.dx, a.po))) return 1;
+    if (!h->share_model || C < 2 || a.u_fly || !spd_fits(std::max(a.dx, a.po), 2 * std::max(a.dx, a.po))) return 1;
     for (const Arr* q : {&a.m0, &a.P0, &a.Fs, &a.Qs, &a.bs, &a.Hs, &a.Rs, &a.cs})
         if (q->sc != 0 || q->sb != 0) return 1;
     if ((a.ys.sc != 0 || a.ys_x.ptr) && a.nan_policy != 0) return 1;

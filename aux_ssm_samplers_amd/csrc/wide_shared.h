@@ -162,9 +162,6 @@ template <typename R> __global__ void __launch_bounds__(NT) wk_gain_tab(FilterAr
             o.H_[r * ldd + q] = o.nan[r] ? (R)0 : rH.v[u];
         }
     }
-#if defined(AUXSSM_GT_PHASE)
-    if (AUXSSM_GT_PHASE == 1) return;
-#endif
     // P^- = F P F^T + Q (not symmetrised, filtering.py:200-201 / predict)
     gemm<false, false>(d, d, d, F, ldd, P, ldd, T1, ldd, (R)1, (R)0, tid);
     gemm<false, true>(d, d, d, T1, ldd, F, ldd, P, ldd, (R)1, (R)0, tid);
@@ -177,9 +174,6 @@ template <typename R> __global__ void __launch_bounds__(NT) wk_gain_tab(FilterAr
         }
     }
     __syncthreads();
-#if defined(AUXSSM_GT_PHASE)
-    if (AUXSSM_GT_PHASE == 2) return;
-#endif
     // S = H_ P^- H_^T + R_ ; right-hand sides H_ P^- and the identity.  A step with nothing observed needs no special case: H_ = 0, every row deleted -> X = 0, S^-1
     // rows 0, half log-determinant 0, i.e. A = F, g = b, ell_t = 0 (_passthrough, filtering.py:239-248)
     gemm<false, false>(p, d, d, o.H_, ldd, P, ldd, HP, ldd, (R)1, (R)0, tid);
@@ -204,15 +198,9 @@ template <typename R> __global__ void __launch_bounds__(NT) wk_gain_tab(FilterAr
         }
     }
     __syncthreads();
-#if defined(AUXSSM_GT_PHASE)
-    if (AUXSSM_GT_PHASE == 3) return;
-#endif
     R hl;
     const bool ok = spd_split_fits(p, nct, ldz) ? spd_solve_split<R>(Z, ldz, p, nct, o.nan, rowbuf, piv, &hl, tid)
                                                 : spd_solve<R>(Z, ldz, p, nct, o.nan, rowbuf, piv, &hl, tid, true);
-#if defined(AUXSSM_GT_PHASE)
-    if (AUXSSM_GT_PHASE == 4) return;
-#endif
     // H F;  A = F - X^T (H F);  hb = H_ b + c_;  g = b - X^T hb
     gemm<false, false>(p, d, d, o.H_, ldd, F, ldd, HF, ldd, (R)1, (R)0, tid);
     gemm<true, false>(d, d, p, Z + p, ldz, HF, ldd, T1, ldd, (R)-1, (R)1, tid, F, ldd);
@@ -220,9 +208,6 @@ template <typename R> __global__ void __launch_bounds__(NT) wk_gain_tab(FilterAr
     for (int k = tid; k < p; k += NT) hb[k] = o.nan[k] ? (R)0 : hb[k] + o.c_[k];
     __syncthreads();
     gemv<R, true>(d, p, Z + p, ldz, hb, g0, (R)1, (R)0, tid);
-#if defined(AUXSSM_GT_PHASE)
-    if (AUXSSM_GT_PHASE == 5) return;
-#endif
     const R bad = r_nan<R>();
     for (int e = tid; e < p * ldd; e += NT) {
         const int r = e / ldd, q = e - r * ldd;

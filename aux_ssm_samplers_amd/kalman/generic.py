@@ -12,7 +12,6 @@ Two execution paths, same semantics:
 """
 import ctypes as C
 import math
-import os
 from dataclasses import dataclass
 from typing import Any
 
@@ -118,12 +117,11 @@ class DeviceChains:
             x = x[None]
         self.handle = handle
         self.C, self.T, self.dx = x.shape
-        env = os.environ.get("AUXSSM_CM")
         auto = self.C >= 32
         if (model is not None and getattr(model, "kmodel", None) == _lib.KMODEL_LG_CONCAT and self.C >= 4 and self.C % 2 == 0 and self.T >= 64
                 and self.dx <= 4 and 1 <= getattr(model, "p_obs", 0) <= 4):
             auto = True   # (the conditions of csrc/api.hip::fused_refusal; anything else keeps the time-minor general path below 32 chains)
-        self.chain_minor = bool(int(env)) if env is not None and chain_minor is None else (auto if chain_minor is None else bool(chain_minor))
+        self.chain_minor = auto if chain_minor is None else bool(chain_minor)
         if self.dx > 4 and chain_minor is None:
             self.chain_minor = False  # dx > 4 runs the wide-state kernels (csrc/wide.hip): a workgroup per time step, dense layout
         self.layout = _lib.LAYOUT_CHAIN_MINOR if self.chain_minor else _lib.LAYOUT_DENSE
@@ -137,8 +135,6 @@ class DeviceChains:
         # lazy state of the fused chain-shared sweep (auxssm_kalman_sweep_fused): chain c lives in x_alt where sel[c] != 0; allocated on first use
         self.x_alt = None
         self.sel = None
-        if fused is None and os.environ.get("AUXSSM_FUSED") == "0":   # measurement switch: the keyed sweep of rounds 1-2
-            fused = False
         self.fused = None if fused is None or fused else False  # None: not tried yet; False: refused (by the library or the caller): keyed sweeps
 
     # per-sweep noise buffers of the unfused sweeps (allocated once, on first use: the fused sweep draws inside its passes and needs none)

@@ -73,7 +73,7 @@ int auxssm_create(int device, auxssm_handle* out);
 int auxssm_destroy(auxssm_handle h);
 int auxssm_sync(auxssm_handle h);
 /* Options of a handle.
- * AUXSSM_OPT_SHARE_MODEL (default 1; environment AUXSSM_SHARED=0 changes the default): in the chain-minor sweep, when the
+ * AUXSSM_OPT_SHARE_MODEL (default 1): in the chain-minor sweep, when the
  *   model's parameter arrays do not depend on the chain (chain stride 0: the factories of a linear-Gaussian model ignore the
  *   linearisation point), everything that depends on the parameters only -- element matrices, gains, Cholesky factors of Q_t /
  *   R_t, the filtered covariances -- is computed once per time step and sweep instead of once per chain (what jax.vmap leaves

@@ -153,8 +153,7 @@ def test_model_stage_memo_is_exact(monkeypatch):
     """The fused sweep's model stage is MEMOISED per slab (ctx.h::SideStage, round 4): rebuilt only when its inputs differ byte for byte from the snapshot the slab's
     tables were built from -- decided on the device, no host synchronisation.  A run of sweeps with a fixed step size (every stage after the first three is skipped),
     then a new step size, then the DATA and a MODEL MATRIX rewritten in place on the device (same pointers: only the comparison kernel can notice), then the old data
-    back: bit for bit the results of the same run with the memo switched off (AUXSSM_STAGE_MEMO=0, a separate library instance would read the variable once, so the
-    switch here is the single-stream sweep, which has no stage to memoise)."""
+    back: bit for bit the results of the same run without the memo (the single-stream sweep, which has no stage to memoise)."""
     from aux_ssm_samplers_amd import random as R
     from aux_ssm_samplers_amd.kalman import LGConcatModel
     h = _lib.default_handle()

@@ -1,5 +1,5 @@
 import sys, os, numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from aux_ssm_samplers_amd import _lib, random as R
 from aux_ssm_samplers_amd.kalman import get_kernel
 from aux_ssm_samplers_amd.kalman.generic import DeviceChains, KalmanSampler
