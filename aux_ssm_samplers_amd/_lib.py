@@ -50,6 +50,11 @@ class CsmcNoise(C.Structure):
                 ("eps_aux", C.c_void_p), ("eps_prop", C.c_void_p), ("u_res", C.c_void_p), ("u_bwd", C.c_void_p)]
 
 
+class FkUser(C.Structure):
+    _fields_ = [("y", C.c_void_p), ("theta_g", C.c_void_p), ("theta_m", C.c_void_p), ("p", C.c_int32), ("reserved", C.c_int32)]
+
+
+FK_USER_POTENTIAL, FK_USER_MEAN = 1, 2
 PROP_BOOTSTRAP_LG, PROP_AUX_INDEPENDENT = 0, 1
 POT_FLAT, POT_GAUSS_OBS, POT_SV, POT_GAUSS_OBS_MASKED = 0, 1, 2, 3
 TRANS_LINEAR, TRANS_LORENZ63_EM = 0, 1
@@ -105,6 +110,11 @@ def load():
         "auxssm_kalman_sweep_fused": ([vp, i32, i32, P(Dims), P(Lgssm), P(Arr), dbl, vp, P(C.c_uint32), i32, i32, i32, vp, vp, vp, vp, vp, vp], C.c_int),
         "auxssm_kalman_state_resolve": ([vp, i32, P(Dims), vp, vp, vp], C.c_int),
         "auxssm_csmc_sweep": ([vp, i32, P(FkModel), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, P(CsmcNoise), vp, vp, vp, vp], C.c_int),
+        "auxssm_fk_program_compile": ([C.c_char_p, C.c_char_p, i32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t, P(vp)], C.c_int),
+        "auxssm_fk_program_free": ([vp], C.c_int),
+        "auxssm_fk_program_info": ([vp, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32)], C.c_int),
+        "auxssm_csmc_sweep_program": ([vp, vp, i32, P(FkModel), P(FkUser), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, P(CsmcNoise), vp, vp, vp, vp],
+                                      C.c_int),
         "auxssm_csmc_pit_sweep": ([vp, i32, P(FkModel), C.c_int32, C.c_int32, C.c_int32, vp, vp, P(CsmcNoise), vp], C.c_int),
         "auxssm_normalize_resample": ([vp, i32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp], C.c_int),
         "auxssm_systematic_resample": ([vp, i32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp], C.c_int),

@@ -28,7 +28,7 @@ def get_kernel(Mt, G0, Gt, N, Qt=None):
     if (grad is not None) != (Qt is not None):
         raise NotImplementedError("gradient proposals need both Mt.params[2] and Qt (independent.py:81-84); " + _MSG)
     gmode = _lib.GRAD_EXACT if grad is not None else _lib.GRAD_NONE
-    fk = _device.describe_independent(G0.M0, G0.G0, Gt.Mt, Gt.Gt, None, gmode)
+    fk = _device.describe_independent(G0.M0, G0.G0, Gt.Mt, Gt.Gt, None, gmode, parallel=True)
     u = np.asarray(u)
 
     def kernel(key, state):

@@ -1,11 +1,13 @@
 """Host driver of auxssm_csmc_sweep: model description, noise, buffers."""
 import ctypes as C
+import hashlib
+import os
 
 import numpy as np
 
 from .. import _lib, random as _random
 from .models import (GaussianInit, LinearGaussianDynamics, FlatPotential, GaussianObsPotential, SVPotential, Lorenz63Dynamics,
-                     MaskedGaussianObsPotential)
+                     MaskedGaussianObsPotential, DevicePotential, DeviceGaussianDynamics)
 
 _UNSUPPORTED = ("{what} is a Python object the HIP kernels cannot evaluate. The cSMC kernels run the closed model family "
                 "of aux_ssm_samplers_amd.csmc.models (GaussianInit, LinearGaussianDynamics, Lorenz63Dynamics, FlatPotential, "
@@ -33,6 +35,7 @@ class FkDesc:
         self.y = None if y is None else np.asarray(y)
         self._ydev = {}
         self._tvdev = {}
+        self.user = None  # UserModel: the parts of the model compiled from device code (auxssm_csmc_sweep_program)
 
     def tvdev(self, handle, dtype, T):
         """device copies of the time-varying transition arrays (or None)"""
@@ -41,9 +44,10 @@ class FkDesc:
         if self.tv[0].shape[0] != T - 1:
             raise ValueError(f"time-varying dynamics have {self.tv[0].shape[0]} rows, the state has T - 1 = {T - 1} transitions")
         key = (id(handle), np.dtype(dtype).str)
-        if key not in self._tvdev:
-            self._tvdev[key] = tuple(handle.to_device(a, dtype) for a in self.tv)
-        return self._tvdev[key]
+        ent = self._tvdev.get(key)
+        if ent is None or ent[0] is not handle:  # (the entry keeps its handle alive, so its id cannot pass to another handle: UserModel.struct)
+            ent = self._tvdev[key] = (handle, tuple(handle.to_device(a, dtype) for a in self.tv))
+        return ent[1]
 
     def struct(self, handle, dtype, T):
         """the auxssm_fk_model of this description on `handle` (keeps the device arrays alive through self)"""
@@ -63,9 +67,10 @@ class FkDesc:
         if self.y is None:
             return None
         key = (id(handle), np.dtype(dtype).str)
-        if key not in self._ydev:
-            self._ydev[key] = handle.to_device(self.y, dtype)
-        return self._ydev[key]
+        ent = self._ydev.get(key)
+        if ent is None or ent[0] is not handle:
+            ent = self._ydev[key] = (handle, handle.to_device(self.y, dtype))
+        return ent[1]
 
 
 def _potential(G0, Gt, d):
@@ -113,8 +118,145 @@ def _trans(Mt):
     return _lib.TRANS_LINEAR, Mt.F, Mt.b
 
 
+# ---- user-defined models (models.DevicePotential / DeviceGaussianDynamics) ------------------------------------------------------------------------------
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
+_programs = {}         # (sha256 of the source, dtype, dx, flags) -> auxssm_fk_program, for the life of the process
+_compiles = [0]
+
+
+def program_compiles():
+    """how many programs this process has compiled (a cached program is not compiled again)"""
+    return _compiles[0]
+
+
+def compile_program(source, dtype, dx, flags):
+    """auxssm_fk_program_compile, cached in-process by source hash; a source hipRTC rejects raises AuxSSMError with hipRTC's log"""
+    key = (hashlib.sha256(source.encode()).hexdigest(), np.dtype(dtype).str, int(dx), int(flags))
+    prog = _programs.get(key)
+    if prog is not None:
+        return prog
+    lib = _lib.load()
+    log = C.create_string_buffer(1 << 16)
+    out = C.c_void_p()
+    rc = lib.auxssm_fk_program_compile(source.encode(), _CSRC.encode(), _lib.dtype_code(dtype), int(dx), int(flags), log, len(log), C.byref(out))
+    if rc != 0:
+        msg = lib.auxssm_last_error().decode(errors="replace")
+        if rc == -1 and log.value:
+            raise _lib.AuxSSMError(f"auxssm: {msg}\n{log.value.decode(errors='replace')}")
+        if rc == -2:  # AUXSSM_ERR_UNSUPPORTED
+            raise NotImplementedError(f"auxssm: {msg}")
+        _lib.check(rc)
+    _compiles[0] += 1
+    _programs[key] = out
+    return out
+
+
+def program_info(prog):
+    """dict(dtype code, dx, flags, has_bound) of a compiled program (auxssm_fk_program_info)"""
+    v = [C.c_int32() for _ in range(4)]
+    _lib.check(_lib.load().auxssm_fk_program_info(prog, *(C.byref(x) for x in v)))
+    return dict(zip(("dtype", "dx", "flags", "has_bound"), (x.value for x in v)))
+
+
+class UserModel:
+    """the device-code parts of a model: the program source and flags, the user potential's observations (T, p) and the two parameter vectors"""
+
+    def __init__(self, source, flags, dx, y=None, theta_g=None, theta_m=None):
+        self.source, self.flags, self.dx = source, int(flags), int(dx)
+        self.y = None if y is None else np.ascontiguousarray(y, np.float64)
+        self.p = 0 if self.y is None else self.y.shape[1]
+        self.theta_g = None if theta_g is None else np.ascontiguousarray(np.reshape(theta_g, -1), np.float64)
+        self.theta_m = None if theta_m is None else np.ascontiguousarray(np.reshape(theta_m, -1), np.float64)
+        self._dev = {}
+        for dt in (np.float32, np.float64):  # compiled now (get_kernel time), not at the first sweep
+            self.program(dt)
+
+    def program(self, dtype):
+        return compile_program(self.source, dtype, self.dx, self.flags)
+
+    def struct(self, handle, dtype, T):
+        # the entry keeps its handle: an id is only unique among live objects, so a cache keyed by id(handle) alone could hand a later handle
+        # another one's device pointers
+        key = (id(handle), np.dtype(dtype).str)
+        ent = self._dev.get(key)
+        if ent is None or ent[0] is not handle:
+            ent = self._dev[key] = (handle, tuple(None if a is None else handle.to_device(a, dtype) for a in (self.y, self.theta_g, self.theta_m)))
+        yd, tg, tm = ent[1]
+        if yd is not None and yd.shape[0] != T:
+            raise ValueError(f"observations have {yd.shape[0]} time steps, state has {T}")
+        u = _lib.FkUser()
+        u.y, u.theta_g, u.theta_m = (None if a is None else a.ptr.value for a in (yd, tg, tm))
+        u.p = self.p
+        return u
+
+
+def _is_user(*objs):
+    return any(isinstance(o, (DevicePotential, DeviceGaussianDynamics)) for o in objs)
+
+
+def _describe_user(proposal, M0, G0, Mt, Gt, gradient, parallel):
+    """the FkDesc of a model with device-code parts (the rest from the built-in family); every limit of the program path raises NotImplementedError"""
+    if parallel:
+        raise NotImplementedError("user-defined models (DevicePotential / DeviceGaussianDynamics) run the sequential cSMC sweep only: parallel=True "
+                                  "(the parallel-in-time kernels) is not compiled for them")
+    if gradient:
+        raise NotImplementedError("gradient-informed proposals need the gradient of the model's log-density; for user-defined device code "
+                                  "(DevicePotential / DeviceGaussianDynamics) there are no derivatives: use gradient=False")
+    if not isinstance(M0, GaussianInit):
+        raise NotImplementedError(f"a user-defined M0 ({type(M0).__name__}) is not supported: user-defined models keep the Gaussian initial "
+                                  "distribution GaussianInit(m0, P0)")
+    d = int(np.size(M0.m0))
+    if d > 4:
+        raise NotImplementedError(f"dx={d}: user-defined models run the sequential kernels of dx <= 4; the wide-state path (dx > 4) is not "
+                                  "compiled for them")
+    flags, src, theta_g, theta_m, yu = 0, [], None, None, None
+    if isinstance(G0, DevicePotential) or isinstance(Gt, DevicePotential):
+        if not (isinstance(G0, DevicePotential) and isinstance(Gt, DevicePotential)):
+            raise NotImplementedError("G0 and Gt must both be DevicePotential (with the same source and theta)")
+        if G0.source != Gt.source:
+            raise ValueError("G0 and Gt must carry the same source")
+        tg0, tgt = (None if th is None else np.asarray(th, np.float64).reshape(-1) for th in (G0.theta, Gt.theta))
+        if (tg0 is None) != (tgt is None) or (tg0 is not None and not np.array_equal(tg0, tgt)):
+            raise ValueError("G0 and Gt must carry the same theta")
+        if (G0.y is None) != (Gt.params is None):
+            raise ValueError("the potential's observations: give both G0.y = ys[0] and Gt.params = ys[1:], or neither")
+        if G0.y is not None:
+            p = G0.p or Gt.p or int(np.size(G0.y))
+            yu = np.concatenate([np.reshape(G0.y, (1, p)), np.reshape(Gt.params, (-1, p))], axis=0)
+        flags |= _lib.FK_USER_POTENTIAL
+        src.append(Gt.source)
+        theta_g = tgt
+        pot, y, sig = _lib.POT_FLAT, None, 1.0
+    else:
+        pot, y, sig = _potential(G0, Gt, d)
+    if isinstance(Mt, DeviceGaussianDynamics):
+        Q = np.asarray(Mt.Q, np.float64)
+        if Q.ndim == 3:
+            raise NotImplementedError("DeviceGaussianDynamics: a time-varying Q together with a user mean is not supported (Q must be (d, d))")
+        flags |= _lib.FK_USER_MEAN
+        if Mt.source not in src:
+            src.append(Mt.source)
+        theta_m = Mt.theta
+        tk, F, b, LQ = _lib.TRANS_LINEAR, np.zeros((d, d)), np.zeros(d), Mt.chol()
+    elif isinstance(Mt, (LinearGaussianDynamics, Lorenz63Dynamics)):
+        if isinstance(Mt, LinearGaussianDynamics) and Mt.time_varying:
+            raise NotImplementedError("user-defined potentials run time-invariant transitions: time-varying LinearGaussianDynamics is not supported with them")
+        tk, F, b = _trans(Mt)
+        LQ = Mt.chol()
+    else:
+        raise NotImplementedError(f"Mt={type(Mt).__name__}: user-defined transitions are Gaussian, x_t ~ N(mean(x_{{t-1}}), Q) (DeviceGaussianDynamics); "
+                                  "non-Gaussian transition noise is not supported")
+    fk = FkDesc(proposal, pot, M0.m0, M0.chol(), F, b, LQ, y, sig, tk)
+    fk.user = UserModel("\n".join(src), flags, d, yu, theta_g, theta_m)
+    return fk
+
+
 def describe_bootstrap(M0, G0, Mt, Gt, Pt):
     """_primitives.csmc.get_kernel: M0/Mt are the proposals, G0/Gt the potentials."""
+    if _is_user(M0, G0, Mt, Gt):
+        if Pt is not None and Pt is not Mt:
+            raise NotImplementedError("backward sampling with Pt != Mt is not supported by the bootstrap device kernel")
+        return _describe_user(_lib.PROP_BOOTSTRAP_LG, M0, G0, Mt, Gt, _lib.GRAD_NONE, False)
     M0, Mt = _dyn(M0, Mt)
     if Pt is not None and Pt is not Mt and not (isinstance(Pt, LinearGaussianDynamics) and isinstance(Mt, LinearGaussianDynamics)
                                                    and np.array_equal(Pt.F, Mt.F) and np.array_equal(Pt.Q, Mt.Q) and np.array_equal(Pt.b, Mt.b)):
@@ -125,8 +267,12 @@ def describe_bootstrap(M0, G0, Mt, Gt, Pt):
     return FkDesc(_lib.PROP_BOOTSTRAP_LG, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk)
 
 
-def describe_independent(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE):
+def describe_independent(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE, parallel=False):
     """csmc.get_independent_kernel (classical): proposals N(u_t [+ delta_t/2 grad_t], delta_t/2 I); M0/Mt enter the weights."""
+    if _is_user(M0, G0, Mt, Gt):
+        if Pt is not None and Pt is not Mt:
+            raise NotImplementedError("Pt must be the model dynamics Mt")
+        return _describe_user(_lib.PROP_AUX_INDEPENDENT, M0, G0, Mt, Gt, gradient, parallel)
     M0, Mt = _dyn(M0, Mt)
     if Pt is not None and Pt is not Mt:
         raise NotImplementedError("Pt must be the model dynamics Mt")
@@ -202,9 +348,18 @@ def sweep_resident(fk, chains, N, backward, key):
     k = _random.as_key(key)
     nz = _lib.CsmcNoise()
     nz.mode, nz.key0, nz.key1 = _lib.NOISE_THREEFRY, int(k[0]), int(k[1])
-    _lib.check(handle.lib.auxssm_csmc_sweep(
-        handle.h, _lib.dtype_code(chains.dtype), C.byref(m), chains.C, chains.T, N, int(bool(backward)), shd.ptr if shd is not None else None,
-        chains.x.ptr, C.byref(nz), chains.ancestors.ptr, None, None, None))
+    _csmc_call(handle, fk, chains.dtype, m, chains.C, chains.T, N, backward, shd, chains.x, nz, chains.ancestors, None, None, None)
+
+
+def _csmc_call(handle, fk, dtype, m, Cn, T, N, backward, shd, xd, nz, anc, xs, lws, As):
+    """auxssm_csmc_sweep, or auxssm_csmc_sweep_program for a model with device-code parts"""
+    args = (Cn, T, N, int(bool(backward)), shd.ptr if shd is not None else None, xd.ptr, C.byref(nz), anc.ptr,
+            xs.ptr if xs else None, lws.ptr if lws else None, As.ptr if As else None)
+    if fk.user is None:
+        _lib.check(handle.lib.auxssm_csmc_sweep(handle.h, _lib.dtype_code(dtype), C.byref(m), *args))
+    else:
+        u = fk.user.struct(handle, dtype, T)
+        _lib.check(handle.lib.auxssm_csmc_sweep_program(handle.h, fk.user.program(dtype), _lib.dtype_code(dtype), C.byref(m), C.byref(u), *args))
 
 
 def _fk_struct(fk, handle, dtype, T):
@@ -217,6 +372,7 @@ def pit_sweep_resident(fk, chains, N, key):
         raise NotImplementedError('random.set_compat("jax") runs the particle kernels on explicit arrays of the reference\'s draws (T x N x d per chain): pass host '
                                   "states (csmc/_device.py::sweep); resident chains draw inside the kernels from this package's own streams")
     handle = chains.handle
+    _no_user_pit(fk)
     if chains.dx != fk.dx:
         raise ValueError(f"state dimension {chains.dx} != model dimension {fk.dx}")
     if chains.sqrt_half_delta is None:
@@ -229,9 +385,16 @@ def pit_sweep_resident(fk, chains, N, key):
                                                 chains.sqrt_half_delta.ptr, chains.x.ptr, C.byref(nz), chains.ancestors.ptr))
 
 
+def _no_user_pit(fk):
+    if fk.user is not None:
+        raise NotImplementedError("user-defined models (DevicePotential / DeviceGaussianDynamics) run the sequential cSMC sweep only: the "
+                                  "parallel-in-time kernels are not compiled for them")
+
+
 def pit_sweep(fk, x, N, *, key=None, noise=None, delta=None, handle=None):
     """Parallel-in-time cSMC sweep.  x: (T, d) one chain or (C, T, d).  noise: dict(eps_aux (C,T,d), eps_prop (C,T,N,d), u_res (C,T,N)) of
     explicit arrays or None -> Threefry(key).  Returns (x_new, ancestors)."""
+    _no_user_pit(fk)
     handle = handle or _lib.default_handle()
     x = np.asarray(x)
     single = x.ndim == 2
@@ -321,9 +484,7 @@ def sweep(fk, x, N, backward, *, key=None, noise=None, delta=None, handle=None, 
         xs = handle.empty((Cn, T, N, d), dtype)
         lws = handle.empty((Cn, T, N), dtype)
         As = handle.zeros((Cn, max(T - 1, 1), N), np.int32)
-    _lib.check(handle.lib.auxssm_csmc_sweep(
-        handle.h, _lib.dtype_code(dtype), C.byref(m), Cn, T, N, int(bool(backward)), shd.ptr if shd is not None else None,
-        xd.ptr, C.byref(nz), anc.ptr, xs.ptr if xs else None, lws.ptr if lws else None, As.ptr if As else None))
+    _csmc_call(handle, fk, dtype, m, Cn, T, N, backward, shd, xd, nz, anc, xs, lws, As)
     xo, ao = xd.to_host(), anc.to_host()
     if want_history:
         hist = dict(xs=xs.to_host(), log_ws=lws.to_host(), As=As.to_host()[:, :T - 1])

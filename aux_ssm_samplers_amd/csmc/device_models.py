@@ -1,0 +1,104 @@
+"""Example models written as device code for DevicePotential / DeviceGaussianDynamics (csmc.models; contract in csrc/fk_user_pre.h).
+
+BUILTIN_*: the built-in potentials / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc.hip::k_csmc_potbound written as user source, in the
+built-in operation order (fma_, det_exp, det_log), so that a program sweep reproduces the closed-family sweep bit for bit (the tests and
+tools/fk_program_bench.py use them).  The constants the host computes for the built-ins (csmc_dev.h::fill_model) are formed the same way on
+the device from theta = [sig].  RARE_EVENT, STUDENT_T, GROWTH: models the closed family cannot express."""
+
+HALF_LOG_2PI = "(R)0.91893853320467274178"
+
+# y ~ N(x, sig^2 I): theta = [sig]
+BUILTIN_GAUSS_OBS = r"""
+template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta) {
+    const R inv = (R)1 / theta[0];
+    const R c_obs = -(R)D * det_log(theta[0]) - (R)D * (R)0.91893853320467274178;
+    R q = 0;
+    for (int k = 0; k < D; ++k) {
+        const R z = (y[k] - x[k]) * inv;
+        q = fma_(z, z, q);
+    }
+    return fma_((R)-0.5, q, c_obs);
+}
+template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta) {
+    return -(R)D * det_log(theta[0]) - (R)D * (R)0.91893853320467274178;
+}
+"""
+
+# stochastic volatility y_k ~ N(0, exp(x_k)), NaN terms -> 0; the bound of k_csmc_potbound
+BUILTIN_SV = r"""
+template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta) {
+    const R c_obs = -(R)0.91893853320467274178;
+    R acc = 0;
+    for (int k = 0; k < D; ++k) {
+        const R e = det_exp(-x[k]);
+        const R s = fma_(y[k] * y[k], e, x[k]);
+        const R v = fma_((R)-0.5, s, c_obs);
+        acc += (v == v) ? v : (R)0;
+    }
+    return acc;
+}
+template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta) {
+    const R c_obs = -(R)0.91893853320467274178;
+    R b = 0;
+    for (int k = 0; k < D; ++k) {
+        const R yk = y[k], y2 = yk * yk;
+        R v = (R)0;
+        if (y2 - y2 == 0) v = y2 > (R)0 ? fma_((R)-0.5, (R)1 + det_log(y2), c_obs) : (R)INFINITY;
+        b += v > (R)0 ? v : (R)0;
+    }
+    return b;
+}
+"""
+
+# mean F x + b: theta = [F (D x D, row-major) | b (D)]
+BUILTIN_LINEAR_MEAN = r"""
+template <typename R, int D> __device__ void mean(int t, const R* xprev, const R* theta, R* mu) {
+    for (int k = 0; k < D; ++k) {
+        R acc = theta[D * D + k];
+        for (int j = 0; j < D; ++j) acc = fma_(theta[k * D + j], xprev[j], acc);
+        mu[k] = acc;
+    }
+}
+"""
+
+# the reference's rare-event example (examples/rare_event/auxiliary_csmc.py): AR(1) x_t = rho x_{t-1} + sqrt(1 - rho^2) eps, and a potential that is
+# zero except at t = T - 1, log N(y; x, r^2).  theta_g = [T, y, r], theta_m = [rho]
+RARE_EVENT = r"""
+template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta) {
+    if (t != (int)theta[0] - 1) return (R)0;
+    const R z = (theta[1] - x[0]) / theta[2];
+    return (R)-0.5 * (z * z) - log(theta[2]) - (R)0.91893853320467274178;
+}
+template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta) {
+    return t == (int)theta[0] - 1 ? -log(theta[2]) - (R)0.91893853320467274178 : (R)0;
+}
+template <typename R, int D> __device__ void mean(int t, const R* xprev, const R* theta, R* mu) {
+    mu[0] = theta[0] * xprev[0];
+}
+"""
+
+# Student-t observations y_k ~ x_k + s t_nu: theta = [nu, s]
+STUDENT_T = r"""
+template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta) {
+    const R nu = theta[0], s = theta[1];
+    const R c = lgamma((nu + (R)1) / (R)2) - lgamma(nu / (R)2) - (R)0.5 * log(nu * (R)3.14159265358979323846 * s * s);
+    R acc = 0;
+    for (int k = 0; k < D; ++k) {
+        const R z = (y[k] - x[k]) / s;
+        acc += c - (nu + (R)1) / (R)2 * log1p(z * z / nu);
+    }
+    return acc;
+}
+"""
+
+# the classic nonlinear growth model: x_t = x/2 + 25 x / (1 + x^2) + 8 cos(1.2 t) + noise, y_t ~ N(x_t^2 / 20, sig^2): theta_g = [sig]
+GROWTH = r"""
+template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta) {
+    const R z = (y[0] - x[0] * x[0] / (R)20) / theta[0];
+    return (R)-0.5 * (z * z) - log(theta[0]) - (R)0.91893853320467274178;
+}
+template <typename R, int D> __device__ void mean(int t, const R* xprev, const R* theta, R* mu) {
+    const R v = xprev[0];
+    mu[0] = v / (R)2 + (R)25 * v / ((R)1 + v * v) + (R)8 * cos((R)1.2 * (R)t);
+}
+"""

@@ -49,7 +49,7 @@ class AuxiliaryGt(Potential):
 
 
 def _get_parallel_kernel(M0, G0, Mt, Gt, N, gmode=0):
-    fk = _device.describe_independent(M0, G0, Mt, Gt, None, gmode)
+    fk = _device.describe_independent(M0, G0, Mt, Gt, None, gmode, parallel=True)
 
     def kernel(key, state, delta, noise=None):
         if isinstance(state.x, _device.CsmcChains):  # resident chains: in place, asynchronous; delta None = the chains' device delta

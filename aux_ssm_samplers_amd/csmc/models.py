@@ -93,3 +93,33 @@ class MaskedGaussianObsPotential(UnivariatePotential, Potential):
     sig: float = 1.0
     y: Optional[Any] = None
     params: Optional[Any] = None
+
+
+# ---- user-defined models: device code compiled when the kernel is built (csrc/fk_program.hip, include/auxssm.h auxssm_fk_program_compile) ----------
+@dataclass
+class DevicePotential(UnivariatePotential, Potential):
+    """A potential written as HIP device code, compiled into the sequential cSMC kernels at get_kernel time.  `source` defines
+        template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta);
+    and optionally  template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta)  (sup_x log G_t, or +inf).
+    t = the time index of x (0 for G0); xprev = x_{t-1} (nullptr at t = 0); y = row t of the (T, p) observations (nullptr without); theta = `theta`.
+    As G0 give y = ys[0]; as Gt give params = ys[1:], like the built-in potentials; G0 and Gt carry the same source and theta.  p: the number of
+    observation columns (default: inferred from y / params).  The code may call fma_, det_exp, det_log and the device math library (exp, log, lgamma, ...)."""
+    source: str = ""
+    y: Optional[Any] = None
+    params: Optional[Any] = None
+    theta: Optional[Any] = None
+    p: Optional[int] = None
+
+
+@dataclass
+class DeviceGaussianDynamics(Dynamics, Potential):
+    """x_t | x_{t-1} ~ N(mean(x_{t-1}), Q) with the mean written as HIP device code (compiled at get_kernel time):
+        template <typename R, int D> __device__ void mean(int t, const R* xprev, const R* theta, R* mu);
+    t = the time index of x_t.  Q (d, d) is time-invariant; the backward pass evaluates N(x_{t+1}; mean(x_t), Q) through the same code."""
+    source: str = ""
+    Q: Any = None
+    theta: Optional[Any] = None
+    params: Optional[Any] = None
+
+    def chol(self):
+        return np.linalg.cholesky(np.atleast_2d(np.asarray(self.Q, np.float64)))

@@ -1617,6 +1617,7 @@ int auxssm_destroy(auxssm_handle h) {
     if (h->ws) (void)hipFree(h->ws);
     if (h->dblock) (void)hipFree(h->dblock);
     if (h->cw_dev) (void)hipFree(h->cw_dev);
+    fk_modules_release(h);
     if (h->side.streams[0]) {
         for (int p = 0; p < auxssm_ctx::SideStage::NS; ++p) {
             (void)hipStreamSynchronize(h->side.streams[p]);

@@ -15,365 +15,9 @@
 // the standalone primitives (normalize / multinomial / systematic) and the parallel-in-time sweep keep the Kogge-Stone-in-64 cumsum,
 // the balanced-tree-in-64 sum and the plain binary search of csmc_dev.h.
 #include "csmc_dev.h"
+#include "fk_program.h"
 
 namespace ax {
-
-// gb[t] = sup_x G_t(x): the reduction-free part of the forward weights' shift (sweep contract, csmc_dev.h); +inf where the potential is unbounded
-template <typename R, int D> __global__ void k_csmc_potbound(int T, FkDev<R> m, const R* __restrict__ y, R* __restrict__ gb) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    R b = 0;
-    if (m.potential == 1) b = m.c_obs;
-    else if (m.potential == 3) {
-        int nobs = 0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) nobs += (y[(long long)t * D + k] - y[(long long)t * D + k] == 0) ? 1 : 0;
-        b = (R)nobs * m.c_obs;
-    } else if (m.potential == 2) {  // sum_k [c_obs - (x + y^2 e^-x) / 2] <= sum_k max(0, c_obs - (1 + log y^2) / 2)  (a NaN term counts 0)
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            const R yk = y[(long long)t * D + k], y2 = yk * yk;
-            R v = (R)0;
-            if (y2 - y2 == 0) v = y2 > (R)0 ? fma_((R)-0.5, (R)1 + det_log(y2), m.c_obs) : (R)INFINITY;
-            b += v > (R)0 ? v : (R)0;
-        }
-    }
-    gb[t] = b;
-}
-// ---- forward pass (_csmc, csmc.py:69-107) -------------------------------------------------------------------------------
-// NW = 8 / 16: exactly NW full waves (N = blockDim = 64 NW: the C4 / C3 shapes): no liveness / group-bound selects (csmc_dev.h); NW = 0: any N
-// SP = 1: the instantiation of config C3's shape -- auxiliary independent proposals, the stochastic-volatility potential, a time-invariant linear transition, draws
-// generated in the kernel, no ancestor trace (backward sampling): the run-time switches on the model kind are folded at compile time (they are wave-uniform
-// branches, two dozen per time step); same operations on the same operands, bit for bit (tests/test_gpu_csmc.py runs both instantiations on C3's model)
-template <typename R, int D, bool TV, bool GRAD, int NW, int SP = 0> __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m) {
-    if constexpr (SP == 1) {
-        m.proposal = 1;
-        m.potential = 2;
-        m.transition = 0;
-        a.As = nullptr;
-        a.noise_mode = 1;
-        a.pregen = 0;
-    }
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int TB = blockDim.x, nw = TB >> 6, tid = threadIdx.x, N = a.N, T = a.T;
-    // two images of (c, xprev), alternated by time-step parity: readers of step t never race writers of step t+1,
-    // which removes the end-of-step barrier (4 barriers per step: max, sum, wave totals, publish)
-    const int CP = cpad(TB);            // the cumsum image is padded against LDS bank conflicts of the search (csmc_dev.h::cpad)
-    R* cbuf = (R*)smem;                 // [2][CP]
-    R* xbuf = cbuf + 2 * CP;            // [2][TB][D]
-    R* red = xbuf + 2 * TB * D;         // [48]
-    const int ch = a.c0 + blockIdx.x;
-    const bool live = NW > 0 ? true : tid < N;
-    if (tid < 16) red[32 + tid] = 0;  // totals of absent groups: +0 (totals_prefix reads all 16 slots; ordered by the first barrier below)
-    const R* xstar = (const R*)a.x + (long long)ch * T * D;
-    const R* uaux = (const R*)a.u + (long long)ch * T * D;
-    const R* gaux = GRAD ? (const R*)a.grad + (long long)ch * T * D : uaux;
-    const R* yv = (const R*)a.y;
-    R* xs = (R*)a.xs + (long long)ch * T * N * D;
-    R* lws = (R*)a.lws + (long long)ch * T * N;
-    int32_t* As = a.As ? a.As + (long long)ch * (T - 1) * N : nullptr;
-    const long long eps_base = (long long)ch * T * N * D;
-    const long long ures_base = (long long)ch * (T - 1) * N;
-    const R ninf = -INFINITY;
-
-    // t = 0  (csmc.py:74-80)
-    // In-kernel draws (THREEFRY): one Threefry block serves TWO consecutive time steps of a particle, so each step pays for
-    // one block (normals on even t, uniforms on odd t) instead of two.  With T2 = ceil(T/2):
-    //   eps_prop[ch][t][n][k] = normal  2 * (((ch T2 + (t >> 1)) N + n) D + k) + (t & 1)  of stream 2
-    //   u_res[ch][s][n]       = uniform 2 * ((ch T2 + (s >> 1)) N + n) + (s & 1)          of stream 3
-    // (flat auxssm_rng_* indices; csmc/_device.py::key_noise builds the equivalent explicit arrays).
-    const bool gen = a.noise_mode != 0 && !a.pregen;
-    const long long T2 = (T + 1) >> 1;
-    R x[D], eps[D], eps_nx[D], ycur[D], pm[D], un_nx = 0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        eps_nx[k] = 0;
-        if (gen) {
-            R z0, z1;
-            stream_normal2<R>(a.key0, a.key1, STREAM_EPS_PROP, (unsigned long long)(((long long)ch * T2 * N + tid) * D + k), z0, z1);
-            eps[k] = live ? z0 : (R)0;
-            eps_nx[k] = live ? z1 : (R)0;
-        } else {
-            eps[k] = live ? ((const R*)a.eps_prop)[eps_base + (long long)tid * D + k] : (R)0;
-        }
-        ycur[k] = yv ? yv[k] : (R)0;
-    }
-    if (m.proposal == 0) {  // M0 = N(m0, P0)
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            R acc = m.m0[k];
-#pragma unroll
-            for (int j = 0; j <= k; ++j) acc = fma_(m.LP0[k * CS_MAXD + j], eps[j], acc);
-            x[k] = acc;
-        }
-    } else {  // AuxiliaryM0: N(u_0 [+ delta_0/2 grad_0], delta_0/2 I)  (independent.py:143-158)
-        const R s0 = ((const R*)a.shd)[0];
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            pm[k] = GRAD ? fma_(s0 * s0, gaux[k], uaux[k]) : uaux[k];
-            x[k] = fma_(s0, eps[k], pm[k]);
-        }
-    }
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) x[k] = xstar[k];
-    }
-    R lw;
-    {
-        R g = potential<R, D>(m, x, ycur);
-        if (m.proposal == 1) {
-            g = g + gauss_chol_logpdf<R, D>(x, m.m0, m.LP0, m.iLP0, m.c_init);  // AuxiliaryG0 (independent.py:163-169)
-            if constexpr (GRAD) g = g + grad_correction<R, D>(x, uaux, pm, ((const R*)a.shd)[0]);  // GradientAuxiliaryG0 (:173-190)
-        }
-        lw = live ? g : ninf;
-    }
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) xs[(long long)tid * D + k] = x[k];
-        lws[tid] = lw;
-    }
-    R* fmax = a.fmax ? (R*)a.fmax + (long long)ch * T : nullptr;
-    R mstep;
-    R w = block_expmax<R, NW>(lw, red, tid, nw, &mstep);
-    if (fmax && tid == 0) fmax[0] = mstep;
-    const R* gbp = (const R*)a.gb;
-    const bool bmode = gbp != nullptr && !(GRAD && m.gradient == 2);  // (the exact-gradient correction is unbounded in x)
-    bool used_bound = false;
-
-    for (int t = 1; t < T; ++t) {
-        // issue this step's independent loads first
-        R un = 0;
-        const R gbt = bmode ? gbp[t] : (R)0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) ycur[k] = yv ? yv[(long long)t * D + k] : (R)0;
-        if (!gen) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) eps[k] = live ? ((const R*)a.eps_prop)[eps_base + ((long long)t * N + tid) * D + k] : (R)0;
-            if (live) un = ((const R*)a.u_res)[ures_base + (long long)(t - 1) * N + tid];
-        } else if (t & 1) {  // normals cached by step t - 1; uniforms of steps t and t + 1
-#pragma unroll
-            for (int k = 0; k < D; ++k) eps[k] = eps_nx[k];
-            stream_uniform2<R>(a.key0, a.key1, STREAM_U_RES, (unsigned long long)(((long long)ch * T2 + ((t - 1) >> 1)) * N + tid), un, un_nx);
-        } else {  // uniform cached by step t - 1; normals of steps t and t + 1
-            un = un_nx;
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                R z0, z1;
-                stream_normal2<R>(a.key0, a.key1, STREAM_EPS_PROP, (unsigned long long)((((long long)ch * T2 + (t >> 1)) * N + tid) * D + k), z0, z1);
-                eps[k] = live ? z0 : (R)0;
-                eps_nx[k] = live ? z1 : (R)0;
-            }
-        }
-        // conditional multinomial resampling (resamplings.py:14-37 -> jax.random.choice: cumsum, r = c[-1] (1-u), searchsorted)
-        R* c = cbuf + (t & 1) * CP;
-        R* xprev = xbuf + (t & 1) * TB * D;
-#pragma unroll
-        for (int k = 0; k < D; ++k) xprev[tid * D + k] = x[k];
-        R tot;
-        block_cumsum_dpp<R, NW, true>(w, c, red, tid, nw, tot);  // trailing barrier also publishes xprev; tot = c[N - 1]
-        if (used_bound && !(tot > (R)0)) {  // every weight of step t - 1 underflowed under its bound: the exact maximum after all (uniform)
-            __syncthreads();                // (every lane is past its reads of the step's images before they are rewritten)
-            w = block_expmax<R, NW>(lw, red, tid, nw, &mstep);
-            if (fmax && tid == 0) fmax[t - 1] = mstep;
-            block_cumsum_dpp<R, NW, true>(w, c, red, tid, nw, tot);
-        }
-        int idx = 0;
-        if (live && tid > 0) idx = search2<R, NW, true>(c, N, tot * ((R)1 - un));
-        R xp[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) xp[k] = xprev[idx * D + k];
-        // propagate (csmc.py:91-92); the transition t - 1 -> t (time-varying: row t - 1 of the device arrays)
-        const TransT<R> tr = trans_at_c<R, D, TV>(m, t - 1);
-        if (m.proposal == 0) {
-            R mu[D];
-            trans_mean_t<R, D>(m, tr, xp, mu);
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                R acc = mu[k];
-#pragma unroll
-                for (int j = 0; j <= k; ++j) acc = fma_(tr.LQ[k * tr.ld + j], eps[j], acc);
-                x[k] = acc;
-            }
-        } else {  // AuxiliaryMtDynamics: N(u_t [+ delta_t/2 grad_t], delta_t/2 I), independent of the parent (independent.py:192-198)
-            const R st = ((const R*)a.shd)[t];
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                pm[k] = GRAD ? fma_(st * st, gaux[(long long)t * D + k], uaux[(long long)t * D + k]) : uaux[(long long)t * D + k];
-                x[k] = fma_(st, eps[k], pm[k]);
-            }
-        }
-        if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) x[k] = xstar[(long long)t * D + k];
-        }
-        // weights (csmc.py:95-96)
-        R g = potential<R, D>(m, x, ycur);
-        if (m.proposal == 1) {  // AuxiliaryGt = Mt.logpdf + Gt (independent.py:238-248)
-            R mu[D];
-            trans_mean_t<R, D>(m, tr, xp, mu);
-            g = gauss_chol_logpdf<R, D>(x, mu, tr.LQ, tr.iL, tr.c_trans, tr.ld) + g;
-            // GradientAuxiliaryGt (:252-268): in the reference the correction is summed over all particles, i.e. a constant of the
-            // step (AUXSSM_GRAD_REFERENCE: nothing to add); AUXSSM_GRAD_EXACT applies it per particle
-            if constexpr (GRAD) {
-                if (m.gradient == 2) g = g + grad_correction<R, D>(x, uaux + (long long)t * D, pm, ((const R*)a.shd)[t]);
-            }
-        }
-        lw = live ? g : ninf;
-        if (live) {
-            const long long o = (long long)t * N + tid;
-#pragma unroll
-            for (int k = 0; k < D; ++k) xs[o * D + k] = x[k];
-            lws[o] = lw;
-            if (As) As[(long long)(t - 1) * N + tid] = idx;
-        }
-        // the shift of this step's weights (sweep contract): a reduction-free bound where there is one, else the block maximum
-        R Mb = gbt + (m.proposal == 1 ? tr.c_trans : (R)0);
-        used_bound = bmode && t < T - 1 && (Mb - Mb == 0);
-        if (used_bound) {
-            w = det_exp(lw - Mb);
-            mstep = Mb;
-        } else {
-            w = block_expmax<R, NW>(lw, red, tid, nw, &mstep);
-        }
-        if (fmax && tid == 0) fmax[t] = mstep;
-    }
-    if (live) ((R*)a.wT)[(long long)ch * N + tid] = w;
-}
-
-// ---- backward passes (csmc.py:110-149) ------------------------------------------------------------------------------------
-// One draw per step: B = #{j : c_j < r} by ballot + per-wave counts (no serial search), the candidate particles of the step are
-// published to LDS before the first barrier so that x_t^B is an LDS read, and the next step's rows (xs, log_ws) and uniform are
-// fetched one step ahead: no global-memory latency on the dependent chain.  4 barriers per step (max, wave totals, publish, counts).
-template <typename R, int D, bool TV, int NW> __global__ void __launch_bounds__(1024) k_csmc_bwd(CsmcArgs a, FkDev<R> m) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int TB = blockDim.x, nw = TB >> 6, tid = threadIdx.x, N = a.N, T = a.T;
-    R* c = (R*)smem;                 // [2][TB] the step's cumulative weights (generic) / local scan values (full workgroups), by step parity
-    R* red = c + 2 * TB;             // [48] + [16]: a second set of wave totals (slots [48, 64)) for the odd steps of the one-barrier loop
-    R* xpub = red + 64;              // [2][TB][D] candidate particles of the step, by step parity
-    R* ubuf = xpub + 2 * TB * D;     // [2] the step's uniform, by step parity
-    const int ch = a.c0 + blockIdx.x;
-    const bool live = NW > 0 ? true : tid < N;
-    if (tid < 16) red[32 + tid] = 0, red[48 + tid] = 0;  // totals of absent groups: +0 (csmc_dev.h::totals_prefix)
-    const R* xs = (const R*)a.xs + (long long)ch * T * N * D;
-    const R* lws = (const R*)a.lws + (long long)ch * T * N;
-    const int32_t* As = a.As ? a.As + (long long)ch * (T - 1) * N : nullptr;
-    R* xout = (R*)a.x + (long long)ch * T * D;
-    int32_t* anc = a.anc + (long long)ch * T;
-    const long long ub_base = (long long)ch * T;
-    const R ninf = -INFINITY;
-
-    // B_T ~ choice(w_T)   (csmc.py:111 / :131); w_T are the forward pass's unnormalised weights
-    R w = live ? ((const R*)a.wT)[(long long)ch * N + tid] : (R)0;
-    if (tid == 0) ubuf[1] = ((const R*)a.u_bwd)[ub_base + (T - 1)];
-    {
-        R xi[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) xi[k] = live ? xs[((long long)(T - 1) * N + tid) * D + k] : (R)0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) xpub[(TB + tid) * D + k] = xi[k];
-    }
-    R tot;
-    int B;
-    {   // (sweep contract: the two-level single draw; the generic cumsum image c[] holds base + local, so the local values are recovered per group)
-        const int lane = tid & 63, wv = tid >> 6;
-        const R v = wave_scan_dpp(w);
-        c[TB + tid] = v;
-        if (lane == 63) red[32 + wv] = v;
-        __syncthreads();
-        R pre, Pv;
-        totals_prefix<R>(red, lane, wv, nw - 1, pre, tot, &Pv);
-        B = draw_two_level<R>(c + TB, Pv, lane, nw, N, tot * ((R)1 - ubuf[1]));
-    }
-    R xn[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) xn[k] = xpub[(TB + B) * D + k];
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) xout[(long long)(T - 1) * D + k] = xn[k];
-        anc[T - 1] = B;
-    }
-    if (!a.backward) {
-        // ancestor tracing: B_{t-1} = A_t[B_t]  (csmc.py:114-121); a dependent pointer chase, one lane
-        if (tid == 0) {
-            for (int t = T - 1; t >= 1; --t) {
-                B = As[(long long)(t - 1) * N + B];
-#pragma unroll
-                for (int k = 0; k < D; ++k) xout[(long long)(t - 1) * D + k] = xs[((long long)(t - 1) * N + B) * D + k];
-                anc[t - 1] = B;
-            }
-        }
-        return;
-    }
-    // backward sampling (Whiteley), csmc.py:134-146
-    __syncthreads();  // the parity-1 slots of the first draw are free again
-    R xi_nx[D], lw_nx = ninf, un_nx = 0, fm_nx = 0;
-    const R* fmax = (const R*)a.fmax + (long long)ch * T;
-    if (T >= 2) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) xi_nx[k] = live ? xs[((long long)(T - 2) * N + tid) * D + k] : (R)0;
-        lw_nx = live ? lws[(long long)(T - 2) * N + tid] : ninf;
-        fm_nx = fmax[T - 2];
-        if (tid == 0) un_nx = ((const R*)a.u_bwd)[ub_base + (T - 2)];
-    }
-    for (int t = T - 2; t >= 0; --t) {
-        const int par = t & 1;
-        R xi[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) xi[k] = xi_nx[k];
-        const R lwi = lw_nx, un_t = un_nx, fm_t = fm_nx;
-        if (t > 0) {  // the rows of step t - 1: independent of this step's draw
-#pragma unroll
-            for (int k = 0; k < D; ++k) xi_nx[k] = live ? xs[((long long)(t - 1) * N + tid) * D + k] : (R)0;
-            lw_nx = live ? lws[(long long)(t - 1) * N + tid] : ninf;
-            fm_nx = fmax[t - 1];
-            if (tid == 0) un_nx = ((const R*)a.u_bwd)[ub_base + (t - 1)];
-        }
-        R lw = ninf;
-        const TransT<R> tr = trans_at_c<R, D, TV>(m, t);  // Pt.logpdf(x_{t+1}, xs_t, params_t) (csmc.py:136)
-        if (live) {
-            R mu[D];
-            trans_mean_t<R, D>(m, tr, xi, mu);
-            lw = gauss_chol_logpdf<R, D>(xn, mu, tr.LQ, tr.iL, tr.c_trans, tr.ld) + lwi;
-        }
-#pragma unroll
-        for (int k = 0; k < D; ++k) xpub[(par * TB + tid) * D + k] = xi[k];
-        if (tid == 0) ubuf[par] = un_t;
-        // weights shifted by a bound of their maximum that needs no reduction (sweep contract): the forward pass's block maximum of
-        // log_ws[t] plus the transition's log-normaliser; the exact maximum only if everything underflowed
-        R Mb = fm_t + tr.c_trans;
-        if (!(Mb - Mb == 0)) Mb = 0;
-        w = det_exp(lw - Mb);
-        {   // ONE barrier per step: local scan values and wave totals of this parity are published together with xpub / ubuf; every wave then finds the
-            // group and counts inside it on its own (csmc_dev.h::draw_two_level)
-            const int lane = tid & 63, wv = tid >> 6;
-            R* vloc = c + par * TB;
-            R* tl = red + 32 + par * 16;
-            R v = wave_scan_dpp(w);
-            vloc[tid] = v;
-            if (lane == 63) tl[wv] = v;
-            __syncthreads();
-            R pre, Pv;
-            totals_prefix<R>(tl - 32, lane, wv, nw - 1, pre, tot, &Pv);
-            if (!(tot > (R)0)) {  // (uniform) every weight underflowed under its bound: the exact maximum after all
-                __syncthreads();  // (every wave has read this parity's totals before they are rewritten)
-                w = block_expmax<R, NW>(lw, red, tid, nw);
-                v = wave_scan_dpp(w);
-                vloc[tid] = v;
-                if (lane == 63) tl[wv] = v;
-                __syncthreads();
-                totals_prefix<R>(tl - 32, lane, wv, nw - 1, pre, tot, &Pv);
-            }
-            B = draw_two_level<R>(vloc, Pv, lane, nw, N, tot * ((R)1 - ubuf[par]));
-        }
-#pragma unroll
-        for (int k = 0; k < D; ++k) xn[k] = xpub[(par * TB + B) * D + k];
-        if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) xout[(long long)t * D + k] = xn[k];
-            anc[t] = B;
-        }
-    }
-}
 
 // ---- standalone primitives: normalize (math/utils.py:23-39) and conditional multinomial resampling (resamplings.py:14-37),
 // one workgroup per row, exactly the block primitives of the forward pass
@@ -453,6 +97,20 @@ __global__ void __launch_bounds__(1024) k_systematic(int M, int N, const R* __re
     }
 }
 
+// dynamic LDS of the forward / backward pass (csmc_sweep.h: k_csmc_fwd, k_csmc_bwd) for TB lanes
+static size_t fwd_lds(int TB, int D, size_t sR) { return (size_t)2 * (cpad(TB) + TB * D) * sR + 48 * sR + 64; }
+static size_t bwd_lds(int TB, int D, size_t sR) { return (size_t)2 * TB * sR + 64 * sR + (size_t)2 * TB * D * sR + 2 * sR + 64; }
+// the arguments of the batch [c0, c0 + cb) of chains (CsmcArgs::c0)
+static CsmcArgs csmc_batch(const CsmcArgs& a, int c0, int cb) {
+    CsmcArgs ab = a;
+    ab.c0 = c0;
+    ab.C = a.C - c0 < cb ? a.C - c0 : cb;
+    ab.xs = (char*)a.xs - (size_t)c0 * a.xs_rec;
+    ab.lws = (char*)a.lws - (size_t)c0 * a.lws_rec;
+    if (a.As) ab.As = (int32_t*)((char*)a.As - (size_t)c0 * a.As_rec);
+    return ab;
+}
+
 template <typename R, int D>
 static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, const double* host_model, CsmcArgs& a, void* ctt) {
     FkDev<R> m;
@@ -479,15 +137,10 @@ static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, const double* host
     // forward + backward pass, batch of chains by batch (CsmcArgs::c0; one batch unless the particle systems of all chains do not fit the device)
     const int cb = a.cb > 0 ? a.cb : a.C;
     for (int c0 = 0; c0 < a.C; c0 += cb) {
-    CsmcArgs ab = a;
-    ab.c0 = c0;
-    ab.C = a.C - c0 < cb ? a.C - c0 : cb;
-    ab.xs = (char*)a.xs - (size_t)c0 * a.xs_rec;
-    ab.lws = (char*)a.lws - (size_t)c0 * a.lws_rec;
-    if (a.As) ab.As = (int32_t*)((char*)a.As - (size_t)c0 * a.As_rec);
+    const CsmcArgs ab = csmc_batch(a, c0, cb);
     {
         ProfScope ps(h, AUXSSM_K_CSMC_FWD);
-        const size_t lds = (size_t)2 * (cpad(TB) + TB * D) * sizeof(R) + 48 * sizeof(R) + 64;
+        const size_t lds = fwd_lds(TB, D, sizeof(R));
         const bool tv = m.Ft != nullptr, gr = m.gradient != 0;
         const int fullw = (TB == a.N && (a.N == 1024 || a.N == 512)) ? a.N / 64 : 0;
 #define AX_FWD1(TVv, GRv, NWv)                                                                                                                                  \
@@ -517,7 +170,7 @@ static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, const double* host
     }
     {
         ProfScope ps(h, AUXSSM_K_CSMC_BWD);
-        const size_t lds = (size_t)2 * TB * sizeof(R) + 64 * sizeof(R) + (size_t)2 * TB * D * sizeof(R) + 2 * sizeof(R) + 64;
+        const size_t lds = bwd_lds(TB, D, sizeof(R));
         const int fullw = (TB == a.N && (a.N == 1024 || a.N == 512)) ? a.N / 64 : 0;
 #define AX_BWD(TVv, NWv)                                                                                                                                 \
     do {                                                                                                                                                 \
@@ -535,6 +188,63 @@ static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, const double* host
         }
 #undef AX_BWD
     }
+    }
+    AX_HIP(hipGetLastError());
+    return AUXSSM_OK;
+}
+
+// run_csmc with a user-defined model (fk_program.hip): the same launches, the forward / backward passes and the potential's bound from the program's
+// module.  Time-invariant transitions, no gradient (auxssm_csmc_sweep_program refuses the rest).
+static int fk_launch(auxssm_ctx* h, hipFunction_t f, unsigned grid, unsigned block, size_t lds, void** args) {
+    if (lds > 48 * 1024) {  // (module functions have no hipFuncSetAttribute: their limit is what the device grants, checked here)
+        int mx = 0;
+        AX_HIP(hipFuncGetAttribute(&mx, HIP_FUNC_ATTRIBUTE_MAX_DYNAMIC_SHARED_SIZE_BYTES, f));
+        if ((size_t)mx < lds) {
+            set_error("the user-model sweep needs %zu bytes of LDS, the device grants %d", lds, mx);
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+    }
+    AX_HIP(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, (unsigned)lds, h->stream, args, nullptr));
+    return AUXSSM_OK;
+}
+template <typename R, int D>
+static int run_csmc_program(auxssm_ctx* h, const auxssm_fk_program_s* prog, const auxssm_fk_model* fk, const double* host_model, const auxssm_fk_user* user,
+                            CsmcArgs& a) {
+    const hipFunction_t* fn = nullptr;
+    int rc = fk_program_functions(h, prog, &fn);
+    if (rc) return rc;
+    FkDev<R> m;
+    fill_model<R>(m, fk, host_model);
+    FkUser<R> u{(const R*)user->y, (const R*)user->theta_g, (const R*)user->theta_m, user->p};
+    const int TB = (a.N + 63) / 64 * 64;
+    if (a.gb) {
+        if (prog->flags & AUXSSM_FK_USER_POTENTIAL) {
+            int T = a.T;
+            R* gb = (R*)a.gb;
+            void* args[] = {&T, &u, &gb};
+            if ((rc = fk_launch(h, fn[FK_BOUND], (unsigned)((a.T + 255) / 256), 256, 0, args))) return rc;
+        } else {
+            hipLaunchKernelGGL((k_csmc_potbound<R, D>), dim3((a.T + 255) / 256), dim3(256), 0, h->stream, a.T, m, (const R*)a.y, (R*)a.gb);
+        }
+    }
+    if (fk->proposal == 1) {
+        const long long total = (long long)a.C * a.T * D;
+        hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
+    }
+    const int fullw = (TB == a.N && (a.N == 1024 || a.N == 512)) ? a.N / 64 : 0;
+    const int sel = fullw == 16 ? 2 : (fullw == 8 ? 1 : 0);
+    const int cb = a.cb > 0 ? a.cb : a.C;
+    for (int c0 = 0; c0 < a.C; c0 += cb) {
+        CsmcArgs ab = csmc_batch(a, c0, cb);
+        void* args[] = {&ab, &m, &u};
+        {
+            ProfScope ps(h, AUXSSM_K_CSMC_FWD);
+            if ((rc = fk_launch(h, fn[FK_FWD0 + sel], (unsigned)ab.C, (unsigned)TB, fwd_lds(TB, D, sizeof(R)), args))) return rc;
+        }
+        {
+            ProfScope ps(h, AUXSSM_K_CSMC_BWD);
+            if ((rc = fk_launch(h, fn[FK_BWD0 + sel], (unsigned)ab.C, (unsigned)TB, bwd_lds(TB, D, sizeof(R)), args))) return rc;
+        }
     }
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;
@@ -613,9 +323,10 @@ extern "C" int auxssm_systematic_resample(auxssm_handle h, int dtype, int32_t ro
     return AUXSSM_OK;
 }
 
-extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_model* fk, int32_t C, int32_t T, int32_t N,
-                                 int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise,
-                                 int32_t* ancestors, void* xs_out, void* log_ws_out, int32_t* As_out) {
+// auxssm_csmc_sweep (prog == nullptr) and auxssm_csmc_sweep_program: one validation, one workspace plan, one chain batching
+static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk, const auxssm_fk_program_s* prog, const auxssm_fk_user* user, int32_t C,
+                           int32_t T, int32_t N, int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise, int32_t* ancestors,
+                           void* xs_out, void* log_ws_out, int32_t* As_out) {
     if (!h) {
         set_error("handle is NULL");
         return AUXSSM_ERR_ARG;
@@ -636,6 +347,29 @@ extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_mod
     }
     const int D = fk->dx;
     const bool wide = D > CS_MAXD;  // csmc_wide.hip: one wave per chain, particles' components in LDS rows
+    const bool ug = prog && (prog->flags & AUXSSM_FK_USER_POTENTIAL), um = prog && (prog->flags & AUXSSM_FK_USER_MEAN);
+    if (prog) {
+        if (!user) {
+            set_error("user must be non-NULL");
+            return AUXSSM_ERR_ARG;
+        }
+        if (prog->dtype != dtype || prog->dx != D) {
+            set_error("the program was compiled for dtype %d, dx %d (sweep: dtype %d, dx %d)", prog->dtype, prog->dx, dtype, D);
+            return AUXSSM_ERR_ARG;
+        }
+        if (fk->F_t || fk->b_t || fk->chol_Q_t || fk->gradient != AUXSSM_GRAD_NONE) {
+            set_error("user-defined models run time-invariant transitions without gradient proposals");
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+        if (um && fk->transition != AUXSSM_TRANS_LINEAR) {
+            set_error("a user transition mean replaces the linear one (transition must be AUXSSM_TRANS_LINEAR)");
+            return AUXSSM_ERR_ARG;
+        }
+        if (user->y && user->p < 1) {
+            set_error("user observations need p >= 1 columns");
+            return AUXSSM_ERR_ARG;
+        }
+    }
     if (D < 1 || D > 32) {
         set_error("dx=%d: the cSMC kernels cover 1 <= dx <= 32", D);
         return AUXSSM_ERR_UNSUPPORTED;
@@ -656,7 +390,7 @@ extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_mod
         set_error("model has a NULL m0/chol_P0/F/b/chol_Q host pointer");
         return AUXSSM_ERR_ARG;
     }
-    if (fk->potential != AUXSSM_POT_FLAT && !fk->y) {
+    if (!ug && fk->potential != AUXSSM_POT_FLAT && !fk->y) {
         set_error("potential needs observations y");
         return AUXSSM_ERR_ARG;
     }
@@ -769,7 +503,7 @@ extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_mod
     a.As = As_out ? As_out : (!backward ? (int32_t*)ws_take(h, (size_t)cb * (T > 1 ? T - 1 : 1) * N * 4) : nullptr);
     a.wT = ws_take(h, (size_t)C * N * sR);
     a.fmax = ws_take(h, (size_t)C * T * sR);
-    a.gb = (fk->potential == 0 || fk->y) ? ws_take(h, (size_t)T * sR) : nullptr;
+    a.gb = (ug ? prog->has_bound : (fk->potential == 0 || fk->y != nullptr)) ? ws_take(h, (size_t)T * sR) : nullptr;
     a.anc = ancestors;
     a.noise_mode = noise->mode;
     a.key0 = noise->key0; a.key1 = noise->key1;
@@ -797,6 +531,17 @@ extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_mod
         a.u_res = pu;
     }
     if (wide) return run_csmc_wide(h, dtype, fk, a, ctt);
+    if (prog) {
+#define AX_CSMC_P(R)                                                                 \
+    switch (D) {                                                                     \
+        case 1: return run_csmc_program<R, 1>(h, prog, fk, hm.data(), user, a);     \
+        case 2: return run_csmc_program<R, 2>(h, prog, fk, hm.data(), user, a);     \
+        case 3: return run_csmc_program<R, 3>(h, prog, fk, hm.data(), user, a);     \
+        default: return run_csmc_program<R, 4>(h, prog, fk, hm.data(), user, a);    \
+    }
+        if (dtype == AUXSSM_F32) { AX_CSMC_P(float) } else { AX_CSMC_P(double) }
+#undef AX_CSMC_P
+    }
 #define AX_CSMC_D(R)                                                        \
     switch (D) {                                                            \
         case 1: return run_csmc<R, 1>(h, fk, hm.data(), a, ctt);                 \
@@ -806,4 +551,20 @@ extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_mod
     }
     if (dtype == AUXSSM_F32) { AX_CSMC_D(float) } else { AX_CSMC_D(double) }
 #undef AX_CSMC_D
+}
+
+extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_model* fk, int32_t C, int32_t T, int32_t N,
+                                 int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise,
+                                 int32_t* ancestors, void* xs_out, void* log_ws_out, int32_t* As_out) {
+    return csmc_sweep_impl(h, dtype, fk, nullptr, nullptr, C, T, N, backward, sqrt_half_delta, x, noise, ancestors, xs_out, log_ws_out, As_out);
+}
+
+extern "C" int auxssm_csmc_sweep_program(auxssm_handle h, auxssm_fk_program prog, int dtype, const auxssm_fk_model* fk, const auxssm_fk_user* user,
+                                         int32_t C, int32_t T, int32_t N, int32_t backward, const void* sqrt_half_delta, void* x,
+                                         const auxssm_csmc_noise* noise, int32_t* ancestors, void* xs_out, void* log_ws_out, int32_t* As_out) {
+    if (!prog) {
+        set_error("program is NULL");
+        return AUXSSM_ERR_ARG;
+    }
+    return csmc_sweep_impl(h, dtype, fk, prog, user, C, T, N, backward, sqrt_half_delta, x, noise, ancestors, xs_out, log_ws_out, As_out);
 }

@@ -11,6 +11,7 @@
 namespace ax {
 
 void set_error(const char* fmt, ...);
+void fk_modules_release(auxssm_ctx* h);  // fk_program.hip
 
 #define AX_HIP(expr)                                                                         \
     do {                                                                                     \
@@ -52,6 +53,7 @@ struct auxssm_ctx {
     int st_dtype = -1;
     unsigned long long api_calls = 0;  // entry points that may enqueue work or change device data (not: sync, device-to-host copies, profiler reads)
     int overlap_model_stage = 0;       // AUXSSM_OPT_OVERLAP_MODEL_STAGE (off unless the caller opts in: include/auxssm.h)
+    void* fk_modules = nullptr;        // the user-model programs loaded on this handle (fk_program.hip; released by auxssm_destroy)
     bool stream_exposed = false;       // auxssm_stream() has handed out `stream`: work the library cannot see may be queued on it, so a model stage
                                        // always waits for the tail of `stream` from then on (side_open)
     // a helper stream for memory-bound side work of ONE call that needs none of the call's later results (the covariance broadcast of the chain-shared wide

@@ -8,12 +8,17 @@
 // Accuracy: ~1 ulp (fp32), ~1-2 ulp (fp64); algorithms after fdlibm's e_expf/e_logf/e_exp/e_log.
 // oracle/csmc_ref.c carries its own independent restatement of the same sequences.
 #pragma once
+#include "rtc_compat.h"
+#ifndef __HIPCC_RTC__
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#endif
 
 #if defined(__HIPCC__)
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#endif
 #define AXD_HD __host__ __device__ __forceinline__
 #else
 #define AXD_HD inline
@@ -21,10 +26,10 @@
 
 namespace ax {
 
-AXD_HD float u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-AXD_HD uint32_t f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-AXD_HD double u2d(uint64_t u) { double f; memcpy(&f, &u, 8); return f; }
-AXD_HD uint64_t d2u(double f) { uint64_t u; memcpy(&u, &f, 8); return u; }
+AXD_HD float u2f(uint32_t u) { float f; AX_MEMCPY(&f, &u, 4); return f; }
+AXD_HD uint32_t f2u(float f) { uint32_t u; AX_MEMCPY(&u, &f, 4); return u; }
+AXD_HD double u2d(uint64_t u) { double f; AX_MEMCPY(&f, &u, 8); return f; }
+AXD_HD uint64_t d2u(double f) { uint64_t u; AX_MEMCPY(&u, &f, 8); return u; }
 
 // ---- exp, fp32: x = k ln2 + r, |r| <= ln2/2, degree-7 Taylor in Horner form with fma ----------------
 AXD_HD float det_exp(float x) {

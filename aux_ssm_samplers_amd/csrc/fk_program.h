@@ -1,0 +1,26 @@
+// fk_program.h -- a compiled user-defined Feynman-Kac model (fk_program.hip) as the sweep launcher (csmc.hip) sees it.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "csmc_dev.h"
+
+namespace ax {
+
+// the program's kernels: forward / backward pass with NW = 0 / 8 / 16 (csmc.hip::run_csmc's choice), and the user potential's bound
+enum { FK_FWD0 = 0, FK_BWD0 = 3, FK_BOUND = 6, FK_NFUNC = 7 };
+// (one more name expression, not a launched function: k_fk_bound<R, D, true>, whose lowered name equals FK_BOUND's iff the source defines log_g_bound)
+enum { FK_BOUND_TRUE = FK_NFUNC, FK_NNAMES = FK_NFUNC + 1 };
+
+// the module's functions on handle h (loaded on first use)
+int fk_program_functions(auxssm_ctx* h, const auxssm_fk_program_s* p, const hipFunction_t** out);
+
+}  // namespace ax
+
+struct auxssm_fk_program_s {
+    unsigned long long id = 0;  // (never reused: the handles' module caches key on it)
+    int dtype = 0, dx = 0, flags = 0;
+    bool has_bound = false;  // the source defines log_g_bound
+    std::vector<char> code;  // the gfx950 code object
+    std::string lowered[ax::FK_NFUNC];
+};

@@ -3,11 +3,16 @@
 // AX_HD functions also compile for the host so tests can single-step a kernel body without a GPU
 // (tests/hostsim only; the product path is the HIP build).
 #pragma once
+#include "rtc_compat.h"
+#ifndef __HIPCC_RTC__
 #include <cmath>
 #include <cstdint>
+#endif
 
 #if defined(__HIPCC__)
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#endif
 #define AX_HD __host__ __device__ __forceinline__
 #else
 #define AX_HD inline

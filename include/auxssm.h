@@ -331,6 +331,38 @@ int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_model* model, 
                       int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise,
                       int32_t* ancestors, void* xs_out, void* log_ws_out, int32_t* As_out);
 
+/* ---- user-defined Feynman-Kac models: the sequential sweep compiled at run time ----------------------------------------------
+ * == the reference's cSMC kernels on ANY model object that follows its protocol (_primitives/csmc/base.py:18-71), for the models whose
+ * potential and / or transition mean can be written as device code.  auxssm_fk_program_compile compiles `source` (hipRTC, gfx950, the flags of
+ * the static sweep: -O3 -std=c++17 -ffp-contract=off) together with the sweep kernels of csrc/csmc_sweep.h, every instantiation the launcher may
+ * pick (full workgroups of 8 / 16 waves and the generic one, forward and backward).  It needs no handle and no device.  The source defines, at
+ * global scope (R = float / double, D = dx):
+ *   template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta);       [AUXSSM_FK_USER_POTENTIAL]
+ *   template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta);                             [optional: sup_x log G_t]
+ *   template <typename R, int D> __device__ void mean(int t, const R* xprev, const R* theta, R* mu);                      [AUXSSM_FK_USER_MEAN]
+ * (t = the time index of x, resp. of x_t; xprev = x_{t-1}, NULL at t = 0; y = row t of auxssm_fk_user::y or NULL; theta = theta_g / theta_m).
+ * What the flags leave to the built-in family comes from `model` as in auxssm_csmc_sweep.  include_dir: the directory of csmc_sweep.h.  On a
+ * compile error `log` (log_len bytes) receives hipRTC's log and the call returns AUXSSM_ERR_ARG.  dx 1..4.
+ * auxssm_csmc_sweep_program: auxssm_csmc_sweep (same arguments, validation, workspace and chain batching) with the program's model; the module is
+ * loaded once per handle.  Not covered: time-varying transitions (F_t) and gradient proposals (AUXSSM_ERR_UNSUPPORTED). */
+typedef struct auxssm_fk_program_s* auxssm_fk_program;
+typedef enum { AUXSSM_FK_USER_POTENTIAL = 1, AUXSSM_FK_USER_MEAN = 2 } auxssm_fk_program_flag;
+typedef struct {
+    const void* y;        /* device (T, p) of dtype, shared by all chains, or NULL */
+    const void* theta_g;  /* device, the potential's parameters, or NULL */
+    const void* theta_m;  /* device, the transition mean's parameters, or NULL */
+    int32_t p;
+    int32_t reserved;
+} auxssm_fk_user;
+int auxssm_fk_program_compile(const char* source, const char* include_dir, int dtype, int32_t dx, int32_t flags, char* log, size_t log_len,
+                              auxssm_fk_program* out);
+int auxssm_fk_program_free(auxssm_fk_program prog);
+/* what a compiled program holds: its dtype, dx and flags, and whether the source defines log_g_bound (has_bound 1 / 0); any pointer may be NULL */
+int auxssm_fk_program_info(auxssm_fk_program prog, int32_t* dtype, int32_t* dx, int32_t* flags, int32_t* has_bound);
+int auxssm_csmc_sweep_program(auxssm_handle h, auxssm_fk_program prog, int dtype, const auxssm_fk_model* model, const auxssm_fk_user* user, int32_t C,
+                              int32_t T, int32_t N, int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise,
+                              int32_t* ancestors, void* xs_out, void* log_ws_out, int32_t* As_out);
+
 /* ---- parallel-in-time conditional SMC (conditional dSMC) ------------------------------------------------------------
  * == kernel(key, state, delta) of aux_samplers.csmc.get_independent_kernel(..., parallel=True), classical branch
  * (csmc/independent.py:78-118 on _primitives/csmc/pit/csmc.py:69-114, operator.py, dc_map.py), for C chains at once: all T x N
