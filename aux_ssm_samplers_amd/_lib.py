@@ -54,7 +54,7 @@ class FkUser(C.Structure):
     _fields_ = [("y", C.c_void_p), ("theta_g", C.c_void_p), ("theta_m", C.c_void_p), ("p", C.c_int32), ("reserved", C.c_int32)]
 
 
-FK_USER_POTENTIAL, FK_USER_MEAN = 1, 2
+FK_USER_POTENTIAL, FK_USER_MEAN, FK_USER_GRADIENT = 1, 2, 4
 PROP_BOOTSTRAP_LG, PROP_AUX_INDEPENDENT = 0, 1
 POT_FLAT, POT_GAUSS_OBS, POT_SV, POT_GAUSS_OBS_MASKED = 0, 1, 2, 3
 TRANS_LINEAR, TRANS_LORENZ63_EM = 0, 1

@@ -199,9 +199,6 @@ def _describe_user(proposal, M0, G0, Mt, Gt, gradient, parallel):
     if parallel:
         raise NotImplementedError("user-defined models (DevicePotential / DeviceGaussianDynamics) run the sequential cSMC sweep only: parallel=True "
                                   "(the parallel-in-time kernels) is not compiled for them")
-    if gradient:
-        raise NotImplementedError("gradient-informed proposals need the gradient of the model's log-density; for user-defined device code "
-                                  "(DevicePotential / DeviceGaussianDynamics) there are no derivatives: use gradient=False")
     if not isinstance(M0, GaussianInit):
         raise NotImplementedError(f"a user-defined M0 ({type(M0).__name__}) is not supported: user-defined models keep the Gaussian initial "
                                   "distribution GaussianInit(m0, P0)")
@@ -246,7 +243,9 @@ def _describe_user(proposal, M0, G0, Mt, Gt, gradient, parallel):
     else:
         raise NotImplementedError(f"Mt={type(Mt).__name__}: user-defined transitions are Gaussian, x_t ~ N(mean(x_{{t-1}}), Q) (DeviceGaussianDynamics); "
                                   "non-Gaussian transition noise is not supported")
-    fk = FkDesc(proposal, pot, M0.m0, M0.chol(), F, b, LQ, y, sig, tk)
+    if gradient:  # the program also holds the gradient kernel, from the derivatives of the user-defined parts (grad_log_g / mean_vjp)
+        flags |= _lib.FK_USER_GRADIENT
+    fk = FkDesc(proposal, pot, M0.m0, M0.chol(), F, b, LQ, y, sig, tk, gradient)
     fk.user = UserModel("\n".join(src), flags, d, yu, theta_g, theta_m)
     return fk
 

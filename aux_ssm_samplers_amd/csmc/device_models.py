@@ -3,7 +3,11 @@
 BUILTIN_*: the built-in potentials / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc.hip::k_csmc_potbound written as user source, in the
 built-in operation order (fma_, det_exp, det_log), so that a program sweep reproduces the closed-family sweep bit for bit (the tests and
 tools/fk_program_bench.py use them).  The constants the host computes for the built-ins (csmc_dev.h::fill_model) are formed the same way on
-the device from theta = [sig].  RARE_EVENT, STUDENT_T, GROWTH: models the closed family cannot express."""
+the device from theta = [sig].  RARE_EVENT, STUDENT_T, GROWTH: models the closed family cannot express.
+
+*_GRAD / *_VJP: the same sources with the derivatives that gradient-informed proposals need (grad_log_g for a potential, mean_vjp for a mean;
+csrc/fk_user_pre.h).  BUILTIN_GAUSS_OBS_GRAD, BUILTIN_SV_GRAD and BUILTIN_LINEAR_MEAN_VJP follow csrc/csmc_sweep.h::k_csmc_grad's operation
+order, so that their gradient sweep is the closed family's bit for bit.  INCREMENT_OBS_GRAD: a potential that reads x_{t-1}."""
 
 HALF_LOG_2PI = "(R)0.91893853320467274178"
 
@@ -100,5 +104,93 @@ template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xpre
 template <typename R, int D> __device__ void mean(int t, const R* xprev, const R* theta, R* mu) {
     const R v = xprev[0];
     mu[0] = v / (R)2 + (R)25 * v / ((R)1 + v * v) + (R)8 * cos((R)1.2 * (R)t);
+}
+"""
+
+
+# ---- with derivatives (gradient-informed proposals) -----------------------------------------------------------------------------------------------
+# d/dx log N(y; x, sig^2 I) = (y - x) / sig^2, as ((y - x) inv) inv
+BUILTIN_GAUSS_OBS_GRAD = BUILTIN_GAUSS_OBS + r"""
+template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
+    const R inv = (R)1 / theta[0];
+    for (int k = 0; k < D; ++k) gx[k] = ((y[k] - x[k]) * inv) * inv;
+}
+"""
+
+# d/dx_k of -0.5 (y_k^2 e^{-x_k} + x_k) = 0.5 (y_k^2 e^{-x_k} - 1), NaN -> 0
+BUILTIN_SV_GRAD = BUILTIN_SV + r"""
+template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
+    for (int k = 0; k < D; ++k) {
+        const R e = det_exp(-x[k]);
+        const R v = (R)0.5 * fma_(y[k] * y[k], e, (R)-1);
+        gx[k] = (v == v) ? v : (R)0;
+    }
+}
+"""
+
+# J = F: out = F^T v
+BUILTIN_LINEAR_MEAN_VJP = BUILTIN_LINEAR_MEAN + r"""
+template <typename R, int D> __device__ void mean_vjp(int t, const R* xprev, const R* theta, const R* v, R* out) {
+    for (int k = 0; k < D; ++k) {
+        R acc = 0;
+        for (int j = 0; j < D; ++j) acc = fma_(theta[j * D + k], v[j], acc);
+        out[k] = acc;
+    }
+}
+"""
+
+RARE_EVENT_GRAD = RARE_EVENT + r"""
+template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
+    if (t == (int)theta[0] - 1) gx[0] = (theta[1] - x[0]) / (theta[2] * theta[2]);
+}
+template <typename R, int D> __device__ void mean_vjp(int t, const R* xprev, const R* theta, const R* v, R* out) {
+    out[0] = theta[0] * v[0];
+}
+"""
+
+# d/dx_k [-(nu + 1) / 2 log1p(z^2 / nu)], z = (y_k - x_k) / s:  (nu + 1) z / (s (nu + z^2))
+STUDENT_T_GRAD = STUDENT_T + r"""
+template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
+    const R nu = theta[0], s = theta[1];
+    for (int k = 0; k < D; ++k) {
+        const R z = (y[k] - x[k]) / s;
+        gx[k] = (nu + (R)1) * z / (s * (nu + z * z));
+    }
+}
+"""
+
+# potential: z x / (10 sig) with z = (y - x^2 / 20) / sig;  mean: d/dv [v / 2 + 25 v / (1 + v^2)] = 1 / 2 + 25 (1 - v^2) / (1 + v^2)^2
+GROWTH_GRAD = GROWTH + r"""
+template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
+    const R z = (y[0] - x[0] * x[0] / (R)20) / theta[0];
+    gx[0] = z * x[0] / ((R)10 * theta[0]);
+}
+template <typename R, int D> __device__ void mean_vjp(int t, const R* xprev, const R* theta, const R* v, R* out) {
+    const R a = xprev[0], q = (R)1 + a * a;
+    out[0] = ((R)0.5 + (R)25 * ((R)1 - a * a) / (q * q)) * v[0];
+}
+"""
+
+# observed increments: y_t ~ N(x_t - x_{t-1}, s^2 I) (y_0 ~ N(x_0, s^2 I)), a potential of (x_t, x_{t-1}): theta = [s]
+INCREMENT_OBS_GRAD = r"""
+template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta) {
+    const R s = theta[0];
+    R acc = 0;
+    for (int k = 0; k < D; ++k) {
+        const R z = (y[k] - (xprev ? x[k] - xprev[k] : x[k])) / s;
+        acc += (R)-0.5 * (z * z) - log(s) - (R)0.91893853320467274178;
+    }
+    return acc;
+}
+template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta) {
+    return (R)D * (-log(theta[0]) - (R)0.91893853320467274178);
+}
+template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
+    const R s = theta[0];
+    for (int k = 0; k < D; ++k) {
+        const R z = (y[k] - (xprev ? x[k] - xprev[k] : x[k])) / s;
+        gx[k] = z / s;
+        if (gxprev) gxprev[k] = -z / s;
+    }
 }
 """

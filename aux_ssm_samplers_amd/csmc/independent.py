@@ -10,7 +10,8 @@ gradient=True with parallel=True: the proposals are shifted the same way and eve
 (independent.py:81-84, pit/csmc.py:83-88), per particle; time-varying dynamics are read row by row in both sweeps.
 gradient=True (classical sweep): proposals N(u_t + delta_t/2 grad_t, delta_t/2 I) with grad the gradient at u of the model's joint
 log-density (independent.py:121-134), which the reference gets from jax.grad and the device kernel evaluates in closed form for the
-model family (csrc/csmc.hip::k_csmc_grad).  gradient=True follows the reference to the letter: the importance correction of the shifted
+model family (csrc/csmc_sweep.h::k_csmc_grad), and from the derivatives a user-defined model's source supplies (DevicePotential.grad_log_g,
+DeviceGaussianDynamics.mean_vjp).  gradient=True follows the reference to the letter: the importance correction of the shifted
 proposal enters the weights at t = 0 (GradientAuxiliaryG0, :173-190) while for t >= 1 GradientAuxiliaryGt sums it over ALL particles
 (jnp.sum without an axis, :265-266), i.e. adds a constant that cancels -- no correction.  gradient="exact" applies the per-particle
 correction at every step (the weights the construction intends; AUXSSM_GRAD_EXACT)."""
@@ -30,7 +31,7 @@ from .generic import get_kernel as get_base_kernel, IndependentFactory
 class AuxiliaryMtDistribution(Distribution):
     """proposals N(u_t [+ delta_t / 2 grad_t], delta_t / 2 I): params = (u (T, d), sqrt(delta / 2) scalar or (T,), grad_pi or None)   (independent.py:202-225).
     A non-None third entry switches the gradient-informed proposals on; the device evaluates the gradient of the model's log-density at u itself
-    (csrc/csmc.hip::k_csmc_grad), the array's values are not read."""
+    (csrc/csmc_sweep.h::k_csmc_grad), the array's values are not read."""
     params: Any = None
 
 

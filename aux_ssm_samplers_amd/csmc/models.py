@@ -103,7 +103,10 @@ class DevicePotential(UnivariatePotential, Potential):
     and optionally  template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta)  (sup_x log G_t, or +inf).
     t = the time index of x (0 for G0); xprev = x_{t-1} (nullptr at t = 0); y = row t of the (T, p) observations (nullptr without); theta = `theta`.
     As G0 give y = ys[0]; as Gt give params = ys[1:], like the built-in potentials; G0 and Gt carry the same source and theta.  p: the number of
-    observation columns (default: inferred from y / params).  The code may call fma_, det_exp, det_log and the device math library (exp, log, lgamma, ...)."""
+    observation columns (default: inferred from y / params).  The code may call fma_, det_exp, det_log and the device math library (exp, log, lgamma, ...).
+    Gradient-informed proposals (get_independent_kernel(..., gradient=True / "exact")) also need its partial derivatives:
+        template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev);
+    gx (D) w.r.t. x, gxprev (D) w.r.t. xprev (nullptr at t = 0), both zero-filled by the caller."""
     source: str = ""
     y: Optional[Any] = None
     params: Optional[Any] = None
@@ -115,7 +118,9 @@ class DevicePotential(UnivariatePotential, Potential):
 class DeviceGaussianDynamics(Dynamics, Potential):
     """x_t | x_{t-1} ~ N(mean(x_{t-1}), Q) with the mean written as HIP device code (compiled at get_kernel time):
         template <typename R, int D> __device__ void mean(int t, const R* xprev, const R* theta, R* mu);
-    t = the time index of x_t.  Q (d, d) is time-invariant; the backward pass evaluates N(x_{t+1}; mean(x_t), Q) through the same code."""
+    t = the time index of x_t.  Q (d, d) is time-invariant; the backward pass evaluates N(x_{t+1}; mean(x_t), Q) through the same code.
+    Gradient-informed proposals also need the vector-Jacobian product of the mean, out = J^T v with J = d mean(t, xprev) / d xprev:
+        template <typename R, int D> __device__ void mean_vjp(int t, const R* xprev, const R* theta, const R* v, R* out);"""
     source: str = ""
     Q: Any = None
     theta: Optional[Any] = None

@@ -193,8 +193,8 @@ static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, const double* host
     return AUXSSM_OK;
 }
 
-// run_csmc with a user-defined model (fk_program.hip): the same launches, the forward / backward passes and the potential's bound from the program's
-// module.  Time-invariant transitions, no gradient (auxssm_csmc_sweep_program refuses the rest).
+// run_csmc with a user-defined model (fk_program.hip): the same launches, the forward / backward passes, the potential's bound and the gradient from the
+// program's module.  Time-invariant transitions; gradient proposals with a gradient program only (auxssm_csmc_sweep_program refuses the rest).
 static int fk_launch(auxssm_ctx* h, hipFunction_t f, unsigned grid, unsigned block, size_t lds, void** args) {
     if (lds > 48 * 1024) {  // (module functions have no hipFuncSetAttribute: their limit is what the device grants, checked here)
         int mx = 0;
@@ -215,6 +215,7 @@ static int run_csmc_program(auxssm_ctx* h, const auxssm_fk_program_s* prog, cons
     if (rc) return rc;
     FkDev<R> m;
     fill_model<R>(m, fk, host_model);
+    m.gradient = fk->gradient;
     FkUser<R> u{(const R*)user->y, (const R*)user->theta_g, (const R*)user->theta_m, user->p};
     const int TB = (a.N + 63) / 64 * 64;
     if (a.gb) {
@@ -230,16 +231,22 @@ static int run_csmc_program(auxssm_ctx* h, const auxssm_fk_program_s* prog, cons
     if (fk->proposal == 1) {
         const long long total = (long long)a.C * a.T * D;
         hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
+        if (fk->gradient) {
+            const long long tot = (long long)a.C * a.T;
+            void* args[] = {&a, &m, &u};
+            if ((rc = fk_launch(h, fn[FK_GRAD], (unsigned)((tot + 255) / 256), 256, 0, args))) return rc;
+        }
     }
     const int fullw = (TB == a.N && (a.N == 1024 || a.N == 512)) ? a.N / 64 : 0;
     const int sel = fullw == 16 ? 2 : (fullw == 8 ? 1 : 0);
+    const int fwd0 = m.gradient != 0 ? FK_FWDG0 : FK_FWD0;
     const int cb = a.cb > 0 ? a.cb : a.C;
     for (int c0 = 0; c0 < a.C; c0 += cb) {
         CsmcArgs ab = csmc_batch(a, c0, cb);
         void* args[] = {&ab, &m, &u};
         {
             ProfScope ps(h, AUXSSM_K_CSMC_FWD);
-            if ((rc = fk_launch(h, fn[FK_FWD0 + sel], (unsigned)ab.C, (unsigned)TB, fwd_lds(TB, D, sizeof(R)), args))) return rc;
+            if ((rc = fk_launch(h, fn[fwd0 + sel], (unsigned)ab.C, (unsigned)TB, fwd_lds(TB, D, sizeof(R)), args))) return rc;
         }
         {
             ProfScope ps(h, AUXSSM_K_CSMC_BWD);
@@ -357,8 +364,12 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
             set_error("the program was compiled for dtype %d, dx %d (sweep: dtype %d, dx %d)", prog->dtype, prog->dx, dtype, D);
             return AUXSSM_ERR_ARG;
         }
-        if (fk->F_t || fk->b_t || fk->chol_Q_t || fk->gradient != AUXSSM_GRAD_NONE) {
-            set_error("user-defined models run time-invariant transitions without gradient proposals");
+        if (fk->F_t || fk->b_t || fk->chol_Q_t) {
+            set_error("user-defined models run time-invariant transitions");
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+        if (fk->gradient != AUXSSM_GRAD_NONE && !(prog->flags & AUXSSM_FK_USER_GRADIENT)) {
+            set_error("gradient proposals need a program compiled with AUXSSM_FK_USER_GRADIENT (the derivatives of the user-defined parts)");
             return AUXSSM_ERR_UNSUPPORTED;
         }
         if (um && fk->transition != AUXSSM_TRANS_LINEAR) {

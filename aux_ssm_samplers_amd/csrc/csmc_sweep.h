@@ -177,6 +177,63 @@ template <typename R, int D> AXD_HD R potential(const FkDev<R>& m, const R* x, c
     }
     return acc;
 }
+// gx = d potential / dx at x (the closed family's potentials do not read x_{t-1}); y = the D reals of row t, or nullptr
+template <typename R, int D> __device__ __forceinline__ void potential_grad(const FkDev<R>& m, const R* x, const R* y, R* gx) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const R yk = y ? y[k] : (R)0;
+        R v = 0;
+        if (m.potential == 1 || (m.potential == 3 && yk - yk == 0)) v = ((yk - x[k]) * m.inv_sig_y) * m.inv_sig_y;
+        else if (m.potential == 2) {
+            const R e = det_exp(-x[k]);
+            v = (R)0.5 * fma_(yk * yk, e, (R)-1);
+            v = (v == v) ? v : (R)0;
+        }
+        gx[k] = v;
+    }
+}
+// out = J^T v, J = d mean / d xp of the transition tr (trans_mean_t): F^T, or the Lorenz-63 step's I + dt dphi/dx (examples/lorenz/model.py:10-25)
+template <typename R, int D> __device__ __forceinline__ void trans_mean_vjp_t(const FkDev<R>& m, const TransT<R>& tr, const R* xp, const R* v, R* out) {
+    if constexpr (D == 3) {
+        if (m.transition == 1) {
+            const R th1 = m.F[0], th2 = m.F[1], th3 = m.F[2], dt = m.b[0];
+            const R J[9] = {-th1, th1, (R)0, th2 - xp[2], (R)-1, -xp[0], xp[1], xp[0], -th3};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                R acc = 0;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc = fma_(J[j * 3 + k], v[j], acc);
+                out[k] = fma_(dt, acc, v[k]);
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        R acc = 0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) acc = fma_(tr.F[j * tr.ld + k], v[j], acc);
+        out[k] = acc;
+    }
+}
+// w <- (L L^T)^-1 r, L lower with leading dimension ld; fixed operation order (restated by oracle/csmc_ref.c::cho_solve_)
+template <typename R, int D> __device__ __forceinline__ void cho_solve_fixed(const R* L, int ld, const R* r, R* w) {
+    R z[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        R acc = r[k];
+#pragma unroll
+        for (int j = 0; j < k; ++j) acc = fma_(-L[k * ld + j], z[j], acc);
+        z[k] = acc / L[k * ld + k];
+    }
+#pragma unroll
+    for (int k = D - 1; k >= 0; --k) {
+        R acc = z[k];
+#pragma unroll
+        for (int j = k + 1; j < D; ++j) acc = fma_(-L[j * ld + k], w[j], acc);
+        w[k] = acc / L[k * ld + k];
+    }
+}
 
 // ---- block primitives (TB threads = NW waves) ---------------------------------------------------------------------
 template <typename R> __device__ __forceinline__ R wave_max(R v) {
@@ -499,12 +556,81 @@ template <typename R> struct FkUser {
 // The bodies below ask a policy object for the two model functions of a step:
 //   pol.log_g(m, t, x, xprev, y)     log G_t(x_t) (xprev = x_{t-1}, nullptr at t = 0; y = the D reals of row t of CsmcArgs::y)
 //   pol.mean(m, tr, t, xprev, mu)    the mean of x_t | x_{t-1} = xprev under the transition tr (t = the index of x_t)
+// and the gradient kernel (k_csmc_grad) for their derivatives:
+//   pol.grad_log_g(m, t, x, xprev, y, gx, gxprev)   gx = d log G_t / dx, gxprev = d log G_t / dxprev (nullptr at t = 0); both zero-filled by the caller
+//   pol.mean_vjp(m, tr, t, xprev, v, out)           out = J^T v, J = d pol.mean(m, tr, t, xprev) / d xprev
+//   P::grad_xprev                                   whether log G_t may depend on xprev (false: k_csmc_grad adds no d / dxprev term)
 // FkBuiltin is the closed family of include/auxssm.h, dispatched on the integers of FkDev (the kernels of csmc.hip); fk_user.h's FkUserPolicy calls
 // device functions of a user's source (fk_program.hip).  The backward pass evaluates the Gaussian transition density around pol.mean.
 template <typename R, int D> struct FkBuiltin {
+    static constexpr bool grad_xprev = false;
     __device__ __forceinline__ R log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y) const { return potential<R, D>(m, x, y); }
     __device__ __forceinline__ void mean(const FkDev<R>& m, const TransT<R>& tr, int, const R* xp, R* mu) const { trans_mean_t<R, D>(m, tr, xp, mu); }
+    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y, R* gx, R*) const { potential_grad<R, D>(m, x, y, gx); }
+    __device__ __forceinline__ void mean_vjp(const FkDev<R>& m, const TransT<R>& tr, int, const R* xp, const R* v, R* out) const {
+        trans_mean_vjp_t<R, D>(m, tr, xp, v, out);
+    }
 };
+
+// gradient at u of  log M0(u_0) + G0(u_0) + sum_t [log Mt(u_{t+1} | u_t) + Gt(u_{t+1}, u_t)]  (csmc/independent.py:121-134, jax.grad there), one thread per
+// (chain, time step):  d_x log G_t(u_t, u_{t-1}) [+ d_xprev log G_{t+1}(u_{t+1}, u_t)] - Q^-1 (u_t - mean_t(u_{t-1})) + J_{t+1}(u_t)^T Q^-1 (u_{t+1} - mean_{t+1}(u_t))
+// (t = 0: the prior term -P0^-1 (u_0 - m0); t = T - 1: no t + 1 terms).  The d_xprev term only exists for a policy whose potential may read xprev, and is
+// added to the d_x term before anything else: a potential that leaves it at zero gives the built-in gradient bit for bit.
+template <typename R, int D, typename P = FkBuiltin<R, D>, typename... PA> __global__ void k_csmc_grad(CsmcArgs a, FkDev<R> m, PA... pa) {
+    const P pol{pa...};
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (long long)a.C * a.T) return;
+    const long long t = g % a.T;
+    const R* u = (const R*)a.u + g * D;
+    R ut[D], gr[D], r[D], w[D], mu[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) ut[k] = u[k];
+    const R* yv = (const R*)a.y;
+    // potential
+    {
+        R gp[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) gr[k] = gp[k] = (R)0;
+        pol.grad_log_g(m, (int)t, ut, t > 0 ? u - D : nullptr, yv ? yv + t * D : nullptr, gr, t > 0 ? gp : nullptr);
+        if constexpr (P::grad_xprev) {
+            if (t + 1 < a.T) {  // log G_{t+1}(u_{t+1}, u_t) as a function of u_t
+                R gn[D], gq[D];
+#pragma unroll
+                for (int k = 0; k < D; ++k) gn[k] = gq[k] = (R)0;
+                pol.grad_log_g(m, (int)t + 1, u + D, ut, yv ? yv + (t + 1) * D : nullptr, gn, gq);
+#pragma unroll
+                for (int k = 0; k < D; ++k) gr[k] = gr[k] + gq[k];
+            }
+        }
+    }
+    // density of u_t given the past
+    if (t == 0) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) r[k] = ut[k] - m.m0[k];
+        cho_solve_fixed<R, D>(m.LP0, CS_MAXD, r, w);
+    } else {
+        const TransT<R> tr = trans_at<R, D>(m, t - 1);
+        pol.mean(m, tr, (int)t, u - D, mu);
+#pragma unroll
+        for (int k = 0; k < D; ++k) r[k] = ut[k] - mu[k];
+        cho_solve_fixed<R, D>(tr.LQ, tr.ld, r, w);
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) gr[k] = gr[k] - w[k];
+    // density of u_{t+1} given u_t:  J(u_t)^T Q^-1 (u_{t+1} - mean(u_t))
+    if (t + 1 < a.T) {
+        const TransT<R> tr = trans_at<R, D>(m, t);
+        pol.mean(m, tr, (int)t + 1, ut, mu);
+#pragma unroll
+        for (int k = 0; k < D; ++k) r[k] = u[D + k] - mu[k];
+        cho_solve_fixed<R, D>(tr.LQ, tr.ld, r, w);
+        pol.mean_vjp(m, tr, (int)t + 1, ut, w, mu);  // (mu: J^T w)
+#pragma unroll
+        for (int k = 0; k < D; ++k) gr[k] = gr[k] + mu[k];
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) ((R*)a.grad)[g * D + k] = gr[k];
+}
 
 // gb[t] = sup_x G_t(x): the reduction-free part of the forward weights' shift (sweep contract, csmc_dev.h); +inf where the potential is unbounded
 template <typename R, int D> __global__ void k_csmc_potbound(int T, FkDev<R> m, const R* __restrict__ y, R* __restrict__ gb) {

@@ -92,7 +92,7 @@ template <typename R> __global__ void k_cw_ctrans(int n, int D, const R* __restr
     }
     ct[t] = c - (R)D * (R)0.91893853320467274178;
 }
-// w <- (L L^T)^-1 r (csmc_dev.h::cho_solve_fixed, runtime dimension, leading dimension D)
+// w <- (L L^T)^-1 r (csmc_sweep.h::cho_solve_fixed, runtime dimension, leading dimension D)
 template <typename R> __device__ __forceinline__ void cho_solve_w(int D, const R* L, const R* r, R* w) {
     R z[CSW_MAXD];
     for (int k = 0; k < D; ++k) {
@@ -106,7 +106,7 @@ template <typename R> __device__ __forceinline__ void cho_solve_w(int D, const R
         w[k] = acc / L[k * D + k];
     }
 }
-// the gradient of the model's joint log-density at u (csmc_dev.h::k_csmc_grad, same operations in the same order; one thread per (chain, time step):
+// the gradient of the model's joint log-density at u (csmc_sweep.h::k_csmc_grad, same operations in the same order; one thread per (chain, time step):
 // C T threads of O(dx^2) work, once per sweep -- 0.5 M multiply-adds at the SV protocol's size)
 template <typename R> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;

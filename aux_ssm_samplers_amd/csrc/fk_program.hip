@@ -43,7 +43,7 @@ int fk_program_functions(auxssm_ctx* h, const auxssm_fk_program_s* p, const hipF
     FkModules::Entry e{};
     e.id = p->id;
     AX_HIP(hipModuleLoadData(&e.mod, p->code.data()));
-    for (int i = 0; i < FK_NFUNC; ++i) {
+    for (int i = 0; i < p->nfunc; ++i) {
         const hipError_t rc = hipModuleGetFunction(&e.f[i], e.mod, p->lowered[i].c_str());
         if (rc != hipSuccess) {
             (void)hipModuleUnload(e.mod);
@@ -83,11 +83,11 @@ extern "C" int auxssm_fk_program_compile(const char* source, const char* include
         set_error("dx=%d: user-defined models run the sequential kernels of 1 <= dx <= %d", dx, CS_MAXD);
         return AUXSSM_ERR_UNSUPPORTED;
     }
-    if (flags & ~(AUXSSM_FK_USER_POTENTIAL | AUXSSM_FK_USER_MEAN) || !flags) {
-        set_error("flags must be a non-empty set of AUXSSM_FK_USER_POTENTIAL | AUXSSM_FK_USER_MEAN (got %d)", flags);
+    if (flags & ~(AUXSSM_FK_USER_POTENTIAL | AUXSSM_FK_USER_MEAN | AUXSSM_FK_USER_GRADIENT) || !(flags & (AUXSSM_FK_USER_POTENTIAL | AUXSSM_FK_USER_MEAN))) {
+        set_error("flags must be a non-empty set of AUXSSM_FK_USER_POTENTIAL | AUXSSM_FK_USER_MEAN, optionally | AUXSSM_FK_USER_GRADIENT (got %d)", flags);
         return AUXSSM_ERR_ARG;
     }
-    const bool ug = flags & AUXSSM_FK_USER_POTENTIAL, um = flags & AUXSSM_FK_USER_MEAN;
+    const bool ug = flags & AUXSSM_FK_USER_POTENTIAL, um = flags & AUXSSM_FK_USER_MEAN, gr = flags & AUXSSM_FK_USER_GRADIENT;
     // #line: hipRTC's diagnostics count the lines of the user's source
     const std::string src = std::string("#include \"fk_user_pre.h\"\n#line 1 \"model.hip\"\n") + source + "\n#include \"fk_user.h\"\n";
     const std::string R = dtype == AUXSSM_F32 ? "float" : "double", Ds = std::to_string(dx);
@@ -98,16 +98,25 @@ extern "C" int auxssm_fk_program_compile(const char* source, const char* include
     for (int i = 0; i < 3; ++i) {
         names[FK_FWD0 + i] = "ax::k_csmc_fwd<" + R + ", " + Ds + ", false, false, " + std::to_string(nws[i]) + ", 0, " + P + ", " + U + ">";
         names[FK_BWD0 + i] = "ax::k_csmc_bwd<" + R + ", " + Ds + ", false, " + std::to_string(nws[i]) + ", " + P + ", " + U + ">";
+        if (gr) names[FK_FWDG0 + i] = "ax::k_csmc_fwd<" + R + ", " + Ds + ", false, true, " + std::to_string(nws[i]) + ", 0, " + P + ", " + U + ">";
     }
     names[FK_BOUND] = "ax::k_fk_bound<" + R + ", " + Ds + ", " + (ug ? "ax::fk_has_bound<" + R + ", " + Ds + ">::value" : std::string("false")) + ">";
     names[FK_BOUND_TRUE] = "ax::k_fk_bound<" + R + ", " + Ds + ", true>";
+    if (gr) {
+        names[FK_GRAD] = "ax::k_csmc_grad<" + R + ", " + Ds + ", " + P + ", " + U + ">";
+        names[FK_PROBE_G] = "ax::k_fk_probe<" + R + ", " + Ds + ", 0, ax::fk_has_grad_log_g<" + R + ", " + Ds + ">::value>";
+        names[FK_PROBE_G_TRUE] = "ax::k_fk_probe<" + R + ", " + Ds + ", 0, true>";
+        names[FK_PROBE_M] = "ax::k_fk_probe<" + R + ", " + Ds + ", 1, ax::fk_has_mean_vjp<" + R + ", " + Ds + ">::value>";
+        names[FK_PROBE_M_TRUE] = "ax::k_fk_probe<" + R + ", " + Ds + ", 1, true>";
+    }
 
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), "fk_program.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
         set_error("hiprtcCreateProgram failed");
         return AUXSSM_ERR_HIP;
     }
-    for (auto& n : names) hiprtcAddNameExpression(prog, n.c_str());
+    for (auto& n : names)
+        if (!n.empty()) hiprtcAddNameExpression(prog, n.c_str());  // (a program without AUXSSM_FK_USER_GRADIENT: the kernels of the plain sweep only)
     const std::string inc = std::string("-I") + include_dir;
     const std::string dg = std::string("-DAXFK_USER_G=") + (ug ? "1" : "0"), dm = std::string("-DAXFK_USER_M=") + (um ? "1" : "0");
     const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(), dg.c_str(), dm.c_str()};
@@ -129,8 +138,10 @@ extern "C" int auxssm_fk_program_compile(const char* source, const char* include
     p->dtype = dtype;
     p->dx = dx;
     p->flags = flags;
+    p->nfunc = gr ? FK_NFUNC : FK_NFUNC_PLAIN;
     std::string lowered[FK_NNAMES];
     for (int i = 0; i < FK_NNAMES; ++i) {
+        if (names[i].empty()) continue;
         const char* low = nullptr;
         if (hiprtcGetLoweredName(prog, names[i].c_str(), &low) != HIPRTC_SUCCESS || !low) {
             hiprtcDestroyProgram(&prog);
@@ -143,6 +154,19 @@ extern "C" int auxssm_fk_program_compile(const char* source, const char* include
     }
     // k_fk_bound<R, D, fk_has_bound<R, D>::value> IS k_fk_bound<R, D, true> exactly when the source defines log_g_bound (a user potential only)
     p->has_bound = ug && lowered[FK_BOUND] == lowered[FK_BOUND_TRUE];
+    // a gradient program needs the derivative of every user-defined part (the same comparison: the probe with the detected value IS its `true` twin)
+    std::string missing;
+    if (gr && ug && lowered[FK_PROBE_G] != lowered[FK_PROBE_G_TRUE])
+        missing += "  template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev)";
+    if (gr && um && lowered[FK_PROBE_M] != lowered[FK_PROBE_M_TRUE])
+        missing += "  template <typename R, int D> __device__ void mean_vjp(int t, const R* xprev, const R* theta, const R* v, R* out)";
+    if (!missing.empty()) {
+        hiprtcDestroyProgram(&prog);
+        delete p;
+        set_error("gradient-informed proposals differentiate the user-defined model parts; the source must define (it lacks them, or has another signature):%s",
+                  missing.c_str());
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
     size_t cs = 0;
     if (hiprtcGetCodeSize(prog, &cs) != HIPRTC_SUCCESS || !cs) {
         hiprtcDestroyProgram(&prog);

@@ -341,12 +341,21 @@ int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_model* model, 
  *   template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta);                             [optional: sup_x log G_t]
  *   template <typename R, int D> __device__ void mean(int t, const R* xprev, const R* theta, R* mu);                      [AUXSSM_FK_USER_MEAN]
  * (t = the time index of x, resp. of x_t; xprev = x_{t-1}, NULL at t = 0; y = row t of auxssm_fk_user::y or NULL; theta = theta_g / theta_m).
+ * With AUXSSM_FK_USER_GRADIENT the program also holds the gradient-informed sweep (model->gradient != AUXSSM_GRAD_NONE), and the source must
+ * define the derivative of each user-defined part (a built-in part keeps its closed form):
+ *   template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev);
+ *       the partial derivatives of log_g w.r.t. x (gx, D) and xprev (gxprev, D; NULL at t = 0), both zero-filled by the caller   [user potential]
+ *   template <typename R, int D> __device__ void mean_vjp(int t, const R* xprev, const R* theta, const R* v, R* out);
+ *       out = J^T v, J = d mean(t, xprev) / d xprev                                                                           [user mean]
+ * A missing derivative (or one of another signature) returns AUXSSM_ERR_UNSUPPORTED.  The gradient at u is then
+ *   d_x log G_t(u_t, u_{t-1}) + d_xprev log G_{t+1}(u_{t+1}, u_t) - Q^-1 (u_t - mean_t(u_{t-1})) + J_{t+1}(u_t)^T Q^-1 (u_{t+1} - mean_{t+1}(u_t)).
  * What the flags leave to the built-in family comes from `model` as in auxssm_csmc_sweep.  include_dir: the directory of csmc_sweep.h.  On a
  * compile error `log` (log_len bytes) receives hipRTC's log and the call returns AUXSSM_ERR_ARG.  dx 1..4.
  * auxssm_csmc_sweep_program: auxssm_csmc_sweep (same arguments, validation, workspace and chain batching) with the program's model; the module is
- * loaded once per handle.  Not covered: time-varying transitions (F_t) and gradient proposals (AUXSSM_ERR_UNSUPPORTED). */
+ * loaded once per handle.  Not covered: time-varying transitions (F_t), and gradient proposals with a program compiled without
+ * AUXSSM_FK_USER_GRADIENT (AUXSSM_ERR_UNSUPPORTED). */
 typedef struct auxssm_fk_program_s* auxssm_fk_program;
-typedef enum { AUXSSM_FK_USER_POTENTIAL = 1, AUXSSM_FK_USER_MEAN = 2 } auxssm_fk_program_flag;
+typedef enum { AUXSSM_FK_USER_POTENTIAL = 1, AUXSSM_FK_USER_MEAN = 2, AUXSSM_FK_USER_GRADIENT = 4 } auxssm_fk_program_flag;
 typedef struct {
     const void* y;        /* device (T, p) of dtype, shared by all chains, or NULL */
     const void* theta_g;  /* device, the potential's parameters, or NULL */
