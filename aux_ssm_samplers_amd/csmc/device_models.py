@@ -1,8 +1,8 @@
 """Example models written as device code for DevicePotential / DeviceGaussianDynamics (csmc.models; contract in csrc/fk_user_pre.h).
 
-BUILTIN_*: the built-in potentials / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc.hip::k_csmc_potbound written as user source, in the
+BUILTIN_*: the built-in potentials / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc_host.h::k_csmc_potbound written as user source, in the
 built-in operation order (fma_, det_exp, det_log), so that a program sweep reproduces the closed-family sweep bit for bit (the tests and
-tools/fk_program_bench.py use them).  The constants the host computes for the built-ins (csmc_dev.h::fill_model) are formed the same way on
+tools/fk_program_bench.py use them).  The constants the host computes for the built-ins (csmc_host.h::fk_model) are formed the same way on
 the device from theta = [sig].  RARE_EVENT, STUDENT_T, GROWTH: models the closed family cannot express.
 
 *_GRAD / *_VJP: the same sources with the derivatives that gradient-informed proposals need (grad_log_g for a potential, mean_vjp for a mean;

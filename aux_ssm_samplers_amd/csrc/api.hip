@@ -257,13 +257,6 @@ static int check_dims(const auxssm_dims* d, bool need_dy) {
     }
     return AUXSSM_OK;
 }
-static int check_dtype(int dtype) {
-    if (dtype != AUXSSM_F32 && dtype != AUXSSM_F64) {
-        set_error("dtype must be AUXSSM_F32 (0) or AUXSSM_F64 (1), got %d", dtype);
-        return AUXSSM_ERR_ARG;
-    }
-    return AUXSSM_OK;
-}
 static int check_lgssm(const auxssm_lgssm* g, int T) {
     if (!g) {
         set_error("lgssm is NULL");
@@ -1638,22 +1631,6 @@ int auxssm_destroy(auxssm_handle h) {
     delete h;
     return AUXSSM_OK;
 }
-
-#define AX_NEED_H(h)                         \
-    do {                                     \
-        if (!(h)) {                          \
-            set_error("handle is NULL");     \
-            return AUXSSM_ERR_ARG;           \
-        }                                    \
-        AX_HIP(hipSetDevice((h)->device));   \
-        ++(h)->api_calls;                    \
-    } while (0)
-// entry points that neither enqueue work nor change device data (ctx.h: SideStage::last_call)
-#define AX_NEED_H_RO(h)                      \
-    do {                                     \
-        AX_NEED_H(h);                        \
-        --(h)->api_calls;                    \
-    } while (0)
 
 int auxssm_sync(auxssm_handle h) {
     AX_NEED_H_RO(h);

@@ -11,10 +11,10 @@
 // -> normalise.  xs, log_ws, As stream to HBM with the particle index fastest (coalesced).
 //
 // Reduction orders (the contract the oracle restates, SURVEY 7 "bit-exact ancestors"): the sweep kernels follow the "sweep contract"
-// of csmc_dev.h (unnormalised weights exp(lw - max), the hardware's DPP scan order, two-level search, ballot-counted single draw);
+// of csmc_sweep.h (unnormalised weights exp(lw - max), the hardware's DPP scan order, two-level search, ballot-counted single draw);
 // the standalone primitives (normalize / multinomial / systematic) and the parallel-in-time sweep keep the Kogge-Stone-in-64 cumsum,
-// the balanced-tree-in-64 sum and the plain binary search of csmc_dev.h.
-#include "csmc_dev.h"
+// the balanced-tree-in-64 sum and the plain binary search of csmc_sweep.h.
+#include "csmc_host.h"
 #include "fk_program.h"
 
 namespace ax {
@@ -100,32 +100,13 @@ __global__ void __launch_bounds__(1024) k_systematic(int M, int N, const R* __re
 // dynamic LDS of the forward / backward pass (csmc_sweep.h: k_csmc_fwd, k_csmc_bwd) for TB lanes
 static size_t fwd_lds(int TB, int D, size_t sR) { return (size_t)2 * (cpad(TB) + TB * D) * sR + 48 * sR + 64; }
 static size_t bwd_lds(int TB, int D, size_t sR) { return (size_t)2 * TB * sR + 64 * sR + (size_t)2 * TB * D * sR + 2 * sR + 64; }
-// the arguments of the batch [c0, c0 + cb) of chains (CsmcArgs::c0)
-static CsmcArgs csmc_batch(const CsmcArgs& a, int c0, int cb) {
-    CsmcArgs ab = a;
-    ab.c0 = c0;
-    ab.C = a.C - c0 < cb ? a.C - c0 : cb;
-    ab.xs = (char*)a.xs - (size_t)c0 * a.xs_rec;
-    ab.lws = (char*)a.lws - (size_t)c0 * a.lws_rec;
-    if (a.As) ab.As = (int32_t*)((char*)a.As - (size_t)c0 * a.As_rec);
-    return ab;
-}
 
 template <typename R, int D>
-static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, const double* host_model, CsmcArgs& a, void* ctt) {
-    FkDev<R> m;
-    fill_model<R>(m, fk, host_model);
-    m.gradient = fk->gradient;
+static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void* ctt) {
+    FkDev<R> m = fk_dev<R>(fk);
     const int TB = (a.N + 63) / 64 * 64;
-    if (fk->F_t && a.T > 1) {
-        m.Ft = (const R*)fk->F_t;
-        m.bt = (const R*)fk->b_t;
-        m.LQt = (const R*)fk->chol_Q_t;
-        m.ctt = (const R*)ctt;
-        m.idt = (const R*)ctt + (a.T - 1);  // (the caller sizes ctt for (T - 1) (1 + D) reals)
-        hipLaunchKernelGGL((k_csmc_ctrans<R, D>), dim3((a.T - 1 + 255) / 256), dim3(256), 0, h->stream, a.T - 1, m.LQt, (R*)ctt, (R*)ctt + (a.T - 1));
-    }
-    if (a.gb) hipLaunchKernelGGL((k_csmc_potbound<R, D>), dim3((a.T + 255) / 256), dim3(256), 0, h->stream, a.T, m, (const R*)a.y, (R*)a.gb);
+    fk_time_varying<R>(h, fk, a.T, ctt, m);
+    if (a.gb) fk_potbound<R>(h, a, m);
     if (fk->proposal == 1) {
         const long long total = (long long)a.C * a.T * D;
         hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
@@ -208,14 +189,11 @@ static int fk_launch(auxssm_ctx* h, hipFunction_t f, unsigned grid, unsigned blo
     return AUXSSM_OK;
 }
 template <typename R, int D>
-static int run_csmc_program(auxssm_ctx* h, const auxssm_fk_program_s* prog, const auxssm_fk_model* fk, const double* host_model, const auxssm_fk_user* user,
-                            CsmcArgs& a) {
+static int run_csmc_program(auxssm_ctx* h, const auxssm_fk_program_s* prog, const auxssm_fk_model* fk, const auxssm_fk_user* user, CsmcArgs& a) {
     const hipFunction_t* fn = nullptr;
     int rc = fk_program_functions(h, prog, &fn);
     if (rc) return rc;
-    FkDev<R> m;
-    fill_model<R>(m, fk, host_model);
-    m.gradient = fk->gradient;
+    FkDev<R> m = fk_dev<R>(fk);
     FkUser<R> u{(const R*)user->y, (const R*)user->theta_g, (const R*)user->theta_m, user->p};
     const int TB = (a.N + 63) / 64 * 64;
     if (a.gb) {
@@ -225,7 +203,7 @@ static int run_csmc_program(auxssm_ctx* h, const auxssm_fk_program_s* prog, cons
             void* args[] = {&T, &u, &gb};
             if ((rc = fk_launch(h, fn[FK_BOUND], (unsigned)((a.T + 255) / 256), 256, 0, args))) return rc;
         } else {
-            hipLaunchKernelGGL((k_csmc_potbound<R, D>), dim3((a.T + 255) / 256), dim3(256), 0, h->stream, a.T, m, (const R*)a.y, (R*)a.gb);
+            fk_potbound<R>(h, a, m);
         }
     }
     if (fk->proposal == 1) {
@@ -266,16 +244,8 @@ using namespace ax;
 
 extern "C" int auxssm_normalize_resample(auxssm_handle h, int dtype, int32_t rows, int32_t N, const void* log_weights,
                                          const void* weights, const void* uniforms, void* weights_out, int32_t* indices) {
-    if (!h) {
-        set_error("handle is NULL");
-        return AUXSSM_ERR_ARG;
-    }
-    AX_HIP(hipSetDevice(h->device));
-    ++h->api_calls;
-    if (dtype != AUXSSM_F32 && dtype != AUXSSM_F64) {
-        set_error("dtype must be 0 (f32) or 1 (f64)");
-        return AUXSSM_ERR_ARG;
-    }
+    AX_NEED_H(h);
+    if (int rc = check_dtype(dtype)) return rc;
     if (rows < 1 || N < 1 || N > 1024) {
         set_error("need rows >= 1 and 1 <= N <= 1024");
         return AUXSSM_ERR_ARG;
@@ -301,16 +271,8 @@ extern "C" int auxssm_normalize_resample(auxssm_handle h, int dtype, int32_t row
 
 extern "C" int auxssm_systematic_resample(auxssm_handle h, int dtype, int32_t rows, int32_t M, int32_t N, const void* weights, const void* uvw,
                                           int32_t* indices) {
-    if (!h) {
-        set_error("handle is NULL");
-        return AUXSSM_ERR_ARG;
-    }
-    AX_HIP(hipSetDevice(h->device));
-    ++h->api_calls;
-    if (dtype != AUXSSM_F32 && dtype != AUXSSM_F64) {
-        set_error("dtype must be 0 (f32) or 1 (f64)");
-        return AUXSSM_ERR_ARG;
-    }
+    AX_NEED_H(h);
+    if (int rc = check_dtype(dtype)) return rc;
     if (rows < 1 || M < 1 || M > 1024 || N < 1 || N > 1024) {
         set_error("need rows >= 1, 1 <= M <= 1024 weights and 1 <= N <= 1024 draws");
         return AUXSSM_ERR_ARG;
@@ -334,16 +296,8 @@ extern "C" int auxssm_systematic_resample(auxssm_handle h, int dtype, int32_t ro
 static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk, const auxssm_fk_program_s* prog, const auxssm_fk_user* user, int32_t C,
                            int32_t T, int32_t N, int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise, int32_t* ancestors,
                            void* xs_out, void* log_ws_out, int32_t* As_out) {
-    if (!h) {
-        set_error("handle is NULL");
-        return AUXSSM_ERR_ARG;
-    }
-    AX_HIP(hipSetDevice(h->device));
-    ++h->api_calls;
-    if (dtype != AUXSSM_F32 && dtype != AUXSSM_F64) {
-        set_error("dtype must be 0 (f32) or 1 (f64)");
-        return AUXSSM_ERR_ARG;
-    }
+    AX_NEED_H(h);
+    if (int rc = check_dtype(dtype)) return rc;
     if (!fk || !x || !noise || !ancestors) {
         set_error("model/x/noise/ancestors must be non-NULL");
         return AUXSSM_ERR_ARG;
@@ -393,64 +347,19 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
         set_error("unknown proposal kind %d", fk->proposal);
         return AUXSSM_ERR_ARG;
     }
-    if (fk->potential < AUXSSM_POT_FLAT || fk->potential > AUXSSM_POT_GAUSS_OBS_MASKED) {
-        set_error("unknown potential kind %d", fk->potential);
-        return AUXSSM_ERR_ARG;
-    }
-    if (!fk->m0 || !fk->chol_P0 || !fk->F || !fk->b || !fk->chol_Q) {
-        set_error("model has a NULL m0/chol_P0/F/b/chol_Q host pointer");
-        return AUXSSM_ERR_ARG;
-    }
-    if (!ug && fk->potential != AUXSSM_POT_FLAT && !fk->y) {
-        set_error("potential needs observations y");
-        return AUXSSM_ERR_ARG;
-    }
-    if (fk->potential == AUXSSM_POT_GAUSS_OBS && !(fk->sig_y > 0)) {
-        set_error("sig_y must be > 0");
-        return AUXSSM_ERR_ARG;
-    }
+    if (int rc = check_fk_model(fk, noise, ug)) return rc;
     if (fk->proposal == AUXSSM_PROP_AUX_INDEPENDENT && !sqrt_half_delta) {
         set_error("the auxiliary proposal needs sqrt_half_delta (T)");
-        return AUXSSM_ERR_ARG;
-    }
-    {
-        const int ntv = (fk->F_t != nullptr) + (fk->b_t != nullptr) + (fk->chol_Q_t != nullptr);
-        if (ntv != 0 && ntv != 3) {
-            set_error("time-varying transitions need F_t, b_t and chol_Q_t together");
-            return AUXSSM_ERR_ARG;
-        }
-        if (ntv && fk->transition != AUXSSM_TRANS_LINEAR) {
-            set_error("time-varying parameters are for the linear transition only");
-            return AUXSSM_ERR_ARG;
-        }
-    }
-    if (fk->gradient != AUXSSM_GRAD_NONE && fk->gradient != AUXSSM_GRAD_REFERENCE && fk->gradient != AUXSSM_GRAD_EXACT) {
-        set_error("unknown gradient mode %d", fk->gradient);
         return AUXSSM_ERR_ARG;
     }
     if (fk->gradient != AUXSSM_GRAD_NONE && fk->proposal != AUXSSM_PROP_AUX_INDEPENDENT) {
         set_error("gradient-informed proposals belong to AUXSSM_PROP_AUX_INDEPENDENT");
         return AUXSSM_ERR_ARG;
     }
-    if (noise->mode == AUXSSM_NOISE_EXPLICIT) {
-        if (!noise->eps_prop || !noise->u_bwd || (T > 1 && !noise->u_res) ||
-            (fk->proposal == AUXSSM_PROP_AUX_INDEPENDENT && !noise->eps_aux)) {
-            set_error("explicit noise needs eps_prop, u_res, u_bwd (and eps_aux for the auxiliary proposal)");
-            return AUXSSM_ERR_ARG;
-        }
-    } else if (noise->mode != AUXSSM_NOISE_THREEFRY) {
-        set_error("unknown noise mode %d", noise->mode);
+    if (noise->mode == AUXSSM_NOISE_EXPLICIT &&
+        (!noise->eps_prop || !noise->u_bwd || (T > 1 && !noise->u_res) || (fk->proposal == AUXSSM_PROP_AUX_INDEPENDENT && !noise->eps_aux))) {
+        set_error("explicit noise needs eps_prop, u_res, u_bwd (and eps_aux for the auxiliary proposal)");
         return AUXSSM_ERR_ARG;
-    }
-    // host-side model parameters (doubles): m0 | chol_P0 | F | b | chol_Q
-    std::vector<double> hm((size_t)2 * D + 3 * D * D);
-    {
-        double* p = hm.data();
-        memcpy(p, fk->m0, D * sizeof(double)); p += D;
-        memcpy(p, fk->chol_P0, D * D * sizeof(double)); p += D * D;
-        memcpy(p, fk->F, D * D * sizeof(double)); p += D * D;
-        memcpy(p, fk->b, D * sizeof(double)); p += D;
-        memcpy(p, fk->chol_Q, D * D * sizeof(double));
     }
     const size_t sR = dtype == AUXSSM_F32 ? 4 : 8;
     const size_t CT = (size_t)C * T;
@@ -489,7 +398,7 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
     need += 2 * (CT * sR + 256);  // fmax, the backward pass's uniforms
     need += (size_t)T * sR + 256;  // gb
     need += 2 * (CT * D * sR + 256) + (size_t)T * (1 + D) * sR + 256;
-    // fewer chains than CUs: the forward pass's draws are generated up front by the whole chip (csmc_dev.h::k_csmc_pregen) when the two arrays fit
+    // fewer chains than CUs: the forward pass's draws are generated up front by the whole chip (csmc_sweep.h::k_csmc_pregen) when the two arrays fit
     const size_t pre_eps = CT * N * D * sR + 256, pre_u = (size_t)C * (T > 1 ? T - 1 : 1) * N * sR + 256;
     bool pregen = noise->mode == AUXSSM_NOISE_THREEFRY && !wide && T > 1 && C < h->num_cu && cb == C &&
                   !getenv("AUXSSM_CSMC_NO_PREGEN");  // test hook: tests/test_gpu_csmc.py and tests/test_gpu_full_size.py force the in-pass draws
@@ -519,7 +428,7 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
     a.noise_mode = noise->mode;
     a.key0 = noise->key0; a.key1 = noise->key1;
     a.eps_aux = noise->eps_aux; a.eps_prop = noise->eps_prop; a.u_res = noise->u_res; a.u_bwd = noise->u_bwd;
-    if (noise->mode == AUXSSM_NOISE_THREEFRY) {  // the backward pass's uniforms, drawn once (csmc_dev.h::k_csmc_ubwd)
+    if (noise->mode == AUXSSM_NOISE_THREEFRY) {  // the backward pass's uniforms, drawn once (csmc_sweep.h::k_csmc_ubwd)
         void* ub = ws_take(h, CT * sR);
         if (!ub) return AUXSSM_ERR_NOMEM;
         const long long n = (long long)CT;
@@ -542,26 +451,11 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
         a.u_res = pu;
     }
     if (wide) return run_csmc_wide(h, dtype, fk, a, ctt);
-    if (prog) {
-#define AX_CSMC_P(R)                                                                 \
-    switch (D) {                                                                     \
-        case 1: return run_csmc_program<R, 1>(h, prog, fk, hm.data(), user, a);     \
-        case 2: return run_csmc_program<R, 2>(h, prog, fk, hm.data(), user, a);     \
-        case 3: return run_csmc_program<R, 3>(h, prog, fk, hm.data(), user, a);     \
-        default: return run_csmc_program<R, 4>(h, prog, fk, hm.data(), user, a);    \
-    }
-        if (dtype == AUXSSM_F32) { AX_CSMC_P(float) } else { AX_CSMC_P(double) }
-#undef AX_CSMC_P
-    }
-#define AX_CSMC_D(R)                                                        \
-    switch (D) {                                                            \
-        case 1: return run_csmc<R, 1>(h, fk, hm.data(), a, ctt);                 \
-        case 2: return run_csmc<R, 2>(h, fk, hm.data(), a, ctt);                 \
-        case 3: return run_csmc<R, 3>(h, fk, hm.data(), a, ctt);                 \
-        default: return run_csmc<R, 4>(h, fk, hm.data(), a, ctt);                \
-    }
-    if (dtype == AUXSSM_F32) { AX_CSMC_D(float) } else { AX_CSMC_D(double) }
-#undef AX_CSMC_D
+    return csmc_dispatch(dtype, D, [&](auto r, auto d) {
+        using R = decltype(r);
+        constexpr int DD = decltype(d)::value;
+        return prog ? run_csmc_program<R, DD>(h, prog, fk, user, a) : run_csmc<R, DD>(h, fk, a, ctt);
+    });
 }
 
 extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_model* fk, int32_t C, int32_t T, int32_t N,

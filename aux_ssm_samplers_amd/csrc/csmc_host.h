@@ -1,0 +1,172 @@
+// csmc_host.h -- the host side the conditional-SMC drivers share (csmc.hip: the sequential sweep, built-in and user-defined models; csmc_wide.hip: the
+// wide-state sweep; pit.hip: the parallel-in-time sweep): the model checks of both entry points, the model in precision R, the time-varying setup, the two
+// per-sweep kernels of the model (transition constants, potential bound), chain batching and the dtype x dx dispatch.  hipcc only (the device side,
+// csmc_sweep.h, also compiles under hipRTC).  Units including this are compiled with -ffp-contract=off.
+#pragma once
+#include <cstring>
+#include <type_traits>
+
+#include "ctx.h"
+#include "csmc_sweep.h"
+
+namespace ax {
+
+// the model checks auxssm_csmc_sweep(_program) and auxssm_csmc_pit_sweep share; each entry point adds its own (proposals, dimensions, the explicit noise
+// arrays it reads).  user_potential: the potential is a program's, which brings its own observations
+static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* noise, bool user_potential) {
+    if (fk->potential < AUXSSM_POT_FLAT || fk->potential > AUXSSM_POT_GAUSS_OBS_MASKED) {
+        set_error("unknown potential kind %d", fk->potential);
+        return AUXSSM_ERR_ARG;
+    }
+    if (!fk->m0 || !fk->chol_P0 || !fk->F || !fk->b || !fk->chol_Q) {
+        set_error("model has a NULL m0/chol_P0/F/b/chol_Q host pointer");
+        return AUXSSM_ERR_ARG;
+    }
+    if (!user_potential && fk->potential != AUXSSM_POT_FLAT && !fk->y) {
+        set_error("potential needs observations y");
+        return AUXSSM_ERR_ARG;
+    }
+    if (fk->potential == AUXSSM_POT_GAUSS_OBS && !(fk->sig_y > 0)) {
+        set_error("sig_y must be > 0");
+        return AUXSSM_ERR_ARG;
+    }
+    const int ntv = (fk->F_t != nullptr) + (fk->b_t != nullptr) + (fk->chol_Q_t != nullptr);
+    if (ntv != 0 && ntv != 3) {
+        set_error("time-varying transitions need F_t, b_t and chol_Q_t together (device arrays with T - 1 rows)");
+        return AUXSSM_ERR_ARG;
+    }
+    if (ntv && fk->transition != AUXSSM_TRANS_LINEAR) {
+        set_error("time-varying parameters are for the linear transition only");
+        return AUXSSM_ERR_ARG;
+    }
+    if (fk->gradient != AUXSSM_GRAD_NONE && fk->gradient != AUXSSM_GRAD_REFERENCE && fk->gradient != AUXSSM_GRAD_EXACT) {
+        set_error("unknown gradient mode %d", fk->gradient);
+        return AUXSSM_ERR_ARG;
+    }
+    if (noise->mode != AUXSSM_NOISE_EXPLICIT && noise->mode != AUXSSM_NOISE_THREEFRY) {
+        set_error("unknown noise mode %d", noise->mode);
+        return AUXSSM_ERR_ARG;
+    }
+    return AUXSSM_OK;
+}
+
+// The model of fk in precision R, as both kernel families read it: the parameters into m0 | LP0 | F | b | LQ (matrices row-major, leading dimension ld), the
+// reciprocal Cholesky diagonals into iLP0 / iLQ, the kinds, the gradient mode and the additive constants into m (FkDev<R>, or csmc_wide.hip's FkW<R>).  The
+// constants are computed once, here, in precision R: they enter both the GPU and the oracle as data.
+template <typename R, typename M>
+static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* iLP0, R* F, R* b, R* LQ, R* iLQ) {
+    const int D = fk->dx;
+    m.proposal = fk->proposal;
+    m.potential = fk->potential;
+    m.D = D;
+    m.gradient = fk->gradient;
+    for (int k = 0; k < D; ++k) m0[k] = (R)fk->m0[k], b[k] = (R)fk->b[k];
+    for (int i = 0; i < D; ++i)
+        for (int j = 0; j < D; ++j) {
+            LP0[i * ld + j] = (R)fk->chol_P0[i * D + j];
+            F[i * ld + j] = (R)fk->F[i * D + j];
+            LQ[i * ld + j] = (R)fk->chol_Q[i * D + j];
+        }
+    R ci = 0, ct = 0;
+    for (int k = 0; k < D; ++k) {
+        ci -= det_log(LP0[k * ld + k]);
+        ct -= det_log(LQ[k * ld + k]);
+        iLP0[k] = (R)1 / LP0[k * ld + k];
+        iLQ[k] = (R)1 / LQ[k * ld + k];
+    }
+    const R half_log_2pi = (R)0.91893853320467274178;
+    m.c_init = ci - (R)D * half_log_2pi;
+    m.c_trans = ct - (R)D * half_log_2pi;
+    if (fk->potential == 1) {
+        m.inv_sig_y = (R)1 / (R)fk->sig_y;
+        m.c_obs = -(R)D * det_log((R)fk->sig_y) - (R)D * half_log_2pi;
+    } else if (fk->potential == 3) {  // per observed component
+        m.inv_sig_y = (R)1 / (R)fk->sig_y;
+        m.c_obs = -det_log((R)fk->sig_y) - half_log_2pi;
+    } else {
+        m.inv_sig_y = 0;
+        m.c_obs = -half_log_2pi;
+    }
+}
+// the register kernels' model (the time-varying arrays null: fk_time_varying sets them)
+template <typename R> static FkDev<R> fk_dev(const auxssm_fk_model* fk) {
+    FkDev<R> m;
+    memset(&m, 0, sizeof(m));
+    m.transition = fk->transition;
+    fk_model<R>(fk, m, CS_MAXD, m.m0, m.LP0, m.iLP0, m.F, m.b, m.LQ, m.iLQ);
+    return m;
+}
+
+// additive constants ct[t] = -sum_k log LQ_t[k][k] - D/2 log 2 pi and reciprocal diagonals of the time-varying transition densities, one thread per transition
+template <typename R> __global__ void k_csmc_ctrans(int n, int D, const R* __restrict__ LQt, R* __restrict__ ct, R* __restrict__ idt) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    R c = 0;
+    for (int k = 0; k < D; ++k) {
+        const R l = LQt[((long long)t * D + k) * D + k];
+        c -= det_log(l);
+        idt[(long long)t * D + k] = (R)1 / l;  // reciprocal diagonal (sweep contract v3)
+    }
+    ct[t] = c - (R)D * (R)0.91893853320467274178;
+}
+// time-varying transitions (fk's device rows F_t, b_t, chol_Q_t of the T - 1 transitions): m reads them, and ctt -- (T - 1) (1 + D) reals of workspace --
+// receives their constants and reciprocal diagonals.  Nothing to do for a time-invariant model.
+template <typename R, typename M> static void fk_time_varying(auxssm_ctx* h, const auxssm_fk_model* fk, int T, void* ctt, M& m) {
+    if (!fk->F_t || T < 2) return;
+    m.Ft = (const R*)fk->F_t;
+    m.bt = (const R*)fk->b_t;
+    m.LQt = (const R*)fk->chol_Q_t;
+    m.ctt = (const R*)ctt;
+    m.idt = (const R*)ctt + (T - 1);
+    hipLaunchKernelGGL((k_csmc_ctrans<R>), dim3((T - 1 + 255) / 256), dim3(256), 0, h->stream, T - 1, fk->dx, m.LQt, (R*)ctt, (R*)ctt + (T - 1));
+}
+
+// gb[t] = sup_x G_t(x): the reduction-free part of the forward weights' shift (sweep contract, csmc_sweep.h); +inf where the potential is unbounded
+template <typename R> __global__ void k_csmc_potbound(int T, int D, int potential, R c_obs, const R* __restrict__ y, R* __restrict__ gb) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    R b = 0;
+    if (potential == 1) b = c_obs;
+    else if (potential == 3) {
+        int nobs = 0;
+        for (int k = 0; k < D; ++k) nobs += (y[(long long)t * D + k] - y[(long long)t * D + k] == 0) ? 1 : 0;
+        b = (R)nobs * c_obs;
+    } else if (potential == 2) {  // sum_k [c_obs - (x + y^2 e^-x) / 2] <= sum_k max(0, c_obs - (1 + log y^2) / 2)  (a NaN term counts 0)
+        for (int k = 0; k < D; ++k) {
+            const R yk = y[(long long)t * D + k], y2 = yk * yk;
+            R v = (R)0;
+            if (y2 - y2 == 0) v = y2 > (R)0 ? fma_((R)-0.5, (R)1 + det_log(y2), c_obs) : (R)INFINITY;
+            b += v > (R)0 ? v : (R)0;
+        }
+    }
+    gb[t] = b;
+}
+template <typename R, typename M> static void fk_potbound(auxssm_ctx* h, const CsmcArgs& a, const M& m) {
+    hipLaunchKernelGGL((k_csmc_potbound<R>), dim3((a.T + 255) / 256), dim3(256), 0, h->stream, a.T, m.D, m.potential, m.c_obs, (const R*)a.y, (R*)a.gb);
+}
+
+// the arguments of the batch [c0, c0 + cb) of chains (CsmcArgs::c0)
+static CsmcArgs csmc_batch(const CsmcArgs& a, int c0, int cb) {
+    CsmcArgs ab = a;
+    ab.c0 = c0;
+    ab.C = a.C - c0 < cb ? a.C - c0 : cb;
+    ab.xs = (char*)a.xs - (size_t)c0 * a.xs_rec;
+    ab.lws = (char*)a.lws - (size_t)c0 * a.lws_rec;
+    if (a.As) ab.As = (int32_t*)((char*)a.As - (size_t)c0 * a.As_rec);
+    return ab;
+}
+
+// f(R(), std::integral_constant<int, D>()) for the sweep's dtype and dx: the register kernels' instantiations, 1 <= dx <= CS_MAXD
+template <typename F> static int csmc_dispatch(int dtype, int D, F&& f) {
+    auto dx = [&](auto r) {
+        switch (D) {
+            case 1: return f(r, std::integral_constant<int, 1>{});
+            case 2: return f(r, std::integral_constant<int, 2>{});
+            case 3: return f(r, std::integral_constant<int, 3>{});
+            default: return f(r, std::integral_constant<int, 4>{});
+        }
+    };
+    return dtype == AUXSSM_F32 ? dx(0.0f) : dx(0.0);
+}
+
+}  // namespace ax

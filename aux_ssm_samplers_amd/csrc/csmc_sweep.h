@@ -1,6 +1,6 @@
 // csmc_sweep.h -- the device side of the sequential conditional-SMC sweep (k_csmc_fwd / k_csmc_bwd of csmc.hip) and what the cSMC units share
 // with it: the device-side Feynman-Kac model, its densities in fixed operation order, the workgroup reductions whose orders the C oracle
-// (oracle/csmc_ref.c) restates, and the forward / backward pass bodies.  Self-contained device code: it compiles under hipcc (through csmc_dev.h)
+// (oracle/csmc_ref.c) restates, and the forward / backward pass bodies.  Self-contained device code: it compiles under hipcc (through csmc_host.h)
 // AND under hipRTC (fk_program.hip: a user-defined model compiled at get_kernel time; rtc_compat.h), so nothing here may include host C++ or ctx.h.
 // Units including this are compiled with -ffp-contract=off (hipRTC programs too).
 #pragma once
@@ -343,7 +343,7 @@ template <typename R> __device__ __forceinline__ int lower_bound(const R* c, int
 //            exact maximum otherwise, and the exact maximum after all whenever every e_i underflowed (cumulative total not > 0: detected where
 //            the total is formed -- one step later in the forward pass, in the same step in the backward pass).  Scale-invariant as above.
 //            Forward, 1 <= t < T - 1, not the exact-gradient proposals: M_t = gb_t (+ c_t for the auxiliary proposals), gb_t = sup_x G_t(x)
-//            (k_csmc_potbound: 0 | c_obs | nobs c_obs | sum_k max(0, c_obs - (1 + log y_k^2) / 2); +inf -> no bound), c_t the log-normaliser
+//            (csmc_host.h::k_csmc_potbound: 0 | c_obs | nobs c_obs | sum_k max(0, c_obs - (1 + log y_k^2) / 2); +inf -> no bound), c_t the log-normaliser
 //            of the transition density; t = 0 and t = T - 1 use the exact maximum.  fmax[t] = the shift finally used.
 //            Backward: lw_i = log_ws[t][i] + log p(x_{t+1} | x_t^i) <= M := fmax[t] + c_t.
 //   max    : exact, any order.
@@ -632,30 +632,8 @@ template <typename R, int D, typename P = FkBuiltin<R, D>, typename... PA> __glo
     for (int k = 0; k < D; ++k) ((R*)a.grad)[g * D + k] = gr[k];
 }
 
-// gb[t] = sup_x G_t(x): the reduction-free part of the forward weights' shift (sweep contract, csmc_dev.h); +inf where the potential is unbounded
-template <typename R, int D> __global__ void k_csmc_potbound(int T, FkDev<R> m, const R* __restrict__ y, R* __restrict__ gb) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    R b = 0;
-    if (m.potential == 1) b = m.c_obs;
-    else if (m.potential == 3) {
-        int nobs = 0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) nobs += (y[(long long)t * D + k] - y[(long long)t * D + k] == 0) ? 1 : 0;
-        b = (R)nobs * m.c_obs;
-    } else if (m.potential == 2) {  // sum_k [c_obs - (x + y^2 e^-x) / 2] <= sum_k max(0, c_obs - (1 + log y^2) / 2)  (a NaN term counts 0)
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            const R yk = y[(long long)t * D + k], y2 = yk * yk;
-            R v = (R)0;
-            if (y2 - y2 == 0) v = y2 > (R)0 ? fma_((R)-0.5, (R)1 + det_log(y2), m.c_obs) : (R)INFINITY;
-            b += v > (R)0 ? v : (R)0;
-        }
-    }
-    gb[t] = b;
-}
 // ---- forward pass (_csmc, csmc.py:69-107) -------------------------------------------------------------------------------
-// NW = 8 / 16: exactly NW full waves (N = blockDim = 64 NW: the C4 / C3 shapes): no liveness / group-bound selects (csmc_dev.h); NW = 0: any N
+// NW = 8 / 16: exactly NW full waves (N = blockDim = 64 NW: the C4 / C3 shapes): no liveness / group-bound selects (block_expmax); NW = 0: any N
 // SP = 1: the instantiation of config C3's shape -- auxiliary independent proposals, the stochastic-volatility potential, a time-invariant linear transition, draws
 // generated in the kernel, no ancestor trace (backward sampling): the run-time switches on the model kind are folded at compile time (they are wave-uniform
 // branches, two dozen per time step); same operations on the same operands, bit for bit (tests/test_gpu_csmc.py runs both instantiations on C3's model)
@@ -675,7 +653,7 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
     const int TB = blockDim.x, nw = TB >> 6, tid = threadIdx.x, N = a.N, T = a.T;
     // two images of (c, xprev), alternated by time-step parity: readers of step t never race writers of step t+1,
     // which removes the end-of-step barrier (4 barriers per step: max, sum, wave totals, publish)
-    const int CP = cpad(TB);            // the cumsum image is padded against LDS bank conflicts of the search (csmc_dev.h::cpad)
+    const int CP = cpad(TB);            // the cumsum image is padded against LDS bank conflicts of the search (cpad)
     R* cbuf = (R*)smem;                 // [2][CP]
     R* xbuf = cbuf + 2 * CP;            // [2][TB][D]
     R* red = xbuf + 2 * TB * D;         // [48]
@@ -872,7 +850,7 @@ __global__ void __launch_bounds__(1024) k_csmc_bwd(CsmcArgs a, FkDev<R> m, PA...
     R* ubuf = xpub + 2 * TB * D;     // [2] the step's uniform, by step parity
     const int ch = a.c0 + blockIdx.x;
     const bool live = NW > 0 ? true : tid < N;
-    if (tid < 16) red[32 + tid] = 0, red[48 + tid] = 0;  // totals of absent groups: +0 (csmc_dev.h::totals_prefix)
+    if (tid < 16) red[32 + tid] = 0, red[48 + tid] = 0;  // totals of absent groups: +0 (totals_prefix)
     const R* xs = (const R*)a.xs + (long long)ch * T * N * D;
     const R* lws = (const R*)a.lws + (long long)ch * T * N;
     const int32_t* As = a.As ? a.As + (long long)ch * (T - 1) * N : nullptr;
@@ -963,7 +941,7 @@ __global__ void __launch_bounds__(1024) k_csmc_bwd(CsmcArgs a, FkDev<R> m, PA...
         if (!(Mb - Mb == 0)) Mb = 0;
         w = det_exp(lw - Mb);
         {   // ONE barrier per step: local scan values and wave totals of this parity are published together with xpub / ubuf; every wave then finds the
-            // group and counts inside it on its own (csmc_dev.h::draw_two_level)
+            // group and counts inside it on its own (draw_two_level)
             const int lane = tid & 63, wv = tid >> 6;
             R* vloc = c + par * TB;
             R* tl = red + 32 + par * 16;

@@ -1,7 +1,7 @@
 // csmc_wide.hip -- the conditional-SMC sweep for WIDE states with FEW particles: 4 < dx <= 32, N <= 64 (the reference's own timed stochastic-volatility
 // protocol is D = 30, N = 25, T = 250: examples/stochastic_volatility/experiment.sh:1-10, experiment.py:38-55, auxiliary_csmc.py:14-46).
 //
-// Same algorithm, same sweep contract (csmc_dev.h: unnormalised weights shifted by a bound or the exact maximum, DPP-order cumsum, descent search,
+// Same algorithm, same sweep contract (csmc_sweep.h: unnormalised weights shifted by a bound or the exact maximum, DPP-order cumsum, descent search,
 // ballot-counted single draw, reciprocal Cholesky diagonals, det_exp / det_log, explicit fma) and the same oracle (oracle/csmc_ref.c, MAXD = 32) as the
 // register kernels of csmc.hip -- what changes is where a particle lives (the register kernels keep R x[D], eps[D], mu[D], z[D] per lane and the model BY VALUE
 // in the kernel arguments, which stops at dx = 4): here a particle's dx components sit ACROSS the 32 lanes of a half-wave, two particles per wave, 16 waves per
@@ -17,7 +17,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "csmc_dev.h"
+#include "csmc_host.h"
 
 namespace ax {
 
@@ -28,7 +28,7 @@ template <typename R> struct FkW {
     const R *m0, *LP0, *iLP0, *F, *b, *LQ, *iLQ;  // device arrays, matrices row-major with leading dimension D
     R c_init, c_trans, c_obs, inv_sig_y;
     int gradient;                          // AUXSSM_GRAD_*
-    const R *Ft, *bt, *LQt, *ctt, *idt;    // time-varying transitions (csmc_dev.h::FkDev: row t = transition t -> t + 1), or null
+    const R *Ft, *bt, *LQt, *ctt, *idt;    // time-varying transitions (csmc_sweep.h::FkDev: row t = transition t -> t + 1), or null
 };
 // the transition t -> t + 1 in global memory (gradient kernel; the sweep kernels read it from LDS)
 template <typename R> struct TransW {
@@ -40,7 +40,7 @@ template <typename R> __device__ __forceinline__ TransW<R> trans_w(const FkW<R>&
     return TransW<R>{m.F, m.b, m.LQ};
 }
 
-// e_i = exp(lw_i - max lw) over ONE wave (csmc_dev.h::block_expmax)
+// e_i = exp(lw_i - max lw) over ONE wave (csmc_sweep.h::block_expmax)
 template <typename R> __device__ __forceinline__ R wave_expmax(R lw, R* m_out) {
     R m = wave_max_dpp(lw);
     if (!(m - m == 0)) m = 0;
@@ -59,39 +59,6 @@ template <typename R> __device__ __forceinline__ int search_w(const R* c, int N,
     return pos < N - 1 ? pos : N - 1;
 }
 
-template <typename R> __global__ void k_cw_potbound(int T, FkW<R> m, const R* __restrict__ y, R* __restrict__ gb) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    const int D = m.D;
-    R b = 0;
-    if (m.potential == 1) b = m.c_obs;
-    else if (m.potential == 3) {
-        int nobs = 0;
-        for (int k = 0; k < D; ++k) nobs += (y[(long long)t * D + k] - y[(long long)t * D + k] == 0) ? 1 : 0;
-        b = (R)nobs * m.c_obs;
-    } else if (m.potential == 2) {
-        for (int k = 0; k < D; ++k) {
-            const R yk = y[(long long)t * D + k], y2 = yk * yk;
-            R v = (R)0;
-            if (y2 - y2 == 0) v = y2 > (R)0 ? fma_((R)-0.5, (R)1 + det_log(y2), m.c_obs) : (R)INFINITY;
-            b += v > (R)0 ? v : (R)0;
-        }
-    }
-    gb[t] = b;
-}
-
-// additive constants and reciprocal diagonals of the time-varying transition densities (csmc_dev.h::k_csmc_ctrans with a runtime dimension, same operations)
-template <typename R> __global__ void k_cw_ctrans(int n, int D, const R* __restrict__ LQt, R* __restrict__ ct, R* __restrict__ idt) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    R c = 0;
-    for (int k = 0; k < D; ++k) {
-        const R l = LQt[((long long)t * D + k) * D + k];
-        c -= det_log(l);
-        idt[(long long)t * D + k] = (R)1 / l;
-    }
-    ct[t] = c - (R)D * (R)0.91893853320467274178;
-}
 // w <- (L L^T)^-1 r (csmc_sweep.h::cho_solve_fixed, runtime dimension, leading dimension D)
 template <typename R> __device__ __forceinline__ void cho_solve_w(int D, const R* L, const R* r, R* w) {
     R z[CSW_MAXD];
@@ -163,7 +130,7 @@ template <typename R> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
 //   * a mean component is one dot product, accumulated over j = 0 .. dx - 1 by the lane that owns the component;
 //   * the forward substitution runs COLUMN by column -- z_j = acc_j / L_jj is final once columns < j have been applied, it is broadcast inside the
 //     half-wave by v_readlane and every lane k > j applies acc_k = fma(-L_kj, z_j, acc_k): each acc_k receives the same updates in the same order
-//     as the row-oriented loop of the contract (csmc_dev.h::gauss_chol_logpdf), so z, q = sum z_k^2 (accumulated in k order by every lane alike) and the densities are bit-identical;
+//     as the row-oriented loop of the contract (csmc_sweep.h::gauss_chol_logpdf), so z, q = sum z_k^2 (accumulated in k order by every lane alike) and the densities are bit-identical;
 //   * the potential's sum over components is accumulated in component order from readlane broadcasts of the per-component terms;
 //   * weights, cumulative sums, searches and the single draw of the backward pass are done by wave 0 with one lane per particle, exactly as before.
 // Two workgroup barriers per time step in either pass.  In-kernel draws keep the natural flat indices (and use both normals of a Threefry block).
@@ -253,7 +220,7 @@ template <int J, int N, typename F> __device__ __forceinline__ void static_for(F
         static_for<J + 1, N>(f);
     }
 }
-// sum_k ((x_k - pm_k)^2 - (x_k - u_k)^2) / (2 s^2) of the particle whose component k this lane holds (csmc_dev.h::grad_correction: the two multiply-adds per
+// sum_k ((x_k - pm_k)^2 - (x_k - u_k)^2) / (2 s^2) of the particle whose component k this lane holds (csmc_sweep.h::grad_correction: the two multiply-adds per
 // component, in component order, from broadcasts of the lanes' differences; components beyond D add fma(0, 0, acc) = acc)
 template <typename R> __device__ __forceinline__ R grad_corr_half(int D, int k, R xk, R uk, R pmk, R s) {
     const R d1 = k < D ? xk - uk : (R)0, d2 = k < D ? xk - pmk : (R)0;
@@ -317,7 +284,7 @@ template <typename R> __device__ __forceinline__ R gauss_half_blk(int D, int k, 
     });
     return fma_((R)-0.5, q, cst);
 }
-// g_t(x) of that particle: per-component terms in the lanes, summed in component order (csmc_dev.h::potential with a runtime dimension, same operations)
+// g_t(x) of that particle: per-component terms in the lanes, summed in component order (csmc_sweep.h::potential with a runtime dimension, same operations)
 template <typename R> __device__ __forceinline__ R potential_half(const FkW<R>& m, int k, bool hi, R xk, R yk) {
     const int D = m.D;
     if (m.potential == 0) return (R)0;
@@ -636,44 +603,16 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
     }
 }
 
-// host: the model as one device block [m0 | LP0 | iLP0 | F | b | LQ | iLQ], constants as csmc_dev.h::fill_model computes them
-template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, R* host_block, void* ctt) {
+// host: the model as one device block [m0 | LP0 | iLP0 | F | b | LQ | iLQ] (csmc_host.h::fk_model, leading dimension D)
+template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void* ctt) {
     const int D = fk->dx;
     FkW<R> m;
     memset(&m, 0, sizeof(m));
-    m.proposal = fk->proposal; m.potential = fk->potential; m.D = D;
-    m.gradient = fk->gradient;
-    R* p = host_block;
-    R* hm0 = p; p += D;
-    R* hLP0 = p; p += D * D;
-    R* hiLP0 = p; p += D;
-    R* hF = p; p += D * D;
-    R* hb = p; p += D;
-    R* hLQ = p; p += D * D;
-    R* hiLQ = p; p += D;
-    for (int k = 0; k < D; ++k) hm0[k] = (R)fk->m0[k], hb[k] = (R)fk->b[k];
-    for (int i = 0; i < D * D; ++i) hLP0[i] = (R)fk->chol_P0[i], hF[i] = (R)fk->F[i], hLQ[i] = (R)fk->chol_Q[i];
-    R ci = 0, ct = 0;
-    for (int k = 0; k < D; ++k) {
-        ci -= det_log(hLP0[k * D + k]);
-        ct -= det_log(hLQ[k * D + k]);
-        hiLP0[k] = (R)1 / hLP0[k * D + k];
-        hiLQ[k] = (R)1 / hLQ[k * D + k];
-    }
-    const R half_log_2pi = (R)0.91893853320467274178;
-    m.c_init = ci - (R)D * half_log_2pi;
-    m.c_trans = ct - (R)D * half_log_2pi;
-    if (fk->potential == 1) {
-        m.inv_sig_y = (R)1 / (R)fk->sig_y;
-        m.c_obs = -(R)D * det_log((R)fk->sig_y) - (R)D * half_log_2pi;
-    } else if (fk->potential == 3) {
-        m.inv_sig_y = (R)1 / (R)fk->sig_y;
-        m.c_obs = -det_log((R)fk->sig_y) - half_log_2pi;
-    } else {
-        m.inv_sig_y = 0;
-        m.c_obs = -half_log_2pi;
-    }
-    const size_t nb = (size_t)(p - host_block) * sizeof(R);
+    std::vector<R> block((size_t)3 * D * D + 4 * D);
+    R* const host_block = block.data();
+    R *hm0 = host_block, *hLP0 = hm0 + D, *hiLP0 = hLP0 + D * D, *hF = hiLP0 + D, *hb = hF + D * D, *hLQ = hb + D, *hiLQ = hLQ + D * D;
+    fk_model<R>(fk, m, D, hm0, hLP0, hiLP0, hF, hb, hLQ, hiLQ);
+    const size_t nb = block.size() * sizeof(R);
     {   // the handle's copy of the block: a new upload only when the content differs from the last one (a model that changes between sweeps pays one
         // stream synchronisation -- earlier sweeps may still be reading the old block -- a fixed model none: include/auxssm.h, auxssm_csmc_sweep)
         const int hdr[2] = {(int)sizeof(R), D};
@@ -702,15 +641,8 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     m.b = d; d += D;
     m.LQ = d; d += D * D;
     m.iLQ = d;
-    if (fk->F_t && a.T > 1) {  // time-varying transitions: device rows + their constants and reciprocal diagonals (csmc.hip::run_csmc does the same for dx <= 4)
-        m.Ft = (const R*)fk->F_t;
-        m.bt = (const R*)fk->b_t;
-        m.LQt = (const R*)fk->chol_Q_t;
-        m.ctt = (const R*)ctt;
-        m.idt = (const R*)ctt + (a.T - 1);
-        hipLaunchKernelGGL((k_cw_ctrans<R>), dim3((a.T - 1 + 255) / 256), dim3(256), 0, h->stream, a.T - 1, D, m.LQt, (R*)ctt, (R*)ctt + (a.T - 1));
-    }
-    if (a.gb) hipLaunchKernelGGL((k_cw_potbound<R>), dim3((a.T + 255) / 256), dim3(256), 0, h->stream, a.T, m, (const R*)a.y, (R*)a.gb);
+    fk_time_varying<R>(h, fk, a.T, ctt, m);
+    if (a.gb) fk_potbound<R>(h, a, m);
     if (fk->proposal == 1) {
         const long long total = (long long)a.C * a.T * D;
         hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
@@ -731,12 +663,7 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     // waves at N = 25, two passes) once there are more chains than CUs
     const bool wide16 = sizeof(R) == 4 && a.C <= h->num_cu;  // (fp64: the unrolled loops need more than the 128 registers of a 1024-lane workgroup)
     for (int c0 = 0; c0 < a.C; c0 += cb) {
-        CsmcArgs ab = a;
-        ab.c0 = c0;
-        ab.C = a.C - c0 < cb ? a.C - c0 : cb;
-        ab.xs = (char*)a.xs - (size_t)c0 * a.xs_rec;
-        ab.lws = (char*)a.lws - (size_t)c0 * a.lws_rec;
-        if (a.As) ab.As = (int32_t*)((char*)a.As - (size_t)c0 * a.As_rec);
+        const CsmcArgs ab = csmc_batch(a, c0, cb);
         {
             ProfScope ps(h, AUXSSM_K_CSMC_FWD);
             if (wide16) hipLaunchKernelGGL((k_cw2_fwd<R, 16>), dim3(ab.C), dim3(1024), lds, h->stream, ab, m);
@@ -754,10 +681,8 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
 
 // called by auxssm_csmc_sweep (csmc.hip) for dx > CS_MAXD
 int run_csmc_wide(auxssm_ctx* h, int dtype, const auxssm_fk_model* fk, CsmcArgs& a, void* ctt) {
-    const int D = fk->dx;
-    std::vector<double> host((size_t)3 * D * D + 4 * D + 8);
-    if (dtype == AUXSSM_F32) return run_cw<float>(h, fk, a, (float*)host.data(), ctt);
-    return run_cw<double>(h, fk, a, host.data(), ctt);
+    if (dtype == AUXSSM_F32) return run_cw<float>(h, fk, a, ctt);
+    return run_cw<double>(h, fk, a, ctt);
 }
 
 }  // namespace ax

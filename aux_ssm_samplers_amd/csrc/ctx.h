@@ -22,6 +22,31 @@ void fk_modules_release(auxssm_ctx* h);  // fk_program.hip
         }                                                                                    \
     } while (0)
 
+// the prologue of an entry point: a NULL handle is refused, the handle's device made current and the call counted (auxssm_ctx::api_calls)
+#define AX_NEED_H(h)                          \
+    do {                                      \
+        if (!(h)) {                           \
+            ax::set_error("handle is NULL");  \
+            return AUXSSM_ERR_ARG;            \
+        }                                     \
+        AX_HIP(hipSetDevice((h)->device));    \
+        ++(h)->api_calls;                     \
+    } while (0)
+// entry points that neither enqueue work nor change device data (SideStage::last_call)
+#define AX_NEED_H_RO(h)                       \
+    do {                                      \
+        AX_NEED_H(h);                         \
+        --(h)->api_calls;                     \
+    } while (0)
+
+inline int check_dtype(int dtype) {
+    if (dtype != AUXSSM_F32 && dtype != AUXSSM_F64) {
+        set_error("dtype must be AUXSSM_F32 (0) or AUXSSM_F64 (1), got %d", dtype);
+        return AUXSSM_ERR_ARG;
+    }
+    return AUXSSM_OK;
+}
+
 struct Prof {
     int kernel_id = 0;  // AUXSSM_K_ALL (-1): every kernel group is bracketed, each slot remembers its group
     int max_launches = 0;

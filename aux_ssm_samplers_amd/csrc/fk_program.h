@@ -3,7 +3,8 @@
 #include <string>
 #include <vector>
 
-#include "csmc_dev.h"
+#include "ctx.h"
+#include "csmc_sweep.h"
 
 namespace ax {
 

@@ -87,22 +87,6 @@ __global__ void __launch_bounds__(256) k_lorenz_theta(int C, int T, int cfast, c
     }
 }
 
-#define AX_NEED_H(h)                         \
-    do {                                     \
-        if (!(h)) {                          \
-            set_error("handle is NULL");     \
-            return AUXSSM_ERR_ARG;           \
-        }                                    \
-        AX_HIP(hipSetDevice((h)->device));   \
-        ++(h)->api_calls;                    \
-    } while (0)
-
-static int need_dtype(int dtype) {
-    if (dtype == AUXSSM_F32 || dtype == AUXSSM_F64) return AUXSSM_OK;
-    set_error("dtype must be AUXSSM_F32 or AUXSSM_F64");
-    return AUXSSM_ERR_ARG;
-}
-
 template <typename R>
 static int stats_update(auxssm_ctx* h, int64_t n, int64_t iter, const void* xp, const void* xn, void* sj, void* mn, void* sq) {
     hipLaunchKernelGGL((k_stats_update<R>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (long long)n, (long long)iter,
@@ -706,7 +690,7 @@ int auxssm_stats_attach(auxssm_handle h, int dtype, int64_t n, const void* x, vo
         return AUXSSM_ERR_ARG;
     }
     if (nn == 3) {
-        if (int rc = need_dtype(dtype)) return rc;
+        if (int rc = check_dtype(dtype)) return rc;
         if (!x || n < 1) {
             set_error("attach needs the resident state x (non-NULL) and its element count n >= 1");
             return AUXSSM_ERR_ARG;
@@ -729,7 +713,7 @@ int auxssm_stats_attach(auxssm_handle h, int dtype, int64_t n, const void* x, vo
 int auxssm_stats_update(auxssm_handle h, int dtype, int64_t n, int64_t iter, const void* x_prev, const void* x_next, void* sq_jump,
                         void* mean, void* sq_mean) {
     AX_NEED_H(h);
-    if (int rc = need_dtype(dtype)) return rc;
+    if (int rc = check_dtype(dtype)) return rc;
     if (n < 0 || iter < 0) {
         set_error("n and iter must be >= 0");
         return AUXSSM_ERR_ARG;
@@ -745,9 +729,8 @@ int auxssm_stats_update(auxssm_handle h, int dtype, int64_t n, int64_t iter, con
 
 int auxssm_accept_update(auxssm_handle h, int dtype, int32_t C, int32_t m, int64_t iter, double beta, const int32_t* flags, void* avg,
                          void* window) {
-    AX_NEED_H(h);
-    --h->api_calls;  // (reads the sweep's flags, writes its own averages: a chain-shared sweep's model stage may still run ahead of it, ctx.h::SideStage)
-    if (int rc = need_dtype(dtype)) return rc;
+    AX_NEED_H_RO(h);  // (reads the sweep's flags, writes its own averages: a chain-shared sweep's model stage may still run ahead of it, ctx.h::SideStage)
+    if (int rc = check_dtype(dtype)) return rc;
     if (C < 0 || m < 0 || iter < 0) {
         set_error("C, m and iter must be >= 0");
         return AUXSSM_ERR_ARG;
@@ -765,7 +748,7 @@ int auxssm_accept_update(auxssm_handle h, int dtype, int32_t C, int32_t m, int64
 int auxssm_delta_adapt(auxssm_handle h, int dtype, int32_t C, int32_t m, const void* window, double target, double rate, double min_delta,
                        double max_delta, void* delta, void* sqrt_half_delta) {
     AX_NEED_H(h);
-    if (int rc = need_dtype(dtype)) return rc;
+    if (int rc = check_dtype(dtype)) return rc;
     if (C < 1 || m < 0) {
         set_error("C must be >= 1 and m >= 0");
         return AUXSSM_ERR_ARG;
@@ -782,7 +765,7 @@ int auxssm_delta_adapt(auxssm_handle h, int dtype, int32_t C, int32_t m, const v
 int auxssm_lorenz_theta_update(auxssm_handle h, int dtype, int32_t C, int32_t T, int layout, const void* x, double sigma_theta, double sigma_x,
                                const void* eps, void* par, void* mean_chol) {
     AX_NEED_H(h);
-    if (int rc = need_dtype(dtype)) return rc;
+    if (int rc = check_dtype(dtype)) return rc;
     if (C < 0 || T < 1) {
         set_error("C must be >= 0 and T >= 1");
         return AUXSSM_ERR_ARG;
@@ -808,7 +791,7 @@ int auxssm_lorenz_theta_update(auxssm_handle h, int dtype, int32_t C, int32_t T,
 int auxssm_mvn_logpdf(auxssm_handle h, int dtype, int64_t n, int32_t dim, const void* x, int64_t sx, const void* m, int64_t sm, const void* chol,
                       int64_t sl, void* out) {
     AX_NEED_H(h);
-    if (int rc = need_dtype(dtype)) return rc;
+    if (int rc = check_dtype(dtype)) return rc;
     if (n < 0 || dim < 1 || dim > MVN_MAX_DIM) {
         set_error("n must be >= 0 and 1 <= dim <= %d (got n=%lld, dim=%d)", MVN_MAX_DIM, (long long)n, dim);
         return AUXSSM_ERR_ARG;
@@ -831,7 +814,7 @@ int auxssm_mvn_logpdf(auxssm_handle h, int dtype, int64_t n, int32_t dim, const 
 
 int auxssm_mvn_optimal_covariance(auxssm_handle h, int dtype, int32_t dim, int vector, const void* chol_P, const void* chol_Sig, void* out) {
     AX_NEED_H(h);
-    if (int rc = need_dtype(dtype)) return rc;
+    if (int rc = check_dtype(dtype)) return rc;
     if (dim < 1 || (!vector && dim > MVN_MAX_DIM)) {
         set_error("1 <= dim <= %d (got %d)", MVN_MAX_DIM, dim);
         return AUXSSM_ERR_ARG;
@@ -854,7 +837,7 @@ int auxssm_mvn_optimal_covariance(auxssm_handle h, int dtype, int32_t dim, int v
 
 int auxssm_ess(auxssm_handle h, int dtype, int64_t M, int64_t N, int64_t K, const void* a, const void* var, void* out) {
     AX_NEED_H(h);
-    if (int rc = need_dtype(dtype)) return rc;
+    if (int rc = check_dtype(dtype)) return rc;
     if (M < 1 || N < 4 || K < 1 || N > 0x7fffffffLL || K > 65535 || M * K > 0x7fffffffLL) {
         set_error("need M >= 1 chains, 4 <= N draws, 1 <= K <= 65535 series (got M=%lld N=%lld K=%lld)", (long long)M, (long long)N, (long long)K);
         return AUXSSM_ERR_ARG;
@@ -886,7 +869,7 @@ int auxssm_ess(auxssm_handle h, int dtype, int64_t M, int64_t N, int64_t K, cons
 int auxssm_linearise(auxssm_handle h, int dtype, int method, int order, int fn_kind, int64_t n, int32_t dim, int32_t dim_out, const void* A, const void* a,
                      const void* Qc, const void* nodes, const void* weights, const void* x_star, const void* P_star, int64_t sP, void* F, void* Q, void* b) {
     AX_NEED_H(h);
-    if (int rc = need_dtype(dtype)) return rc;
+    if (int rc = check_dtype(dtype)) return rc;
     if (method < AUXSSM_LIN_EXTENDED || method > AUXSSM_LIN_GAUSS_HERMITE || fn_kind < AUXSSM_FN_AFFINE || fn_kind > AUXSSM_FN_LORENZ63) {
         set_error("unknown linearisation method %d / function kind %d", method, fn_kind);
         return AUXSSM_ERR_ARG;
@@ -927,7 +910,7 @@ int auxssm_linearise(auxssm_handle h, int dtype, int method, int order, int fn_k
 int auxssm_rng_jax(auxssm_handle h, int dtype, int kind, int64_t nkeys, int64_t n, const uint32_t* keys, double minval, double maxval, void* out, int64_t key_stride,
                    int64_t elem_stride) {
     AX_NEED_H(h);
-    if (int rc = need_dtype(dtype)) return rc;
+    if (int rc = check_dtype(dtype)) return rc;
     if (kind < 0 || kind > 1 || nkeys < 0 || n < 0 || (2 * n > 0xffffffffLL) || !keys || !out) {
         set_error("kind 0 (uniform) / 1 (normal), nkeys, n >= 0, 2 n < 2^32, keys / out non-NULL (got kind=%d nkeys=%lld n=%lld)", kind, (long long)nkeys, (long long)n);
         return AUXSSM_ERR_ARG;

@@ -20,12 +20,12 @@
 //                       reciprocal diagonal of chol(Q) as a multiplier;
 //   M = max v (exact); e[p] = exp(v[p] - M);  the N^2 values are cut into NCH consecutive chunks of Lc = ceil(N^2/NCH), NCH = 64 (N <= 32),
 //   256 (N <= 128) or 1024 = the lanes of the stitch's workgroup; chunk sums are serial left to right, the cumsum over the NCH chunk sums is
-//   the block cumsum of csmc_dev.h.  A chunk is cut again into SC = 8 consecutive sub-chunks of Ls = ceil(Lc/8): the chunk sum is the
+//   the block cumsum of csmc_sweep.h.  A chunk is cut again into SC = 8 consecutive sub-chunks of Ls = ceil(Lc/8): the chunk sum is the
 //   left-to-right sum of its sub-chunk sums, each a serial sum from 0.  A draw r = total (1 - u) picks the first chunk with cumsum >= r,
 //   inside it the first sub-chunk b with (previous chunks' cumsum + (S_0 + .. + S_b)) >= r (the last non-empty one if none), inside that
 //   the first p with (previous chunks' cumsum + ((S_0 + .. + S_{b-1}) + e .. + e_p)) >= r (its last p if none): a draw recomputes one
 //   sub-chunk, not the chunk.
-#include "csmc_dev.h"
+#include "csmc_host.h"
 
 namespace ax {
 
@@ -317,19 +317,10 @@ template <typename R> __global__ void k_pit_trace(PitArgs a, int D) {
     for (int kk = 0; kk < D; ++kk) ((R*)a.x)[g * D + kk] = ((const R*)a.xs)[(g * a.N + q) * D + kk];
 }
 
-template <typename R, int D> static int run_pit(auxssm_ctx* h, const auxssm_fk_model* fk, const double* host_model, PitArgs& a, void* ctt) {
-    FkDev<R> m;
-    fill_model<R>(m, fk, host_model);
-    m.gradient = fk->gradient;
+template <typename R, int D> static int run_pit(auxssm_ctx* h, const auxssm_fk_model* fk, PitArgs& a, void* ctt) {
+    FkDev<R> m = fk_dev<R>(fk);
     const int TB = (a.N + 63) / 64 * 64;
-    if (fk->F_t) {  // time-varying transitions (csmc.py:103 scans Mt.params; here AuxiliaryGt's Mt, independent.py:238-248)
-        m.Ft = (const R*)fk->F_t;
-        m.bt = (const R*)fk->b_t;
-        m.LQt = (const R*)fk->chol_Q_t;
-        m.ctt = (const R*)ctt;
-        m.idt = (const R*)ctt + (a.T - 1);
-        hipLaunchKernelGGL((k_csmc_ctrans<R, D>), dim3((a.T - 1 + 255) / 256), dim3(256), 0, h->stream, a.T - 1, m.LQt, (R*)ctt, (R*)ctt + (a.T - 1));
-    }
+    fk_time_varying<R>(h, fk, a.T, ctt, m);  // (csmc.py:103 scans Mt.params; here AuxiliaryGt's Mt, independent.py:238-248)
     if (fk->gradient) {  // u and the gradient of the model's joint log-density at u (independent.py:82, :121-134): the sequential sweep's kernels
         CsmcArgs ca{};
         ca.C = a.C; ca.T = a.T; ca.N = a.N;
@@ -364,16 +355,8 @@ using namespace ax;
 
 extern "C" int auxssm_csmc_pit_sweep(auxssm_handle h, int dtype, const auxssm_fk_model* fk, int32_t C, int32_t T, int32_t N,
                                      const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise, int32_t* ancestors) {
-    if (!h) {
-        set_error("handle is NULL");
-        return AUXSSM_ERR_ARG;
-    }
-    AX_HIP(hipSetDevice(h->device));
-    ++h->api_calls;
-    if (dtype != AUXSSM_F32 && dtype != AUXSSM_F64) {
-        set_error("dtype must be 0 (f32) or 1 (f64)");
-        return AUXSSM_ERR_ARG;
-    }
+    AX_NEED_H(h);
+    if (int rc = check_dtype(dtype)) return rc;
     if (!fk || !x || !noise || !ancestors || !sqrt_half_delta) {
         set_error("model/x/noise/ancestors/sqrt_half_delta must be non-NULL");
         return AUXSSM_ERR_ARG;
@@ -391,51 +374,10 @@ extern "C" int auxssm_csmc_pit_sweep(auxssm_handle h, int dtype, const auxssm_fk
         set_error("the parallel-in-time sweep needs proposals that are independent across time: AUXSSM_PROP_AUX_INDEPENDENT");
         return AUXSSM_ERR_ARG;
     }
-    if ((fk->F_t || fk->b_t || fk->chol_Q_t) && !(fk->F_t && fk->b_t && fk->chol_Q_t)) {
-        set_error("time-varying transitions need all of F_t, b_t, chol_Q_t (device arrays with T - 1 rows)");
+    if (int rc = check_fk_model(fk, noise, false)) return rc;
+    if (noise->mode == AUXSSM_NOISE_EXPLICIT && (!noise->eps_prop || !noise->u_res || !noise->eps_aux)) {
+        set_error("explicit noise needs eps_aux (C,T,dx), eps_prop (C,T,N,dx) and u_res (C,T,N)");
         return AUXSSM_ERR_ARG;
-    }
-    if (fk->F_t && fk->transition != AUXSSM_TRANS_LINEAR) {
-        set_error("time-varying transitions are linear-Gaussian");
-        return AUXSSM_ERR_ARG;
-    }
-    if (fk->gradient != AUXSSM_GRAD_NONE && fk->gradient != AUXSSM_GRAD_REFERENCE && fk->gradient != AUXSSM_GRAD_EXACT) {
-        set_error("unknown gradient mode %d", fk->gradient);
-        return AUXSSM_ERR_ARG;
-    }
-    if (fk->potential < AUXSSM_POT_FLAT || fk->potential > AUXSSM_POT_GAUSS_OBS_MASKED) {
-        set_error("unknown potential kind %d", fk->potential);
-        return AUXSSM_ERR_ARG;
-    }
-    if (!fk->m0 || !fk->chol_P0 || !fk->F || !fk->b || !fk->chol_Q) {
-        set_error("model has a NULL m0/chol_P0/F/b/chol_Q host pointer");
-        return AUXSSM_ERR_ARG;
-    }
-    if (fk->potential != AUXSSM_POT_FLAT && !fk->y) {
-        set_error("potential needs observations y");
-        return AUXSSM_ERR_ARG;
-    }
-    if (fk->potential == AUXSSM_POT_GAUSS_OBS && !(fk->sig_y > 0)) {
-        set_error("sig_y must be > 0");
-        return AUXSSM_ERR_ARG;
-    }
-    if (noise->mode == AUXSSM_NOISE_EXPLICIT) {
-        if (!noise->eps_prop || !noise->u_res || !noise->eps_aux) {
-            set_error("explicit noise needs eps_aux (C,T,dx), eps_prop (C,T,N,dx) and u_res (C,T,N)");
-            return AUXSSM_ERR_ARG;
-        }
-    } else if (noise->mode != AUXSSM_NOISE_THREEFRY) {
-        set_error("unknown noise mode %d", noise->mode);
-        return AUXSSM_ERR_ARG;
-    }
-    std::vector<double> hm((size_t)2 * D + 3 * D * D);
-    {
-        double* p = hm.data();
-        memcpy(p, fk->m0, D * sizeof(double)); p += D;
-        memcpy(p, fk->chol_P0, D * D * sizeof(double)); p += D * D;
-        memcpy(p, fk->F, D * D * sizeof(double)); p += D * D;
-        memcpy(p, fk->b, D * sizeof(double)); p += D;
-        memcpy(p, fk->chol_Q, D * D * sizeof(double));
     }
     PitArgs a;
     memset(&a, 0, sizeof(a));
@@ -480,13 +422,5 @@ extern "C" int auxssm_csmc_pit_sweep(auxssm_handle h, int dtype, const auxssm_fk
     a.key0 = noise->key0; a.key1 = noise->key1;
     a.eps_aux = noise->eps_aux; a.eps_prop = noise->eps_prop; a.u_res = noise->u_res;
     if (!a.xs || !a.lw0 || !a.Ls || !a.Rs || !a.Fi || !a.La) return AUXSSM_ERR_NOMEM;
-#define AX_PIT_D(R)                                                    \
-    switch (D) {                                                       \
-        case 1: return run_pit<R, 1>(h, fk, hm.data(), a, ctt);             \
-        case 2: return run_pit<R, 2>(h, fk, hm.data(), a, ctt);             \
-        case 3: return run_pit<R, 3>(h, fk, hm.data(), a, ctt);             \
-        default: return run_pit<R, 4>(h, fk, hm.data(), a, ctt);            \
-    }
-    if (dtype == AUXSSM_F32) { AX_PIT_D(float) } else { AX_PIT_D(double) }
-#undef AX_PIT_D
+    return csmc_dispatch(dtype, D, [&](auto r, auto d) { return run_pit<decltype(r), decltype(d)::value>(h, fk, a, ctt); });
 }

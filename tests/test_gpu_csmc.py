@@ -128,7 +128,7 @@ def test_c3_shape_instantiation_equals_the_generic_kernel_bit_for_bit(monkeypatc
 @pytest.mark.parametrize("d,N,T,C", [(1, 64, 2, 3), (1, 100, 7, 2), (3, 512, 8, 4), (2, 33, 65, 5), (4, 1024, 5, 2)])
 @pytest.mark.parametrize("proposal", ["independent", "bootstrap"])
 def test_draws_generated_ahead_of_the_forward_pass_equal_in_kernel_draws(dtype, d, N, T, C, proposal, monkeypatch):
-    """Fewer chains than CUs: the forward pass's Threefry draws are written out by a separate full-chip kernel first (csmc_dev.h::k_csmc_pregen) and read back
+    """Fewer chains than CUs: the forward pass's Threefry draws are written out by a separate full-chip kernel first (csmc_sweep.h::k_csmc_pregen) and read back
     as explicit arrays.  Same trajectories, ancestors, particle systems and log-weights bit for bit as with the draws made inside the pass
     (AUXSSM_CSMC_NO_PREGEN=1), for odd and even T, partial last waves and every state dimension of the register kernels."""
     from aux_ssm_samplers_amd import random as R

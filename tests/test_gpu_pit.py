@@ -168,6 +168,25 @@ def test_argument_errors():
         _device.pit_sweep(fk, np.zeros((1, 1)), 8, key=0, delta=0.5)   # T >= 2
     with pytest.raises(ValueError):
         _device.pit_sweep(fk, np.zeros((4, 1)), 2048, key=0, delta=0.5)
+    # the model checks the parallel-in-time and the sequential sweep share (csrc/csmc_host.h::check_fk_model): refused by both entry points
+    from aux_ssm_samplers_amd import _lib
+    F_t = _lib.default_handle().zeros((3, 1, 1), np.float64)
+    G0g, Gtg = _pot(O.POT_GAUSS_OBS, np.ones((4, 1)))
+    for fields, msg in ((dict(potential=9), "unknown potential kind"), (dict(sig_y=0.0), "sig_y must be > 0"), (dict(gradient=7), "unknown gradient mode"),
+                        (dict(y=None), "needs observations y"), (dict(F_t=F_t.ptr.value), "F_t, b_t and chol_Q_t together")):
+        fkg = _device.describe_independent(M0, G0g, Mt, Gtg, Mt)
+        struct = fkg.struct
+
+        def tampered(handle, dtype, T, struct=struct, fields=fields):
+            m = struct(handle, dtype, T)
+            for name, value in fields.items():
+                setattr(m, name, value)
+            return m
+        fkg.struct = tampered
+        with pytest.raises(ValueError, match=msg):
+            _device.pit_sweep(fkg, np.zeros((4, 1)), 8, key=0, delta=0.5)
+        with pytest.raises(ValueError, match=msg):
+            _device.sweep(fkg, np.zeros((4, 1)), 8, True, key=0, delta=0.5)
 
 
 def test_full_size_properties_T65536():
