@@ -55,7 +55,7 @@ class FkUser(C.Structure):
 
 
 FK_USER_POTENTIAL, FK_USER_MEAN, FK_USER_GRADIENT = 1, 2, 4
-PROP_BOOTSTRAP_LG, PROP_AUX_INDEPENDENT = 0, 1
+PROP_BOOTSTRAP_LG, PROP_AUX_INDEPENDENT, PROP_AUX_GUIDED = 0, 1, 2
 POT_FLAT, POT_GAUSS_OBS, POT_SV, POT_GAUSS_OBS_MASKED = 0, 1, 2, 3
 TRANS_LINEAR, TRANS_LORENZ63_EM = 0, 1
 NOISE_EXPLICIT, NOISE_THREEFRY = 0, 1

@@ -281,6 +281,30 @@ def describe_independent(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE, parallel=F
     return FkDesc(_lib.PROP_AUX_INDEPENDENT, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk, gradient)
 
 
+def describe_guided(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE):
+    """csmc.get_guided_kernel: proposals N(pred + K_t (u_t - pred), P - K_t P) conditioned on the auxiliary variable AND the parent (pred = m0 / P = P0
+    at t = 0, pred = the transition mean of the parent / P = Q after), K_t = P (P + delta_t/2 I)^-1; with a gradient, u_t is shifted by
+    delta_t/2 grad log g_t(u_t) inside the proposal mean.  The closed model family with time-invariant transitions only."""
+    if _is_user(M0, G0, Mt, Gt):
+        raise NotImplementedError("guided proposals run the closed model family only: user-defined models (DevicePotential / DeviceGaussianDynamics) "
+                                  "are not compiled into the guided kernels")
+    M0, Mt = _dyn(M0, Mt)
+    if isinstance(Mt, LinearGaussianDynamics) and Mt.time_varying:
+        raise NotImplementedError("guided proposals run time-invariant transitions: time-varying LinearGaussianDynamics is not supported with them")
+    if Pt is not None and Pt is not Mt:
+        raise NotImplementedError("Pt must be the model dynamics Mt")
+    if gradient not in (_lib.GRAD_NONE, _lib.GRAD_REFERENCE):
+        raise NotImplementedError('guided proposals take gradient=False or True (the potential\'s gradient at u, as the reference has it): gradient="exact" '
+                                  "is a weighting of the independent proposals")
+    d = np.size(M0.m0)
+    pot, y, sig = _potential(G0, Gt, d)
+    tk, F, b = _trans(Mt)
+    return FkDesc(_lib.PROP_AUX_GUIDED, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk, gradient)
+
+
+_AUXILIARY = (_lib.PROP_AUX_INDEPENDENT, _lib.PROP_AUX_GUIDED)  # the proposals built around u = x + sqrt(delta / 2) eps_aux
+
+
 def key_noise(handle, key, Cn, T, N, d, dtype, wide=None):
     """The explicit noise arrays a THREEFRY sweep with `key` draws in-kernel (index map: csrc/csmc.hip::k_csmc_fwd): an
     EXPLICIT sweep on these arrays is bit-identical to the keyed one.  Debug / test utility.  wide (default: d > 4): the wide-state kernels
@@ -340,7 +364,7 @@ def sweep_resident(fk, chains, N, backward, key):
         raise ValueError(f"state dimension {d} != model dimension {fk.dx}")
     m = fk.struct(handle, chains.dtype, chains.T)
     shd = None
-    if fk.proposal == _lib.PROP_AUX_INDEPENDENT:
+    if fk.proposal in _AUXILIARY:
         if chains.sqrt_half_delta is None:
             raise ValueError("delta is required")
         shd = chains.sqrt_half_delta
@@ -446,7 +470,7 @@ def sweep(fk, x, N, backward, *, key=None, noise=None, delta=None, handle=None, 
     anc = handle.zeros((Cn, T), np.int32)
     m = fk.struct(handle, dtype, T)
     shd = None
-    if fk.proposal == _lib.PROP_AUX_INDEPENDENT:
+    if fk.proposal in _AUXILIARY:
         if delta is None:
             raise ValueError("delta is required")
         shd_h = np.sqrt(0.5 * np.asarray(delta, np.float64)) * np.ones(T)  # csmc/generic.py:61-63
@@ -457,7 +481,7 @@ def sweep(fk, x, N, backward, *, key=None, noise=None, delta=None, handle=None, 
         # the reference's own draws from this key (random.jax_csmc_noise), as explicit arrays; several chains: one key per chain, `key` (C, 2) or split(key, C)
         # (the plain cSMC kernel: its draws are made by the model's own M0.sample / Mt.sample in the reference -- one normal(key, (N, d)) per call in every model
         # the reference defines, which is what the device proposal kernels apply their Cholesky factors to)
-        aux = fk.proposal == _lib.PROP_AUX_INDEPENDENT
+        aux = fk.proposal in _AUXILIARY  # (the reference draws the same shapes for the independent and the guided kernel)
         kk = np.asarray(key, np.uint32)
         keys = kk if kk.ndim == 2 else (_random.as_key(key)[None] if Cn == 1 else _random.jax_split(_random.as_key(key), Cn))
         if keys.shape[0] != Cn:

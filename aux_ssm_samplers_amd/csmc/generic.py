@@ -3,7 +3,8 @@
 get_kernel(factory, N, backward=False, Pt=None) -> (init, kernel); kernel(key, state, delta) -> CSMCState.
 `factory(u, sqrt_half_delta) -> (M0, G0, Mt, Gt)` builds auxiliary model objects in the reference; here the factory
 must be one this package can describe for the device: the independent-proposal factory of csmc.independent (an
-`IndependentFactory`).  Any other callable raises NotImplementedError (no CPU fallback)."""
+`IndependentFactory`) or the guided-proposal factory of csmc.guided (a `GuidedFactory`).  Any other callable raises NotImplementedError
+(no CPU fallback)."""
 import numpy as np
 
 from .._primitives.csmc.base import CSMCState
@@ -25,7 +26,8 @@ def get_kernel(factory, N, backward=False, Pt=None):
         raise ValueError("If backward is True, the true dynamics `Pt` must be provided.")  # generic.py:44-45
     elif backward and not hasattr(Pt, "logpdf"):
         raise ValueError("`Pt` must implement a valid logpdf method.")  # generic.py:46-47
-    if not isinstance(factory, IndependentFactory):
+    from .guided import GuidedFactory
+    if not isinstance(factory, (IndependentFactory, GuidedFactory)):
         raise NotImplementedError(_device._UNSUPPORTED.format(what=f"factory={factory!r}"))
     fk = factory.fk
 

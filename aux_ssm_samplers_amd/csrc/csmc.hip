@@ -107,6 +107,7 @@ static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void*
     const int TB = (a.N + 63) / 64 * 64;
     fk_time_varying<R>(h, fk, a.T, ctt, m);
     if (a.gb) fk_potbound<R>(h, a, m);
+    const bool guided = fk->proposal == AUXSSM_PROP_AUX_GUIDED;
     if (fk->proposal == 1) {
         const long long total = (long long)a.C * a.T * D;
         hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
@@ -114,6 +115,10 @@ static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void*
             const long long tot = (long long)a.C * a.T;
             hipLaunchKernelGGL((k_csmc_grad<R, D>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, a, m);
         }
+    } else if (guided) {
+        const long long total = (long long)a.C * a.T * D;
+        hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
+        fk_guided<R>(h, a, m);
     }
     // forward + backward pass, batch of chains by batch (CsmcArgs::c0; one batch unless the particle systems of all chains do not fit the device)
     const int cb = a.cb > 0 ? a.cb : a.C;
@@ -137,7 +142,18 @@ static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void*
     } while (0)
         const bool c3_shape = D == 1 && sizeof(R) == 4 && fullw == 16 && !tv && !gr && fk->proposal == 1 && fk->potential == 2 && m.transition == 0 &&
                               ab.As == nullptr && ab.noise_mode != 0 && !ab.pregen;
-        if (c3_shape) {
+        if (guided) {  // the guided instantiations (SP = 2): time-invariant transitions; N = 1024 as sixteen full waves, any other N through the generic one
+#define AX_FWDG(GRv, NWv)                                                                                                                                          \
+    do {                                                                                                                                                           \
+        if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_csmc_fwd<R, D, false, GRv, NWv, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        hipLaunchKernelGGL((k_csmc_fwd<R, D, false, GRv, NWv, 2>), dim3(ab.C), dim3(TB), lds, h->stream, ab, m);                                                   \
+    } while (0)
+            if (gr && fullw == 16) AX_FWDG(true, 16);
+            else if (gr) AX_FWDG(true, 0);
+            else if (fullw == 16) AX_FWDG(false, 16);
+            else AX_FWDG(false, 0);
+#undef AX_FWDG
+        } else if (c3_shape) {
             if constexpr (D == 1 && sizeof(R) == 4) {
                 if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_csmc_fwd<R, D, false, false, 16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 hipLaunchKernelGGL((k_csmc_fwd<R, D, false, false, 16, 1>), dim3(ab.C), dim3(TB), lds, h->stream, ab, m);
@@ -343,22 +359,34 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
         set_error("dx=%d runs the wide-state cSMC kernels: N <= 64 particles, linear-Gaussian transitions", D);
         return AUXSSM_ERR_UNSUPPORTED;
     }
-    if (fk->proposal != AUXSSM_PROP_BOOTSTRAP_LG && fk->proposal != AUXSSM_PROP_AUX_INDEPENDENT) {
+    if (fk->proposal != AUXSSM_PROP_BOOTSTRAP_LG && fk->proposal != AUXSSM_PROP_AUX_INDEPENDENT && fk->proposal != AUXSSM_PROP_AUX_GUIDED) {
         set_error("unknown proposal kind %d", fk->proposal);
         return AUXSSM_ERR_ARG;
     }
+    const bool guided = fk->proposal == AUXSSM_PROP_AUX_GUIDED, auxiliary = guided || fk->proposal == AUXSSM_PROP_AUX_INDEPENDENT;
+    if (guided && prog) {
+        set_error("guided proposals run the closed model family: they are not compiled into user-defined programs");
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    if (guided && (fk->F_t || fk->b_t || fk->chol_Q_t)) {
+        set_error("guided proposals run time-invariant transitions");
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
     if (int rc = check_fk_model(fk, noise, ug)) return rc;
-    if (fk->proposal == AUXSSM_PROP_AUX_INDEPENDENT && !sqrt_half_delta) {
-        set_error("the auxiliary proposal needs sqrt_half_delta (T)");
+    if (auxiliary && !sqrt_half_delta) {
+        set_error("the auxiliary proposals need sqrt_half_delta (T)");
         return AUXSSM_ERR_ARG;
     }
-    if (fk->gradient != AUXSSM_GRAD_NONE && fk->proposal != AUXSSM_PROP_AUX_INDEPENDENT) {
-        set_error("gradient-informed proposals belong to AUXSSM_PROP_AUX_INDEPENDENT");
+    if (fk->gradient != AUXSSM_GRAD_NONE && !auxiliary) {
+        set_error("gradient-informed proposals belong to AUXSSM_PROP_AUX_INDEPENDENT and AUXSSM_PROP_AUX_GUIDED");
         return AUXSSM_ERR_ARG;
     }
-    if (noise->mode == AUXSSM_NOISE_EXPLICIT &&
-        (!noise->eps_prop || !noise->u_bwd || (T > 1 && !noise->u_res) || (fk->proposal == AUXSSM_PROP_AUX_INDEPENDENT && !noise->eps_aux))) {
-        set_error("explicit noise needs eps_prop, u_res, u_bwd (and eps_aux for the auxiliary proposal)");
+    if (guided && fk->gradient != AUXSSM_GRAD_NONE && fk->gradient != AUXSSM_GRAD_REFERENCE) {
+        set_error("guided proposals take AUXSSM_GRAD_NONE or AUXSSM_GRAD_REFERENCE (the potential's gradient at u shifts the proposal mean; there is no other weighting)");
+        return AUXSSM_ERR_ARG;
+    }
+    if (noise->mode == AUXSSM_NOISE_EXPLICIT && (!noise->eps_prop || !noise->u_bwd || (T > 1 && !noise->u_res) || (auxiliary && !noise->eps_aux))) {
+        set_error("explicit noise needs eps_prop, u_res, u_bwd (and eps_aux for the auxiliary proposals)");
         return AUXSSM_ERR_ARG;
     }
     const size_t sR = dtype == AUXSSM_F32 ? 4 : 8;
@@ -398,6 +426,7 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
     need += 2 * (CT * sR + 256);  // fmax, the backward pass's uniforms
     need += (size_t)T * sR + 256;  // gb
     need += 2 * (CT * D * sR + 256) + (size_t)T * (1 + D) * sR + 256;
+    if (guided) need += guided_tab_reals(T, D) * sR + 256;  // K_t, chol Lambda_t and their constants, every step
     // fewer chains than CUs: the forward pass's draws are generated up front by the whole chip (csmc_sweep.h::k_csmc_pregen) when the two arrays fit
     const size_t pre_eps = CT * N * D * sR + 256, pre_u = (size_t)C * (T > 1 ? T - 1 : 1) * N * sR + 256;
     bool pregen = noise->mode == AUXSSM_NOISE_THREEFRY && !wide && T > 1 && C < h->num_cu && cb == C &&
@@ -423,7 +452,9 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
     a.As = As_out ? As_out : (!backward ? (int32_t*)ws_take(h, (size_t)cb * (T > 1 ? T - 1 : 1) * N * 4) : nullptr);
     a.wT = ws_take(h, (size_t)C * N * sR);
     a.fmax = ws_take(h, (size_t)C * T * sR);
-    a.gb = (ug ? prog->has_bound : (fk->potential == 0 || fk->y != nullptr)) ? ws_take(h, (size_t)T * sR) : nullptr;
+    // (the guided weights are not bounded by gb + c_trans: no bound array, every step shifts by its exact maximum)
+    a.gb = !guided && (ug ? prog->has_bound : (fk->potential == 0 || fk->y != nullptr)) ? ws_take(h, (size_t)T * sR) : nullptr;
+    a.gtab = guided ? ws_take(h, guided_tab_reals(T, D) * sR) : nullptr;
     a.anc = ancestors;
     a.noise_mode = noise->mode;
     a.key0 = noise->key0; a.key1 = noise->key1;
@@ -436,7 +467,7 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
         else hipLaunchKernelGGL((k_csmc_ubwd<double>), dim3((unsigned)(((n + 1) / 2 + 255) / 256)), dim3(256), 0, h->stream, n, noise->key0, noise->key1, (double*)ub);
         a.u_bwd = ub;
     }
-    if (!a.u || !a.xs || !a.lws || !a.wT || !a.fmax || (!backward && !a.As) || (fk->gradient && !a.grad) || (fk->F_t && !ctt)) return AUXSSM_ERR_NOMEM;
+    if (!a.u || !a.xs || !a.lws || !a.wT || !a.fmax || (!backward && !a.As) || (fk->gradient && !a.grad) || (fk->F_t && !ctt) || (guided && !a.gtab)) return AUXSSM_ERR_NOMEM;
     if (pregen) {
         void* pe = ws_take(h, pre_eps - 256);
         void* pu = ws_take(h, pre_u - 256);

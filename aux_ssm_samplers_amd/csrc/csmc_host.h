@@ -8,6 +8,7 @@
 
 #include "ctx.h"
 #include "csmc_sweep.h"
+#include "csmc_guided.h"
 
 namespace ax {
 
@@ -143,6 +144,17 @@ template <typename R> __global__ void k_csmc_potbound(int T, int D, int potentia
 }
 template <typename R, typename M> static void fk_potbound(auxssm_ctx* h, const CsmcArgs& a, const M& m) {
     hipLaunchKernelGGL((k_csmc_potbound<R>), dim3((a.T + 255) / 256), dim3(256), 0, h->stream, a.T, m.D, m.potential, m.c_obs, (const R*)a.y, (R*)a.gb);
+}
+
+// guided proposals (AUXSSM_PROP_AUX_GUIDED), after k_csmc_aux has formed u: the shifted auxiliary variables of the gradient variant into a.grad and the tables
+// of the T steps into a.gtab ((2 D D + D + 4) reals per step: guided_tab_reals).  Rebuilt at every sweep: delta may change between sweeps.
+static size_t guided_tab_reals(int T, int D) { return (size_t)T * ((size_t)2 * D * D + D + 4); }
+template <typename R, typename M> static void fk_guided(auxssm_ctx* h, const CsmcArgs& a, const M& m) {
+    if (m.gradient) {
+        const long long total = (long long)a.C * a.T * m.D;
+        hipLaunchKernelGGL((k_csmc_gshift<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, m.D, m.potential, m.inv_sig_y);
+    }
+    hipLaunchKernelGGL((k_csmc_gtab<R, M>), dim3(a.T), dim3(64), 0, h->stream, a.T, m, (const R*)a.shd, (R*)a.gtab);
 }
 
 // the arguments of the batch [c0, c0 + cb) of chains (CsmcArgs::c0)

@@ -74,6 +74,7 @@ struct CsmcArgs {
     int c0 = 0;
     int cb = 0;                               // host side: chains per batch
     size_t xs_rec = 0, lws_rec = 0, As_rec = 0;  // host side: bytes per chain of the workspace-owned arrays (0: caller-owned, indexed globally anyway)
+    const void* gtab = nullptr;  // guided proposals only: the tables of the T steps (GuidedT; csmc_guided.h::k_csmc_gtab); `grad` then holds the shifted u
 };
 
 enum { STREAM_EPS_AUX = 1, STREAM_EPS_PROP = 2, STREAM_U_RES = 3, STREAM_U_BWD = 4 };
@@ -105,6 +106,50 @@ template <typename R, int D> AXD_HD R gauss_chol_logpdf(const R* x, const R* mea
     }
     return fma_((R)-0.5, q, cst);
 }
+// ---- guided proposals (AUXSSM_PROP_AUX_GUIDED) ------------------------------------------------------------------------------------------------------
+// x_t ~ N(mu_t, Lambda_t), mu_t = pred + K_t (u~_t - pred), K_t = P (P + s_t^2 I)^-1, Lambda_t = P - K_t P with pred / P = m0 / P0 at t = 0, the parent's transition
+// mean / Q after; weight log g_t(x) + log N(x; pred, P) + sum_k log N(x_k; u_k, s_t^2) - log N(x; mu_t, Lambda_t).  Row t of the table k_csmc_gtab builds per sweep:
+template <typename R> struct GuidedT {
+    const R *K, *L, *iL;   // K_t (D x D), chol Lambda_t (D x D lower) and its reciprocal diagonal, leading dimension D
+    R c_lam, c_u, inv_s;   // the additive constants of N(.; ., Lambda_t) and of sum_k N(.; u_k, s_t^2); 1 / s_t
+};
+template <typename R> __device__ __forceinline__ GuidedT<R> guided_at(const void* tab, int D, long long t) {
+    const R* p = (const R*)tab + t * (2 * D * D + D + 4);
+    const R* c = p + 2 * D * D + D;
+    return GuidedT<R>{p, p + D * D, p + 2 * D * D, c[0], c[1], c[2]};
+}
+// mu = pred + K (ut - pred), x = mu + L eps (rows in component order, explicit fma)
+template <typename R, int D> __device__ __forceinline__ void guided_propose(const GuidedT<R>& g, const R* pred, const R* ut, const R* eps, R* mu, R* x) {
+    R dv[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) dv[k] = ut[k] - pred[k];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        R acc = pred[k];
+#pragma unroll
+        for (int j = 0; j < D; ++j) acc = fma_(g.K[k * D + j], dv[j], acc);
+        mu[k] = acc;
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        R acc = mu[k];
+#pragma unroll
+        for (int j = 0; j <= k; ++j) acc = fma_(g.L[k * D + j], eps[j], acc);
+        x[k] = acc;
+    }
+}
+// lw + sum_k log N(x_k; u_k, s^2) - log N(x; mu, Lambda)   (lw = log g + log N(x; pred, P))
+template <typename R, int D> __device__ __forceinline__ R guided_weight(const GuidedT<R>& g, R lw, const R* x, const R* u, const R* mu) {
+    R q = 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const R z = (x[k] - u[k]) * g.inv_s;
+        q = fma_(z, z, q);
+    }
+    lw = lw + fma_((R)-0.5, q, g.c_u);
+    return lw - gauss_chol_logpdf<R, D>(x, mu, g.L, g.iL, g.c_lam, D);
+}
+
 template <typename R, int D> AXD_HD void trans_mean(const FkDev<R>& m, const R* xp, R* mu);
 // mean of the transition tr applied to xp (linear, or the Lorenz-63 Euler-Maruyama step of the invariant model)
 template <typename R, int D> __device__ __forceinline__ void trans_mean_t(const FkDev<R>& m, const TransT<R>& tr, const R* xp, R* mu) {
@@ -637,6 +682,8 @@ template <typename R, int D, typename P = FkBuiltin<R, D>, typename... PA> __glo
 // SP = 1: the instantiation of config C3's shape -- auxiliary independent proposals, the stochastic-volatility potential, a time-invariant linear transition, draws
 // generated in the kernel, no ancestor trace (backward sampling): the run-time switches on the model kind are folded at compile time (they are wave-uniform
 // branches, two dozen per time step); same operations on the same operands, bit for bit (tests/test_gpu_csmc.py runs both instantiations on C3's model)
+// SP = 2: the guided proposals (GuidedT above; time-invariant transitions, GRAD = the proposal mean reads the shifted u of CsmcArgs::grad): a compile-time variant, so
+// that the instantiations of the other proposals hold none of its code; its weights have no reduction-free bound (CsmcArgs::gb is null: exact maxima)
 // P: the model policy (above); PA: its kernel arguments (none for the built-in family, so the built-in kernels take exactly (CsmcArgs, FkDev) as before)
 template <typename R, int D, bool TV, bool GRAD, int NW, int SP = 0, typename P = FkBuiltin<R, D>, typename... PA>
 __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA... pa) {
@@ -693,7 +740,12 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
         }
         ycur[k] = yv ? yv[k] : (R)0;
     }
-    if (m.proposal == 0) {  // M0 = N(m0, P0)
+    if constexpr (SP == 2) {  // guided: pred = m0, P = P0
+        R ut[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) ut[k] = gaux[k];
+        guided_propose<R, D>(guided_at<R>(a.gtab, D, 0), m.m0, ut, eps, pm, x);
+    } else if (m.proposal == 0) {  // M0 = N(m0, P0)
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             R acc = m.m0[k];
@@ -716,7 +768,10 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
     R lw;
     {
         R g = pol.log_g(m, 0, x, nullptr, ycur);
-        if (m.proposal == 1) {
+        if constexpr (SP == 2) {
+            g = g + gauss_chol_logpdf<R, D>(x, m.m0, m.LP0, m.iLP0, m.c_init);
+            g = guided_weight<R, D>(guided_at<R>(a.gtab, D, 0), g, x, uaux, pm);
+        } else if (m.proposal == 1) {
             g = g + gauss_chol_logpdf<R, D>(x, m.m0, m.LP0, m.iLP0, m.c_init);  // AuxiliaryG0 (independent.py:163-169)
             if constexpr (GRAD) g = g + grad_correction<R, D>(x, uaux, pm, ((const R*)a.shd)[0]);  // GradientAuxiliaryG0 (:173-190)
         }
@@ -779,7 +834,13 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
         for (int k = 0; k < D; ++k) xp[k] = xprev[idx * D + k];
         // propagate (csmc.py:91-92); the transition t - 1 -> t (time-varying: row t - 1 of the device arrays)
         const TransT<R> tr = trans_at_c<R, D, TV>(m, t - 1);
-        if (m.proposal == 0) {
+        if constexpr (SP == 2) {  // guided: pred = the parent's transition mean, P = Q
+            R mu[D], ut[D];
+            pol.mean(m, tr, t, xp, mu);
+#pragma unroll
+            for (int k = 0; k < D; ++k) ut[k] = gaux[(long long)t * D + k];
+            guided_propose<R, D>(guided_at<R>(a.gtab, D, t), mu, ut, eps, pm, x);
+        } else if (m.proposal == 0) {
             R mu[D];
             pol.mean(m, tr, t, xp, mu);
 #pragma unroll
@@ -803,7 +864,12 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
         }
         // weights (csmc.py:95-96)
         R g = pol.log_g(m, t, x, xp, ycur);
-        if (m.proposal == 1) {  // AuxiliaryGt = Mt.logpdf + Gt (independent.py:238-248)
+        if constexpr (SP == 2) {
+            R mu[D];
+            pol.mean(m, tr, t, xp, mu);
+            g = g + gauss_chol_logpdf<R, D>(x, mu, tr.LQ, tr.iL, tr.c_trans, tr.ld);
+            g = guided_weight<R, D>(guided_at<R>(a.gtab, D, t), g, x, uaux + (long long)t * D, pm);
+        } else if (m.proposal == 1) {  // AuxiliaryGt = Mt.logpdf + Gt (independent.py:238-248)
             R mu[D];
             pol.mean(m, tr, t, xp, mu);
             g = gauss_chol_logpdf<R, D>(x, mu, tr.LQ, tr.iL, tr.c_trans, tr.ld) + g;

@@ -8,6 +8,8 @@
 // chain while there are CUs to spare (8 beyond), the model's matrices in LDS.  Linear-Gaussian transitions, every potential / proposal of the family,
 // gradient-informed proposals (csmc/independent.py:57-75 gradient=True, :173-190, :252-268; both AUXSSM_GRAD_* weightings: the reference's own SV protocol
 // exposes --gradient at D = 30) and time-varying transitions (the step's F_t, b_t, chol Q_t re-staged into LDS before the step's first barrier) since round 4.
+// Guided proposals (AUXSSM_PROP_AUX_GUIDED, csmc_sweep.h::GuidedT) are a compile-time variant of the forward kernel (k_cw2_fwd<R, NW2, true>): the step's K_t and chol Lambda_t staged
+// into LDS like a time-varying transition, one more row product and one more blocked log-density per particle; the backward kernel is shared.
 // (The first version of this file -- one wave per chain, one lane per particle walking its dx x dx products alone: 30.5 ms per sweep of the SV protocol against
 // 2.6 now -- is in the history)
 //
@@ -34,6 +36,8 @@ template <typename R> struct FkW {
 template <typename R> struct TransW {
     const R *F, *b, *LQ;
 };
+// element (i, j) of chol P0 (init) or chol Q (csmc_guided.h::k_csmc_gtab)
+template <typename R> __device__ __forceinline__ R gt_chol(const FkW<R>& m, bool init, int i, int j) { return (init ? m.LP0 : m.LQ)[i * m.D + j]; }
 template <typename R> __device__ __forceinline__ TransW<R> trans_w(const FkW<R>& m, long long t) {
     const long long D = m.D;
     if (m.Ft) return TransW<R>{m.Ft + t * D * D, m.bt + t * D, m.LQt + t * D * D};
@@ -138,7 +142,8 @@ template <typename R> struct Cw2Lds {
     int D, S;
     R *F, *LQ, *b, *iL, *c, *lwv, *xa, *xb, *eps, *blk;
     int* idx;
-    __device__ Cw2Lds(char* smem, int D_) : D(D_), S(CSW_MAXD + 1) {  // rows padded with zeros to 32 columns (+ 1: odd stride): every component loop runs 32 steps, unrolled
+    R *Kg, *Lg, *blkg, *dv;  // guided proposals only (behind idx): the step's K_t and chol Lambda_t, the block table of chol Lambda_t, u~ - pred of every half-wave
+    __device__ Cw2Lds(char* smem, int D_, bool guided = false) : D(D_), S(CSW_MAXD + 1) {  // rows padded with zeros to 32 columns (+ 1: odd stride): every component loop runs 32 steps, unrolled
         F = (R*)smem;           // [D][S]
         LQ = F + D * S;         // [D][S]
         b = LQ + D * S;
@@ -150,9 +155,30 @@ template <typename R> struct Cw2Lds {
         eps = xb + 64 * S;      // [64][S]
         blk = eps + 64 * S;     // [8][12] the 4 x 4 diagonal blocks of chol Q and the reciprocal diagonal, in the order gauss_half_blk reads them
         idx = (int*)(blk + 96);  // [64]
+        if (guided) {
+            Kg = (R*)(idx + 64);  // [D][S]
+            Lg = Kg + D * S;      // [D][S]
+            blkg = Lg + D * S;    // [8][12]
+            dv = blkg + 96;       // [32][S]
+        }
     }
-    static size_t bytes(int D) { return ((size_t)2 * D * (CSW_MAXD + 1) + 2 * D + 128 + (size_t)3 * 64 * (CSW_MAXD + 1) + 96) * sizeof(R) + 64 * sizeof(int) + 64; }
+    static constexpr size_t guided_bytes(int D) { return ((size_t)2 * D * (CSW_MAXD + 1) + 96 + (size_t)32 * (CSW_MAXD + 1)) * sizeof(R); }
+    static constexpr size_t bytes(int D) { return ((size_t)2 * D * (CSW_MAXD + 1) + 2 * D + 128 + (size_t)3 * 64 * (CSW_MAXD + 1) + 96) * sizeof(R) + 64 * sizeof(int) + 64; }
 };
+// entry `tid` (< 96) of the block table gauss_half_blk reads, for the lower factor Lf (leading dimension D) with reciprocal diagonal iLf:
+// block jb = 4 (tid / 12): [L10 L20 L21 L30 L31 L32 | i0 i1 i2 i3 | 0 0], zeros beyond D
+template <typename R> __device__ __forceinline__ R cw2_blk_entry(const R* Lf, const R* iLf, int D, int tid) {
+    const int bq = tid / 12, e = tid - 12 * bq, jb = 4 * bq;
+    const int rr[6] = {1, 2, 2, 3, 3, 3}, cc[6] = {0, 0, 1, 0, 1, 2};
+    R v = 0;
+    if (e < 6) {
+        const int r = jb + rr[e], q = jb + cc[e];
+        v = r < D ? Lf[r * D + q] : (R)0;
+    } else if (e < 10) {
+        v = jb + e - 6 < D ? iLf[jb + e - 6] : (R)0;
+    }
+    return v;
+}
 template <typename R> __device__ __forceinline__ void cw2_stage(const FkW<R>& m, Cw2Lds<R>& L, int tid, int nt) {
     const int D = m.D, S = L.S;
     for (int i = tid; i < D * S; i += nt) {
@@ -162,18 +188,7 @@ template <typename R> __device__ __forceinline__ void cw2_stage(const FkW<R>& m,
     }
     for (int i = tid; i < D; i += nt) L.b[i] = m.b[i], L.iL[i] = m.iLQ[i];
     for (int i = tid; i < 64 * S; i += nt) L.xa[i] = 0, L.xb[i] = 0, L.eps[i] = 0;
-    if (tid < 96) {  // block jb = 4 (tid / 12): [L10 L20 L21 L30 L31 L32 | i0 i1 i2 i3 | 0 0], zeros beyond D
-        const int bq = tid / 12, e = tid - 12 * bq, jb = 4 * bq;
-        const int rr[6] = {1, 2, 2, 3, 3, 3}, cc[6] = {0, 0, 1, 0, 1, 2};
-        R v = 0;
-        if (e < 6) {
-            const int r = jb + rr[e], q = jb + cc[e];
-            v = r < D ? m.LQ[r * D + q] : (R)0;
-        } else if (e < 10) {
-            v = jb + e - 6 < D ? m.iLQ[jb + e - 6] : (R)0;
-        }
-        L.blk[tid] = v;
-    }
+    if (tid < 96) L.blk[tid] = cw2_blk_entry<R>(m.LQ, m.iLQ, D, tid);
     __syncthreads();
 }
 // time-varying transitions: the rows of transition tt -> tt + 1 replace the staged model (same layout; called by every thread between the two barriers that
@@ -190,18 +205,18 @@ template <typename R> __device__ __forceinline__ void cw2_stage_t(const FkW<R>& 
         L.LQ[i] = q < D ? LQ[r * D + q] : (R)0;
     }
     for (int i = tid; i < D; i += nt) L.b[i] = b[i], L.iL[i] = iL[i];
-    if (tid < 96) {
-        const int bq = tid / 12, e = tid - 12 * bq, jb = 4 * bq;
-        const int rr[6] = {1, 2, 2, 3, 3, 3}, cc[6] = {0, 0, 1, 0, 1, 2};
-        R v = 0;
-        if (e < 6) {
-            const int r = jb + rr[e], q = jb + cc[e];
-            v = r < D ? LQ[r * D + q] : (R)0;
-        } else if (e < 10) {
-            v = jb + e - 6 < D ? iL[jb + e - 6] : (R)0;
-        }
-        L.blk[tid] = v;
+    if (tid < 96) L.blk[tid] = cw2_blk_entry<R>(LQ, iL, D, tid);
+}
+// guided proposals: the step's K_t and chol Lambda_t (row t of the table k_csmc_gtab built) into LDS, rows zero-padded like the model's, and the block table of
+// chol Lambda_t in the order gauss_half_blk reads it; called where cw2_stage_t is, between the two barriers that separate the particle sections of two steps
+template <typename R> __device__ __forceinline__ void cw2_stage_g(const GuidedT<R>& g, Cw2Lds<R>& L, int tid, int nt) {
+    const int D = L.D, S = L.S;
+    for (int i = tid; i < D * S; i += nt) {
+        const int r = i / S, q = i - r * S;
+        L.Kg[i] = q < D ? g.K[r * D + q] : (R)0;
+        L.Lg[i] = q < D ? g.L[r * D + q] : (R)0;
     }
+    if (tid < 96) L.blkg[tid] = cw2_blk_entry<R>(g.L, g.iL, D, tid);
 }
 // value of lane J of MY half-wave: ds_swizzle in bit mode (lane' = (lane & and) | or inside each group of 32 lanes, and = 0, or = J) -- one LDS-crossbar
 // instruction, no memory, no scalar round trip (two v_readlane + two v_mov + a select before: the component loops are bound by the CU's instruction issue,
@@ -309,6 +324,16 @@ template <typename R> __device__ __forceinline__ R potential_half(const FkW<R>& 
     static_for<0, CSW_MAXD>([&](auto jc) { acc += half_bcast<R, decltype(jc)::value>(v); });
     return acc;
 }
+// sum_k log N(x_k; u_k, s^2) = c_u - sum_k ((x_k - u_k) / s)^2 / 2 of the particle whose component k this lane holds (csmc_sweep.h::guided_weight: component order)
+template <typename R> __device__ __forceinline__ R nu_half(int D, int k, R xk, R uk, R inv_s, R c_u) {
+    const R z = k < D ? (xk - uk) * inv_s : (R)0;
+    R q = 0;
+    static_for<0, CSW_MAXD>([&](auto jc) {
+        const R zj = half_bcast<R, decltype(jc)::value>(z);
+        q = fma_(zj, zj, q);
+    });
+    return fma_((R)-0.5, q, c_u);
+}
 // this step's proposal noise into the LDS rows eps[n][k]: natural flat index ((ch T + t) N + n) D + k of stream 2, both normals of every Threefry block used
 template <typename R> __device__ __forceinline__ void cw2_draw(const CsmcArgs& a, Cw2Lds<R>& L, int ch, int t, int r, int nr) {
     const int N = a.N, D = L.D, S = L.S, ND = N * D;
@@ -336,19 +361,20 @@ template <typename R> __device__ __forceinline__ void cw2_draw(const CsmcArgs& a
     }
 }
 
-template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2_fwd(CsmcArgs a, FkW<R> m) {
+// GD: the guided proposals, a compile-time variant; false: the kernel as it was, holding none of their code
+template <typename R, int NW2, bool GD = false> __global__ void __launch_bounds__(64 * NW2) k_cw2_fwd(CsmcArgs a, FkW<R> m) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT_ = 64 * NW2;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, N = a.N, T = a.T, D = m.D;
     const bool hi = lane >= 32;
     const int k = lane & 31;
-    Cw2Lds<R> L(smem, D);
+    Cw2Lds<R> L(smem, D, GD);
     cw2_stage<R>(m, L, tid, NT_);
     const int S = L.S, nslot = (N + 2 * NW2 - 1) / (2 * NW2);
     const int ch = a.c0 + blockIdx.x;
     const R* xstar = (const R*)a.x + (long long)ch * T * D;
     const R* uaux = (const R*)a.u + (long long)ch * T * D;
-    const bool grad = m.gradient != 0 && m.proposal == 1, tv = m.Ft != nullptr;
+    const bool grad = m.gradient != 0 && (GD || m.proposal == 1), tv = m.Ft != nullptr;  // (guided: a.grad holds the shifted u the proposal mean reads)
     const R* gaux = grad ? (const R*)a.grad + (long long)ch * T * D : uaux;
     const R* yv = (const R*)a.y;
     R* xs = (R*)a.xs + (long long)ch * T * N * D;
@@ -361,16 +387,35 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
     R bk = k < D ? L.b[k] : (R)0;
     const R* Frow = L.F + (k < D ? k : 0) * S;
     const R* Lrow = L.LQ + (k < D ? k : 0) * S;
+    // guided: this lane's rows of the staged K_t / chol Lambda_t and its half-wave's row of u~ - pred
+    const R* Kgrow = GD ? L.Kg + (k < D ? k : 0) * S : nullptr;
+    const R* Lgrow = GD ? L.Lg + (k < D ? k : 0) * S : nullptr;
+    R* dvr = GD ? L.dv + (2 * wv + (hi ? 1 : 0)) * S : nullptr;
 
     // ---- t = 0 (csmc.py:74-80)
     cw2_draw<R>(a, L, ch, 0, tid, NT_);
+    if constexpr (GD) cw2_stage_g<R>(guided_at<R>(a.gtab, D, 0), L, tid, NT_);
     __syncthreads();
     for (int s = 0; s < nslot; ++s) {
         const int i = s * 2 * NW2 + 2 * wv + (hi ? 1 : 0);
         const bool pl = i < N;  // (uniform per half-wave)
         const int ir = pl ? i : 0;
         R xk = 0, acc0 = 0, pmk = 0;
-        if (k < D) {
+        if constexpr (GD) {  // pred = m0, P = P0: x ~ N(m0 + K_0 (u~_0 - m0), Lambda_0)
+            const R m0k = k < D ? m.m0[k] : (R)0;
+            dvr[k] = k < D ? gaux[k] - m0k : (R)0;
+            __builtin_amdgcn_wave_barrier();  // (a half-wave reads back only its own row: ordered inside the wave)
+            pmk = m0k;
+#pragma unroll
+            for (int j = 0; j < CSW_MAXD; ++j) pmk = fma_(Kgrow[j], dvr[j], pmk);
+            R acc = pmk;
+#pragma unroll
+            for (int j = 0; j < CSW_MAXD; ++j) acc = j <= k ? fma_(Lgrow[j], L.eps[ir * S + j], acc) : acc;
+            if (k < D) {
+                xk = i == 0 ? xstar[k] : acc;
+                acc0 = xk - m0k;
+            }
+        } else if (k < D) {
             if (m.proposal == 0) {
                 R acc = m.m0[k];
                 for (int j = 0; j <= k; ++j) acc = fma_(m.LP0[k * D + j], L.eps[ir * S + j], acc);
@@ -386,7 +431,12 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
         const R yk = (yv && k < D) ? yv[k] : (R)0;
         R g = potential_half<R>(m, k, hi, xk, yk);
         if (m.proposal == 1) g = g + gauss_half<R>(D, k, hi, acc0, m.LP0 + (long long)(k < D ? k : 0) * D, k < D ? m.iLP0[k] : (R)0, m.c_init);  // AuxiliaryG0
-        if (grad) g = g + grad_corr_half<R>(D, k, xk, k < D ? uaux[k] : (R)0, pmk, ((const R*)a.shd)[0]);  // GradientAuxiliaryG0 (:173-190)
+        if constexpr (GD) {  // log g + log N(x; m0, P0) + sum_k log N(x_k; u_k, s^2) - log N(x; mu, Lambda_0)
+            const GuidedT<R> gd = guided_at<R>(a.gtab, D, 0);
+            g = g + gauss_half<R>(D, k, hi, acc0, m.LP0 + (long long)(k < D ? k : 0) * D, k < D ? m.iLP0[k] : (R)0, m.c_init);
+            g = g + nu_half<R>(D, k, xk, k < D ? uaux[k] : (R)0, gd.inv_s, gd.c_u);
+            g = g - gauss_half_blk<R>(D, k, xk - pmk, Lgrow, L.blkg, gd.c_lam);
+        } else if (grad) g = g + grad_corr_half<R>(D, k, xk, k < D ? uaux[k] : (R)0, pmk, ((const R*)a.shd)[0]);  // GradientAuxiliaryG0 (:173-190)
         if (pl && k < D) {
             L.xa[i * S + k] = xk;
             xs[(long long)i * D + k] = xk;
@@ -408,6 +458,12 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
         const R gk = (grad && k < D) ? gaux[(long long)t * D + k] : (R)0;
         const R ctr = tv ? m.ctt[t - 1] : m.c_trans;  // the transition t - 1 -> t (time-varying: row t - 1)
         if (tv) cw2_stage_t<R>(m, L, t - 1, tid, NT_);  // (the previous step's particle section is behind its barrier)
+        R c_lam = 0, c_u = 0, inv_s = 0;
+        if constexpr (GD) {
+            const GuidedT<R> gd = guided_at<R>(a.gtab, D, t);
+            c_lam = gd.c_lam, c_u = gd.c_u, inv_s = gd.inv_s;
+            cw2_stage_g<R>(gd, L, tid, NT_);
+        }
         if (wv == 0) {
             // weights of step t - 1 and the conditional multinomial resampling (resamplings.py:14-37), one lane per particle
             const bool live = lane < N;
@@ -453,7 +509,17 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
 #pragma unroll
             for (int j = 0; j < CSW_MAXD; ++j) mu = fma_(Frow[j], xp[j], mu);  // (columns beyond D are zeros on both sides: fma(0, 0, mu) = mu)
             R xk = 0, pmk = 0;
-            if (k < D) {
+            if constexpr (GD) {  // x ~ N(mu + K_t (u~_t - mu), Lambda_t): one more row product, the draw as the bootstrap branch has it
+                dvr[k] = k < D ? (grad ? gk : uk) - mu : (R)0;
+                __builtin_amdgcn_wave_barrier();  // (a half-wave reads back only its own row: ordered inside the wave)
+                pmk = mu;
+#pragma unroll
+                for (int j = 0; j < CSW_MAXD; ++j) pmk = fma_(Kgrow[j], dvr[j], pmk);
+                R acc = pmk;
+#pragma unroll
+                for (int j = 0; j < CSW_MAXD; ++j) acc = j <= k ? fma_(Lgrow[j], L.eps[ir * S + j], acc) : acc;
+                if (k < D) xk = i == 0 ? xsk : acc;
+            } else if (k < D) {
                 if (m.proposal == 0) {
                     R acc = mu;
 #pragma unroll
@@ -470,7 +536,11 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
             if (m.proposal == 1) g = gauss_half_blk<R>(D, k, xk - mu, Lrow, L.blk, ctr) + g;  // AuxiliaryGt = Mt.logpdf + Gt (independent.py:238-248)
             // GradientAuxiliaryGt (:252-268): summed over the particles in the reference, i.e. a constant of the step (AUXSSM_GRAD_REFERENCE: nothing to add);
             // AUXSSM_GRAD_EXACT applies it per particle
-            if (grad && m.gradient == 2) g = g + grad_corr_half<R>(D, k, xk, uk, pmk, st);
+            if constexpr (GD) {  // log g + log N(x; pred, Q) + sum_k log N(x_k; u_k, s^2) - log N(x; mu_t, Lambda_t)
+                g = g + gauss_half_blk<R>(D, k, xk - mu, Lrow, L.blk, ctr);
+                g = g + nu_half<R>(D, k, xk, uk, inv_s, c_u);
+                g = g - gauss_half_blk<R>(D, k, xk - pmk, Lgrow, L.blkg, c_lam);
+            } else if (grad && m.gradient == 2) g = g + grad_corr_half<R>(D, k, xk, uk, pmk, st);
             if (pl && k < D) {
                 xcur[i * S + k] = xk;
                 xs[((long long)t * N + i) * D + k] = xk;
@@ -643,6 +713,7 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     m.iLQ = d;
     fk_time_varying<R>(h, fk, a.T, ctt, m);
     if (a.gb) fk_potbound<R>(h, a, m);
+    const bool guided = fk->proposal == AUXSSM_PROP_AUX_GUIDED;
     if (fk->proposal == 1) {
         const long long total = (long long)a.C * a.T * D;
         hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
@@ -650,8 +721,16 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
             const long long tot = (long long)a.C * a.T;
             hipLaunchKernelGGL((k_cw_grad<R>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0, h->stream, a, m);
         }
+    } else if (guided) {
+        const long long total = (long long)a.C * a.T * D;
+        hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
+        fk_guided<R>(h, a, m);
     }
     const size_t lds = Cw2Lds<R>::bytes(D);
+    // the guided forward pass adds two D x 33 matrices, one block table and 32 rows of u~ - pred: 96 320 bytes in all at dx = 32 in fp64
+    const size_t ldsg = lds + Cw2Lds<R>::guided_bytes(D);
+    static_assert(Cw2Lds<double>::bytes(CSW_MAXD) + Cw2Lds<double>::guided_bytes(CSW_MAXD) <= 160 * 1024, "the guided forward pass must fit the 160 KB of LDS of a CU");
+    if (guided && ldsg > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg));
     if (lds > 48 * 1024) {
         AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         AX_HIP(hipFuncSetAttribute((const void*)k_cw2_bwd<R, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -666,7 +745,10 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
         const CsmcArgs ab = csmc_batch(a, c0, cb);
         {
             ProfScope ps(h, AUXSSM_K_CSMC_FWD);
-            if (wide16) hipLaunchKernelGGL((k_cw2_fwd<R, 16>), dim3(ab.C), dim3(1024), lds, h->stream, ab, m);
+            // (guided: eight waves whatever the chain count -- under the 128 registers of a 1024-lane workgroup the two extra row products and the second blocked
+            // density spill, 360 bytes per lane in fp32: 7.47 ms against 5.11 ms per sweep of the SV protocol at 256 chains)
+            if (guided) hipLaunchKernelGGL((k_cw2_fwd<R, 8, true>), dim3(ab.C), dim3(512), ldsg, h->stream, ab, m);
+            else if (wide16) hipLaunchKernelGGL((k_cw2_fwd<R, 16>), dim3(ab.C), dim3(1024), lds, h->stream, ab, m);
             else hipLaunchKernelGGL((k_cw2_fwd<R, 8>), dim3(ab.C), dim3(512), lds, h->stream, ab, m);
         }
         {

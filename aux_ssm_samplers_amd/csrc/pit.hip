@@ -370,6 +370,10 @@ extern "C" int auxssm_csmc_pit_sweep(auxssm_handle h, int dtype, const auxssm_fk
         set_error("dx=%d not instantiated (1..%d)", D, CS_MAXD);
         return AUXSSM_ERR_UNSUPPORTED;
     }
+    if (fk->proposal == AUXSSM_PROP_AUX_GUIDED) {
+        set_error("guided proposals depend on the parent particle: they run the sequential sweep (auxssm_csmc_sweep) only");
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
     if (fk->proposal != AUXSSM_PROP_AUX_INDEPENDENT) {
         set_error("the parallel-in-time sweep needs proposals that are independent across time: AUXSSM_PROP_AUX_INDEPENDENT");
         return AUXSSM_ERR_ARG;

@@ -276,7 +276,18 @@ int auxssm_kalman_state_resolve(auxssm_handle h, int dtype, const auxssm_dims* d
  * csmc.py:59).  xs_out (C,T,N,dx), log_ws_out (C,T,N), As_out (C,T-1,N) int32: optional full particle history
  * (NULL -> kept in the handle's workspace).  N <= 1024.  Arithmetic uses the fixed reduction orders and the
  * bit-reproducible exp/log documented in csrc/csmc.hip, so ancestors are bit-exact against oracle/csmc_ref.c. */
-typedef enum { AUXSSM_PROP_BOOTSTRAP_LG = 0, AUXSSM_PROP_AUX_INDEPENDENT = 1 } auxssm_fk_proposal;
+/* AUX_GUIDED (the `csmc-guided` sampler style of the reference's examples, examples/stochastic_volatility/auxiliary_guided_csmc.py on csmc/generic.py:56-72):
+ * proposals conditioned on the auxiliary variable AND the parent particle.  With s_t = sqrt(delta_t / 2), u_t = x_t + s_t eps_aux_t, pred / P = m0 / P0 at
+ * t = 0 and the transition mean of the parent / Q after:
+ *   K_t = P (P + s_t^2 I)^-1,  Lambda_t = P - K_t P,  x_t^i ~ N(mu_t, Lambda_t),  mu_t = pred + K_t (u~_t - pred),
+ *   log w = log g_t(x) + log N(x; pred, P) + sum_k log N(x_k; u_{t,k}, s_t^2) - log N(x; mu_t, Lambda_t),  Pt = transition.
+ * u~ = u, or with gradient = AUXSSM_GRAD_REFERENCE u + s_t^2 grad_x log g_t(u_t) (the POTENTIAL's gradient only, written once per chain and step; the third
+ * term of the weight stays at u).  K_t and chol Lambda_t (a factor with a non-finite entry is replaced by s_t I) are built on the device from chol_P0, chol_Q
+ * and sqrt_half_delta at every sweep.  The weights have no reduction-free bound: every step shifts by its exact maximum.  Noise, including eps_aux, as for
+ * AUX_INDEPENDENT.  Covered: every potential, LINEAR and LORENZ63_EM transitions at dx <= 4, LINEAR at 4 < dx <= 32 (N <= 64), gradient NONE / REFERENCE.
+ * AUXSSM_ERR_UNSUPPORTED: time-varying transitions, auxssm_csmc_sweep_program, auxssm_csmc_pit_sweep.  No contract oracle restates this proposal: parity is
+ * against the literal NumPy restatement to rounding, not bit for bit (DESIGN). */
+typedef enum { AUXSSM_PROP_BOOTSTRAP_LG = 0, AUXSSM_PROP_AUX_INDEPENDENT = 1, AUXSSM_PROP_AUX_GUIDED = 2 } auxssm_fk_proposal;
 typedef enum {
     AUXSSM_POT_FLAT = 0,
     AUXSSM_POT_GAUSS_OBS = 1,        /* y_t ~ N(x_t, sig_y^2 I) */

@@ -3,6 +3,7 @@
    C3k  stochastic volatility d=1 T=65536, auxiliary-Kalman sweep (first / second order), fp64
    C4   Lorenz-63 T=16384 dt=1.25e-4 obs every 80 steps, fp32: Kalman sweep (extended linearisation) + cSMC sweep N=512 (bootstrap, backward sampling)
    C5   dense d = p = 64 T=8192 fp32: filter + sampler + joint log-density of one chain (wide-state path)
+   guided  guided proposals beside the independent ones: C3's shape and the reference's SV protocol (D = 30, N = 25), 256 chains
    loop the MCMC loop around the sweeps (aux_ssm_samplers_amd.loop: running moments, acceptance averages, adaptation, Lorenz theta step) on C2 / C3 / C4
 Prints one JSON line per measurement.  Inputs are resident in HBM (DeviceChains) where the API allows it; device Threefry noise."""
 import json
@@ -262,6 +263,39 @@ def sv30(T=250, D=30, N=25):
                                   updated=float((cc.ancestors.to_host() != 0).mean()))), flush=True)
 
 
+def guided(chains=256, reps=5):
+    """guided (locally optimal) proposals beside the independent ones of the same run, resident chains, backward sampling, fp32:
+    config C3's shape (SV d = 1, T = 65536, N = 1024) and the reference's SV protocol (D = 30, T = 250, N = 25), with and without gradient"""
+    import bench
+    from aux_ssm_samplers_amd.workloads import sv_setup
+    from aux_ssm_samplers_amd.csmc import (CsmcChains, CSMCState, get_independent_kernel, get_guided_kernel, GaussianInit, LinearGaussianDynamics,
+                                           SVPotential)
+    h = _lib.default_handle()
+    T3 = 65536
+    phi, q, xsv, ysv = bench.sv_data(T3, 0)
+    y30, x30, (m0, P0, F, Q, b) = sv_setup(250, 30)
+    shapes = (("C3 shape SV d=1 T=65536 N=1024", GaussianInit(m0=[0.0], P0=[[q]]), LinearGaussianDynamics(F=[[phi]], b=[0.0], Q=[[q]]), ysv.reshape(T3, 1),
+               xsv.reshape(T3, 1), 1024, 0.5),
+              ("SV protocol D=30 T=250 N=25", GaussianInit(m0=m0, P0=P0), LinearGaussianDynamics(F=F, b=b, Q=Q), y30, x30, 25, 0.05))
+    for label, M0, Mt, y, x, N, delta in shapes:
+        for name, get in (("independent", get_independent_kernel), ("guided", get_guided_kernel)):
+            for gradient in (False, True):
+                init, kernel = get(M0, SVPotential(y=y[0]), Mt, SVPotential(params=y[1:]), N, backward=True, Pt=Mt, gradient=gradient)
+                cc = CsmcChains(h, np.repeat(x[None], chains, axis=0).astype(np.float32))
+                st = CSMCState(x=cc, updated=None)
+                kernel(0, st, delta)
+                h.sync()
+                t0 = time.perf_counter()
+                for k in range(reps):
+                    kernel(1 + k, st, None)
+                h.sync()
+                el = time.perf_counter() - t0
+                print(json.dumps(dict(config=f"{label}, aux-cSMC {name} proposals (gradient={gradient}) + backward sampling, fp32, resident chains", chains=chains,
+                                      sweeps_per_s=round(chains * reps / el, 1), ms_per_sweep_call=round(el / reps * 1e3, 3),
+                                      updated=float((cc.ancestors.to_host() != 0).mean()))), flush=True)
+                del cc, st
+
+
 def sv30_kalman(T=250, D=30, chains=(1, 16, 64)):
     """the other sampler of the same protocol: the auxiliary Kalman sampler with first / second order linearisation of the SV observation model at D = 30
     (examples/stochastic_volatility/auxiliary_kalman.py:22-48), fp64 as the reference runs it, parallel scan; wide-state kernels (dx = 30)"""
@@ -285,6 +319,8 @@ if __name__ == "__main__":
     which = sys.argv[1:] or ["c3k", "c4", "c5"]
     if "sv30" in which:
         sv30()
+    if "guided" in which:
+        guided()
     if "sv30k" in which:
         sv30_kalman()
     if "pit" in which:
