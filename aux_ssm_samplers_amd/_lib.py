@@ -42,7 +42,7 @@ class FkModel(C.Structure):
     _fields_ = [("proposal", C.c_int32), ("potential", C.c_int32), ("dx", C.c_int32), ("transition", C.c_int32),
                 ("m0", C.c_void_p), ("chol_P0", C.c_void_p), ("F", C.c_void_p), ("b", C.c_void_p), ("chol_Q", C.c_void_p),
                 ("y", C.c_void_p), ("sig_y", C.c_double), ("F_t", C.c_void_p), ("b_t", C.c_void_p), ("chol_Q_t", C.c_void_p),
-                ("gradient", C.c_int32), ("reserved", C.c_int32)]
+                ("gradient", C.c_int32), ("reserved", C.c_int32), ("nu", C.c_double), ("prec", C.c_void_p)]
 
 
 class CsmcNoise(C.Structure):
@@ -56,7 +56,7 @@ class FkUser(C.Structure):
 
 FK_USER_POTENTIAL, FK_USER_MEAN, FK_USER_GRADIENT = 1, 2, 4
 PROP_BOOTSTRAP_LG, PROP_AUX_INDEPENDENT, PROP_AUX_GUIDED = 0, 1, 2
-POT_FLAT, POT_GAUSS_OBS, POT_SV, POT_GAUSS_OBS_MASKED = 0, 1, 2, 3
+POT_FLAT, POT_GAUSS_OBS, POT_SV, POT_GAUSS_OBS_MASKED, POT_MVT = 0, 1, 2, 3, 4
 TRANS_LINEAR, TRANS_LORENZ63_EM = 0, 1
 NOISE_EXPLICIT, NOISE_THREEFRY = 0, 1
 GRAD_NONE, GRAD_REFERENCE, GRAD_EXACT = 0, 1, 2

@@ -7,11 +7,11 @@ import numpy as np
 
 from .. import _lib, random as _random
 from .models import (GaussianInit, LinearGaussianDynamics, FlatPotential, GaussianObsPotential, SVPotential, Lorenz63Dynamics,
-                     MaskedGaussianObsPotential, DevicePotential, DeviceGaussianDynamics)
+                     MaskedGaussianObsPotential, MultivariateTPotential, DevicePotential, DeviceGaussianDynamics)
 
 _UNSUPPORTED = ("{what} is a Python object the HIP kernels cannot evaluate. The cSMC kernels run the closed model family "
                 "of aux_ssm_samplers_amd.csmc.models (GaussianInit, LinearGaussianDynamics, Lorenz63Dynamics, FlatPotential, "
-                "GaussianObsPotential, MaskedGaussianObsPotential, SVPotential) in-kernel; there is no CPU fallback.")
+                "GaussianObsPotential, MaskedGaussianObsPotential, SVPotential, MultivariateTPotential) in-kernel; there is no CPU fallback.")
 
 
 class FkDesc:
@@ -36,6 +36,12 @@ class FkDesc:
         self._ydev = {}
         self._tvdev = {}
         self.user = None  # UserModel: the parts of the model compiled from device code (auxssm_csmc_sweep_program)
+        self.nu, self.prec = 0.0, None  # POT_MVT: degrees of freedom and the (dx, dx) precision matrix (host, like F)
+
+    def set_mvt(self, nu, prec):
+        self.nu = float(nu)
+        self.prec = np.ascontiguousarray(prec, np.float64).reshape(self.dx, self.dx)
+        return self
 
     def tvdev(self, handle, dtype, T):
         """device copies of the time-varying transition arrays (or None)"""
@@ -52,7 +58,8 @@ class FkDesc:
     def struct(self, handle, dtype, T):
         """the auxssm_fk_model of this description on `handle` (keeps the device arrays alive through self)"""
         m = _lib.FkModel(self.proposal, self.potential, self.dx, self.transition, self.m0.ctypes.data, self.chol_P0.ctypes.data,
-                         self.F.ctypes.data, self.b.ctypes.data, self.chol_Q.ctypes.data, None, self.sig_y, None, None, None, self.gradient, 0)
+                         self.F.ctypes.data, self.b.ctypes.data, self.chol_Q.ctypes.data, None, self.sig_y, None, None, None, self.gradient, 0,
+                         self.nu, None if self.prec is None else self.prec.ctypes.data)
         yd = self.ydev(handle, dtype)
         if yd is not None:
             if yd.shape[0] != T:
@@ -78,6 +85,14 @@ def _potential(G0, Gt, d):
         raise NotImplementedError(_UNSUPPORTED.format(what=f"G0={type(G0).__name__} with Gt={type(Gt).__name__}"))
     if isinstance(Gt, FlatPotential):
         return _lib.POT_FLAT, None, 1.0
+    if isinstance(Gt, MultivariateTPotential):
+        if G0.y is None or Gt.params is None:
+            raise ValueError("the potential needs y (G0.y = ys[0]) and params (Gt.params = ys[1:])")
+        if G0.nu != Gt.nu or not np.array_equal(G0.prec, Gt.prec):
+            raise ValueError("G0 and Gt must carry the same nu and prec")
+        if Gt.dx != d:
+            raise ValueError(f"the potential's precision matrix is {Gt.dx} x {Gt.dx}, the state has dimension {d}")
+        return _lib.POT_MVT, np.concatenate([np.reshape(G0.y, (1, d)), np.reshape(Gt.params, (-1, d))], axis=0), 1.0
     if isinstance(Gt, MaskedGaussianObsPotential):
         if G0.y is None or Gt.params is None:
             raise ValueError("the potential needs y (G0.y = ys[0]) and params (Gt.params = ys[1:])")
@@ -99,6 +114,11 @@ def _potential(G0, Gt, d):
                 raise NotImplementedError("G0 and Gt must share the observation noise scale")
         return _lib.POT_GAUSS_OBS, y, sig
     raise NotImplementedError(_UNSUPPORTED.format(what=f"Gt={type(Gt).__name__}"))
+
+
+def _mvt(fk, Gt):
+    """the multivariate-t potential's own parameters into the description (every other potential: nothing)"""
+    return fk.set_mvt(Gt.nu, Gt.prec) if isinstance(Gt, MultivariateTPotential) else fk
 
 
 def _dyn(M0, Mt):
@@ -245,7 +265,7 @@ def _describe_user(proposal, M0, G0, Mt, Gt, gradient, parallel):
                                   "non-Gaussian transition noise is not supported")
     if gradient:  # the program also holds the gradient kernel, from the derivatives of the user-defined parts (grad_log_g / mean_vjp)
         flags |= _lib.FK_USER_GRADIENT
-    fk = FkDesc(proposal, pot, M0.m0, M0.chol(), F, b, LQ, y, sig, tk, gradient)
+    fk = _mvt(FkDesc(proposal, pot, M0.m0, M0.chol(), F, b, LQ, y, sig, tk, gradient), Gt)
     fk.user = UserModel("\n".join(src), flags, d, yu, theta_g, theta_m)
     return fk
 
@@ -263,7 +283,7 @@ def describe_bootstrap(M0, G0, Mt, Gt, Pt):
     d = np.size(M0.m0)
     pot, y, sig = _potential(G0, Gt, d)
     tk, F, b = _trans(Mt)
-    return FkDesc(_lib.PROP_BOOTSTRAP_LG, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk)
+    return _mvt(FkDesc(_lib.PROP_BOOTSTRAP_LG, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk), Gt)
 
 
 def describe_independent(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE, parallel=False):
@@ -278,7 +298,7 @@ def describe_independent(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE, parallel=F
     d = np.size(M0.m0)
     pot, y, sig = _potential(G0, Gt, d)
     tk, F, b = _trans(Mt)
-    return FkDesc(_lib.PROP_AUX_INDEPENDENT, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk, gradient)
+    return _mvt(FkDesc(_lib.PROP_AUX_INDEPENDENT, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk, gradient), Gt)
 
 
 def describe_guided(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE):
@@ -299,7 +319,7 @@ def describe_guided(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE):
     d = np.size(M0.m0)
     pot, y, sig = _potential(G0, Gt, d)
     tk, F, b = _trans(Mt)
-    return FkDesc(_lib.PROP_AUX_GUIDED, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk, gradient)
+    return _mvt(FkDesc(_lib.PROP_AUX_GUIDED, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk, gradient), Gt)
 
 
 _AUXILIARY = (_lib.PROP_AUX_INDEPENDENT, _lib.PROP_AUX_GUIDED)  # the proposals built around u = x + sqrt(delta / 2) eps_aux

@@ -1,6 +1,6 @@
 """Example models written as device code for DevicePotential / DeviceGaussianDynamics (csmc.models; contract in csrc/fk_user_pre.h).
 
-BUILTIN_*: the built-in potentials / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc_host.h::k_csmc_potbound written as user source, in the
+BUILTIN_*: the built-in potentials (Gaussian, stochastic volatility, multivariate Student-t) / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc_host.h::k_csmc_potbound written as user source, in the
 built-in operation order (fma_, det_exp, det_log), so that a program sweep reproduces the closed-family sweep bit for bit (the tests and
 tools/fk_program_bench.py use them).  The constants the host computes for the built-ins (csmc_host.h::fk_model) are formed the same way on
 the device from theta = [sig].  RARE_EVENT, STUDENT_T, GROWTH: models the closed family cannot express.
@@ -52,6 +52,32 @@ template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R
     }
     return b;
 }
+"""
+
+# multivariate Student-t with a precision matrix (AUXSSM_POT_MVT): theta = [nu | prec (D x D, row-major)]; csrc/csmc_sweep.h::mvt_quad / mvt_value in their order,
+# the two constants formed as csmc_host.h::fk_model forms them; sup_x log g = 0
+BUILTIN_MVT = r"""
+template <typename R, int D> __device__ R mvt_s_(const R* x, const R* y, const R* theta, R* z) {
+    const R inv_nu = (R)1 / theta[0];
+    const R* P = theta + 1;
+    R r[D];
+    for (int k = 0; k < D; ++k) r[k] = x[k] - y[k];
+    R q = 0;
+    for (int k = 0; k < D; ++k) {
+        R acc = 0;
+        for (int j = 0; j < D; ++j) acc = fma_(P[k * D + j], r[j], acc);
+        z[k] = acc;
+    }
+    for (int k = 0; k < D; ++k) q = fma_(z[k], r[k], q);
+    return (R)1 + q * inv_nu;
+}
+template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta) {
+    R z[D];
+    const R hc = (theta[0] + (R)D) / (R)2;
+    const R v = -hc * det_log(mvt_s_<R, D>(x, y, theta, z));
+    return (v == v) ? v : (R)0;
+}
+template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta) { return (R)0; }
 """
 
 # mean F x + b: theta = [F (D x D, row-major) | b (D)]
@@ -114,6 +140,17 @@ BUILTIN_GAUSS_OBS_GRAD = BUILTIN_GAUSS_OBS + r"""
 template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
     const R inv = (R)1 / theta[0];
     for (int k = 0; k < D; ++k) gx[k] = ((y[k] - x[k]) * inv) * inv;
+}
+"""
+
+# d/dx log g = (-(hc + hc) / nu / s) z with s = 1 + q / nu, z = prec (x - y); every component 0 where s is NaN (csrc/csmc_sweep.h::mvt_grad_coef / mvt_grad_term)
+BUILTIN_MVT_GRAD = BUILTIN_MVT + r"""
+template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
+    R z[D];
+    const R hc = (theta[0] + (R)D) / (R)2, inv_nu = (R)1 / theta[0];
+    const R s = mvt_s_<R, D>(x, y, theta, z);
+    const R c = -((hc + hc) * inv_nu) / s;
+    for (int k = 0; k < D; ++k) gx[k] = (s == s) ? c * z[k] : (R)0;
 }
 """
 

@@ -95,6 +95,52 @@ class MaskedGaussianObsPotential(UnivariatePotential, Potential):
     params: Optional[Any] = None
 
 
+@dataclass
+class MultivariateTPotential(UnivariatePotential, Potential):
+    """The unnormalised multivariate Student-t log-density with a precision matrix (examples/spatial/t_distribution.py:98-104, model.py:121-124):
+        log g_t(x) = -(nu + d) / 2 log(1 + (x - y_t)^T prec (x - y_t) / nu),   the whole value 0 when it is NaN
+    (a NaN anywhere in y_t makes the step flat).  The one potential of the closed family that couples the components of a state.
+    As G0 give y = ys[0]; as Gt give params = ys[1:]; both carry the same nu and prec.  Validated here, without a GPU: nu > 0, prec square,
+    symmetric to 1e-12 relative, positive definite, of y's dimension -- anything else raises ValueError."""
+    nu: float = 1.0
+    prec: Any = None
+    y: Optional[Any] = None
+    params: Optional[Any] = None
+
+    def __post_init__(self):
+        if not (np.ndim(self.nu) == 0 and float(self.nu) > 0 and np.isfinite(float(self.nu))):
+            raise ValueError(f"MultivariateTPotential: nu must be a finite scalar > 0 (got {self.nu!r})")
+        if self.prec is None:
+            raise ValueError("MultivariateTPotential: prec (the precision matrix) is required")
+        P = np.atleast_2d(np.asarray(self.prec, np.float64))
+        if P.ndim != 2 or P.shape[0] != P.shape[1]:
+            raise ValueError(f"MultivariateTPotential: prec must be a square matrix (got shape {np.shape(self.prec)})")
+        if not np.all(np.isfinite(P)) or np.max(np.abs(P - P.T)) > 1e-12 * np.max(np.abs(P)):
+            raise ValueError("MultivariateTPotential: prec must be finite and symmetric (to 1e-12 relative)")
+        try:
+            np.linalg.cholesky(P)
+        except np.linalg.LinAlgError:
+            raise ValueError("MultivariateTPotential: prec must be positive definite") from None
+        d = P.shape[0]
+        if self.y is not None and np.size(self.y) != d:
+            raise ValueError(f"MultivariateTPotential: y has shape {np.shape(self.y)}, prec is {d} x {d}")
+        if self.params is not None and (np.shape(self.params)[-1] if np.ndim(self.params) >= 2 else (d if d == 1 else -1)) != d:
+            raise ValueError(f"MultivariateTPotential: params has shape {np.shape(self.params)}, expected (T - 1, {d})")
+        self.nu, self.prec = float(self.nu), 0.5 * (P + P.T)
+
+    @property
+    def dx(self):
+        return self.prec.shape[0]
+
+    def __call__(self, x, y):
+        """the NumPy formula (batched over the leading axes of x), with the reference's NaN rule"""
+        r = np.asarray(x, np.float64) - np.asarray(y, np.float64)
+        with np.errstate(invalid="ignore"):
+            q = np.einsum("...i,ij,...j->...", r, self.prec, r)
+            v = -0.5 * (self.nu + self.dx) * np.log1p(q / self.nu)
+        return np.where(np.isnan(v), 0.0, v)
+
+
 # ---- user-defined models: device code compiled when the kernel is built (csrc/fk_program.hip, include/auxssm.h auxssm_fk_program_compile) ----------
 @dataclass
 class DevicePotential(UnivariatePotential, Potential):

@@ -101,19 +101,27 @@ __global__ void __launch_bounds__(1024) k_systematic(int M, int N, const R* __re
 static size_t fwd_lds(int TB, int D, size_t sR) { return (size_t)2 * (cpad(TB) + TB * D) * sR + 48 * sR + 64; }
 static size_t bwd_lds(int TB, int D, size_t sR) { return (size_t)2 * TB * sR + 64 * sR + (size_t)2 * TB * D * sR + 2 * sR + 64; }
 
+// one forward launch through a kernel pointer (the instantiations of the multivariate-t potential; the others go through the macros of run_csmc)
+template <typename R> static int launch_fwd(auxssm_ctx* h, void (*kern)(CsmcArgs, FkDev<R>), const CsmcArgs& ab, const FkDev<R>& m, int TB, size_t lds) {
+    if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(ab.C), dim3(TB), lds, h->stream, ab, m);
+    return AUXSSM_OK;
+}
+
 template <typename R, int D>
 static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void* ctt) {
     FkDev<R> m = fk_dev<R>(fk);
     const int TB = (a.N + 63) / 64 * 64;
     fk_time_varying<R>(h, fk, a.T, ctt, m);
     if (a.gb) fk_potbound<R>(h, a, m);
-    const bool guided = fk->proposal == AUXSSM_PROP_AUX_GUIDED;
+    const bool guided = fk->proposal == AUXSSM_PROP_AUX_GUIDED, mvt = fk->potential == AUXSSM_POT_MVT;
     if (fk->proposal == 1) {
         const long long total = (long long)a.C * a.T * D;
         hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
         if (fk->gradient) {
             const long long tot = (long long)a.C * a.T;
-            hipLaunchKernelGGL((k_csmc_grad<R, D>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, a, m);
+            if (mvt) hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, true>>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, a, m);
+            else hipLaunchKernelGGL((k_csmc_grad<R, D>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, a, m);
         }
     } else if (guided) {
         const long long total = (long long)a.C * a.T * D;
@@ -140,9 +148,18 @@ static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void*
         else if (fullw == 8) AX_FWD1(TVv, GRv, 8); \
         else AX_FWD1(TVv, GRv, 0);      \
     } while (0)
+        int rc_fwd = AUXSSM_OK;
         const bool c3_shape = D == 1 && sizeof(R) == 4 && fullw == 16 && !tv && !gr && fk->proposal == 1 && fk->potential == 2 && m.transition == 0 &&
                               ab.As == nullptr && ab.noise_mode != 0 && !ab.pregen;
-        if (guided) {  // the guided instantiations (SP = 2): time-invariant transitions; N = 1024 as sixteen full waves, any other N through the generic one
+        if (mvt) {  // the multivariate-t potential: its own instantiations (FkBuiltin<R, D, true>: the potential kind fixed at compile time), the generic workgroup for every N
+            using PM = FkBuiltin<R, D, true>;
+            const bool tvm = m.Ft != nullptr, grm = m.gradient != 0;
+            if (guided) rc_fwd = grm ? launch_fwd<R>(h, k_csmc_fwd<R, D, false, true, 0, 2, PM>, ab, m, TB, lds) : launch_fwd<R>(h, k_csmc_fwd<R, D, false, false, 0, 2, PM>, ab, m, TB, lds);
+            else if (tvm && grm) rc_fwd = launch_fwd<R>(h, k_csmc_fwd<R, D, true, true, 0, 0, PM>, ab, m, TB, lds);
+            else if (tvm) rc_fwd = launch_fwd<R>(h, k_csmc_fwd<R, D, true, false, 0, 0, PM>, ab, m, TB, lds);
+            else if (grm) rc_fwd = launch_fwd<R>(h, k_csmc_fwd<R, D, false, true, 0, 0, PM>, ab, m, TB, lds);
+            else rc_fwd = launch_fwd<R>(h, k_csmc_fwd<R, D, false, false, 0, 0, PM>, ab, m, TB, lds);
+        } else if (guided) {  // the guided instantiations (SP = 2): time-invariant transitions; N = 1024 as sixteen full waves, any other N through the generic one
 #define AX_FWDG(GRv, NWv)                                                                                                                                          \
     do {                                                                                                                                                           \
         if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_csmc_fwd<R, D, false, GRv, NWv, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
@@ -164,6 +181,7 @@ static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void*
         else AX_FWD(false, false);
 #undef AX_FWD
 #undef AX_FWD1
+        if (rc_fwd) return rc_fwd;
     }
     {
         ProfScope ps(h, AUXSSM_K_CSMC_BWD);
@@ -418,7 +436,7 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
         }
     }
     const size_t CBT = (size_t)cb * T;
-    size_t need = 4096 + ((size_t)3 * D * D + 4 * D + 8) * sR + 256;  // (+ the wide kernels' model block)
+    size_t need = 4096 + ((size_t)4 * D * D + 4 * D + 8) * sR + 256;  // (+ the wide kernels' model block)
     if (!xs_out) need += CBT * N * D * sR + 256;
     if (!log_ws_out) need += CBT * N * sR + 256;
     if (!backward && !As_out) need += (size_t)cb * (T > 1 ? T - 1 : 1) * N * 4 + 256;
@@ -453,7 +471,10 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
     a.wT = ws_take(h, (size_t)C * N * sR);
     a.fmax = ws_take(h, (size_t)C * T * sR);
     // (the guided weights are not bounded by gb + c_trans: no bound array, every step shifts by its exact maximum)
-    a.gb = !guided && (ug ? prog->has_bound : (fk->potential == 0 || fk->y != nullptr)) ? ws_take(h, (size_t)T * sR) : nullptr;
+    // (nor do the wide kernels shift the multivariate-t potential's weights by its bound sup_x log g = 0: at dx > 4 the weights sit tens of nats below it -- (nu + dx) / 2
+    // times a logarithm -- and fp32 weights exp(lw - bound) leave the normal range, which costs the resampling draws their precision long before every weight is zero)
+    const bool loose = wide && !ug && fk->potential == AUXSSM_POT_MVT;
+    a.gb = !guided && !loose && (ug ? prog->has_bound : (fk->potential == 0 || fk->y != nullptr)) ? ws_take(h, (size_t)T * sR) : nullptr;
     a.gtab = guided ? ws_take(h, guided_tab_reals(T, D) * sR) : nullptr;
     a.anc = ancestors;
     a.noise_mode = noise->mode;

@@ -8,6 +8,9 @@ namespace ax {
 
 // element (i, j) of chol P0 (init) or chol Q of a model; csmc_wide.hip adds the overload of its FkW
 template <typename R> __device__ __forceinline__ R gt_chol(const FkDev<R>& m, bool init, int i, int j) { return (init ? m.LP0 : m.LQ)[i * CS_MAXD + j]; }
+// element (i, j) of the multivariate-t potential's precision matrix; csmc_wide.hip adds the overload of its FkW
+template <typename R> __device__ __forceinline__ R mvt_prec(const FkDev<R>& m, int i, int j) { return m.prec[i * CS_MAXD + j]; }
+constexpr int GT_MAXD = 32;  // the widest state of either kernel family
 
 constexpr int GT_S = 33;  // row stride of the 32 x 32 work matrices in LDS (odd: a column walk touches every bank)
 
@@ -122,6 +125,29 @@ template <typename R> __global__ void k_csmc_gshift(CsmcArgs a, int D, int poten
         v = (v == v) ? v : (R)0;
     }
     ((R*)a.grad)[g] = fma_(s * s, v, u);
+}
+
+// the same for the multivariate Student-t potential (AUXSSM_POT_MVT), whose gradient couples the components: one thread per (chain, t), the operations of
+// csmc_sweep.h::mvt_quad / mvt_grad_coef in their order with a runtime dimension (M: FkDev or csmc_wide.hip's FkW)
+template <typename R, typename M> __global__ void k_csmc_gshift_mvt(CsmcArgs a, M m) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (long long)a.C * a.T) return;
+    const int D = m.D;
+    const long long t = g % a.T;
+    const R* u = (const R*)a.u + g * D;
+    const R* y = (const R*)a.y + t * D;
+    const R s = ((const R*)a.shd)[t];
+    R r[GT_MAXD], z[GT_MAXD];
+    for (int k = 0; k < D; ++k) r[k] = u[k] - y[k];
+    R q = 0;
+    for (int k = 0; k < D; ++k) {
+        R acc = 0;
+        for (int j = 0; j < D; ++j) acc = fma_(mvt_prec(m, k, j), r[j], acc);
+        z[k] = acc;
+    }
+    for (int k = 0; k < D; ++k) q = fma_(z[k], r[k], q);
+    const R sq = (R)1 + q * m.mvt_inv_nu, c = mvt_grad_coef<R>(m.mvt_hc, m.mvt_inv_nu, sq);
+    for (int k = 0; k < D; ++k) ((R*)a.grad)[g * D + k] = fma_(s * s, mvt_grad_term<R>(c, sq, z[k]), u[k]);
 }
 
 }  // namespace ax

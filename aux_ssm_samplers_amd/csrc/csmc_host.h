@@ -15,7 +15,7 @@ namespace ax {
 // the model checks auxssm_csmc_sweep(_program) and auxssm_csmc_pit_sweep share; each entry point adds its own (proposals, dimensions, the explicit noise
 // arrays it reads).  user_potential: the potential is a program's, which brings its own observations
 static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* noise, bool user_potential) {
-    if (fk->potential < AUXSSM_POT_FLAT || fk->potential > AUXSSM_POT_GAUSS_OBS_MASKED) {
+    if (fk->potential < AUXSSM_POT_FLAT || fk->potential > AUXSSM_POT_MVT) {
         set_error("unknown potential kind %d", fk->potential);
         return AUXSSM_ERR_ARG;
     }
@@ -30,6 +30,16 @@ static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* no
     if (fk->potential == AUXSSM_POT_GAUSS_OBS && !(fk->sig_y > 0)) {
         set_error("sig_y must be > 0");
         return AUXSSM_ERR_ARG;
+    }
+    if (fk->potential == AUXSSM_POT_MVT && !user_potential) {
+        if (!fk->prec) {
+            set_error("the multivariate-t potential needs its precision matrix prec (host, dx x dx)");
+            return AUXSSM_ERR_ARG;
+        }
+        if (!(fk->nu > 0)) {
+            set_error("the multivariate-t potential needs nu > 0");
+            return AUXSSM_ERR_ARG;
+        }
     }
     const int ntv = (fk->F_t != nullptr) + (fk->b_t != nullptr) + (fk->chol_Q_t != nullptr);
     if (ntv != 0 && ntv != 3) {
@@ -53,9 +63,9 @@ static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* no
 
 // The model of fk in precision R, as both kernel families read it: the parameters into m0 | LP0 | F | b | LQ (matrices row-major, leading dimension ld), the
 // reciprocal Cholesky diagonals into iLP0 / iLQ, the kinds, the gradient mode and the additive constants into m (FkDev<R>, or csmc_wide.hip's FkW<R>).  The
-// constants are computed once, here, in precision R: they enter both the GPU and the oracle as data.
+// constants are computed once, here, in precision R: they enter both the GPU and the oracle as data.  prec (AUXSSM_POT_MVT): where the precision matrix goes.
 template <typename R, typename M>
-static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* iLP0, R* F, R* b, R* LQ, R* iLQ) {
+static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* iLP0, R* F, R* b, R* LQ, R* iLQ, R* prec) {
     const int D = fk->dx;
     m.proposal = fk->proposal;
     m.potential = fk->potential;
@@ -88,13 +98,20 @@ static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* 
         m.inv_sig_y = 0;
         m.c_obs = -half_log_2pi;
     }
+    m.mvt_hc = 0, m.mvt_inv_nu = 0;
+    if (fk->potential == AUXSSM_POT_MVT) {  // (nu + D) / 2 and 1 / nu, formed here once in precision R
+        m.mvt_hc = ((R)fk->nu + (R)D) / (R)2;
+        m.mvt_inv_nu = (R)1 / (R)fk->nu;
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j) prec[i * ld + j] = (R)fk->prec[i * D + j];
+    }
 }
 // the register kernels' model (the time-varying arrays null: fk_time_varying sets them)
 template <typename R> static FkDev<R> fk_dev(const auxssm_fk_model* fk) {
     FkDev<R> m;
     memset(&m, 0, sizeof(m));
     m.transition = fk->transition;
-    fk_model<R>(fk, m, CS_MAXD, m.m0, m.LP0, m.iLP0, m.F, m.b, m.LQ, m.iLQ);
+    fk_model<R>(fk, m, CS_MAXD, m.m0, m.LP0, m.iLP0, m.F, m.b, m.LQ, m.iLQ, m.prec);
     return m;
 }
 
@@ -126,7 +143,7 @@ template <typename R, typename M> static void fk_time_varying(auxssm_ctx* h, con
 template <typename R> __global__ void k_csmc_potbound(int T, int D, int potential, R c_obs, const R* __restrict__ y, R* __restrict__ gb) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;
-    R b = 0;
+    R b = 0;  // (FLAT, and the multivariate-t potential: sup_x log g = 0 for a positive definite precision)
     if (potential == 1) b = c_obs;
     else if (potential == 3) {
         int nobs = 0;
@@ -150,7 +167,10 @@ template <typename R, typename M> static void fk_potbound(auxssm_ctx* h, const C
 // of the T steps into a.gtab ((2 D D + D + 4) reals per step: guided_tab_reals).  Rebuilt at every sweep: delta may change between sweeps.
 static size_t guided_tab_reals(int T, int D) { return (size_t)T * ((size_t)2 * D * D + D + 4); }
 template <typename R, typename M> static void fk_guided(auxssm_ctx* h, const CsmcArgs& a, const M& m) {
-    if (m.gradient) {
+    if (m.gradient && m.potential == AUXSSM_POT_MVT) {
+        const long long total = (long long)a.C * a.T;
+        hipLaunchKernelGGL((k_csmc_gshift_mvt<R, M>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, h->stream, a, m);
+    } else if (m.gradient) {
         const long long total = (long long)a.C * a.T * m.D;
         hipLaunchKernelGGL((k_csmc_gshift<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, m.D, m.potential, m.inv_sig_y);
     }

@@ -24,6 +24,9 @@ template <typename R> struct FkDev {
     const R* ctt;  // (T-1) additive constants of the transition densities (k_csmc_ctrans)
     const R* idt;  // (T-1, D) reciprocal diagonals of LQt (k_csmc_ctrans)
     int gradient;  // AUXSSM_GRAD_*
+    // AUXSSM_POT_MVT (potential == 4): the precision matrix (leading dimension CS_MAXD) and the two constants (nu + D) / 2 and 1 / nu, formed on the host in R
+    R prec[CS_MAXD * CS_MAXD];
+    R mvt_hc, mvt_inv_nu;
 };
 // the transition t -> t+1 of the model: matrices through pointers (wave-uniform loads when time-varying)
 template <typename R> struct TransT {
@@ -186,8 +189,41 @@ template <typename R, int D> AXD_HD void trans_mean(const FkDev<R>& m, const R* 
         mu[k] = acc;
     }
 }
+// The multivariate Student-t potential (AUXSSM_POT_MVT; examples/spatial/t_distribution.py:98-104 with model.py:121-124), the ONE definition every kernel
+// family uses.  r = x - y;  z = prec r (row k: fma over j ascending from 0);  q = sum_k fma(z_k, r_k, .) (k ascending from 0);  s = 1 + q / nu.
+// mvt_quad returns s and leaves z; the value is -((nu + D) / 2) det_log(s) with NaN -> 0, the gradient (-(hc + hc) inv_nu / s) z, every component 0 where s is NaN.
+template <typename R, int D> AXD_HD R mvt_quad(const R* P, int ld, R inv_nu, const R* x, const R* y, R* z) {
+    R r[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) r[k] = x[k] - y[k];
+    R q = 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        R acc = 0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) acc = fma_(P[k * ld + j], r[j], acc);
+        z[k] = acc;
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) q = fma_(z[k], r[k], q);
+    return (R)1 + q * inv_nu;
+}
+template <typename R> AXD_HD R mvt_value(R hc, R s) {
+    const R v = -hc * det_log(s);
+    return (v == v) ? v : (R)0;
+}
+// the gradient: component k is c z_k with c = -(nu + D) / nu / s = -(nu + D) / (nu + q), and 0 where s is NaN (a missing observation: the step is flat)
+template <typename R> AXD_HD R mvt_grad_coef(R hc, R inv_nu, R s) { return -((hc + hc) * inv_nu) / s; }
+template <typename R> AXD_HD R mvt_grad_term(R c, R s, R zk) { return (s == s) ? c * zk : (R)0; }
 // potential g_t(x_t) (csmc test fixtures test_csmc/common.py:52-75; SV examples/stochastic_volatility/auxiliary_csmc.py:40-46)
-template <typename R, int D> AXD_HD R potential(const FkDev<R>& m, const R* x, const R* y) {
+// MV: the multivariate-t potential, chosen at COMPILE time -- as a fifth run-time branch it cost every forward instantiation of the other potentials twelve
+// registers in fp64 and a wave of occupancy, so the instantiations of the other potentials (MV = false) hold none of its code; potential_rt
+// below is the run-time choice for the callers that are not register-bound
+template <typename R, int D, bool MV = false> AXD_HD R potential(const FkDev<R>& m, const R* x, const R* y) {
+    if constexpr (MV) {
+        R z[D];
+        return mvt_value<R>(m.mvt_hc, mvt_quad<R, D>(m.prec, CS_MAXD, m.mvt_inv_nu, x, y, z));
+    }
     if (m.potential == 0) return (R)0;
     if (m.potential == 1) {  // y ~ N(x, sig_y^2 I)
         R q = 0;
@@ -223,7 +259,14 @@ template <typename R, int D> AXD_HD R potential(const FkDev<R>& m, const R* x, c
     return acc;
 }
 // gx = d potential / dx at x (the closed family's potentials do not read x_{t-1}); y = the D reals of row t, or nullptr
-template <typename R, int D> __device__ __forceinline__ void potential_grad(const FkDev<R>& m, const R* x, const R* y, R* gx) {
+template <typename R, int D, bool MV = false> __device__ __forceinline__ void potential_grad(const FkDev<R>& m, const R* x, const R* y, R* gx) {
+    if constexpr (MV) {  // (the one potential that couples the components)
+        R z[D];
+        const R s = mvt_quad<R, D>(m.prec, CS_MAXD, m.mvt_inv_nu, x, y, z), c = mvt_grad_coef<R>(m.mvt_hc, m.mvt_inv_nu, s);
+#pragma unroll
+        for (int k = 0; k < D; ++k) gx[k] = mvt_grad_term<R>(c, s, z[k]);
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         const R yk = y ? y[k] : (R)0;
@@ -236,6 +279,15 @@ template <typename R, int D> __device__ __forceinline__ void potential_grad(cons
         }
         gx[k] = v;
     }
+}
+// the potential kind of m at run time, the multivariate-t potential included (the parallel-in-time kernels, a user program that keeps the built-in potential)
+template <typename R, int D> __device__ __forceinline__ R potential_rt(const FkDev<R>& m, const R* x, const R* y) {
+    if (m.potential == 4) return potential<R, D, true>(m, x, y);
+    return potential<R, D, false>(m, x, y);
+}
+template <typename R, int D> __device__ __forceinline__ void potential_grad_rt(const FkDev<R>& m, const R* x, const R* y, R* gx) {
+    if (m.potential == 4) potential_grad<R, D, true>(m, x, y, gx);
+    else potential_grad<R, D, false>(m, x, y, gx);
 }
 // out = J^T v, J = d mean / d xp of the transition tr (trans_mean_t): F^T, or the Lorenz-63 step's I + dt dphi/dx (examples/lorenz/model.py:10-25)
 template <typename R, int D> __device__ __forceinline__ void trans_mean_vjp_t(const FkDev<R>& m, const TransT<R>& tr, const R* xp, const R* v, R* out) {
@@ -605,13 +657,14 @@ template <typename R> struct FkUser {
 //   pol.grad_log_g(m, t, x, xprev, y, gx, gxprev)   gx = d log G_t / dx, gxprev = d log G_t / dxprev (nullptr at t = 0); both zero-filled by the caller
 //   pol.mean_vjp(m, tr, t, xprev, v, out)           out = J^T v, J = d pol.mean(m, tr, t, xprev) / d xprev
 //   P::grad_xprev                                   whether log G_t may depend on xprev (false: k_csmc_grad adds no d / dxprev term)
-// FkBuiltin is the closed family of include/auxssm.h, dispatched on the integers of FkDev (the kernels of csmc.hip); fk_user.h's FkUserPolicy calls
+// FkBuiltin is the closed family of include/auxssm.h, dispatched on the integers of FkDev (the kernels of csmc.hip), FkBuiltin<R, D, true> the same with the
+// multivariate-t potential fixed at compile time (potential<R, D, MV> above); fk_user.h's FkUserPolicy calls
 // device functions of a user's source (fk_program.hip).  The backward pass evaluates the Gaussian transition density around pol.mean.
-template <typename R, int D> struct FkBuiltin {
+template <typename R, int D, bool MV = false> struct FkBuiltin {
     static constexpr bool grad_xprev = false;
-    __device__ __forceinline__ R log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y) const { return potential<R, D>(m, x, y); }
+    __device__ __forceinline__ R log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y) const { return potential<R, D, MV>(m, x, y); }
     __device__ __forceinline__ void mean(const FkDev<R>& m, const TransT<R>& tr, int, const R* xp, R* mu) const { trans_mean_t<R, D>(m, tr, xp, mu); }
-    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y, R* gx, R*) const { potential_grad<R, D>(m, x, y, gx); }
+    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y, R* gx, R*) const { potential_grad<R, D, MV>(m, x, y, gx); }
     __device__ __forceinline__ void mean_vjp(const FkDev<R>& m, const TransT<R>& tr, int, const R* xp, const R* v, R* out) const {
         trans_mean_vjp_t<R, D>(m, tr, xp, v, out);
     }

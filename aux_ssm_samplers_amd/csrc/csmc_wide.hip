@@ -10,6 +10,8 @@
 // exposes --gradient at D = 30) and time-varying transitions (the step's F_t, b_t, chol Q_t re-staged into LDS before the step's first barrier) since round 4.
 // Guided proposals (AUXSSM_PROP_AUX_GUIDED, csmc_sweep.h::GuidedT) are a compile-time variant of the forward kernel (k_cw2_fwd<R, NW2, true>): the step's K_t and chol Lambda_t staged
 // into LDS like a time-varying transition, one more row product and one more blocked log-density per particle; the backward kernel is shared.
+// The multivariate-t potential (AUXSSM_POT_MVT, csmc_sweep.h::mvt_quad) is a compile-time variant in the same way (k_cw2_fwd<R, NW2, GD, true>): its precision matrix staged
+// once per workgroup, one more row product per particle (mvt_half); its sweeps carry no bound array (csmc.hip), every step shifts by its exact maximum.
 // (The first version of this file -- one wave per chain, one lane per particle walking its dx x dx products alone: 30.5 ms per sweep of the SV protocol against
 // 2.6 now -- is in the history)
 //
@@ -31,6 +33,8 @@ template <typename R> struct FkW {
     R c_init, c_trans, c_obs, inv_sig_y;
     int gradient;                          // AUXSSM_GRAD_*
     const R *Ft, *bt, *LQt, *ctt, *idt;    // time-varying transitions (csmc_sweep.h::FkDev: row t = transition t -> t + 1), or null
+    const R* prec;                         // AUXSSM_POT_MVT: the precision matrix (device, leading dimension D) and the constants (nu + D) / 2, 1 / nu
+    R mvt_hc, mvt_inv_nu;
 };
 // the transition t -> t + 1 in global memory (gradient kernel; the sweep kernels read it from LDS)
 template <typename R> struct TransW {
@@ -38,6 +42,7 @@ template <typename R> struct TransW {
 };
 // element (i, j) of chol P0 (init) or chol Q (csmc_guided.h::k_csmc_gtab)
 template <typename R> __device__ __forceinline__ R gt_chol(const FkW<R>& m, bool init, int i, int j) { return (init ? m.LP0 : m.LQ)[i * m.D + j]; }
+template <typename R> __device__ __forceinline__ R mvt_prec(const FkW<R>& m, int i, int j) { return m.prec[i * m.D + j]; }
 template <typename R> __device__ __forceinline__ TransW<R> trans_w(const FkW<R>& m, long long t) {
     const long long D = m.D;
     if (m.Ft) return TransW<R>{m.Ft + t * D * D, m.bt + t * D, m.LQt + t * D * D};
@@ -79,7 +84,8 @@ template <typename R> __device__ __forceinline__ void cho_solve_w(int D, const R
 }
 // the gradient of the model's joint log-density at u (csmc_sweep.h::k_csmc_grad, same operations in the same order; one thread per (chain, time step):
 // C T threads of O(dx^2) work, once per sweep -- 0.5 M multiply-adds at the SV protocol's size)
-template <typename R> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
+// MV: the multivariate-t potential's gradient (a compile-time variant: its z[32] would otherwise add scratch to the kernel of the other potentials)
+template <typename R, bool MV = false> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)a.C * a.T) return;
     const int D = m.D;
@@ -87,16 +93,30 @@ template <typename R> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
     const R* u = (const R*)a.u + g * D;
     R gr[CSW_MAXD], r[CSW_MAXD], w[CSW_MAXD];
     const R* yv = (const R*)a.y;
-    for (int k = 0; k < D; ++k) {
-        const R y = yv ? yv[t * D + k] : (R)0;
-        R v = 0;
-        if (m.potential == 1 || (m.potential == 3 && y - y == 0)) v = ((y - u[k]) * m.inv_sig_y) * m.inv_sig_y;
-        else if (m.potential == 2) {
-            const R e = det_exp(-u[k]);
-            v = (R)0.5 * fma_(y * y, e, (R)-1);
-            v = (v == v) ? v : (R)0;
+    if constexpr (MV) {  // multivariate Student-t: csmc_sweep.h::potential_grad's branch (mvt_quad / mvt_grad_coef) with a runtime dimension
+        R z[CSW_MAXD];
+        for (int k = 0; k < D; ++k) r[k] = u[k] - yv[t * D + k];
+        R q = 0;
+        for (int k = 0; k < D; ++k) {
+            R acc = 0;
+            for (int j = 0; j < D; ++j) acc = fma_(m.prec[k * D + j], r[j], acc);
+            z[k] = acc;
         }
-        gr[k] = v;
+        for (int k = 0; k < D; ++k) q = fma_(z[k], r[k], q);
+        const R sq = (R)1 + q * m.mvt_inv_nu, c = mvt_grad_coef<R>(m.mvt_hc, m.mvt_inv_nu, sq);
+        for (int k = 0; k < D; ++k) gr[k] = mvt_grad_term<R>(c, sq, z[k]);
+    } else {
+        for (int k = 0; k < D; ++k) {
+            const R y = yv ? yv[t * D + k] : (R)0;
+            R v = 0;
+            if (m.potential == 1 || (m.potential == 3 && y - y == 0)) v = ((y - u[k]) * m.inv_sig_y) * m.inv_sig_y;
+            else if (m.potential == 2) {
+                const R e = det_exp(-u[k]);
+                v = (R)0.5 * fma_(y * y, e, (R)-1);
+                v = (v == v) ? v : (R)0;
+            }
+            gr[k] = v;
+        }
     }
     if (t == 0) {
         for (int k = 0; k < D; ++k) r[k] = u[k] - m.m0[k];
@@ -143,7 +163,8 @@ template <typename R> struct Cw2Lds {
     R *F, *LQ, *b, *iL, *c, *lwv, *xa, *xb, *eps, *blk;
     int* idx;
     R *Kg, *Lg, *blkg, *dv;  // guided proposals only (behind idx): the step's K_t and chol Lambda_t, the block table of chol Lambda_t, u~ - pred of every half-wave
-    __device__ Cw2Lds(char* smem, int D_, bool guided = false) : D(D_), S(CSW_MAXD + 1) {  // rows padded with zeros to 32 columns (+ 1: odd stride): every component loop runs 32 steps, unrolled
+    R* Pm;                   // multivariate-t potential only (behind everything else): the precision matrix, rows zero-padded like F's
+    __device__ Cw2Lds(char* smem, int D_, bool guided = false, bool mvt = false) : D(D_), S(CSW_MAXD + 1) {  // rows padded with zeros to 32 columns (+ 1: odd stride): every component loop runs 32 steps, unrolled
         F = (R*)smem;           // [D][S]
         LQ = F + D * S;         // [D][S]
         b = LQ + D * S;
@@ -161,7 +182,9 @@ template <typename R> struct Cw2Lds {
             blkg = Lg + D * S;    // [8][12]
             dv = blkg + 96;       // [32][S]
         }
+        if (mvt) Pm = guided ? dv + 32 * S : (R*)(idx + 64);  // [D][S]
     }
+    static constexpr size_t mvt_bytes(int D) { return (size_t)D * (CSW_MAXD + 1) * sizeof(R); }
     static constexpr size_t guided_bytes(int D) { return ((size_t)2 * D * (CSW_MAXD + 1) + 96 + (size_t)32 * (CSW_MAXD + 1)) * sizeof(R); }
     static constexpr size_t bytes(int D) { return ((size_t)2 * D * (CSW_MAXD + 1) + 2 * D + 128 + (size_t)3 * 64 * (CSW_MAXD + 1) + 96) * sizeof(R) + 64 * sizeof(int) + 64; }
 };
@@ -217,6 +240,14 @@ template <typename R> __device__ __forceinline__ void cw2_stage_g(const GuidedT<
         L.Lg[i] = q < D ? g.L[r * D + q] : (R)0;
     }
     if (tid < 96) L.blkg[tid] = cw2_blk_entry<R>(g.L, g.iL, D, tid);
+}
+// multivariate-t potential: the precision matrix into LDS, once per workgroup (it does not change over time), rows zero-padded to 32 columns
+template <typename R> __device__ __forceinline__ void cw2_stage_p(const FkW<R>& m, Cw2Lds<R>& L, int tid, int nt) {
+    const int D = m.D, S = L.S;
+    for (int i = tid; i < D * S; i += nt) {
+        const int r = i / S, q = i - r * S;
+        L.Pm[i] = q < D ? m.prec[r * D + q] : (R)0;
+    }
 }
 // value of lane J of MY half-wave: ds_swizzle in bit mode (lane' = (lane & and) | or inside each group of 32 lanes, and = 0, or = J) -- one LDS-crossbar
 // instruction, no memory, no scalar round trip (two v_readlane + two v_mov + a select before: the component loops are bound by the CU's instruction issue,
@@ -324,6 +355,27 @@ template <typename R> __device__ __forceinline__ R potential_half(const FkW<R>& 
     static_for<0, CSW_MAXD>([&](auto jc) { acc += half_bcast<R, decltype(jc)::value>(v); });
     return acc;
 }
+// the multivariate Student-t potential of that particle (csmc_sweep.h::mvt_quad / mvt_value, same operations in the same order): r_k in the lane that owns
+// component k, z_k = row k of the precision matrix (Prow: this lane's zero-padded LDS row) times r from half-wave broadcasts of r_j, j ascending, and q accumulated in
+// component order by every lane alike from broadcasts of z_k and r_k.  Columns / components beyond D contribute fma(0, 0, acc) = acc.
+template <typename R> __device__ __forceinline__ R mvt_half(int D, int k, R xk, R yk, const R* Prow, R hc, R inv_nu) {
+    const R r = k < D ? xk - yk : (R)0;
+    R p[CSW_MAXD];
+#pragma unroll
+    for (int j = 0; j < CSW_MAXD; ++j) p[j] = Prow[j];
+    R z = 0;
+    static_for<0, CSW_MAXD>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        z = fma_(p[j], half_bcast<R, j>(r), z);
+    });
+    z = k < D ? z : (R)0;
+    R q = 0;
+    static_for<0, CSW_MAXD>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        q = fma_(half_bcast<R, j>(z), half_bcast<R, j>(r), q);
+    });
+    return mvt_value<R>(hc, (R)1 + q * inv_nu);
+}
 // sum_k log N(x_k; u_k, s^2) = c_u - sum_k ((x_k - u_k) / s)^2 / 2 of the particle whose component k this lane holds (csmc_sweep.h::guided_weight: component order)
 template <typename R> __device__ __forceinline__ R nu_half(int D, int k, R xk, R uk, R inv_s, R c_u) {
     const R z = k < D ? (xk - uk) * inv_s : (R)0;
@@ -362,13 +414,15 @@ template <typename R> __device__ __forceinline__ void cw2_draw(const CsmcArgs& a
 }
 
 // GD: the guided proposals, a compile-time variant; false: the kernel as it was, holding none of their code
-template <typename R, int NW2, bool GD = false> __global__ void __launch_bounds__(64 * NW2) k_cw2_fwd(CsmcArgs a, FkW<R> m) {
+// MV: the multivariate-t potential (AUXSSM_POT_MVT), a compile-time variant in the same way: the precision matrix staged in LDS, mvt_half in place of potential_half
+template <typename R, int NW2, bool GD = false, bool MV = false> __global__ void __launch_bounds__(64 * NW2) k_cw2_fwd(CsmcArgs a, FkW<R> m) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT_ = 64 * NW2;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, N = a.N, T = a.T, D = m.D;
     const bool hi = lane >= 32;
     const int k = lane & 31;
-    Cw2Lds<R> L(smem, D, GD);
+    Cw2Lds<R> L(smem, D, GD, MV);
+    if constexpr (MV) cw2_stage_p<R>(m, L, tid, NT_);  // (published by cw2_stage's barrier)
     cw2_stage<R>(m, L, tid, NT_);
     const int S = L.S, nslot = (N + 2 * NW2 - 1) / (2 * NW2);
     const int ch = a.c0 + blockIdx.x;
@@ -391,6 +445,7 @@ template <typename R, int NW2, bool GD = false> __global__ void __launch_bounds_
     const R* Kgrow = GD ? L.Kg + (k < D ? k : 0) * S : nullptr;
     const R* Lgrow = GD ? L.Lg + (k < D ? k : 0) * S : nullptr;
     R* dvr = GD ? L.dv + (2 * wv + (hi ? 1 : 0)) * S : nullptr;
+    const R* Prow = MV ? L.Pm + (k < D ? k : 0) * S : nullptr;
 
     // ---- t = 0 (csmc.py:74-80)
     cw2_draw<R>(a, L, ch, 0, tid, NT_);
@@ -429,7 +484,9 @@ template <typename R, int NW2, bool GD = false> __global__ void __launch_bounds_
             acc0 = xk - m.m0[k];
         }
         const R yk = (yv && k < D) ? yv[k] : (R)0;
-        R g = potential_half<R>(m, k, hi, xk, yk);
+        R g;
+        if constexpr (MV) g = mvt_half<R>(D, k, xk, yk, Prow, m.mvt_hc, m.mvt_inv_nu);
+        else g = potential_half<R>(m, k, hi, xk, yk);
         if (m.proposal == 1) g = g + gauss_half<R>(D, k, hi, acc0, m.LP0 + (long long)(k < D ? k : 0) * D, k < D ? m.iLP0[k] : (R)0, m.c_init);  // AuxiliaryG0
         if constexpr (GD) {  // log g + log N(x; m0, P0) + sum_k log N(x_k; u_k, s^2) - log N(x; mu, Lambda_0)
             const GuidedT<R> gd = guided_at<R>(a.gtab, D, 0);
@@ -532,7 +589,9 @@ template <typename R, int NW2, bool GD = false> __global__ void __launch_bounds_
                 if (i == 0) xk = xsk;
             }
             // weights (csmc.py:95-96)
-            R g = potential_half<R>(m, k, hi, xk, yk);
+            R g;
+            if constexpr (MV) g = mvt_half<R>(D, k, xk, yk, Prow, m.mvt_hc, m.mvt_inv_nu);
+            else g = potential_half<R>(m, k, hi, xk, yk);
             if (m.proposal == 1) g = gauss_half_blk<R>(D, k, xk - mu, Lrow, L.blk, ctr) + g;  // AuxiliaryGt = Mt.logpdf + Gt (independent.py:238-248)
             // GradientAuxiliaryGt (:252-268): summed over the particles in the reference, i.e. a constant of the step (AUXSSM_GRAD_REFERENCE: nothing to add);
             // AUXSSM_GRAD_EXACT applies it per particle
@@ -678,10 +737,11 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     const int D = fk->dx;
     FkW<R> m;
     memset(&m, 0, sizeof(m));
-    std::vector<R> block((size_t)3 * D * D + 4 * D);
+    const bool mvt = fk->potential == AUXSSM_POT_MVT;
+    std::vector<R> block((size_t)3 * D * D + 4 * D + (mvt ? (size_t)D * D : 0));  // (+ the multivariate-t potential's precision matrix)
     R* const host_block = block.data();
-    R *hm0 = host_block, *hLP0 = hm0 + D, *hiLP0 = hLP0 + D * D, *hF = hiLP0 + D, *hb = hF + D * D, *hLQ = hb + D, *hiLQ = hLQ + D * D;
-    fk_model<R>(fk, m, D, hm0, hLP0, hiLP0, hF, hb, hLQ, hiLQ);
+    R *hm0 = host_block, *hLP0 = hm0 + D, *hiLP0 = hLP0 + D * D, *hF = hiLP0 + D, *hb = hF + D * D, *hLQ = hb + D, *hiLQ = hLQ + D * D, *hprec = hiLQ + D;
+    fk_model<R>(fk, m, D, hm0, hLP0, hiLP0, hF, hb, hLQ, hiLQ, hprec);
     const size_t nb = block.size() * sizeof(R);
     {   // the handle's copy of the block: a new upload only when the content differs from the last one (a model that changes between sweeps pays one
         // stream synchronisation -- earlier sweeps may still be reading the old block -- a fixed model none: include/auxssm.h, auxssm_csmc_sweep)
@@ -710,7 +770,8 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     m.F = d; d += D * D;
     m.b = d; d += D;
     m.LQ = d; d += D * D;
-    m.iLQ = d;
+    m.iLQ = d; d += D;
+    m.prec = mvt ? d : nullptr;
     fk_time_varying<R>(h, fk, a.T, ctt, m);
     if (a.gb) fk_potbound<R>(h, a, m);
     const bool guided = fk->proposal == AUXSSM_PROP_AUX_GUIDED;
@@ -719,7 +780,8 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
         hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
         if (fk->gradient) {
             const long long tot = (long long)a.C * a.T;
-            hipLaunchKernelGGL((k_cw_grad<R>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0, h->stream, a, m);
+            if (mvt) hipLaunchKernelGGL((k_cw_grad<R, true>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0, h->stream, a, m);
+            else hipLaunchKernelGGL((k_cw_grad<R>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0, h->stream, a, m);
         }
     } else if (guided) {
         const long long total = (long long)a.C * a.T * D;
@@ -731,6 +793,15 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     const size_t ldsg = lds + Cw2Lds<R>::guided_bytes(D);
     static_assert(Cw2Lds<double>::bytes(CSW_MAXD) + Cw2Lds<double>::guided_bytes(CSW_MAXD) <= 160 * 1024, "the guided forward pass must fit the 160 KB of LDS of a CU");
     if (guided && ldsg > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg));
+    // the multivariate-t potential adds its D x 33 precision matrix: with the guided tables 104 768 bytes at dx = 32 in fp64, the largest plan of this file
+    const size_t ldsm = lds + Cw2Lds<R>::mvt_bytes(D), ldsgm = ldsg + Cw2Lds<R>::mvt_bytes(D);
+    static_assert(Cw2Lds<double>::bytes(CSW_MAXD) + Cw2Lds<double>::guided_bytes(CSW_MAXD) + Cw2Lds<double>::mvt_bytes(CSW_MAXD) <= 160 * 1024,
+                  "the guided forward pass with the multivariate-t potential must fit the 160 KB of LDS of a CU");
+    if (mvt && guided && ldsgm > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsgm));
+    if (mvt && !guided && ldsm > 48 * 1024) {
+        AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm));
+        AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm));
+    }
     if (lds > 48 * 1024) {
         AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         AX_HIP(hipFuncSetAttribute((const void*)k_cw2_bwd<R, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -747,7 +818,10 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
             ProfScope ps(h, AUXSSM_K_CSMC_FWD);
             // (guided: eight waves whatever the chain count -- under the 128 registers of a 1024-lane workgroup the two extra row products and the second blocked
             // density spill, 360 bytes per lane in fp32: 7.47 ms against 5.11 ms per sweep of the SV protocol at 256 chains)
-            if (guided) hipLaunchKernelGGL((k_cw2_fwd<R, 8, true>), dim3(ab.C), dim3(512), ldsg, h->stream, ab, m);
+            if (mvt && guided) hipLaunchKernelGGL((k_cw2_fwd<R, 8, true, true>), dim3(ab.C), dim3(512), ldsgm, h->stream, ab, m);
+            else if (mvt && wide16) hipLaunchKernelGGL((k_cw2_fwd<R, 16, false, true>), dim3(ab.C), dim3(1024), ldsm, h->stream, ab, m);
+            else if (mvt) hipLaunchKernelGGL((k_cw2_fwd<R, 8, false, true>), dim3(ab.C), dim3(512), ldsm, h->stream, ab, m);
+            else if (guided) hipLaunchKernelGGL((k_cw2_fwd<R, 8, true>), dim3(ab.C), dim3(512), ldsg, h->stream, ab, m);
             else if (wide16) hipLaunchKernelGGL((k_cw2_fwd<R, 16>), dim3(ab.C), dim3(1024), lds, h->stream, ab, m);
             else hipLaunchKernelGGL((k_cw2_fwd<R, 8>), dim3(ab.C), dim3(512), lds, h->stream, ab, m);
         }

@@ -48,7 +48,7 @@ template <typename R, int D, bool UG, bool UM> struct FkUserPolicy {
     FkUser<R> u;
     __device__ __forceinline__ R log_g(const FkDev<R>& m, int t, const R* x, const R* xprev, const R* y) const {
         if constexpr (UG) return ::log_g<R, D>(t, x, xprev, u.y ? u.y + (long long)t * u.p : nullptr, u.theta_g);
-        else return potential<R, D>(m, x, y);
+        else return potential_rt<R, D>(m, x, y);
     }
     __device__ __forceinline__ void mean(const FkDev<R>& m, const TransT<R>& tr, int t, const R* xp, R* mu) const {
         if constexpr (UM) ::mean<R, D>(t, xp, u.theta_m, mu);
@@ -61,7 +61,7 @@ template <typename R, int D, bool UG, bool UM> struct FkUserPolicy {
         if constexpr (UG) {
             if constexpr (fk_has_grad_log_g<R, D>::value) ::grad_log_g<R, D>(t, x, xprev, u.y ? u.y + (long long)t * u.p : nullptr, u.theta_g, gx, gxprev);
         } else {
-            potential_grad<R, D>(m, x, y, gx);
+            potential_grad_rt<R, D>(m, x, y, gx);
         }
     }
     __device__ __forceinline__ void mean_vjp(const FkDev<R>& m, const TransT<R>& tr, int t, const R* xp, const R* v, R* out) const {

@@ -121,7 +121,7 @@ template <typename R, int D, bool GRAD> __global__ void __launch_bounds__(1024) 
         R y0[D];
 #pragma unroll
         for (int k = 0; k < D; ++k) y0[k] = a.y ? ((const R*)a.y)[k] : (R)0;
-        R g0 = potential<R, D>(m, x, y0);
+        R g0 = potential_rt<R, D>(m, x, y0);
         g0 = g0 + gauss_chol_logpdf<R, D>(x, m.m0, m.LP0, m.iLP0, m.c_init);  // AuxiliaryG0 (independent.py:163-169)
         g = GRAD ? g + g0 : g0;                                               // log_wts.at[0].add(log_w0) (pit/csmc.py:90-91)
     }
@@ -190,7 +190,7 @@ template <typename R, int D> __global__ void __launch_bounds__(1024) k_pit_stitc
         } else if (mid == 1) {
             wl = ((const R*)a.lw0)[(long long)c * N + ia];
         }
-        pg[tid] = potential<R, D>(m, xr, yv) + wr;
+        pg[tid] = potential_rt<R, D>(m, xr, yv) + wr;
         hh[tid] = wl;
     }
     __syncthreads();
@@ -328,7 +328,8 @@ template <typename R, int D> static int run_pit(auxssm_ctx* h, const auxssm_fk_m
         ca.noise_mode = a.noise_mode; ca.key0 = a.key0; ca.key1 = a.key1; ca.eps_aux = a.eps_aux;
         const long long total = (long long)a.C * a.T * D, tot = (long long)a.C * a.T;
         hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, ca, D);
-        hipLaunchKernelGGL((k_csmc_grad<R, D>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, ca, m);
+        if (fk->potential == AUXSSM_POT_MVT) hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, true>>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, ca, m);
+        else hipLaunchKernelGGL((k_csmc_grad<R, D>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, ca, m);
         hipLaunchKernelGGL((k_pit_leaves<R, D, true>), dim3(a.T, a.C), dim3(TB), 0, h->stream, a, m);
     } else {
         hipLaunchKernelGGL((k_pit_leaves<R, D, false>), dim3(a.T, a.C), dim3(TB), 0, h->stream, a, m);

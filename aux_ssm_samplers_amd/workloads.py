@@ -49,6 +49,33 @@ def sv_setup(T, d, seed=0, phi=0.9, tau=2.0, rho=0.25):
     return y, x, (m0, Q, F, Q, b)
 
 
+def spatial_precision(grid, tau=-0.25, r_y=1):
+    """The spatial example's precision matrix on a grid x grid lattice flattened row by row: entry ((i, j), (k, l)) is tau^(|i - k| + |j - l|) where that
+    lattice distance is <= r_y, else 0 (grid 2: the 4 x 4 matrix examples/spatial/model.py:43-46 prints)."""
+    ii, jj = np.divmod(np.arange(grid * grid), grid)
+    dist = np.abs(ii[:, None] - ii[None, :]) + np.abs(jj[:, None] - jj[None, :])
+    return np.where(dist <= r_y, float(tau) ** dist, 0.0)
+
+
+def spatial_setup(T, grid, seed=0, sigma_x=1.0, nu=1.0, tau=-0.25, r_y=1):
+    """The spatial example (examples/spatial/model.py) on a grid x grid lattice, dx = grid^2: x_0 ~ N(0, sigma_x^2 I), a random walk
+    x_t = x_{t-1} + sigma_x eps_t, and multivariate Student-t observations y_t = x_t + chol(prec^-1) z_t / sqrt(w_t / nu), w_t ~ chi^2_nu, with the
+    precision matrix of spatial_precision.  Returns (M0, Mt, G0, Gt, x, y, prec): the model as the cSMC kernels take it, the simulated states and data."""
+    from aux_ssm_samplers_amd.csmc import GaussianInit, LinearGaussianDynamics, MultivariateTPotential
+    rng = np.random.Generator(np.random.PCG64(seed))
+    d = grid * grid
+    prec = spatial_precision(grid, tau, r_y)
+    Lc = np.linalg.cholesky(np.linalg.inv(prec))
+    x = np.cumsum(sigma_x * rng.standard_normal((T, d)), axis=0)
+    w = rng.chisquare(nu, size=T)
+    y = x + (rng.standard_normal((T, d)) @ Lc.T) / np.sqrt(w / nu)[:, None]
+    M0 = GaussianInit(m0=np.zeros(d), P0=sigma_x ** 2 * np.eye(d))
+    Mt = LinearGaussianDynamics(F=np.eye(d), b=np.zeros(d), Q=sigma_x ** 2 * np.eye(d))
+    G0 = MultivariateTPotential(nu=nu, prec=prec, y=y[0])
+    Gt = MultivariateTPotential(nu=nu, prec=prec, params=y[1:])
+    return M0, Mt, G0, Gt, x, y, prec
+
+
 def lorenz_kalman_setup(T, every=8, dt=0.01, seed=0):
     """examples/lorenz: theta = (10, 28, 8/3), sigma_x = 3, m0 = (1.5, -1.5, 25), P0 = diag(400, 20, 20), (x2, x3) observed every `every`-th
     step with variance 5, NaN rows (ys AND Hs, as model.py:43-56) elsewhere."""

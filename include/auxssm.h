@@ -258,7 +258,8 @@ int auxssm_kalman_state_resolve(auxssm_handle h, int dtype, const auxssm_dims* d
  *
  * A Python Mt/Gt object cannot run inside a kernel; the Feynman-Kac model is a closed family instead:
  *   transition  x_t | x_{t-1} ~ N(F x_{t-1} + b, Q)   (time-invariant), initial N(m0, P0)
- *   potential   FLAT: 0 | GAUSS_OBS: log N(y_t; x_t, sig_y^2 I) | SV: sum_k log N(y_{t,k}; 0, exp(x_{t,k}))
+ *   potential   FLAT: 0 | GAUSS_OBS: log N(y_t; x_t, sig_y^2 I) | SV: sum_k log N(y_{t,k}; 0, exp(x_{t,k})) | GAUSS_OBS_MASKED | MVT: multivariate Student-t
+ *               with a precision matrix (auxssm_fk_potential below)
  *   proposal    BOOTSTRAP_LG:    M0 = initial, Mt = transition, G0/Gt = potential          (test_csmc/common.py fixtures)
  *               AUX_INDEPENDENT: u = x + sqrt(delta_t/2) eps_aux; M0/Mt = N(u_t, delta_t/2 I);
  *                                G0 = log initial + potential, Gt = log transition + potential, Pt = transition
@@ -292,8 +293,17 @@ typedef enum {
     AUXSSM_POT_FLAT = 0,
     AUXSSM_POT_GAUSS_OBS = 1,        /* y_t ~ N(x_t, sig_y^2 I) */
     AUXSSM_POT_SV = 2,               /* y_{t,k} ~ N(0, exp(x_{t,k})) */
-    AUXSSM_POT_GAUSS_OBS_MASKED = 3  /* y_{t,k} ~ N(x_{t,k}, sig_y^2) for the finite y_{t,k} only: missing components / steps skipped
+    AUXSSM_POT_GAUSS_OBS_MASKED = 3, /* y_{t,k} ~ N(x_{t,k}, sig_y^2) for the finite y_{t,k} only: missing components / steps skipped
                                         (examples/lorenz/model.py:43-56: x2, x3 observed every 80th step) */
+    AUXSSM_POT_MVT = 4               /* the unnormalised multivariate Student-t log-density with a precision matrix (examples/spatial/t_distribution.py:98-104,
+                                        model.py:121-124), the one potential of the family that couples the components of a state:
+                                          log g_t(x) = -(nu + dx)/2 log(1 + (x - y_t)^T prec (x - y_t) / nu),  the whole value 0 when it is NaN
+                                        (any NaN component of y_t makes the step flat, as the reference's nan_to_num does).  nu > 0, prec symmetric positive definite.
+                                        Arithmetic order (every kernel; explicit fma, det_log, no contraction):  r_k = x_k - y_k;  z_k = sum_j fma(prec_kj, r_j, .) with j
+                                        ascending from 0;  q = sum_k fma(z_k, r_k, .) with k ascending from 0;  s = 1 + q * (1/nu);  v = -((nu + dx)/2) * det_log(s);
+                                        log g = (v == v) ? v : 0.  The constants (nu + dx)/2 and 1/nu are formed once on the host in the sweep's dtype.  Gradient (prec
+                                        symmetric):  d log g / dx_k = (-((nu + dx)/2 + (nu + dx)/2) * (1/nu) / s) * z_k = -(nu + dx)/(nu + q) z_k to rounding, every component 0 when s is NaN.
+                                        sup_x log g = 0, which is the forward pass's reduction-free bound at dx <= 4; the wide kernels (dx > 4) shift by the exact maximum of every step, the bound being tens of nats above the weights there. */
 } auxssm_fk_potential;
 /* transition x_{t+1} | x_t ~ N(mean(x_t), Q): LINEAR mean = F x + b; LORENZ63_EM mean = x + dt (phi_0(x) + theta * phi(x)), the
  * Euler-Maruyama step of examples/lorenz/model.py:10-25 (dx = 3; theta = F[0..2], dt = b[0], Q = chol_Q chol_Q^T = dt sigma_x^2 I) */
@@ -323,6 +333,9 @@ typedef struct {
      *   AUXSSM_GRAD_EXACT      at every step (the weights the construction intends). */
     int32_t gradient;
     int32_t reserved;
+    /* AUXSSM_POT_MVT only (appended: every field above keeps its offset) */
+    double nu;             /* degrees of freedom, > 0 */
+    const double* prec;    /* host (dx,dx) row-major, symmetric positive definite, like F */
 } auxssm_fk_model;
 typedef enum { AUXSSM_GRAD_NONE = 0, AUXSSM_GRAD_REFERENCE = 1, AUXSSM_GRAD_EXACT = 2 } auxssm_fk_gradient;
 typedef struct {
