@@ -270,6 +270,14 @@ def _describe_user(proposal, M0, G0, Mt, Gt, gradient, parallel):
     return fk
 
 
+def _describe_builtin(proposal, M0, G0, Mt, Gt, gradient):
+    """the FkDesc of a model of the closed family, once the proposal's own checks have passed"""
+    d = np.size(M0.m0)
+    pot, y, sig = _potential(G0, Gt, d)
+    tk, F, b = _trans(Mt)
+    return _mvt(FkDesc(proposal, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk, gradient), Gt)
+
+
 def describe_bootstrap(M0, G0, Mt, Gt, Pt):
     """_primitives.csmc.get_kernel: M0/Mt are the proposals, G0/Gt the potentials."""
     if _is_user(M0, G0, Mt, Gt):
@@ -280,10 +288,7 @@ def describe_bootstrap(M0, G0, Mt, Gt, Pt):
     if Pt is not None and Pt is not Mt and not (isinstance(Pt, LinearGaussianDynamics) and isinstance(Mt, LinearGaussianDynamics)
                                                    and np.array_equal(Pt.F, Mt.F) and np.array_equal(Pt.Q, Mt.Q) and np.array_equal(Pt.b, Mt.b)):
         raise NotImplementedError("backward sampling with Pt != Mt is not supported by the bootstrap device kernel")
-    d = np.size(M0.m0)
-    pot, y, sig = _potential(G0, Gt, d)
-    tk, F, b = _trans(Mt)
-    return _mvt(FkDesc(_lib.PROP_BOOTSTRAP_LG, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk), Gt)
+    return _describe_builtin(_lib.PROP_BOOTSTRAP_LG, M0, G0, Mt, Gt, _lib.GRAD_NONE)
 
 
 def describe_independent(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE, parallel=False):
@@ -295,10 +300,7 @@ def describe_independent(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE, parallel=F
     M0, Mt = _dyn(M0, Mt)
     if Pt is not None and Pt is not Mt:
         raise NotImplementedError("Pt must be the model dynamics Mt")
-    d = np.size(M0.m0)
-    pot, y, sig = _potential(G0, Gt, d)
-    tk, F, b = _trans(Mt)
-    return _mvt(FkDesc(_lib.PROP_AUX_INDEPENDENT, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk, gradient), Gt)
+    return _describe_builtin(_lib.PROP_AUX_INDEPENDENT, M0, G0, Mt, Gt, gradient)
 
 
 def describe_guided(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE):
@@ -316,10 +318,7 @@ def describe_guided(M0, G0, Mt, Gt, Pt, gradient=_lib.GRAD_NONE):
     if gradient not in (_lib.GRAD_NONE, _lib.GRAD_REFERENCE):
         raise NotImplementedError('guided proposals take gradient=False or True (the potential\'s gradient at u, as the reference has it): gradient="exact" '
                                   "is a weighting of the independent proposals")
-    d = np.size(M0.m0)
-    pot, y, sig = _potential(G0, Gt, d)
-    tk, F, b = _trans(Mt)
-    return _mvt(FkDesc(_lib.PROP_AUX_GUIDED, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk, gradient), Gt)
+    return _describe_builtin(_lib.PROP_AUX_GUIDED, M0, G0, Mt, Gt, gradient)
 
 
 _AUXILIARY = (_lib.PROP_AUX_INDEPENDENT, _lib.PROP_AUX_GUIDED)  # the proposals built around u = x + sqrt(delta / 2) eps_aux
@@ -342,6 +341,39 @@ def key_noise(handle, key, Cn, T, N, d, dtype, wide=None):
                 eps_prop=np.ascontiguousarray(np.moveaxis(ep, 4, 2).reshape(Cn, 2 * T2, N, d)[:, :T]),
                 u_res=np.ascontiguousarray(np.moveaxis(ur, 3, 2).reshape(Cn, 2 * T2, N)[:, :max(T - 1, 0)]),
                 u_bwd=handle.rng_uniform(key, 4, (Cn, T), dtype).to_host())
+
+
+def _noise(handle, dtype, Cn, key, noise=None, shapes=None, jax_noise=None, need_all=False):
+    """(CsmcNoise, the device buffers it points to) of one sweep.  noise: dict of explicit arrays, uploaded in the shapes of `shapes` (need_all: every name of
+    `shapes` must be there; otherwise an absent one stays NULL); None -> Threefry(key), or under random.set_compat("jax") the reference's own draws from this
+    key as explicit arrays, jax_noise(key) per chain (several chains: one key per chain, `key` (C, 2) or split(key, C))."""
+    nz, keep = _lib.CsmcNoise(), []
+    if noise is None and _random.compat() == "jax":
+        kk = np.asarray(key, np.uint32)
+        keys = kk if kk.ndim == 2 else (_random.as_key(key)[None] if Cn == 1 else _random.jax_split(_random.as_key(key), Cn))
+        if keys.shape[0] != Cn:
+            raise ValueError(f"{keys.shape[0]} keys for {Cn} chains")
+        per = [jax_noise(k_) for k_ in keys]
+        noise = {name: np.stack([p_[name] for p_ in per]) for name in per[0]}
+    if noise is None:
+        k = _random.as_key(key)
+        nz.mode, nz.key0, nz.key1 = _lib.NOISE_THREEFRY, int(k[0]), int(k[1])
+        return nz, keep
+    nz.mode = _lib.NOISE_EXPLICIT
+    for name, shp in shapes.items():
+        a = noise[name] if need_all else noise.get(name)
+        if a is None:
+            continue
+        buf = handle.to_device(np.asarray(a, dtype).reshape(shp))
+        keep.append(buf)
+        setattr(nz, name, buf.ptr.value)
+    return nz, keep
+
+
+def _no_jax_resident():
+    if _random.compat() == "jax":
+        raise NotImplementedError('random.set_compat("jax") runs the particle kernels on explicit arrays of the reference\'s draws (T x N x d per chain): pass host '
+                                  "states (csmc/_device.py::sweep); resident chains draw inside the kernels from this package's own streams")
 
 
 class CsmcChains:
@@ -376,9 +408,7 @@ class CsmcChains:
 
 def sweep_resident(fk, chains, N, backward, key):
     """One Threefry-keyed auxssm_csmc_sweep on resident chains.  Asynchronous."""
-    if _random.compat() == "jax":
-        raise NotImplementedError('random.set_compat("jax") runs the particle kernels on explicit arrays of the reference\'s draws (T x N x d per chain): pass host '
-                                  "states (csmc/_device.py::sweep); resident chains draw inside the kernels from this package's own streams")
+    _no_jax_resident()
     handle, d = chains.handle, chains.dx
     if d != fk.dx:
         raise ValueError(f"state dimension {d} != model dimension {fk.dx}")
@@ -388,9 +418,7 @@ def sweep_resident(fk, chains, N, backward, key):
         if chains.sqrt_half_delta is None:
             raise ValueError("delta is required")
         shd = chains.sqrt_half_delta
-    k = _random.as_key(key)
-    nz = _lib.CsmcNoise()
-    nz.mode, nz.key0, nz.key1 = _lib.NOISE_THREEFRY, int(k[0]), int(k[1])
+    nz, _ = _noise(handle, chains.dtype, chains.C, key)
     _csmc_call(handle, fk, chains.dtype, m, chains.C, chains.T, N, backward, shd, chains.x, nz, chains.ancestors, None, None, None)
 
 
@@ -405,25 +433,17 @@ def _csmc_call(handle, fk, dtype, m, Cn, T, N, backward, shd, xd, nz, anc, xs, l
         _lib.check(handle.lib.auxssm_csmc_sweep_program(handle.h, fk.user.program(dtype), _lib.dtype_code(dtype), C.byref(m), C.byref(u), *args))
 
 
-def _fk_struct(fk, handle, dtype, T):
-    return fk.struct(handle, dtype, T)
-
-
 def pit_sweep_resident(fk, chains, N, key):
     """One Threefry-keyed auxssm_csmc_pit_sweep (parallel-in-time cSMC) on resident chains.  Asynchronous."""
-    if _random.compat() == "jax":
-        raise NotImplementedError('random.set_compat("jax") runs the particle kernels on explicit arrays of the reference\'s draws (T x N x d per chain): pass host '
-                                  "states (csmc/_device.py::sweep); resident chains draw inside the kernels from this package's own streams")
+    _no_jax_resident()
     handle = chains.handle
     _no_user_pit(fk)
     if chains.dx != fk.dx:
         raise ValueError(f"state dimension {chains.dx} != model dimension {fk.dx}")
     if chains.sqrt_half_delta is None:
         raise ValueError("delta is required")
-    m = _fk_struct(fk, handle, chains.dtype, chains.T)
-    k = _random.as_key(key)
-    nz = _lib.CsmcNoise()
-    nz.mode, nz.key0, nz.key1 = _lib.NOISE_THREEFRY, int(k[0]), int(k[1])
+    m = fk.struct(handle, chains.dtype, chains.T)
+    nz, _ = _noise(handle, chains.dtype, chains.C, key)
     _lib.check(handle.lib.auxssm_csmc_pit_sweep(handle.h, _lib.dtype_code(chains.dtype), C.byref(m), chains.C, chains.T, N,
                                                 chains.sqrt_half_delta.ptr, chains.x.ptr, C.byref(nz), chains.ancestors.ptr))
 
@@ -450,26 +470,10 @@ def pit_sweep(fk, x, N, *, key=None, noise=None, delta=None, handle=None):
     dtype = np.dtype(np.float32) if xc.dtype == np.float32 else np.dtype(np.float64)
     xd = handle.to_device(xc, dtype)
     anc = handle.zeros((Cn, T), np.int32)
-    m = _fk_struct(fk, handle, dtype, T)
+    m = fk.struct(handle, dtype, T)
     shd = handle.to_device(np.sqrt(0.5 * np.asarray(delta, np.float64)) * np.ones(T), dtype)
-    keep = []
-    nz = _lib.CsmcNoise()
-    if noise is None and _random.compat() == "jax":   # the reference's own draws from this key (random.jax_pit_noise); several chains: `key` (C, 2) or split(key, C)
-        kk = np.asarray(key, np.uint32)
-        keys = kk if kk.ndim == 2 else (_random.as_key(key)[None] if Cn == 1 else _random.jax_split(_random.as_key(key), Cn))
-        if keys.shape[0] != Cn:
-            raise ValueError(f"{keys.shape[0]} keys for {Cn} chains")
-        per = [_random.jax_pit_noise(k_, T, N, d, dtype, handle) for k_ in keys]
-        noise = {name: np.stack([p_[name] for p_ in per]) for name in per[0]}
-    if noise is None:
-        k = _random.as_key(key)
-        nz.mode, nz.key0, nz.key1 = _lib.NOISE_THREEFRY, int(k[0]), int(k[1])
-    else:
-        nz.mode = _lib.NOISE_EXPLICIT
-        for name, shp in dict(eps_prop=(Cn, T, N, d), u_res=(Cn, T, N), eps_aux=(Cn, T, d)).items():
-            buf = handle.to_device(np.asarray(noise[name], dtype).reshape(shp))
-            keep.append(buf)
-            setattr(nz, name, buf.ptr.value)
+    nz, keep = _noise(handle, dtype, Cn, key, noise, dict(eps_prop=(Cn, T, N, d), u_res=(Cn, T, N), eps_aux=(Cn, T, d)),
+                      lambda k_: _random.jax_pit_noise(k_, T, N, d, dtype, handle), need_all=True)
     _lib.check(handle.lib.auxssm_csmc_pit_sweep(handle.h, _lib.dtype_code(dtype), C.byref(m), Cn, T, N, shd.ptr, xd.ptr, C.byref(nz), anc.ptr))
     xo, ao = xd.to_host(), anc.to_host()
     return (xo[0], ao[0]) if single else (xo, ao)
@@ -495,32 +499,11 @@ def sweep(fk, x, N, backward, *, key=None, noise=None, delta=None, handle=None, 
             raise ValueError("delta is required")
         shd_h = np.sqrt(0.5 * np.asarray(delta, np.float64)) * np.ones(T)  # csmc/generic.py:61-63
         shd = handle.to_device(shd_h, dtype)
-    keep = []
-    nz = _lib.CsmcNoise()
-    if noise is None and _random.compat() == "jax":
-        # the reference's own draws from this key (random.jax_csmc_noise), as explicit arrays; several chains: one key per chain, `key` (C, 2) or split(key, C)
-        # (the plain cSMC kernel: its draws are made by the model's own M0.sample / Mt.sample in the reference -- one normal(key, (N, d)) per call in every model
-        # the reference defines, which is what the device proposal kernels apply their Cholesky factors to)
-        aux = fk.proposal in _AUXILIARY  # (the reference draws the same shapes for the independent and the guided kernel)
-        kk = np.asarray(key, np.uint32)
-        keys = kk if kk.ndim == 2 else (_random.as_key(key)[None] if Cn == 1 else _random.jax_split(_random.as_key(key), Cn))
-        if keys.shape[0] != Cn:
-            raise ValueError(f"{keys.shape[0]} keys for {Cn} chains")
-        per = [_random.jax_csmc_noise(k_, T, N, d, dtype, bool(backward), handle, auxiliary=aux) for k_ in keys]
-        noise = {name: np.stack([p_[name] for p_ in per]) for name in per[0]}
-    if noise is None:
-        k = _random.as_key(key)
-        nz.mode, nz.key0, nz.key1 = _lib.NOISE_THREEFRY, int(k[0]), int(k[1])
-    else:
-        nz.mode = _lib.NOISE_EXPLICIT
-        shapes = dict(eps_prop=(Cn, T, N, d), u_res=(Cn, max(T - 1, 0), N), u_bwd=(Cn, T), eps_aux=(Cn, T, d))
-        for name, shp in shapes.items():
-            a = noise.get(name)
-            if a is None:
-                continue
-            buf = handle.to_device(np.asarray(a, dtype).reshape(shp))
-            keep.append(buf)
-            setattr(nz, name, buf.ptr.value)
+    # jax compat, the plain cSMC kernel: its draws are made by the model's own M0.sample / Mt.sample in the reference -- one normal(key, (N, d)) per call in every
+    # model the reference defines, which is what the device proposal kernels apply their Cholesky factors to (random.jax_csmc_noise; the reference draws the same
+    # shapes for the independent and the guided kernel)
+    nz, keep = _noise(handle, dtype, Cn, key, noise, dict(eps_prop=(Cn, T, N, d), u_res=(Cn, max(T - 1, 0), N), u_bwd=(Cn, T), eps_aux=(Cn, T, d)),
+                      lambda k_: _random.jax_csmc_noise(k_, T, N, d, dtype, bool(backward), handle, auxiliary=fk.proposal in _AUXILIARY))
     hist = None
     xs = lws = As = None
     if want_history:

@@ -14,6 +14,10 @@
 // of csmc_sweep.h (unnormalised weights exp(lw - max), the hardware's DPP scan order, two-level search, ballot-counted single draw);
 // the standalone primitives (normalize / multinomial / systematic) and the parallel-in-time sweep keep the Kogge-Stone-in-64 cumsum,
 // the balanced-tree-in-64 sum and the plain binary search of csmc_sweep.h.
+//
+// Host side: csmc_sweep_impl validates, batches the chains and lays out the workspace (csmc_host.h::WsPlan); run_csmc / run_csmc_program enqueue the shared
+// prologue (csmc_host.h::csmc_prologue) and then, batch by batch, the forward and the backward pass that fwd_kernel / bwd_kernel (a program's module:
+// fk_fwd_index / fk_bwd_index) pick for the model and nw_class(N).
 #include "csmc_host.h"
 #include "fk_program.h"
 
@@ -101,108 +105,77 @@ __global__ void __launch_bounds__(1024) k_systematic(int M, int N, const R* __re
 static size_t fwd_lds(int TB, int D, size_t sR) { return (size_t)2 * (cpad(TB) + TB * D) * sR + 48 * sR + 64; }
 static size_t bwd_lds(int TB, int D, size_t sR) { return (size_t)2 * TB * sR + 64 * sR + (size_t)2 * TB * D * sR + 2 * sR + 64; }
 
-// one forward launch through a kernel pointer (the instantiations of the multivariate-t potential; the others go through the macros of run_csmc)
-template <typename R> static int launch_fwd(auxssm_ctx* h, void (*kern)(CsmcArgs, FkDev<R>), const CsmcArgs& ab, const FkDev<R>& m, int TB, size_t lds) {
-    if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(ab.C), dim3(TB), lds, h->stream, ab, m);
-    return AUXSSM_OK;
+// the workgroup shapes with instantiations of their own (NW of k_csmc_fwd / k_csmc_bwd): sixteen full waves, eight full waves, 0 = any N
+static int nw_class(int N) { return N == 1024 ? 16 : (N == 512 ? 8 : 0); }
+// f(std::true_type / std::false_type) for b; f(std::integral_constant<int, nw>) for an nw_class
+template <typename F> static auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <typename F> static auto with_nw(int nw, F&& f) {
+    return nw == 16 ? f(std::integral_constant<int, 16>{}) : (nw == 8 ? f(std::integral_constant<int, 8>{}) : f(std::integral_constant<int, 0>{}));
+}
+
+// a pass of the built-in family, as run_csmc launches it
+template <typename R> using SweepKernel = void (*)(CsmcArgs, FkDev<R>);
+
+// config C3's shape: the one instantiation with the model kinds folded at compile time (SP = 1, csmc_sweep.h)
+template <typename R, int D> static bool c3_shape(const FkDev<R>& m, const CsmcArgs& a, int nw) {
+    return D == 1 && sizeof(R) == 4 && nw == 16 && !m.Ft && !m.gradient && m.proposal == AUXSSM_PROP_AUX_INDEPENDENT && m.potential == AUXSSM_POT_SV &&
+           m.transition == AUXSSM_TRANS_LINEAR && a.As == nullptr && a.noise_mode != AUXSSM_NOISE_EXPLICIT && !a.pregen;
+}
+
+// The forward pass of (model, sweep), nw = nw_class(N).  TV: time-varying transitions; GRAD: gradient-informed proposals; PM = FkBuiltin<R, D, true>.
+//   case                                 k_csmc_fwd<R, D, ...>
+//   multivariate-t potential, guided     <false, GRAD, 0, 2, PM>
+//   multivariate-t potential, otherwise  <TV, GRAD, 0, 0, PM>                  the generic workgroup for every N
+//   guided, other potentials             <false, GRAD, nw == 16 ? 16 : 0, 2>   N = 512 takes the generic one
+//   c3_shape                             <float, 1, false, false, 16, 1>
+//   everything else                      <TV, GRAD, nw, 0>
+template <typename R, int D> static SweepKernel<R> fwd_kernel(const FkDev<R>& m, const CsmcArgs& a, int nw) {
+    const bool tv = m.Ft != nullptr, guided = m.proposal == AUXSSM_PROP_AUX_GUIDED;
+    return with_bool(m.gradient != 0, [&](auto gr) -> SweepKernel<R> {
+        constexpr bool GR = decltype(gr)::value;
+        if (m.potential == AUXSSM_POT_MVT) {
+            using PM = FkBuiltin<R, D, true>;
+            if (guided) return k_csmc_fwd<R, D, false, GR, 0, 2, PM>;
+            if (tv) return k_csmc_fwd<R, D, true, GR, 0, 0, PM>;
+            return k_csmc_fwd<R, D, false, GR, 0, 0, PM>;
+        }
+        if (guided) {
+            if (nw == 16) return k_csmc_fwd<R, D, false, GR, 16, 2>;
+            return k_csmc_fwd<R, D, false, GR, 0, 2>;
+        }
+        if constexpr (D == 1 && sizeof(R) == 4 && !GR) {
+            if (c3_shape<R, D>(m, a, nw)) return k_csmc_fwd<R, D, false, false, 16, 1>;
+        }
+        return with_bool(tv, [&](auto tvc) {
+            return with_nw(nw, [&](auto n) -> SweepKernel<R> { return k_csmc_fwd<R, D, decltype(tvc)::value, GR, decltype(n)::value, 0>; });
+        });
+    });
+}
+// The backward pass: k_csmc_bwd<R, D, TV, nw>, whatever the proposal and the potential.
+template <typename R, int D> static SweepKernel<R> bwd_kernel(const FkDev<R>& m, int nw) {
+    return with_bool(m.Ft != nullptr, [&](auto tvc) {
+        return with_nw(nw, [&](auto n) -> SweepKernel<R> { return k_csmc_bwd<R, D, decltype(tvc)::value, decltype(n)::value>; });
+    });
 }
 
 template <typename R, int D>
 static int run_csmc(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void* ctt) {
     FkDev<R> m = fk_dev<R>(fk);
-    const int TB = (a.N + 63) / 64 * 64;
-    fk_time_varying<R>(h, fk, a.T, ctt, m);
-    if (a.gb) fk_potbound<R>(h, a, m);
-    const bool guided = fk->proposal == AUXSSM_PROP_AUX_GUIDED, mvt = fk->potential == AUXSSM_POT_MVT;
-    if (fk->proposal == 1) {
-        const long long total = (long long)a.C * a.T * D;
-        hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
-        if (fk->gradient) {
-            const long long tot = (long long)a.C * a.T;
-            if (mvt) hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, true>>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, a, m);
-            else hipLaunchKernelGGL((k_csmc_grad<R, D>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, a, m);
-        }
-    } else if (guided) {
-        const long long total = (long long)a.C * a.T * D;
-        hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
-        fk_guided<R>(h, a, m);
-    }
+    int rc = csmc_prologue<R>(h, fk, a, ctt, m, false, [&] { return builtin_grad<R, D>(h, a, m); });
+    if (rc) return rc;
+    const int TB = (a.N + 63) / 64 * 64, nw = nw_class(a.N);
     // forward + backward pass, batch of chains by batch (CsmcArgs::c0; one batch unless the particle systems of all chains do not fit the device)
     const int cb = a.cb > 0 ? a.cb : a.C;
     for (int c0 = 0; c0 < a.C; c0 += cb) {
-    const CsmcArgs ab = csmc_batch(a, c0, cb);
-    {
-        ProfScope ps(h, AUXSSM_K_CSMC_FWD);
-        const size_t lds = fwd_lds(TB, D, sizeof(R));
-        const bool tv = m.Ft != nullptr, gr = m.gradient != 0;
-        const int fullw = (TB == a.N && (a.N == 1024 || a.N == 512)) ? a.N / 64 : 0;
-#define AX_FWD1(TVv, GRv, NWv)                                                                                                                                  \
-    do {                                                                                                                                                        \
-        if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_csmc_fwd<R, D, TVv, GRv, NWv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((k_csmc_fwd<R, D, TVv, GRv, NWv>), dim3(ab.C), dim3(TB), lds, h->stream, ab, m);                                                   \
-    } while (0)
-#define AX_FWD(TVv, GRv)                \
-    do {                                \
-        if (fullw == 16) AX_FWD1(TVv, GRv, 16); \
-        else if (fullw == 8) AX_FWD1(TVv, GRv, 8); \
-        else AX_FWD1(TVv, GRv, 0);      \
-    } while (0)
-        int rc_fwd = AUXSSM_OK;
-        const bool c3_shape = D == 1 && sizeof(R) == 4 && fullw == 16 && !tv && !gr && fk->proposal == 1 && fk->potential == 2 && m.transition == 0 &&
-                              ab.As == nullptr && ab.noise_mode != 0 && !ab.pregen;
-        if (mvt) {  // the multivariate-t potential: its own instantiations (FkBuiltin<R, D, true>: the potential kind fixed at compile time), the generic workgroup for every N
-            using PM = FkBuiltin<R, D, true>;
-            const bool tvm = m.Ft != nullptr, grm = m.gradient != 0;
-            if (guided) rc_fwd = grm ? launch_fwd<R>(h, k_csmc_fwd<R, D, false, true, 0, 2, PM>, ab, m, TB, lds) : launch_fwd<R>(h, k_csmc_fwd<R, D, false, false, 0, 2, PM>, ab, m, TB, lds);
-            else if (tvm && grm) rc_fwd = launch_fwd<R>(h, k_csmc_fwd<R, D, true, true, 0, 0, PM>, ab, m, TB, lds);
-            else if (tvm) rc_fwd = launch_fwd<R>(h, k_csmc_fwd<R, D, true, false, 0, 0, PM>, ab, m, TB, lds);
-            else if (grm) rc_fwd = launch_fwd<R>(h, k_csmc_fwd<R, D, false, true, 0, 0, PM>, ab, m, TB, lds);
-            else rc_fwd = launch_fwd<R>(h, k_csmc_fwd<R, D, false, false, 0, 0, PM>, ab, m, TB, lds);
-        } else if (guided) {  // the guided instantiations (SP = 2): time-invariant transitions; N = 1024 as sixteen full waves, any other N through the generic one
-#define AX_FWDG(GRv, NWv)                                                                                                                                          \
-    do {                                                                                                                                                           \
-        if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_csmc_fwd<R, D, false, GRv, NWv, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((k_csmc_fwd<R, D, false, GRv, NWv, 2>), dim3(ab.C), dim3(TB), lds, h->stream, ab, m);                                                   \
-    } while (0)
-            if (gr && fullw == 16) AX_FWDG(true, 16);
-            else if (gr) AX_FWDG(true, 0);
-            else if (fullw == 16) AX_FWDG(false, 16);
-            else AX_FWDG(false, 0);
-#undef AX_FWDG
-        } else if (c3_shape) {
-            if constexpr (D == 1 && sizeof(R) == 4) {
-                if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_csmc_fwd<R, D, false, false, 16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL((k_csmc_fwd<R, D, false, false, 16, 1>), dim3(ab.C), dim3(TB), lds, h->stream, ab, m);
-            }
-        } else if (tv && gr) AX_FWD(true, true);
-        else if (tv) AX_FWD(true, false);
-        else if (gr) AX_FWD(false, true);
-        else AX_FWD(false, false);
-#undef AX_FWD
-#undef AX_FWD1
-        if (rc_fwd) return rc_fwd;
-    }
-    {
-        ProfScope ps(h, AUXSSM_K_CSMC_BWD);
-        const size_t lds = bwd_lds(TB, D, sizeof(R));
-        const int fullw = (TB == a.N && (a.N == 1024 || a.N == 512)) ? a.N / 64 : 0;
-#define AX_BWD(TVv, NWv)                                                                                                                                 \
-    do {                                                                                                                                                 \
-        if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_csmc_bwd<R, D, TVv, NWv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((k_csmc_bwd<R, D, TVv, NWv>), dim3(ab.C), dim3(TB), lds, h->stream, ab, m);                                                   \
-    } while (0)
-        if (m.Ft) {
-            if (fullw == 16) AX_BWD(true, 16);
-            else if (fullw == 8) AX_BWD(true, 8);
-            else AX_BWD(true, 0);
-        } else {
-            if (fullw == 16) AX_BWD(false, 16);
-            else if (fullw == 8) AX_BWD(false, 8);
-            else AX_BWD(false, 0);
+        const CsmcArgs ab = csmc_batch(a, c0, cb);
+        {
+            ProfScope ps(h, AUXSSM_K_CSMC_FWD);
+            if ((rc = launch(h, fwd_kernel<R, D>(m, ab, nw), dim3(ab.C), dim3(TB), fwd_lds(TB, D, sizeof(R)), ab, m))) return rc;
         }
-#undef AX_BWD
-    }
+        {
+            ProfScope ps(h, AUXSSM_K_CSMC_BWD);
+            if ((rc = launch(h, bwd_kernel<R, D>(m, nw), dim3(ab.C), dim3(TB), bwd_lds(TB, D, sizeof(R)), ab, m))) return rc;
+        }
     }
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;
@@ -222,6 +195,11 @@ static int fk_launch(auxssm_ctx* h, hipFunction_t f, unsigned grid, unsigned blo
     AX_HIP(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, (unsigned)lds, h->stream, args, nullptr));
     return AUXSSM_OK;
 }
+// The program's passes for nw = nw_class(N), by their index in the module (fk_program.h: three of each kind, NW = 0 / 8 / 16):
+//   forward   FK_FWD0 + nw / 8, with gradient proposals FK_FWDG0 + nw / 8
+//   backward  FK_BWD0 + nw / 8
+static int fk_fwd_index(int gradient, int nw) { return (gradient ? FK_FWDG0 : FK_FWD0) + nw / 8; }
+static int fk_bwd_index(int nw) { return FK_BWD0 + nw / 8; }
 template <typename R, int D>
 static int run_csmc_program(auxssm_ctx* h, const auxssm_fk_program_s* prog, const auxssm_fk_model* fk, const auxssm_fk_user* user, CsmcArgs& a) {
     const hipFunction_t* fn = nullptr;
@@ -229,40 +207,30 @@ static int run_csmc_program(auxssm_ctx* h, const auxssm_fk_program_s* prog, cons
     if (rc) return rc;
     FkDev<R> m = fk_dev<R>(fk);
     FkUser<R> u{(const R*)user->y, (const R*)user->theta_g, (const R*)user->theta_m, user->p};
-    const int TB = (a.N + 63) / 64 * 64;
-    if (a.gb) {
-        if (prog->flags & AUXSSM_FK_USER_POTENTIAL) {
-            int T = a.T;
-            R* gb = (R*)a.gb;
-            void* args[] = {&T, &u, &gb};
-            if ((rc = fk_launch(h, fn[FK_BOUND], (unsigned)((a.T + 255) / 256), 256, 0, args))) return rc;
-        } else {
-            fk_potbound<R>(h, a, m);
-        }
+    const bool user_bound = (prog->flags & AUXSSM_FK_USER_POTENTIAL) != 0;
+    if (a.gb && user_bound) {
+        int T = a.T;
+        R* gb = (R*)a.gb;
+        void* args[] = {&T, &u, &gb};
+        if ((rc = fk_launch(h, fn[FK_BOUND], (unsigned)((a.T + 255) / 256), 256, 0, args))) return rc;
     }
-    if (fk->proposal == 1) {
-        const long long total = (long long)a.C * a.T * D;
-        hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
-        if (fk->gradient) {
-            const long long tot = (long long)a.C * a.T;
-            void* args[] = {&a, &m, &u};
-            if ((rc = fk_launch(h, fn[FK_GRAD], (unsigned)((tot + 255) / 256), 256, 0, args))) return rc;
-        }
-    }
-    const int fullw = (TB == a.N && (a.N == 1024 || a.N == 512)) ? a.N / 64 : 0;
-    const int sel = fullw == 16 ? 2 : (fullw == 8 ? 1 : 0);
-    const int fwd0 = m.gradient != 0 ? FK_FWDG0 : FK_FWD0;
+    rc = csmc_prologue<R>(h, fk, a, nullptr, m, user_bound, [&] {
+        void* args[] = {&a, &m, &u};
+        return fk_launch(h, fn[FK_GRAD], (unsigned)(((long long)a.C * a.T + 255) / 256), 256, 0, args);
+    });
+    if (rc) return rc;
+    const int TB = (a.N + 63) / 64 * 64, nw = nw_class(a.N);
     const int cb = a.cb > 0 ? a.cb : a.C;
     for (int c0 = 0; c0 < a.C; c0 += cb) {
         CsmcArgs ab = csmc_batch(a, c0, cb);
         void* args[] = {&ab, &m, &u};
         {
             ProfScope ps(h, AUXSSM_K_CSMC_FWD);
-            if ((rc = fk_launch(h, fn[fwd0 + sel], (unsigned)ab.C, (unsigned)TB, fwd_lds(TB, D, sizeof(R)), args))) return rc;
+            if ((rc = fk_launch(h, fn[fk_fwd_index(m.gradient, nw)], (unsigned)ab.C, (unsigned)TB, fwd_lds(TB, D, sizeof(R)), args))) return rc;
         }
         {
             ProfScope ps(h, AUXSSM_K_CSMC_BWD);
-            if ((rc = fk_launch(h, fn[FK_BWD0 + sel], (unsigned)ab.C, (unsigned)TB, bwd_lds(TB, D, sizeof(R)), args))) return rc;
+            if ((rc = fk_launch(h, fn[fk_bwd_index(nw)], (unsigned)ab.C, (unsigned)TB, bwd_lds(TB, D, sizeof(R)), args))) return rc;
         }
     }
     AX_HIP(hipGetLastError());
@@ -435,64 +403,56 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
             if (v >= 1 && v < cb) cb = v;
         }
     }
-    const size_t CBT = (size_t)cb * T;
-    size_t need = 4096 + ((size_t)4 * D * D + 4 * D + 8) * sR + 256;  // (+ the wide kernels' model block)
-    if (!xs_out) need += CBT * N * D * sR + 256;
-    if (!log_ws_out) need += CBT * N * sR + 256;
-    if (!backward && !As_out) need += (size_t)cb * (T > 1 ? T - 1 : 1) * N * 4 + 256;
-    need += (size_t)C * N * sR + 256;
-    need += 2 * (CT * sR + 256);  // fmax, the backward pass's uniforms
-    need += (size_t)T * sR + 256;  // gb
-    need += 2 * (CT * D * sR + 256) + (size_t)T * (1 + D) * sR + 256;
-    if (guided) need += guided_tab_reals(T, D) * sR + 256;  // K_t, chol Lambda_t and their constants, every step
-    // fewer chains than CUs: the forward pass's draws are generated up front by the whole chip (csmc_sweep.h::k_csmc_pregen) when the two arrays fit
-    const size_t pre_eps = CT * N * D * sR + 256, pre_u = (size_t)C * (T > 1 ? T - 1 : 1) * N * sR + 256;
-    bool pregen = noise->mode == AUXSSM_NOISE_THREEFRY && !wide && T > 1 && C < h->num_cu && cb == C &&
-                  !getenv("AUXSSM_CSMC_NO_PREGEN");  // test hook: tests/test_gpu_csmc.py and tests/test_gpu_full_size.py force the in-pass draws
-    if (pregen) {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) != hipSuccess || (double)(need + pre_eps + pre_u) > 0.7 * (double)(fr + h->ws_bytes)) pregen = false;
-    }
-    if (pregen) need += pre_eps + pre_u;
-    int rc = ws_reserve(h, need);
-    if (rc) return rc;
-    CsmcArgs a;
+    const size_t CBT = (size_t)cb * T, T1 = (size_t)(T > 1 ? T - 1 : 1);
+    CsmcArgs a{};
     a.C = C; a.T = T; a.N = N; a.backward = backward ? 1 : 0;
     a.y = fk->y;
     a.shd = sqrt_half_delta;
     a.x = x;
-    a.u = ws_take(h, CT * D * sR);
-    a.grad = fk->gradient ? ws_take(h, CT * D * sR) : nullptr;
-    void* ctt = fk->F_t ? ws_take(h, (size_t)T * (1 + D) * sR) : nullptr;  // constants + reciprocal diagonals of the T - 1 transitions
     a.cb = cb; a.xs_rec = xs_rec; a.lws_rec = lws_rec; a.As_rec = As_rec;
-    a.xs = xs_out ? xs_out : ws_take(h, CBT * N * D * sR);
-    a.lws = log_ws_out ? log_ws_out : ws_take(h, CBT * N * sR);
-    a.As = As_out ? As_out : (!backward ? (int32_t*)ws_take(h, (size_t)cb * (T > 1 ? T - 1 : 1) * N * 4) : nullptr);
-    a.wT = ws_take(h, (size_t)C * N * sR);
-    a.fmax = ws_take(h, (size_t)C * T * sR);
-    // (the guided weights are not bounded by gb + c_trans: no bound array, every step shifts by its exact maximum)
-    // (nor do the wide kernels shift the multivariate-t potential's weights by its bound sup_x log g = 0: at dx > 4 the weights sit tens of nats below it -- (nu + dx) / 2
-    // times a logarithm -- and fp32 weights exp(lw - bound) leave the normal range, which costs the resampling draws their precision long before every weight is zero)
-    const bool loose = wide && !ug && fk->potential == AUXSSM_POT_MVT;
-    a.gb = !guided && !loose && (ug ? prog->has_bound : (fk->potential == 0 || fk->y != nullptr)) ? ws_take(h, (size_t)T * sR) : nullptr;
-    a.gtab = guided ? ws_take(h, guided_tab_reals(T, D) * sR) : nullptr;
+    a.xs = xs_out; a.lws = log_ws_out; a.As = As_out;
     a.anc = ancestors;
     a.noise_mode = noise->mode;
     a.key0 = noise->key0; a.key1 = noise->key1;
     a.eps_aux = noise->eps_aux; a.eps_prop = noise->eps_prop; a.u_res = noise->u_res; a.u_bwd = noise->u_bwd;
-    if (noise->mode == AUXSSM_NOISE_THREEFRY) {  // the backward pass's uniforms, drawn once (csmc_sweep.h::k_csmc_ubwd)
-        void* ub = ws_take(h, CT * sR);
-        if (!ub) return AUXSSM_ERR_NOMEM;
+    // the workspace plan: the buffers this sweep owns
+    WsPlan ws;
+    void *ctt = nullptr, *ub = nullptr, *pe = nullptr, *pu = nullptr;
+    ws.add(a.u, CT * D * sR);
+    if (fk->gradient) ws.add(a.grad, CT * D * sR);
+    if (fk->F_t) ws.add(ctt, (size_t)T * (1 + D) * sR);  // constants + reciprocal diagonals of the T - 1 transitions
+    if (!xs_out) ws.add(a.xs, CBT * N * D * sR);
+    if (!log_ws_out) ws.add(a.lws, CBT * N * sR);
+    if (!As_out && !backward) ws.add(a.As, (size_t)cb * T1 * N * 4);
+    ws.add(a.wT, (size_t)C * N * sR);
+    ws.add(a.fmax, CT * sR);
+    // (the guided weights are not bounded by gb + c_trans: no bound array, every step shifts by its exact maximum)
+    // (nor do the wide kernels shift the multivariate-t potential's weights by its bound sup_x log g = 0: at dx > 4 the weights sit tens of nats below it -- (nu + dx) / 2
+    // times a logarithm -- and fp32 weights exp(lw - bound) leave the normal range, which costs the resampling draws their precision long before every weight is zero)
+    const bool loose = wide && !ug && fk->potential == AUXSSM_POT_MVT;
+    if (!guided && !loose && (ug ? prog->has_bound : (fk->potential == AUXSSM_POT_FLAT || fk->y != nullptr))) ws.add(a.gb, (size_t)T * sR);
+    if (guided) ws.add(a.gtab, guided_tab_reals(T, D) * sR);  // K_t, chol Lambda_t and their constants, every step
+    if (noise->mode == AUXSSM_NOISE_THREEFRY) ws.add(ub, CT * sR);  // the backward pass's uniforms, drawn once (csmc_sweep.h::k_csmc_ubwd)
+    // fewer chains than CUs: the forward pass's draws are generated up front by the whole chip (csmc_sweep.h::k_csmc_pregen) when the two arrays fit
+    bool pregen = noise->mode == AUXSSM_NOISE_THREEFRY && !wide && T > 1 && C < h->num_cu && cb == C &&
+                  !getenv("AUXSSM_CSMC_NO_PREGEN");  // test hook: tests/test_gpu_csmc.py and tests/test_gpu_full_size.py force the in-pass draws
+    if (pregen) {
+        ws.add(pe, CT * N * D * sR);
+        ws.add(pu, (size_t)C * T1 * N * sR);
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess || (double)ws.total() > 0.7 * (double)(fr + h->ws_bytes)) {
+            ws.drop(2);
+            pregen = false;
+        }
+    }
+    if (int rc = ws.reserve(h)) return rc;
+    if (ub) {
         const long long n = (long long)CT;
         if (dtype == AUXSSM_F32) hipLaunchKernelGGL((k_csmc_ubwd<float>), dim3((unsigned)(((n + 1) / 2 + 255) / 256)), dim3(256), 0, h->stream, n, noise->key0, noise->key1, (float*)ub);
         else hipLaunchKernelGGL((k_csmc_ubwd<double>), dim3((unsigned)(((n + 1) / 2 + 255) / 256)), dim3(256), 0, h->stream, n, noise->key0, noise->key1, (double*)ub);
         a.u_bwd = ub;
     }
-    if (!a.u || !a.xs || !a.lws || !a.wT || !a.fmax || (!backward && !a.As) || (fk->gradient && !a.grad) || (fk->F_t && !ctt) || (guided && !a.gtab)) return AUXSSM_ERR_NOMEM;
     if (pregen) {
-        void* pe = ws_take(h, pre_eps - 256);
-        void* pu = ws_take(h, pre_u - 256);
-        if (!pe || !pu) return AUXSSM_ERR_NOMEM;
         const int T2 = (T + 1) >> 1;
         const dim3 grid((unsigned)C * T2, (unsigned)((N * D + 255) / 256));
         ProfScope ps(h, AUXSSM_K_RNG);

@@ -1,16 +1,63 @@
 // csmc_host.h -- the host side the conditional-SMC drivers share (csmc.hip: the sequential sweep, built-in and user-defined models; csmc_wide.hip: the
-// wide-state sweep; pit.hip: the parallel-in-time sweep): the model checks of both entry points, the model in precision R, the time-varying setup, the two
-// per-sweep kernels of the model (transition constants, potential bound), chain batching and the dtype x dx dispatch.  hipcc only (the device side,
-// csmc_sweep.h, also compiles under hipRTC).  Units including this are compiled with -ffp-contract=off.
+// wide-state sweep; pit.hip: the parallel-in-time sweep): the model checks of both entry points, the model in precision R, the one kernel launch helper
+// (launch), the workspace plan (WsPlan), the per-sweep prologue (csmc_prologue: transition constants, potential bound, auxiliary variables, gradient or guided
+// tables), chain batching and the dtype x dx dispatch.  hipcc only (the device side, csmc_sweep.h, also compiles under hipRTC).  Units including this are
+// compiled with -ffp-contract=off.
 #pragma once
 #include <cstring>
 #include <type_traits>
+#include <utility>
 
 #include "ctx.h"
 #include "csmc_sweep.h"
 #include "csmc_guided.h"
 
 namespace ax {
+
+// The one kernel launch of the cSMC drivers: kern<<<grid, block, lds, h->stream>>>(args...), the kernel's dynamic LDS limit raised first when the launch asks
+// for more than the 48 KB every kernel is granted.  (Functions of a hipRTC module have no such attribute: csmc.hip::fk_launch.)
+template <typename... P, typename... A> static int launch(auxssm_ctx* h, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, A&&... args) {
+    if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, h->stream, std::forward<A>(args)...);
+    return AUXSSM_OK;
+}
+
+// The workspace of one sweep, said once: add() registers a buffer with its byte count and the pointer that receives it, total() is what the registered buffers
+// occupy as ws_take lays them out (each on a 256-byte boundary, in the order of registration), reserve() sizes the handle's workspace to it and fills the
+// pointers.  Fixed capacity, no heap.
+struct WsPlan {
+    struct Entry {
+        size_t bytes;
+        void* slot;
+        void (*set)(void* slot, void* p);
+    };
+    static constexpr int CAP = 24;
+    Entry e[CAP];
+    int n = 0;
+    template <typename T> void add(T*& slot, size_t bytes) {
+        if (n < CAP) e[n] = Entry{bytes, &slot, [](void* s, void* p) { *(T**)s = (T*)p; }};
+        ++n;
+    }
+    void drop(int k) { n -= k; }  // the last k buffers are not wanted after all
+    size_t total() const {
+        size_t off = 0;
+        for (int i = 0; i < n && i < CAP; ++i) off = ((off + 255) & ~(size_t)255) + e[i].bytes;
+        return off;
+    }
+    int reserve(auxssm_ctx* h) const {
+        if (n > CAP) {
+            set_error("internal: workspace plan of %d buffers (capacity %d)", n, CAP);
+            return AUXSSM_ERR_ARG;
+        }
+        if (int rc = ws_reserve(h, total())) return rc;
+        for (int i = 0; i < n; ++i) {
+            void* p = ws_take(h, e[i].bytes);
+            if (!p) return AUXSSM_ERR_NOMEM;
+            e[i].set(e[i].slot, p);
+        }
+        return AUXSSM_OK;
+    }
+};
 
 // the model checks auxssm_csmc_sweep(_program) and auxssm_csmc_pit_sweep share; each entry point adds its own (proposals, dimensions, the explicit noise
 // arrays it reads).  user_potential: the potential is a program's, which brings its own observations
@@ -88,10 +135,10 @@ static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* 
     const R half_log_2pi = (R)0.91893853320467274178;
     m.c_init = ci - (R)D * half_log_2pi;
     m.c_trans = ct - (R)D * half_log_2pi;
-    if (fk->potential == 1) {
+    if (fk->potential == AUXSSM_POT_GAUSS_OBS) {
         m.inv_sig_y = (R)1 / (R)fk->sig_y;
         m.c_obs = -(R)D * det_log((R)fk->sig_y) - (R)D * half_log_2pi;
-    } else if (fk->potential == 3) {  // per observed component
+    } else if (fk->potential == AUXSSM_POT_GAUSS_OBS_MASKED) {  // per observed component
         m.inv_sig_y = (R)1 / (R)fk->sig_y;
         m.c_obs = -det_log((R)fk->sig_y) - half_log_2pi;
     } else {
@@ -144,12 +191,12 @@ template <typename R> __global__ void k_csmc_potbound(int T, int D, int potentia
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;
     R b = 0;  // (FLAT, and the multivariate-t potential: sup_x log g = 0 for a positive definite precision)
-    if (potential == 1) b = c_obs;
-    else if (potential == 3) {
+    if (potential == AUXSSM_POT_GAUSS_OBS) b = c_obs;
+    else if (potential == AUXSSM_POT_GAUSS_OBS_MASKED) {
         int nobs = 0;
         for (int k = 0; k < D; ++k) nobs += (y[(long long)t * D + k] - y[(long long)t * D + k] == 0) ? 1 : 0;
         b = (R)nobs * c_obs;
-    } else if (potential == 2) {  // sum_k [c_obs - (x + y^2 e^-x) / 2] <= sum_k max(0, c_obs - (1 + log y^2) / 2)  (a NaN term counts 0)
+    } else if (potential == AUXSSM_POT_SV) {  // sum_k [c_obs - (x + y^2 e^-x) / 2] <= sum_k max(0, c_obs - (1 + log y^2) / 2)  (a NaN term counts 0)
         for (int k = 0; k < D; ++k) {
             const R yk = y[(long long)t * D + k], y2 = yk * yk;
             R v = (R)0;
@@ -175,6 +222,37 @@ template <typename R, typename M> static void fk_guided(auxssm_ctx* h, const Csm
         hipLaunchKernelGGL((k_csmc_gshift<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, m.D, m.potential, m.inv_sig_y);
     }
     hipLaunchKernelGGL((k_csmc_gtab<R, M>), dim3(a.T), dim3(64), 0, h->stream, a.T, m, (const R*)a.shd, (R*)a.gtab);
+}
+
+// the gradient launch of the built-in family on the register kernels (csmc.hip::run_csmc, pit.hip::run_pit)
+template <typename R, int D> static int builtin_grad(auxssm_ctx* h, const CsmcArgs& a, const FkDev<R>& m) {
+    const dim3 grid((unsigned)(((long long)a.C * a.T + 255) / 256));
+    if (m.potential == AUXSSM_POT_MVT) hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, true>>), grid, dim3(256), 0, h->stream, a, m);
+    else hipLaunchKernelGGL((k_csmc_grad<R, D>), grid, dim3(256), 0, h->stream, a, m);
+    return AUXSSM_OK;
+}
+
+// What a sweep enqueues before its passes, in this order: the constants of time-varying transitions (m then reads them), the built-in potential's bound into
+// a.gb (user_bound: the program has launched its own), the auxiliary variables u = x + sqrt(delta / 2) eps of the auxiliary proposals (a.u null: the caller's
+// kernels form them themselves -- pit.hip without gradients), then the gradient at u for gradient-informed independent proposals -- grad(), the one launch the
+// drivers differ in: it returns an AUXSSM_* code -- or the guided proposals' shift and tables.  SEQ = false: the parallel-in-time sweep, which has neither a
+// bound array nor guided proposals (its unit then holds none of their kernels).
+template <typename R, bool SEQ = true, typename M, typename G>
+static int csmc_prologue(auxssm_ctx* h, const auxssm_fk_model* fk, const CsmcArgs& a, void* ctt, M& m, bool user_bound, G&& grad) {
+    fk_time_varying<R>(h, fk, a.T, ctt, m);
+    if constexpr (SEQ) {
+        if (a.gb && !user_bound) fk_potbound<R>(h, a, m);
+    }
+    if (m.proposal == AUXSSM_PROP_BOOTSTRAP_LG || !a.u) return AUXSSM_OK;
+    const long long total = (long long)a.C * a.T * m.D;
+    hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, m.D);
+    if constexpr (SEQ) {
+        if (m.proposal == AUXSSM_PROP_AUX_GUIDED) {
+            fk_guided<R>(h, a, m);
+            return AUXSSM_OK;
+        }
+    }
+    return m.gradient ? grad() : AUXSSM_OK;
 }
 
 // the arguments of the batch [c0, c0 + cb) of chains (CsmcArgs::c0)

@@ -187,7 +187,12 @@ template <typename R> struct Cw2Lds {
     static constexpr size_t mvt_bytes(int D) { return (size_t)D * (CSW_MAXD + 1) * sizeof(R); }
     static constexpr size_t guided_bytes(int D) { return ((size_t)2 * D * (CSW_MAXD + 1) + 96 + (size_t)32 * (CSW_MAXD + 1)) * sizeof(R); }
     static constexpr size_t bytes(int D) { return ((size_t)2 * D * (CSW_MAXD + 1) + 2 * D + 128 + (size_t)3 * 64 * (CSW_MAXD + 1) + 96) * sizeof(R) + 64 * sizeof(int) + 64; }
+    // the forward pass's plan: guided adds two D x 33 matrices, one block table and 32 rows of u~ - pred (96 320 bytes in all at dx = 32 in fp64), the
+    // multivariate-t potential its D x 33 precision matrix (with the guided tables 104 768 bytes, the largest plan of this file)
+    static constexpr size_t fwd_bytes(int D, bool guided, bool mvt) { return bytes(D) + (guided ? guided_bytes(D) : 0) + (mvt ? mvt_bytes(D) : 0); }
 };
+static_assert(Cw2Lds<double>::fwd_bytes(CSW_MAXD, true, false) <= 160 * 1024, "the guided forward pass must fit the 160 KB of LDS of a CU");
+static_assert(Cw2Lds<double>::fwd_bytes(CSW_MAXD, true, true) <= 160 * 1024, "the guided forward pass with the multivariate-t potential must fit the 160 KB of LDS of a CU");
 // entry `tid` (< 96) of the block table gauss_half_blk reads, for the lower factor Lf (leading dimension D) with reciprocal diagonal iLf:
 // block jb = 4 (tid / 12): [L10 L20 L21 L30 L31 L32 | i0 i1 i2 i3 | 0 0], zeros beyond D
 template <typename R> __device__ __forceinline__ R cw2_blk_entry(const R* Lf, const R* iLf, int D, int tid) {
@@ -732,6 +737,21 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
     }
 }
 
+// The passes of (model, sweep); wide16: fp32 and no more chains than CUs (run_cw).
+//   forward   guided                 k_cw2_fwd<R, 8, true, MV>                   eight waves whatever the chain count
+//             otherwise              k_cw2_fwd<R, wide16 ? 16 : 8, false, MV>
+//   backward                         k_cw2_bwd<R, wide16 ? 16 : 8>               the base LDS plan (Cw2Lds::bytes)
+// MV: the multivariate-t potential.  The forward pass's LDS is Cw2Lds::fwd_bytes(D, guided, mvt).
+// (guided: under the 128 registers of a 1024-lane workgroup the two extra row products and the second blocked density spill, 360 bytes per lane in fp32:
+// 7.47 ms against 5.11 ms per sweep of the SV protocol at 256 chains)
+template <typename R> using WideKernel = void (*)(CsmcArgs, FkW<R>);
+template <typename R> static WideKernel<R> cw_fwd_kernel(bool guided, bool mvt, bool wide16) {
+    if (guided) return mvt ? k_cw2_fwd<R, 8, true, true> : k_cw2_fwd<R, 8, true>;
+    if (wide16) return mvt ? k_cw2_fwd<R, 16, false, true> : k_cw2_fwd<R, 16>;
+    return mvt ? k_cw2_fwd<R, 8, false, true> : k_cw2_fwd<R, 8>;
+}
+template <typename R> static WideKernel<R> cw_bwd_kernel(bool wide16) { return wide16 ? k_cw2_bwd<R, 16> : k_cw2_bwd<R, 8>; }
+
 // host: the model as one device block [m0 | LP0 | iLP0 | F | b | LQ | iLQ] (csmc_host.h::fk_model, leading dimension D)
 template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void* ctt) {
     const int D = fk->dx;
@@ -772,63 +792,28 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     m.LQ = d; d += D * D;
     m.iLQ = d; d += D;
     m.prec = mvt ? d : nullptr;
-    fk_time_varying<R>(h, fk, a.T, ctt, m);
-    if (a.gb) fk_potbound<R>(h, a, m);
+    int rc = csmc_prologue<R>(h, fk, a, ctt, m, false, [&] {
+        const dim3 grid((unsigned)(((long long)a.C * a.T + 63) / 64));
+        if (mvt) hipLaunchKernelGGL((k_cw_grad<R, true>), grid, dim3(64), 0, h->stream, a, m);
+        else hipLaunchKernelGGL((k_cw_grad<R>), grid, dim3(64), 0, h->stream, a, m);
+        return AUXSSM_OK;
+    });
+    if (rc) return rc;
     const bool guided = fk->proposal == AUXSSM_PROP_AUX_GUIDED;
-    if (fk->proposal == 1) {
-        const long long total = (long long)a.C * a.T * D;
-        hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
-        if (fk->gradient) {
-            const long long tot = (long long)a.C * a.T;
-            if (mvt) hipLaunchKernelGGL((k_cw_grad<R, true>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0, h->stream, a, m);
-            else hipLaunchKernelGGL((k_cw_grad<R>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0, h->stream, a, m);
-        }
-    } else if (guided) {
-        const long long total = (long long)a.C * a.T * D;
-        hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
-        fk_guided<R>(h, a, m);
-    }
-    const size_t lds = Cw2Lds<R>::bytes(D);
-    // the guided forward pass adds two D x 33 matrices, one block table and 32 rows of u~ - pred: 96 320 bytes in all at dx = 32 in fp64
-    const size_t ldsg = lds + Cw2Lds<R>::guided_bytes(D);
-    static_assert(Cw2Lds<double>::bytes(CSW_MAXD) + Cw2Lds<double>::guided_bytes(CSW_MAXD) <= 160 * 1024, "the guided forward pass must fit the 160 KB of LDS of a CU");
-    if (guided && ldsg > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg));
-    // the multivariate-t potential adds its D x 33 precision matrix: with the guided tables 104 768 bytes at dx = 32 in fp64, the largest plan of this file
-    const size_t ldsm = lds + Cw2Lds<R>::mvt_bytes(D), ldsgm = ldsg + Cw2Lds<R>::mvt_bytes(D);
-    static_assert(Cw2Lds<double>::bytes(CSW_MAXD) + Cw2Lds<double>::guided_bytes(CSW_MAXD) + Cw2Lds<double>::mvt_bytes(CSW_MAXD) <= 160 * 1024,
-                  "the guided forward pass with the multivariate-t potential must fit the 160 KB of LDS of a CU");
-    if (mvt && guided && ldsgm > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsgm));
-    if (mvt && !guided && ldsm > 48 * 1024) {
-        AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm));
-        AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm));
-    }
-    if (lds > 48 * 1024) {
-        AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        AX_HIP(hipFuncSetAttribute((const void*)k_cw2_bwd<R, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        AX_HIP(hipFuncSetAttribute((const void*)k_cw2_fwd<R, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        AX_HIP(hipFuncSetAttribute((const void*)k_cw2_bwd<R, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
     const int cb = a.cb > 0 ? a.cb : a.C;
     // sixteen waves per chain (every particle of N <= 32 in its own half-wave at once: the shortest step) while the chains leave CUs to spare, eight (no idle
     // waves at N = 25, two passes) once there are more chains than CUs
     const bool wide16 = sizeof(R) == 4 && a.C <= h->num_cu;  // (fp64: the unrolled loops need more than the 128 registers of a 1024-lane workgroup)
+    const int fwd_waves = wide16 && !guided ? 16 : 8, bwd_waves = wide16 ? 16 : 8;
     for (int c0 = 0; c0 < a.C; c0 += cb) {
         const CsmcArgs ab = csmc_batch(a, c0, cb);
         {
             ProfScope ps(h, AUXSSM_K_CSMC_FWD);
-            // (guided: eight waves whatever the chain count -- under the 128 registers of a 1024-lane workgroup the two extra row products and the second blocked
-            // density spill, 360 bytes per lane in fp32: 7.47 ms against 5.11 ms per sweep of the SV protocol at 256 chains)
-            if (mvt && guided) hipLaunchKernelGGL((k_cw2_fwd<R, 8, true, true>), dim3(ab.C), dim3(512), ldsgm, h->stream, ab, m);
-            else if (mvt && wide16) hipLaunchKernelGGL((k_cw2_fwd<R, 16, false, true>), dim3(ab.C), dim3(1024), ldsm, h->stream, ab, m);
-            else if (mvt) hipLaunchKernelGGL((k_cw2_fwd<R, 8, false, true>), dim3(ab.C), dim3(512), ldsm, h->stream, ab, m);
-            else if (guided) hipLaunchKernelGGL((k_cw2_fwd<R, 8, true>), dim3(ab.C), dim3(512), ldsg, h->stream, ab, m);
-            else if (wide16) hipLaunchKernelGGL((k_cw2_fwd<R, 16>), dim3(ab.C), dim3(1024), lds, h->stream, ab, m);
-            else hipLaunchKernelGGL((k_cw2_fwd<R, 8>), dim3(ab.C), dim3(512), lds, h->stream, ab, m);
+            if ((rc = launch(h, cw_fwd_kernel<R>(guided, mvt, wide16), dim3(ab.C), dim3(64 * fwd_waves), Cw2Lds<R>::fwd_bytes(D, guided, mvt), ab, m))) return rc;
         }
         {
             ProfScope ps(h, AUXSSM_K_CSMC_BWD);
-            if (wide16) hipLaunchKernelGGL((k_cw2_bwd<R, 16>), dim3(ab.C), dim3(1024), lds, h->stream, ab, m);
-            else hipLaunchKernelGGL((k_cw2_bwd<R, 8>), dim3(ab.C), dim3(512), lds, h->stream, ab, m);
+            if ((rc = launch(h, cw_bwd_kernel<R>(wide16), dim3(ab.C), dim3(64 * bwd_waves), Cw2Lds<R>::bytes(D), ab, m))) return rc;
         }
     }
     AX_HIP(hipGetLastError());

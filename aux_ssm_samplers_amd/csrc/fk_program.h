@@ -8,7 +8,7 @@
 
 namespace ax {
 
-// the program's kernels: forward / backward pass with NW = 0 / 8 / 16 (csmc.hip::run_csmc's choice), and the user potential's bound; a gradient program
+// the program's kernels: forward / backward pass with NW = 0 / 8 / 16 (csmc.hip::nw_class; fk_fwd_index / fk_bwd_index pick among them), and the user potential's bound; a gradient program
 // (AUXSSM_FK_USER_GRADIENT) adds the GRAD = true forward passes and the gradient kernel k_csmc_grad
 enum { FK_FWD0 = 0, FK_BWD0 = 3, FK_BOUND = 6, FK_NFUNC_PLAIN = 7, FK_FWDG0 = 7, FK_GRAD = 10, FK_NFUNC = 11 };
 // (name expressions that are not launched functions: k_fk_bound<R, D, true>, whose lowered name equals FK_BOUND's iff the source defines log_g_bound, and

@@ -320,28 +320,23 @@ template <typename R> __global__ void k_pit_trace(PitArgs a, int D) {
 template <typename R, int D> static int run_pit(auxssm_ctx* h, const auxssm_fk_model* fk, PitArgs& a, void* ctt) {
     FkDev<R> m = fk_dev<R>(fk);
     const int TB = (a.N + 63) / 64 * 64;
-    fk_time_varying<R>(h, fk, a.T, ctt, m);  // (csmc.py:103 scans Mt.params; here AuxiliaryGt's Mt, independent.py:238-248)
-    if (fk->gradient) {  // u and the gradient of the model's joint log-density at u (independent.py:82, :121-134): the sequential sweep's kernels
-        CsmcArgs ca{};
-        ca.C = a.C; ca.T = a.T; ca.N = a.N;
-        ca.y = a.y; ca.shd = a.shd; ca.x = a.x; ca.u = const_cast<void*>(a.u); ca.grad = const_cast<void*>(a.grad);
-        ca.noise_mode = a.noise_mode; ca.key0 = a.key0; ca.key1 = a.key1; ca.eps_aux = a.eps_aux;
-        const long long total = (long long)a.C * a.T * D, tot = (long long)a.C * a.T;
-        hipLaunchKernelGGL((k_csmc_aux<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, ca, D);
-        if (fk->potential == AUXSSM_POT_MVT) hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, true>>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, ca, m);
-        else hipLaunchKernelGGL((k_csmc_grad<R, D>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, ca, m);
-        hipLaunchKernelGGL((k_pit_leaves<R, D, true>), dim3(a.T, a.C), dim3(TB), 0, h->stream, a, m);
-    } else {
-        hipLaunchKernelGGL((k_pit_leaves<R, D, false>), dim3(a.T, a.C), dim3(TB), 0, h->stream, a, m);
-    }
+    // the sequential sweep's prologue on a CsmcArgs view: the time-varying constants (csmc.py:103 scans Mt.params; here AuxiliaryGt's Mt, independent.py:238-248)
+    // and, for gradient proposals, u and the gradient of the model's joint log-density at u (independent.py:82, :121-134) -- a.u is null without them
+    CsmcArgs ca{};
+    ca.C = a.C; ca.T = a.T; ca.N = a.N;
+    ca.y = a.y; ca.shd = a.shd; ca.x = a.x; ca.u = const_cast<void*>(a.u); ca.grad = const_cast<void*>(a.grad);
+    ca.noise_mode = a.noise_mode; ca.key0 = a.key0; ca.key1 = a.key1; ca.eps_aux = a.eps_aux;
+    int rc = csmc_prologue<R, false>(h, fk, ca, ctt, m, false, [&] { return builtin_grad<R, D>(h, ca, m); });
+    if (rc) return rc;
+    if (m.gradient) hipLaunchKernelGGL((k_pit_leaves<R, D, true>), dim3(a.T, a.C), dim3(TB), 0, h->stream, a, m);
+    else hipLaunchKernelGGL((k_pit_leaves<R, D, false>), dim3(a.T, a.C), dim3(TB), 0, h->stream, a, m);
     const int NCH = a.N <= 32 ? 64 : (a.N <= 128 ? 256 : 1024);  // part of the arithmetic contract (header)
     const size_t lds = ((size_t)a.N * (2 * D + 2) + NCH + 48 + (size_t)PIT_SC * NCH) * sizeof(R) + 64;
-    if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_pit_stitch<R, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     {
         ProfScope ps(h, AUXSSM_K_PIT_STITCH);
         for (int k = 0; k < a.K; ++k) {
             const long long nodes = ((long long)a.T + (2ll << k) - 1) >> (k + 1);
-            hipLaunchKernelGGL((k_pit_stitch<R, D>), dim3((unsigned)nodes, a.C), dim3(NCH), lds, h->stream, a, m, k);
+            if ((rc = launch(h, k_pit_stitch<R, D>, dim3((unsigned)nodes, a.C), dim3(NCH), lds, a, m, k))) return rc;
         }
     }
     const long long total = (long long)a.C * a.T;
@@ -400,32 +395,27 @@ extern "C" int auxssm_csmc_pit_sweep(auxssm_handle h, int dtype, const auxssm_fk
     const size_t sR = dtype == AUXSSM_F32 ? 4 : 8;
     const size_t CT = (size_t)C * T;
     const size_t tree = (size_t)C * tot * N * sizeof(uint16_t);
-    size_t need = 8192 + CT * N * D * sR + (size_t)C * N * sR + 4 * (tree + 256);
-    if (fk->gradient) need += 2 * (CT * D * sR + 256) + CT * N * sR + 256;  // u, grad, the leaf log-weights of every time step
-    if (fk->F_t) need += (size_t)T * (1 + D) * sR + 256;
-    int rc = ws_reserve(h, need);
-    if (rc) return rc;
     a.y = fk->y;
     a.shd = sqrt_half_delta;
     a.x = x;
-    a.xs = ws_take(h, CT * N * D * sR);
-    a.lw0 = ws_take(h, (size_t)C * N * sR);
-    if (fk->gradient) {  // (in the parallel kernel the correction is per particle in either mode: pit/csmc.py:83-88 has no summed variant)
-        a.u = ws_take(h, CT * D * sR);
-        a.grad = ws_take(h, CT * D * sR);
-        a.lwt = ws_take(h, CT * N * sR);
-        if (!a.u || !a.grad || !a.lwt) return AUXSSM_ERR_NOMEM;
-    }
-    void* ctt = fk->F_t ? ws_take(h, (size_t)T * (1 + D) * sR) : nullptr;
-    if (fk->F_t && !ctt) return AUXSSM_ERR_NOMEM;
-    a.Ls = (uint16_t*)ws_take(h, tree);
-    a.Rs = (uint16_t*)ws_take(h, tree);
-    a.Fi = (uint16_t*)ws_take(h, tree);
-    a.La = (uint16_t*)ws_take(h, tree);
     a.anc = ancestors;
     a.noise_mode = noise->mode;
     a.key0 = noise->key0; a.key1 = noise->key1;
     a.eps_aux = noise->eps_aux; a.eps_prop = noise->eps_prop; a.u_res = noise->u_res;
-    if (!a.xs || !a.lw0 || !a.Ls || !a.Rs || !a.Fi || !a.La) return AUXSSM_ERR_NOMEM;
+    WsPlan ws;
+    void* ctt = nullptr;
+    ws.add(a.xs, CT * N * D * sR);
+    ws.add(a.lw0, (size_t)C * N * sR);
+    if (fk->gradient) {  // (in the parallel kernel the correction is per particle in either mode: pit/csmc.py:83-88 has no summed variant)
+        ws.add(a.u, CT * D * sR);
+        ws.add(a.grad, CT * D * sR);
+        ws.add(a.lwt, CT * N * sR);  // the leaf log-weights of every time step
+    }
+    if (fk->F_t) ws.add(ctt, (size_t)T * (1 + D) * sR);
+    ws.add(a.Ls, tree);
+    ws.add(a.Rs, tree);
+    ws.add(a.Fi, tree);
+    ws.add(a.La, tree);
+    if (int rc = ws.reserve(h)) return rc;
     return csmc_dispatch(dtype, D, [&](auto r, auto d) { return run_pit<decltype(r), decltype(d)::value>(h, fk, a, ctt); });
 }

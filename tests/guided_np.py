@@ -136,7 +136,8 @@ def closed_form(m, t, x, x_prev, u, s):
 
 
 # ---- the cases of the test files: the model on both sides (device family objects, literal objects) -------------------------------------------------------
-CASES = [(1, 1024, 60), (2, 100, 40), (4, 65, 33), (8, 25, 20), (30, 25, 25), (32, 64, 12)]
+CASES = [(1, 1024, 60), (2, 100, 40), (4, 65, 33), (8, 25, 20), (30, 25, 25), (32, 64, 12),
+         (1, 512, 3)]  # eight full waves: the guided kernels have no instantiation of that shape, the generic workgroup runs it (csmc.hip::fwd_kernel)
 
 
 def spd(d, rng, base=0.3, small=0.05):

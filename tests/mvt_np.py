@@ -55,6 +55,14 @@ class Model(G.Model):
         super().__init__(m0, P0, dyn, Q, MvtPotential(nu, prec, y[0], first=True), MvtPotential(nu, prec, y[1:]), "mvt", y)
         self.nu, self.prec = float(nu), np.asarray(prec, np.float64)
         self.F, self.b = np.asarray(dyn.params[0][0], float), np.asarray(dyn.params[1][0], float)
+        self.tv = False  # time-varying transitions: dyn.params has a row per transition, Q / LQ / F / b above are those of the first
+
+    def trans(self, t):
+        """(F, b, Q, chol Q) of the transition into step t >= 1"""
+        if not self.tv:
+            return self.F, self.b, self.Q, self.LQ
+        F, b, LQ = (np.asarray(p[t - 1], float) for p in self.dyn.params)
+        return F, b, LQ @ LQ.T, LQ
 
     def literal(self):
         """(M0, G0, Mt, Gt) of the literal sampler"""
@@ -65,12 +73,12 @@ def joint_grad(m, u):
     """the gradient at u (T, d) of log M0(u_0) + G0(u_0) + sum_t [log Mt(u_{t+1} | u_t) + Gt(u_{t+1})] (csmc/independent.py:121-134), in closed form"""
     T = u.shape[0]
     g = np.stack([grad_log_g(u[t], m.y[t], m.nu, m.prec) for t in range(T)])
-    iP0, iQ = np.linalg.inv(m.P0), np.linalg.inv(m.Q)
-    g[0] -= iP0 @ (u[0] - m.m0)
+    g[0] -= np.linalg.inv(m.P0) @ (u[0] - m.m0)
     for t in range(1, T):
-        w = iQ @ (u[t] - (m.F @ u[t - 1] + m.b))
+        F, b, Q, _ = m.trans(t)
+        w = np.linalg.inv(Q) @ (u[t] - (F @ u[t - 1] + b))
         g[t] -= w
-        g[t - 1] += m.F.T @ w
+        g[t - 1] += F.T @ w
     return g
 
 
@@ -111,9 +119,10 @@ def bootstrap_kernel(m, N, backward=False):
 
 
 # ---- cases: the model on both sides ---------------------------------------------------------------------------------------------------------------------
-def case(d, T, rng, nu=4.0, prec=None, nan_rows=(), walk=False):
+def case(d, T, rng, nu=4.0, prec=None, nan_rows=(), walk=False, tv=False):
     """linear-Gaussian dynamics with the multivariate-t potential: tests/guided_np.py::sv_case's dynamics, or (walk) the spatial example's random walk
-    x_t = x_{t-1} + eps; prec: default a dense random SPD matrix.  nan_rows: time steps whose observation has a NaN component (the step is flat).
+    x_t = x_{t-1} + eps, or (tv) sv_case's dynamics with an F_t, b_t and Q_t of its own for each of the T - 1 transitions; prec: default a dense random SPD
+    matrix.  nan_rows: time steps whose observation has a NaN component (the step is flat).
     Returns (device objects (M0, G0, Mt, Gt), literal Model, a trajectory, delta in [0.2, 0.8] / d: proposals that N <= 64 particles can follow at every d)."""
     from aux_ssm_samplers_amd.csmc import GaussianInit, LinearGaussianDynamics, MultivariateTPotential
     if walk:
@@ -122,6 +131,11 @@ def case(d, T, rng, nu=4.0, prec=None, nan_rows=(), walk=False):
         F = 0.9 * np.eye(d) + 0.02 * rng.standard_normal((d, d)) / np.sqrt(d)
         b = 0.05 * rng.standard_normal(d)
         Q, P0, m0 = G.spd(d, rng), G.spd(d, rng, 0.5), 0.1 * rng.standard_normal(d)
+    if tv:
+        F = F + 0.05 * rng.standard_normal((T - 1, d, d)) / np.sqrt(d)
+        b = b + 0.05 * rng.standard_normal((T - 1, d))
+        Q = np.stack([G.spd(d, rng) for _ in range(T - 1)])
+    Ft, bt, Qt = (np.broadcast_to(a, (T - 1,) + a.shape[-n:]) for a, n in ((F, 2), (b, 1), (Q, 2)))
     if prec is None:
         A = rng.standard_normal((d, d))
         prec = 1.5 * np.eye(d) + 0.8 * (A @ A.T) / d
@@ -129,14 +143,15 @@ def case(d, T, rng, nu=4.0, prec=None, nan_rows=(), walk=False):
     x = np.zeros((T, d))
     x[0] = m0 + np.linalg.cholesky(P0) @ rng.standard_normal(d)
     for t in range(1, T):
-        x[t] = F @ x[t - 1] + b + np.linalg.cholesky(Q) @ rng.standard_normal(d)
+        x[t] = Ft[t - 1] @ x[t - 1] + bt[t - 1] + np.linalg.cholesky(Qt[t - 1]) @ rng.standard_normal(d)
     Lc = np.linalg.cholesky(np.linalg.inv(prec))
     y = x + (rng.standard_normal((T, d)) @ Lc.T) / np.sqrt(rng.chisquare(nu, T) / nu)[:, None]
     for i, t in enumerate(nan_rows):
         y[t, i % d] = np.nan
     M0, Mt = GaussianInit(m0=m0, P0=P0), LinearGaussianDynamics(F=F, b=b, Q=Q)
     dev = (M0, MultivariateTPotential(nu=nu, prec=prec, y=y[0]), Mt, MultivariateTPotential(nu=nu, prec=prec, params=y[1:]))
-    m = Model(m0, P0, L.LinearGaussianDynamics(F, b, np.linalg.cholesky(Q), T), Q, nu, prec, y)
+    m = Model(m0, P0, L.LinearGaussianDynamics(F, b, np.linalg.cholesky(Q), T), Qt[0], nu, prec, y)
+    m.tv = tv
     return dev, m, x, (0.2 + 0.6 * rng.random(T)) / d
 
 

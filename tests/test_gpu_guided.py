@@ -87,7 +87,7 @@ def test_guided_models_of_the_closed_family(model, gradient):
 
 
 @pytest.mark.parametrize("batched", [False, True])
-@pytest.mark.parametrize("d,N", [(2, 100), (1, 1024), (8, 25)])
+@pytest.mark.parametrize("d,N", [(2, 100), (1, 1024), (8, 25), (1, 65), (1, 512)])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_keyed_noise_equals_explicit_noise(dtype, d, N, batched, monkeypatch):
     """a Threefry sweep and an explicit sweep on _device.key_noise of the same key: bitwise equal, register and wide path, several chains; batched: more chains
@@ -96,6 +96,8 @@ def test_keyed_noise_equals_explicit_noise(dtype, d, N, batched, monkeypatch):
     from aux_ssm_samplers_amd.csmc import _device
     rng = np.random.default_rng(11 * d)
     T, Cn = 21, (260 if d == 8 else 5)  # (wide path: more chains than CUs, the eight-wave kernel in fp32 too)
+    if N in (65, 512):  # a partial last wave and eight full waves, both on the generic workgroup: two chains, three steps (the paired Threefry step has a tail)
+        T, Cn = 3, 2
     dev, m, xtrue, delta = G.sv_case(d, T, rng)
     x0 = (xtrue[None] + 0.3 * rng.standard_normal((Cn, T, d))).astype(dtype)
     key = R.PRNGKey(77)

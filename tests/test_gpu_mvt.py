@@ -71,10 +71,14 @@ def test_builtin_potential_equals_the_user_program_bit_for_bit(dtype, d, N, T, C
 # ---- 2. literal parity -----------------------------------------------------------------------------------------------------------------------------------
 def _literal_case(name, rng):
     """(d, N, T) and the model: register path (1, 1024, 40), (3, 100, 33); wide path (5, 33, 20), the 3 x 3 and 5 x 5 grids of the spatial example
-    (random walk, its precision matrix; nu = 1 on the 5 x 5 grid, the example's own value) and (32, 64, 12)"""
+    (random walk, its precision matrix; nu = 1 on the 5 x 5 grid, the example's own value) and (32, 64, 12); time-varying transitions on the register path at
+    N = 65, 512 and 1024 (a partial last wave, eight and sixteen full waves: this potential runs the generic workgroup at every N), three steps"""
     from aux_ssm_samplers_amd.workloads import spatial_precision
-    d, N, T = dict(r1=(1, 1024, 40), r3=(3, 100, 33), w5=(5, 33, 20), grid3=(9, 25, 20), grid5=(25, 25, 25), w32=(32, 64, 12))[name]
-    if name.startswith("grid"):
+    d, N, T = dict(r1=(1, 1024, 40), r3=(3, 100, 33), w5=(5, 33, 20), grid3=(9, 25, 20), grid5=(25, 25, 25), w32=(32, 64, 12),
+                   tv65=(1, 65, 3), tv512=(1, 512, 3), tv1024=(1, 1024, 3))[name]
+    if name.startswith("tv"):
+        dev, m, xtrue, delta = MV.case(d, T, rng, tv=True)
+    elif name.startswith("grid"):
         dev, m, xtrue, delta = MV.case(d, T, rng, nu=1.0 if name == "grid5" else 3.0, prec=spatial_precision(int(name[-1])), walk=True, nan_rows=(4,))
     else:
         dev, m, xtrue, delta = MV.case(d, T, rng, nan_rows=(2, T - 1))
@@ -120,7 +124,8 @@ def _against_literal(style, gradient, backward, name, seed):
             if t == 0:
                 dens = L._mvn_chol_logpdf(hist["xs"][0], m.m0, m.LP0)
             else:
-                dens = L._mvn_chol_logpdf(hist["xs"][t], hist["xs"][t - 1][hist["As"][t - 1]] @ m.F.T + m.b, m.LQ)
+                F, b, _, LQ = m.trans(t)
+                dens = L._mvn_chol_logpdf(hist["xs"][t], hist["xs"][t - 1][hist["As"][t - 1]] @ F.T + b, LQ)
             npt.assert_allclose(hist["log_ws"][t], g + dens, rtol=1e-10, atol=1e-10)
     return anc, ex, el
 
@@ -130,7 +135,8 @@ def _against_literal(style, gradient, backward, name, seed):
 def test_sweep_fp64_equals_the_literal_sampler(style, gradient, backward):
     """register and wide path; a single case may update nothing, over the set every (style, gradient, backward) cell moves the trajectory somewhere"""
     moved = 0
-    for i, name in enumerate(("r1", "r3", "w5", "grid3", "grid5", "w32")):
+    names = ("r1", "r3", "w5", "grid3", "grid5", "w32") + (() if style == "guided" else ("tv65", "tv512", "tv1024"))  # (guided: time-invariant transitions only)
+    for i, name in enumerate(names):
         moved += int((_against_literal(style, gradient, backward, name, 7000 + 10 * i + backward)[0] != 0).sum())
     assert moved > 0
 

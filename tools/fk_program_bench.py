@@ -2,7 +2,7 @@
 
   compile   hipRTC time of one program (the sweep's seven kernels), f32 / f64 x dx = 1 / 4, a potential + mean source; no device needed
   sweep     C3's shape (SV d = 1, N = 1024, fp32, 256 chains, independent auxiliary proposals, backward sampling, Threefry noise) in sweeps/s:
-              builtin        the closed family -- C3's special SP = 1 instantiation of k_csmc_fwd (csmc.hip::run_csmc, c3_shape)
+              builtin        the closed family -- C3's special SP = 1 instantiation of k_csmc_fwd (csmc.hip::fwd_kernel, c3_shape)
               builtin_trace  the closed family with the ancestor trace stored (As_out), which the SP = 1 path excludes: the generic NW = 16 kernel
               user           the same potential and bound as user source (csmc/device_models.py::BUILTIN_SV): the program's NW = 16 kernel
               user_trace     the same with the ancestor trace stored (like for like with builtin_trace)

@@ -7,6 +7,7 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "aux_ssm_samplers_amd", "csrc")
+NO_CONTRACT = ("csmc.hip", "csmc_wide.hip", "pit.hip", "loop.hip")  # the units csrc/Makefile builds with -ffp-contract=off
 KEYS = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]")
 
 
@@ -38,7 +39,7 @@ def demangle(names):
 def table(unit):
     """{demangled kernel or device-function name: resources} of one unit of csrc/"""
     src = os.path.join(CSRC, unit)
-    res = resources(src, ["-ffp-contract=off"] if unit in ("csmc.hip", "pit.hip", "loop.hip") else [])
+    res = resources(src, ["-ffp-contract=off"] if unit in NO_CONTRACT else [])
     names = list(res)
     return dict(zip(demangle(names), (res[n] for n in names)))
 
@@ -52,7 +53,7 @@ if __name__ == "__main__":
     if not os.path.exists(src):
         src = os.path.join(CSRC, os.path.basename(src))
     flt = sys.argv[2:]
-    res = resources(src, ["-ffp-contract=off"] if os.path.basename(src) in ("csmc.hip", "pit.hip", "loop.hip") else [])
+    res = resources(src, ["-ffp-contract=off"] if os.path.basename(src) in NO_CONTRACT else [])
     names = list(res)
     for n, dn in zip(names, demangle(names)):
         if flt and not all(f in dn for f in flt):
