@@ -50,6 +50,8 @@ def get_kernel(Mt, G0, Gt, N, Qt=None):
 
     def init(x_star):
         T = np.shape(x_star)[0]
-        return CSMCState(x=x_star, updated=np.zeros((T,), bool))  # pit/csmc.py:60-63
+        # pit/csmc.py:60-63: `ancestors == 0` of zero ancestors -> all True, like the sequential primitive (_primitives/csmc/csmc.py:61-64); only the
+        # csmc/independent.py wrapper starts from `ancestors != 0` (:113-116)
+        return CSMCState(x=x_star, updated=np.ones((T,), bool))
 
     return init, kernel

@@ -177,7 +177,8 @@ def test_fp32_ancestors_against_the_literal_order_tie_rate(style, grid, N):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_parallel_in_time_sweep_runs_and_returns_consistent_paths(dtype, d, N, T, gradient):
     """parallel=True: finite trajectories whose every step is the leaf particle its ancestor index names (slot 0 = the reference trajectory), keyed ==
-    explicit noise, and the trajectory moves"""
+    explicit noise, and the trajectory moves.  WHICH particles the stitches pick -- the observation row, the transition term and the whole precision matrix in the
+    stitch weights -- is held against the literal tree of oracle/pit_np.py in tests/test_gpu_pit_literal.py::test_hip_pit_sweep_student_t_fp64_equals_the_literal_tree"""
     from aux_ssm_samplers_amd import _lib, random as R
     from aux_ssm_samplers_amd.csmc import _device
     rng = np.random.default_rng(10 * d + N)

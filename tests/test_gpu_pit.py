@@ -138,7 +138,7 @@ def test_reference_call_shape_through_pit_get_kernel(gradient):
     init, kernel = pit.get_kernel(mt, AuxiliaryG0(M0=M0, G0=G0), AuxiliaryGt(Mt=Mt, Gt=Gt), N, qt)
     key = R.PRNGKey(11)
     st = init(x)
-    assert st.updated.shape == (T,) and not st.updated.any()
+    assert st.updated.shape == (T,) and st.updated.all()  # pit/csmc.py:60-63: `ancestors == 0` (tests/test_oracle_pit_literal.py::test_init_states)
     out = kernel(key, st)
     h = _lib.default_handle()
     k_prop, k_res = R.split(key, 2)

@@ -1,0 +1,195 @@
+"""The two oracles of the PARALLEL-IN-TIME cSMC sweep against each other (CPU only):
+
+* `oracle/pit_np.py` -- the LITERAL NumPy restatement of the reference's tree (pit/csmc.py, operator.py, dc_map.py driven as csmc/independent.py:78-118 does):
+  everything padded to 2^K with NaN, whole blocks gathered at every stitch, padded right children passed through, normalised weights, plain cumsum,
+  `searchsorted`, N pinned draws per stitch and one unpinned draw at the root;
+* `oracle/csmc_ref.c::csmc_ref_pit_sweep` -- the CONTRACT oracle the HIP kernels of csrc/pit.hip reproduce bit for bit (unnormalised `exp(v - max)`, N^2 values
+  in 64 / 256 / 1024 chunks of 8 sub-chunks, a three-level search), designed together with the kernels.
+
+fp64, identical explicit noise: identical origins; trajectory and leaf particles within rtol = atol = 1e-12, the bar tests/test_oracle_csmc_literal.py sets for
+the same comparison of the sequential sweep.
+
+Ties.  An index can differ legitimately only where a draw lies within summation-order rounding of a cell edge, so every case FIRST asserts, on the literal
+alone, that its smallest draw margin (the distance from r = c[-1] (1 - u) to the nearer edge of its cell, in units of c[-1]) is >= 2 N^2 eps: N^2 eps bounds
+the difference between any two orders of summing N^2 non-negative terms of total 1, the factor 2 covers the per-term rounding of exp and of the normalisation.
+The seeds of tests/pit_cases.py were chosen for this (a condition on the inputs, not a measurement of either side); with it met, an index mismatch is a defect
+of the contract, never a tie.  The cells: tests/pit_cases.py."""
+import numpy as np
+import numpy.testing as npt
+import pytest
+
+from oracle import csmc_np as L
+from oracle import pit_np as P
+from tests import pit_cases as PC
+
+
+def test_cells_cover_every_value_with_gradient_and_time_varying_off_and_on():
+    """the table itself: each N, T, d and potential of the list appears with gradient proposals off and on and with time-varying transitions off and on
+    (the Lorenz-63 transition has no time-varying form: gradient only); N = 1024 only at T <= 3, every other cell at T <= 37"""
+    cells = PC.CELLS
+    assert 38 <= len(cells) <= 44 and len(set(cells)) == len(cells)
+    want = dict(N=[2, 16, 32, 33, 100, 128, 129, 256, 1024], T=[2, 3, 5, 8, 9, 33, 37], d=[1, 2, 3, 4, "lorenz"], pot=[PC.FLAT, PC.GAUSS, PC.SV, PC.MASKED])
+    col = dict(d=0, N=1, T=2, pot=3)
+    for name, values in want.items():
+        assert sorted(set(c[col[name]] for c in cells), key=str) == sorted(values, key=str), name
+        for v in values:
+            rows = [c for c in cells if c[col[name]] == v]
+            assert {c[4] for c in rows} == {0, 1}, (name, v, "gradient")
+            assert {c[5] for c in rows} == ({0} if v == "lorenz" else {0, 1}), (name, v, "time-varying")
+    for d, N, T, *_ in cells:
+        assert T <= (3 if N == 1024 else 37)
+    assert {(c[2]) for c in cells if c[1] == 1024} == {2, 3}
+
+
+@pytest.mark.parametrize("cell", PC.CELLS, ids=PC.cell_id)
+def test_contract_oracle_equals_the_literal_tree_fp64(cell):
+    c = PC.case(cell)
+    x, origins, hist = PC.literal(cell)
+    threshold = PC.margin_threshold(c.N)
+    print(f"{PC.cell_id(cell)}: smallest draw margin {hist['min_margin']:.2e} (threshold {threshold:.2e}), {len(hist['stitches'])} stitches, "
+          f"{int((origins != 0).sum())} of {c.T} steps updated")
+    assert hist["min_margin"] >= threshold                       # the condition on the inputs: no draw of this case is a tie
+    ref = c.oracle_sweep()
+    npt.assert_array_equal(ref["ancestors"], origins)
+    npt.assert_allclose(ref["xs"], hist["xs"], rtol=1e-12, atol=1e-12)
+    npt.assert_allclose(ref["x"], x, rtol=1e-12, atol=1e-12)
+    if c.pot == PC.MASKED:
+        assert np.all(np.isnan(c.y[PC.top_boundary(c.T)]))         # the whole missing step sits on the root's stitch boundary
+        assert hist["stitches"][-1]["t"] == PC.top_boundary(c.T)
+
+
+# ---- the literal by itself -------------------------------------------------------------------------------------------------------------------------------
+STRUCTURE = [c for c in PC.CELLS if c[1] <= 33 and c[2] in (2, 3, 5, 8, 9, 37)]
+
+
+@pytest.mark.parametrize("cell", STRUCTURE, ids=PC.cell_id)
+def test_literal_tree_structure(cell):
+    """slot 0 of every leaf is x0; the output is made of leaf particles, origins naming them; every boundary 1..T-1 is stitched exactly once, in the order of
+    the levels, and nothing else is (padded right children pass through); N pairs per stitch with pair 0 pinned, one unpinned pair at the root; forcing every
+    uniform to 1 - 2^-53 (r -> the first cell) returns the reference trajectory with all origins 0"""
+    c = PC.case(cell)
+    x, origins, hist = PC.literal(cell)
+    T, N = c.T, c.N
+    npt.assert_array_equal(hist["xs"][:, 0], c.x0)
+    assert origins.shape == (T,) and origins.min() >= 0 and origins.max() < N and x.shape == (T, c.d)
+    npt.assert_array_equal(x, hist["xs"][np.arange(T), origins])
+    npt.assert_allclose(np.exp(hist["log_ws"]).sum(axis=1), 1.0, rtol=1e-12)
+    if not c.gradient:
+        npt.assert_allclose(hist["log_ws"][1:], -np.log(N), rtol=1e-15)
+    K = P.next_power_of_2(T).bit_length() - 1
+    levels = [[s0 + 2 ** k for s0 in range(0, T, 2 ** (k + 1)) if s0 + 2 ** k < T] for k in range(K)]
+    assert [s["t"] for s in hist["stitches"]] == [t for lev in levels for t in lev]
+    assert sorted(s["t"] for s in hist["stitches"]) == list(range(1, T))
+    for s in hist["stitches"][:-1]:
+        assert s["left"].shape == s["right"].shape == (N,) and s["left"][0] == 0 and s["right"][0] == 0 and s["margins"].shape == (N - 1,)
+    root = hist["stitches"][-1]
+    assert root["left"].shape == () and root["margins"].shape == (1,) and root["t"] == PC.top_boundary(T)
+    forced = dict(c.noise, u_res=np.full((T, N), 1.0 - 2.0 ** -53))
+    xf, of, _ = c.literal_sweep(forced)
+    npt.assert_array_equal(of, 0)
+    npt.assert_array_equal(xf, c.x0)
+
+
+@pytest.mark.parametrize("kind,cell", [("gauss", (2, 8, 8, PC.SV, 0, 1, 0)), ("gauss", (3, 5, 4, PC.MASKED, 1, 0, 0)), ("gauss", ("lorenz", 6, 8, PC.GAUSS, 1, 0, 0)),
+                                       ("gauss", (1, 7, 2, PC.FLAT, 0, 0, 0)), ("mvt", (3, 6, 8, 4.0, 1, 0)), ("mvt", (2, 8, 4, 1.0, 0, 0))])
+def test_literal_tree_equals_a_naive_recursion_at_powers_of_two(kind, cell):
+    """T = 2^K: the padded tree has no padding, and must equal a second restatement that has none of its machinery (oracle/pit_np.py::naive_power_of_two:
+    top-down recursion, pair by pair weights, no parameter tree) -- same origins, same trajectory bit for bit up to the order of one addition"""
+    c = PC.Case(cell) if kind == "gauss" else PC.MvtCase(cell)
+    x, origins, hist = c.literal_sweep()
+    M0, G0, Mt, Gt = c.literal_objects()
+    T, N = c.T, c.N
+    shd = np.sqrt(0.5 * c.delta)
+    u = c.x0 + shd[:, None] * c.noise["eps_aux"]
+    grad = c.joint_grad(u) if c.gradient else None
+    mt = [P.AuxiliaryMtDistribution((u[t], shd[t], None if grad is None else grad[t])) for t in range(T)]
+    qt = [P.AuxiliaryMtDistribution((u[t], shd[t], None)) for t in range(T)] if c.gradient else None
+    xn, on = P.naive_power_of_two(L.Noise(u_bwd=None, **c.noise), c.x0, mt, L.AuxiliaryG0(M0, G0), L.AuxiliaryGt(Mt, Gt), N, qt)
+    assert hist["min_margin"] >= PC.margin_threshold(N)
+    npt.assert_array_equal(on, origins)
+    npt.assert_array_equal(xn, x)
+    assert (origins != 0).any()
+
+
+def test_margins_are_distances_to_the_cell_edges():
+    p = np.array([0.1, 0.2, 0.0, 0.3, 0.4])
+    u = np.array([0.95, 0.75, 0.3, 0.0])          # r = 0.05, 0.25, 0.7, 1.0
+    idx = L.choice(u, p)
+    npt.assert_array_equal(idx, [0, 1, 4, 4])
+    npt.assert_allclose(P.margins(u, p, idx), [0.05, 0.05, 0.1, 0.0], atol=1e-15)
+
+
+@pytest.mark.parametrize("cell", [(2, 16, 5, PC.SV, 1, 1, 0), (3, 16, 5, PC.MASKED, 1, 0, 0), ("lorenz", 16, 5, PC.GAUSS, 1, 0, 0), (1, 16, 5, PC.FLAT, 1, 1, 0)])
+def test_closed_form_joint_gradient_equals_central_differences(cell):
+    """tests/pit_cases.py::Case.joint_grad (what stands in for jax.grad where particles are held to 1e-12) against csmc_np.grad_fd of csmc_np._log_pdf, the
+    literal's own stand-in; and the literal sweep with either gradient picks the same origins.  Allowance: 10 x the 9.6e-11 measured for grad_fd itself on a
+    density with a known gradient (tests/test_user_model_literals.py), relative to max(1, |gradient|_inf)"""
+    c = PC.Case(cell)
+    M0, G0, Mt, Gt = c.literal_objects()
+    u = c.x0 + np.sqrt(0.5 * c.delta)[:, None] * c.noise["eps_aux"]
+    g = c.joint_grad(u)
+    fd = L.grad_fd(lambda v: float(np.sum(L._log_pdf(v, M0, G0, Mt, Gt))), u)
+    err = np.max(np.abs(g - fd)) / max(1.0, np.max(np.abs(fd)))
+    print(f"{PC.cell_id(cell)}: closed form vs central differences {err:.1e}")
+    assert err <= 9.6e-10
+    nz = L.Noise(u_bwd=None, **c.noise)
+    xa, oa, ha = c.literal_kernel(closed_form=True)(nz, c.x0, c.delta)
+    xb, ob, hb = c.literal_kernel(closed_form=False)(nz, c.x0, c.delta)
+    npt.assert_array_equal(oa, ob)
+    npt.assert_allclose(ha["xs"], hb["xs"], rtol=1e-7, atol=1e-7)
+    assert np.max(np.abs(ha["xs"][:, 1:] - (u[:, None, :] + np.sqrt(0.5 * c.delta)[:, None, None] * c.noise["eps_prop"])[:, 1:])) > 0  # the proposals are shifted
+
+
+def test_student_t_literal_reads_y_the_transition_and_the_whole_precision_matrix():
+    """what the Student-t cells of tests/test_gpu_pit_literal.py can tell apart: the literal's origins change when the stitch reads y[t - 1] for y[t], when the
+    transition term is dropped, and when the precision matrix loses its off-diagonal"""
+    from tests import mvt_np as MV
+    cell = (3, 33, 9, 4.0, 0, 0)
+    c = PC.MvtCase(cell)
+    x, origins, hist = c.literal_sweep()
+    M0, G0, Mt, Gt = c.literal_objects()
+    nz = L.Noise(u_bwd=None, **c.noise)
+    y, nu, prec = c.m.y, c.m.nu, c.m.prec
+
+    def run(G0_, Mt_, Gt_):
+        return P.get_independent_parallel_kernel(M0, G0_, Mt_, Gt_, c.N)[1](nz, c.x0, c.delta)[1]
+
+    class NoTransition(L.LinearGaussianDynamics):
+        def logpdf(self, x_t_p_1, x_t, params):
+            return np.zeros(np.shape(x_t_p_1)[:-1])
+
+    npt.assert_array_equal(run(G0, Mt, Gt), origins)
+    assert np.any(run(G0, Mt, MV.MvtPotential(nu, prec, y[:-1])) != origins)
+    assert np.any(run(G0, NoTransition(c.m.F, c.m.b, c.m.LQ, c.T), Gt) != origins)
+    diag = np.diag(np.diag(prec))
+    assert np.any(run(MV.MvtPotential(nu, diag, y[0], first=True), Mt, MV.MvtPotential(nu, diag, y[1:])) != origins)
+
+
+# ---- init() ------------------------------------------------------------------------------------------------------------------------------------------------
+def test_init_states():
+    """the reference's three `init`s: both primitives return `ancestors == 0` of zero ancestors, all True (_primitives/csmc/csmc.py:61-64, pit/csmc.py:60-63);
+    the csmc/independent.py wrapper of the parallel kernel returns `ancestors != 0`, all False (:113-116).  The literals say the same."""
+    from aux_ssm_samplers_amd._primitives.csmc import get_kernel as get_sequential_primitive
+    from aux_ssm_samplers_amd._primitives.csmc import pit
+    from aux_ssm_samplers_amd.csmc import get_independent_kernel, GaussianInit, LinearGaussianDynamics, GaussianObsPotential
+    from aux_ssm_samplers_amd.csmc.independent import AuxiliaryMtDistribution, AuxiliaryG0, AuxiliaryGt
+    T, d, N = 5, 2, 8
+    y = np.zeros((T, d))
+    M0, Mt = GaussianInit(m0=np.zeros(d), P0=np.eye(d)), LinearGaussianDynamics(F=0.9 * np.eye(d), b=np.zeros(d), Q=np.eye(d))
+    G0, Gt = GaussianObsPotential(sig=1.0, y=y[0]), GaussianObsPotential(sig=1.0, params=y[1:])
+    x = np.arange(T * d, dtype=np.float64).reshape(T, d)
+
+    def check(init, value):
+        st = init(x)
+        assert st.x is x and st.updated.shape == (T,) and st.updated.dtype == bool and np.all(st.updated == value)
+
+    check(get_sequential_primitive(M0, G0, Mt, Gt, N)[0], True)
+    for grad in (None, np.zeros((T, d))):
+        mt = AuxiliaryMtDistribution(params=(x, 0.5 * np.ones(T), grad))
+        qt = None if grad is None else AuxiliaryMtDistribution(params=(x, 0.5 * np.ones(T), None))
+        check(pit.get_kernel(mt, AuxiliaryG0(M0=M0, G0=G0), AuxiliaryGt(Mt=Mt, Gt=Gt), N, qt)[0], True)
+    for gradient in (False, True):
+        check(get_independent_kernel(M0, G0, Mt, Gt, N, gradient=gradient, parallel=True)[0], False)
+    lit = PC.Case((d, N, T, PC.GAUSS, 0, 0, 0)).literal_objects()
+    assert L.get_kernel(*lit, N)[0](x)[1].all() and P.get_kernel(None, None, None, N)[0](x)[1].all()
+    assert not P.get_independent_parallel_kernel(*lit, N)[0](x)[1].any()
