@@ -184,61 +184,22 @@ ScanPlan plan_scan(const auxssm_ctx* h, int S, int n, int parallel, int waves) {
 AX_DECL_UNIT(f32_d1) AX_DECL_UNIT(f32_d2) AX_DECL_UNIT(f32_d3) AX_DECL_UNIT(f32_d4)
 AX_DECL_UNIT(f64_d1) AX_DECL_UNIT(f64_d2) AX_DECL_UNIT(f64_d3) AX_DECL_UNIT(f64_d4)
 
-const KalmanEntry* kalman_entry(int dtype, int D, int P) {
-    if (dtype == AUXSSM_F32) {
-        switch (D) {
-            case 1: return kalman_unit_f32_d1(P);
-            case 2: return kalman_unit_f32_d2(P);
-            case 3: return kalman_unit_f32_d3(P);
-            case 4: return kalman_unit_f32_d4(P);
-        }
-    } else if (dtype == AUXSSM_F64) {
-        switch (D) {
-            case 1: return kalman_unit_f64_d1(P);
-            case 2: return kalman_unit_f64_d2(P);
-            case 3: return kalman_unit_f64_d3(P);
-            case 4: return kalman_unit_f64_d4(P);
-        }
-    }
-    return nullptr;
-}
-const SampleEntry* sample_entry(int dtype, int D) {
-    if (dtype == AUXSSM_F32) {
-        switch (D) {
-            case 1: return sample_unit_f32_d1();
-            case 2: return sample_unit_f32_d2();
-            case 3: return sample_unit_f32_d3();
-            case 4: return sample_unit_f32_d4();
-        }
-    } else if (dtype == AUXSSM_F64) {
-        switch (D) {
-            case 1: return sample_unit_f64_d1();
-            case 2: return sample_unit_f64_d2();
-            case 3: return sample_unit_f64_d3();
-            case 4: return sample_unit_f64_d4();
-        }
-    }
-    return nullptr;
-}
-
-const SweepLogpdfEntry* sweep_logpdf_entry(int dtype, int D, int PO) {
-    if (dtype == AUXSSM_F32) {
-        switch (D) {
-            case 1: return sweep_logpdf_unit_f32_d1(PO);
-            case 2: return sweep_logpdf_unit_f32_d2(PO);
-            case 3: return sweep_logpdf_unit_f32_d3(PO);
-            case 4: return sweep_logpdf_unit_f32_d4(PO);
-        }
-    } else if (dtype == AUXSSM_F64) {
-        switch (D) {
-            case 1: return sweep_logpdf_unit_f64_d1(PO);
-            case 2: return sweep_logpdf_unit_f64_d2(PO);
-            case 3: return sweep_logpdf_unit_f64_d3(PO);
-            case 4: return sweep_logpdf_unit_f64_d4(PO);
-        }
-    }
-    return nullptr;
-}
+// the (dtype, D) table of the units, once: NAME_unit_<dtype>_d<D>(args...), or null for a size that is not built
+#define AX_UNIT_ENTRY(NAME, ...)                                                                                        \
+    do {                                                                                                                \
+        if (dtype != AUXSSM_F32 && dtype != AUXSSM_F64) return nullptr;                                                 \
+        const bool f32 = dtype == AUXSSM_F32;                                                                           \
+        switch (D) {                                                                                                    \
+            case 1: return f32 ? NAME##_unit_f32_d1(__VA_ARGS__) : NAME##_unit_f64_d1(__VA_ARGS__);                     \
+            case 2: return f32 ? NAME##_unit_f32_d2(__VA_ARGS__) : NAME##_unit_f64_d2(__VA_ARGS__);                     \
+            case 3: return f32 ? NAME##_unit_f32_d3(__VA_ARGS__) : NAME##_unit_f64_d3(__VA_ARGS__);                     \
+            case 4: return f32 ? NAME##_unit_f32_d4(__VA_ARGS__) : NAME##_unit_f64_d4(__VA_ARGS__);                     \
+        }                                                                                                               \
+        return nullptr;                                                                                                 \
+    } while (0)
+const KalmanEntry* kalman_entry(int dtype, int D, int P) { AX_UNIT_ENTRY(kalman, P); }
+const SampleEntry* sample_entry(int dtype, int D) { AX_UNIT_ENTRY(sample); }
+const SweepLogpdfEntry* sweep_logpdf_entry(int dtype, int D, int PO) { AX_UNIT_ENTRY(sweep_logpdf, PO); }
 
 static inline Arr cv(const auxssm_arr& a) { return Arr{a.ptr, (long long)a.sc, (long long)a.st, (long long)a.sb, 1}; }
 
@@ -303,9 +264,56 @@ static void fill_logpdf_args(LogpdfArgs& a, const auxssm_dims* d, const auxssm_l
     a.dx = d->dx; a.dy = d->dy;
 }
 
+// ---- RNG fill -----------------------------------------------------------------------------------------------------
+// one Threefry block -> out[2 i], out[2 i + 1] (both fills)
+template <typename R> __global__ void k_rng_uniform(uint32_t k0, uint32_t k1, uint32_t stream, long long n, R* out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (2 * i >= n) return;
+    R u0, u1;
+    stream_uniform2<R>(k0, k1, stream, (unsigned long long)i, u0, u1);
+    out[2 * i] = u0;
+    if (2 * i + 1 < n) out[2 * i + 1] = u1;
+}
+template <typename R> __global__ void k_rng_normal(uint32_t k0, uint32_t k1, uint32_t stream, long long n, R* out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (2 * i >= n) return;
+    uint32_t x0, x1;
+    stream_counter(stream, (unsigned long long)i, x0, x1);
+    threefry2x32(k0, k1, x0, x1);
+    R z0, z1;
+    bits_to_normal2<R>(x0, x1, z0, z1);
+    out[2 * i] = z0;
+    if (2 * i + 1 < n) out[2 * i + 1] = z1;
+}
+
+// the three noise fills of one Kalman sweep in one launch: the same values as auxssm_rng_normal (keys a, b; stream 0; n each) and
+// auxssm_rng_uniform (key c; stream 0; nu) -- workgroups [0, g1) fill eps_aux, [g1, 2 g1) eps_samp, the rest u_acc
 template <typename R>
 __global__ void k_rng_sweep(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0, uint32_t c1, long long n, long long nu, unsigned g1,
-                            R* eps_aux, R* eps_samp, R* u_acc);  // (defined below)
+                            R* eps_aux, R* eps_samp, R* u_acc) {
+    const unsigned blk = blockIdx.x;
+    if (blk < 2 * g1) {
+        const bool second = blk >= g1;
+        const long long i = (long long)(second ? blk - g1 : blk) * blockDim.x + threadIdx.x;
+        if (2 * i >= n) return;
+        uint32_t x0, x1;
+        stream_counter(0, (unsigned long long)i, x0, x1);
+        threefry2x32(second ? b0 : a0, second ? b1 : a1, x0, x1);
+        R z0, z1;
+        bits_to_normal2<R>(x0, x1, z0, z1);
+        R* out = second ? eps_samp : eps_aux;
+        out[2 * i] = z0;
+        if (2 * i + 1 < n) out[2 * i + 1] = z1;
+    } else {
+        const long long i = (long long)(blk - 2 * g1) * blockDim.x + threadIdx.x;
+        if (2 * i >= nu) return;
+        R u0, u1;
+        stream_uniform2<R>(c0, c1, 0, (unsigned long long)i, u0, u1);
+        u_acc[2 * i] = u0;
+        if (2 * i + 1 < nu) u_acc[2 * i + 1] = u1;
+    }
+}
+
 // the noise fills of a keyed sweep: the first n entries of eps_aux and eps_samp and the nu uniforms, on the handle's stream
 template <typename R> static void launch_rng_sweep(auxssm_ctx* h, const uint32_t* keys, long long n, long long nu, void* eps_aux, void* eps_samp, void* u_acc) {
     const unsigned g1 = (unsigned)(((n + 1) / 2 + 255) / 256), g2 = (unsigned)(((nu + 1) / 2 + 255) / 256);
@@ -536,11 +544,144 @@ template <typename R> __global__ void k_concat_carrier(int T, int D, int P, Arr 
     out[g] = k < D ? (R)0 : at<R>(yobs, 0, t, 0)[k - D];
 }
 
-template <typename R>
-static int sweep_lg_concat(auxssm_ctx* h, int dtype, const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs,
-                           double delta, const double* dptr, const uint32_t* keys, int parallel, int nan_policy, int layout, void* x, const void* eps_aux, const void* eps_samp,
-                           const void* u_acc, int32_t* accepted, void* logs) {
-    const int C = dims->C, T = dims->T, D = dims->dx, PO = dims->dy, P = D + PO;
+// ---- the host side the Kalman sweep drivers share --------------------------------------------------------------------------------------------
+// One sweep call, as the entry points hand it to sweep_lg_concat, sweep_lg_concat_fused, sweep_sv and sweep_lorenz
+struct SweepCall {
+    auxssm_ctx* h;
+    int dtype;
+    const auxssm_dims* dims;
+    const auxssm_lgssm* model;
+    const auxssm_arr* yobs;
+    double delta;          // host step size (a placeholder when dptr is set)
+    const double* dptr;    // device-resident {delta, sqrt(delta / 2)} (delta_block), or null
+    const uint32_t* keys;  // keyed sweep: {aux0, aux1, samp0, samp1, acc0, acc1}; null: the noise arrays hold the draws
+    int parallel, nan_policy, layout;
+    void* x;
+    const void *eps_aux, *eps_samp, *u_acc;
+    int32_t* accepted;
+    void* logs;
+    int order = 0;          // sweep_sv: 1 or 2
+    void* x_alt = nullptr;  // sweep_lg_concat_fused: the second state buffer and the lazy state's selector
+    int32_t* sel = nullptr;
+    int cm() const { return layout == AUXSSM_LAYOUT_CHAIN_MINOR ? 1 : 0; }
+    double shd() const { return sqrt(0.5 * delta); }
+};
+// f(R()) for the sweep's dtype (csmc_host.h::csmc_dispatch is the cSMC drivers' form of this)
+template <typename F> static int by_dtype(int dtype, F&& f) { return dtype == AUXSSM_F32 ? f(0.0f) : f(0.0); }
+
+// which of a model's arrays the chains share (chain stride 0): the dynamics and the initial covariance -- what chain_shared_mode asks for --, those and the
+// initial mean, the real observation model
+static bool dynamics_chain_shared(const auxssm_lgssm* m) { return m->Fs.sc == 0 && m->Qs.sc == 0 && m->bs.sc == 0 && m->P0.sc == 0; }
+static bool prior_chain_shared(const auxssm_lgssm* m) { return dynamics_chain_shared(m) && m->m0.sc == 0; }
+static bool obs_model_chain_shared(const auxssm_lgssm* m) { return m->Hs.sc == 0 && m->Rs.sc == 0 && m->cs.sc == 0; }
+
+// the view of a per-chain (C, T, rec) buffer in the sweep's layout: dense, or chain-minor (T, rec, C)
+struct SweepViews {
+    int cm;
+    KDims kd;
+    Arr operator()(const void* p, long long rec) const { return cm ? cm_arr(p, kd, rec) : dense_arr(p, kd, rec); }
+};
+
+// bytes of the side slab of a model stage (ctx.h::SideStage) of sweep_lg_concat and sweep_sv: per time step the `own` reals the driver itself takes there
+// (its observation model), the shared covariances, what run_filter_shared takes (mask, gain rows, two sets of scan elements) and the sampler's / log-density's
+// tables; + chunk products
+static size_t side_stage_bytes(size_t sR, int T, size_t D, size_t P, size_t PO, size_t own) {
+    const size_t gain = D * D + D + 2 * D * P + P + P * (P + 1) / 2 + 4, felem = 3 * D * D + 2 * D + 8;
+    return (size_t)(T + 64) * sR * (own + D * D + P + D + gain + 2 * felem + 8 * D * D + 8 * D + 2 * PO * PO + 4 * PO + 32) + (4u << 20);
+}
+
+// The concatenated observation model of the LG_CONCAT and Lorenz sweeps: H = [I; Hobs], R = blkdiag(delta/2 I, Robs), c = [0; cobs] into Hc / Rc / cc (the model
+// stage: on the side stream when a stage is open), then -- obs set -- rows [0, Tc) of u = x + sqrt(delta/2) eps and of the observations [u ; yobs].  Returns the
+// model and the sizes the filter sees.  tinv: the real observation model is time-invariant (time stride 0 on Hs, Rs, cs: the broadcast views of a constant
+// model), so the concatenated one is ONE record with time stride 0 instead of T of them (C2 at one chain: 54 MB written and read back per sweep, 27 of its
+// 240 us)
+struct ConcatObs {
+    int Tc;
+    Arr x, eps, u, ysc;
+};
+struct ConcatModel {
+    auxssm_lgssm g;
+    auxssm_dims d;
+};
+static bool obs_model_time_invariant(const auxssm_lgssm* m) { return m->Hs.st == 0 && m->Rs.st == 0 && m->cs.st == 0; }
+template <typename R> static ConcatModel concat_model(const SweepCall& c, bool tinv, R* Hc, R* Rc, R* cc, const int* memo, const ConcatObs* obs) {
+    auxssm_ctx* h = c.h;
+    const int C = c.dims->C, D = c.dims->dx, PO = c.dims->dy, P = D + PO, Tm = tinv ? 1 : c.dims->T;
+    {
+        ProfScope ps(h, AUXSSM_K_FACTORY);
+        const long long n1 = (long long)Tm * (P * D + P * P + P);
+        {
+            SideScope sc(h);  // (model stage)
+            hipLaunchKernelGGL((k_concat_model<R>), dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, h->stream, Tm, D, PO, cv(c.model->Hs), cv(c.model->Rs),
+                               cv(c.model->cs), (R)(0.5 * c.delta), c.dptr, Hc, Rc, cc, memo);
+        }
+        if (obs) {
+            const long long n2 = (long long)C * obs->Tc * P;
+            hipLaunchKernelGGL((k_concat_obs<R>), dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, h->stream, C, obs->Tc, D, PO, obs->x, obs->eps, (R)c.shd(), c.dptr,
+                               cv(*c.yobs), obs->u, obs->ysc, c.cm());
+        }
+    }
+    ConcatModel m{*c.model, *c.dims};
+    m.g.Hs = auxssm_arr{Hc, 0, tinv ? 0 : (int64_t)P * D, 0};
+    m.g.Rs = auxssm_arr{Rc, 0, tinv ? 0 : (int64_t)P * P, 0};
+    m.g.cs = auxssm_arr{cc, 0, tinv ? 0 : (int64_t)P, 0};
+    m.d.dy = P;
+    m.d.B = 1;
+    return m;
+}
+
+// FilterArgs of a sweep's filter: the model g at the sizes d, observations / filtered means / covariances through the sweep's own views
+static void sweep_filter_args(FilterArgs& fa, const auxssm_dims& d, const auxssm_lgssm& g, const Arr& ys, const Arr& ms, const Arr& Ps, int cm) {
+    const auxssm_arr none{nullptr, 0, 0, 0};
+    fill_filter_args(fa, &d, &g, &none, nullptr, nullptr);
+    fa.ys = ys;
+    fa.ms = ms;
+    fa.Ps = Ps;
+    fa.lay.cm = cm;
+}
+// FilterArgs' "auxiliary observations on the fly" block: the filter forms u = x + sqrt(delta/2) eps (written to u) and the observation from it step by step, so
+// it -- and only then the filter -- reads the step size: host value and device block go in together.  aux_on: the concatenated [u ; yobs] form (0: the SV
+// sweep's, which says sv_order instead)
+static void set_aux_fly(FilterArgs& fa, const SweepCall& c, int aux_on, const Arr& x, const Arr& eps, const Arr& u) {
+    fa.aux_on = aux_on;
+    fa.aux_x = x;
+    fa.aux_eps = eps;
+    fa.aux_u = u;
+    fa.aux_yobs = cv(*c.yobs);
+    fa.aux_shd = c.shd();
+    fa.dptr = c.dptr;
+}
+static void fill_sample_args(SampleArgs& sa, const KDims& kd, int D, const Arr& Fs, const Arr& Qs, const Arr& bs, const Arr& ms, const Arr& Ps, const Arr& eps,
+                             const Arr& xs, int cm) {
+    sa.d = kd;
+    sa.dx = D;
+    sa.Fs = Fs; sa.Qs = Qs; sa.bs = bs;
+    sa.ms = ms; sa.Ps = Ps; sa.eps = eps; sa.xs = xs; sa.elem = nullptr;
+    sa.lay = ScanLayout{1, 1, 1, 1, cm, kd.C};
+}
+// SweepLogpdfArgs of a sweep: dynamics and observation model of g, the data ys, state / proposal / auxiliary variable; u_fly: rows t >= 1 of u were never
+// materialised and are re-formed from eps_aux
+static void fill_sweep_logpdf_args(SweepLogpdfArgs& la, const SweepCall& c, const KDims& kd, const auxssm_lgssm& g, const Arr& ys, const Arr& x, const Arr& xp,
+                                   const Arr& u, int u_fly, const Arr& eps_aux) {
+    la.d = kd;
+    la.dx = c.dims->dx; la.po = c.dims->dy;
+    la.m0 = cv(g.m0); la.P0 = cv(g.P0); la.Fs = cv(g.Fs); la.Qs = cv(g.Qs); la.bs = cv(g.bs);
+    la.Hs = cv(g.Hs); la.Rs = cv(g.Rs); la.cs = cv(g.cs); la.ys = ys;
+    la.x = x; la.xp = xp; la.u = u; la.delta = c.delta; la.nan_policy = c.nan_policy;
+    la.u_fly = u_fly; la.eps_aux = eps_aux; la.shd = c.shd(); la.dptr = c.dptr;
+}
+// _get_alpha + bernoulli from the log-density pass's totals, sums [5][C] = jp_prop, jp_rev, lt_prop, lt_rev, corr, and the two filters' log-likelihoods
+template <typename R> static void launch_accept(const SweepCall& c, const Acc* sums, const R* ell_prop, const R* ell_rev) {
+    const int C = c.dims->C;
+    hipLaunchKernelGGL((k_accept<R>), dim3((C + 127) / 128), dim3(128), 0, c.h->stream, C, sums, sums + C, ell_prop, ell_rev, sums + 2 * C, sums + 3 * C, sums + 4 * C,
+                       (const R*)c.u_acc, c.accepted, (R*)c.logs);
+}
+
+template <typename R> static int sweep_lg_concat(const SweepCall& c) {
+    auxssm_ctx* h = c.h;
+    const auxssm_lgssm* model = c.model;
+    const int dtype = c.dtype, parallel = c.parallel;
+    const int C = c.dims->C, T = c.dims->T, D = c.dims->dx, PO = c.dims->dy, P = D + PO;
     // one path for the whole sweep: the register kernels when every piece is instantiated, else the wide-state path
     const bool wide = is_wide(D, P) || PO > 4;
     const KalmanEntry* ke = wide ? nullptr : need_kalman(dtype, D, P);
@@ -552,7 +693,7 @@ static int sweep_lg_concat(auxssm_ctx* h, int dtype, const auxssm_dims* dims, co
             set_error("%s", why.c_str());
             return AUXSSM_ERR_UNSUPPORTED;
         }
-        if (layout != AUXSSM_LAYOUT_DENSE) {
+        if (c.layout != AUXSSM_LAYOUT_DENSE) {
             set_error("(dx=%d, dy=%d) runs the wide-state path, which takes the dense (C, T, dx) layout only", D, P);
             return AUXSSM_ERR_UNSUPPORTED;
         }
@@ -561,58 +702,48 @@ static int sweep_lg_concat(auxssm_ctx* h, int dtype, const auxssm_dims* dims, co
     if (!ke || !se || !sl) return AUXSSM_ERR_UNSUPPORTED;
     const KDims kd{C, T, 1};
     // layout 1: x and the noise are chain-minor (T, dx, C) and so is every internal per-chain buffer: lanes <-> chains
-    const int cm = layout == AUXSSM_LAYOUT_CHAIN_MINOR ? 1 : 0;
+    const int cm = c.cm();
+    const SweepViews view{cm, kd};
     const size_t sR = sizeof(R);
     const size_t CT = (size_t)C * T;
-    size_t need = 0;
-    auto add = [&](size_t b) { need += b + 256; };
-    add(CT * P * sR);                                  // ys_c
-    add((size_t)T * (P * D + P * P + P) * sR);         // Hc, Rc, cc (three takes)
-    add(512);
-    add(CT * D * sR);                                  // u
-    add(CT * D * sR);                                  // ms
-    add(CT * D * D * sR);                              // Ps
-    add(CT * D * sR);                                  // x_prop
-    add((size_t)C * sR + (size_t)5 * C * sizeof(Acc) + 2048);  // ell, the five totals
-    if (wide) add((size_t)T * P * sR);                 // the observation-pattern carrier of the chain-shared wide filter
-    add(wide ? wide_filter_ws(h, dtype, kd, parallel, D, P) : ke->filter_ws(h, kd, parallel));
-    add(wide ? wide_sample_ws(h, dtype, kd, parallel, D) : se->sample_ws(h, kd, parallel));
-    add(wide ? wide_logpdf_ws(dtype, kd) : sl->ws(h, kd));
-    int rc = ws_reserve(h, need);
-    if (rc) return rc;
-    R* ysc = (R*)ws_take(h, CT * P * sR);
-    R* Hc = (R*)ws_take(h, (size_t)T * P * D * sR);
-    R* Rc = (R*)ws_take(h, (size_t)T * P * P * sR);
-    R* cc = (R*)ws_take(h, (size_t)T * P * sR);
-    R* u = (R*)ws_take(h, CT * D * sR);
-    R* ms = (R*)ws_take(h, CT * D * sR);
-    R* Ps = (R*)ws_take(h, CT * D * D * sR);
-    R* xp = (R*)ws_take(h, CT * D * sR);
-    R* ell = (R*)ws_take(h, C * sR);
-    Acc* sums = (Acc*)ws_take(h, (size_t)5 * C * sizeof(Acc));
-    if (!ysc || !Hc || !Rc || !cc || !u || !ms || !Ps || !xp || !ell || !sums) return AUXSSM_ERR_NOMEM;
-    const size_t mark = h->ws_off;
     // chain-shared parameters: the filtered covariances do not depend on the chain and are stored once, (T, D, D) dense with chain stride 0
-    const bool shared_mode = !wide && chain_shared_mode(h, cm, C, T, model->Fs.sc == 0 && model->Qs.sc == 0 && model->bs.sc == 0 && model->P0.sc == 0);
+    const bool shared_mode = !wide && chain_shared_mode(h, cm, C, T, dynamics_chain_shared(model));
     const bool aux_fly = cm && T > 1 && !wide;  // u and the concatenated observations of t >= 1 are formed inside the filter
-    // a time-invariant real observation model (time stride 0 on Hs, Rs, cs: the broadcast views of a constant model) gives a time-invariant concatenated one: ONE
-    // record with time stride 0 instead of T of them (C2 at one chain: 54 MB written and read back per sweep, 27 of its 240 us)
-    const bool tinv = model->Hs.st == 0 && model->Rs.st == 0 && model->cs.st == 0;
-    const int Tm = tinv ? 1 : T;
+    const bool tinv = obs_model_time_invariant(model);
+    // general chain-minor sweep: the filtered covariances are an internal buffer the sampler reads twice -- kept symmetric-packed (10 instead of 16
+    // reals at d = 4)
+    const bool ps_pack = cm && !shared_mode && !wide;
+    // wide states, several chains on one model: ONE copy of the filtered covariances (chain stride 0) -- the chain-shared wide filter then skips its broadcast to
+    // the chains' slots and the sampler builds its gain / factor tables once (wide.hip::run_sample_shared); the pattern carrier below replaces the filter's read-back
+    const bool wide_shared = wide && C >= 2 && h->share_model && dynamics_chain_shared(model) && obs_model_chain_shared(model) && c.yobs->sc == 0;
+    R *ysc, *Hc, *Rc, *cc, *u, *ms, *Ps, *xp, *ell, *carrier = nullptr;
+    Acc* sums;
+    WsPlan ws;
+    ws.add(ysc, CT * P * sR);
+    ws.add(Hc, (size_t)T * P * D * sR);
+    ws.add(Rc, (size_t)T * P * P * sR);
+    ws.add(cc, (size_t)T * P * sR);
+    ws.add(u, CT * D * sR);
+    ws.add(ms, CT * D * sR);
+    ws.add(Ps, CT * D * D * sR);
+    ws.add(xp, CT * D * sR);
+    ws.add(ell, C * sR);
+    ws.add(sums, (size_t)5 * C * sizeof(Acc));  // the five totals
+    if (wide_shared) ws.add(carrier, (size_t)T * P * sR);  // the observation-pattern carrier of the chain-shared wide filter
+    ws.after(wide ? wide_filter_ws(h, dtype, kd, parallel, D, P) : ke->filter_ws(h, kd, parallel));
+    ws.after(wide ? wide_sample_ws(h, dtype, kd, parallel, D) : se->sample_ws(h, kd, parallel));
+    ws.after(wide ? wide_logpdf_ws(dtype, kd) : sl->ws(h, kd));
+    int rc = ws.reserve(h);
+    if (rc) return rc;
+    const size_t mark = h->ws_off;
     // Chain-shared sweep with a host step size: the MODEL STAGE (concatenated observation model here, matrix filter + gain table in
     // run_filter_shared) reads neither a chain nor anything the previous sweep wrote, so it goes to the side stream with its own double-buffered
     // slab (ctx.h::SideStage) and overlaps the chain passes of the sweep before; its products -- Hc, Rc, cc, the shared covariances, the gain
     // rows -- live in that slab.  AUXSSM_OPT_OVERLAP_MODEL_STAGE = 0 (environment AUXSSM_OVERLAP_TAB=0): everything on the one stream, as before.
-    bool overlap = h->overlap_model_stage != 0 && shared_mode && aux_fly && parallel && !dptr;
-    struct SweepEnd {  // whatever way the sweep returns: everything it enqueued on `stream` precedes the mark the next stage of this parity waits for
-        auxssm_ctx* h;
-        ~SweepEnd() { side_sweep_end(h); }
-    } sweep_end{h};
+    bool overlap = h->overlap_model_stage != 0 && shared_mode && aux_fly && parallel && !c.dptr;
+    SweepEnd sweep_end{h};
     if (overlap) {
-        const size_t gain = (size_t)D * D + D + 2 * (size_t)D * P + P + (size_t)P * (P + 1) / 2 + 4, felem = 3 * (size_t)D * D + 2 * D + 8;
-        const size_t need_side = (size_t)(T + 64) * sR * ((size_t)P * D + (size_t)P * P + P + (size_t)D * D + P + D + gain + 2 * felem +
-                                                          8 * (size_t)D * D + 8 * D + 2 * (size_t)PO * PO + 4 * PO + 32) + (4u << 20);  // + sampler / log-density tables, chunk products
-        if ((rc = side_open(h, need_side))) return rc;
+        if ((rc = side_open(h, side_stage_bytes(sR, T, D, P, PO, (size_t)P * D + (size_t)P * P + P)))) return rc;
         overlap = h->side.open;  // (false when the device gave no second stream)
     }
     if (overlap) {
@@ -623,94 +754,46 @@ static int sweep_lg_concat(auxssm_ctx* h, int dtype, const auxssm_dims* dims, co
         Ps = (R*)ws_take(h, (size_t)T * D * D * sR);
         if (!Hc || !Rc || !cc || !Ps) return AUXSSM_ERR_NOMEM;
     }
-    const Arr yscA = cm ? cm_arr(ysc, kd, P) : dense_arr(ysc, kd, P);
-    const Arr uA = cm ? cm_arr(u, kd, D) : dense_arr(u, kd, D);
-    const Arr msA = cm ? cm_arr(ms, kd, D) : dense_arr(ms, kd, D);
-    // general chain-minor sweep: the filtered covariances are an internal buffer the sampler reads twice -- kept symmetric-packed (10 instead of 16
-    // reals at d = 4)
-    const bool ps_pack = cm && !shared_mode && !wide;
-    // wide states, several chains on one model: ONE copy of the filtered covariances (chain stride 0) -- the chain-shared wide filter then skips its broadcast to
-    // the chains' slots and the sampler builds its gain / factor tables once (wide.hip::run_sample_shared); the pattern carrier below replaces the filter's read-back
-    const bool wide_shared = wide && C >= 2 && h->share_model && model->Fs.sc == 0 && model->Qs.sc == 0 && model->bs.sc == 0 && model->P0.sc == 0 &&
-                             model->Hs.sc == 0 && model->Rs.sc == 0 && model->cs.sc == 0 && yobs->sc == 0;
-    const Arr PsA = (shared_mode || wide_shared) ? Arr{Ps, 0, (long long)D * D, 0, 1}
-                    : cm                         ? cm_arr(Ps, kd, ps_pack ? (long long)symsize(D) : (long long)D * D)
-                                                 : dense_arr(Ps, kd, (long long)D * D);
-    const Arr xpA = cm ? cm_arr(xp, kd, D) : dense_arr(xp, kd, D);
-    const Arr xA = cm ? cm_arr(x, kd, D) : dense_arr(x, kd, D);
-    const Arr epsauxA = cm ? cm_arr(eps_aux, kd, D) : dense_arr(eps_aux, kd, D);
-    const Arr epsA = cm ? cm_arr(eps_samp, kd, D) : dense_arr(eps_samp, kd, D);
+    const Arr yscA = view(ysc, P), uA = view(u, D), msA = view(ms, D), xpA = view(xp, D), xA = view(c.x, D);
+    const Arr PsA = (shared_mode || wide_shared) ? Arr{Ps, 0, (long long)D * D, 0, 1} : view(Ps, ps_pack ? (long long)symsize(D) : (long long)D * D);
+    const Arr epsauxA = view(c.eps_aux, D), epsA = view(c.eps_samp, D);
 
-    // observations_factory / dynamics_factory of the LG_CONCAT device model.  With chain-shared parameters in the chain-minor layout
-    // the filter builds u and the concatenated observation on the fly for t >= 1 (FilterArgs::aux_*): only row t = 0 is materialised.
+    // observations_factory / dynamics_factory of the LG_CONCAT device model.
     // In the chain-minor layout the filter builds u and the concatenated observation on the fly for t >= 1 (FilterArgs::aux_*), in
-    // both of its modes (chain-shared parameters: gain-form recursion; otherwise: elements built inside the scan passes).
+    // both of its modes (chain-shared parameters: gain-form recursion; otherwise: elements built inside the scan passes): only row t = 0 is materialised.
     // Keyed sweep (auxssm_kalman_sweep_keyed): the noise is a function of the keys.  Where the chain-shared affine scans run, their reduce
     // passes -- the first readers of eps_aux (t >= 1) and eps_samp -- GENERATE it and store it for the later readers (the fill kernel then
     // only draws row t = 0 and the acceptance uniforms); everywhere else the fill kernel draws all of it first.  Same values either way.
+    const uint32_t* keys = c.keys;
     bool gen = false;
     if (keys) {
         gen = aux_fly && shared_mode && parallel && (C % 2 == 0) && plan_aff(h, C, T - 1, 1).nchunk > 1 && plan_aff(h, C, T, 1).nchunk > 1;
-        launch_rng_sweep<R>(h, keys, gen ? (long long)D * C : (long long)C * T * D, C, const_cast<void*>(eps_aux), const_cast<void*>(eps_samp), const_cast<void*>(u_acc));
+        launch_rng_sweep<R>(h, keys, gen ? (long long)D * C : (long long)C * T * D, C, const_cast<void*>(c.eps_aux), const_cast<void*>(c.eps_samp),
+                            const_cast<void*>(c.u_acc));
     }
-    {
-        ProfScope ps(h, AUXSSM_K_FACTORY);
-        const long long n1 = (long long)Tm * (P * D + P * P + P);
-        {
-            SideScope sc(h);  // (model stage)
-            hipLaunchKernelGGL((k_concat_model<R>), dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, h->stream, Tm, D, PO,
-                               cv(model->Hs), cv(model->Rs), cv(model->cs), (R)(0.5 * delta), dptr, Hc, Rc, cc);
-        }
-        const int Tc = aux_fly ? 1 : T;
-        const long long n2 = (long long)C * Tc * P;
-        hipLaunchKernelGGL((k_concat_obs<R>), dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, h->stream, C, Tc, D, PO,
-                           xA, epsauxA, (R)sqrt(0.5 * delta), dptr, cv(*yobs), uA, yscA, cm);
-    }
-    auxssm_lgssm gc = *model;
-    gc.Hs = auxssm_arr{Hc, 0, tinv ? 0 : (int64_t)P * D, 0};
-    gc.Rs = auxssm_arr{Rc, 0, tinv ? 0 : (int64_t)P * P, 0};
-    gc.cs = auxssm_arr{cc, 0, tinv ? 0 : (int64_t)P, 0};
-    const auxssm_arr ysc_dummy{ysc, (int64_t)T * P, (int64_t)P, 0};
-    auxssm_dims dc = *dims;
-    dc.dy = P;
-    dc.B = 1;
+    const ConcatObs obs{aux_fly ? 1 : T, xA, epsauxA, uA, yscA};
+    const ConcatModel cmod = concat_model<R>(c, tinv, Hc, Rc, cc, nullptr, &obs);
 
     // proposal LGSSM: filter + pathwise sample (generic.py:80-86).  The factories of this model do not depend on the
     // linearisation point, so the reverse LGSSM (generic.py:67) is the same one and its filter pass is not repeated.
     FilterArgs fa;
-    fill_filter_args(fa, &dc, &gc, &ysc_dummy, ms, Ps);
-    fa.ys = yscA;
-    fa.ms = msA;
-    fa.Ps = PsA;
-    fa.lay.cm = cm;
+    sweep_filter_args(fa, cmod.d, cmod.g, yscA, msA, PsA, cm);
     fa.pblk = D;  // R = blkdiag(delta/2 I_d, Robs) by construction
     fa.ps_packed = ps_pack ? 1 : 0;
     if (aux_fly) {
-        fa.aux_on = 1;
-        fa.aux_x = xA;
-        fa.aux_eps = epsauxA;
-        fa.aux_u = uA;
-        fa.aux_yobs = cv(*yobs);
-        fa.aux_shd = sqrt(0.5 * delta);
-        fa.dptr = dptr;
+        set_aux_fly(fa, c, 1, xA, epsauxA, uA);
         if (gen) fa.aux_gen = 1, fa.gen_k0 = keys[0], fa.gen_k1 = keys[1];
     }
     if (wide_shared) {
-        R* carrier = (R*)ws_take(h, (size_t)T * P * sR);
-        if (!carrier) return AUXSSM_ERR_NOMEM;
         const long long tot = (long long)T * P;
-        hipLaunchKernelGGL((k_concat_carrier<R>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, T, D, P, cv(*yobs), carrier);
+        hipLaunchKernelGGL((k_concat_carrier<R>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, T, D, P, cv(*c.yobs), carrier);
         fa.mask_ys = Arr{carrier, 0, (long long)P, 0, 1};
     }
     rc = ke->filter(h, fa, parallel, ell);
     if (rc) return rc;
     h->ws_off = mark;
     SampleArgs sa;
-    sa.d = kd;
-    sa.dx = D;
-    sa.Fs = cv(model->Fs); sa.Qs = cv(model->Qs); sa.bs = cv(model->bs);
-    sa.ms = msA; sa.Ps = PsA; sa.eps = epsA; sa.xs = xpA; sa.elem = nullptr;
-    sa.lay = ScanLayout{1, 1, 1, 1, cm, C};
+    fill_sample_args(sa, kd, D, cv(model->Fs), cv(model->Qs), cv(model->bs), msA, PsA, epsA, xpA, cm);
     // the filtered covariances of this model do not depend on the chain when its parameters do not
     sa.ps_shared = shared_mode ? 1 : 0;
     sa.ps_packed = ps_pack ? 1 : 0;
@@ -720,22 +803,13 @@ static int sweep_lg_concat(auxssm_ctx* h, int dtype, const auxssm_dims* dims, co
     h->ws_off = mark;
 
     // all proposal / target log-densities and the MH correction in one pass (generic.py:88-89, :103-105)
-    {
-        SweepLogpdfArgs la;
-        la.d = kd;
-        la.dx = D; la.po = PO;
-        la.m0 = cv(model->m0); la.P0 = cv(model->P0); la.Fs = cv(model->Fs); la.Qs = cv(model->Qs); la.bs = cv(model->bs);
-        la.Hs = cv(model->Hs); la.Rs = cv(model->Rs); la.cs = cv(model->cs); la.ys = cv(*yobs);
-        la.x = xA; la.xp = xpA; la.u = uA; la.delta = delta; la.nan_policy = nan_policy;
-        la.u_fly = aux_fly ? 1 : 0; la.eps_aux = epsauxA; la.shd = sqrt(0.5 * delta); la.dptr = dptr;
-        rc = sl->run(h, la, sums);
-        if (rc) return rc;
-        h->ws_off = mark;
-    }
-    const Acc* jp_prop = sums; const Acc* jp_rev = sums + C; const Acc* lt_prop = sums + 2 * C; const Acc* lt_rev = sums + 3 * C; const Acc* corr = sums + 4 * C;
-    hipLaunchKernelGGL((k_accept<R>), dim3((C + 127) / 128), dim3(128), 0, h->stream, C, jp_prop, jp_rev, (const R*)ell, (const R*)ell, lt_prop, lt_rev,
-                       corr, (const R*)u_acc, accepted, (R*)logs);
-    if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)accepted, xpA, xA, cm))) return rc;
+    SweepLogpdfArgs la;
+    fill_sweep_logpdf_args(la, c, kd, *model, cv(*c.yobs), xA, xpA, uA, aux_fly ? 1 : 0, epsauxA);
+    rc = sl->run(h, la, sums);
+    if (rc) return rc;
+    h->ws_off = mark;
+    launch_accept<R>(c, sums, ell, ell);
+    if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)c.accepted, xpA, xA, cm))) return rc;
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;
 }
@@ -790,54 +864,47 @@ static const char* fused_refusal(const auxssm_ctx* h, const auxssm_dims* dims, c
     if (D > MAX_D || PO < 1 || PO > 4) return "the fused sweep is instantiated for dx <= 4, 1 <= dy <= 4";
     if (!parallel) return "the fused sweep is the parallel-in-time one";
     if (!h->share_model) return "AUXSSM_OPT_SHARE_MODEL is off";
-    if (!(model->Fs.sc == 0 && model->Qs.sc == 0 && model->bs.sc == 0 && model->P0.sc == 0 && model->m0.sc == 0))
-        return "the fused sweep needs chain-shared model parameters (chain stride 0)";
+    if (!prior_chain_shared(model)) return "the fused sweep needs chain-shared model parameters (chain stride 0)";
     if (C < 2 || (C % 2) != 0) return "the fused sweep pairs chains for its in-kernel draws: the chain count must be even";
     if (T < 64) return "the fused sweep needs T >= 64";
     return nullptr;
 }
-template <typename R>
-static int sweep_lg_concat_fused(auxssm_ctx* h, int dtype, const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs, double delta, const double* dptr,
-                                 const uint32_t* keys, int nan_policy, void* x, void* x_alt, int32_t* sel, void* u_acc, int32_t* accepted, void* logs) {
-    const int C = dims->C, T = dims->T, D = dims->dx, PO = dims->dy, P = D + PO;
-    const SweepLogpdfEntry* sl = sweep_logpdf_entry(dtype, D, PO);
+template <typename R> static int sweep_lg_concat_fused(const SweepCall& c) {
+    auxssm_ctx* h = c.h;
+    const auxssm_lgssm* model = c.model;
+    const auxssm_arr* yobs = c.yobs;
+    const double delta = c.delta;
+    void *x = c.x, *x_alt = c.x_alt;
+    const int C = c.dims->C, T = c.dims->T, D = c.dims->dx, PO = c.dims->dy, P = D + PO;
+    const SweepLogpdfEntry* sl = sweep_logpdf_entry(c.dtype, D, PO);
     if (!sl || !sl->fused) {
         set_error("(dx=%d, dy=%d) has no fused sweep in this build", D, PO);
         return AUXSSM_ERR_UNSUPPORTED;
     }
     const KDims kd{C, T, 1};
     const size_t sR = sizeof(R), CT = (size_t)C * T;
-    size_t need = 0;
-    auto add = [&](size_t b) { need += b + 256; };
-    add(CT * D * sR);                                   // u
-    add(CT * D * sR);                                   // inc
-    add((size_t)T * (P * D + P * P + P + D * D) * sR);  // Hc, Rc, cc, Ps (four takes; in the side slab when the stage overlaps)
-    add(1024);
-    add((size_t)C * (P + 3 * D) * sR + 1024);           // ysc0, m0p, eps0a, eps0s
-    add(sl->fused_ws(h, kd));
-    int rc = ws_reserve(h, need);
+    const size_t stage[4] = {(size_t)T * P * D * sR, (size_t)T * P * P * sR, (size_t)T * P * sR, (size_t)T * D * D * sR};  // Hc, Rc, cc, Ps
+    R *u, *inc, *ysc0, *m0p, *eps0a, *eps0s;
+    WsPlan ws;
+    ws.add(u, CT * D * sR);
+    ws.add(inc, CT * D * sR);
+    ws.add(ysc0, (size_t)C * P * sR);
+    ws.add(m0p, (size_t)C * D * sR);
+    ws.add(eps0a, (size_t)C * D * sR);
+    ws.add(eps0s, (size_t)C * D * sR);
+    for (size_t b : stage) ws.after(b);  // (taken below: in the side slab when the stage overlaps, else here)
+    ws.after(sl->fused_ws(h, kd));
+    int rc = ws.reserve(h);
     if (rc) return rc;
-    R* u = (R*)ws_take(h, CT * D * sR);
-    R* inc = (R*)ws_take(h, CT * D * sR);
-    R* ysc0 = (R*)ws_take(h, (size_t)C * P * sR);
-    R* m0p = (R*)ws_take(h, (size_t)C * D * sR);
-    R* eps0a = (R*)ws_take(h, (size_t)C * D * sR);
-    R* eps0s = (R*)ws_take(h, (size_t)C * D * sR);
-    if (!u || !inc || !ysc0 || !m0p || !eps0a || !eps0s) return AUXSSM_ERR_NOMEM;
-    bool overlap = h->overlap_model_stage != 0 && !dptr;
-    struct SweepEnd {
-        auxssm_ctx* h;
-        ~SweepEnd() { side_sweep_end(h); }
-    } sweep_end{h};
+    bool overlap = h->overlap_model_stage != 0 && !c.dptr;
+    SweepEnd sweep_end{h};
     if (overlap) {
         const size_t need_side = sl->fused_ws(h, kd) + (size_t)(T + 64) * sR * ((size_t)P * D + (size_t)P * P + P + (size_t)D * D) + (4u << 20) +
                                  (size_t)(T + 2) * sR * (3 * (size_t)D * D + 2 * D + (size_t)PO * D + (size_t)PO * PO + 2 * PO);  // (+ the memo's snapshot of the inputs)
         if ((rc = side_open(h, need_side))) return rc;
         overlap = h->side.open;
     }
-    R *Hc, *Rc, *cc, *Ps;
-    const bool tinv = model->Hs.st == 0 && model->Rs.st == 0 && model->cs.st == 0;  // time-invariant observation model: one concatenated record (sweep_lg_concat)
-    const int Tm = tinv ? 1 : T;
+    const bool tinv = obs_model_time_invariant(model);
     const int* memo = nullptr;
     struct MemoGuard {  // a sweep that fails after claiming its slab's tables leaves nobody's tables behind
         auxssm_ctx* h;
@@ -871,7 +938,7 @@ static int sweep_lg_concat_fused(auxssm_ctx* h, int dtype, const auxssm_dims* di
             // host key: everything the tables depend on besides the arrays' contents
             std::vector<unsigned char> key;
             auto put = [&](const void* v, size_t nb) { key.insert(key.end(), (const unsigned char*)v, (const unsigned char*)v + nb); };
-            const int hdr[8] = {(int)sR, C, T, D, PO, nan_policy, 0, 0};  // (the chunk length is a function of C and T)
+            const int hdr[8] = {(int)sR, C, T, D, PO, c.nan_policy, 0, 0};  // (the chunk length is a function of C and T)
             put(hdr, sizeof(hdr));
             put(&delta, sizeof(delta));
             for (int q = 0; q < 9; ++q) put(srcs[q], sizeof(auxssm_arr));
@@ -890,70 +957,44 @@ static int sweep_lg_concat_fused(auxssm_ctx* h, int dtype, const auxssm_dims* di
             memo = rebuild;
         }
     }
+    R *Hc, *Rc, *cc, *Ps;
+    ConcatModel cmod;
     {
         SideScope sc(h);  // (model stage: the side slab when a stage is open, else the main one)
-        Hc = (R*)ws_take(h, (size_t)T * P * D * sR);
-        Rc = (R*)ws_take(h, (size_t)T * P * P * sR);
-        cc = (R*)ws_take(h, (size_t)T * P * sR);
-        Ps = (R*)ws_take(h, (size_t)T * D * D * sR);
+        Hc = (R*)ws_take(h, stage[0]);
+        Rc = (R*)ws_take(h, stage[1]);
+        cc = (R*)ws_take(h, stage[2]);
+        Ps = (R*)ws_take(h, stage[3]);
         if (!Hc || !Rc || !cc || !Ps) return AUXSSM_ERR_NOMEM;
-        ProfScope ps(h, AUXSSM_K_FACTORY);
-        const long long n1 = (long long)Tm * (P * D + P * P + P);
-        hipLaunchKernelGGL((k_concat_model<R>), dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, h->stream, Tm, D, PO, cv(model->Hs), cv(model->Rs), cv(model->cs),
-                           (R)(0.5 * delta), dptr, Hc, Rc, cc, memo);
+        cmod = concat_model<R>(c, tinv, Hc, Rc, cc, memo, nullptr);
     }
     // row 0 of the two normal draws and the acceptance uniforms (the rest is drawn inside passes A and C), then u_0 and [u_0 ; yobs_0]
-    launch_rng_sweep<R>(h, keys, (long long)D * C, C, eps0a, eps0s, u_acc);
-    hipLaunchKernelGGL((k_fs_concat0<R>), dim3((unsigned)((C * P + 255) / 256)), dim3(256), 0, h->stream, C, D, PO, (const R*)x, (const R*)x_alt, (const int32_t*)sel,
-                       (const R*)eps0a, (R)sqrt(0.5 * delta), dptr, cv(*yobs), u, ysc0);
+    launch_rng_sweep<R>(h, c.keys, (long long)D * C, C, eps0a, eps0s, const_cast<void*>(c.u_acc));
+    hipLaunchKernelGGL((k_fs_concat0<R>), dim3((unsigned)((C * P + 255) / 256)), dim3(256), 0, h->stream, C, D, PO, (const R*)x, (const R*)x_alt, (const int32_t*)c.sel,
+                       (const R*)eps0a, (R)c.shd(), c.dptr, cv(*yobs), u, ysc0);
     FusedHost f{};
-    auxssm_lgssm gc = *model;
-    gc.Hs = auxssm_arr{Hc, 0, tinv ? 0 : (int64_t)P * D, 0};
-    gc.Rs = auxssm_arr{Rc, 0, tinv ? 0 : (int64_t)P * P, 0};
-    gc.cs = auxssm_arr{cc, 0, tinv ? 0 : (int64_t)P, 0};
-    const auxssm_arr ysc_dummy{ysc0, (int64_t)P, (int64_t)P, 0};
-    auxssm_dims dc = *dims;
-    dc.dy = P;
-    dc.B = 1;
-    fill_filter_args(f.fa, &dc, &gc, &ysc_dummy, m0p, Ps);
     const KDims k1{C, 1, 1};
-    f.fa.ys = cm_arr(ysc0, k1, P);
-    f.fa.ms = cm_arr(m0p, k1, D);
-    f.fa.Ps = Arr{Ps, 0, (long long)D * D, 0, 1};
-    f.fa.lay.cm = 1;
+    const Arr none{};
+    sweep_filter_args(f.fa, cmod.d, cmod.g, cm_arr(ysc0, k1, P), cm_arr(m0p, k1, D), Arr{Ps, 0, (long long)D * D, 0, 1}, 1);
     f.fa.pblk = D;
-    f.fa.aux_on = 1;
-    f.fa.aux_yobs = cv(*yobs);
-    f.fa.aux_shd = sqrt(0.5 * delta);
-    f.fa.dptr = dptr;
-    f.sa.d = kd;
-    f.sa.dx = D;
-    f.sa.Fs = cv(model->Fs); f.sa.Qs = cv(model->Qs); f.sa.bs = cv(model->bs);
-    f.sa.Ps = f.fa.Ps;
+    set_aux_fly(f.fa, c, 1, none, none, none);  // (passes A and B read the chains' buffers themselves)
+    fill_sample_args(f.sa, kd, D, cv(model->Fs), cv(model->Qs), cv(model->bs), none, f.fa.Ps, none, none, 1);
     f.sa.ps_shared = 1;
-    f.sa.elem = nullptr;
-    f.sa.lay = ScanLayout{1, 1, 1, 1, 1, C};
-    SweepLogpdfArgs& la = f.la;
-    la.d = kd;
-    la.dx = D; la.po = PO;
-    la.m0 = cv(model->m0); la.P0 = cv(model->P0); la.Fs = cv(model->Fs); la.Qs = cv(model->Qs); la.bs = cv(model->bs);
-    la.Hs = cv(model->Hs); la.Rs = cv(model->Rs); la.cs = cv(model->cs); la.ys = cv(*yobs);
-    la.x = cm_arr(x, kd, D); la.xp = cm_arr(x_alt, kd, D); la.u = cm_arr(u, kd, D);
-    la.delta = delta; la.nan_policy = nan_policy; la.u_fly = 0; la.shd = sqrt(0.5 * delta); la.dptr = dptr;
+    fill_sweep_logpdf_args(f.la, c, kd, *model, cv(*yobs), cm_arr(x, kd, D), cm_arr(x_alt, kd, D), cm_arr(u, kd, D), 0, none);
     f.memo = memo;
-    f.xa = x; f.xb = x_alt; f.sel = sel; f.u = u; f.inc = inc; f.keys = keys; f.eps0s = eps0s; f.u_acc = u_acc; f.accepted = accepted; f.logs = logs;
+    f.xa = x; f.xb = x_alt; f.sel = c.sel; f.u = u; f.inc = inc; f.keys = c.keys; f.eps0s = eps0s; f.u_acc = c.u_acc; f.accepted = c.accepted; f.logs = c.logs;
     if (h->st_mean && (h->st_x != x || h->st_n != (long long)C * T * D || h->st_dtype != (sizeof(R) == 4 ? AUXSSM_F32 : AUXSSM_F64))) {
         set_error("running moments are attached to another state (x=%p, n=%lld, dtype=%d): detach them (auxssm_stats_attach with NULLs) "
                   "before sweeping a different state on this handle", h->st_x, h->st_n, h->st_dtype);
         return AUXSSM_ERR_ARG;
     }
     if ((rc = sl->fused(h, f))) return rc;
-    if (!sel) {  // plain state: x' sits in x_alt, the usual select moves the accepted chains (and folds attached moments)
-        if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)accepted, cm_arr(x_alt, kd, D), cm_arr(x, kd, D), 1))) return rc;
+    if (!c.sel) {  // plain state: x' sits in x_alt, the usual select moves the accepted chains (and folds attached moments)
+        if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)c.accepted, cm_arr(x_alt, kd, D), cm_arr(x, kd, D), 1))) return rc;
     } else if (h->st_mean) {  // lazy state: the moments' fold as its own pass over the pair of buffers
         ProfScope ps(h, AUXSSM_K_SELECT);
         const long long rows = (long long)T * D;
-        hipLaunchKernelGGL((k_fs_stats<R>), dim3((unsigned)rows, (unsigned)((C + 255) / 256)), dim3(256), 0, h->stream, C, (const int32_t*)accepted, (const int32_t*)sel,
+        hipLaunchKernelGGL((k_fs_stats<R>), dim3((unsigned)rows, (unsigned)((C + 255) / 256)), dim3(256), 0, h->stream, C, (const int32_t*)c.accepted, (const int32_t*)c.sel,
                            (const R*)x, (const R*)x_alt, (R*)h->st_sq_jump, (R*)h->st_mean, (R*)h->st_sq_mean, h->st_iter);
         ++h->st_iter;
     }
@@ -1093,83 +1134,76 @@ __global__ void k_sv_accept(int C, const R* j1, const R* j2, const R* ell1, cons
 
 // kernel(key, state, delta) of kalman/generic.py:53-76 with the SV factories: both linearisation points (x for the proposal,
 // x_prop for the reverse move) get their own observation set and filter pass, as in the reference.
-template <typename R>
-static int sweep_sv(auxssm_ctx* h, int dtype, int order, const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs,
-                    double delta, const double* dptr, int parallel, int nan_policy, int layout, void* x, const void* eps_aux, const void* eps_samp,
-                    const void* u_acc, int32_t* accepted, void* logs) {
-    const int C = dims->C, T = dims->T, D = dims->dx;
+template <typename R> static int sweep_sv(const SweepCall& c) {
+    auxssm_ctx* h = c.h;
+    const auxssm_lgssm* model = c.model;
+    const auxssm_arr* yobs = c.yobs;
+    const int dtype = c.dtype, order = c.order, parallel = c.parallel, nan_policy = c.nan_policy;
+    const double delta = c.delta;
+    const double* dptr = c.dptr;
+    void* x = c.x;
+    const int C = c.dims->C, T = c.dims->T, D = c.dims->dx;
     const bool wide = is_wide(D, D);
     const KalmanEntry* ke = need_kalman(dtype, D, D);
     const SampleEntry* se = wide ? wide_sample_entry(dtype) : sample_entry(dtype, D);
     if (!ke || !se) return AUXSSM_ERR_UNSUPPORTED;
     // layout 1 (register kernels only): state, noise and every internal per-chain buffer chain-minor, lanes <-> chains
-    const int cm = layout == AUXSSM_LAYOUT_CHAIN_MINOR ? 1 : 0;
+    const int cm = c.cm();
     if (cm && wide) {
         set_error("dx=%d runs the wide-state path, which takes the dense (C, T, dx) layout only", D);
         return AUXSSM_ERR_UNSUPPORTED;
     }
     const KDims kd{C, T, 1};
+    const SweepViews view{cm, kd};
     const size_t sR = sizeof(R), CT = (size_t)C * T;
     const bool second = order == 2;
+    // First-order factory with chain-shared dynamics: the filtered covariances and the gain rows depend on the model and the step size only (the
+    // pseudo-observations are finite whatever the data: every component is observed), the same for the proposal and the reverse filter.
+    const int ps_shared = (!second && !wide && chain_shared_mode(h, cm, C, T, dynamics_chain_shared(model))) ? 1 : 0;
     // Per-chain observation model in the chain-minor layout (second order, or first order without chain-shared dynamics): no observation arrays -- the
     // scan passes and the log-density pass re-form the pseudo-observations from (x, u, y) (FilterArgs::sv_order)
-    const bool fly = cm && !wide && T > 1 &&
-                     !(!second && chain_shared_mode(h, cm, C, T, model->Fs.sc == 0 && model->Qs.sc == 0 && model->bs.sc == 0 && model->P0.sc == 0));
-    size_t need = 0;
-    auto add = [&](size_t b) { need += b + 256; };
-    for (int q = 0; q < (fly ? 2 : 4); ++q) add(CT * D * sR);   // u, x_prop (, ys1, ys2)
-    if (second && !fly) add(2 * CT * D * D * sR);              // Rs1, Rs2
-    add(CT * D * sR);                                        // ms
-    add(CT * D * D * sR);                                    // Ps
-    add((size_t)(D * D + D * D + D) * sR + (size_t)16 * C * sR + (size_t)5 * C * sizeof(Acc) + 4096);
+    const bool fly = cm && !wide && T > 1 && !ps_shared;
     const bool wide_carrier = wide && !second && C >= 2 && h->share_model;  // (below: the observation pattern said to the chain-shared wide filter)
-    if (wide_carrier) add((size_t)T * D * sR);
-    if (wide_carrier) add(wide_gain_tab_bytes(dtype, T, D, D));  // the gain rows: built by the proposal filter, reused by the reverse filter
-    add(wide ? wide_filter_ws(h, dtype, kd, parallel, D, D) : ke->filter_ws(h, kd, parallel));
-    add(wide ? wide_sample_ws(h, dtype, kd, parallel, D) : se->sample_ws(h, kd, parallel));
-    add(wide ? wide_logpdf_ws(dtype, kd) : std::max(ke->logpdf_ws(h, kd), se->sv_logpdf_ws(h, kd)));
-    int rc = ws_reserve(h, need);
+    R *u, *ys1, *ys2, *xp, *Rs1 = nullptr, *Rs2 = nullptr, *ms, *Ps, *eye, *Rc, *zero, *sc, *wide_mask = nullptr;
+    Acc* sums;
+    void* wide_gtab = nullptr;
+    WsPlan ws;
+    ws.add(u, CT * D * sR);
+    if (!fly) ws.add(ys1, CT * D * sR), ws.add(ys2, CT * D * sR);
+    ws.add(xp, CT * D * sR);
+    if (second && !fly) ws.add(Rs1, CT * D * D * sR), ws.add(Rs2, CT * D * D * sR);
+    ws.add(ms, CT * D * sR);
+    ws.add(Ps, CT * D * D * sR);
+    ws.add(eye, (size_t)D * D * sR);
+    ws.add(Rc, (size_t)D * D * sR);
+    ws.add(zero, (size_t)D * sR);
+    ws.add(sc, (size_t)16 * C * sR);
+    ws.add(sums, (size_t)5 * C * sizeof(Acc));
+    if (wide_carrier) {
+        ws.add(wide_mask, (size_t)T * D * sR);
+        ws.add(wide_gtab, wide_gain_tab_bytes(dtype, T, D, D));  // the gain rows: built by the proposal filter, reused by the reverse filter
+    }
+    ws.after(wide ? wide_filter_ws(h, dtype, kd, parallel, D, D) : ke->filter_ws(h, kd, parallel));
+    ws.after(wide ? wide_sample_ws(h, dtype, kd, parallel, D) : se->sample_ws(h, kd, parallel));
+    ws.after(wide ? wide_logpdf_ws(dtype, kd) : std::max(ke->logpdf_ws(h, kd), se->sv_logpdf_ws(h, kd)));
+    int rc = ws.reserve(h);
     if (rc) return rc;
-    R* u = (R*)ws_take(h, CT * D * sR);
-    R* ys1 = fly ? u : (R*)ws_take(h, CT * D * sR);  // (fly: never read; non-null for the checks below)
-    R* ys2 = fly ? u : (R*)ws_take(h, CT * D * sR);
-    R* xp = (R*)ws_take(h, CT * D * sR);
-    R* Rs1 = second && !fly ? (R*)ws_take(h, CT * D * D * sR) : nullptr;
-    R* Rs2 = second && !fly ? (R*)ws_take(h, CT * D * D * sR) : nullptr;
-    R* ms = (R*)ws_take(h, CT * D * sR);
-    R* Ps = (R*)ws_take(h, CT * D * D * sR);
-    R* eye = (R*)ws_take(h, (size_t)D * D * sR);
-    R* Rc = (R*)ws_take(h, (size_t)D * D * sR);
-    R* zero = (R*)ws_take(h, (size_t)D * sR);
-    R* sc = (R*)ws_take(h, (size_t)16 * C * sR);
-    Acc* sums = (Acc*)ws_take(h, (size_t)5 * C * sizeof(Acc));
-    R* wide_mask = wide_carrier ? (R*)ws_take(h, (size_t)T * D * sR) : nullptr;
-    void* wide_gtab = wide_carrier ? ws_take(h, wide_gain_tab_bytes(dtype, T, D, D) - 256) : nullptr;
-    if (!u || !ys1 || !ys2 || !xp || !ms || !Ps || !eye || !Rc || !zero || !sc || !sums || (wide_carrier && !wide_mask)) return AUXSSM_ERR_NOMEM;
+    if (fly) ys1 = ys2 = u;  // (never read)
     R* ell1 = sc; R* ell2 = sc + C; R* j1 = sc + 2 * C; R* j2 = sc + 3 * C; R* terms = sc + 4 * C;
     const size_t mark = h->ws_off;
     const long long tot = (long long)CT * D;
     const unsigned gb = (unsigned)((tot + 255) / 256);
-    auto arr = [&](const void* p, long long rec) { return cm ? cm_arr(p, kd, rec) : dense_arr(p, kd, rec); };
-    const Arr xA = arr(x, D), xpA = arr(xp, D), uA = arr(u, D), y1A = arr(ys1, D), y2A = arr(ys2, D);
-    const Arr R1A = Rs1 ? arr(Rs1, (long long)D * D) : Arr{nullptr, 0, 0, 0, 1};
-    const Arr R2A = Rs2 ? arr(Rs2, (long long)D * D) : Arr{nullptr, 0, 0, 0, 1};
+    const Arr xA = view(x, D), xpA = view(xp, D), uA = view(u, D), y1A = view(ys1, D), y2A = view(ys2, D);
+    const Arr R1A = Rs1 ? view(Rs1, (long long)D * D) : Arr{nullptr, 0, 0, 0, 1};
+    const Arr R2A = Rs2 ? view(Rs2, (long long)D * D) : Arr{nullptr, 0, 0, 0, 1};
 
-    // First-order factory with chain-shared dynamics: the filtered covariances and the gain rows depend on the model and the step size only (the
-    // pseudo-observations are finite whatever the data: every component is observed), the same for the proposal and the reverse filter.  That MODEL
-    // STAGE runs once per sweep, on the side stream beside the previous sweep (ctx.h::SideStage, as in sweep_lg_concat); the reverse filter reuses
-    // its gain rows.
-    const int ps_shared = (!second && !wide && chain_shared_mode(h, cm, C, T, model->Fs.sc == 0 && model->Qs.sc == 0 && model->bs.sc == 0 && model->P0.sc == 0)) ? 1 : 0;
+    // The MODEL STAGE of the chain-shared first-order sweep runs once per sweep, on the side stream beside the previous sweep (ctx.h::SideStage, as in
+    // sweep_lg_concat); the reverse filter reuses its gain rows.
     bool overlap = h->overlap_model_stage != 0 && ps_shared && cm && parallel && !dptr;
-    struct SweepEnd {
-        auxssm_ctx* h;
-        ~SweepEnd() { side_sweep_end(h); }
-    } sweep_end{h};
+    SweepEnd sweep_end{h};
     R* mask_carrier = nullptr;
     if (overlap) {
-        const size_t P_ = D, gain = (size_t)D * D + D + 2 * (size_t)D * P_ + P_ + P_ * (P_ + 1) / 2 + 4, felem = 3 * (size_t)D * D + 2 * D + 8;
-        const size_t need_side = (size_t)(T + 64) * sR * (3 * (size_t)D * D + 4 * D + gain + 2 * felem + 8 * (size_t)D * D + 8 * D + 32) + (4u << 20);
-        if ((rc = side_open(h, need_side))) return rc;
+        if ((rc = side_open(h, side_stage_bytes(sR, T, D, D, 0, 2 * (size_t)D * D + 2 * D)))) return rc;
         overlap = h->side.open;
     }
     if (overlap) {
@@ -1205,44 +1239,42 @@ static int sweep_sv(auxssm_ctx* h, int dtype, int order, const auxssm_dims* dims
         SideScope sc_(h);
         hipLaunchKernelGGL((k_scaled_eye<R>), dim3((D * D + 255) / 256), dim3(256), 0, h->stream, D, (R)(0.5 * delta), Rc, dptr);
     }
-    auxssm_dims dc = *dims;
+    auxssm_dims dc = *c.dims;
     dc.dy = D;
     dc.B = 1;
     const auxssm_arr y1d{ys1, (int64_t)T * D, (int64_t)D, 0}, y2d{ys2, (int64_t)T * D, (int64_t)D, 0};
     // the filtered covariances do not depend on the chain when neither the dynamics nor R do (first order); wide states: one copy too -- the chain-shared wide filter
     // then skips its broadcast to the chains' slots and the sampler builds its gain / factor tables once per time step (wide.hip::run_sample_shared)
-    const bool wide_ps_once = wide_carrier && model->Fs.sc == 0 && model->Qs.sc == 0 && model->bs.sc == 0 && model->P0.sc == 0 && model->m0.sc == 0;
-    const Arr PsA = (ps_shared || wide_ps_once) ? Arr{Ps, 0, (long long)D * D, 0, 1} : arr(Ps, (long long)D * D);
+    const bool wide_ps_once = wide_carrier && prior_chain_shared(model);
+    const Arr PsA = (ps_shared || wide_ps_once) ? Arr{Ps, 0, (long long)D * D, 0, 1} : view(Ps, (long long)D * D);
+    // The FilterArgs of one of the two filters, each built from nothing: the model g with pseudo-observations ys (second order: and their covariances Rs)
+    // linearised at xlin.  What the two have in common is said here once -- the views, the on-the-fly form (sv_order; eps: the noise that forms u, or none when
+    // u exists), the mask carrier and the buffer the chain-shared wide filter leaves its gain rows in (pc)
+    auto filter_args = [&](FilterArgs& fa, const auxssm_lgssm& g, const Arr& ys, const Arr& Rs, const Arr& xlin, const Arr& eps) {
+        sweep_filter_args(fa, dc, g, ys, view(ms, D), PsA, cm);
+        if (second) fa.Rs = Rs;
+        if (fly) {
+            fa.sv_order = order;
+            fa.sv_delta = delta;
+            set_aux_fly(fa, c, 0, xlin, eps, uA);
+        }
+        if (overlap || wide_carrier) fa.mask_ys = Arr{mask_carrier, 0, (long long)D, 0, 1};
+        if (wide_ps_once && wide_gtab) fa.pc = wide_gtab;
+    };
 
     // proposal: observations linearised at x, filter, pathwise sample (generic.py:80-86)
     if (!fly) {
         ProfScope ps(h, AUXSSM_K_FACTORY);
-        hipLaunchKernelGGL((k_sv_obs<R>), dim3(gb), dim3(256), 0, h->stream, tot, C, T, D, order, cm, (const R*)x, (const R*)eps_aux,
-                           (R)sqrt(0.5 * delta), (R)delta, dptr, cv(*yobs), u, ys1, Rs1);
+        hipLaunchKernelGGL((k_sv_obs<R>), dim3(gb), dim3(256), 0, h->stream, tot, C, T, D, order, cm, (const R*)x, (const R*)c.eps_aux,
+                           (R)c.shd(), (R)delta, dptr, cv(*yobs), u, ys1, Rs1);
     }
     FilterArgs fa;
-    fill_filter_args(fa, &dc, &g1, &y1d, ms, Ps);
-    fa.ys = y1A;
-    fa.ms = arr(ms, D);
-    fa.Ps = PsA;
-    fa.lay.cm = cm;
-    if (second) fa.Rs = R1A;
-    if (fly) {
-        fa.sv_order = order; fa.sv_delta = delta; fa.aux_shd = sqrt(0.5 * delta); fa.dptr = dptr;
-        fa.aux_x = xA; fa.aux_eps = arr(eps_aux, D); fa.aux_u = uA; fa.aux_yobs = cv(*yobs);
-    }
-    if (overlap || wide_carrier) fa.mask_ys = Arr{mask_carrier, 0, (long long)D, 0, 1};
-    if (wide_ps_once && wide_gtab) fa.pc = wide_gtab;  // (the chain-shared wide filter leaves its gain rows here)
+    filter_args(fa, g1, y1A, R1A, xA, view(c.eps_aux, D));
     rc = ke->filter(h, fa, parallel, ell1);
     if (rc) return rc;
     h->ws_off = mark;
     SampleArgs sa;
-    sa.d = kd;
-    sa.dx = D;
-    sa.Fs = cv(model->Fs); sa.Qs = cv(model->Qs); sa.bs = cv(model->bs);
-    sa.ms = arr(ms, D); sa.Ps = PsA;
-    sa.eps = arr(eps_samp, D); sa.xs = xpA; sa.elem = nullptr;
-    sa.lay = ScanLayout{1, 1, 1, 1, cm, C};
+    fill_sample_args(sa, kd, D, cv(model->Fs), cv(model->Qs), cv(model->bs), view(ms, D), PsA, view(c.eps_samp, D), xpA, cm);
     sa.ps_shared = cm ? ps_shared : 0;
     rc = se->sample(h, sa, parallel);
     if (rc) return rc;
@@ -1253,28 +1285,17 @@ static int sweep_sv(auxssm_ctx* h, int dtype, int order, const auxssm_dims* dims
         hipLaunchKernelGGL((k_sv_obs<R>), dim3(gb), dim3(256), 0, h->stream, tot, C, T, D, order, cm, (const R*)xp, (const R*)nullptr, (R)0,
                            (R)delta, dptr, cv(*yobs), u, ys2, Rs2);
     }
-    fill_filter_args(fa, &dc, &g2, &y2d, ms, Ps);
-    fa.ys = y2A;
-    fa.ms = arr(ms, D);
-    fa.Ps = PsA;
-    fa.lay.cm = cm;
-    if (second) fa.Rs = R2A;
-    if (fly) {  // (only ell2 is used: generic.py:67)
-        fa.sv_order = order; fa.sv_delta = delta; fa.aux_shd = sqrt(0.5 * delta); fa.dptr = dptr;
-        fa.aux_x = xpA; fa.aux_eps = Arr{nullptr, 0, 0, 0, 1}; fa.aux_u = uA; fa.aux_yobs = cv(*yobs);
-        fa.no_moments = 1;
-    }
+    FilterArgs fr;
+    filter_args(fr, g2, y2A, R2A, xpA, Arr{nullptr, 0, 0, 0, 1});
+    if (fly) fr.no_moments = 1;  // (only ell2 is used: generic.py:67)
     if (overlap && h->side.last_tab) {  // the proposal filter's gain rows (same model, step size and mask)
-        fa.mask_ys = Arr{mask_carrier, 0, (long long)D, 0, 1};
-        fa.tab = h->side.last_tab;
-        fa.tab_ready = 1;
+        fr.tab = h->side.last_tab;
+        fr.tab_ready = 1;
     }
-    if (wide_carrier) fa.mask_ys = Arr{mask_carrier, 0, (long long)D, 0, 1};
-    if (wide_ps_once && wide_gtab && parallel && T >= 5) {  // same model, same step size, same pattern: the proposal filter's covariances and gain rows (if it took the shared form:
-        fa.pc = wide_gtab;                                   // it does whenever this one would -- same sizes, same strides)
-        fa.tab_ready = 1;
-    }
-    rc = ke->filter(h, fa, parallel, ell2);
+    // wide states: same model, same step size, same pattern -- pc holds the proposal filter's covariances and gain rows (if it took the shared form: it does
+    // whenever this one would -- same sizes, same strides)
+    if (wide_ps_once && wide_gtab && parallel && T >= 5) fr.tab_ready = 1;
+    rc = ke->filter(h, fr, parallel, ell2);
     if (rc) return rc;
     h->ws_off = mark;
     if (!wide) {
@@ -1290,9 +1311,7 @@ static int sweep_sv(auxssm_ctx* h, int dtype, int order, const auxssm_dims* dims
         rc = se->sv_logpdf(h, la, sums);  // [5][C] = jp_prop, jp_rev, lt_prop, lt_rev, corr
         if (rc) return rc;
         h->ws_off = mark;
-        hipLaunchKernelGGL((k_accept<R>), dim3((C + 127) / 128), dim3(128), 0, h->stream, C, (const Acc*)sums, (const Acc*)(sums + C), (const R*)ell1,
-                           (const R*)ell2, (const Acc*)(sums + 2 * C), (const Acc*)(sums + 3 * C), (const Acc*)(sums + 4 * C), (const R*)u_acc, accepted,
-                           (R*)logs);
+        launch_accept<R>(c, sums, ell1, ell2);
     } else {
         // wide-state path: joint log-densities of both auxiliary models (posterior_logpdf + ell, base.py:72-96), then the SV terms
         bool both = false;
@@ -1301,13 +1320,8 @@ static int sweep_sv(auxssm_ctx* h, int dtype, int order, const auxssm_dims* dims
             // first order on one model: both joints from ONE launch pair -- Q_t^-1, R^-1 and their determinants once per time step, the chains as columns, ys1 scored
             // against x' and ys2 against x (wide_shared.h::wk_lp_cols); sums [2] / [3] = observation + transition terms of x' / x
             SweepLogpdfArgs sl_;
-            sl_.d = kd;
-            sl_.dx = D; sl_.po = D;
-            sl_.m0 = cv(model->m0); sl_.P0 = cv(model->P0); sl_.Fs = cv(model->Fs); sl_.Qs = cv(model->Qs); sl_.bs = cv(model->bs);
-            sl_.Hs = cv(g1.Hs); sl_.Rs = cv(g1.Rs); sl_.cs = cv(g1.cs);
-            sl_.ys = cv(y1d); sl_.ys_x = cv(y2d);
-            sl_.x = dense_arr(x, kd, D); sl_.xp = dense_arr(xp, kd, D); sl_.u = dense_arr(u, kd, D);
-            sl_.delta = delta; sl_.dptr = dptr; sl_.nan_policy = nan_policy; sl_.u_fly = 0; sl_.shd = sqrt(0.5 * delta);
+            fill_sweep_logpdf_args(sl_, c, kd, g1, cv(y1d), dense_arr(x, kd, D), dense_arr(xp, kd, D), dense_arr(u, kd, D), 0, Arr{});
+            sl_.ys_x = cv(y2d);
             rc = wsl->wide_shared(h, sl_, sums);
             if (rc == AUXSSM_OK) {
                 hipLaunchKernelGGL((k_acc_to_real<R>), dim3((2 * C + 127) / 128), dim3(128), 0, h->stream, C, (const Acc*)(sums + 2 * C), j1, j2);
@@ -1331,9 +1345,9 @@ static int sweep_sv(auxssm_ctx* h, int dtype, int order, const auxssm_dims* dims
         hipLaunchKernelGGL((k_sv_terms<R>), dim3(C), dim3(256), 0, h->stream, C, T, D, (R)delta, dptr, (const R*)x, (const R*)xp, (const R*)u,
                            cv(*yobs), (const R*)ys1, (const R*)ys2, (const R*)Rs1, (const R*)Rs2, terms);
         hipLaunchKernelGGL((k_sv_accept<R>), dim3((C + 127) / 128), dim3(128), 0, h->stream, C, (const R*)j1, (const R*)j2, (const R*)ell1,
-                           (const R*)ell2, (const R*)terms, (const R*)u_acc, accepted, (R*)logs);
+                           (const R*)ell2, (const R*)terms, (const R*)c.u_acc, c.accepted, (R*)c.logs);
     }
-    if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)accepted, xpA, xA, cm))) return rc;
+    if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)c.accepted, xpA, xA, cm))) return rc;
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;
 }
@@ -1366,118 +1380,83 @@ __global__ void k_lorenz_dyn(int C, int T, int cfast, const R* __restrict__ par,
     for (int r = 0; r < 3; ++r) bo[r * xs_] = mu[r] - (F[r * 3] * x[0] + F[r * 3 + 1] * x[1] + F[r * 3 + 2] * x[2]);
 }
 
-template <typename R>
-static int sweep_lorenz(auxssm_ctx* h, int dtype, const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs, double delta, const double* dptr,
-                        int parallel, int nan_policy, int layout, void* x, const void* eps_aux, const void* eps_samp, const void* u_acc,
-                        int32_t* accepted, void* logs) {
-    const int C = dims->C, T = dims->T, D = 3, PO = dims->dy, P = D + PO;
+template <typename R> static int sweep_lorenz(const SweepCall& c) {
+    auxssm_ctx* h = c.h;
+    const auxssm_lgssm* model = c.model;
+    const int dtype = c.dtype, parallel = c.parallel;
+    const int C = c.dims->C, T = c.dims->T, D = 3, PO = c.dims->dy, P = D + PO;
     const KalmanEntry* ke = need_kalman(dtype, D, P);
     const SampleEntry* se = sample_entry(dtype, D);
     const SweepLogpdfEntry* sl = sweep_logpdf_entry(dtype, D, PO);
     if (!ke || !se || !sl || !sl->lorenz) return AUXSSM_ERR_UNSUPPORTED;
-    const int cm = layout == AUXSSM_LAYOUT_CHAIN_MINOR ? 1 : 0;  // state, noise and every per-chain buffer (T, ., C): lanes <-> chains
+    const int cm = c.cm();  // state, noise and every per-chain buffer (T, ., C): lanes <-> chains
     const KDims kd{C, T, 1};
+    const SweepViews view{cm, kd};
     const size_t sR = sizeof(R), CT = (size_t)C * T, n = (size_t)(T > 1 ? T - 1 : 1);
-    size_t need = 0;
-    auto add = [&](size_t b) { need += b + 256; };
-    add(CT * P * sR);
-    add((size_t)T * (P * D + P * P + P) * sR + 1024);
-    for (int q = 0; q < 4; ++q) add(CT * D * sR);             // u, ms, xp, (spare)
-    add(CT * D * D * sR);                                     // Ps
-    add(2 * (size_t)C * n * (9 + 3) * sR + 1024);             // Fs1, bs1, Fs2, bs2
-    add((size_t)16 * C * sR + (size_t)5 * C * sizeof(Acc) + 2048);
-    add(ke->filter_ws(h, kd, parallel));
-    add(se->sample_ws(h, kd, parallel));
-    add(sl->ws(h, kd));
-    int rc = ws_reserve(h, need);
+    R *ysc, *Hc, *Rc, *cc, *u, *ms, *xp, *Ps, *Fs1, *bs1, *Fs2, *bs2, *sc;
+    Acc* sums;
+    WsPlan ws;
+    ws.add(ysc, CT * P * sR);
+    ws.add(Hc, (size_t)T * P * D * sR);
+    ws.add(Rc, (size_t)T * P * P * sR);
+    ws.add(cc, (size_t)T * P * sR);
+    ws.add(u, CT * D * sR);
+    ws.add(ms, CT * D * sR);
+    ws.add(xp, CT * D * sR);
+    ws.add(Ps, CT * D * D * sR);
+    ws.add(Fs1, (size_t)C * n * 9 * sR);
+    ws.add(bs1, (size_t)C * n * 3 * sR);
+    ws.add(Fs2, (size_t)C * n * 9 * sR);
+    ws.add(bs2, (size_t)C * n * 3 * sR);
+    ws.add(sc, (size_t)16 * C * sR);
+    ws.add(sums, (size_t)5 * C * sizeof(Acc));
+    ws.after(ke->filter_ws(h, kd, parallel));
+    ws.after(se->sample_ws(h, kd, parallel));
+    ws.after(sl->ws(h, kd));
+    int rc = ws.reserve(h);
     if (rc) return rc;
-    R* ysc = (R*)ws_take(h, CT * P * sR);
-    R* Hc = (R*)ws_take(h, (size_t)T * P * D * sR);
-    R* Rc = (R*)ws_take(h, (size_t)T * P * P * sR);
-    R* cc = (R*)ws_take(h, (size_t)T * P * sR);
-    R* u = (R*)ws_take(h, CT * D * sR);
-    R* ms = (R*)ws_take(h, CT * D * sR);
-    R* xp = (R*)ws_take(h, CT * D * sR);
-    R* Ps = (R*)ws_take(h, CT * D * D * sR);
-    R* Fs1 = (R*)ws_take(h, (size_t)C * n * 9 * sR);
-    R* bs1 = (R*)ws_take(h, (size_t)C * n * 3 * sR);
-    R* Fs2 = (R*)ws_take(h, (size_t)C * n * 9 * sR);
-    R* bs2 = (R*)ws_take(h, (size_t)C * n * 3 * sR);
-    R* sc = (R*)ws_take(h, (size_t)16 * C * sR);
-    Acc* sums = (Acc*)ws_take(h, (size_t)5 * C * sizeof(Acc));
-    if (!ysc || !Hc || !Rc || !cc || !u || !ms || !xp || !Ps || !Fs1 || !bs1 || !Fs2 || !bs2 || !sc || !sums) return AUXSSM_ERR_NOMEM;
     R* ell1 = sc; R* ell2 = sc + C;
     const size_t mark = h->ws_off;
     const R* par = (const R*)model->Fs.ptr;  // [theta1, theta2, theta3, dt], chain stride model->Fs.sc (0 = one theta for all chains)
     const long long psc = model->Fs.sc;
-    auto arr = [&](const void* p, long long rec) { return cm ? cm_arr(p, kd, rec) : dense_arr(p, kd, rec); };
-    const Arr xA = arr(x, D), xpA = arr(xp, D), uA = arr(u, D), yscA = arr(ysc, P);
+    const Arr xA = view(c.x, D), xpA = view(xp, D), uA = view(u, D), yscA = view(ysc, P), epsauxA = view(c.eps_aux, D);
     const bool aux_fly = cm && T > 1;  // u and the concatenated observations of t >= 1 are formed inside the filter
     // per-chain transition arrays have n = T - 1 rows: same strides as a T-row array of that record size
-    const Arr F1A = arr(Fs1, 9), b1A = arr(bs1, 3), F2A = arr(Fs2, 9), b2A = arr(bs2, 3);
-    {
-        ProfScope ps(h, AUXSSM_K_FACTORY);
-        const long long n1 = (long long)T * (P * D + P * P + P);
-        hipLaunchKernelGGL((k_concat_model<R>), dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, h->stream, T, D, PO, cv(model->Hs),
-                           cv(model->Rs), cv(model->cs), (R)(0.5 * delta), dptr, Hc, Rc, cc);
-        const int Tc = aux_fly ? 1 : T;
-        const long long n2 = (long long)C * Tc * P;
-        hipLaunchKernelGGL((k_concat_obs<R>), dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, h->stream, C, Tc, D, PO, xA,
-                           arr(eps_aux, D), (R)sqrt(0.5 * delta), dptr, cv(*yobs), uA, yscA, cm);
-    }
+    const Arr F1A = view(Fs1, 9), b1A = view(bs1, 3), F2A = view(Fs2, 9), b2A = view(bs2, 3);
+    const ConcatObs obs{aux_fly ? 1 : T, xA, epsauxA, uA, yscA};
+    const ConcatModel cmod = concat_model<R>(c, false, Hc, Rc, cc, nullptr, &obs);  // (T records whatever the time strides of the real model)
     const unsigned gd = (unsigned)(((long long)C * (T - 1) + 255) / 256);
-    auxssm_lgssm g1 = *model;
-    g1.Hs = auxssm_arr{Hc, 0, (int64_t)P * D, 0};
-    g1.Rs = auxssm_arr{Rc, 0, (int64_t)P * P, 0};
-    g1.cs = auxssm_arr{cc, 0, (int64_t)P, 0};
+    auxssm_lgssm g1 = cmod.g;
     g1.Fs = auxssm_arr{Fs1, (int64_t)n * 9, 9, 0};
     g1.bs = auxssm_arr{bs1, (int64_t)n * 3, 3, 0};
     auxssm_lgssm g2 = g1;
     g2.Fs = auxssm_arr{Fs2, (int64_t)n * 9, 9, 0};
     g2.bs = auxssm_arr{bs2, (int64_t)n * 3, 3, 0};
-    auxssm_dims dc = *dims;
-    dc.dy = P;
-    dc.B = 1;
-    const auxssm_arr yd{ysc, (int64_t)T * P, (int64_t)P, 0};
-    auto set_views = [&](FilterArgs& fa, const Arr& FA, const Arr& bA) {
-        fa.ys = yscA;
-        fa.ms = arr(ms, D);
-        fa.Ps = arr(Ps, (long long)D * D);
-        fa.lay.cm = cm;
+    // The FilterArgs of one of the two filters, each built from nothing: the concatenated model with the dynamics g linearised at one point (chain-minor: through
+    // the views FA, bA).  The step size goes in with the on-the-fly block and only with it (set_aux_fly): in the dense layout, and at T = 1, u, the observations
+    // and R = blkdiag(delta/2 I, Robs) reach the filter as arrays already formed from the step size -- host or device-resident -- by concat_model
+    auto filter_args = [&](FilterArgs& fa, const auxssm_lgssm& g, const Arr& FA, const Arr& bA) {
+        sweep_filter_args(fa, cmod.d, g, yscA, view(ms, D), view(Ps, (long long)D * D), cm);
         fa.pblk = D;
         if (cm) {
             fa.Fs = FA;
             fa.bs = bA;
         }
-        if (aux_fly) {
-            fa.aux_on = 1;
-            fa.aux_x = xA;
-            fa.aux_eps = arr(eps_aux, D);
-            fa.aux_u = uA;
-            fa.aux_yobs = cv(*yobs);
-            fa.aux_shd = sqrt(0.5 * delta);
-        fa.dptr = dptr;
-        }
+        if (aux_fly) set_aux_fly(fa, c, 1, xA, epsauxA, uA);
     };
 
     // proposal: dynamics linearised at x (generic.py:80-86)
     if (T > 1) {
         ProfScope ps(h, AUXSSM_K_FACTORY);
-        hipLaunchKernelGGL((k_lorenz_dyn<R>), dim3(gd), dim3(256), 0, h->stream, C, T, cm, par, psc, (const R*)x, Fs1, bs1);
+        hipLaunchKernelGGL((k_lorenz_dyn<R>), dim3(gd), dim3(256), 0, h->stream, C, T, cm, par, psc, (const R*)c.x, Fs1, bs1);
     }
     FilterArgs fa;
-    fill_filter_args(fa, &dc, &g1, &yd, ms, Ps);
-    set_views(fa, F1A, b1A);
+    filter_args(fa, g1, F1A, b1A);
     rc = ke->filter(h, fa, parallel, ell1);
     if (rc) return rc;
     h->ws_off = mark;
     SampleArgs sa;
-    sa.d = kd;
-    sa.dx = D;
-    sa.Fs = cm ? F1A : cv(g1.Fs); sa.Qs = cv(model->Qs); sa.bs = cm ? b1A : cv(g1.bs);
-    sa.ms = arr(ms, D); sa.Ps = arr(Ps, (long long)D * D);
-    sa.eps = arr(eps_samp, D); sa.xs = xpA; sa.elem = nullptr;
-    sa.lay = ScanLayout{1, 1, 1, 1, cm, C};
+    fill_sample_args(sa, kd, D, cm ? F1A : cv(g1.Fs), cv(model->Qs), cm ? b1A : cv(g1.bs), view(ms, D), view(Ps, (long long)D * D), view(c.eps_samp, D), xpA, cm);
     rc = se->sample(h, sa, parallel);
     if (rc) return rc;
     h->ws_off = mark;
@@ -1486,82 +1465,23 @@ static int sweep_lorenz(auxssm_ctx* h, int dtype, const auxssm_dims* dims, const
         ProfScope ps(h, AUXSSM_K_FACTORY);
         hipLaunchKernelGGL((k_lorenz_dyn<R>), dim3(gd), dim3(256), 0, h->stream, C, T, cm, par, psc, (const R*)xp, Fs2, bs2);
     }
-    fill_filter_args(fa, &dc, &g2, &yd, ms, Ps);
-    set_views(fa, F2A, b2A);
-    rc = ke->filter(h, fa, parallel, ell2);
+    FilterArgs fr;
+    filter_args(fr, g2, F2A, b2A);
+    rc = ke->filter(h, fr, parallel, ell2);
     if (rc) return rc;
     h->ws_off = mark;
     // every log-density of the MH ratio in one pass (generic.py:88-89, :98-106); the linearised transitions are rebuilt from x / x_prop
-    {
-        SweepLogpdfArgs la;
-        la.d = kd;
-        la.dx = D; la.po = PO;
-        la.m0 = cv(model->m0); la.P0 = cv(model->P0); la.Qs = cv(model->Qs);
-        la.Fs = Arr{nullptr, 0, 0, 0, 1}; la.bs = Arr{nullptr, 0, 0, 0, 1};
-        la.Hs = cv(model->Hs); la.Rs = cv(model->Rs); la.cs = cv(model->cs); la.ys = cv(*yobs);
-        la.x = xA; la.xp = xpA; la.u = uA; la.delta = delta; la.nan_policy = nan_policy;
-        la.u_fly = aux_fly ? 1 : 0; la.eps_aux = arr(eps_aux, D); la.shd = sqrt(0.5 * delta); la.dptr = dptr;
-        la.lor_par = par; la.lor_psc = psc;
-        rc = sl->lorenz(h, la, sums);  // [5][C]: jp_prop, jp_rev, lt_prop, lt_rev, corr
-        if (rc) return rc;
-        h->ws_off = mark;
-    }
-    hipLaunchKernelGGL((k_accept<R>), dim3((C + 127) / 128), dim3(128), 0, h->stream, C, (const Acc*)sums, (const Acc*)(sums + C), (const R*)ell1,
-                       (const R*)ell2, (const Acc*)(sums + 2 * C), (const Acc*)(sums + 3 * C), (const Acc*)(sums + 4 * C), (const R*)u_acc, accepted,
-                       (R*)logs);
-    if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)accepted, xpA, xA, cm))) return rc;
+    SweepLogpdfArgs la;
+    fill_sweep_logpdf_args(la, c, kd, *model, cv(*c.yobs), xA, xpA, uA, aux_fly ? 1 : 0, epsauxA);
+    la.Fs = Arr{nullptr, 0, 0, 0, 1}; la.bs = Arr{nullptr, 0, 0, 0, 1};
+    la.lor_par = par; la.lor_psc = psc;
+    rc = sl->lorenz(h, la, sums);
+    if (rc) return rc;
+    h->ws_off = mark;
+    launch_accept<R>(c, sums, ell1, ell2);
+    if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)c.accepted, xpA, xA, cm))) return rc;
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;
-}
-
-// ---- RNG fill -----------------------------------------------------------------------------------------------------
-// one Threefry block -> out[2 i], out[2 i + 1] (both fills)
-template <typename R> __global__ void k_rng_uniform(uint32_t k0, uint32_t k1, uint32_t stream, long long n, R* out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (2 * i >= n) return;
-    R u0, u1;
-    stream_uniform2<R>(k0, k1, stream, (unsigned long long)i, u0, u1);
-    out[2 * i] = u0;
-    if (2 * i + 1 < n) out[2 * i + 1] = u1;
-}
-template <typename R> __global__ void k_rng_normal(uint32_t k0, uint32_t k1, uint32_t stream, long long n, R* out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (2 * i >= n) return;
-    uint32_t x0, x1;
-    stream_counter(stream, (unsigned long long)i, x0, x1);
-    threefry2x32(k0, k1, x0, x1);
-    R z0, z1;
-    bits_to_normal2<R>(x0, x1, z0, z1);
-    out[2 * i] = z0;
-    if (2 * i + 1 < n) out[2 * i + 1] = z1;
-}
-
-// the three noise fills of one Kalman sweep in one launch: the same values as auxssm_rng_normal (keys a, b; stream 0; n each) and
-// auxssm_rng_uniform (key c; stream 0; nu) -- workgroups [0, g1) fill eps_aux, [g1, 2 g1) eps_samp, the rest u_acc
-template <typename R>
-__global__ void k_rng_sweep(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0, uint32_t c1, long long n, long long nu, unsigned g1,
-                            R* eps_aux, R* eps_samp, R* u_acc) {
-    const unsigned blk = blockIdx.x;
-    if (blk < 2 * g1) {
-        const bool second = blk >= g1;
-        const long long i = (long long)(second ? blk - g1 : blk) * blockDim.x + threadIdx.x;
-        if (2 * i >= n) return;
-        uint32_t x0, x1;
-        stream_counter(0, (unsigned long long)i, x0, x1);
-        threefry2x32(second ? b0 : a0, second ? b1 : a1, x0, x1);
-        R z0, z1;
-        bits_to_normal2<R>(x0, x1, z0, z1);
-        R* out = second ? eps_samp : eps_aux;
-        out[2 * i] = z0;
-        if (2 * i + 1 < n) out[2 * i + 1] = z1;
-    } else {
-        const long long i = (long long)(blk - 2 * g1) * blockDim.x + threadIdx.x;
-        if (2 * i >= nu) return;
-        R u0, u1;
-        stream_uniform2<R>(c0, c1, 0, (unsigned long long)i, u0, u1);
-        u_acc[2 * i] = u0;
-        if (2 * i + 1 < nu) u_acc[2 * i + 1] = u1;
-    }
 }
 
 }  // namespace ax
@@ -1878,6 +1798,65 @@ int auxssm_kalman_joint_logpdf(auxssm_handle h, int dtype, const auxssm_dims* di
     return e->logpdf(h, a, out);
 }
 
+// What auxssm_kalman_sweep* and auxssm_kalman_sweep_fused both refuse: B != 1, a step size that is not positive (unless it is device-resident), an unknown
+// nan_policy, NULL arrays (ptrs_ok: the entry point's own list, yobs and yobs->ptr among them) and per-chain copies of the data or -- obs_model -- of the real
+// observation model.  Each entry point keeps the order and the words it always had: `fused` refuses the first four in one message and has no layout check of
+// its own (fused_refusal speaks about the layout).
+static int check_sweep_common(bool fused, const auxssm_dims* dims, double delta, bool delta_on_device, int nan_policy, int layout, bool ptrs_ok,
+                              const auxssm_lgssm* model, const auxssm_arr* yobs, bool obs_model) {
+    const bool b_ok = dims->B == 1, delta_ok = delta_on_device || delta > 0;
+    const bool nan_ok = nan_policy == AUXSSM_NAN_REFERENCE || nan_policy == AUXSSM_NAN_MASKED;
+    if (fused) {
+        if (!b_ok || !delta_ok || !ptrs_ok || !nan_ok) {
+            set_error("auxssm_kalman_sweep_fused: B must be 1, delta > 0 (or delta_dev), keys / yobs / x / x_alt / u_acc / accepted non-NULL, nan_policy 0 or 1");
+            return AUXSSM_ERR_ARG;
+        }
+    } else {
+        if (!b_ok) {
+            set_error("auxssm_kalman_sweep needs B == 1");
+            return AUXSSM_ERR_ARG;
+        }
+        if (!delta_ok) {
+            set_error("delta must be > 0");
+            return AUXSSM_ERR_ARG;
+        }
+        if (layout != AUXSSM_LAYOUT_DENSE && layout != AUXSSM_LAYOUT_CHAIN_MINOR) {
+            set_error("layout must be AUXSSM_LAYOUT_DENSE (0) or AUXSSM_LAYOUT_CHAIN_MINOR (1)");
+            return AUXSSM_ERR_ARG;
+        }
+        if (!ptrs_ok) {
+            set_error("yobs/x/eps_aux/eps_samp/u_acc/accepted must be non-NULL");
+            return AUXSSM_ERR_ARG;
+        }
+        if (!nan_ok) {
+            set_error("nan_policy must be 0 (reference) or 1 (masked)");
+            return AUXSSM_ERR_ARG;
+        }
+    }
+    // The data and the REAL observation model are what the chains have in common (the reference's factories close over them,
+    // examples/lorenz/auxiliary_kalman.py:26-35): the concatenated model is built once per time step, so per-chain copies are refused
+    // rather than silently read at chain 0.
+    if (yobs->sc != 0 || (obs_model && !obs_model_chain_shared(model))) {
+        set_error("yobs and the observation model (Hs, Rs, cs) are shared by the chains of a sweep: their chain strides must be 0");
+        return AUXSSM_ERR_ARG;
+    }
+    return AUXSSM_OK;
+}
+// device-resident step size: {delta, sqrt(delta / 2)} for the kernels of this sweep into the handle's block (lazily allocated), on the stream -- nothing returns
+// to the host; *dptr = that block, or null with a host step size
+static int delta_block(auxssm_ctx* h, int dtype, const void* delta_dev, const double** dptr) {
+    *dptr = nullptr;
+    if (!delta_dev) return AUXSSM_OK;
+    if (!h->dblock) AX_HIP(hipMalloc((void**)&h->dblock, 2 * sizeof(double)));
+    by_dtype(dtype, [&](auto r) {
+        using R = decltype(r);
+        hipLaunchKernelGGL((k_delta_block<R>), dim3(1), dim3(1), 0, h->stream, (const R*)delta_dev, h->dblock);
+        return AUXSSM_OK;
+    });
+    *dptr = h->dblock;
+    return AUXSSM_OK;
+}
+
 // delta_dev != NULL: the step size is a device scalar of `dtype` (auxssm_kalman_sweep_dd); `delta` is then only a placeholder
 static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const auxssm_dims* dims, const auxssm_lgssm* model,
                              const auxssm_arr* yobs, double delta, const void* delta_dev, const uint32_t* keys, int parallel, int nan_policy, int layout,
@@ -1912,57 +1891,23 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
     } else if ((rc = check_lgssm(model, dims->T))) {
         return rc;
     }
-    if (dims->B != 1) {
-        set_error("auxssm_kalman_sweep needs B == 1");
-        return AUXSSM_ERR_ARG;
-    }
-    if (!(delta > 0)) {
-        set_error("delta must be > 0");
-        return AUXSSM_ERR_ARG;
-    }
-    if (layout != AUXSSM_LAYOUT_DENSE && layout != AUXSSM_LAYOUT_CHAIN_MINOR) {
-        set_error("layout must be AUXSSM_LAYOUT_DENSE (0) or AUXSSM_LAYOUT_CHAIN_MINOR (1)");
-        return AUXSSM_ERR_ARG;
-    }
-    if (!yobs || !yobs->ptr || !x || !eps_aux || !eps_samp || !u_acc || !accepted) {
-        set_error("yobs/x/eps_aux/eps_samp/u_acc/accepted must be non-NULL");
-        return AUXSSM_ERR_ARG;
-    }
-    if (nan_policy != AUXSSM_NAN_REFERENCE && nan_policy != AUXSSM_NAN_MASKED) {
-        set_error("nan_policy must be 0 (reference) or 1 (masked)");
-        return AUXSSM_ERR_ARG;
-    }
-    // The data and the REAL observation model are what the chains have in common (the reference's factories close over them,
-    // examples/lorenz/auxiliary_kalman.py:26-35): the concatenated model is built once per time step, so per-chain copies are refused
-    // rather than silently read at chain 0.
-    if (yobs->sc != 0 || (!sv && (model->Hs.sc != 0 || model->Rs.sc != 0 || model->cs.sc != 0))) {
-        set_error("yobs and the observation model (Hs, Rs, cs) are shared by the chains of a sweep: their chain strides must be 0");
-        return AUXSSM_ERR_ARG;
-    }
-    const double* dptr = nullptr;
-    if (delta_dev) {  // {delta, sqrt(delta / 2)} for the kernels of this sweep, on the stream: nothing returns to the host
-        if (!h->dblock) AX_HIP(hipMalloc((void**)&h->dblock, 2 * sizeof(double)));
-        if (dtype == AUXSSM_F32) hipLaunchKernelGGL((k_delta_block<float>), dim3(1), dim3(1), 0, h->stream, (const float*)delta_dev, h->dblock);
-        else hipLaunchKernelGGL((k_delta_block<double>), dim3(1), dim3(1), 0, h->stream, (const double*)delta_dev, h->dblock);
-        dptr = h->dblock;
-    }
-    if (keys && (lorenz || sv)) {  // these sweeps read the noise from the arrays: draw all of it first (auxssm_kalman_draw)
-        const long long nn = (long long)dims->C * dims->T * dims->dx;
-        if (dtype == AUXSSM_F32) launch_rng_sweep<float>(h, keys, nn, dims->C, const_cast<void*>(eps_aux), const_cast<void*>(eps_samp), const_cast<void*>(u_acc));
-        else launch_rng_sweep<double>(h, keys, nn, dims->C, const_cast<void*>(eps_aux), const_cast<void*>(eps_samp), const_cast<void*>(u_acc));
-    }
-    if (lorenz) {
-        rc = dtype == AUXSSM_F32 ? sweep_lorenz<float>(h, dtype, dims, model, yobs, delta, dptr, parallel, nan_policy, layout, x, eps_aux, eps_samp, u_acc, accepted, logs)
-                                 : sweep_lorenz<double>(h, dtype, dims, model, yobs, delta, dptr, parallel, nan_policy, layout, x, eps_aux, eps_samp, u_acc, accepted, logs);
-    } else if (sv) {
-        const int order = model_kind == AUXSSM_KMODEL_SV_FIRST ? 1 : 2;
-        rc = dtype == AUXSSM_F32 ? sweep_sv<float>(h, dtype, order, dims, model, yobs, delta, dptr, parallel, nan_policy, layout, x, eps_aux, eps_samp, u_acc, accepted, logs)
-                                 : sweep_sv<double>(h, dtype, order, dims, model, yobs, delta, dptr, parallel, nan_policy, layout, x, eps_aux, eps_samp, u_acc, accepted, logs);
-    } else {
-        rc = dtype == AUXSSM_F32 ? sweep_lg_concat<float>(h, dtype, dims, model, yobs, delta, dptr, keys, parallel, nan_policy, layout, x, eps_aux, eps_samp, u_acc, accepted, logs)
-                                 : sweep_lg_concat<double>(h, dtype, dims, model, yobs, delta, dptr, keys, parallel, nan_policy, layout, x, eps_aux, eps_samp, u_acc, accepted, logs);
-    }
-    return rc;
+    if ((rc = check_sweep_common(false, dims, delta, delta_dev != nullptr, nan_policy, layout, yobs && yobs->ptr && x && eps_aux && eps_samp && u_acc && accepted, model,
+                                 yobs, !sv)))
+        return rc;
+    const double* dptr;
+    if ((rc = delta_block(h, dtype, delta_dev, &dptr))) return rc;
+    SweepCall c{h, dtype, dims, model, yobs, delta, dptr, keys, parallel, nan_policy, layout, x, eps_aux, eps_samp, u_acc, accepted, logs};
+    if (keys && (lorenz || sv))  // these sweeps read the noise from the arrays: draw all of it first (auxssm_kalman_draw)
+        by_dtype(dtype, [&](auto r) {
+            launch_rng_sweep<decltype(r)>(h, keys, (long long)dims->C * dims->T * dims->dx, dims->C, const_cast<void*>(eps_aux), const_cast<void*>(eps_samp),
+                                          const_cast<void*>(u_acc));
+            return AUXSSM_OK;
+        });
+    if (sv) c.order = model_kind == AUXSSM_KMODEL_SV_FIRST ? 1 : 2;
+    return by_dtype(dtype, [&](auto r) {
+        using R = decltype(r);
+        return lorenz ? sweep_lorenz<R>(c) : sv ? sweep_sv<R>(c) : sweep_lg_concat<R>(c);
+    });
 }
 
 int auxssm_kalman_sweep(auxssm_handle h, int dtype, int model_kind, const auxssm_dims* dims, const auxssm_lgssm* model,
@@ -2003,29 +1948,18 @@ int auxssm_kalman_sweep_fused(auxssm_handle h, int dtype, int model_kind, const 
         return AUXSSM_ERR_UNSUPPORTED;
     }
     if ((rc = check_lgssm(model, dims->T))) return rc;
-    if (dims->B != 1 || !(delta_dev || delta > 0) || !keys || !yobs || !yobs->ptr || !x || !x_alt || !u_acc || !accepted ||
-        (nan_policy != AUXSSM_NAN_REFERENCE && nan_policy != AUXSSM_NAN_MASKED)) {
-        set_error("auxssm_kalman_sweep_fused: B must be 1, delta > 0 (or delta_dev), keys / yobs / x / x_alt / u_acc / accepted non-NULL, nan_policy 0 or 1");
-        return AUXSSM_ERR_ARG;
-    }
-    if (yobs->sc != 0 || model->Hs.sc != 0 || model->Rs.sc != 0 || model->cs.sc != 0) {
-        set_error("yobs and the observation model (Hs, Rs, cs) are shared by the chains of a sweep: their chain strides must be 0");
-        return AUXSSM_ERR_ARG;
-    }
+    if ((rc = check_sweep_common(true, dims, delta, delta_dev != nullptr, nan_policy, layout, keys && yobs && yobs->ptr && x && x_alt && u_acc && accepted, model, yobs, true)))
+        return rc;
     if (const char* why = fused_refusal(h, dims, model, parallel, layout)) {  // (nothing has been enqueued: the caller runs auxssm_kalman_sweep_keyed instead)
         set_error("auxssm_kalman_sweep_fused: %s", why);
         return AUXSSM_ERR_UNSUPPORTED;
     }
-    const double* dptr = nullptr;
-    if (delta_dev) {
-        if (!h->dblock) AX_HIP(hipMalloc((void**)&h->dblock, 2 * sizeof(double)));
-        if (dtype == AUXSSM_F32) hipLaunchKernelGGL((k_delta_block<float>), dim3(1), dim3(1), 0, h->stream, (const float*)delta_dev, h->dblock);
-        else hipLaunchKernelGGL((k_delta_block<double>), dim3(1), dim3(1), 0, h->stream, (const double*)delta_dev, h->dblock);
-        dptr = h->dblock;
-    }
-    const double dl = delta_dev ? 1.0 : delta;
-    return dtype == AUXSSM_F32 ? sweep_lg_concat_fused<float>(h, dtype, dims, model, yobs, dl, dptr, keys, nan_policy, x, x_alt, sel, u_acc, accepted, logs)
-                               : sweep_lg_concat_fused<double>(h, dtype, dims, model, yobs, dl, dptr, keys, nan_policy, x, x_alt, sel, u_acc, accepted, logs);
+    const double* dptr;
+    if ((rc = delta_block(h, dtype, delta_dev, &dptr))) return rc;
+    SweepCall c{h, dtype, dims, model, yobs, delta_dev ? 1.0 : delta, dptr, keys, parallel, nan_policy, layout, x, nullptr, nullptr, u_acc, accepted, logs};
+    c.x_alt = x_alt;
+    c.sel = sel;
+    return by_dtype(dtype, [&](auto r) { return sweep_lg_concat_fused<decltype(r)>(c); });
 }
 int auxssm_kalman_state_resolve(auxssm_handle h, int dtype, const auxssm_dims* dims, void* x, const void* x_alt, int32_t* sel) {
     AX_NEED_H(h);
@@ -2078,14 +2012,10 @@ int auxssm_kalman_draw(auxssm_handle h, int dtype, const uint32_t* keys, int64_t
         set_error("keys/eps_aux/eps_samp/u_acc must be non-NULL and n, nu >= 1");
         return AUXSSM_ERR_ARG;
     }
-    const unsigned g1 = (unsigned)(((n + 1) / 2 + 255) / 256), g2 = (unsigned)(((nu + 1) / 2 + 255) / 256);
-    ProfScope ps(h, AUXSSM_K_RNG);
-    if (dtype == AUXSSM_F32)
-        hipLaunchKernelGGL((k_rng_sweep<float>), dim3(2 * g1 + g2), dim3(256), 0, h->stream, keys[0], keys[1], keys[2], keys[3], keys[4], keys[5],
-                           (long long)n, (long long)nu, g1, (float*)eps_aux, (float*)eps_samp, (float*)u_acc);
-    else
-        hipLaunchKernelGGL((k_rng_sweep<double>), dim3(2 * g1 + g2), dim3(256), 0, h->stream, keys[0], keys[1], keys[2], keys[3], keys[4], keys[5],
-                           (long long)n, (long long)nu, g1, (double*)eps_aux, (double*)eps_samp, (double*)u_acc);
+    by_dtype(dtype, [&](auto r) {
+        launch_rng_sweep<decltype(r)>(h, keys, (long long)n, (long long)nu, eps_aux, eps_samp, u_acc);
+        return AUXSSM_OK;
+    });
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;
 }

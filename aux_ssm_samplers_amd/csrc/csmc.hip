@@ -15,7 +15,7 @@
 // the standalone primitives (normalize / multinomial / systematic) and the parallel-in-time sweep keep the Kogge-Stone-in-64 cumsum,
 // the balanced-tree-in-64 sum and the plain binary search of csmc_sweep.h.
 //
-// Host side: csmc_sweep_impl validates, batches the chains and lays out the workspace (csmc_host.h::WsPlan); run_csmc / run_csmc_program enqueue the shared
+// Host side: csmc_sweep_impl validates, batches the chains and lays out the workspace (ctx.h::WsPlan); run_csmc / run_csmc_program enqueue the shared
 // prologue (csmc_host.h::csmc_prologue) and then, batch by batch, the forward and the backward pass that fwd_kernel / bwd_kernel (a program's module:
 // fk_fwd_index / fk_bwd_index) pick for the model and nw_class(N).
 #include "csmc_host.h"

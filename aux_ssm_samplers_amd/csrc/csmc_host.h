@@ -1,8 +1,8 @@
 // csmc_host.h -- the host side the conditional-SMC drivers share (csmc.hip: the sequential sweep, built-in and user-defined models; csmc_wide.hip: the
 // wide-state sweep; pit.hip: the parallel-in-time sweep): the model checks of both entry points, the model in precision R, the one kernel launch helper
-// (launch), the workspace plan (WsPlan), the per-sweep prologue (csmc_prologue: transition constants, potential bound, auxiliary variables, gradient or guided
-// tables), chain batching and the dtype x dx dispatch.  hipcc only (the device side, csmc_sweep.h, also compiles under hipRTC).  Units including this are
-// compiled with -ffp-contract=off.
+// (launch), the per-sweep prologue (csmc_prologue: transition constants, potential bound, auxiliary variables, gradient or guided tables), chain batching and
+// the dtype x dx dispatch.  (The workspace plan the drivers fill, WsPlan, is ctx.h's.)  hipcc only (the device side, csmc_sweep.h, also compiles under
+// hipRTC).  Units including this are compiled with -ffp-contract=off.
 #pragma once
 #include <cstring>
 #include <type_traits>
@@ -21,43 +21,6 @@ template <typename... P, typename... A> static int launch(auxssm_ctx* h, void (*
     hipLaunchKernelGGL(kern, grid, block, lds, h->stream, std::forward<A>(args)...);
     return AUXSSM_OK;
 }
-
-// The workspace of one sweep, said once: add() registers a buffer with its byte count and the pointer that receives it, total() is what the registered buffers
-// occupy as ws_take lays them out (each on a 256-byte boundary, in the order of registration), reserve() sizes the handle's workspace to it and fills the
-// pointers.  Fixed capacity, no heap.
-struct WsPlan {
-    struct Entry {
-        size_t bytes;
-        void* slot;
-        void (*set)(void* slot, void* p);
-    };
-    static constexpr int CAP = 24;
-    Entry e[CAP];
-    int n = 0;
-    template <typename T> void add(T*& slot, size_t bytes) {
-        if (n < CAP) e[n] = Entry{bytes, &slot, [](void* s, void* p) { *(T**)s = (T*)p; }};
-        ++n;
-    }
-    void drop(int k) { n -= k; }  // the last k buffers are not wanted after all
-    size_t total() const {
-        size_t off = 0;
-        for (int i = 0; i < n && i < CAP; ++i) off = ((off + 255) & ~(size_t)255) + e[i].bytes;
-        return off;
-    }
-    int reserve(auxssm_ctx* h) const {
-        if (n > CAP) {
-            set_error("internal: workspace plan of %d buffers (capacity %d)", n, CAP);
-            return AUXSSM_ERR_ARG;
-        }
-        if (int rc = ws_reserve(h, total())) return rc;
-        for (int i = 0; i < n; ++i) {
-            void* p = ws_take(h, e[i].bytes);
-            if (!p) return AUXSSM_ERR_NOMEM;
-            e[i].set(e[i].slot, p);
-        }
-        return AUXSSM_OK;
-    }
-};
 
 // the model checks auxssm_csmc_sweep(_program) and auxssm_csmc_pit_sweep share; each entry point adds its own (proposals, dimensions, the explicit noise
 // arrays it reads).  user_potential: the potential is a program's, which brings its own observations

@@ -141,6 +141,46 @@ namespace ax {
 int ws_reserve(auxssm_ctx* h, size_t bytes);
 void* ws_take(auxssm_ctx* h, size_t bytes);
 
+// The workspace of one sweep, said once: add() registers a buffer with its byte count and the pointer that receives it, after() says how many bytes a callee
+// will take behind the registered buffers (the drivers reset the bump offset to their mark between callees, and still reserve the SUM of the callees' own
+// estimates), total() is what the registered buffers occupy as ws_take lays them out (each on a 256-byte boundary, in the order of registration) plus that tail,
+// reserve() sizes the handle's workspace to it and fills the pointers.  Fixed capacity, no heap.
+struct WsPlan {
+    struct Entry {
+        size_t bytes;
+        void* slot;
+        void (*set)(void* slot, void* p);
+    };
+    static constexpr int CAP = 24;
+    Entry e[CAP];
+    int n = 0;
+    size_t tail = 0;
+    template <typename T> void add(T*& slot, size_t bytes) {
+        if (n < CAP) e[n] = Entry{bytes, &slot, [](void* s, void* p) { *(T**)s = (T*)p; }};
+        ++n;
+    }
+    void drop(int k) { n -= k; }  // the last k buffers are not wanted after all
+    void after(size_t bytes) { tail += bytes + 256; }  // (+ the alignment of the callee's first take)
+    size_t total() const {
+        size_t off = 0;
+        for (int i = 0; i < n && i < CAP; ++i) off = ((off + 255) & ~(size_t)255) + e[i].bytes;
+        return off + tail;
+    }
+    int reserve(auxssm_ctx* h) const {
+        if (n > CAP) {
+            set_error("internal: workspace plan of %d buffers (capacity %d)", n, CAP);
+            return AUXSSM_ERR_ARG;
+        }
+        if (int rc = ws_reserve(h, total())) return rc;
+        for (int i = 0; i < n; ++i) {
+            void* p = ws_take(h, e[i].bytes);
+            if (!p) return AUXSSM_ERR_NOMEM;
+            e[i].set(e[i].slot, p);
+        }
+        return AUXSSM_OK;
+    }
+};
+
 // model stage on the side stream (see auxssm_ctx::SideStage).  side_open: next parity, slab of at least `need` bytes, the side stream waits for the
 // last sweep that read it; SideScope: launches and ws_take inside the scope go to the side stream / slab (no-op unless a stage is open);
 // side_close: `stream` waits for the stage; side_sweep_end: marks the end of the sweep that consumed it.
@@ -166,6 +206,12 @@ struct SideScope {
         h->stream = s.m_stream; h->ws = s.m_ws; h->ws_bytes = s.m_bytes; h->ws_off = s.m_off;
         s.inside = false;
     }
+};
+
+// whatever way a sweep returns: everything it enqueued on `stream` precedes the mark the next stage of this parity waits for
+struct SweepEnd {
+    auxssm_ctx* h;
+    ~SweepEnd() { side_sweep_end(h); }
 };
 
 struct ProfScope {
