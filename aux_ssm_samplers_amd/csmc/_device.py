@@ -7,11 +7,12 @@ import numpy as np
 
 from .. import _lib, random as _random
 from .models import (GaussianInit, LinearGaussianDynamics, FlatPotential, GaussianObsPotential, SVPotential, Lorenz63Dynamics,
-                     MaskedGaussianObsPotential, MultivariateTPotential, DevicePotential, DeviceGaussianDynamics)
+                     MaskedGaussianObsPotential, MultivariateTPotential, LinearGaussianPotential, DevicePotential,
+                     DeviceGaussianDynamics)
 
 _UNSUPPORTED = ("{what} is a Python object the HIP kernels cannot evaluate. The cSMC kernels run the closed model family "
                 "of aux_ssm_samplers_amd.csmc.models (GaussianInit, LinearGaussianDynamics, Lorenz63Dynamics, FlatPotential, "
-                "GaussianObsPotential, MaskedGaussianObsPotential, SVPotential, MultivariateTPotential) in-kernel; there is no CPU fallback.")
+                "GaussianObsPotential, MaskedGaussianObsPotential, SVPotential, MultivariateTPotential, LinearGaussianPotential) in-kernel; there is no CPU fallback.")
 
 
 class FkDesc:
@@ -37,6 +38,12 @@ class FkDesc:
         self._tvdev = {}
         self.user = None  # UserModel: the parts of the model compiled from device code (auxssm_csmc_sweep_program)
         self.nu, self.prec = 0.0, None  # POT_MVT: degrees of freedom and the (dx, dx) precision matrix (host, like F)
+        self.obs_H, self.obs_const = None, 0.0  # POT_LIN_GAUSS: the whitened observation matrix, zero-padded to (dx, dx), and c_lin (self.y: the whitened rows)
+
+    def set_lingauss(self, Hw, c_lin):
+        self.obs_H = np.ascontiguousarray(Hw, np.float64).reshape(self.dx, self.dx)
+        self.obs_const = float(c_lin)
+        return self
 
     def set_mvt(self, nu, prec):
         self.nu = float(nu)
@@ -57,9 +64,10 @@ class FkDesc:
 
     def struct(self, handle, dtype, T):
         """the auxssm_fk_model of this description on `handle` (keeps the device arrays alive through self)"""
-        m = _lib.FkModel(self.proposal, self.potential, self.dx, self.transition, self.m0.ctypes.data, self.chol_P0.ctypes.data,
+        m = _lib.FkModelObs(self.proposal, self.potential, self.dx, self.transition, self.m0.ctypes.data, self.chol_P0.ctypes.data,
                          self.F.ctypes.data, self.b.ctypes.data, self.chol_Q.ctypes.data, None, self.sig_y, None, None, None, self.gradient, 0,
-                         self.nu, None if self.prec is None else self.prec.ctypes.data)
+                         self.nu, None if self.prec is None else self.prec.ctypes.data,
+                         None if self.obs_H is None else self.obs_H.ctypes.data, self.obs_const)
         yd = self.ydev(handle, dtype)
         if yd is not None:
             if yd.shape[0] != T:
@@ -93,6 +101,16 @@ def _potential(G0, Gt, d):
         if Gt.dx != d:
             raise ValueError(f"the potential's precision matrix is {Gt.dx} x {Gt.dx}, the state has dimension {d}")
         return _lib.POT_MVT, np.concatenate([np.reshape(G0.y, (1, d)), np.reshape(Gt.params, (-1, d))], axis=0), 1.0
+    if isinstance(Gt, LinearGaussianPotential):
+        if G0.y is None or Gt.params is None:
+            raise ValueError("the potential needs y (G0.y = ys[0]) and params (Gt.params = ys[1:])")
+        if not (np.array_equal(G0.H, Gt.H) and np.array_equal(G0.R, Gt.R) and np.array_equal(G0.c, Gt.c)):
+            raise ValueError("G0 and Gt must carry the same H, R and c")
+        if Gt.dx != d:
+            raise ValueError(f"the potential's observation matrix has {Gt.dx} columns, the state has dimension {d}")
+        # the device's observation array is the whitened rows yw (T, dx); _mvt puts Hw and c_lin into the description
+        ys = np.concatenate([np.reshape(G0.y, (1, Gt.dy)), np.reshape(Gt.params, (-1, Gt.dy))], axis=0)
+        return _lib.POT_LIN_GAUSS, Gt.whitened(ys)[1], 1.0
     if isinstance(Gt, MaskedGaussianObsPotential):
         if G0.y is None or Gt.params is None:
             raise ValueError("the potential needs y (G0.y = ys[0]) and params (Gt.params = ys[1:])")
@@ -117,7 +135,10 @@ def _potential(G0, Gt, d):
 
 
 def _mvt(fk, Gt):
-    """the multivariate-t potential's own parameters into the description (every other potential: nothing)"""
+    """the own parameters of the multivariate-t and the linear-Gaussian observation potential into the description (every other potential: nothing)"""
+    if isinstance(Gt, LinearGaussianPotential):  # whitened once, in float64, here at description time
+        Hw, _, c_lin = Gt.whitened(np.zeros((1, Gt.dy)))
+        return fk.set_lingauss(Hw, c_lin)
     return fk.set_mvt(Gt.nu, Gt.prec) if isinstance(Gt, MultivariateTPotential) else fk
 
 

@@ -1,6 +1,6 @@
 """Example models written as device code for DevicePotential / DeviceGaussianDynamics (csmc.models; contract in csrc/fk_user_pre.h).
 
-BUILTIN_*: the built-in potentials (Gaussian, stochastic volatility, multivariate Student-t) / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc_host.h::k_csmc_potbound written as user source, in the
+BUILTIN_*: the built-in potentials (Gaussian, stochastic volatility, multivariate Student-t, linear-Gaussian observation) / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc_host.h::k_csmc_potbound written as user source, in the
 built-in operation order (fma_, det_exp, det_log), so that a program sweep reproduces the closed-family sweep bit for bit (the tests and
 tools/fk_program_bench.py use them).  The constants the host computes for the built-ins (csmc_host.h::fk_model) are formed the same way on
 the device from theta = [sig].  RARE_EVENT, STUDENT_T, GROWTH: models the closed family cannot express.
@@ -80,6 +80,32 @@ template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xpre
 template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta) { return (R)0; }
 """
 
+# linear-Gaussian observation y ~ N(H x + c, R) in the whitened residual form (AUXSSM_POT_LIN_GAUSS): theta = [c_lin | Hw (D x D, row-major, rows beyond dy zero)],
+# observations = the whitened rows yw (T, D); csrc/csmc_sweep.h::lin_resid / lin_value in their order; the bound of k_csmc_potbound (c_lin, 0 on a NaN row)
+BUILTIN_LINGAUSS = r"""
+template <typename R, int D> __device__ R lin_q_(const R* x, const R* y, const R* theta, R* z) {
+    const R* H = theta + 1;
+    for (int k = 0; k < D; ++k) {
+        R acc = 0;
+        for (int j = 0; j < D; ++j) acc = fma_(H[k * D + j], x[j], acc);
+        z[k] = y[k] - acc;
+    }
+    R q = 0;
+    for (int k = 0; k < D; ++k) q = fma_(z[k], z[k], q);
+    return q;
+}
+template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta) {
+    R z[D];
+    const R v = fma_((R)-0.5, lin_q_<R, D>(x, y, theta, z), theta[0]);
+    return (v == v) ? v : (R)0;
+}
+template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta) {
+    bool obs = true;
+    for (int k = 0; k < D; ++k) obs = obs && (y[k] - y[k] == 0);
+    return obs ? theta[0] : (R)0;
+}
+"""
+
 # mean F x + b: theta = [F (D x D, row-major) | b (D)]
 BUILTIN_LINEAR_MEAN = r"""
 template <typename R, int D> __device__ void mean(int t, const R* xprev, const R* theta, R* mu) {
@@ -151,6 +177,20 @@ template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const
     const R s = mvt_s_<R, D>(x, y, theta, z);
     const R c = -((hc + hc) * inv_nu) / s;
     for (int k = 0; k < D; ++k) gx[k] = (s == s) ? c * z[k] : (R)0;
+}
+"""
+
+# d/dx log g = Hw^T z with z = yw - Hw x (component j: fma over k ascending); every component 0 where the value is NaN (csrc/csmc_sweep.h::lin_grad)
+BUILTIN_LINGAUSS_GRAD = BUILTIN_LINGAUSS + r"""
+template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
+    R z[D];
+    const R* H = theta + 1;
+    const R v = fma_((R)-0.5, lin_q_<R, D>(x, y, theta, z), theta[0]);
+    for (int j = 0; j < D; ++j) {
+        R acc = 0;
+        for (int k = 0; k < D; ++k) acc = fma_(H[k * D + j], z[k], acc);
+        gx[j] = (v == v) ? acc : (R)0;
+    }
 }
 """
 

@@ -141,6 +141,89 @@ class MultivariateTPotential(UnivariatePotential, Potential):
         return np.where(np.isnan(v), 0.0, v)
 
 
+@dataclass
+class LinearGaussianPotential(UnivariatePotential, Potential):
+    """The linear-Gaussian observation y_t ~ N(H x_t + c, R):
+        log g_t(x) = log N(y_t; H x + c, R),   the whole value 0 when it is NaN
+    (a NaN anywhere in y_t makes the step flat: a step is observed whole or not at all).  H is (dy, dx) with 1 <= dy <= dx <= 32, R (dy, dy) symmetric
+    positive definite, c (dy,) with default 0.  As G0 give y = ys[0]; as Gt give params = ys[1:]; both carry the same H, R and c.  Validated here, without a
+    GPU: shapes, finiteness, R symmetric to 1e-12 relative and positive definite -- anything else raises ValueError; dy > dx raises NotImplementedError.
+    The device evaluates the whitened residual form c_lin - |yw_t - Hw x|^2 / 2 (whitened(): Hw = L^-1 H, yw = L^-1 (y - c), L = chol R, formed once in float64)."""
+    H: Any = None
+    R: Any = None
+    c: Optional[Any] = None
+    y: Optional[Any] = None
+    params: Optional[Any] = None
+
+    def __post_init__(self):
+        name = "LinearGaussianPotential"
+        if self.H is None or self.R is None:
+            raise ValueError(f"{name}: H (the observation matrix) and R (the observation covariance) are required")
+        H = np.asarray(self.H, np.float64)
+        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
+            raise ValueError(f"{name}: H must be a (dy, dx) matrix (got shape {np.shape(self.H)})")
+        dy, dx = H.shape
+        if dx > 32:
+            raise ValueError(f"{name}: dx = {dx}: the cSMC kernels cover dx <= 32")
+        if dy > dx:
+            raise NotImplementedError(f"{name}: dy = {dy} > dx = {dx}: the potential covers 1 <= dy <= dx (more observations than state components "
+                                      "would need a reduction to dx sufficient statistics per step, which is not done)")
+        Rm = np.asarray(self.R, np.float64)
+        if Rm.ndim == 0 and dy == 1:
+            Rm = Rm.reshape(1, 1)
+        if Rm.shape != (dy, dy):
+            raise ValueError(f"{name}: R must be ({dy}, {dy}) for H of shape {H.shape} (got shape {np.shape(self.R)})")
+        if not np.all(np.isfinite(H)):
+            raise ValueError(f"{name}: H must be finite")
+        if not np.all(np.isfinite(Rm)) or np.max(np.abs(Rm - Rm.T)) > 1e-12 * np.max(np.abs(Rm)):
+            raise ValueError(f"{name}: R must be finite and symmetric (to 1e-12 relative)")
+        Rm = 0.5 * (Rm + Rm.T)
+        try:
+            np.linalg.cholesky(Rm)
+        except np.linalg.LinAlgError:
+            raise ValueError(f"{name}: R must be positive definite") from None
+        c = np.zeros(dy) if self.c is None else np.asarray(self.c, np.float64)
+        if c.shape != (dy,) or not np.all(np.isfinite(c)):
+            raise ValueError(f"{name}: c must be a finite vector of shape ({dy},) (got shape {np.shape(self.c)})")
+        if self.y is not None and np.size(self.y) != dy:
+            raise ValueError(f"{name}: y has shape {np.shape(self.y)}, H has {dy} rows")
+        if self.params is not None and (np.shape(self.params)[-1] if np.ndim(self.params) >= 2 else (dy if dy == 1 else -1)) != dy:
+            raise ValueError(f"{name}: params has shape {np.shape(self.params)}, expected (T - 1, {dy})")
+        self.H, self.R, self.c = H, Rm, c
+
+    @property
+    def dx(self):
+        return self.H.shape[1]
+
+    @property
+    def dy(self):
+        return self.H.shape[0]
+
+    def whitened(self, ys):
+        """(Hw zero-padded to (dx, dx), yw zero-padded to (T, dx), c_lin) of the observations ys (T, dy): L = chol R, Hw = L^-1 H, yw_t = L^-1 (y_t - c),
+        c_lin = -sum_k log L_kk - (dy / 2) log 2 pi; a row of ys with any NaN becomes an all-NaN row of yw.  float64."""
+        dy, dx = self.H.shape
+        ys = np.asarray(ys, np.float64).reshape(-1, dy)
+        L = np.linalg.cholesky(self.R)
+        Hw = np.zeros((dx, dx))
+        Hw[:dy] = np.linalg.solve(L, self.H)
+        yw = np.zeros((ys.shape[0], dx))
+        miss = np.isnan(ys).any(axis=1)
+        yw[:, :dy] = np.linalg.solve(L, (np.where(miss[:, None], 0.0, ys) - self.c).T).T
+        yw[miss] = np.nan
+        c_lin = -float(np.sum(np.log(np.diag(L)))) - 0.5 * dy * float(np.log(2.0 * np.pi))
+        return Hw, yw, c_lin
+
+    def __call__(self, x, y):
+        """the NumPy formula (batched over the leading axes of x): solve + slogdet on the unwhitened residual, NaN -> 0"""
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        with np.errstate(invalid="ignore"):
+            r = y - (x @ self.H.T + self.c)
+            q = np.sum(r * np.linalg.solve(self.R, r[..., None])[..., 0], axis=-1)
+            v = -0.5 * q - 0.5 * np.linalg.slogdet(self.R)[1] - 0.5 * self.dy * np.log(2.0 * np.pi)
+        return np.where(np.isnan(v), 0.0, v)
+
+
 # ---- user-defined models: device code compiled when the kernel is built (csrc/fk_program.hip, include/auxssm.h auxssm_fk_program_compile) ----------
 @dataclass
 class DevicePotential(UnivariatePotential, Potential):

@@ -122,7 +122,8 @@ template <typename R, int D> static bool c3_shape(const FkDev<R>& m, const CsmcA
            m.transition == AUXSSM_TRANS_LINEAR && a.As == nullptr && a.noise_mode != AUXSSM_NOISE_EXPLICIT && !a.pregen;
 }
 
-// The forward pass of (model, sweep), nw = nw_class(N).  TV: time-varying transitions; GRAD: gradient-informed proposals; PM = FkBuiltin<R, D, true>.
+// The forward pass of (model, sweep), nw = nw_class(N).  TV: time-varying transitions; GRAD: gradient-informed proposals; PM = FkBuiltin<R, D, true>
+// (the linear-Gaussian observation potential: the same two rows with PM = FkBuiltin<R, D, false, true>).
 //   case                                 k_csmc_fwd<R, D, ...>
 //   multivariate-t potential, guided     <false, GRAD, 0, 2, PM>
 //   multivariate-t potential, otherwise  <TV, GRAD, 0, 0, PM>                  the generic workgroup for every N
@@ -138,6 +139,12 @@ template <typename R, int D> static SweepKernel<R> fwd_kernel(const FkDev<R>& m,
             if (guided) return k_csmc_fwd<R, D, false, GR, 0, 2, PM>;
             if (tv) return k_csmc_fwd<R, D, true, GR, 0, 0, PM>;
             return k_csmc_fwd<R, D, false, GR, 0, 0, PM>;
+        }
+        if (m.potential == AUXSSM_POT_LIN_GAUSS) {
+            using PL = FkBuiltin<R, D, false, true>;
+            if (guided) return k_csmc_fwd<R, D, false, GR, 0, 2, PL>;
+            if (tv) return k_csmc_fwd<R, D, true, GR, 0, 0, PL>;
+            return k_csmc_fwd<R, D, false, GR, 0, 0, PL>;
         }
         if (guided) {
             if (nw == 16) return k_csmc_fwd<R, D, false, GR, 16, 2>;
@@ -429,7 +436,9 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
     // (the guided weights are not bounded by gb + c_trans: no bound array, every step shifts by its exact maximum)
     // (nor do the wide kernels shift the multivariate-t potential's weights by its bound sup_x log g = 0: at dx > 4 the weights sit tens of nats below it -- (nu + dx) / 2
     // times a logarithm -- and fp32 weights exp(lw - bound) leave the normal range, which costs the resampling draws their precision long before every weight is zero)
-    const bool loose = wide && !ug && fk->potential == AUXSSM_POT_MVT;
+    // (the linear-Gaussian observation potential likewise: its bound c_lin is attained only where Hw x = yw_t, and at dx > 4 the particles' residuals leave the weights
+    // as far below it)
+    const bool loose = wide && !ug && (fk->potential == AUXSSM_POT_MVT || fk->potential == AUXSSM_POT_LIN_GAUSS);
     if (!guided && !loose && (ug ? prog->has_bound : (fk->potential == AUXSSM_POT_FLAT || fk->y != nullptr))) ws.add(a.gb, (size_t)T * sR);
     if (guided) ws.add(a.gtab, guided_tab_reals(T, D) * sR);  // K_t, chol Lambda_t and their constants, every step
     if (noise->mode == AUXSSM_NOISE_THREEFRY) ws.add(ub, CT * sR);  // the backward pass's uniforms, drawn once (csmc_sweep.h::k_csmc_ubwd)

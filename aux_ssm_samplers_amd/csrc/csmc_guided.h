@@ -128,8 +128,9 @@ template <typename R> __global__ void k_csmc_gshift(CsmcArgs a, int D, int poten
 }
 
 // the same for the multivariate Student-t potential (AUXSSM_POT_MVT), whose gradient couples the components: one thread per (chain, t), the operations of
-// csmc_sweep.h::mvt_quad / mvt_grad_coef in their order with a runtime dimension (M: FkDev or csmc_wide.hip's FkW)
-template <typename R, typename M> __global__ void k_csmc_gshift_mvt(CsmcArgs a, M m) {
+// csmc_sweep.h::mvt_quad / mvt_grad_coef in their order with a runtime dimension (M: FkDev or csmc_wide.hip's FkW).  LG: the other coupled potential, the
+// linear-Gaussian observation potential (AUXSSM_POT_LIN_GAUSS: csmc_sweep.h::lin_resid / lin_raw / lin_grad in their order, the matrix in the same storage)
+template <typename R, typename M, bool LG = false> __global__ void k_csmc_gshift_mvt(CsmcArgs a, M m) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)a.C * a.T) return;
     const int D = m.D;
@@ -138,6 +139,22 @@ template <typename R, typename M> __global__ void k_csmc_gshift_mvt(CsmcArgs a, 
     const R* y = (const R*)a.y + t * D;
     const R s = ((const R*)a.shd)[t];
     R r[GT_MAXD], z[GT_MAXD];
+    if constexpr (LG) {
+        for (int k = 0; k < D; ++k) {
+            R acc = 0;
+            for (int j = 0; j < D; ++j) acc = fma_(mvt_prec(m, k, j), u[j], acc);
+            z[k] = y[k] - acc;
+        }
+        R q = 0;
+        for (int k = 0; k < D; ++k) q = fma_(z[k], z[k], q);
+        const R v = lin_raw<R>(m.c_obs, q);
+        for (int j = 0; j < D; ++j) {
+            R acc = 0;
+            for (int k = 0; k < D; ++k) acc = fma_(mvt_prec(m, k, j), z[k], acc);
+            ((R*)a.grad)[g * D + j] = fma_(s * s, (v == v) ? acc : (R)0, u[j]);
+        }
+        return;
+    }
     for (int k = 0; k < D; ++k) r[k] = u[k] - y[k];
     R q = 0;
     for (int k = 0; k < D; ++k) {

@@ -25,7 +25,7 @@ template <typename... P, typename... A> static int launch(auxssm_ctx* h, void (*
 // the model checks auxssm_csmc_sweep(_program) and auxssm_csmc_pit_sweep share; each entry point adds its own (proposals, dimensions, the explicit noise
 // arrays it reads).  user_potential: the potential is a program's, which brings its own observations
 static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* noise, bool user_potential) {
-    if (fk->potential < AUXSSM_POT_FLAT || fk->potential > AUXSSM_POT_MVT) {
+    if (fk->potential < AUXSSM_POT_FLAT || fk->potential > AUXSSM_POT_LIN_GAUSS) {
         set_error("unknown potential kind %d", fk->potential);
         return AUXSSM_ERR_ARG;
     }
@@ -51,6 +51,10 @@ static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* no
             return AUXSSM_ERR_ARG;
         }
     }
+    if (fk->potential == AUXSSM_POT_LIN_GAUSS && !user_potential && !fk->obs_H) {
+        set_error("the linear-Gaussian observation potential needs its whitened observation matrix obs_H (host, dx x dx)");
+        return AUXSSM_ERR_ARG;
+    }
     const int ntv = (fk->F_t != nullptr) + (fk->b_t != nullptr) + (fk->chol_Q_t != nullptr);
     if (ntv != 0 && ntv != 3) {
         set_error("time-varying transitions need F_t, b_t and chol_Q_t together (device arrays with T - 1 rows)");
@@ -73,7 +77,8 @@ static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* no
 
 // The model of fk in precision R, as both kernel families read it: the parameters into m0 | LP0 | F | b | LQ (matrices row-major, leading dimension ld), the
 // reciprocal Cholesky diagonals into iLP0 / iLQ, the kinds, the gradient mode and the additive constants into m (FkDev<R>, or csmc_wide.hip's FkW<R>).  The
-// constants are computed once, here, in precision R: they enter both the GPU and the oracle as data.  prec (AUXSSM_POT_MVT): where the precision matrix goes.
+// constants are computed once, here, in precision R: they enter both the GPU and the oracle as data.  prec: where the precision matrix (AUXSSM_POT_MVT) or the
+// whitened observation matrix (AUXSSM_POT_LIN_GAUSS, with c_lin in c_obs) goes.
 template <typename R, typename M>
 static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* iLP0, R* F, R* b, R* LQ, R* iLQ, R* prec) {
     const int D = fk->dx;
@@ -104,6 +109,11 @@ static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* 
     } else if (fk->potential == AUXSSM_POT_GAUSS_OBS_MASKED) {  // per observed component
         m.inv_sig_y = (R)1 / (R)fk->sig_y;
         m.c_obs = -det_log((R)fk->sig_y) - half_log_2pi;
+    } else if (fk->potential == AUXSSM_POT_LIN_GAUSS) {  // c_lin, formed on the host in double with the whitening
+        m.inv_sig_y = 0;
+        m.c_obs = (R)fk->obs_const;
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j) prec[i * ld + j] = (R)fk->obs_H[i * D + j];
     } else {
         m.inv_sig_y = 0;
         m.c_obs = -half_log_2pi;
@@ -159,6 +169,10 @@ template <typename R> __global__ void k_csmc_potbound(int T, int D, int potentia
         int nobs = 0;
         for (int k = 0; k < D; ++k) nobs += (y[(long long)t * D + k] - y[(long long)t * D + k] == 0) ? 1 : 0;
         b = (R)nobs * c_obs;
+    } else if (potential == AUXSSM_POT_LIN_GAUSS) {  // c_lin - |yw - Hw x|^2 / 2 <= c_lin; a missing row (all NaN) makes the step flat
+        bool obs = true;
+        for (int k = 0; k < D; ++k) obs = obs && (y[(long long)t * D + k] - y[(long long)t * D + k] == 0);
+        b = obs ? c_obs : (R)0;
     } else if (potential == AUXSSM_POT_SV) {  // sum_k [c_obs - (x + y^2 e^-x) / 2] <= sum_k max(0, c_obs - (1 + log y^2) / 2)  (a NaN term counts 0)
         for (int k = 0; k < D; ++k) {
             const R yk = y[(long long)t * D + k], y2 = yk * yk;
@@ -177,7 +191,10 @@ template <typename R, typename M> static void fk_potbound(auxssm_ctx* h, const C
 // of the T steps into a.gtab ((2 D D + D + 4) reals per step: guided_tab_reals).  Rebuilt at every sweep: delta may change between sweeps.
 static size_t guided_tab_reals(int T, int D) { return (size_t)T * ((size_t)2 * D * D + D + 4); }
 template <typename R, typename M> static void fk_guided(auxssm_ctx* h, const CsmcArgs& a, const M& m) {
-    if (m.gradient && m.potential == AUXSSM_POT_MVT) {
+    if (m.gradient && m.potential == AUXSSM_POT_LIN_GAUSS) {
+        const long long total = (long long)a.C * a.T;
+        hipLaunchKernelGGL((k_csmc_gshift_mvt<R, M, true>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, h->stream, a, m);
+    } else if (m.gradient && m.potential == AUXSSM_POT_MVT) {
         const long long total = (long long)a.C * a.T;
         hipLaunchKernelGGL((k_csmc_gshift_mvt<R, M>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, h->stream, a, m);
     } else if (m.gradient) {
@@ -190,7 +207,8 @@ template <typename R, typename M> static void fk_guided(auxssm_ctx* h, const Csm
 // the gradient launch of the built-in family on the register kernels (csmc.hip::run_csmc, pit.hip::run_pit)
 template <typename R, int D> static int builtin_grad(auxssm_ctx* h, const CsmcArgs& a, const FkDev<R>& m) {
     const dim3 grid((unsigned)(((long long)a.C * a.T + 255) / 256));
-    if (m.potential == AUXSSM_POT_MVT) hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, true>>), grid, dim3(256), 0, h->stream, a, m);
+    if (m.potential == AUXSSM_POT_LIN_GAUSS) hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, false, true>>), grid, dim3(256), 0, h->stream, a, m);
+    else if (m.potential == AUXSSM_POT_MVT) hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, true>>), grid, dim3(256), 0, h->stream, a, m);
     else hipLaunchKernelGGL((k_csmc_grad<R, D>), grid, dim3(256), 0, h->stream, a, m);
     return AUXSSM_OK;
 }

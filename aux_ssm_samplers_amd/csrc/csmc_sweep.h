@@ -25,6 +25,8 @@ template <typename R> struct FkDev {
     const R* idt;  // (T-1, D) reciprocal diagonals of LQt (k_csmc_ctrans)
     int gradient;  // AUXSSM_GRAD_*
     // AUXSSM_POT_MVT (potential == 4): the precision matrix (leading dimension CS_MAXD) and the two constants (nu + D) / 2 and 1 / nu, formed on the host in R
+    // AUXSSM_POT_LIN_GAUSS (potential == 5) shares the storage -- one potential is live per model: prec holds the whitened observation matrix Hw (rows beyond dy
+    // zero), c_obs the constant c_lin
     R prec[CS_MAXD * CS_MAXD];
     R mvt_hc, mvt_inv_nu;
 };
@@ -215,11 +217,46 @@ template <typename R> AXD_HD R mvt_value(R hc, R s) {
 // the gradient: component k is c z_k with c = -(nu + D) / nu / s = -(nu + D) / (nu + q), and 0 where s is NaN (a missing observation: the step is flat)
 template <typename R> AXD_HD R mvt_grad_coef(R hc, R inv_nu, R s) { return -((hc + hc) * inv_nu) / s; }
 template <typename R> AXD_HD R mvt_grad_term(R c, R s, R zk) { return (s == s) ? c * zk : (R)0; }
+// The linear-Gaussian observation potential (AUXSSM_POT_LIN_GAUSS): log N(y_t; H x + c, R) whitened on the host into c_lin - |yw_t - Hw x|^2 / 2, the ONE definition
+// every kernel family uses.  a_k = row k of Hw times x (fma over j ascending from 0);  z_k = yw_k - a_k;  q = sum_k fma(z_k, z_k, .) (k ascending from 0).
+// lin_resid leaves z and returns q; the value is c_lin - q / 2 with NaN -> 0 (a missing observation row is all NaN), the gradient Hw^T z (component j: fma over k
+// ascending from 0), every component 0 where the value is NaN.  Hw is dx x dx with zero rows beyond dy and yw zero beyond dy: those components add fma(0, 0, .).
+template <typename R, int D> AXD_HD R lin_resid(const R* H, int ld, const R* x, const R* y, R* z) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        R acc = 0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) acc = fma_(H[k * ld + j], x[j], acc);
+        z[k] = y[k] - acc;
+    }
+    R q = 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) q = fma_(z[k], z[k], q);
+    return q;
+}
+template <typename R> AXD_HD R lin_raw(R c_lin, R q) { return fma_((R)-0.5, q, c_lin); }  // (q / 2 is exact: this is c_lin - q / 2 rounded once)
+template <typename R> AXD_HD R lin_value(R c_lin, R q) {
+    const R v = lin_raw<R>(c_lin, q);
+    return (v == v) ? v : (R)0;
+}
+template <typename R, int D> AXD_HD void lin_grad(const R* H, int ld, R v, const R* z, R* gx) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        R acc = 0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) acc = fma_(H[k * ld + j], z[k], acc);
+        gx[j] = (v == v) ? acc : (R)0;
+    }
+}
 // potential g_t(x_t) (csmc test fixtures test_csmc/common.py:52-75; SV examples/stochastic_volatility/auxiliary_csmc.py:40-46)
 // MV: the multivariate-t potential, chosen at COMPILE time -- as a fifth run-time branch it cost every forward instantiation of the other potentials twelve
 // registers in fp64 and a wave of occupancy, so the instantiations of the other potentials (MV = false) hold none of its code; potential_rt
-// below is the run-time choice for the callers that are not register-bound
-template <typename R, int D, bool MV = false> AXD_HD R potential(const FkDev<R>& m, const R* x, const R* y) {
+// below is the run-time choice for the callers that are not register-bound.  LG: the linear-Gaussian observation potential, a compile-time variant in the same way
+template <typename R, int D, bool MV = false, bool LG = false> AXD_HD R potential(const FkDev<R>& m, const R* x, const R* y) {
+    if constexpr (LG) {
+        R z[D];
+        return lin_value<R>(m.c_obs, lin_resid<R, D>(m.prec, CS_MAXD, x, y, z));
+    }
     if constexpr (MV) {
         R z[D];
         return mvt_value<R>(m.mvt_hc, mvt_quad<R, D>(m.prec, CS_MAXD, m.mvt_inv_nu, x, y, z));
@@ -259,7 +296,13 @@ template <typename R, int D, bool MV = false> AXD_HD R potential(const FkDev<R>&
     return acc;
 }
 // gx = d potential / dx at x (the closed family's potentials do not read x_{t-1}); y = the D reals of row t, or nullptr
-template <typename R, int D, bool MV = false> __device__ __forceinline__ void potential_grad(const FkDev<R>& m, const R* x, const R* y, R* gx) {
+template <typename R, int D, bool MV = false, bool LG = false> __device__ __forceinline__ void potential_grad(const FkDev<R>& m, const R* x, const R* y, R* gx) {
+    if constexpr (LG) {  // (couples the components through Hw)
+        R z[D];
+        const R q = lin_resid<R, D>(m.prec, CS_MAXD, x, y, z);
+        lin_grad<R, D>(m.prec, CS_MAXD, lin_raw<R>(m.c_obs, q), z, gx);
+        return;
+    }
     if constexpr (MV) {  // (the one potential that couples the components)
         R z[D];
         const R s = mvt_quad<R, D>(m.prec, CS_MAXD, m.mvt_inv_nu, x, y, z), c = mvt_grad_coef<R>(m.mvt_hc, m.mvt_inv_nu, s);
@@ -280,13 +323,15 @@ template <typename R, int D, bool MV = false> __device__ __forceinline__ void po
         gx[k] = v;
     }
 }
-// the potential kind of m at run time, the multivariate-t potential included (the parallel-in-time kernels, a user program that keeps the built-in potential)
+// the potential kind of m at run time, the multivariate-t and the linear-Gaussian observation potential included (the parallel-in-time kernels, a user program that keeps the built-in potential)
 template <typename R, int D> __device__ __forceinline__ R potential_rt(const FkDev<R>& m, const R* x, const R* y) {
     if (m.potential == 4) return potential<R, D, true>(m, x, y);
+    if (m.potential == 5) return potential<R, D, false, true>(m, x, y);
     return potential<R, D, false>(m, x, y);
 }
 template <typename R, int D> __device__ __forceinline__ void potential_grad_rt(const FkDev<R>& m, const R* x, const R* y, R* gx) {
     if (m.potential == 4) potential_grad<R, D, true>(m, x, y, gx);
+    else if (m.potential == 5) potential_grad<R, D, false, true>(m, x, y, gx);
     else potential_grad<R, D, false>(m, x, y, gx);
 }
 // out = J^T v, J = d mean / d xp of the transition tr (trans_mean_t): F^T, or the Lorenz-63 step's I + dt dphi/dx (examples/lorenz/model.py:10-25)
@@ -658,13 +703,13 @@ template <typename R> struct FkUser {
 //   pol.mean_vjp(m, tr, t, xprev, v, out)           out = J^T v, J = d pol.mean(m, tr, t, xprev) / d xprev
 //   P::grad_xprev                                   whether log G_t may depend on xprev (false: k_csmc_grad adds no d / dxprev term)
 // FkBuiltin is the closed family of include/auxssm.h, dispatched on the integers of FkDev (the kernels of csmc.hip), FkBuiltin<R, D, true> the same with the
-// multivariate-t potential fixed at compile time (potential<R, D, MV> above); fk_user.h's FkUserPolicy calls
+// multivariate-t potential fixed at compile time (potential<R, D, MV> above), FkBuiltin<R, D, false, true> with the linear-Gaussian observation potential; fk_user.h's FkUserPolicy calls
 // device functions of a user's source (fk_program.hip).  The backward pass evaluates the Gaussian transition density around pol.mean.
-template <typename R, int D, bool MV = false> struct FkBuiltin {
+template <typename R, int D, bool MV = false, bool LG = false> struct FkBuiltin {
     static constexpr bool grad_xprev = false;
-    __device__ __forceinline__ R log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y) const { return potential<R, D, MV>(m, x, y); }
+    __device__ __forceinline__ R log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y) const { return potential<R, D, MV, LG>(m, x, y); }
     __device__ __forceinline__ void mean(const FkDev<R>& m, const TransT<R>& tr, int, const R* xp, R* mu) const { trans_mean_t<R, D>(m, tr, xp, mu); }
-    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y, R* gx, R*) const { potential_grad<R, D, MV>(m, x, y, gx); }
+    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y, R* gx, R*) const { potential_grad<R, D, MV, LG>(m, x, y, gx); }
     __device__ __forceinline__ void mean_vjp(const FkDev<R>& m, const TransT<R>& tr, int, const R* xp, const R* v, R* out) const {
         trans_mean_vjp_t<R, D>(m, tr, xp, v, out);
     }

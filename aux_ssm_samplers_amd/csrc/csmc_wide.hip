@@ -12,6 +12,8 @@
 // into LDS like a time-varying transition, one more row product and one more blocked log-density per particle; the backward kernel is shared.
 // The multivariate-t potential (AUXSSM_POT_MVT, csmc_sweep.h::mvt_quad) is a compile-time variant in the same way (k_cw2_fwd<R, NW2, GD, true>): its precision matrix staged
 // once per workgroup, one more row product per particle (mvt_half); its sweeps carry no bound array (csmc.hip), every step shifts by its exact maximum.
+// The linear-Gaussian observation potential (AUXSSM_POT_LIN_GAUSS, csmc_sweep.h::lin_resid) is the next such variant (k_cw2_fwd<R, NW2, GD, false, true>): its whitened
+// observation matrix in the precision matrix's LDS slot and layout, the same row product (lin_half), no bound array either.
 // (The first version of this file -- one wave per chain, one lane per particle walking its dx x dx products alone: 30.5 ms per sweep of the SV protocol against
 // 2.6 now -- is in the history)
 //
@@ -33,7 +35,8 @@ template <typename R> struct FkW {
     R c_init, c_trans, c_obs, inv_sig_y;
     int gradient;                          // AUXSSM_GRAD_*
     const R *Ft, *bt, *LQt, *ctt, *idt;    // time-varying transitions (csmc_sweep.h::FkDev: row t = transition t -> t + 1), or null
-    const R* prec;                         // AUXSSM_POT_MVT: the precision matrix (device, leading dimension D) and the constants (nu + D) / 2, 1 / nu
+    const R* prec;                         // AUXSSM_POT_MVT: the precision matrix (device, leading dimension D) and the constants (nu + D) / 2, 1 / nu;
+                                           // AUXSSM_POT_LIN_GAUSS: the whitened observation matrix Hw (rows beyond dy zero), c_lin in c_obs
     R mvt_hc, mvt_inv_nu;
 };
 // the transition t -> t + 1 in global memory (gradient kernel; the sweep kernels read it from LDS)
@@ -85,7 +88,8 @@ template <typename R> __device__ __forceinline__ void cho_solve_w(int D, const R
 // the gradient of the model's joint log-density at u (csmc_sweep.h::k_csmc_grad, same operations in the same order; one thread per (chain, time step):
 // C T threads of O(dx^2) work, once per sweep -- 0.5 M multiply-adds at the SV protocol's size)
 // MV: the multivariate-t potential's gradient (a compile-time variant: its z[32] would otherwise add scratch to the kernel of the other potentials)
-template <typename R, bool MV = false> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
+// LG: the linear-Gaussian observation potential's gradient Hw^T (yw - Hw u), a compile-time variant for the same reason
+template <typename R, bool MV = false, bool LG = false> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)a.C * a.T) return;
     const int D = m.D;
@@ -93,7 +97,22 @@ template <typename R, bool MV = false> __global__ void k_cw_grad(CsmcArgs a, FkW
     const R* u = (const R*)a.u + g * D;
     R gr[CSW_MAXD], r[CSW_MAXD], w[CSW_MAXD];
     const R* yv = (const R*)a.y;
-    if constexpr (MV) {  // multivariate Student-t: csmc_sweep.h::potential_grad's branch (mvt_quad / mvt_grad_coef) with a runtime dimension
+    if constexpr (LG) {  // csmc_sweep.h::potential_grad's branch (lin_resid / lin_raw / lin_grad) with a runtime dimension
+        R z[CSW_MAXD];
+        for (int k = 0; k < D; ++k) {
+            R acc = 0;
+            for (int j = 0; j < D; ++j) acc = fma_(m.prec[k * D + j], u[j], acc);
+            z[k] = yv[t * D + k] - acc;
+        }
+        R q = 0;
+        for (int k = 0; k < D; ++k) q = fma_(z[k], z[k], q);
+        const R v = lin_raw<R>(m.c_obs, q);
+        for (int j = 0; j < D; ++j) {
+            R acc = 0;
+            for (int k = 0; k < D; ++k) acc = fma_(m.prec[k * D + j], z[k], acc);
+            gr[j] = (v == v) ? acc : (R)0;
+        }
+    } else if constexpr (MV) {  // multivariate Student-t: csmc_sweep.h::potential_grad's branch (mvt_quad / mvt_grad_coef) with a runtime dimension
         R z[CSW_MAXD];
         for (int k = 0; k < D; ++k) r[k] = u[k] - yv[t * D + k];
         R q = 0;
@@ -163,7 +182,8 @@ template <typename R> struct Cw2Lds {
     R *F, *LQ, *b, *iL, *c, *lwv, *xa, *xb, *eps, *blk;
     int* idx;
     R *Kg, *Lg, *blkg, *dv;  // guided proposals only (behind idx): the step's K_t and chol Lambda_t, the block table of chol Lambda_t, u~ - pred of every half-wave
-    R* Pm;                   // multivariate-t potential only (behind everything else): the precision matrix, rows zero-padded like F's
+    R* Pm;                   // multivariate-t potential only (behind everything else): the precision matrix, rows zero-padded like F's (the linear-Gaussian
+                             // observation potential: its whitened observation matrix in the same slot)
     __device__ Cw2Lds(char* smem, int D_, bool guided = false, bool mvt = false) : D(D_), S(CSW_MAXD + 1) {  // rows padded with zeros to 32 columns (+ 1: odd stride): every component loop runs 32 steps, unrolled
         F = (R*)smem;           // [D][S]
         LQ = F + D * S;         // [D][S]
@@ -381,6 +401,27 @@ template <typename R> __device__ __forceinline__ R mvt_half(int D, int k, R xk, 
     });
     return mvt_value<R>(hc, (R)1 + q * inv_nu);
 }
+// the linear-Gaussian observation potential of that particle (csmc_sweep.h::lin_resid / lin_value, same operations in the same order): a_k = row k of Hw (Hrow: this
+// lane's zero-padded LDS row) times x from half-wave broadcasts of x_j, j ascending; z_k = yw_k - a_k in the lane that owns component k; q accumulated in component
+// order by every lane alike from broadcasts of z_k.  Columns / components beyond D contribute fma(0, 0, acc) = acc.
+template <typename R> __device__ __forceinline__ R lin_half(int D, int k, R xk, R yk, const R* Hrow, R c_lin) {
+    const R x = k < D ? xk : (R)0;
+    R p[CSW_MAXD];
+#pragma unroll
+    for (int j = 0; j < CSW_MAXD; ++j) p[j] = Hrow[j];
+    R a = 0;
+    static_for<0, CSW_MAXD>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        a = fma_(p[j], half_bcast<R, j>(x), a);
+    });
+    const R z = k < D ? yk - a : (R)0;
+    R q = 0;
+    static_for<0, CSW_MAXD>([&](auto jc) {
+        const R zj = half_bcast<R, decltype(jc)::value>(z);
+        q = fma_(zj, zj, q);
+    });
+    return lin_value<R>(c_lin, q);
+}
 // sum_k log N(x_k; u_k, s^2) = c_u - sum_k ((x_k - u_k) / s)^2 / 2 of the particle whose component k this lane holds (csmc_sweep.h::guided_weight: component order)
 template <typename R> __device__ __forceinline__ R nu_half(int D, int k, R xk, R uk, R inv_s, R c_u) {
     const R z = k < D ? (xk - uk) * inv_s : (R)0;
@@ -420,14 +461,16 @@ template <typename R> __device__ __forceinline__ void cw2_draw(const CsmcArgs& a
 
 // GD: the guided proposals, a compile-time variant; false: the kernel as it was, holding none of their code
 // MV: the multivariate-t potential (AUXSSM_POT_MVT), a compile-time variant in the same way: the precision matrix staged in LDS, mvt_half in place of potential_half
-template <typename R, int NW2, bool GD = false, bool MV = false> __global__ void __launch_bounds__(64 * NW2) k_cw2_fwd(CsmcArgs a, FkW<R> m) {
+// LG: the linear-Gaussian observation potential (AUXSSM_POT_LIN_GAUSS), the same with its whitened observation matrix in that slot and lin_half
+template <typename R, int NW2, bool GD = false, bool MV = false, bool LG = false> __global__ void __launch_bounds__(64 * NW2) k_cw2_fwd(CsmcArgs a, FkW<R> m) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT_ = 64 * NW2;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, N = a.N, T = a.T, D = m.D;
     const bool hi = lane >= 32;
     const int k = lane & 31;
-    Cw2Lds<R> L(smem, D, GD, MV);
-    if constexpr (MV) cw2_stage_p<R>(m, L, tid, NT_);  // (published by cw2_stage's barrier)
+    static_assert(!(MV && LG), "one potential per kernel");
+    Cw2Lds<R> L(smem, D, GD, MV || LG);
+    if constexpr (MV || LG) cw2_stage_p<R>(m, L, tid, NT_);  // (published by cw2_stage's barrier)
     cw2_stage<R>(m, L, tid, NT_);
     const int S = L.S, nslot = (N + 2 * NW2 - 1) / (2 * NW2);
     const int ch = a.c0 + blockIdx.x;
@@ -450,7 +493,7 @@ template <typename R, int NW2, bool GD = false, bool MV = false> __global__ void
     const R* Kgrow = GD ? L.Kg + (k < D ? k : 0) * S : nullptr;
     const R* Lgrow = GD ? L.Lg + (k < D ? k : 0) * S : nullptr;
     R* dvr = GD ? L.dv + (2 * wv + (hi ? 1 : 0)) * S : nullptr;
-    const R* Prow = MV ? L.Pm + (k < D ? k : 0) * S : nullptr;
+    const R* Prow = (MV || LG) ? L.Pm + (k < D ? k : 0) * S : nullptr;
 
     // ---- t = 0 (csmc.py:74-80)
     cw2_draw<R>(a, L, ch, 0, tid, NT_);
@@ -490,7 +533,8 @@ template <typename R, int NW2, bool GD = false, bool MV = false> __global__ void
         }
         const R yk = (yv && k < D) ? yv[k] : (R)0;
         R g;
-        if constexpr (MV) g = mvt_half<R>(D, k, xk, yk, Prow, m.mvt_hc, m.mvt_inv_nu);
+        if constexpr (LG) g = lin_half<R>(D, k, xk, yk, Prow, m.c_obs);
+        else if constexpr (MV) g = mvt_half<R>(D, k, xk, yk, Prow, m.mvt_hc, m.mvt_inv_nu);
         else g = potential_half<R>(m, k, hi, xk, yk);
         if (m.proposal == 1) g = g + gauss_half<R>(D, k, hi, acc0, m.LP0 + (long long)(k < D ? k : 0) * D, k < D ? m.iLP0[k] : (R)0, m.c_init);  // AuxiliaryG0
         if constexpr (GD) {  // log g + log N(x; m0, P0) + sum_k log N(x_k; u_k, s^2) - log N(x; mu, Lambda_0)
@@ -595,7 +639,8 @@ template <typename R, int NW2, bool GD = false, bool MV = false> __global__ void
             }
             // weights (csmc.py:95-96)
             R g;
-            if constexpr (MV) g = mvt_half<R>(D, k, xk, yk, Prow, m.mvt_hc, m.mvt_inv_nu);
+            if constexpr (LG) g = lin_half<R>(D, k, xk, yk, Prow, m.c_obs);
+            else if constexpr (MV) g = mvt_half<R>(D, k, xk, yk, Prow, m.mvt_hc, m.mvt_inv_nu);
             else g = potential_half<R>(m, k, hi, xk, yk);
             if (m.proposal == 1) g = gauss_half_blk<R>(D, k, xk - mu, Lrow, L.blk, ctr) + g;  // AuxiliaryGt = Mt.logpdf + Gt (independent.py:238-248)
             // GradientAuxiliaryGt (:252-268): summed over the particles in the reference, i.e. a constant of the step (AUXSSM_GRAD_REFERENCE: nothing to add);
@@ -741,11 +786,17 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
 //   forward   guided                 k_cw2_fwd<R, 8, true, MV>                   eight waves whatever the chain count
 //             otherwise              k_cw2_fwd<R, wide16 ? 16 : 8, false, MV>
 //   backward                         k_cw2_bwd<R, wide16 ? 16 : 8>               the base LDS plan (Cw2Lds::bytes)
-// MV: the multivariate-t potential.  The forward pass's LDS is Cw2Lds::fwd_bytes(D, guided, mvt).
+// MV: the multivariate-t potential; the linear-Gaussian observation potential takes the same rows with <..., false, true> (pk: 0 neither, 1 MV, 2 LG).
+// The forward pass's LDS is Cw2Lds::fwd_bytes(D, guided, pk != 0): the two potentials' matrices share one slot, so neither plan exceeds the other's.
 // (guided: under the 128 registers of a 1024-lane workgroup the two extra row products and the second blocked density spill, 360 bytes per lane in fp32:
 // 7.47 ms against 5.11 ms per sweep of the SV protocol at 256 chains)
 template <typename R> using WideKernel = void (*)(CsmcArgs, FkW<R>);
-template <typename R> static WideKernel<R> cw_fwd_kernel(bool guided, bool mvt, bool wide16) {
+template <typename R> static WideKernel<R> cw_fwd_kernel(bool guided, int pk, bool wide16) {
+    if (pk == 2) {
+        if (guided) return k_cw2_fwd<R, 8, true, false, true>;
+        return wide16 ? k_cw2_fwd<R, 16, false, false, true> : k_cw2_fwd<R, 8, false, false, true>;
+    }
+    const bool mvt = pk == 1;
     if (guided) return mvt ? k_cw2_fwd<R, 8, true, true> : k_cw2_fwd<R, 8, true>;
     if (wide16) return mvt ? k_cw2_fwd<R, 16, false, true> : k_cw2_fwd<R, 16>;
     return mvt ? k_cw2_fwd<R, 8, false, true> : k_cw2_fwd<R, 8>;
@@ -757,8 +808,8 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     const int D = fk->dx;
     FkW<R> m;
     memset(&m, 0, sizeof(m));
-    const bool mvt = fk->potential == AUXSSM_POT_MVT;
-    std::vector<R> block((size_t)3 * D * D + 4 * D + (mvt ? (size_t)D * D : 0));  // (+ the multivariate-t potential's precision matrix)
+    const bool lg = fk->potential == AUXSSM_POT_LIN_GAUSS, mvt = fk->potential == AUXSSM_POT_MVT || lg;  // (mvt: a potential with a matrix in the block)
+    std::vector<R> block((size_t)3 * D * D + 4 * D + (mvt ? (size_t)D * D : 0));  // (+ the precision matrix / the whitened observation matrix)
     R* const host_block = block.data();
     R *hm0 = host_block, *hLP0 = hm0 + D, *hiLP0 = hLP0 + D * D, *hF = hiLP0 + D, *hb = hF + D * D, *hLQ = hb + D, *hiLQ = hLQ + D * D, *hprec = hiLQ + D;
     fk_model<R>(fk, m, D, hm0, hLP0, hiLP0, hF, hb, hLQ, hiLQ, hprec);
@@ -794,7 +845,8 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     m.prec = mvt ? d : nullptr;
     int rc = csmc_prologue<R>(h, fk, a, ctt, m, false, [&] {
         const dim3 grid((unsigned)(((long long)a.C * a.T + 63) / 64));
-        if (mvt) hipLaunchKernelGGL((k_cw_grad<R, true>), grid, dim3(64), 0, h->stream, a, m);
+        if (lg) hipLaunchKernelGGL((k_cw_grad<R, false, true>), grid, dim3(64), 0, h->stream, a, m);
+        else if (mvt) hipLaunchKernelGGL((k_cw_grad<R, true>), grid, dim3(64), 0, h->stream, a, m);
         else hipLaunchKernelGGL((k_cw_grad<R>), grid, dim3(64), 0, h->stream, a, m);
         return AUXSSM_OK;
     });
@@ -809,7 +861,7 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
         const CsmcArgs ab = csmc_batch(a, c0, cb);
         {
             ProfScope ps(h, AUXSSM_K_CSMC_FWD);
-            if ((rc = launch(h, cw_fwd_kernel<R>(guided, mvt, wide16), dim3(ab.C), dim3(64 * fwd_waves), Cw2Lds<R>::fwd_bytes(D, guided, mvt), ab, m))) return rc;
+            if ((rc = launch(h, cw_fwd_kernel<R>(guided, lg ? 2 : (mvt ? 1 : 0), wide16), dim3(ab.C), dim3(64 * fwd_waves), Cw2Lds<R>::fwd_bytes(D, guided, mvt), ab, m))) return rc;
         }
         {
             ProfScope ps(h, AUXSSM_K_CSMC_BWD);

@@ -76,6 +76,29 @@ def spatial_setup(T, grid, seed=0, sigma_x=1.0, nu=1.0, tau=-0.25, r_y=1):
     return M0, Mt, G0, Gt, x, y, prec
 
 
+def lgssm_tracking_setup(T, dx, dy, seed=0):
+    """A partially observed linear-Gaussian state-space model, 1 <= dy <= dx: x_0 ~ N(0, I), x_t = F x_{t-1} + eps_t with a stable banded F (0.9 on the
+    diagonal, 0.05 / -0.05 beside it) and Q = 0.25 I, observations y_t ~ N(H x_t, R) with a dense H (every entry non-zero: each sensor sees a mixture of all
+    components) and a non-diagonal R of condition number <= 50 (an orthogonal basis with eigenvalues between 0.1 and 2).
+    Returns (M0, Mt, G0, Gt, x, y, H, R): the model as the cSMC kernels take it (csmc.LinearGaussianPotential), the simulated states and data."""
+    from aux_ssm_samplers_amd.csmc import GaussianInit, LinearGaussianDynamics, LinearGaussianPotential
+    rng = np.random.Generator(np.random.PCG64(seed))
+    F = 0.9 * np.eye(dx) + 0.05 * np.eye(dx, k=1) - 0.05 * np.eye(dx, k=-1)
+    Q = 0.25 * np.eye(dx)
+    H = rng.standard_normal((dy, dx)) / np.sqrt(dx)
+    H = np.where(np.abs(H) < 0.05 / np.sqrt(dx), 0.05 / np.sqrt(dx), H)
+    U = np.linalg.qr(rng.standard_normal((dy, dy)))[0]
+    R = (U * np.linspace(0.1, 2.0, dy)) @ U.T
+    R = 0.5 * (R + R.T)
+    x = np.zeros((T, dx))
+    x[0] = rng.standard_normal(dx)
+    for t in range(1, T):
+        x[t] = F @ x[t - 1] + 0.5 * rng.standard_normal(dx)
+    y = x @ H.T + rng.standard_normal((T, dy)) @ np.linalg.cholesky(R).T
+    M0, Mt = GaussianInit(m0=np.zeros(dx), P0=np.eye(dx)), LinearGaussianDynamics(F=F, b=np.zeros(dx), Q=Q)
+    return M0, Mt, LinearGaussianPotential(H=H, R=R, y=y[0]), LinearGaussianPotential(H=H, R=R, params=y[1:]), x, y, H, R
+
+
 def lorenz_kalman_setup(T, every=8, dt=0.01, seed=0):
     """examples/lorenz: theta = (10, 28, 8/3), sigma_x = 3, m0 = (1.5, -1.5, 25), P0 = diag(400, 20, 20), (x2, x3) observed every `every`-th
     step with variance 5, NaN rows (ys AND Hs, as model.py:43-56) elsewhere."""

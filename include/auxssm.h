@@ -259,7 +259,7 @@ int auxssm_kalman_state_resolve(auxssm_handle h, int dtype, const auxssm_dims* d
  * A Python Mt/Gt object cannot run inside a kernel; the Feynman-Kac model is a closed family instead:
  *   transition  x_t | x_{t-1} ~ N(F x_{t-1} + b, Q)   (time-invariant), initial N(m0, P0)
  *   potential   FLAT: 0 | GAUSS_OBS: log N(y_t; x_t, sig_y^2 I) | SV: sum_k log N(y_{t,k}; 0, exp(x_{t,k})) | GAUSS_OBS_MASKED | MVT: multivariate Student-t
- *               with a precision matrix (auxssm_fk_potential below)
+ *               with a precision matrix | LIN_GAUSS: log N(y_t; H x_t + c, R), dy <= dx (auxssm_fk_potential below)
  *   proposal    BOOTSTRAP_LG:    M0 = initial, Mt = transition, G0/Gt = potential          (test_csmc/common.py fixtures)
  *               AUX_INDEPENDENT: u = x + sqrt(delta_t/2) eps_aux; M0/Mt = N(u_t, delta_t/2 I);
  *                                G0 = log initial + potential, Gt = log transition + potential, Pt = transition
@@ -295,7 +295,7 @@ typedef enum {
     AUXSSM_POT_SV = 2,               /* y_{t,k} ~ N(0, exp(x_{t,k})) */
     AUXSSM_POT_GAUSS_OBS_MASKED = 3, /* y_{t,k} ~ N(x_{t,k}, sig_y^2) for the finite y_{t,k} only: missing components / steps skipped
                                         (examples/lorenz/model.py:43-56: x2, x3 observed every 80th step) */
-    AUXSSM_POT_MVT = 4               /* the unnormalised multivariate Student-t log-density with a precision matrix (examples/spatial/t_distribution.py:98-104,
+    AUXSSM_POT_MVT = 4,              /* the unnormalised multivariate Student-t log-density with a precision matrix (examples/spatial/t_distribution.py:98-104,
                                         model.py:121-124), the one potential of the family that couples the components of a state:
                                           log g_t(x) = -(nu + dx)/2 log(1 + (x - y_t)^T prec (x - y_t) / nu),  the whole value 0 when it is NaN
                                         (any NaN component of y_t makes the step flat, as the reference's nan_to_num does).  nu > 0, prec symmetric positive definite.
@@ -304,6 +304,18 @@ typedef enum {
                                         log g = (v == v) ? v : 0.  The constants (nu + dx)/2 and 1/nu are formed once on the host in the sweep's dtype.  Gradient (prec
                                         symmetric):  d log g / dx_k = (-((nu + dx)/2 + (nu + dx)/2) * (1/nu) / s) * z_k = -(nu + dx)/(nu + q) z_k to rounding, every component 0 when s is NaN.
                                         sup_x log g = 0, which is the forward pass's reduction-free bound at dx <= 4; the wide kernels (dx > 4) shift by the exact maximum of every step, the bound being tens of nats above the weights there. */
+    AUXSSM_POT_LIN_GAUSS = 5         /* the linear-Gaussian observation y_t ~ N(H x_t + c, R), H (dy,dx) dense, R (dy,dy) symmetric positive definite, 1 <= dy <= dx:
+                                          log g_t(x) = log N(y_t; H x + c, R),  the whole value 0 when it is NaN
+                                        (any NaN component of y_t makes the step flat).  The CALLER whitens once, in double, with L = chol(R):
+                                          Hw = L^-1 H,  yw_t = L^-1 (y_t - c),  c_lin = -sum_k log L_kk - (dy/2) log 2 pi,   log g_t(x) = c_lin - |yw_t - Hw x|^2 / 2
+                                        and passes obs_H = Hw zero-padded to (dx,dx), obs_const = c_lin and y = yw zero-padded to (T,dx), a row of y with any NaN as an all-NaN
+                                        row.  The residual form on purpose: information-form quantities around the origin cancel in fp32.
+                                        Arithmetic order (every kernel; explicit fma, no contraction; k, j over all dx padded components):
+                                          a_k = sum_j fma(H_kj, x_j, .) with j ascending from 0;  z_k = y_{t,k} - a_k;  q = sum_k fma(z_k, z_k, .) with k ascending from 0;
+                                          v = fma(-1/2, q, c_lin) = c_lin - q/2 rounded once;  log g = (v == v) ? v : 0.
+                                        Gradient:  d log g / dx_j = sum_k fma(H_kj, z_k, .) with k ascending from 0, every component 0 when v is NaN.
+                                        sup_x log g <= c_lin (0 on a NaN row), the forward pass's reduction-free bound at dx <= 4; the wide kernels (dx > 4) shift by the exact
+                                        maximum of every step, as for AUXSSM_POT_MVT. */
 } auxssm_fk_potential;
 /* transition x_{t+1} | x_t ~ N(mean(x_t), Q): LINEAR mean = F x + b; LORENZ63_EM mean = x + dt (phi_0(x) + theta * phi(x)), the
  * Euler-Maruyama step of examples/lorenz/model.py:10-25 (dx = 3; theta = F[0..2], dt = b[0], Q = chol_Q chol_Q^T = dt sigma_x^2 I) */
@@ -336,6 +348,9 @@ typedef struct {
     /* AUXSSM_POT_MVT only (appended: every field above keeps its offset) */
     double nu;             /* degrees of freedom, > 0 */
     const double* prec;    /* host (dx,dx) row-major, symmetric positive definite, like F */
+    /* AUXSSM_POT_LIN_GAUSS only (appended likewise) */
+    const double* obs_H;   /* host (dx,dx) row-major: the whitened observation matrix L^-1 H, rows beyond dy zero */
+    double obs_const;      /* c_lin = -sum_k log L_kk - (dy/2) log 2 pi */
 } auxssm_fk_model;
 typedef enum { AUXSSM_GRAD_NONE = 0, AUXSSM_GRAD_REFERENCE = 1, AUXSSM_GRAD_EXACT = 2 } auxssm_fk_gradient;
 typedef struct {

@@ -5,6 +5,8 @@
    C5   dense d = p = 64 T=8192 fp32: filter + sampler + joint log-density of one chain (wide-state path)
    guided  guided proposals beside the independent ones: C3's shape and the reference's SV protocol (D = 30, N = 25), 256 chains
    spatial  the spatial example on the 5 x 5 grid (dx = 25, T = 1024, N = 25, multivariate Student-t potential) beside the SV potential at the same shape, 256 chains
+   lingauss  a partially observed linear-Gaussian model (dx = 24, dy = 12, T = 1024, N = 25, linear-Gaussian observation potential) beside GaussianObsPotential
+             at the same shape, 256 chains
    loop the MCMC loop around the sweeps (aux_ssm_samplers_amd.loop: running moments, acceptance averages, adaptation, Lorenz theta step) on C2 / C3 / C4
 Prints one JSON line per measurement.  Inputs are resident in HBM (DeviceChains) where the API allows it; device Threefry noise."""
 import json
@@ -332,6 +334,42 @@ def spatial(grid=5, T=1024, N=25, chains=256, reps=5, runs=3):
                               mvt_over_sv_rate=round(best["SV"] / best["multivariate-t"], 3), updated=upd)), flush=True)
 
 
+def lingauss(dx=24, dy=12, T=1024, N=25, chains=256, reps=5, runs=3):
+    """a partially observed linear-Gaussian model (workloads.lgssm_tracking_setup: dx = 24 states seen through dy = 12 dense linear mixtures with correlated
+    noise, T = 1024, N = 25) through the wide cSMC kernels with the linear-Gaussian observation potential: independent proposals, independent with gradient and
+    guided proposals, resident chains, backward sampling, fp32, Threefry noise -- each beside the SAME sweep with GaussianObsPotential (every component observed
+    directly, one isotropic scale) on the same dynamics and a data array of the same shape as the device holds it (what the new potential costs: one more
+    dx x dx row product per particle and step).  `runs` measurements per leg, potentials alternating."""
+    from aux_ssm_samplers_amd.workloads import lgssm_tracking_setup
+    from aux_ssm_samplers_amd.csmc import CsmcChains, CSMCState, get_independent_kernel, get_guided_kernel, GaussianObsPotential
+    h = _lib.default_handle()
+    M0, Mt, G0, Gt, x, y, H, Rm = lgssm_tracking_setup(T, dx, dy)
+    yd = x + 0.7 * np.random.Generator(np.random.PCG64(1)).standard_normal(x.shape)
+    pots = (("linear-Gaussian", G0, Gt), ("Gaussian-obs", GaussianObsPotential(sig=0.7, y=yd[0]), GaussianObsPotential(sig=0.7, params=yd[1:])))
+    for name, get, gradient in (("independent", get_independent_kernel, False), ("independent", get_independent_kernel, True), ("guided", get_guided_kernel, False)):
+        ms = {p[0]: [] for p in pots}
+        upd = {}
+        for run in range(runs):
+            for pname, g0, gt in pots:
+                init, kernel = get(M0, g0, Mt, gt, N, backward=True, Pt=Mt, gradient=gradient)
+                cc = CsmcChains(h, np.repeat(x[None], chains, axis=0).astype(np.float32))
+                st = CSMCState(x=cc, updated=None)
+                kernel(0, st, 0.02)
+                h.sync()
+                t0 = time.perf_counter()
+                for k in range(reps):
+                    kernel(1 + k, st, None)
+                h.sync()
+                ms[pname].append((time.perf_counter() - t0) / reps * 1e3)
+                upd[pname] = float((cc.ancestors.to_host() != 0).mean())
+                del cc, st
+        best = {k: min(v) for k, v in ms.items()}
+        print(json.dumps(dict(config=f"lingauss dx={dx} dy={dy} T={T}, aux-cSMC N={N} {name} proposals (gradient={gradient}) + backward sampling, fp32, "
+                                     "resident chains", chains=chains, ms_per_sweep_call={k: [round(v_, 3) for v_ in v] for k, v in ms.items()},
+                              sweeps_per_s={k: round(chains / v * 1e3, 1) for k, v in best.items()},
+                              lingauss_over_gaussobs_rate=round(best["Gaussian-obs"] / best["linear-Gaussian"], 3), updated=upd)), flush=True)
+
+
 def sv30_kalman(T=250, D=30, chains=(1, 16, 64)):
     """the other sampler of the same protocol: the auxiliary Kalman sampler with first / second order linearisation of the SV observation model at D = 30
     (examples/stochastic_volatility/auxiliary_kalman.py:22-48), fp64 as the reference runs it, parallel scan; wide-state kernels (dx = 30)"""
@@ -359,6 +397,8 @@ if __name__ == "__main__":
         guided()
     if "spatial" in which:
         spatial()
+    if "lingauss" in which:
+        lingauss()
     if "sv30k" in which:
         sv30_kalman()
     if "pit" in which:
