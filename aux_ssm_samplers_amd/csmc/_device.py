@@ -16,9 +16,9 @@ _UNSUPPORTED = ("{what} is a Python object the HIP kernels cannot evaluate. The 
 
 
 class FkDesc:
-    def __init__(self, proposal, potential, m0, chol_P0, F, b, chol_Q, y, sig_y, transition=_lib.TRANS_LINEAR, gradient=_lib.GRAD_NONE):
-        self.proposal, self.potential, self.sig_y, self.transition = proposal, potential, float(sig_y), int(transition)
-        self.gradient = int(gradient)
+    def __init__(self, proposal, pot, m0, chol_P0, F, b, chol_Q, transition=_lib.TRANS_LINEAR, gradient=_lib.GRAD_NONE):
+        """pot: everything about the potential (_potential)"""
+        self.proposal, self.transition, self.gradient = proposal, int(transition), int(gradient)
         self.m0 = np.ascontiguousarray(m0, np.float64).reshape(-1)
         self.dx = self.m0.shape[0]
         d = self.dx
@@ -33,22 +33,14 @@ class FkDesc:
         self.F = np.ascontiguousarray(F, np.float64).reshape(d, d)
         self.b = np.ascontiguousarray(b, np.float64).reshape(d)
         self.chol_Q = np.ascontiguousarray(chol_Q, np.float64).reshape(d, d)
-        self.y = None if y is None else np.asarray(y)
         self._ydev = {}
         self._tvdev = {}
         self.user = None  # UserModel: the parts of the model compiled from device code (auxssm_csmc_sweep_program)
-        self.nu, self.prec = 0.0, None  # POT_MVT: degrees of freedom and the (dx, dx) precision matrix (host, like F)
-        self.obs_H, self.obs_const = None, 0.0  # POT_LIN_GAUSS: the whitened observation matrix, zero-padded to (dx, dx), and c_lin (self.y: the whitened rows)
-
-    def set_lingauss(self, Hw, c_lin):
-        self.obs_H = np.ascontiguousarray(Hw, np.float64).reshape(self.dx, self.dx)
-        self.obs_const = float(c_lin)
-        return self
-
-    def set_mvt(self, nu, prec):
-        self.nu = float(nu)
-        self.prec = np.ascontiguousarray(prec, np.float64).reshape(self.dx, self.dx)
-        return self
+        mat = lambda a: None if a is None else np.ascontiguousarray(a, np.float64).reshape(d, d)  # noqa: E731 -- host (dx, dx), like F
+        self.potential, self.sig_y = pot["kind"], float(pot.get("sig_y", 1.0))
+        self.y = None if pot.get("y") is None else np.asarray(pot["y"])  # the device's observation array (POT_LIN_GAUSS: the whitened rows)
+        self.nu, self.prec = float(pot.get("nu", 0.0)), mat(pot.get("prec"))  # POT_MVT: degrees of freedom and the precision matrix
+        self.obs_H, self.obs_const = mat(pot.get("obs_H")), float(pot.get("obs_const", 0.0))  # POT_LIN_GAUSS: Hw zero-padded to (dx, dx), and c_lin
 
     def tvdev(self, handle, dtype, T):
         """device copies of the time-varying transition arrays (or None)"""
@@ -89,57 +81,38 @@ class FkDesc:
 
 
 def _potential(G0, Gt, d):
+    """everything FkDesc needs about the potential: dict(kind, y = the device's observation array (T, dx) [, sig_y] [, the kind's own parameters])"""
     if type(G0) is not type(Gt) and not (isinstance(G0, GaussianInit) and isinstance(Gt, GaussianObsPotential)):
         raise NotImplementedError(_UNSUPPORTED.format(what=f"G0={type(G0).__name__} with Gt={type(Gt).__name__}"))
     if isinstance(Gt, FlatPotential):
-        return _lib.POT_FLAT, None, 1.0
+        return dict(kind=_lib.POT_FLAT)
+    if not isinstance(Gt, (MultivariateTPotential, LinearGaussianPotential, MaskedGaussianObsPotential, GaussianObsPotential, SVPotential)):
+        raise NotImplementedError(_UNSUPPORTED.format(what=f"Gt={type(Gt).__name__}"))
+    y0 = G0.m0 if isinstance(G0, GaussianInit) else G0.y
+    if y0 is None or Gt.params is None:
+        raise ValueError("the potential needs y (G0.y = ys[0]) and params (Gt.params = ys[1:])")
+    dy = Gt.dy if isinstance(Gt, LinearGaussianPotential) else d
+    ys = np.concatenate([np.reshape(y0, (1, dy)), np.reshape(Gt.params, (-1, dy))], axis=0)
     if isinstance(Gt, MultivariateTPotential):
-        if G0.y is None or Gt.params is None:
-            raise ValueError("the potential needs y (G0.y = ys[0]) and params (Gt.params = ys[1:])")
         if G0.nu != Gt.nu or not np.array_equal(G0.prec, Gt.prec):
             raise ValueError("G0 and Gt must carry the same nu and prec")
         if Gt.dx != d:
             raise ValueError(f"the potential's precision matrix is {Gt.dx} x {Gt.dx}, the state has dimension {d}")
-        return _lib.POT_MVT, np.concatenate([np.reshape(G0.y, (1, d)), np.reshape(Gt.params, (-1, d))], axis=0), 1.0
+        return dict(kind=_lib.POT_MVT, y=ys, nu=Gt.nu, prec=Gt.prec)
     if isinstance(Gt, LinearGaussianPotential):
-        if G0.y is None or Gt.params is None:
-            raise ValueError("the potential needs y (G0.y = ys[0]) and params (Gt.params = ys[1:])")
         if not (np.array_equal(G0.H, Gt.H) and np.array_equal(G0.R, Gt.R) and np.array_equal(G0.c, Gt.c)):
             raise ValueError("G0 and Gt must carry the same H, R and c")
         if Gt.dx != d:
             raise ValueError(f"the potential's observation matrix has {Gt.dx} columns, the state has dimension {d}")
-        # the device's observation array is the whitened rows yw (T, dx); _mvt puts Hw and c_lin into the description
-        ys = np.concatenate([np.reshape(G0.y, (1, Gt.dy)), np.reshape(Gt.params, (-1, Gt.dy))], axis=0)
-        return _lib.POT_LIN_GAUSS, Gt.whitened(ys)[1], 1.0
-    if isinstance(Gt, MaskedGaussianObsPotential):
-        if G0.y is None or Gt.params is None:
-            raise ValueError("the potential needs y (G0.y = ys[0]) and params (Gt.params = ys[1:])")
-        y = np.concatenate([np.reshape(G0.y, (1, d)), np.reshape(Gt.params, (-1, d))], axis=0)
-        if abs(G0.sig - Gt.sig) > 1e-12 * Gt.sig:
-            raise NotImplementedError("G0 and Gt must share the observation noise scale")
-        return _lib.POT_GAUSS_OBS_MASKED, y, Gt.sig
-    if isinstance(Gt, (GaussianObsPotential, SVPotential)):
-        y0 = G0.m0 if isinstance(G0, GaussianInit) else G0.y
-        if y0 is None or Gt.params is None:
-            raise ValueError("the potential needs y (G0.y = ys[0]) and params (Gt.params = ys[1:])")
-        y = np.concatenate([np.reshape(y0, (1, d)), np.reshape(Gt.params, (-1, d))], axis=0)
-        if isinstance(Gt, SVPotential):
-            return _lib.POT_SV, y, 1.0
-        sig = Gt.sig
-        if isinstance(G0, GaussianInit):
-            s0 = float(np.sqrt(np.reshape(G0.P0, -1)[0]))
-            if abs(s0 - sig) > 1e-12 * sig:
-                raise NotImplementedError("G0 and Gt must share the observation noise scale")
-        return _lib.POT_GAUSS_OBS, y, sig
-    raise NotImplementedError(_UNSUPPORTED.format(what=f"Gt={type(Gt).__name__}"))
-
-
-def _mvt(fk, Gt):
-    """the own parameters of the multivariate-t and the linear-Gaussian observation potential into the description (every other potential: nothing)"""
-    if isinstance(Gt, LinearGaussianPotential):  # whitened once, in float64, here at description time
-        Hw, _, c_lin = Gt.whitened(np.zeros((1, Gt.dy)))
-        return fk.set_lingauss(Hw, c_lin)
-    return fk.set_mvt(Gt.nu, Gt.prec) if isinstance(Gt, MultivariateTPotential) else fk
+        Hw, yw, c_lin = Gt.whitened(ys)  # whitened once, in float64, here at description time
+        return dict(kind=_lib.POT_LIN_GAUSS, y=yw, obs_H=Hw, obs_const=c_lin)
+    if isinstance(Gt, SVPotential):
+        return dict(kind=_lib.POT_SV, y=ys)
+    masked = isinstance(Gt, MaskedGaussianObsPotential)
+    s0 = G0.sig if masked else (float(np.sqrt(np.reshape(G0.P0, -1)[0])) if isinstance(G0, GaussianInit) else Gt.sig)
+    if abs(s0 - Gt.sig) > 1e-12 * Gt.sig:
+        raise NotImplementedError("G0 and Gt must share the observation noise scale")
+    return dict(kind=_lib.POT_GAUSS_OBS_MASKED if masked else _lib.POT_GAUSS_OBS, y=ys, sig_y=Gt.sig)
 
 
 def _dyn(M0, Mt):
@@ -264,9 +237,9 @@ def _describe_user(proposal, M0, G0, Mt, Gt, gradient, parallel):
         flags |= _lib.FK_USER_POTENTIAL
         src.append(Gt.source)
         theta_g = tgt
-        pot, y, sig = _lib.POT_FLAT, None, 1.0
+        pot = dict(kind=_lib.POT_FLAT)
     else:
-        pot, y, sig = _potential(G0, Gt, d)
+        pot = _potential(G0, Gt, d)
     if isinstance(Mt, DeviceGaussianDynamics):
         Q = np.asarray(Mt.Q, np.float64)
         if Q.ndim == 3:
@@ -286,7 +259,7 @@ def _describe_user(proposal, M0, G0, Mt, Gt, gradient, parallel):
                                   "non-Gaussian transition noise is not supported")
     if gradient:  # the program also holds the gradient kernel, from the derivatives of the user-defined parts (grad_log_g / mean_vjp)
         flags |= _lib.FK_USER_GRADIENT
-    fk = _mvt(FkDesc(proposal, pot, M0.m0, M0.chol(), F, b, LQ, y, sig, tk, gradient), Gt)
+    fk = FkDesc(proposal, pot, M0.m0, M0.chol(), F, b, LQ, tk, gradient)
     fk.user = UserModel("\n".join(src), flags, d, yu, theta_g, theta_m)
     return fk
 
@@ -294,9 +267,8 @@ def _describe_user(proposal, M0, G0, Mt, Gt, gradient, parallel):
 def _describe_builtin(proposal, M0, G0, Mt, Gt, gradient):
     """the FkDesc of a model of the closed family, once the proposal's own checks have passed"""
     d = np.size(M0.m0)
-    pot, y, sig = _potential(G0, Gt, d)
     tk, F, b = _trans(Mt)
-    return _mvt(FkDesc(proposal, pot, M0.m0, M0.chol(), F, b, Mt.chol(), y, sig, tk, gradient), Gt)
+    return FkDesc(proposal, _potential(G0, Gt, d), M0.m0, M0.chol(), F, b, Mt.chol(), tk, gradient)
 
 
 def describe_bootstrap(M0, G0, Mt, Gt, Pt):

@@ -54,7 +54,7 @@ template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R
 }
 """
 
-# multivariate Student-t with a precision matrix (AUXSSM_POT_MVT): theta = [nu | prec (D x D, row-major)]; csrc/csmc_sweep.h::mvt_quad / mvt_value in their order,
+# multivariate Student-t with a precision matrix (AUXSSM_POT_MVT): theta = [nu | prec (D x D, row-major)]; csrc/csmc_sweep.h::coupled_resid / mvt_value in their order,
 # the two constants formed as csmc_host.h::fk_model forms them; sup_x log g = 0
 BUILTIN_MVT = r"""
 template <typename R, int D> __device__ R mvt_s_(const R* x, const R* y, const R* theta, R* z) {
@@ -81,7 +81,7 @@ template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R
 """
 
 # linear-Gaussian observation y ~ N(H x + c, R) in the whitened residual form (AUXSSM_POT_LIN_GAUSS): theta = [c_lin | Hw (D x D, row-major, rows beyond dy zero)],
-# observations = the whitened rows yw (T, D); csrc/csmc_sweep.h::lin_resid / lin_value in their order; the bound of k_csmc_potbound (c_lin, 0 on a NaN row)
+# observations = the whitened rows yw (T, D); csrc/csmc_sweep.h::coupled_resid / lin_value in their order; the bound of k_csmc_potbound (c_lin, 0 on a NaN row)
 BUILTIN_LINGAUSS = r"""
 template <typename R, int D> __device__ R lin_q_(const R* x, const R* y, const R* theta, R* z) {
     const R* H = theta + 1;
@@ -169,7 +169,7 @@ template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const
 }
 """
 
-# d/dx log g = (-(hc + hc) / nu / s) z with s = 1 + q / nu, z = prec (x - y); every component 0 where s is NaN (csrc/csmc_sweep.h::mvt_grad_coef / mvt_grad_term)
+# d/dx log g = (-(hc + hc) / nu / s) z with s = 1 + q / nu, z = prec (x - y); every component 0 where s is NaN (csrc/csmc_sweep.h::coupled_grad)
 BUILTIN_MVT_GRAD = BUILTIN_MVT + r"""
 template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
     R z[D];
@@ -180,7 +180,7 @@ template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const
 }
 """
 
-# d/dx log g = Hw^T z with z = yw - Hw x (component j: fma over k ascending); every component 0 where the value is NaN (csrc/csmc_sweep.h::lin_grad)
+# d/dx log g = Hw^T z with z = yw - Hw x (component j: fma over k ascending); every component 0 where the value is NaN (csrc/csmc_sweep.h::coupled_grad)
 BUILTIN_LINGAUSS_GRAD = BUILTIN_LINGAUSS + r"""
 template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
     R z[D];

@@ -122,39 +122,34 @@ template <typename R, int D> static bool c3_shape(const FkDev<R>& m, const CsmcA
            m.transition == AUXSSM_TRANS_LINEAR && a.As == nullptr && a.noise_mode != AUXSSM_NOISE_EXPLICIT && !a.pregen;
 }
 
-// The forward pass of (model, sweep), nw = nw_class(N).  TV: time-varying transitions; GRAD: gradient-informed proposals; PM = FkBuiltin<R, D, true>
-// (the linear-Gaussian observation potential: the same two rows with PM = FkBuiltin<R, D, false, true>).
-//   case                                 k_csmc_fwd<R, D, ...>
-//   multivariate-t potential, guided     <false, GRAD, 0, 2, PM>
-//   multivariate-t potential, otherwise  <TV, GRAD, 0, 0, PM>                  the generic workgroup for every N
-//   guided, other potentials             <false, GRAD, nw == 16 ? 16 : 0, 2>   N = 512 takes the generic one
-//   c3_shape                             <float, 1, false, false, 16, 1>
-//   everything else                      <TV, GRAD, nw, 0>
+// The forward pass of (model, sweep), nw = nw_class(N).  TV: time-varying transitions; GRAD: gradient-informed proposals; P = FkBuiltin<R, D, V>, V the variant of
+// the model's potential (csmc_sweep.h::with_pot).
+//   case                            k_csmc_fwd<R, D, ...>
+//   coupled potential, guided       <false, GRAD, 0, 2, P>
+//   coupled potential, otherwise    <TV, GRAD, 0, 0, P>                      the generic workgroup for every N
+//   guided, separable potentials    <false, GRAD, nw == 16 ? 16 : 0, 2, P>   N = 512 takes the generic one
+//   c3_shape                        <float, 1, false, false, 16, 1>
+//   everything else                 <TV, GRAD, nw, 0, P>
 template <typename R, int D> static SweepKernel<R> fwd_kernel(const FkDev<R>& m, const CsmcArgs& a, int nw) {
     const bool tv = m.Ft != nullptr, guided = m.proposal == AUXSSM_PROP_AUX_GUIDED;
-    return with_bool(m.gradient != 0, [&](auto gr) -> SweepKernel<R> {
-        constexpr bool GR = decltype(gr)::value;
-        if (m.potential == AUXSSM_POT_MVT) {
-            using PM = FkBuiltin<R, D, true>;
-            if (guided) return k_csmc_fwd<R, D, false, GR, 0, 2, PM>;
-            if (tv) return k_csmc_fwd<R, D, true, GR, 0, 0, PM>;
-            return k_csmc_fwd<R, D, false, GR, 0, 0, PM>;
-        }
-        if (m.potential == AUXSSM_POT_LIN_GAUSS) {
-            using PL = FkBuiltin<R, D, false, true>;
-            if (guided) return k_csmc_fwd<R, D, false, GR, 0, 2, PL>;
-            if (tv) return k_csmc_fwd<R, D, true, GR, 0, 0, PL>;
-            return k_csmc_fwd<R, D, false, GR, 0, 0, PL>;
-        }
-        if (guided) {
-            if (nw == 16) return k_csmc_fwd<R, D, false, GR, 16, 2>;
-            return k_csmc_fwd<R, D, false, GR, 0, 2>;
-        }
-        if constexpr (D == 1 && sizeof(R) == 4 && !GR) {
-            if (c3_shape<R, D>(m, a, nw)) return k_csmc_fwd<R, D, false, false, 16, 1>;
-        }
-        return with_bool(tv, [&](auto tvc) {
-            return with_nw(nw, [&](auto n) -> SweepKernel<R> { return k_csmc_fwd<R, D, decltype(tvc)::value, GR, decltype(n)::value, 0>; });
+    return with_bool(m.gradient != 0, [&](auto gr) {
+        return with_pot(m.potential, [&](auto pv) -> SweepKernel<R> {
+            constexpr bool GR = decltype(gr)::value, SEP = decltype(pv)::value == PotV::SEP;
+            using P = FkBuiltin<R, D, decltype(pv)::value>;
+            if (guided) {
+                if constexpr (SEP) {
+                    if (nw == 16) return k_csmc_fwd<R, D, false, GR, 16, 2, P>;
+                }
+                return k_csmc_fwd<R, D, false, GR, 0, 2, P>;
+            }
+            if constexpr (D == 1 && sizeof(R) == 4 && !GR && SEP) {
+                if (c3_shape<R, D>(m, a, nw)) return k_csmc_fwd<R, D, false, false, 16, 1>;
+            }
+            return with_bool(tv, [&](auto tvc) -> SweepKernel<R> {
+                constexpr bool TV = decltype(tvc)::value;
+                if constexpr (!SEP) return k_csmc_fwd<R, D, TV, GR, 0, 0, P>;
+                else return with_nw(nw, [&](auto n) -> SweepKernel<R> { return k_csmc_fwd<R, D, TV, GR, decltype(n)::value, 0, P>; });
+            });
         });
     });
 }
@@ -438,7 +433,7 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
     // times a logarithm -- and fp32 weights exp(lw - bound) leave the normal range, which costs the resampling draws their precision long before every weight is zero)
     // (the linear-Gaussian observation potential likewise: its bound c_lin is attained only where Hw x = yw_t, and at dx > 4 the particles' residuals leave the weights
     // as far below it)
-    const bool loose = wide && !ug && (fk->potential == AUXSSM_POT_MVT || fk->potential == AUXSSM_POT_LIN_GAUSS);
+    const bool loose = wide && !ug && pot_kind(fk->potential).wide_no_bound;
     if (!guided && !loose && (ug ? prog->has_bound : (fk->potential == AUXSSM_POT_FLAT || fk->y != nullptr))) ws.add(a.gb, (size_t)T * sR);
     if (guided) ws.add(a.gtab, guided_tab_reals(T, D) * sR);  // K_t, chol Lambda_t and their constants, every step
     if (noise->mode == AUXSSM_NOISE_THREEFRY) ws.add(ub, CT * sR);  // the backward pass's uniforms, drawn once (csmc_sweep.h::k_csmc_ubwd)

@@ -8,9 +8,7 @@ namespace ax {
 
 // element (i, j) of chol P0 (init) or chol Q of a model; csmc_wide.hip adds the overload of its FkW
 template <typename R> __device__ __forceinline__ R gt_chol(const FkDev<R>& m, bool init, int i, int j) { return (init ? m.LP0 : m.LQ)[i * CS_MAXD + j]; }
-// element (i, j) of the multivariate-t potential's precision matrix; csmc_wide.hip adds the overload of its FkW
-template <typename R> __device__ __forceinline__ R mvt_prec(const FkDev<R>& m, int i, int j) { return m.prec[i * CS_MAXD + j]; }
-constexpr int GT_MAXD = 32;  // the widest state of either kernel family
+constexpr int GT_MAXD = CS_MAXD_RT;  // the widest state of either kernel family
 
 constexpr int GT_S = 33;  // row stride of the 32 x 32 work matrices in LDS (odd: a column walk touches every bank)
 
@@ -108,8 +106,8 @@ template <typename R, typename M> __global__ void __launch_bounds__(64) k_csmc_g
     }
 }
 
-// gradient variant: u~ = u + s_t^2 grad_x log g_t(u_t) into a.grad, once per (chain, t, component) -- the potentials of the closed family are sums over
-// components, so the gradient is component by component (csmc_sweep.h::potential_grad, same operations)
+// gradient variant: u~ = u + s_t^2 grad_x log g_t(u_t) into a.grad, once per (chain, t, component) -- the separable potentials are sums over components, so
+// the gradient is component by component (csmc_sweep.h::sep_grad_term)
 template <typename R> __global__ void k_csmc_gshift(CsmcArgs a, int D, int potential, R inv_sig_y) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)a.C * a.T * D) return;
@@ -117,54 +115,19 @@ template <typename R> __global__ void k_csmc_gshift(CsmcArgs a, int D, int poten
     const int k = (int)(g % D);
     const R u = ((const R*)a.u)[g], s = ((const R*)a.shd)[t];
     const R yk = a.y ? ((const R*)a.y)[t * D + k] : (R)0;
-    R v = 0;
-    if (potential == 1 || (potential == 3 && yk - yk == 0)) v = ((yk - u) * inv_sig_y) * inv_sig_y;
-    else if (potential == 2) {
-        const R e = det_exp(-u);
-        v = (R)0.5 * fma_(yk * yk, e, (R)-1);
-        v = (v == v) ? v : (R)0;
-    }
-    ((R*)a.grad)[g] = fma_(s * s, v, u);
+    ((R*)a.grad)[g] = fma_(s * s, sep_grad_term<R>(potential, inv_sig_y, u, yk), u);
 }
 
-// the same for the multivariate Student-t potential (AUXSSM_POT_MVT), whose gradient couples the components: one thread per (chain, t), the operations of
-// csmc_sweep.h::mvt_quad / mvt_grad_coef in their order with a runtime dimension (M: FkDev or csmc_wide.hip's FkW).  LG: the other coupled potential, the
-// linear-Gaussian observation potential (AUXSSM_POT_LIN_GAUSS: csmc_sweep.h::lin_resid / lin_raw / lin_grad in their order, the matrix in the same storage)
-template <typename R, typename M, bool LG = false> __global__ void k_csmc_gshift_mvt(CsmcArgs a, M m) {
+// the same for a coupled potential (variant V: csmc_sweep.h::coupled_grad with the run-time dimension m.D), whose gradient is not component by component: one
+// thread per (chain, t).  M: FkDev or csmc_wide.hip's FkW
+template <typename R, typename M, PotV V> __global__ void k_csmc_gshift_coupled(CsmcArgs a, M m) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)a.C * a.T) return;
     const int D = m.D;
     const long long t = g % a.T;
     const R* u = (const R*)a.u + g * D;
-    const R* y = (const R*)a.y + t * D;
     const R s = ((const R*)a.shd)[t];
-    R r[GT_MAXD], z[GT_MAXD];
-    if constexpr (LG) {
-        for (int k = 0; k < D; ++k) {
-            R acc = 0;
-            for (int j = 0; j < D; ++j) acc = fma_(mvt_prec(m, k, j), u[j], acc);
-            z[k] = y[k] - acc;
-        }
-        R q = 0;
-        for (int k = 0; k < D; ++k) q = fma_(z[k], z[k], q);
-        const R v = lin_raw<R>(m.c_obs, q);
-        for (int j = 0; j < D; ++j) {
-            R acc = 0;
-            for (int k = 0; k < D; ++k) acc = fma_(mvt_prec(m, k, j), z[k], acc);
-            ((R*)a.grad)[g * D + j] = fma_(s * s, (v == v) ? acc : (R)0, u[j]);
-        }
-        return;
-    }
-    for (int k = 0; k < D; ++k) r[k] = u[k] - y[k];
-    R q = 0;
-    for (int k = 0; k < D; ++k) {
-        R acc = 0;
-        for (int j = 0; j < D; ++j) acc = fma_(mvt_prec(m, k, j), r[j], acc);
-        z[k] = acc;
-    }
-    for (int k = 0; k < D; ++k) q = fma_(z[k], r[k], q);
-    const R sq = (R)1 + q * m.mvt_inv_nu, c = mvt_grad_coef<R>(m.mvt_hc, m.mvt_inv_nu, sq);
-    for (int k = 0; k < D; ++k) ((R*)a.grad)[g * D + k] = fma_(s * s, mvt_grad_term<R>(c, sq, z[k]), u[k]);
+    coupled_grad<R, V, 0>(m, m.pot_mat, m.mat_ld(), u, (const R*)a.y + t * D, [&](int k, R v) { ((R*)a.grad)[g * D + k] = fma_(s * s, v, u[k]); });
 }
 
 }  // namespace ax

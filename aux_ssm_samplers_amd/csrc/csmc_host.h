@@ -14,6 +14,31 @@
 
 namespace ax {
 
+// What a built-in potential kind needs, in ONE place, indexed by AUXSSM_POT_* (its compile-time variant: csmc_sweep.h::pot_variant, shared with the device code).
+// A new kind adds its row here.
+struct PotKind {
+    bool needs_y;                               // reads the observations y
+    const double* auxssm_fk_model::*matrix;     // the ABI field of the dx x dx matrix a coupled potential carries (FkDev / FkW::pot_mat), or null
+    const char* matrix_missing;                 // check_fk_model's message when that field is NULL
+    bool wide_no_bound;                         // the wide-state sweep drops the bound array and shifts every step by its exact maximum (csmc.hip::csmc_sweep_impl)
+};
+static const PotKind POT_KINDS[] = {
+    /* AUXSSM_POT_FLAT */ {false, nullptr, nullptr, false},
+    /* AUXSSM_POT_GAUSS_OBS */ {true, nullptr, nullptr, false},
+    /* AUXSSM_POT_SV */ {true, nullptr, nullptr, false},
+    /* AUXSSM_POT_GAUSS_OBS_MASKED */ {true, nullptr, nullptr, false},
+    /* AUXSSM_POT_MVT */ {true, &auxssm_fk_model::prec, "the multivariate-t potential needs its precision matrix prec (host, dx x dx)", true},
+    /* AUXSSM_POT_LIN_GAUSS */
+    {true, &auxssm_fk_model::obs_H, "the linear-Gaussian observation potential needs its whitened observation matrix obs_H (host, dx x dx)", true},
+};
+constexpr int POT_NKINDS = sizeof(POT_KINDS) / sizeof(POT_KINDS[0]);
+static_assert(POT_FLAT == AUXSSM_POT_FLAT && POT_GAUSS_OBS == AUXSSM_POT_GAUSS_OBS && POT_SV == AUXSSM_POT_SV && POT_GAUSS_OBS_MASKED == AUXSSM_POT_GAUSS_OBS_MASKED &&
+                  POT_MVT == AUXSSM_POT_MVT && POT_LIN_GAUSS == AUXSSM_POT_LIN_GAUSS && POT_NKINDS == AUXSSM_POT_LIN_GAUSS + 1,
+              "csmc_sweep.h restates the potential kinds of include/auxssm.h");
+static const PotKind& pot_kind(int kind) { return POT_KINDS[kind]; }  // (kind checked by check_fk_model)
+// the matrix of fk's potential (host, dx x dx), or null for a potential without one
+static const double* pot_matrix(const auxssm_fk_model* fk) { return pot_kind(fk->potential).matrix ? fk->*pot_kind(fk->potential).matrix : nullptr; }
+
 // The one kernel launch of the cSMC drivers: kern<<<grid, block, lds, h->stream>>>(args...), the kernel's dynamic LDS limit raised first when the launch asks
 // for more than the 48 KB every kernel is granted.  (Functions of a hipRTC module have no such attribute: csmc.hip::fk_launch.)
 template <typename... P, typename... A> static int launch(auxssm_ctx* h, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, A&&... args) {
@@ -25,7 +50,7 @@ template <typename... P, typename... A> static int launch(auxssm_ctx* h, void (*
 // the model checks auxssm_csmc_sweep(_program) and auxssm_csmc_pit_sweep share; each entry point adds its own (proposals, dimensions, the explicit noise
 // arrays it reads).  user_potential: the potential is a program's, which brings its own observations
 static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* noise, bool user_potential) {
-    if (fk->potential < AUXSSM_POT_FLAT || fk->potential > AUXSSM_POT_LIN_GAUSS) {
+    if (fk->potential < 0 || fk->potential >= POT_NKINDS) {
         set_error("unknown potential kind %d", fk->potential);
         return AUXSSM_ERR_ARG;
     }
@@ -33,7 +58,8 @@ static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* no
         set_error("model has a NULL m0/chol_P0/F/b/chol_Q host pointer");
         return AUXSSM_ERR_ARG;
     }
-    if (!user_potential && fk->potential != AUXSSM_POT_FLAT && !fk->y) {
+    const PotKind& pk = pot_kind(fk->potential);
+    if (!user_potential && pk.needs_y && !fk->y) {
         set_error("potential needs observations y");
         return AUXSSM_ERR_ARG;
     }
@@ -41,18 +67,12 @@ static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* no
         set_error("sig_y must be > 0");
         return AUXSSM_ERR_ARG;
     }
-    if (fk->potential == AUXSSM_POT_MVT && !user_potential) {
-        if (!fk->prec) {
-            set_error("the multivariate-t potential needs its precision matrix prec (host, dx x dx)");
-            return AUXSSM_ERR_ARG;
-        }
-        if (!(fk->nu > 0)) {
-            set_error("the multivariate-t potential needs nu > 0");
-            return AUXSSM_ERR_ARG;
-        }
+    if (!user_potential && pk.matrix && !pot_matrix(fk)) {
+        set_error("%s", pk.matrix_missing);
+        return AUXSSM_ERR_ARG;
     }
-    if (fk->potential == AUXSSM_POT_LIN_GAUSS && !user_potential && !fk->obs_H) {
-        set_error("the linear-Gaussian observation potential needs its whitened observation matrix obs_H (host, dx x dx)");
+    if (fk->potential == AUXSSM_POT_MVT && !user_potential && !(fk->nu > 0)) {
+        set_error("the multivariate-t potential needs nu > 0");
         return AUXSSM_ERR_ARG;
     }
     const int ntv = (fk->F_t != nullptr) + (fk->b_t != nullptr) + (fk->chol_Q_t != nullptr);
@@ -77,10 +97,10 @@ static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* no
 
 // The model of fk in precision R, as both kernel families read it: the parameters into m0 | LP0 | F | b | LQ (matrices row-major, leading dimension ld), the
 // reciprocal Cholesky diagonals into iLP0 / iLQ, the kinds, the gradient mode and the additive constants into m (FkDev<R>, or csmc_wide.hip's FkW<R>).  The
-// constants are computed once, here, in precision R: they enter both the GPU and the oracle as data.  prec: where the precision matrix (AUXSSM_POT_MVT) or the
-// whitened observation matrix (AUXSSM_POT_LIN_GAUSS, with c_lin in c_obs) goes.
+// constants are computed once, here, in precision R: they enter both the GPU and the oracle as data.  pot_mat: where the matrix of a coupled potential goes
+// (pot_matrix: the precision matrix of AUXSSM_POT_MVT, the whitened observation matrix of AUXSSM_POT_LIN_GAUSS, whose c_lin goes into c_obs).
 template <typename R, typename M>
-static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* iLP0, R* F, R* b, R* LQ, R* iLQ, R* prec) {
+static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* iLP0, R* F, R* b, R* LQ, R* iLQ, R* pot_mat) {
     const int D = fk->dx;
     m.proposal = fk->proposal;
     m.potential = fk->potential;
@@ -112,8 +132,6 @@ static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* 
     } else if (fk->potential == AUXSSM_POT_LIN_GAUSS) {  // c_lin, formed on the host in double with the whitening
         m.inv_sig_y = 0;
         m.c_obs = (R)fk->obs_const;
-        for (int i = 0; i < D; ++i)
-            for (int j = 0; j < D; ++j) prec[i * ld + j] = (R)fk->obs_H[i * D + j];
     } else {
         m.inv_sig_y = 0;
         m.c_obs = -half_log_2pi;
@@ -122,16 +140,17 @@ static void fk_model(const auxssm_fk_model* fk, M& m, int ld, R* m0, R* LP0, R* 
     if (fk->potential == AUXSSM_POT_MVT) {  // (nu + D) / 2 and 1 / nu, formed here once in precision R
         m.mvt_hc = ((R)fk->nu + (R)D) / (R)2;
         m.mvt_inv_nu = (R)1 / (R)fk->nu;
-        for (int i = 0; i < D; ++i)
-            for (int j = 0; j < D; ++j) prec[i * ld + j] = (R)fk->prec[i * D + j];
     }
+    if (const double* A = pot_matrix(fk))
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j) pot_mat[i * ld + j] = (R)A[i * D + j];
 }
 // the register kernels' model (the time-varying arrays null: fk_time_varying sets them)
 template <typename R> static FkDev<R> fk_dev(const auxssm_fk_model* fk) {
     FkDev<R> m;
     memset(&m, 0, sizeof(m));
     m.transition = fk->transition;
-    fk_model<R>(fk, m, CS_MAXD, m.m0, m.LP0, m.iLP0, m.F, m.b, m.LQ, m.iLQ, m.prec);
+    fk_model<R>(fk, m, CS_MAXD, m.m0, m.LP0, m.iLP0, m.F, m.b, m.LQ, m.iLQ, m.pot_mat);
     return m;
 }
 
@@ -191,25 +210,20 @@ template <typename R, typename M> static void fk_potbound(auxssm_ctx* h, const C
 // of the T steps into a.gtab ((2 D D + D + 4) reals per step: guided_tab_reals).  Rebuilt at every sweep: delta may change between sweeps.
 static size_t guided_tab_reals(int T, int D) { return (size_t)T * ((size_t)2 * D * D + D + 4); }
 template <typename R, typename M> static void fk_guided(auxssm_ctx* h, const CsmcArgs& a, const M& m) {
-    if (m.gradient && m.potential == AUXSSM_POT_LIN_GAUSS) {
-        const long long total = (long long)a.C * a.T;
-        hipLaunchKernelGGL((k_csmc_gshift_mvt<R, M, true>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, h->stream, a, m);
-    } else if (m.gradient && m.potential == AUXSSM_POT_MVT) {
-        const long long total = (long long)a.C * a.T;
-        hipLaunchKernelGGL((k_csmc_gshift_mvt<R, M>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, h->stream, a, m);
-    } else if (m.gradient) {
-        const long long total = (long long)a.C * a.T * m.D;
-        hipLaunchKernelGGL((k_csmc_gshift<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, m.D, m.potential, m.inv_sig_y);
-    }
+    if (m.gradient)
+        with_pot(m.potential, [&](auto pv) {
+            constexpr PotV V = decltype(pv)::value;
+            const long long total = (long long)a.C * a.T;
+            if constexpr (V != PotV::SEP) hipLaunchKernelGGL((k_csmc_gshift_coupled<R, M, V>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, h->stream, a, m);
+            else hipLaunchKernelGGL((k_csmc_gshift<R>), dim3((unsigned)((total * m.D + 255) / 256)), dim3(256), 0, h->stream, a, m.D, m.potential, m.inv_sig_y);
+        });
     hipLaunchKernelGGL((k_csmc_gtab<R, M>), dim3(a.T), dim3(64), 0, h->stream, a.T, m, (const R*)a.shd, (R*)a.gtab);
 }
 
 // the gradient launch of the built-in family on the register kernels (csmc.hip::run_csmc, pit.hip::run_pit)
 template <typename R, int D> static int builtin_grad(auxssm_ctx* h, const CsmcArgs& a, const FkDev<R>& m) {
     const dim3 grid((unsigned)(((long long)a.C * a.T + 255) / 256));
-    if (m.potential == AUXSSM_POT_LIN_GAUSS) hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, false, true>>), grid, dim3(256), 0, h->stream, a, m);
-    else if (m.potential == AUXSSM_POT_MVT) hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, true>>), grid, dim3(256), 0, h->stream, a, m);
-    else hipLaunchKernelGGL((k_csmc_grad<R, D>), grid, dim3(256), 0, h->stream, a, m);
+    with_pot(m.potential, [&](auto pv) { hipLaunchKernelGGL((k_csmc_grad<R, D, FkBuiltin<R, D, decltype(pv)::value>>), grid, dim3(256), 0, h->stream, a, m); });
     return AUXSSM_OK;
 }
 

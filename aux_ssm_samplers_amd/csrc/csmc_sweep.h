@@ -24,11 +24,11 @@ template <typename R> struct FkDev {
     const R* ctt;  // (T-1) additive constants of the transition densities (k_csmc_ctrans)
     const R* idt;  // (T-1, D) reciprocal diagonals of LQt (k_csmc_ctrans)
     int gradient;  // AUXSSM_GRAD_*
-    // AUXSSM_POT_MVT (potential == 4): the precision matrix (leading dimension CS_MAXD) and the two constants (nu + D) / 2 and 1 / nu, formed on the host in R
-    // AUXSSM_POT_LIN_GAUSS (potential == 5) shares the storage -- one potential is live per model: prec holds the whitened observation matrix Hw (rows beyond dy
-    // zero), c_obs the constant c_lin
-    R prec[CS_MAXD * CS_MAXD];
+    // the matrix of a coupled potential (leading dimension CS_MAXD; one potential is live per model) -- AUXSSM_POT_MVT: the precision matrix, with the two constants
+    // (nu + D) / 2 and 1 / nu below, formed on the host in R; AUXSSM_POT_LIN_GAUSS: the whitened observation matrix Hw (rows beyond dy zero), with c_lin in c_obs
+    R pot_mat[CS_MAXD * CS_MAXD];
     R mvt_hc, mvt_inv_nu;
+    AXD_HD constexpr int mat_ld() const { return CS_MAXD; }  // the leading dimension of the struct's matrices
 };
 // the transition t -> t+1 of the model: matrices through pointers (wave-uniform loads when time-varying)
 template <typename R> struct TransT {
@@ -191,78 +191,112 @@ template <typename R, int D> AXD_HD void trans_mean(const FkDev<R>& m, const R* 
         mu[k] = acc;
     }
 }
-// The multivariate Student-t potential (AUXSSM_POT_MVT; examples/spatial/t_distribution.py:98-104 with model.py:121-124), the ONE definition every kernel
-// family uses.  r = x - y;  z = prec r (row k: fma over j ascending from 0);  q = sum_k fma(z_k, r_k, .) (k ascending from 0);  s = 1 + q / nu.
-// mvt_quad returns s and leaves z; the value is -((nu + D) / 2) det_log(s) with NaN -> 0, the gradient (-(hc + hc) inv_nu / s) z, every component 0 where s is NaN.
-template <typename R, int D> AXD_HD R mvt_quad(const R* P, int ld, R inv_nu, const R* x, const R* y, R* z) {
-    R r[D];
+// ---- the built-in potentials ----------------------------------------------------------------------------------------------------------------------
+// The kinds (the values of AUXSSM_POT_* of include/auxssm.h, which hipRTC cannot include: csmc_host.h asserts that they agree) and their compile-time VARIANT:
+// the separable kinds share one code path and are told apart at run time inside it; a potential that couples the components through a dx x dx matrix
+// (FkDev::pot_mat) is a variant of its own, so that the instantiations of the other potentials hold none of its code -- as a fifth run-time branch the
+// multivariate-t potential cost every forward instantiation twelve registers in fp64 and a wave of occupancy.
+enum { POT_FLAT = 0, POT_GAUSS_OBS = 1, POT_SV = 2, POT_GAUSS_OBS_MASKED = 3, POT_MVT = 4, POT_LIN_GAUSS = 5 };
+enum class PotV { SEP, MVT, LIN };  // separable (kinds 0 - 3) | multivariate Student-t | linear-Gaussian observation
+template <PotV V> struct PotC { static constexpr PotV value = V; };
+AXD_HD constexpr PotV pot_variant(int kind) { return kind == POT_MVT ? PotV::MVT : (kind == POT_LIN_GAUSS ? PotV::LIN : PotV::SEP); }
+// f(PotC<V>{}) for the variant V of a run-time kind: the ONE place a kind becomes a template argument (host: the kernel choices; device: potential_rt)
+template <typename F> AXD_HD auto with_pot(int kind, F&& f) {
+    if (pot_variant(kind) == PotV::MVT) return f(PotC<PotV::MVT>{});
+    if (pot_variant(kind) == PotV::LIN) return f(PotC<PotV::LIN>{});
+    return f(PotC<PotV::SEP>{});
+}
+
+constexpr int CS_MAXD_RT = 32;  // the widest state of a caller with a run-time dimension (csmc_wide.hip, csmc_guided.h)
+// f(k) for k = 0 .. D - 1, D = DC when the dimension is a compile-time constant (DC > 0: the register kernels, fully unrolled) and d otherwise
+template <int DC, typename F> AXD_HD void for_dim(int d, F&& f) {
+    if constexpr (DC > 0) {
 #pragma unroll
-    for (int k = 0; k < D; ++k) r[k] = x[k] - y[k];
-    R q = 0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        R acc = 0;
-#pragma unroll
-        for (int j = 0; j < D; ++j) acc = fma_(P[k * ld + j], r[j], acc);
-        z[k] = acc;
+        for (int k = 0; k < DC; ++k) f(k);
+    } else {
+        for (int k = 0; k < d; ++k) f(k);
     }
-#pragma unroll
-    for (int k = 0; k < D; ++k) q = fma_(z[k], r[k], q);
-    return (R)1 + q * inv_nu;
+}
+// The coupled potentials, the ONE definition of their arithmetic: every kernel family calls it (the register kernels with DC = D, the wide-state gradient and the
+// guided shift with DC = 0 and the run-time dimension m.D; the half-wave form of csmc_wide.hip::coupled_half lays the same operations across lanes).  A: the
+// potential's matrix, leading dimension ld (CS_MAXD for FkDev, D for csmc_wide.hip's FkW); m: the model, for the constants.  The order is include/auxssm.h's:
+//   MVT (examples/spatial/t_distribution.py:98-104 with model.py:121-124; A = the precision matrix):  r = x - y;  z = A r (row k: fma over j ascending from 0);
+//       q = sum_k fma(z_k, r_k, .) (k ascending from 0);  s = 1 + q / nu.  Value -((nu + D) / 2) det_log(s) with NaN -> 0; gradient component k = c z_k with
+//       c = -(hc + hc) inv_nu / s = -(nu + D) / (nu + q), every component 0 where s is NaN (a missing observation: the step is flat).
+//   LIN (log N(y_t; H x + c, R) whitened on the host into c_lin - |yw_t - Hw x|^2 / 2; A = Hw, dx x dx with zero rows beyond dy, yw zero beyond dy: those
+//       components add fma(0, 0, .)):  a_k = row k of A times x (fma over j ascending from 0);  z_k = yw_k - a_k;  q = sum_k fma(z_k, z_k, .) (k ascending from 0).
+//       Value c_lin - q / 2 with NaN -> 0 (a missing observation row is all NaN); gradient A^T z (component j: fma over k ascending from 0), every component 0
+//       where the value is NaN.
+// coupled_resid leaves z and returns s (MVT) or q (LIN).
+template <typename R, PotV V, int DC> AXD_HD R coupled_resid(int d, const R* A, int ld, R inv_nu, const R* x, const R* y, R* z) {
+    R q = 0;
+    if constexpr (V == PotV::MVT) {
+        R r[DC > 0 ? DC : CS_MAXD_RT];
+        for_dim<DC>(d, [&](int k) { r[k] = x[k] - y[k]; });
+        for_dim<DC>(d, [&](int k) {
+            R acc = 0;
+            for_dim<DC>(d, [&](int j) { acc = fma_(A[k * ld + j], r[j], acc); });
+            z[k] = acc;
+        });
+        for_dim<DC>(d, [&](int k) { q = fma_(z[k], r[k], q); });
+        return (R)1 + q * inv_nu;
+    } else {
+        for_dim<DC>(d, [&](int k) {
+            R acc = 0;
+            for_dim<DC>(d, [&](int j) { acc = fma_(A[k * ld + j], x[j], acc); });
+            z[k] = y[k] - acc;
+        });
+        for_dim<DC>(d, [&](int k) { q = fma_(z[k], z[k], q); });
+        return q;
+    }
 }
 template <typename R> AXD_HD R mvt_value(R hc, R s) {
     const R v = -hc * det_log(s);
     return (v == v) ? v : (R)0;
-}
-// the gradient: component k is c z_k with c = -(nu + D) / nu / s = -(nu + D) / (nu + q), and 0 where s is NaN (a missing observation: the step is flat)
-template <typename R> AXD_HD R mvt_grad_coef(R hc, R inv_nu, R s) { return -((hc + hc) * inv_nu) / s; }
-template <typename R> AXD_HD R mvt_grad_term(R c, R s, R zk) { return (s == s) ? c * zk : (R)0; }
-// The linear-Gaussian observation potential (AUXSSM_POT_LIN_GAUSS): log N(y_t; H x + c, R) whitened on the host into c_lin - |yw_t - Hw x|^2 / 2, the ONE definition
-// every kernel family uses.  a_k = row k of Hw times x (fma over j ascending from 0);  z_k = yw_k - a_k;  q = sum_k fma(z_k, z_k, .) (k ascending from 0).
-// lin_resid leaves z and returns q; the value is c_lin - q / 2 with NaN -> 0 (a missing observation row is all NaN), the gradient Hw^T z (component j: fma over k
-// ascending from 0), every component 0 where the value is NaN.  Hw is dx x dx with zero rows beyond dy and yw zero beyond dy: those components add fma(0, 0, .).
-template <typename R, int D> AXD_HD R lin_resid(const R* H, int ld, const R* x, const R* y, R* z) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        R acc = 0;
-#pragma unroll
-        for (int j = 0; j < D; ++j) acc = fma_(H[k * ld + j], x[j], acc);
-        z[k] = y[k] - acc;
-    }
-    R q = 0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) q = fma_(z[k], z[k], q);
-    return q;
 }
 template <typename R> AXD_HD R lin_raw(R c_lin, R q) { return fma_((R)-0.5, q, c_lin); }  // (q / 2 is exact: this is c_lin - q / 2 rounded once)
 template <typename R> AXD_HD R lin_value(R c_lin, R q) {
     const R v = lin_raw<R>(c_lin, q);
     return (v == v) ? v : (R)0;
 }
-template <typename R, int D> AXD_HD void lin_grad(const R* H, int ld, R v, const R* z, R* gx) {
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        R acc = 0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) acc = fma_(H[k * ld + j], z[k], acc);
-        gx[j] = (v == v) ? acc : (R)0;
+template <typename R, PotV V, int DC, typename M> AXD_HD R coupled_value(const M& m, const R* A, int ld, const R* x, const R* y) {
+    R z[DC > 0 ? DC : CS_MAXD_RT];
+    if constexpr (V == PotV::MVT) return mvt_value<R>(m.mvt_hc, coupled_resid<R, V, DC>(m.D, A, ld, m.mvt_inv_nu, x, y, z));
+    else return lin_value<R>(m.c_obs, coupled_resid<R, V, DC>(m.D, A, ld, m.mvt_inv_nu, x, y, z));
+}
+// the gradient at x, component by component: out(k, d log g / d x_k)
+template <typename R, PotV V, int DC, typename M, typename O> AXD_HD void coupled_grad(const M& m, const R* A, int ld, const R* x, const R* y, O&& out) {
+    R z[DC > 0 ? DC : CS_MAXD_RT];
+    const R sq = coupled_resid<R, V, DC>(m.D, A, ld, m.mvt_inv_nu, x, y, z);
+    if constexpr (V == PotV::MVT) {
+        const R c = -((m.mvt_hc + m.mvt_hc) * m.mvt_inv_nu) / sq;
+        for_dim<DC>(m.D, [&](int k) { out(k, (sq == sq) ? c * z[k] : (R)0); });
+    } else {
+        const R v = lin_raw<R>(m.c_obs, sq);
+        for_dim<DC>(m.D, [&](int j) {
+            R acc = 0;
+            for_dim<DC>(m.D, [&](int k) { acc = fma_(A[k * ld + j], z[k], acc); });
+            out(j, (v == v) ? acc : (R)0);
+        });
     }
 }
-// potential g_t(x_t) (csmc test fixtures test_csmc/common.py:52-75; SV examples/stochastic_volatility/auxiliary_csmc.py:40-46)
-// MV: the multivariate-t potential, chosen at COMPILE time -- as a fifth run-time branch it cost every forward instantiation of the other potentials twelve
-// registers in fp64 and a wave of occupancy, so the instantiations of the other potentials (MV = false) hold none of its code; potential_rt
-// below is the run-time choice for the callers that are not register-bound.  LG: the linear-Gaussian observation potential, a compile-time variant in the same way
-template <typename R, int D, bool MV = false, bool LG = false> AXD_HD R potential(const FkDev<R>& m, const R* x, const R* y) {
-    if constexpr (LG) {
-        R z[D];
-        return lin_value<R>(m.c_obs, lin_resid<R, D>(m.prec, CS_MAXD, x, y, z));
+// d / dx_k of a separable potential (kinds 0 - 3: sums over the components): the ONE definition (potential_grad, csmc_wide.hip::k_cw_grad, csmc_guided.h::k_csmc_gshift)
+template <typename R> AXD_HD R sep_grad_term(int kind, R inv_sig_y, R xk, R yk) {
+    R v = 0;
+    if (kind == POT_GAUSS_OBS || (kind == POT_GAUSS_OBS_MASKED && yk - yk == 0)) v = ((yk - xk) * inv_sig_y) * inv_sig_y;
+    else if (kind == POT_SV) {
+        const R e = det_exp(-xk);
+        v = (R)0.5 * fma_(yk * yk, e, (R)-1);
+        v = (v == v) ? v : (R)0;
     }
-    if constexpr (MV) {
-        R z[D];
-        return mvt_value<R>(m.mvt_hc, mvt_quad<R, D>(m.prec, CS_MAXD, m.mvt_inv_nu, x, y, z));
-    }
-    if (m.potential == 0) return (R)0;
-    if (m.potential == 1) {  // y ~ N(x, sig_y^2 I)
+    return v;
+}
+// potential g_t(x_t) (csmc test fixtures test_csmc/common.py:52-75; SV examples/stochastic_volatility/auxiliary_csmc.py:40-46) of the variant V, chosen at
+// COMPILE time; potential_rt below is the run-time choice for the callers that are not register-bound
+template <typename R, int D, PotV V = PotV::SEP> AXD_HD R potential(const FkDev<R>& m, const R* x, const R* y) {
+    if constexpr (V != PotV::SEP) return coupled_value<R, V, D>(m, m.pot_mat, CS_MAXD, x, y);
+    if (m.potential == POT_FLAT) return (R)0;
+    if (m.potential == POT_GAUSS_OBS) {  // y ~ N(x, sig_y^2 I)
         R q = 0;
 #pragma unroll
         for (int k = 0; k < D; ++k) {
@@ -271,7 +305,7 @@ template <typename R, int D, bool MV = false, bool LG = false> AXD_HD R potentia
         }
         return fma_((R)-0.5, q, m.c_obs);
     }
-    if (m.potential == 3) {  // y_k ~ N(x_k, sig_y^2) for the finite y_k only (missing components / whole missing steps are skipped)
+    if (m.potential == POT_GAUSS_OBS_MASKED) {  // y_k ~ N(x_k, sig_y^2) for the finite y_k only (missing components / whole missing steps are skipped)
         R q = 0;
         int nobs = 0;
 #pragma unroll
@@ -296,43 +330,20 @@ template <typename R, int D, bool MV = false, bool LG = false> AXD_HD R potentia
     return acc;
 }
 // gx = d potential / dx at x (the closed family's potentials do not read x_{t-1}); y = the D reals of row t, or nullptr
-template <typename R, int D, bool MV = false, bool LG = false> __device__ __forceinline__ void potential_grad(const FkDev<R>& m, const R* x, const R* y, R* gx) {
-    if constexpr (LG) {  // (couples the components through Hw)
-        R z[D];
-        const R q = lin_resid<R, D>(m.prec, CS_MAXD, x, y, z);
-        lin_grad<R, D>(m.prec, CS_MAXD, lin_raw<R>(m.c_obs, q), z, gx);
-        return;
-    }
-    if constexpr (MV) {  // (the one potential that couples the components)
-        R z[D];
-        const R s = mvt_quad<R, D>(m.prec, CS_MAXD, m.mvt_inv_nu, x, y, z), c = mvt_grad_coef<R>(m.mvt_hc, m.mvt_inv_nu, s);
+template <typename R, int D, PotV V = PotV::SEP> __device__ __forceinline__ void potential_grad(const FkDev<R>& m, const R* x, const R* y, R* gx) {
+    if constexpr (V != PotV::SEP) {
+        coupled_grad<R, V, D>(m, m.pot_mat, CS_MAXD, x, y, [&](int k, R v) { gx[k] = v; });
+    } else {
 #pragma unroll
-        for (int k = 0; k < D; ++k) gx[k] = mvt_grad_term<R>(c, s, z[k]);
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const R yk = y ? y[k] : (R)0;
-        R v = 0;
-        if (m.potential == 1 || (m.potential == 3 && yk - yk == 0)) v = ((yk - x[k]) * m.inv_sig_y) * m.inv_sig_y;
-        else if (m.potential == 2) {
-            const R e = det_exp(-x[k]);
-            v = (R)0.5 * fma_(yk * yk, e, (R)-1);
-            v = (v == v) ? v : (R)0;
-        }
-        gx[k] = v;
+        for (int k = 0; k < D; ++k) gx[k] = sep_grad_term<R>(m.potential, m.inv_sig_y, x[k], y ? y[k] : (R)0);
     }
 }
-// the potential kind of m at run time, the multivariate-t and the linear-Gaussian observation potential included (the parallel-in-time kernels, a user program that keeps the built-in potential)
+// the potential kind of m at run time, the coupled variants included (the parallel-in-time kernels, a user program that keeps the built-in potential)
 template <typename R, int D> __device__ __forceinline__ R potential_rt(const FkDev<R>& m, const R* x, const R* y) {
-    if (m.potential == 4) return potential<R, D, true>(m, x, y);
-    if (m.potential == 5) return potential<R, D, false, true>(m, x, y);
-    return potential<R, D, false>(m, x, y);
+    return with_pot(m.potential, [&](auto pv) { return potential<R, D, decltype(pv)::value>(m, x, y); });
 }
 template <typename R, int D> __device__ __forceinline__ void potential_grad_rt(const FkDev<R>& m, const R* x, const R* y, R* gx) {
-    if (m.potential == 4) potential_grad<R, D, true>(m, x, y, gx);
-    else if (m.potential == 5) potential_grad<R, D, false, true>(m, x, y, gx);
-    else potential_grad<R, D, false>(m, x, y, gx);
+    with_pot(m.potential, [&](auto pv) { potential_grad<R, D, decltype(pv)::value>(m, x, y, gx); });
 }
 // out = J^T v, J = d mean / d xp of the transition tr (trans_mean_t): F^T, or the Lorenz-63 step's I + dt dphi/dx (examples/lorenz/model.py:10-25)
 template <typename R, int D> __device__ __forceinline__ void trans_mean_vjp_t(const FkDev<R>& m, const TransT<R>& tr, const R* xp, const R* v, R* out) {
@@ -702,14 +713,14 @@ template <typename R> struct FkUser {
 //   pol.grad_log_g(m, t, x, xprev, y, gx, gxprev)   gx = d log G_t / dx, gxprev = d log G_t / dxprev (nullptr at t = 0); both zero-filled by the caller
 //   pol.mean_vjp(m, tr, t, xprev, v, out)           out = J^T v, J = d pol.mean(m, tr, t, xprev) / d xprev
 //   P::grad_xprev                                   whether log G_t may depend on xprev (false: k_csmc_grad adds no d / dxprev term)
-// FkBuiltin is the closed family of include/auxssm.h, dispatched on the integers of FkDev (the kernels of csmc.hip), FkBuiltin<R, D, true> the same with the
-// multivariate-t potential fixed at compile time (potential<R, D, MV> above), FkBuiltin<R, D, false, true> with the linear-Gaussian observation potential; fk_user.h's FkUserPolicy calls
-// device functions of a user's source (fk_program.hip).  The backward pass evaluates the Gaussian transition density around pol.mean.
-template <typename R, int D, bool MV = false, bool LG = false> struct FkBuiltin {
+// FkBuiltin is the closed family of include/auxssm.h, dispatched on the integers of FkDev (the kernels of csmc.hip), FkBuiltin<R, D, V> the same with a coupled
+// potential fixed at compile time (potential<R, D, V> above); fk_user.h's FkUserPolicy calls device functions of a user's source (fk_program.hip).  The backward
+// pass evaluates the Gaussian transition density around pol.mean.
+template <typename R, int D, PotV V = PotV::SEP> struct FkBuiltin {
     static constexpr bool grad_xprev = false;
-    __device__ __forceinline__ R log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y) const { return potential<R, D, MV, LG>(m, x, y); }
+    __device__ __forceinline__ R log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y) const { return potential<R, D, V>(m, x, y); }
     __device__ __forceinline__ void mean(const FkDev<R>& m, const TransT<R>& tr, int, const R* xp, R* mu) const { trans_mean_t<R, D>(m, tr, xp, mu); }
-    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y, R* gx, R*) const { potential_grad<R, D, MV, LG>(m, x, y, gx); }
+    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y, R* gx, R*) const { potential_grad<R, D, V>(m, x, y, gx); }
     __device__ __forceinline__ void mean_vjp(const FkDev<R>& m, const TransT<R>& tr, int, const R* xp, const R* v, R* out) const {
         trans_mean_vjp_t<R, D>(m, tr, xp, v, out);
     }

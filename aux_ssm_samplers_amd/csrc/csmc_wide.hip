@@ -10,10 +10,9 @@
 // exposes --gradient at D = 30) and time-varying transitions (the step's F_t, b_t, chol Q_t re-staged into LDS before the step's first barrier) since round 4.
 // Guided proposals (AUXSSM_PROP_AUX_GUIDED, csmc_sweep.h::GuidedT) are a compile-time variant of the forward kernel (k_cw2_fwd<R, NW2, true>): the step's K_t and chol Lambda_t staged
 // into LDS like a time-varying transition, one more row product and one more blocked log-density per particle; the backward kernel is shared.
-// The multivariate-t potential (AUXSSM_POT_MVT, csmc_sweep.h::mvt_quad) is a compile-time variant in the same way (k_cw2_fwd<R, NW2, GD, true>): its precision matrix staged
-// once per workgroup, one more row product per particle (mvt_half); its sweeps carry no bound array (csmc.hip), every step shifts by its exact maximum.
-// The linear-Gaussian observation potential (AUXSSM_POT_LIN_GAUSS, csmc_sweep.h::lin_resid) is the next such variant (k_cw2_fwd<R, NW2, GD, false, true>): its whitened
-// observation matrix in the precision matrix's LDS slot and layout, the same row product (lin_half), no bound array either.
+// A coupled potential (csmc_sweep.h::PotV: the multivariate-t potential AUXSSM_POT_MVT, the linear-Gaussian observation potential AUXSSM_POT_LIN_GAUSS) is a compile-time
+// variant in the same way (k_cw2_fwd<R, NW2, GD, V>): its matrix (the precision matrix / the whitened observation matrix) staged once per workgroup, one more row
+// product per particle (coupled_half); its sweeps carry no bound array (csmc.hip), every step shifts by its exact maximum.
 // (The first version of this file -- one wave per chain, one lane per particle walking its dx x dx products alone: 30.5 ms per sweep of the SV protocol against
 // 2.6 now -- is in the history)
 //
@@ -35,9 +34,9 @@ template <typename R> struct FkW {
     R c_init, c_trans, c_obs, inv_sig_y;
     int gradient;                          // AUXSSM_GRAD_*
     const R *Ft, *bt, *LQt, *ctt, *idt;    // time-varying transitions (csmc_sweep.h::FkDev: row t = transition t -> t + 1), or null
-    const R* prec;                         // AUXSSM_POT_MVT: the precision matrix (device, leading dimension D) and the constants (nu + D) / 2, 1 / nu;
-                                           // AUXSSM_POT_LIN_GAUSS: the whitened observation matrix Hw (rows beyond dy zero), c_lin in c_obs
+    const R* pot_mat;                      // the matrix of a coupled potential (device, leading dimension D; csmc_sweep.h::FkDev::pot_mat), or null
     R mvt_hc, mvt_inv_nu;
+    AXD_HD int mat_ld() const { return D; }  // the leading dimension of the matrices
 };
 // the transition t -> t + 1 in global memory (gradient kernel; the sweep kernels read it from LDS)
 template <typename R> struct TransW {
@@ -45,7 +44,6 @@ template <typename R> struct TransW {
 };
 // element (i, j) of chol P0 (init) or chol Q (csmc_guided.h::k_csmc_gtab)
 template <typename R> __device__ __forceinline__ R gt_chol(const FkW<R>& m, bool init, int i, int j) { return (init ? m.LP0 : m.LQ)[i * m.D + j]; }
-template <typename R> __device__ __forceinline__ R mvt_prec(const FkW<R>& m, int i, int j) { return m.prec[i * m.D + j]; }
 template <typename R> __device__ __forceinline__ TransW<R> trans_w(const FkW<R>& m, long long t) {
     const long long D = m.D;
     if (m.Ft) return TransW<R>{m.Ft + t * D * D, m.bt + t * D, m.LQt + t * D * D};
@@ -87,9 +85,8 @@ template <typename R> __device__ __forceinline__ void cho_solve_w(int D, const R
 }
 // the gradient of the model's joint log-density at u (csmc_sweep.h::k_csmc_grad, same operations in the same order; one thread per (chain, time step):
 // C T threads of O(dx^2) work, once per sweep -- 0.5 M multiply-adds at the SV protocol's size)
-// MV: the multivariate-t potential's gradient (a compile-time variant: its z[32] would otherwise add scratch to the kernel of the other potentials)
-// LG: the linear-Gaussian observation potential's gradient Hw^T (yw - Hw u), a compile-time variant for the same reason
-template <typename R, bool MV = false, bool LG = false> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
+// V: a coupled potential's gradient is a compile-time variant (its z[32] would otherwise add scratch to the kernel of the other potentials)
+template <typename R, PotV V = PotV::SEP> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)a.C * a.T) return;
     const int D = m.D;
@@ -97,45 +94,10 @@ template <typename R, bool MV = false, bool LG = false> __global__ void k_cw_gra
     const R* u = (const R*)a.u + g * D;
     R gr[CSW_MAXD], r[CSW_MAXD], w[CSW_MAXD];
     const R* yv = (const R*)a.y;
-    if constexpr (LG) {  // csmc_sweep.h::potential_grad's branch (lin_resid / lin_raw / lin_grad) with a runtime dimension
-        R z[CSW_MAXD];
-        for (int k = 0; k < D; ++k) {
-            R acc = 0;
-            for (int j = 0; j < D; ++j) acc = fma_(m.prec[k * D + j], u[j], acc);
-            z[k] = yv[t * D + k] - acc;
-        }
-        R q = 0;
-        for (int k = 0; k < D; ++k) q = fma_(z[k], z[k], q);
-        const R v = lin_raw<R>(m.c_obs, q);
-        for (int j = 0; j < D; ++j) {
-            R acc = 0;
-            for (int k = 0; k < D; ++k) acc = fma_(m.prec[k * D + j], z[k], acc);
-            gr[j] = (v == v) ? acc : (R)0;
-        }
-    } else if constexpr (MV) {  // multivariate Student-t: csmc_sweep.h::potential_grad's branch (mvt_quad / mvt_grad_coef) with a runtime dimension
-        R z[CSW_MAXD];
-        for (int k = 0; k < D; ++k) r[k] = u[k] - yv[t * D + k];
-        R q = 0;
-        for (int k = 0; k < D; ++k) {
-            R acc = 0;
-            for (int j = 0; j < D; ++j) acc = fma_(m.prec[k * D + j], r[j], acc);
-            z[k] = acc;
-        }
-        for (int k = 0; k < D; ++k) q = fma_(z[k], r[k], q);
-        const R sq = (R)1 + q * m.mvt_inv_nu, c = mvt_grad_coef<R>(m.mvt_hc, m.mvt_inv_nu, sq);
-        for (int k = 0; k < D; ++k) gr[k] = mvt_grad_term<R>(c, sq, z[k]);
+    if constexpr (V != PotV::SEP) {
+        coupled_grad<R, V, 0>(m, m.pot_mat, D, u, yv + t * D, [&](int k, R v) { gr[k] = v; });
     } else {
-        for (int k = 0; k < D; ++k) {
-            const R y = yv ? yv[t * D + k] : (R)0;
-            R v = 0;
-            if (m.potential == 1 || (m.potential == 3 && y - y == 0)) v = ((y - u[k]) * m.inv_sig_y) * m.inv_sig_y;
-            else if (m.potential == 2) {
-                const R e = det_exp(-u[k]);
-                v = (R)0.5 * fma_(y * y, e, (R)-1);
-                v = (v == v) ? v : (R)0;
-            }
-            gr[k] = v;
-        }
+        for (int k = 0; k < D; ++k) gr[k] = sep_grad_term<R>(m.potential, m.inv_sig_y, u[k], yv ? yv[t * D + k] : (R)0);
     }
     if (t == 0) {
         for (int k = 0; k < D; ++k) r[k] = u[k] - m.m0[k];
@@ -182,9 +144,8 @@ template <typename R> struct Cw2Lds {
     R *F, *LQ, *b, *iL, *c, *lwv, *xa, *xb, *eps, *blk;
     int* idx;
     R *Kg, *Lg, *blkg, *dv;  // guided proposals only (behind idx): the step's K_t and chol Lambda_t, the block table of chol Lambda_t, u~ - pred of every half-wave
-    R* Pm;                   // multivariate-t potential only (behind everything else): the precision matrix, rows zero-padded like F's (the linear-Gaussian
-                             // observation potential: its whitened observation matrix in the same slot)
-    __device__ Cw2Lds(char* smem, int D_, bool guided = false, bool mvt = false) : D(D_), S(CSW_MAXD + 1) {  // rows padded with zeros to 32 columns (+ 1: odd stride): every component loop runs 32 steps, unrolled
+    R* pot_mat;              // coupled potentials only (behind everything else): the potential's matrix, rows zero-padded like F's
+    __device__ Cw2Lds(char* smem, int D_, bool guided = false, bool coupled = false) : D(D_), S(CSW_MAXD + 1) {  // rows padded with zeros to 32 columns (+ 1: odd stride): every component loop runs 32 steps, unrolled
         F = (R*)smem;           // [D][S]
         LQ = F + D * S;         // [D][S]
         b = LQ + D * S;
@@ -202,17 +163,17 @@ template <typename R> struct Cw2Lds {
             blkg = Lg + D * S;    // [8][12]
             dv = blkg + 96;       // [32][S]
         }
-        if (mvt) Pm = guided ? dv + 32 * S : (R*)(idx + 64);  // [D][S]
+        if (coupled) pot_mat = guided ? dv + 32 * S : (R*)(idx + 64);  // [D][S]
     }
-    static constexpr size_t mvt_bytes(int D) { return (size_t)D * (CSW_MAXD + 1) * sizeof(R); }
+    static constexpr size_t pot_mat_bytes(int D) { return (size_t)D * (CSW_MAXD + 1) * sizeof(R); }
     static constexpr size_t guided_bytes(int D) { return ((size_t)2 * D * (CSW_MAXD + 1) + 96 + (size_t)32 * (CSW_MAXD + 1)) * sizeof(R); }
     static constexpr size_t bytes(int D) { return ((size_t)2 * D * (CSW_MAXD + 1) + 2 * D + 128 + (size_t)3 * 64 * (CSW_MAXD + 1) + 96) * sizeof(R) + 64 * sizeof(int) + 64; }
-    // the forward pass's plan: guided adds two D x 33 matrices, one block table and 32 rows of u~ - pred (96 320 bytes in all at dx = 32 in fp64), the
-    // multivariate-t potential its D x 33 precision matrix (with the guided tables 104 768 bytes, the largest plan of this file)
-    static constexpr size_t fwd_bytes(int D, bool guided, bool mvt) { return bytes(D) + (guided ? guided_bytes(D) : 0) + (mvt ? mvt_bytes(D) : 0); }
+    // the forward pass's plan: guided adds two D x 33 matrices, one block table and 32 rows of u~ - pred (96 320 bytes in all at dx = 32 in fp64), a coupled
+    // potential its D x 33 matrix (with the guided tables 104 768 bytes, the largest plan of this file)
+    static constexpr size_t fwd_bytes(int D, bool guided, bool coupled) { return bytes(D) + (guided ? guided_bytes(D) : 0) + (coupled ? pot_mat_bytes(D) : 0); }
 };
 static_assert(Cw2Lds<double>::fwd_bytes(CSW_MAXD, true, false) <= 160 * 1024, "the guided forward pass must fit the 160 KB of LDS of a CU");
-static_assert(Cw2Lds<double>::fwd_bytes(CSW_MAXD, true, true) <= 160 * 1024, "the guided forward pass with the multivariate-t potential must fit the 160 KB of LDS of a CU");
+static_assert(Cw2Lds<double>::fwd_bytes(CSW_MAXD, true, true) <= 160 * 1024, "the guided forward pass with a coupled potential must fit the 160 KB of LDS of a CU");
 // entry `tid` (< 96) of the block table gauss_half_blk reads, for the lower factor Lf (leading dimension D) with reciprocal diagonal iLf:
 // block jb = 4 (tid / 12): [L10 L20 L21 L30 L31 L32 | i0 i1 i2 i3 | 0 0], zeros beyond D
 template <typename R> __device__ __forceinline__ R cw2_blk_entry(const R* Lf, const R* iLf, int D, int tid) {
@@ -266,12 +227,12 @@ template <typename R> __device__ __forceinline__ void cw2_stage_g(const GuidedT<
     }
     if (tid < 96) L.blkg[tid] = cw2_blk_entry<R>(g.L, g.iL, D, tid);
 }
-// multivariate-t potential: the precision matrix into LDS, once per workgroup (it does not change over time), rows zero-padded to 32 columns
-template <typename R> __device__ __forceinline__ void cw2_stage_p(const FkW<R>& m, Cw2Lds<R>& L, int tid, int nt) {
+// coupled potentials: the potential's matrix into LDS, once per workgroup (it does not change over time), rows zero-padded to 32 columns
+template <typename R> __device__ __forceinline__ void cw2_stage_pot_mat(const FkW<R>& m, Cw2Lds<R>& L, int tid, int nt) {
     const int D = m.D, S = L.S;
     for (int i = tid; i < D * S; i += nt) {
         const int r = i / S, q = i - r * S;
-        L.Pm[i] = q < D ? m.prec[r * D + q] : (R)0;
+        L.pot_mat[i] = q < D ? m.pot_mat[r * D + q] : (R)0;
     }
 }
 // value of lane J of MY half-wave: ds_swizzle in bit mode (lane' = (lane & and) | or inside each group of 32 lanes, and = 0, or = J) -- one LDS-crossbar
@@ -355,8 +316,36 @@ template <typename R> __device__ __forceinline__ R gauss_half_blk(int D, int k, 
     });
     return fma_((R)-0.5, q, cst);
 }
-// g_t(x) of that particle: per-component terms in the lanes, summed in component order (csmc_sweep.h::potential with a runtime dimension, same operations)
-template <typename R> __device__ __forceinline__ R potential_half(const FkW<R>& m, int k, bool hi, R xk, R yk) {
+// a coupled potential of that particle (csmc_sweep.h::coupled_resid / coupled_value, same operations in the same order): with v = r = x - y (MVT) or v = x (LIN) in
+// the lane that owns the component, a_k = row k of the potential's matrix (Mrow: this lane's zero-padded LDS row) times v from half-wave broadcasts of v_j, j ascending;
+// z_k = a_k (MVT) or yw_k - a_k (LIN); q accumulated in component order by every lane alike from broadcasts of z_k and r_k (MVT) or of z_k alone (LIN).  Columns /
+// components beyond D contribute fma(0, 0, acc) = acc.
+template <typename R, PotV V> __device__ __forceinline__ R coupled_half(const FkW<R>& m, int k, R xk, R yk, const R* Mrow) {
+    constexpr bool MVT = V == PotV::MVT;
+    const int D = m.D;
+    const R v = k < D ? (MVT ? xk - yk : xk) : (R)0;
+    R p[CSW_MAXD];
+#pragma unroll
+    for (int j = 0; j < CSW_MAXD; ++j) p[j] = Mrow[j];
+    R a = 0;
+    static_for<0, CSW_MAXD>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        a = fma_(p[j], half_bcast<R, j>(v), a);
+    });
+    const R z = k < D ? (MVT ? a : yk - a) : (R)0;
+    R q = 0;
+    static_for<0, CSW_MAXD>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const R zj = half_bcast<R, j>(z);
+        q = fma_(zj, MVT ? half_bcast<R, j>(v) : zj, q);
+    });
+    if constexpr (MVT) return mvt_value<R>(m.mvt_hc, (R)1 + q * m.mvt_inv_nu);
+    else return lin_value<R>(m.c_obs, q);
+}
+// g_t(x) of that particle, the potential's variant V chosen at compile time.  Separable: per-component terms in the lanes, summed in component order
+// (csmc_sweep.h::potential with a runtime dimension, same operations)
+template <typename R, PotV V> __device__ __forceinline__ R potential_half(const FkW<R>& m, int k, bool hi, R xk, R yk, const R* Mrow) {
+    if constexpr (V != PotV::SEP) return coupled_half<R, V>(m, k, xk, yk, Mrow);
     const int D = m.D;
     if (m.potential == 0) return (R)0;
     if (m.potential == 1 || m.potential == 3) {
@@ -379,48 +368,6 @@ template <typename R> __device__ __forceinline__ R potential_half(const FkW<R>& 
     R acc = 0;
     static_for<0, CSW_MAXD>([&](auto jc) { acc += half_bcast<R, decltype(jc)::value>(v); });
     return acc;
-}
-// the multivariate Student-t potential of that particle (csmc_sweep.h::mvt_quad / mvt_value, same operations in the same order): r_k in the lane that owns
-// component k, z_k = row k of the precision matrix (Prow: this lane's zero-padded LDS row) times r from half-wave broadcasts of r_j, j ascending, and q accumulated in
-// component order by every lane alike from broadcasts of z_k and r_k.  Columns / components beyond D contribute fma(0, 0, acc) = acc.
-template <typename R> __device__ __forceinline__ R mvt_half(int D, int k, R xk, R yk, const R* Prow, R hc, R inv_nu) {
-    const R r = k < D ? xk - yk : (R)0;
-    R p[CSW_MAXD];
-#pragma unroll
-    for (int j = 0; j < CSW_MAXD; ++j) p[j] = Prow[j];
-    R z = 0;
-    static_for<0, CSW_MAXD>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        z = fma_(p[j], half_bcast<R, j>(r), z);
-    });
-    z = k < D ? z : (R)0;
-    R q = 0;
-    static_for<0, CSW_MAXD>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        q = fma_(half_bcast<R, j>(z), half_bcast<R, j>(r), q);
-    });
-    return mvt_value<R>(hc, (R)1 + q * inv_nu);
-}
-// the linear-Gaussian observation potential of that particle (csmc_sweep.h::lin_resid / lin_value, same operations in the same order): a_k = row k of Hw (Hrow: this
-// lane's zero-padded LDS row) times x from half-wave broadcasts of x_j, j ascending; z_k = yw_k - a_k in the lane that owns component k; q accumulated in component
-// order by every lane alike from broadcasts of z_k.  Columns / components beyond D contribute fma(0, 0, acc) = acc.
-template <typename R> __device__ __forceinline__ R lin_half(int D, int k, R xk, R yk, const R* Hrow, R c_lin) {
-    const R x = k < D ? xk : (R)0;
-    R p[CSW_MAXD];
-#pragma unroll
-    for (int j = 0; j < CSW_MAXD; ++j) p[j] = Hrow[j];
-    R a = 0;
-    static_for<0, CSW_MAXD>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        a = fma_(p[j], half_bcast<R, j>(x), a);
-    });
-    const R z = k < D ? yk - a : (R)0;
-    R q = 0;
-    static_for<0, CSW_MAXD>([&](auto jc) {
-        const R zj = half_bcast<R, decltype(jc)::value>(z);
-        q = fma_(zj, zj, q);
-    });
-    return lin_value<R>(c_lin, q);
 }
 // sum_k log N(x_k; u_k, s^2) = c_u - sum_k ((x_k - u_k) / s)^2 / 2 of the particle whose component k this lane holds (csmc_sweep.h::guided_weight: component order)
 template <typename R> __device__ __forceinline__ R nu_half(int D, int k, R xk, R uk, R inv_s, R c_u) {
@@ -460,17 +407,17 @@ template <typename R> __device__ __forceinline__ void cw2_draw(const CsmcArgs& a
 }
 
 // GD: the guided proposals, a compile-time variant; false: the kernel as it was, holding none of their code
-// MV: the multivariate-t potential (AUXSSM_POT_MVT), a compile-time variant in the same way: the precision matrix staged in LDS, mvt_half in place of potential_half
-// LG: the linear-Gaussian observation potential (AUXSSM_POT_LIN_GAUSS), the same with its whitened observation matrix in that slot and lin_half
-template <typename R, int NW2, bool GD = false, bool MV = false, bool LG = false> __global__ void __launch_bounds__(64 * NW2) k_cw2_fwd(CsmcArgs a, FkW<R> m) {
+// V: the potential's variant (csmc_sweep.h::PotV), a compile-time choice in the same way: a coupled potential has its matrix staged in LDS and coupled_half in place of
+// the separable sum (potential_half)
+template <typename R, int NW2, bool GD = false, PotV V = PotV::SEP> __global__ void __launch_bounds__(64 * NW2) k_cw2_fwd(CsmcArgs a, FkW<R> m) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT_ = 64 * NW2;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, N = a.N, T = a.T, D = m.D;
     const bool hi = lane >= 32;
     const int k = lane & 31;
-    static_assert(!(MV && LG), "one potential per kernel");
-    Cw2Lds<R> L(smem, D, GD, MV || LG);
-    if constexpr (MV || LG) cw2_stage_p<R>(m, L, tid, NT_);  // (published by cw2_stage's barrier)
+    constexpr bool coupled = V != PotV::SEP;
+    Cw2Lds<R> L(smem, D, GD, coupled);
+    if constexpr (coupled) cw2_stage_pot_mat<R>(m, L, tid, NT_);  // (published by cw2_stage's barrier)
     cw2_stage<R>(m, L, tid, NT_);
     const int S = L.S, nslot = (N + 2 * NW2 - 1) / (2 * NW2);
     const int ch = a.c0 + blockIdx.x;
@@ -493,7 +440,7 @@ template <typename R, int NW2, bool GD = false, bool MV = false, bool LG = false
     const R* Kgrow = GD ? L.Kg + (k < D ? k : 0) * S : nullptr;
     const R* Lgrow = GD ? L.Lg + (k < D ? k : 0) * S : nullptr;
     R* dvr = GD ? L.dv + (2 * wv + (hi ? 1 : 0)) * S : nullptr;
-    const R* Prow = (MV || LG) ? L.Pm + (k < D ? k : 0) * S : nullptr;
+    const R* Mrow = coupled ? L.pot_mat + (k < D ? k : 0) * S : nullptr;
 
     // ---- t = 0 (csmc.py:74-80)
     cw2_draw<R>(a, L, ch, 0, tid, NT_);
@@ -532,10 +479,7 @@ template <typename R, int NW2, bool GD = false, bool MV = false, bool LG = false
             acc0 = xk - m.m0[k];
         }
         const R yk = (yv && k < D) ? yv[k] : (R)0;
-        R g;
-        if constexpr (LG) g = lin_half<R>(D, k, xk, yk, Prow, m.c_obs);
-        else if constexpr (MV) g = mvt_half<R>(D, k, xk, yk, Prow, m.mvt_hc, m.mvt_inv_nu);
-        else g = potential_half<R>(m, k, hi, xk, yk);
+        R g = potential_half<R, V>(m, k, hi, xk, yk, Mrow);
         if (m.proposal == 1) g = g + gauss_half<R>(D, k, hi, acc0, m.LP0 + (long long)(k < D ? k : 0) * D, k < D ? m.iLP0[k] : (R)0, m.c_init);  // AuxiliaryG0
         if constexpr (GD) {  // log g + log N(x; m0, P0) + sum_k log N(x_k; u_k, s^2) - log N(x; mu, Lambda_0)
             const GuidedT<R> gd = guided_at<R>(a.gtab, D, 0);
@@ -638,10 +582,7 @@ template <typename R, int NW2, bool GD = false, bool MV = false, bool LG = false
                 if (i == 0) xk = xsk;
             }
             // weights (csmc.py:95-96)
-            R g;
-            if constexpr (LG) g = lin_half<R>(D, k, xk, yk, Prow, m.c_obs);
-            else if constexpr (MV) g = mvt_half<R>(D, k, xk, yk, Prow, m.mvt_hc, m.mvt_inv_nu);
-            else g = potential_half<R>(m, k, hi, xk, yk);
+            R g = potential_half<R, V>(m, k, hi, xk, yk, Mrow);
             if (m.proposal == 1) g = gauss_half_blk<R>(D, k, xk - mu, Lrow, L.blk, ctr) + g;  // AuxiliaryGt = Mt.logpdf + Gt (independent.py:238-248)
             // GradientAuxiliaryGt (:252-268): summed over the particles in the reference, i.e. a constant of the step (AUXSSM_GRAD_REFERENCE: nothing to add);
             // AUXSSM_GRAD_EXACT applies it per particle
@@ -782,37 +723,33 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
     }
 }
 
-// The passes of (model, sweep); wide16: fp32 and no more chains than CUs (run_cw).
-//   forward   guided                 k_cw2_fwd<R, 8, true, MV>                   eight waves whatever the chain count
-//             otherwise              k_cw2_fwd<R, wide16 ? 16 : 8, false, MV>
+// The passes of (model, sweep); wide16: fp32 and no more chains than CUs (run_cw); V: the variant of the model's potential (csmc_sweep.h::with_pot).
+//   forward   guided                 k_cw2_fwd<R, 8, true, V>                    eight waves whatever the chain count
+//             otherwise              k_cw2_fwd<R, wide16 ? 16 : 8, false, V>
 //   backward                         k_cw2_bwd<R, wide16 ? 16 : 8>               the base LDS plan (Cw2Lds::bytes)
-// MV: the multivariate-t potential; the linear-Gaussian observation potential takes the same rows with <..., false, true> (pk: 0 neither, 1 MV, 2 LG).
-// The forward pass's LDS is Cw2Lds::fwd_bytes(D, guided, pk != 0): the two potentials' matrices share one slot, so neither plan exceeds the other's.
+// The forward pass's LDS is Cw2Lds::fwd_bytes(D, guided, V != PotV::SEP): the coupled potentials' matrices share one slot, so neither plan exceeds the other's.
 // (guided: under the 128 registers of a 1024-lane workgroup the two extra row products and the second blocked density spill, 360 bytes per lane in fp32:
 // 7.47 ms against 5.11 ms per sweep of the SV protocol at 256 chains)
 template <typename R> using WideKernel = void (*)(CsmcArgs, FkW<R>);
-template <typename R> static WideKernel<R> cw_fwd_kernel(bool guided, int pk, bool wide16) {
-    if (pk == 2) {
-        if (guided) return k_cw2_fwd<R, 8, true, false, true>;
-        return wide16 ? k_cw2_fwd<R, 16, false, false, true> : k_cw2_fwd<R, 8, false, false, true>;
-    }
-    const bool mvt = pk == 1;
-    if (guided) return mvt ? k_cw2_fwd<R, 8, true, true> : k_cw2_fwd<R, 8, true>;
-    if (wide16) return mvt ? k_cw2_fwd<R, 16, false, true> : k_cw2_fwd<R, 16>;
-    return mvt ? k_cw2_fwd<R, 8, false, true> : k_cw2_fwd<R, 8>;
+template <typename R> static WideKernel<R> cw_fwd_kernel(bool guided, int potential, bool wide16) {
+    return with_pot(potential, [&](auto pv) -> WideKernel<R> {
+        constexpr PotV V = decltype(pv)::value;
+        if (guided) return k_cw2_fwd<R, 8, true, V>;
+        return wide16 ? k_cw2_fwd<R, 16, false, V> : k_cw2_fwd<R, 8, false, V>;
+    });
 }
 template <typename R> static WideKernel<R> cw_bwd_kernel(bool wide16) { return wide16 ? k_cw2_bwd<R, 16> : k_cw2_bwd<R, 8>; }
 
-// host: the model as one device block [m0 | LP0 | iLP0 | F | b | LQ | iLQ] (csmc_host.h::fk_model, leading dimension D)
+// host: the model as one device block [m0 | LP0 | iLP0 | F | b | LQ | iLQ | the matrix of a coupled potential] (csmc_host.h::fk_model, leading dimension D)
 template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk, CsmcArgs& a, void* ctt) {
     const int D = fk->dx;
     FkW<R> m;
     memset(&m, 0, sizeof(m));
-    const bool lg = fk->potential == AUXSSM_POT_LIN_GAUSS, mvt = fk->potential == AUXSSM_POT_MVT || lg;  // (mvt: a potential with a matrix in the block)
-    std::vector<R> block((size_t)3 * D * D + 4 * D + (mvt ? (size_t)D * D : 0));  // (+ the precision matrix / the whitened observation matrix)
+    const bool coupled = pot_kind(fk->potential).matrix != nullptr;  // (a potential with a matrix in the block)
+    std::vector<R> block((size_t)3 * D * D + 4 * D + (coupled ? (size_t)D * D : 0));
     R* const host_block = block.data();
-    R *hm0 = host_block, *hLP0 = hm0 + D, *hiLP0 = hLP0 + D * D, *hF = hiLP0 + D, *hb = hF + D * D, *hLQ = hb + D, *hiLQ = hLQ + D * D, *hprec = hiLQ + D;
-    fk_model<R>(fk, m, D, hm0, hLP0, hiLP0, hF, hb, hLQ, hiLQ, hprec);
+    R *hm0 = host_block, *hLP0 = hm0 + D, *hiLP0 = hLP0 + D * D, *hF = hiLP0 + D, *hb = hF + D * D, *hLQ = hb + D, *hiLQ = hLQ + D * D, *hpot_mat = hiLQ + D;
+    fk_model<R>(fk, m, D, hm0, hLP0, hiLP0, hF, hb, hLQ, hiLQ, hpot_mat);
     const size_t nb = block.size() * sizeof(R);
     {   // the handle's copy of the block: a new upload only when the content differs from the last one (a model that changes between sweeps pays one
         // stream synchronisation -- earlier sweeps may still be reading the old block -- a fixed model none: include/auxssm.h, auxssm_csmc_sweep)
@@ -842,12 +779,10 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
     m.b = d; d += D;
     m.LQ = d; d += D * D;
     m.iLQ = d; d += D;
-    m.prec = mvt ? d : nullptr;
+    m.pot_mat = coupled ? d : nullptr;
     int rc = csmc_prologue<R>(h, fk, a, ctt, m, false, [&] {
         const dim3 grid((unsigned)(((long long)a.C * a.T + 63) / 64));
-        if (lg) hipLaunchKernelGGL((k_cw_grad<R, false, true>), grid, dim3(64), 0, h->stream, a, m);
-        else if (mvt) hipLaunchKernelGGL((k_cw_grad<R, true>), grid, dim3(64), 0, h->stream, a, m);
-        else hipLaunchKernelGGL((k_cw_grad<R>), grid, dim3(64), 0, h->stream, a, m);
+        with_pot(m.potential, [&](auto pv) { hipLaunchKernelGGL((k_cw_grad<R, decltype(pv)::value>), grid, dim3(64), 0, h->stream, a, m); });
         return AUXSSM_OK;
     });
     if (rc) return rc;
@@ -861,7 +796,7 @@ template <typename R> static int run_cw(auxssm_ctx* h, const auxssm_fk_model* fk
         const CsmcArgs ab = csmc_batch(a, c0, cb);
         {
             ProfScope ps(h, AUXSSM_K_CSMC_FWD);
-            if ((rc = launch(h, cw_fwd_kernel<R>(guided, lg ? 2 : (mvt ? 1 : 0), wide16), dim3(ab.C), dim3(64 * fwd_waves), Cw2Lds<R>::fwd_bytes(D, guided, mvt), ab, m))) return rc;
+            if ((rc = launch(h, cw_fwd_kernel<R>(guided, m.potential, wide16), dim3(ab.C), dim3(64 * fwd_waves), Cw2Lds<R>::fwd_bytes(D, guided, coupled), ab, m))) return rc;
         }
         {
             ProfScope ps(h, AUXSSM_K_CSMC_BWD);
