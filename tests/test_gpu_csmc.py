@@ -29,12 +29,29 @@ def _odesc(proposal, potential, M0, Mt, sig_y=1.0):
 
 
 def _pot(kind, y, sig=0.7):
-    from aux_ssm_samplers_amd.csmc import FlatPotential, GaussianObsPotential, SVPotential
+    from aux_ssm_samplers_amd.csmc import FlatPotential, GaussianObsPotential, MaskedGaussianObsPotential, SVPotential
     if kind == O.POT_FLAT:
         return FlatPotential(), FlatPotential()
     if kind == O.POT_GAUSS_OBS:
         return GaussianObsPotential(sig=sig, y=y[0]), GaussianObsPotential(sig=sig, params=y[1:])
+    if kind == O.POT_GAUSS_OBS_MASKED:  # (the missing components are the NaNs of y: _masked_obs)
+        return MaskedGaussianObsPotential(sig=sig, y=y[0]), MaskedGaussianObsPotential(sig=sig, params=y[1:])
     return SVPotential(y=y[0]), SVPotential(params=y[1:])
+
+
+def _masked_obs(y, rng, missing_row):
+    """y (T, d) with missing components for the masked potential: about a quarter of all components NaN, scattered, at least one of them and at least one observed
+    component in each of the rows t = 0, an interior step and t = T - 1; and the whole of row `missing_row` NaN (a step without any observation)"""
+    y = np.array(y, np.float64)
+    T, d = y.shape
+    y[rng.random((T, d)) < 0.25] = np.nan
+    for t in {0, T // 2, T - 1}:
+        k = int(rng.integers(d))
+        y[t, k] = np.nan
+        if d > 1:
+            y[t, (k + 1 + int(rng.integers(d - 1))) % d] = rng.standard_normal()
+    y[missing_row] = np.nan
+    return y
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -460,16 +477,20 @@ def test_forward_weights_bound_and_its_fallbacks(dtype, N, case):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("d,N,T", [(5, 25, 12), (8, 64, 20), (30, 25, 16), (32, 33, 9), (16, 2, 7)])
 @pytest.mark.parametrize("proposal", [O.BOOTSTRAP_LG, O.AUX_INDEPENDENT])
-@pytest.mark.parametrize("potential", [O.POT_FLAT, O.POT_GAUSS_OBS, O.POT_SV])
+@pytest.mark.parametrize("potential", [O.POT_FLAT, O.POT_GAUSS_OBS, O.POT_SV, O.POT_GAUSS_OBS_MASKED])
 @pytest.mark.parametrize("backward", [True, False])
 def test_wide_state_sweep_bit_exact_vs_oracle(dtype, d, N, T, proposal, potential, backward):
-    """4 < dx <= 32 with few particles (csrc/csmc_wide.hip: one wave per chain, components in LDS rows) -- the reference's own stochastic-volatility
+    """4 < dx <= 32 with few particles (csrc/csmc_wide.hip: sixteen waves per chain in fp32 at these chain counts, eight in fp64, a particle's components across
+    the 32 lanes of a half-wave; more chains than CUs: tests/test_gpu_csmc_wide_chains.py) -- the reference's own stochastic-volatility
     protocol is D = 30, N = 25 (examples/stochastic_volatility/experiment.sh:1-10): particles, log-weights, ancestors and the trajectory bit-exact
-    against the same oracle as the register kernels."""
+    against the same oracle as the register kernels.  The masked potential has scattered missing components (t = 0, an interior step and t = T - 1 among them)
+    and one step with the whole row missing, at t = 0, T // 2 or T - 1 from cell to cell."""
     from aux_ssm_samplers_amd.csmc import _device
     rng = np.random.default_rng(100 * d + N + T)
     M0, Mt = _models(d, rng)
     y = rng.standard_normal((T, d))
+    if potential == O.POT_GAUSS_OBS_MASKED:  # (a generator of its own: the other potentials' inputs stay what they were)
+        y = _masked_obs(y, np.random.default_rng([d, N, T, proposal, int(backward)]), (0, T // 2, T - 1)[(d + proposal + int(backward)) % 3])
     G0, Gt = _pot(potential, y)
     x0 = rng.standard_normal((T, d)).astype(dtype)
     noise = dict(eps_prop=rng.standard_normal((T, N, d)), u_res=rng.random((T - 1, N)), u_bwd=rng.random(T))

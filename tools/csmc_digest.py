@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the bytes of (x, ancestors, xs, log_ws, As) of one conditional-SMC sweep with its history, for a fixed list of small problems: every
-built-in potential kind on every path a cSMC driver can take (csrc/csmc.hip: the register kernels, dx <= 4; csrc/csmc_wide.hip: the wide-state kernels; csrc/pit.hip:
-the parallel-in-time sweep), every proposal style and gradient mode, with and without backward sampling, in both dtypes, once on explicit noise arrays and once on
+built-in potential kind on every path a cSMC driver can take (csrc/csmc.hip: the register kernels, dx <= 4; csrc/csmc_wide.hip: the wide-state kernels, with few chains and with more chains than the device has CUs -- the two sides of
+csmc_wide.hip::run_cw's choice between sixteen and eight waves per chain in fp32; csrc/pit.hip: the parallel-in-time sweep), every proposal style and gradient mode, with and without backward sampling, in both dtypes, once on explicit noise arrays and once on
 Threefry keys.  For comparing two builds of the library bit for bit:   AUXSSM_LIB=/path/to/libauxssm.so python tools/csmc_digest.py out.json   once per build, then
 compare the files.  A case that raises is recorded with the error's text."""
 import hashlib
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -25,6 +26,17 @@ STYLES = [("bootstrap", _lib.GRAD_NONE), ("independent", _lib.GRAD_NONE), ("inde
 # partial slot and at its widest state
 SHAPES = [("reg2", 2, 20, 5, KINDS), ("reg4", 4, 20, 5, KINDS), ("reg1_n1024", 1, 1024, 4, ("sv",)), ("wide5", 5, 7, 5, KINDS), ("wide32", 32, 64, 5, KINDS)]
 CHAINS = 2
+# more chains than CUs on the wide path (fp32: the eight-wave kernels; the count is CUs + 3, so the digests belong to one device model): (style, gradient, backward, noise)
+MANY_SHAPE = ("wide30_more_chains_than_cus", 30, 25, 4)
+MANY_STYLES = [("bootstrap", _lib.GRAD_NONE, False, "explicit"), ("independent", _lib.GRAD_NONE, True, "keyed"), ("independent", _lib.GRAD_EXACT, True, "explicit"),
+               ("guided", _lib.GRAD_REFERENCE, True, "explicit")]
+
+
+def many_chains():
+    """CUs + 3: the library compares the chain count with hipDeviceProp_t::multiProcessorCount of the handle's device (read by torch in a child process: torch
+    ships a HIP runtime of its own, which stays out of this process)"""
+    code = f"import torch; print(torch.cuda.get_device_properties({_lib.default_handle().device}).multi_processor_count)"
+    return int(subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True).stdout.split()[-1]) + 3
 
 
 def model(kind, d, T):
@@ -67,21 +79,21 @@ def sha(*arrays):
     return h.hexdigest()
 
 
-def start(x, dtype):
-    return np.stack([x + 0.1 * c for c in range(CHAINS)]).astype(dtype)
+def start(x, dtype, chains=CHAINS):
+    return np.stack([x + 0.1 * (c % 7) + 0.01 * (c // 7) for c in range(chains)]).astype(dtype)
 
 
-def noise_kw(how, T, N, d, seed):
-    """the sweep's noise: explicit arrays of CHAINS chains, or a Threefry key"""
+def noise_kw(how, T, N, d, seed, chains=CHAINS):
+    """the sweep's noise: explicit arrays of `chains` chains, or a Threefry key"""
     if how == "keyed":
         return dict(key=R.PRNGKey(seed))
-    per = [G.noise(T, N, d, np.random.default_rng(seed + c)) for c in range(CHAINS)]
+    per = [G.noise(T, N, d, np.random.default_rng(seed + c)) for c in range(chains)]
     return dict(noise={k: np.stack([p[k] for p in per]) for k in per[0]})
 
 
-def sweep_digest(fk, x, delta, N, backward, dtype, how):
+def sweep_digest(fk, x, delta, N, backward, dtype, how, chains=CHAINS):
     T, d = x.shape
-    xo, anc, hist = _device.sweep(fk, start(x, dtype), N, backward, delta=delta, want_history=True, **noise_kw(how, T, N, d, 77))
+    xo, anc, hist = _device.sweep(fk, start(x, dtype, chains), N, backward, delta=delta, want_history=True, **noise_kw(how, T, N, d, 77, chains))
     return sha(xo, anc, hist["xs"], hist["log_ws"], hist["As"])
 
 
@@ -107,6 +119,14 @@ def cases():
                         for how in ("explicit", "keyed"):
                             yield (f"{shape}:{kind}:{style}:grad{gradient}:bw{int(backward)}:{dn}:{how}",
                                    lambda a=(style, gradient, dev, x, delta, N, backward, dtype, how): sweep_digest(describe(*a[:3]), *a[3:]))
+        if dtype == np.float32:  # (fp64 runs eight waves at every chain count: the cases above)
+            shape, d, N, T = MANY_SHAPE
+            Cn = many_chains()
+            for kind in KINDS:
+                dev, x, delta = model(kind, d, T)
+                for style, gradient, backward, how in MANY_STYLES:
+                    yield (f"{shape}:C{Cn}:{kind}:{style}:grad{gradient}:bw{int(backward)}:{dn}:{how}",
+                           lambda a=(style, gradient, dev, x, delta, N, backward, dtype, how, Cn): sweep_digest(describe(*a[:3]), *a[3:]))
         # config C3's shape (csrc/csmc.hip::c3_shape) runs with the draws made inside the forward pass
         dev, x, delta = model("sv", 1, 4)
 
