@@ -25,68 +25,11 @@
 //   inside it the first sub-chunk b with (previous chunks' cumsum + (S_0 + .. + S_b)) >= r (the last non-empty one if none), inside that
 //   the first p with (previous chunks' cumsum + ((S_0 + .. + S_{b-1}) + e .. + e_p)) >= r (its last p if none): a draw recomputes one
 //   sub-chunk, not the chunk.
-#include "csmc_host.h"
+// This unit holds the register kernels of dx <= 4 (a particle in R x[D], the model by value in FkDev), the entry point and the trace.  States of 4 < dx <= 32
+// with N <= 64 run the leaves and stitches of pit_wide.hip under the same contract (the model as FkW pointers, matrices and particles in LDS) and the same trace.
+#include "pit_shared.h"
 
 namespace ax {
-
-struct PitArgs {
-    int C, T, N, K;
-    const void* y;    // (T, D) or null
-    const void* shd;  // (T)
-    void* x;          // (C, T, D) reference trajectory in, new trajectory out
-    void* xs;         // (C, T, N, D) leaf particles
-    void* lw0;        // (C, N) normalised log-weights of the leaf at t = 0
-    // gradient-informed proposals (csmc/independent.py:81-84: mt = N(u + delta/2 grad, delta/2 I), qt = N(u, delta/2 I); pit/csmc.py:83-88: the leaf
-    // weights are qt.logpdf - mt.logpdf, per particle): u, grad (C, T, D) and the normalised leaf log-weights of EVERY time step, lwt (C, T, N); null otherwise
-    const void* u;
-    const void* grad;
-    void* lwt;
-    uint16_t* Ls;     // (C, tot, N) left slot of each stitched pair, nodes of all levels back to back (off[k] = first node of level k)
-    uint16_t* Rs;     // (C, tot, N) right slot
-    uint16_t* Fi;     // (C, tot, N) leaf particle index at the node's first time step
-    uint16_t* La;     // (C, tot, N) leaf particle index at the node's last time step
-    int32_t* anc;     // (C, T)
-    long long tot;
-    long long off[32];
-    double neg_log_n;
-    int noise_mode;
-    uint32_t key0, key1;
-    const void* eps_aux;   // (C, T, D)
-    const void* eps_prop;  // (C, T, N, D)
-    const void* u_res;     // (C, T, N): row t feeds the stitch at the boundary (t-1 | t); row 0 is never read
-};
-
-template <typename R> __device__ __forceinline__ R pit_normal(const PitArgs& a, const void* arr, uint32_t stream, long long idx) {
-    if (a.noise_mode == 0) return ((const R*)arr)[idx];
-    return stream_normal<R>(a.key0, a.key1, stream, (unsigned long long)idx);
-}
-template <typename R> __device__ __forceinline__ R pit_uniform(const PitArgs& a, const void* arr, uint32_t stream, long long idx) {
-    if (a.noise_mode == 0) return ((const R*)arr)[idx];
-    return stream_uniform<R>(a.key0, a.key1, stream, (unsigned long long)idx);
-}
-
-// log(w / sum w) of a block's log-weights, the reductions of block_normalize
-template <typename R> __device__ __forceinline__ R block_lognormalize(R lw, R* red, int tid, int nw) {
-    const int lane = tid & 63, wv = tid >> 6;
-    R m = wave_max(lw);
-    if (lane == 0) red[wv] = m;
-    __syncthreads();
-    R t[16];
-    load16<R>(red, t);
-    m = t[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) m = (k < nw && t[k] > m) ? t[k] : m;
-    if (!(m - m == 0)) m = 0;
-    const R e = det_exp(lw - m);
-    R s = wave_sum_tree(e);
-    if (lane == 0) red[16 + wv] = s;
-    __syncthreads();
-    load16<R>(red + 16, t);
-    s = t[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) s = k < nw ? s + t[k] : s;
-    return lw - (det_log(s) + m);
-}
 
 // leaves: u = x + sqrt(delta/2) eps_aux (csmc/independent.py:101-102); particles ~ N(u_t, delta_t/2 I), slot 0 = x (pit/csmc.py:77-80);
 // weights 0 except G0 at t = 0, normalised per time step (:85-91).  One workgroup per (t, chain), one lane per particle.
@@ -131,8 +74,6 @@ template <typename R, int D, bool GRAD> __global__ void __launch_bounds__(1024) 
         else ((R*)a.lw0)[(long long)c * N + tid] = lw;
     }
 }
-
-constexpr int PIT_SC = 8;  // sub-chunks per chunk (arithmetic contract, see the header)
 
 // the stitch of node j at level k (see the header); grid (nodes of the level, chains), NCH lanes
 template <typename R, int D> __global__ void __launch_bounds__(1024) k_pit_stitch(PitArgs a, FkDev<R> m, int k) {
@@ -317,6 +258,14 @@ template <typename R> __global__ void k_pit_trace(PitArgs a, int D) {
     for (int kk = 0; kk < D; ++kk) ((R*)a.x)[g * D + kk] = ((const R*)a.xs)[(g * a.N + q) * D + kk];
 }
 
+// the trace launch that ends a sweep of either width
+template <typename R> static int pit_trace(auxssm_ctx* h, const PitArgs& a, int D) {
+    const long long total = (long long)a.C * a.T;
+    hipLaunchKernelGGL((k_pit_trace<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
+    AX_HIP(hipGetLastError());
+    return AUXSSM_OK;
+}
+
 template <typename R, int D> static int run_pit(auxssm_ctx* h, const auxssm_fk_model* fk, PitArgs& a, void* ctt) {
     FkDev<R> m = fk_dev<R>(fk);
     const int TB = (a.N + 63) / 64 * 64;
@@ -330,7 +279,7 @@ template <typename R, int D> static int run_pit(auxssm_ctx* h, const auxssm_fk_m
     if (rc) return rc;
     if (m.gradient) hipLaunchKernelGGL((k_pit_leaves<R, D, true>), dim3(a.T, a.C), dim3(TB), 0, h->stream, a, m);
     else hipLaunchKernelGGL((k_pit_leaves<R, D, false>), dim3(a.T, a.C), dim3(TB), 0, h->stream, a, m);
-    const int NCH = a.N <= 32 ? 64 : (a.N <= 128 ? 256 : 1024);  // part of the arithmetic contract (header)
+    const int NCH = pit_nch(a.N);  // part of the arithmetic contract (header)
     const size_t lds = ((size_t)a.N * (2 * D + 2) + NCH + 48 + (size_t)PIT_SC * NCH) * sizeof(R) + 64;
     {
         ProfScope ps(h, AUXSSM_K_PIT_STITCH);
@@ -339,10 +288,7 @@ template <typename R, int D> static int run_pit(auxssm_ctx* h, const auxssm_fk_m
             if ((rc = launch(h, k_pit_stitch<R, D>, dim3((unsigned)nodes, a.C), dim3(NCH), lds, a, m, k))) return rc;
         }
     }
-    const long long total = (long long)a.C * a.T;
-    hipLaunchKernelGGL((k_pit_trace<R>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a, D);
-    AX_HIP(hipGetLastError());
-    return AUXSSM_OK;
+    return pit_trace<R>(h, a, D);
 }
 
 }  // namespace ax
@@ -362,8 +308,23 @@ extern "C" int auxssm_csmc_pit_sweep(auxssm_handle h, int dtype, const auxssm_fk
         return AUXSSM_ERR_ARG;
     }
     const int D = fk->dx;
-    if (D < 1 || D > CS_MAXD) {
-        set_error("dx=%d not instantiated (1..%d)", D, CS_MAXD);
+    if (D < 1 || D > PIT_MAXD) {
+        set_error("dx=%d not instantiated (1..%d)", D, PIT_MAXD);
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    const bool wide = D > CS_MAXD;  // pit_wide.hip: independent proposals, linear transitions, N <= PIT_WIDE_MAXN
+    if (wide && fk->proposal == AUXSSM_PROP_AUX_GUIDED) {
+        set_error("dx=%d: guided proposals depend on the parent particle: they run the sequential sweep (auxssm_csmc_sweep) only; for %d < dx <= %d the "
+                  "parallel-in-time sweep runs the independent auxiliary proposals with N <= %d", D, CS_MAXD, PIT_MAXD, PIT_WIDE_MAXN);
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    if (wide && N > PIT_WIDE_MAXN) {
+        set_error("dx=%d: for %d < dx <= %d the parallel-in-time sweep runs N <= %d particles (got N=%d)", D, CS_MAXD, PIT_MAXD, PIT_WIDE_MAXN, N);
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    if (wide && fk->transition != AUXSSM_TRANS_LINEAR) {
+        set_error("dx=%d: for %d < dx <= %d (N <= %d) the parallel-in-time sweep runs linear-Gaussian transitions only (got transition kind %d)", D, CS_MAXD,
+                  PIT_MAXD, PIT_WIDE_MAXN, fk->transition);
         return AUXSSM_ERR_UNSUPPORTED;
     }
     if (fk->proposal == AUXSSM_PROP_AUX_GUIDED) {
@@ -417,5 +378,9 @@ extern "C" int auxssm_csmc_pit_sweep(auxssm_handle h, int dtype, const auxssm_fk
     ws.add(a.Fi, tree);
     ws.add(a.La, tree);
     if (int rc = ws.reserve(h)) return rc;
+    if (wide) {
+        if (int rc = run_pit_wide(h, dtype, fk, a, ctt)) return rc;
+        return dtype == AUXSSM_F32 ? pit_trace<float>(h, a, D) : pit_trace<double>(h, a, D);
+    }
     return csmc_dispatch(dtype, D, [&](auto r, auto d) { return run_pit<decltype(r), decltype(d)::value>(h, fk, a, ctt); });
 }

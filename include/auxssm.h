@@ -422,7 +422,11 @@ int auxssm_csmc_sweep_program(auxssm_handle h, auxssm_fk_program prog, int dtype
  * potential of the family.  sqrt_half_delta (T) device.  Noise: EXPLICIT eps_aux (C,T,dx), eps_prop (C,T,N,dx), u_res (C,T,N) [row t
  * feeds the stitch at the boundary (t-1 | t); entry (t, 0) is used by the root only; row 0 never] or THREEFRY (streams 1, 2, 3 at the
  * same flat indices).  x (C,T,dx) in/out; ancestors (C,T) int32 = the leaf particle index selected at each step (updated =
- * ancestors != 0).  T >= 2, 2 <= N <= 1024.  Reduction orders and exp/log are fixed (csrc/pit.hip): bit-exact vs oracle/csmc_ref.c. */
+ * ancestors != 0).  T >= 2, 2 <= N <= 1024.  Reduction orders and exp/log are fixed (csrc/pit.hip): bit-exact vs oracle/csmc_ref.c.
+ * Covered: dx <= 4 (csrc/pit.hip) -- every transition and potential of the family, gradient NONE / REFERENCE / EXACT (in the tree both are the per-particle
+ * correction), N <= 1024; 4 < dx <= 32 (csrc/pit_wide.hip) -- AUXSSM_TRANS_LINEAR, time-invariant or time-varying, the six built-in potentials, the same
+ * gradient modes, 2 <= N <= 64, fp32 and fp64, both noise modes, several chains per launch.  AUXSSM_ERR_UNSUPPORTED, with the limit in the message: dx > 32;
+ * at dx > 4, N > 64 and AUXSSM_TRANS_LORENZ63_EM; guided proposals (AUXSSM_PROP_AUX_GUIDED) at any dx.  User programs have no parallel-in-time entry point. */
 int auxssm_csmc_pit_sweep(auxssm_handle h, int dtype, const auxssm_fk_model* model, int32_t C, int32_t T, int32_t N,
                           const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise, int32_t* ancestors);
 

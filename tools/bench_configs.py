@@ -7,6 +7,7 @@
    spatial  the spatial example on the 5 x 5 grid (dx = 25, T = 1024, N = 25, multivariate Student-t potential) beside the SV potential at the same shape, 256 chains
    lingauss  a partially observed linear-Gaussian model (dx = 24, dy = 12, T = 1024, N = 25, linear-Gaussian observation potential) beside GaussianObsPotential
              at the same shape, 256 chains
+   pit30  the reference's SV experiment at its defaults (--parallel, D = 30, N = 25, T = 250): the parallel-in-time sweep beside the sequential wide sweep, 1 / 16 / 256 chains
    loop the MCMC loop around the sweeps (aux_ssm_samplers_amd.loop: running moments, acceptance averages, adaptation, Lorenz theta step) on C2 / C3 / C4
 Prints one JSON line per measurement.  Inputs are resident in HBM (DeviceChains) where the API allows it; device Threefry noise."""
 import json
@@ -212,6 +213,38 @@ def pit(T=65536):
         print(json.dumps(row), flush=True)
 
 
+def pit30(T=250, D=30, N=25):
+    """the reference's stochastic-volatility experiment at its defaults (--parallel --D 30 --N 25: examples/stochastic_volatility/experiment.py:20-22), fp32,
+    Threefry: the parallel-in-time sweep (csrc/pit_wide.hip) beside the sequential wide sweep with backward sampling (csrc/csmc_wide.hip), same run, at 1, 16 and
+    256 chains.  Timing as the `pit` leg: wall time around several sweeps, ending in a device synchronise."""
+    from aux_ssm_samplers_amd.workloads import sv_setup
+    from aux_ssm_samplers_amd.csmc import CsmcChains, CSMCState, get_independent_kernel, GaussianInit, LinearGaussianDynamics, SVPotential
+    h = _lib.default_handle()
+    y, xtrue, (m0, P0, F, Q, b) = sv_setup(T, D)
+    M0, Mt = GaussianInit(m0=m0, P0=P0), LinearGaussianDynamics(F=F, b=b, Q=Q)
+    for chains in (1, 16, 256):
+        row = dict(config=f"SV protocol D={D} T={T} N={N} fp32, Threefry, resident chains", chains=chains)
+        for par in (True, False):
+            init, k = get_independent_kernel(M0, SVPotential(y=y[0]), Mt, SVPotential(params=y[1:]), N, backward=not par, Pt=Mt, parallel=par)
+            cc = CsmcChains(h, np.repeat(xtrue[None], chains, axis=0).astype(np.float32), delta=0.05)
+            st = CSMCState(x=cc, updated=None)
+            keys = R.split(R.PRNGKey(3), 12)
+            for i in range(2):
+                k(keys[i], st, None)
+            h.sync()
+            reps = 10
+            t0 = time.perf_counter()
+            for i in range(reps):
+                k(keys[2 + i], st, None)
+            h.sync()
+            el = (time.perf_counter() - t0) / reps
+            name = "pit" if par else "sequential_backward_sampling"
+            row[name + "_ms_per_sweep"] = round(el * 1e3, 3)
+            row[name + "_updated"] = round(float((cc.ancestors.to_host() != 0).mean()), 3)
+        row["speedup"] = round(row["sequential_backward_sampling_ms_per_sweep"] / row["pit_ms_per_sweep"], 2)
+        print(json.dumps(row), flush=True)
+
+
 def c5_batched_scalar(T=8192, B=64):
     """C5 as the reference's spatial example actually runs it (examples/spatial/model.py:103-112, auxiliary_kalman.py:18-28): d^2 = 64
     INDEPENDENT scalar chains on the batch axis B, not one dense 64 x 64 state.  AR(1) rows of the grid model, first-order aux observations."""
@@ -403,6 +436,8 @@ if __name__ == "__main__":
         sv30_kalman()
     if "pit" in which:
         pit()
+    if "pit30" in which:
+        pit30()
     if "loop" in which:
         loops()
     if "c3k" in which:
