@@ -21,7 +21,9 @@
 // its proposal to the other buffer, and acceptance flips sel[c] (auxssm_kalman_sweep_lazy); without one, x' goes to a scratch buffer and the
 // caller runs the usual select.  Same tables as affine_shared.h / kalman_bodies.h (GainRow, SampShared, LogShared), same per-term arithmetic and NaN
 // policy as FilterMeanOp / SampleAffOp / body_sweep_logpdf_shared; the per-chain totals are summed per (chain, chunk) lane and then over chunks, so
-// they agree with the unfused path to rounding, not bitwise (tests/test_gpu_fused.py: 1e-9 relative on x', 1e-7 absolute on log alpha at C2 size).
+// they agree with the unfused path to rounding, not bitwise (tests/test_gpu_fused.py: 1e-9 relative on x', 1e-7 absolute on log alpha at C2 size, on the
+// benchmark's model; tests/test_gpu_fused_models.py: the same bars against the oracle and the keyed sweep on time-varying models with dy != dx, missing data under
+// both NaN policies, rejected chains and a non-finite chain in the wave, for every (D, PO)).
 #pragma once
 // (included inside namespace ax by kernels.hip.h)
 
@@ -42,6 +44,7 @@ struct FusedArgs {
     Acc* pe;             // (3, C, nchunk): the same of x'
     void* pell;          // (C, nchunk) -1/2 sum |eps_samp|^2 of the chunk: the data part of log q(x' | u) (R)
     const Acc* clog;     // sum_t (sum_i log Lc_t[i][i] + D/2 log 2 pi): the chain-shared part of log q(x' | u) (k_fs_clog, model stage)
+    const int* nanrow;   // != 0: some log-density row is not finite, i.e. (reference policy) an observation is missing and the nansum rule drops that step (k_fs_rows, model stage)
     unsigned ka0, ka1, ks0, ks1;  // keys of eps_aux / eps_samp (stream 0 of auxssm_rng_normal at the (T, D, C) flat index)
     const void* eps0s;   // (D, C): row 0 of eps_samp (fill kernel)
     double delta, shd;
@@ -206,7 +209,8 @@ template <typename R, int D, int PO> __device__ __forceinline__ FsSrc fs_src_e(i
     return {-1, 0};
 }
 // one thread per destination element: blockIdx.y picks the row family (0 AC, 1 E), the flat index runs over (t, k)
-template <typename R, int D, int PO> __global__ void __launch_bounds__(256) k_fs_rows(FusedArgs a, const R* __restrict__ ntab, R* __restrict__ rc, R* __restrict__ re) {
+template <typename R, int D, int PO> __global__ void __launch_bounds__(256) k_fs_rows(FusedArgs a, const R* __restrict__ ntab, R* __restrict__ rc, R* __restrict__ re,
+                                                                                      int* __restrict__ nanrow) {
     if (memo_skip(a)) return;
     constexpr int P = D + PO;
     using F = FsRows<R, D, PO>; using TG = GainRow<R, D, P>; using TS = SampShared<R, D>; using TL = LogShared<R, D, PO>;
@@ -224,6 +228,7 @@ template <typename R, int D, int PO> __global__ void __launch_bounds__(256) k_fs
     else if (sc.tab == 4) { if (t + 1 < a.T) v = ((const R*)a.logt)[(long long)t * TL::NPAD + sc.off]; }
     else if (sc.tab == 5) v = ntab[(long long)t * D * D + sc.off];
     (fam == 0 ? rc : re)[g] = v;
+    if ((sc.tab == 2 || sc.tab == 4) && !finite_(v)) *nanrow = 1;  // (every writer stores the same value; zeroed by k_fs_clog_sum, earlier on the stream)
 }
 
 // the chain-shared part of log q(x' | u): x'_t | x'_{t+1} = G_t x'_{t+1} + M1_t m_t - gb_t + Lc_t eps_t, so log q = sum_t (-1/2 |eps_t|^2 - sum_i log Lc_t[i][i] - D/2 log 2 pi).
@@ -248,8 +253,10 @@ template <typename R, int D> __global__ void __launch_bounds__(256) k_fs_clog_pa
     }
     if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
 }
-template <int D> __global__ void __launch_bounds__(256) k_fs_clog_sum(int T, int nb, const Acc* __restrict__ part, Acc* __restrict__ out, const int* memo) {
+template <int D> __global__ void __launch_bounds__(256) k_fs_clog_sum(int T, int nb, const Acc* __restrict__ part, Acc* __restrict__ out, int* __restrict__ nanrow,
+                                                                      const int* memo) {
     if (memo_skip_p(memo)) return;
+    if (threadIdx.x == 0) *nanrow = 0;  // (k_fs_rows, later on the stream, raises it)
     __shared__ Acc sh[256];
     Acc acc = 0;
     for (int b = threadIdx.x; b < nb; b += 256) acc += part[b];
@@ -661,12 +668,62 @@ template <typename R, int D, int PO> __global__ void __launch_bounds__(TB_ELEM) 
 
 // ---- accept (generic.py:70-73, 98-106): one workgroup per chain sums its chunks' partial totals in a fixed order, forms log alpha in Acc
 // exactly as k_accept does, draws the Bernoulli and -- lazy state -- flips the chain's buffer selector ------------------------------------------
-template <typename R> __global__ void __launch_bounds__(TB_ELEM) k_fs_accept(FusedArgs a, const R* __restrict__ head5, const R* __restrict__ ell0,
-                                                                            const R* __restrict__ u_acc, int32_t* __restrict__ accepted, R* __restrict__ logs,
-                                                                            int32_t* __restrict__ sel) {
+// The steps the reference's nansum dropped from the concatenated likelihood of x' because an observation is missing (base.py:137-166 on ys = [u; y]): what
+// the TRUE joint density of (x', u, y) holds there -- N(u_t; x'_t, delta/2 I) and the density of the finite components of y_t -- from the model's arrays.
+// One workgroup per chain, its lanes over the time steps; the caller asks only when the model stage saw a non-finite log-density row (FusedArgs::nanrow) or y_0 is missing.
+template <typename R, int D, int PO> __device__ __forceinline__ Acc fs_dropped_joint(const FusedArgs& a, const SweepLogpdfArgs& la, int c, const int32_t* sel) {
+    Acc s = 0;
+    const long long C = a.C;
+    const R* xp = (const R*)((sel && sel[c]) ? a.xa : (const void*)a.xb) + c;  // the proposal: the buffer the chain does not live in
+    const R* up = (const R*)a.u + c;
+    const R inv_delta = (R)1 / (R)a.delta;
+    const R cst = (R)-0.5 * (R)D * log_((R)(0.5 * a.delta)) - (R)(0.5 * LOG_2PI) * (R)D;
+    for (int t = threadIdx.x; t < a.T; t += TB_ELEM) {
+        R y[PO];
+        rd<R, PO>(la.ys, c, t, 0, y);
+        bool skip[PO], any = false;
+#pragma unroll
+        for (int k = 0; k < PO; ++k) skip[k] = !finite_(y[k]), any = any || skip[k];
+        if (!any) continue;
+        R H[PO * D], cv[PO], Rm[PO * PO], v[D], r[PO], q = 0;
+        bool b = false;  // (a non-finite u_t - x'_t -- a NaN in the chain's state -- drops the auxiliary block, as fs_terms does; gauss_logpdf drops a non-finite kept residual)
+        rd<R, PO * D>(la.Hs, c, t, 0, H);
+        rd<R, PO>(la.cs, c, t, 0, cv);
+        rd_upper<R, PO>(la.Rs, c, t, 0, Rm);
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            v[k] = xp[((long long)t * D + k) * C];
+            const R d = up[((long long)t * D + k) * C] - v[k];
+            b = b || !finite_(d);
+            q += d * d;
+        }
+#pragma unroll
+        for (int k = 0; k < PO; ++k) {
+            R p = cv[k];
+#pragma unroll
+            for (int j = 0; j < D; ++j) p += H[k * D + j] * v[j];
+            r[k] = y[k] - p;
+        }
+        s += (Acc)(b ? (R)0 : -q * inv_delta + cst) + (Acc)gauss_logpdf<R, PO>(r, Rm, skip);
+    }
+    return s;
+}
+template <typename R, int D, int PO> __global__ void __launch_bounds__(TB_ELEM) k_fs_accept(FusedArgs a, SweepLogpdfArgs lg, const R* __restrict__ head5, const R* __restrict__ ell0,
+                                                                                            const R* __restrict__ u_acc, int32_t* __restrict__ accepted, R* __restrict__ logs,
+                                                                                            int32_t* __restrict__ sel) {
     __shared__ Acc sh[TB_ELEM];
+    fs_resolve(a);
     const int c = blockIdx.x;
     const long long C = a.C;
+    // are there dropped steps to add back?  (workgroup-uniform: the rows of t >= 1 raise the flag, row 0 has no table row; loaded here, used after the sums below)
+    bool any_dropped = false;
+    if (a.nan_policy == 0) {
+        R y0[PO];
+        rd<R, PO>(lg.ys, c, 0, 0, y0);
+        any_dropped = *a.nanrow != 0;
+#pragma unroll
+        for (int k = 0; k < PO; ++k) any_dropped = any_dropped || !finite_(y0[k]);
+    }
     Acc tot[7] = {0, 0, 0, 0, 0, 0, 0};
     const R* pl = (const R*)a.pell + (long long)c * a.nchunk;
     for (int j = threadIdx.x; j < a.nchunk; j += TB_ELEM) {  // (seven independent loads per trip)
@@ -676,14 +733,18 @@ template <typename R> __global__ void __launch_bounds__(TB_ELEM) k_fs_accept(Fus
     }
 #pragma unroll
     for (int k = 0; k < 7; ++k) tot[k] = block_sum<Acc, TB_ELEM>(tot[k], sh);
+    Acc dropped = 0;
+    if (any_dropped) dropped = block_sum<Acc, TB_ELEM>(fs_dropped_joint<R, D, PO>(a, lg, c, sel), sh);
     if (threadIdx.x != 0) return;
     // The marginal log-likelihood of the auxiliary model WITHOUT walking its innovations: for any path z, ell = log p(z, u, y) - log p(z | u, y), and for the sampled
     // proposal x' both are at hand -- the joint is the sum pass E forms anyway (jp_prop), the conditional is the density of the pathwise draw,
     // log q(x' | u) = sum_t (-1/2 |eps_t|^2 - log|Lc_t| - D/2 log 2 pi) (pass C accumulates the first term, k_fs_clog the rest).  Same quantity as filtering.py:55-62
-    // to rounding; log alpha does not depend on it at all (it enters lp_prop and lp_rev alike), only the reported lp_prop / lp_rev do.
+    // to rounding; log alpha does not depend on it at all (it enters lp_prop and lp_rev alike), only the reported lp_prop / lp_rev do.  Under the reference policy
+    // jp_prop lacks the steps the nansum dropped for a missing observation, which log q(x' | u) holds: `dropped` completes the joint (without it lp_prop and lp_rev
+    // were both off by that sum whenever data were missing).
     (void)ell0;
     const Acc jp_prop = tot[3] + (Acc)head5[0 * C + c], jp_rev = tot[0] + (Acc)head5[1 * C + c];
-    const Acc ell = jp_prop - (tot[6] - *a.clog);
+    const Acc ell = (jp_prop + dropped) - (tot[6] - *a.clog);
     const Acc lt_prop = tot[4] + (Acc)head5[2 * C + c], lt_rev = tot[1] + (Acc)head5[3 * C + c];
     const Acc corr = (tot[5] - tot[2]) + (Acc)head5[4 * C + c];
     const Acc lp_prop = jp_prop - ell, lp_rev = jp_rev - ell;
@@ -785,12 +846,14 @@ template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHo
         Acc* clog = (Acc*)ws_take(h, 256 + (size_t)nclb * sizeof(Acc));  // [0] the sum, [32 ...) the partial sums
         if (!f.sa.tab || !f.la.tab || !gpre || !cprod_f || !cprod_s || !rows_c || !rows_e || !fpre || !ntab || !psi || !clog) return AUXSSM_ERR_NOMEM;
         a.clog = clog;
+        int* nanrow = (int*)(clog + 16);  // (in the sum's 256-byte header: lives and is memoised with the tables)
+        a.nanrow = nanrow;
         a.gain = f.fa.tab; a.samp = f.sa.tab; a.logt = f.la.tab; a.gpre = gpre;
         {
             ProfScope ps(h, AUXSSM_K_SAMPLE_INIT);
             hipLaunchKernelGGL((k_sample_shared_tab<R, D>), dim3((T + TB_ELEM - 1) / TB_ELEM), dim3(TB_ELEM), 0, h->stream, f.sa);
             hipLaunchKernelGGL((k_fs_clog_part<R, D>), dim3(nclb), dim3(256), 0, h->stream, T, (const R*)f.sa.tab, clog + 32, f.memo);
-            hipLaunchKernelGGL((k_fs_clog_sum<D>), dim3(1), dim3(256), 0, h->stream, T, nclb, (const Acc*)(clog + 32), clog, f.memo);
+            hipLaunchKernelGGL((k_fs_clog_sum<D>), dim3(1), dim3(256), 0, h->stream, T, nclb, (const Acc*)(clog + 32), clog, nanrow, f.memo);
             hipLaunchKernelGGL((k_sweep_logpdf_tab<R, D, PO>), dim3((n + TB_ELEM - 1) / TB_ELEM), dim3(TB_ELEM), 0, h->stream, f.la);
             hipLaunchKernelGGL((k_fs_fprod<R, D, P>), dim3((a.nchunk + TB_CM - 1) / TB_CM), dim3(TB_CM), 0, h->stream, a, cprod_f, fpre);
             hipLaunchKernelGGL((k_fs_gpre<R, D>), dim3((a.nchunk + TB_CM - 1) / TB_CM), dim3(TB_CM), 0, h->stream, a, gpre, cprod_s);
@@ -798,7 +861,7 @@ template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHo
             {
                 using F = FsRows<R, D, PO>;
                 const long long nmax = (long long)T * (F::NC > F::NE ? F::NC : F::NE);
-                hipLaunchKernelGGL((k_fs_rows<R, D, PO>), dim3((unsigned)((nmax + 255) / 256), 2), dim3(256), 0, h->stream, a, (const R*)ntab, rows_c, rows_e);
+                hipLaunchKernelGGL((k_fs_rows<R, D, PO>), dim3((unsigned)((nmax + 255) / 256), 2), dim3(256), 0, h->stream, a, (const R*)ntab, rows_c, rows_e, nanrow);
             }
         }
     }
@@ -855,7 +918,7 @@ template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHo
     {
         ProfScope ps(h, AUXSSM_K_SELECT);
         hipLaunchKernelGGL((k_fs_head<R, D, PO>), dim3((C + TB_ELEM - 1) / TB_ELEM), dim3(TB_ELEM), 0, h->stream, f.la, f.xa, (const void*)f.xb, (const int32_t*)f.sel, head5);
-        hipLaunchKernelGGL((k_fs_accept<R>), dim3(C), dim3(TB_ELEM), 0, h->stream, a, (const R*)head5, (const R*)f.fa.ell0, (const R*)f.u_acc, f.accepted,
+        hipLaunchKernelGGL((k_fs_accept<R, D, PO>), dim3(C), dim3(TB_ELEM), 0, h->stream, a, f.la, (const R*)head5, (const R*)f.fa.ell0, (const R*)f.u_acc, f.accepted,
                            (R*)f.logs, f.sel);
     }
     AX_HIP(hipGetLastError());

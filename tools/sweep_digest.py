@@ -29,6 +29,15 @@ def lg(T, d, tinv=False):
                          rep(m["cobs"], T), m["y"]), 0.4
 
 
+def lg_missing(policy_tinv):
+    """a time-varying (3, 2) model with missing rows and components (tests/fused_cases.py::tv_model, group A's shape) -- or, tinv, one step's matrices as
+    broadcast views under the same kind of data: the fused sweep outside workloads.lg_model"""
+    from tests import fused_cases as FC
+    m = FC.tv_model(70, 3, 2, 2, tinv=policy_tinv)
+    y = FC.missing(m["y"], {0: "partial", 15: "whole", 16: "partial", 69: "whole"}, np.random.default_rng(5))
+    return LGConcatModel(m["m0"], m["P0"], m["Fs"], m["Qs"], m["bs"], m["Hs"], m["Rs"], m["cs"], y), 0.4
+
+
 def sv(T, d, order):
     y, _, (m0, P0, F, Q, b) = sv_setup(T, d)
     return SVModel(y, m0, P0, F, Q, b, order=order), 0.05
@@ -41,7 +50,7 @@ def lorenz(T, C=None):
     return LorenzModel(base.yobs[:T], base.Hobs[:T], base.Robs[:T], base.cobs[:T], base.m0, base.P0, theta, base.sigma_x, base.dt), 1e-3
 
 
-# name: (model, chains, chain-minor, options {share, overlap, parallel, fused, moments, sweeps})
+# name: (model, chains, chain-minor, options {share, overlap, parallel, fused, moments, sweeps, nan_policy})
 CASES = {
     "lg_dense_parallel": (lambda: lg(40, 2), 3, False, {}),
     "lg_dense_sequential": (lambda: lg(40, 2), 3, False, dict(parallel=False)),
@@ -54,6 +63,9 @@ CASES = {
     "lg_wide_carrier": (lambda: lg(12, 6), 3, False, {}),
     "lg_fused": (lambda: lg(64, 4), 66, True, dict(fused=None, overlap=1, sweeps=5)),
     "lg_fused_moments": (lambda: lg(64, 4), 66, True, dict(fused=None, overlap=1, sweeps=5, moments=True)),
+    "lg_fused_tv_missing_reference": (lambda: lg_missing(False), 6, True, dict(fused=None, overlap=1, sweeps=5)),
+    "lg_fused_tv_missing_masked": (lambda: lg_missing(False), 6, True, dict(fused=None, overlap=1, sweeps=5, nan_policy="masked")),
+    "lg_fused_tinv_missing": (lambda: lg_missing(True), 6, True, dict(fused=None, overlap=1, sweeps=5)),
     "lorenz_dense": (lambda: lorenz(40), 3, False, {}),
     "lorenz_cm": (lambda: lorenz(40), 64, True, {}),
     "lorenz_cm_theta_per_chain": (lambda: lorenz(40, 64), 64, True, {}),
@@ -73,7 +85,11 @@ def digest(make, Cn, chain_minor, opt, dtype):
     try:
         h.set_option(_lib.OPT_SHARE_MODEL, opt.get("share", 1))
         h.set_option(_lib.OPT_OVERLAP_MODEL_STAGE, opt.get("overlap", 0))
-        _, kernel = get_kernel(model.dynamics_factory, model.observations_factory, model.log_likelihood_fn, opt.get("parallel", True))
+        if "nan_policy" in opt:  # (get_kernel is the reference's signature: the policy is the device kernel's own argument)
+            from aux_ssm_samplers_amd.kalman.generic import _get_device_kernel
+            _, kernel = _get_device_kernel(model, opt.get("parallel", True), nan_policy=opt["nan_policy"])
+        else:
+            _, kernel = get_kernel(model.dynamics_factory, model.observations_factory, model.log_likelihood_fn, opt.get("parallel", True))
         x0 = (0.3 * np.random.default_rng(1).standard_normal((Cn, model.T, model.dx))).astype(dtype)
         ch = DeviceChains(h, x0, chain_minor=chain_minor, fused=opt.get("fused", False))
         stats = tuple(h.zeros(ch._x.shape, dtype) for _ in range(3)) if opt.get("moments") else ()
