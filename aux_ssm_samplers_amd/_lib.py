@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("AUXSSM_LIB", os.path.join(_HERE, "libauxssm.so"))  # 
 F32, F64 = 0, 1
 NAN_REFERENCE, NAN_MASKED = 0, 1
 KMODEL_LG_CONCAT, KMODEL_SV_FIRST, KMODEL_SV_SECOND, KMODEL_LORENZ63_EXT = 1, 2, 3, 4
+KMODEL_MVT_FIRST, KMODEL_MVT_SECOND = 5, 6
 LAYOUT_DENSE, LAYOUT_CHAIN_MINOR = 0, 1
 OPT_SHARE_MODEL = 1
 OPT_OVERLAP_MODEL_STAGE = 2

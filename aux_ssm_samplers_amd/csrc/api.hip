@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "ctx.h"
+#include "kalman_mvt.h"
 #include "rng.h"
 
 namespace ax {
@@ -1352,6 +1353,30 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
     return AUXSSM_OK;
 }
 
+// AUXSSM_KMODEL_MVT_FIRST / _SECOND: the sweep up to the five totals is kalman_mvt.hip's (run_mvt); the accept and select steps are the ones every sweep shares
+template <typename R> static int sweep_mvt(const SweepCall& c) {
+    auxssm_ctx* h = c.h;
+    const int C = c.dims->C, T = c.dims->T, D = c.dims->dx;
+    const KDims kd{C, T, 1};
+    R *xp, *ell0;
+    Acc* sums;
+    WsPlan ws;
+    ws.add(xp, (size_t)C * T * D * sizeof(R));
+    ws.add(ell0, (size_t)C * sizeof(R));
+    ws.add(sums, (size_t)5 * C * sizeof(Acc));
+    ws.after(mvt_ws_bytes(c.dtype, C, T, D));
+    int rc = ws.reserve(h);
+    if (rc) return rc;
+    const auxssm_lgssm* m = c.model;
+    const MvtArgs a{C, T, D, c.order, c.delta, c.dptr, m->m0.ptr, m->P0.ptr, m->Fs.ptr, m->Qs.ptr, m->bs.ptr, m->Rs.ptr, m->cs.ptr, c.yobs->ptr, (long long)c.yobs->st,
+                    c.x, c.eps_aux, c.eps_samp, xp, sums, ell0};
+    if ((rc = run_mvt(h, c.dtype, a))) return rc;
+    launch_accept<R>(c, sums, ell0, ell0);
+    if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)c.accepted, dense_arr(xp, kd, D), dense_arr(c.x, kd, D), 0))) return rc;
+    AX_HIP(hipGetLastError());
+    return AUXSSM_OK;
+}
+
 // ---- Lorenz-63 device factories (examples/lorenz/auxiliary_kalman.py:14-52, model.py:10-25, linearisation.py:11-44) ------------
 // dynamics_factory(x) = first-order extended linearisation of mean(x) = x + dt (phi_0(x) + theta * phi(x)) at every x_t, with the
 // analytic Jacobian in place of jacfwd:  F_t = I + dt J(x_t),  b_t = mean(x_t) - F_t x_t,  Q = model Qs;
@@ -1866,7 +1891,8 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
     if ((rc = check_dtype(dtype)) || (rc = check_dims(dims, true))) return rc;
     const bool sv = model_kind == AUXSSM_KMODEL_SV_FIRST || model_kind == AUXSSM_KMODEL_SV_SECOND;
     const bool lorenz = model_kind == AUXSSM_KMODEL_LORENZ63_EXT;
-    if (model_kind != AUXSSM_KMODEL_LG_CONCAT && !sv && !lorenz) {
+    const bool mvt = model_kind == AUXSSM_KMODEL_MVT_FIRST || model_kind == AUXSSM_KMODEL_MVT_SECOND;
+    if (model_kind != AUXSSM_KMODEL_LG_CONCAT && !sv && !lorenz && !mvt) {
         set_error("unknown model_kind %d", model_kind);
         return AUXSSM_ERR_ARG;
     }
@@ -1888,24 +1914,49 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
             set_error("Lorenz-63 has dx = 3 and 1..3 observed combinations (got dx=%d, dy=%d)", dims->dx, dims->dy);
             return AUXSSM_ERR_ARG;
         }
+    } else if (mvt) {
+        if (!model || !model->m0.ptr || !model->P0.ptr || !model->Fs.ptr || !model->Qs.ptr || !model->bs.ptr || !model->Rs.ptr || !model->cs.ptr) {
+            set_error("multivariate-t model needs m0, P0, Fs, Qs, bs as (dx) vectors, Rs (= prec (dx, dx) on the device) and cs (= [nu] on the device)");
+            return AUXSSM_ERR_ARG;
+        }
+        if (dims->dy != dims->dx) {
+            set_error("the multivariate-t model observes every state component: dy (%d) must equal dx (%d)", dims->dy, dims->dx);
+            return AUXSSM_ERR_ARG;
+        }
     } else if ((rc = check_lgssm(model, dims->T))) {
         return rc;
     }
     if ((rc = check_sweep_common(false, dims, delta, delta_dev != nullptr, nan_policy, layout, yobs && yobs->ptr && x && eps_aux && eps_samp && u_acc && accepted, model,
-                                 yobs, !sv)))
+                                 yobs, !sv && !mvt)))
         return rc;
+    if (mvt) {  // (before anything is enqueued)
+        if (dims->dx > 64) {
+            set_error("the batched multivariate-t sweep covers dx <= 64 (one wave per time step, lane = component): got dx = %d", dims->dx);
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+        if (layout != AUXSSM_LAYOUT_DENSE) {
+            set_error("the batched multivariate-t sweep (dx <= 64) takes the dense (C, T, dx) layout only");
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+        if (nan_policy != AUXSSM_NAN_REFERENCE) {
+            set_error("the batched multivariate-t sweep runs nan_policy 0 (reference) only: its sequences observe one scalar, which the reference's nansum drops alone");
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+    }
     const double* dptr;
     if ((rc = delta_block(h, dtype, delta_dev, &dptr))) return rc;
     SweepCall c{h, dtype, dims, model, yobs, delta, dptr, keys, parallel, nan_policy, layout, x, eps_aux, eps_samp, u_acc, accepted, logs};
-    if (keys && (lorenz || sv))  // these sweeps read the noise from the arrays: draw all of it first (auxssm_kalman_draw)
+    if (keys && (lorenz || sv || mvt))  // these sweeps read the noise from the arrays: draw all of it first (auxssm_kalman_draw)
         by_dtype(dtype, [&](auto r) {
             launch_rng_sweep<decltype(r)>(h, keys, (long long)dims->C * dims->T * dims->dx, dims->C, const_cast<void*>(eps_aux), const_cast<void*>(eps_samp),
                                           const_cast<void*>(u_acc));
             return AUXSSM_OK;
         });
     if (sv) c.order = model_kind == AUXSSM_KMODEL_SV_FIRST ? 1 : 2;
+    if (mvt) c.order = model_kind == AUXSSM_KMODEL_MVT_FIRST ? 1 : 2;
     return by_dtype(dtype, [&](auto r) {
         using R = decltype(r);
+        if (mvt) return sweep_mvt<R>(c);
         return lorenz ? sweep_lorenz<R>(c) : sv ? sweep_sv<R>(c) : sweep_lg_concat<R>(c);
     });
 }

@@ -39,8 +39,8 @@ def get_kernel(dynamics_factory, observations_factory, log_likelihood_fn, parall
 def _same_device_model(*fns):
     owners = [getattr(f, "__self__", None) for f in fns]
     names = [getattr(f, "__name__", "") for f in fns]
-    from .models import LGConcatModel, SVModel, LorenzModel
-    if (isinstance(owners[0], (LGConcatModel, SVModel, LorenzModel)) and all(o is owners[0] for o in owners)
+    from .models import LGConcatModel, SVModel, LorenzModel, MVTModel
+    if (isinstance(owners[0], (LGConcatModel, SVModel, LorenzModel, MVTModel)) and all(o is owners[0] for o in owners)
             and names == ["dynamics_factory", "observations_factory", "log_likelihood_fn"]):
         return owners[0]
     return None
@@ -292,6 +292,8 @@ def _get_device_kernel(model, parallel, nan_policy="reference"):
         out.logs = logs
         return out
 
+    if getattr(model, "batched_state", False):
+        kernel = _batched_state_kernel(kernel, model)
     kernel.sweep = sweep
     kernel.draw = draw
 
@@ -299,3 +301,33 @@ def _get_device_kernel(model, parallel, nan_policy="reference"):
         return KalmanSampler(x=x, updated=True)
 
     return init, kernel
+
+
+def _batched_state_kernel(inner, model):
+    """A model in the reference's batched form (kalman.MVTModel): a host state is (T, d, 1) -- what the example's init yields -- or (T, d), either with a leading
+    chain axis.  The device sweep sees (T, d) / (C, T, d); the result has the shape that went in, explicit noise comes in the state's shape.  Resident chains
+    pass straight through."""
+    T, d = model.T, model.dx
+
+    def kernel(key, state, delta, noise=None):
+        if not isinstance(delta, _lib.DeviceArray):
+            model.check_delta(delta)
+        if isinstance(state.x, DeviceChains):
+            if (state.x.T, state.x.dx) != (T, d) or state.x.chain_minor:
+                raise ValueError(f"the model is (T, d) = ({T}, {d}) and sweeps dense chains: DeviceChains(handle, x (C, {T}, {d}), chain_minor=False)")
+            return inner(key, state, delta, noise)
+        x = np.asarray(state.x)
+        shape = x.shape
+        if shape in ((T, d, 1), (T, d)):
+            core = (T, d)
+        elif x.ndim >= 3 and shape[1:] in ((T, d, 1), (T, d)):
+            core = (shape[0], T, d)
+        else:
+            raise ValueError(f"state of shape {shape}: expected ({T}, {d}, 1) or ({T}, {d}), alone or behind a chain axis")
+        if noise is not None:
+            noise = dict(noise, eps_aux=np.reshape(noise["eps_aux"], core), eps_samp=np.reshape(noise["eps_samp"], core))
+        out = inner(key, KalmanSampler(x=x.reshape(core), updated=state.updated), delta, noise)
+        out.x = np.reshape(out.x, shape)
+        return out
+
+    return kernel

@@ -240,3 +240,151 @@ class LorenzModel:
             pbuf = dl.bufs["lorenz_par"] = handle.to_device(np.repeat(pbuf.to_host(), C, axis=0), dtype)
             dl.c.Fs = pbuf.arr(4 if C > 1 else 0, 0, 0)
         return pbuf
+
+
+class _DeviceModel:
+    """the C struct of a device model whose arrays do not have the LGSSM's shapes, with the buffers it points at"""
+
+    def __init__(self):
+        self.c = _lib.Lgssm()
+        self.bufs = {}
+
+
+class MVTModel:
+    """The spatial example's batched model (examples/spatial/auxiliary_kalman.py:10-66, model.py:103-124): d independent scalar LGSSMs
+    x_{t+1,k} = F_k x_{t,k} + b_k + N(0, Q_k), x_{0,k} ~ N(m0_k, P0_k), coupled only through the multivariate Student-t potential
+    log g_t(x) = -(nu + d) / 2 log(1 + (y_t - x)^T prec (y_t - x) / nu) (NaN -> 0), in the reference's batched shapes: the state is (T, d, 1),
+
+        dynamics_factory(x)           -> m0 (d, 1), P0 (d, 1, 1), tile(F), tile(Q) (T - 1, d, 1, 1), tile(b) (T - 1, d, 1)                    (:24-28)
+        observations_factory(x, u, d) -> order 1: ys = u + d/2 nan_to_num(grad(x)), H = 1, R = d/2, c = 0                                       (:30-38)
+                                         order 2: h = -nu diag(prec) / (nu - 2), Om = 1 / (-h + 2/d), ys = Om (2u/d + grad - h x), R = Om       (:40-48)
+        log_likelihood_fn(x)          -> sum_k [log N(x_0k; m0_k, P0_k) + sum_t log N(x_tk; F_k x_{t-1,k} + b_k, Q_k)] + sum_t log g_t(x_t)      (:50-54)
+
+    with the closed-form gradient grad_x log g_t = (nu + d) prec (y_t - x_t) / (nu + q_t), q_t = (y_t - x_t)^T prec (y_t - x_t), in place of jax.grad.
+    ys (T, d) (a NaN anywhere in y_t makes the step's potential flat); m0, b (d,) or (d, 1); P0, F, Q (d,) or (d, 1, 1); prec dense (d, d), symmetric positive
+    definite; nu > 0 (order 2: nu != 2); 1 <= d <= 64.  Pass the three bound methods to kalman.get_kernel: it runs the device sweep (model kind MVT_FIRST /
+    MVT_SECOND, csrc/kalman_mvt.hip: C * d scalar recursions) on host states of shape (T, d, 1), (T, d), either with a leading chain axis, or on resident
+    DeviceChains(handle, x (C, T, d), chain_minor=False).  Order 2 needs -h_k + 2/delta > 0 for every component: checked for a host step size (ValueError), a
+    precondition for a device-resident one.  The same methods are NumPy factories for the host path and the oracle."""
+    dense_only = True
+    batched_state = True  # the reference's state carries a trailing axis of 1 (kalman.generic strips and restores it around the device sweep)
+    MAX_D = 64
+
+    def __init__(self, ys, m0, P0, F, Q, b, nu, prec, order=1):
+        if order not in (1, 2):
+            raise ValueError("order must be 1 or 2")
+        self.yobs = np.asarray(ys)
+        if self.yobs.ndim != 2:
+            raise ValueError(f"MVTModel: ys must be (T, d), got shape {self.yobs.shape}")
+        self.T, self.dx = self.yobs.shape
+        d = self.dx
+        if not 1 <= d <= self.MAX_D:
+            raise ValueError(f"MVTModel: d = {d}: the batched sweep covers 1 <= d <= {self.MAX_D}")
+        if not (np.ndim(nu) == 0 and np.isfinite(float(nu)) and float(nu) > 0):
+            raise ValueError(f"MVTModel: nu must be a finite scalar > 0 (got {nu!r})")
+        if order == 2 and float(nu) == 2.0:
+            raise ValueError("MVTModel: order=2 divides by nu - 2: nu == 2 is refused")
+        P = np.asarray(prec, np.float64)
+        if P.ndim != 2 or P.shape != (d, d):
+            raise ValueError(f"MVTModel: prec must be a dense ({d}, {d}) matrix (got shape {np.shape(prec)})")
+        if not np.all(np.isfinite(P)) or np.max(np.abs(P - P.T)) > 1e-12 * np.max(np.abs(P)):
+            raise ValueError("MVTModel: prec must be finite and symmetric (to 1e-12 relative)")
+        try:
+            np.linalg.cholesky(P)
+        except np.linalg.LinAlgError:
+            raise ValueError("MVTModel: prec must be positive definite") from None
+
+        def diag(a, name, shapes):
+            a = np.asarray(a, np.float64)
+            if a.shape not in shapes:
+                raise ValueError(f"MVTModel: {name} must have shape {' or '.join(map(str, shapes))}, got {a.shape}")
+            return a.reshape(d)
+
+        self.p_obs = d
+        self.nu, self.prec, self.order = float(nu), 0.5 * (P + P.T), order
+        self.m0v, self.bv = diag(m0, "m0", ((d,), (d, 1))), diag(b, "b", ((d,), (d, 1)))
+        self.P0v, self.Fv, self.Qv = (diag(a, n, ((d,), (d, 1, 1))) for a, n in ((P0, "P0"), (F, "F"), (Q, "Q")))
+        if np.any(self.P0v <= 0) or np.any(self.Qv <= 0):
+            raise ValueError("MVTModel: P0 and Q must be positive")
+        self.hess_diag = -self.nu * np.diagonal(self.prec) / (self.nu - 2.0) if order == 2 else np.zeros(d)
+        self.kmodel = _lib.KMODEL_MVT_FIRST if order == 1 else _lib.KMODEL_MVT_SECOND
+        self._dev = {}
+
+    def check_delta(self, delta):
+        """order 2: Omega_k^-1 = -h_k + 2/delta must be positive for every component (it is a variance's inverse)"""
+        if self.order == 2 and not np.all(2.0 / float(delta) + (-self.hess_diag) > 0):
+            raise ValueError(f"MVTModel: order=2 needs 2/delta + nu prec_kk / (nu - 2) > 0 for every component: delta = {float(delta)!r} gives "
+                             f"min {float(np.min(2.0 / float(delta) - self.hess_diag)):.3g}")
+
+    # ---- the potential (t_distribution.py:98-104, model.py:116-124) and its gradient ----
+    def _rz(self, x):
+        x = np.asarray(x)
+        x = x.reshape(-1, self.dx)
+        r = self.yobs.astype(x.dtype) - x
+        return r, r @ self.prec.astype(x.dtype).T
+
+    def log_potential(self, x):
+        """sum_t nan_to_num(log g_t(x_t)), x (T, d) or (T, d, 1)"""
+        r, z = self._rz(x)
+        with np.errstate(all="ignore"):
+            q = np.sum(z * r, -1)
+            val = -(0.5 * (self.nu + self.dx)) * np.log1p(q / self.nu)
+        return float(np.sum(np.nan_to_num(val)))
+
+    def grad_log_potential(self, x):
+        """(T, d): (nu + d) prec (y_t - x_t) / (nu + q_t); NaN where y_t has a NaN (the factories decide what to do with it)"""
+        r, z = self._rz(x)
+        with np.errstate(all="ignore"):
+            q = np.sum(z * r, -1, keepdims=True)
+            return (self.nu + self.dx) * z / (self.nu + q)
+
+    # ---- NumPy factories in the reference's batched shapes ----
+    def dynamics_factory(self, x):
+        dt = np.asarray(x).dtype
+        T, d = self.T, self.dx
+        Fs = np.tile(self.Fv.astype(dt).reshape(1, d, 1, 1), (T - 1, 1, 1, 1))
+        Qs = np.tile(self.Qv.astype(dt).reshape(1, d, 1, 1), (T - 1, 1, 1, 1))
+        bs = np.tile(self.bv.astype(dt).reshape(1, d, 1), (T - 1, 1, 1))
+        return self.m0v.astype(dt).reshape(d, 1), self.P0v.astype(dt).reshape(d, 1, 1), Fs, Qs, bs
+
+    def observations_factory(self, x, u, delta):
+        x, u = np.asarray(x), np.asarray(u)
+        T, d = self.T, self.dx
+        dt = u.dtype
+        x, u = x.reshape(T, d, 1), u.reshape(T, d, 1)
+        eyes, zeros = np.ones((T, d, 1, 1), dt), np.zeros((T, d, 1), dt)
+        grad = self.grad_log_potential(x).reshape(T, d, 1)
+        with np.errstate(all="ignore"):
+            if self.order == 1:
+                grad = np.nan_to_num(grad)
+                return (u + 0.5 * delta * grad).astype(dt), eyes, (0.5 * delta * eyes).astype(dt), zeros
+            h = self.hess_diag.astype(dt)
+            om = 1.0 / (-h[None, :, None, None] + 2 * eyes / delta)
+            ys = om[..., 0] * (2 * u / delta + grad - h[None, :, None] * x)
+        return ys.astype(dt), eyes, om.astype(dt), zeros
+
+    def log_likelihood_fn(self, x):
+        x = np.asarray(x)
+        x = x.reshape(self.T, self.dx)
+
+        def norm(v, loc, var):
+            return -0.5 * (v - loc) ** 2 / var - 0.5 * np.log(var) - 0.5 * np.log(2 * np.pi)
+
+        with np.errstate(all="ignore"):
+            out = np.nansum(norm(x[0], self.m0v, self.P0v))
+            out += np.nansum(norm(x[1:], self.Fv * x[:-1] + self.bv, self.Qv))
+        return float(out) + self.log_potential(x)
+
+    # ---- device side ----
+    def device(self, handle, dtype):
+        key = (id(handle), np.dtype(dtype).str)
+        dev = self._dev.get(key)
+        if dev is None:
+            dl = _DeviceModel()
+            # include/auxssm.h, MVT_FIRST / MVT_SECOND: the diagonal model as (d) vectors; prec rides in the Rs slot, [nu] in the cs slot
+            for name, a in (("m0", self.m0v), ("P0", self.P0v), ("Fs", self.Fv), ("Qs", self.Qv), ("bs", self.bv), ("Rs", self.prec), ("cs", [self.nu])):
+                buf = dl.bufs[name] = handle.to_device(np.asarray(a, np.float64), dtype)
+                setattr(dl.c, name, buf.arr(0, 0, 0))
+            ybuf, yarr = _upload_arr(handle, self.yobs, (self.dx,), 1, self.T, 1, False, False, np.dtype(dtype), "ys")
+            dev = self._dev[key] = (dl, ybuf, yarr)
+        return dev

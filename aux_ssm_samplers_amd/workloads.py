@@ -76,6 +76,17 @@ def spatial_setup(T, grid, seed=0, sigma_x=1.0, nu=1.0, tau=-0.25, r_y=1):
     return M0, Mt, G0, Gt, x, y, prec
 
 
+def spatial_kalman_setup(T, grid, seed=0, sigma_x=1.0, nu=1.0, tau=-0.25, r_y=1, order=1):
+    """The spatial example for its auxiliary Kalman sampler (examples/spatial/auxiliary_kalman.py): the data of spatial_setup (same recipe, same seed -> same
+    x and y) and the batched dynamics of model.py:103-112 (F = 1, Q = P0 = sigma_x^2, b = m0 = 0 per component).
+    Returns (model, x0): a kalman.MVTModel and a start state of the reference's shape (T, d, 1) -- the simulated states."""
+    from aux_ssm_samplers_amd.kalman import MVTModel
+    *_, x, y, prec = spatial_setup(T, grid, seed, sigma_x, nu, tau, r_y)
+    d = grid * grid
+    F, Q, b = np.ones((d, 1, 1)), sigma_x ** 2 * np.ones((d, 1, 1)), np.zeros((d, 1))
+    return MVTModel(y, b, Q, F, Q, b, nu, prec, order=order), x[..., None]
+
+
 def lgssm_tracking_setup(T, dx, dy, seed=0):
     """A partially observed linear-Gaussian state-space model, 1 <= dy <= dx: x_0 ~ N(0, I), x_t = F x_{t-1} + eps_t with a stable banded F (0.9 on the
     diagonal, 0.05 / -0.05 beside it) and Q = 0.25 I, observations y_t ~ N(H x_t, R) with a dense H (every entry non-zero: each sensor sees a mixture of all

@@ -203,7 +203,19 @@ typedef enum {
      * LG_CONCAT does; log_likelihood_fn(x) = log N(x_0; m0, P0) + sum log N(x_{t+1}; mean(x_t), Q) + nansum_t log N(y_t; H_t x_t + c_t, R_t).
      * `model`: m0, P0, Qs as usual; Fs.ptr -> DEVICE array [theta1, theta2, theta3, dt] of `dtype`, chain stride Fs.sc (0: one theta for all chains; 4: one row per chain) (bs unused); Hs, Rs, cs = the
      * real observation model (rows of unobserved steps may be NaN); yobs (T, dy) with NaN = missing; dx = 3, dy <= 3; dense or chain-minor layout. */
-    AUXSSM_KMODEL_LORENZ63_EXT = 4
+    AUXSSM_KMODEL_LORENZ63_EXT = 4,
+    /* The spatial example's batched model (examples/spatial/auxiliary_kalman.py:10-66, model.py:103-124): dx independent scalar LGSSMs
+     * x_{t+1,k} = F_k x_{t,k} + b_k + N(0, Q_k), x_{0,k} ~ N(m0_k, P0_k), coupled only through the multivariate Student-t potential
+     * log g_t(x) = -(nu + dx) / 2 log(1 + (y_t - x)^T prec (y_t - x) / nu), NaN -> 0.  observations_factory(x, u, d) is the first-order
+     * (ys = u + d/2 nan_to_num(grad), R = d/2) or second-order (h_k = -nu prec_kk / (nu - 2), Omega_k = 1 / (-h_k + 2/d),
+     * ys = Omega (2u/d + grad - h x), R = Omega; needs nu != 2 and -h_k + 2/d > 0) auxiliary observation set with H = 1, c = 0 per component;
+     * log_likelihood_fn(x) = sum_k prior_logpdf(x_{.,k}) + sum_t log g_t(x_t).
+     * `model`: m0, P0, Fs, Qs, bs point at (dx) VECTORS of `dtype` (the diagonal model; strides ignored); Rs.ptr -> prec (dx, dx) row-major and
+     * cs.ptr -> [nu], both DEVICE arrays of `dtype` (Hs unused).  yobs (T, dx) with NaN = missing (a NaN anywhere makes the step's potential flat),
+     * dims->dy = dx <= 64; dense layout and nan_policy 0 only (anything else: AUXSSM_ERR_UNSUPPORTED, nothing enqueued); `parallel` is ignored
+     * (csrc/kalman_mvt.hip: C * dx scalar recursions of length T). */
+    AUXSSM_KMODEL_MVT_FIRST = 5,
+    AUXSSM_KMODEL_MVT_SECOND = 6
 } auxssm_kalman_model;
 typedef enum { AUXSSM_LAYOUT_DENSE = 0, AUXSSM_LAYOUT_CHAIN_MINOR = 1 } auxssm_layout;
 int auxssm_kalman_sweep(auxssm_handle h, int dtype, int model_kind, const auxssm_dims* dims,

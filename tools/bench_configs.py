@@ -7,6 +7,8 @@
    spatial  the spatial example on the 5 x 5 grid (dx = 25, T = 1024, N = 25, multivariate Student-t potential) beside the SV potential at the same shape, 256 chains
    lingauss  a partially observed linear-Gaussian model (dx = 24, dy = 12, T = 1024, N = 25, linear-Gaussian observation potential) beside GaussianObsPotential
              at the same shape, 256 chains
+   spatial_kalman  the spatial example's default sampler: the auxiliary Kalman sampler on the batched 8 x 8 model (d = 64, T = 1024, nu = 1, fp32, both orders), device
+             sweep at 1 / 16 / 256 chains beside the host-factory path
    pit30  the reference's SV experiment at its defaults (--parallel, D = 30, N = 25, T = 250): the parallel-in-time sweep beside the sequential wide sweep, 1 / 16 / 256 chains
    loop the MCMC loop around the sweeps (aux_ssm_samplers_amd.loop: running moments, acceptance averages, adaptation, Lorenz theta step) on C2 / C3 / C4
 Prints one JSON line per measurement.  Inputs are resident in HBM (DeviceChains) where the API allows it; device Threefry noise."""
@@ -422,8 +424,67 @@ def sv30_kalman(T=250, D=30, chains=(1, 16, 64)):
                 print(json.dumps(dict(config=f"SV protocol D={D} T={T}, aux-Kalman order {order}", chains=C_, error=f"{type(e).__name__}: {e}")), flush=True)
 
 
+def spatial_kalman(grid=8, T=1024, chains=(1, 16, 256), steps=50, host_reps=3):
+    """the spatial example's own default sampler (examples/spatial/experiment.py --style kalman): the auxiliary Kalman sampler on the batched model, 8 x 8 grid
+    (d = 64), T = 1024, nu = 1, fp32, both orders: the device sweep (kalman.MVTModel, csrc/kalman_mvt.hip) on 1 / 16 / 256 resident chains, keyed noise, beside the
+    host-factory path of the same run (the same methods behind lambdas, one chain).  Step size: the reference's adaptation rule for 200 sweeps (target 0.5).
+    Bytes: what the sweep's passes move, counted from the shapes (PASSES arrays of C T d reals), over the sweep time; beside the device-to-device copy rate of the
+    same run (read + write of a 256 MiB buffer).  The kernel groups' shares come from a separate profiled pass."""
+    import functools
+    from aux_ssm_samplers_amd.common import delta_adaptation
+    from aux_ssm_samplers_amd.loop import loop
+    from aux_ssm_samplers_amd.workloads import spatial_kalman_setup
+    # rng 2 | obs at x: 4 | filter: 3 | sampler: 7 | obs at x': 3 | reverse filter: 2 | select: 2
+    PASSES = 23
+    h = _lib.default_handle()
+    a, b_ = h.zeros((64 << 20,), np.float32), h.zeros((64 << 20,), np.float32)
+    b_.copy_from(a)
+    h.sync()
+    t0 = time.perf_counter()
+    for _ in range(20):
+        b_.copy_from(a)
+    h.sync()
+    copy_rate = 20 * 2 * a.nbytes / (time.perf_counter() - t0)
+    del a, b_
+    d = grid * grid
+    for order in (1, 2):
+        model, x0 = spatial_kalman_setup(T, grid, order=order)
+        x0 = x0[..., 0].astype(np.float32)
+        init, kernel = get_kernel(model.dynamics_factory, model.observations_factory, model.log_likelihood_fn, True)
+        rule = functools.partial(delta_adaptation, min_delta=1e-6, max_delta=1.0)
+        delta = None
+        for C_ in chains:
+            ch = DeviceChains(h, np.repeat(x0[None], C_, axis=0), chain_minor=False)
+            if delta is None:
+                delta = loop(R.PRNGKey(0), 1e-3, KalmanSampler(x=ch, updated=True), kernel, rule, 200, target_alpha=0.5, lr=0.3, beta=0.2)[3]
+            v, ms, acc = timed_sweeps(kernel, ch, delta, steps=steps, warmup=5)
+            h.prof_enable(_lib.K_ALL, 16 * 10)
+            timed_sweeps(kernel, ch, delta, steps=10, warmup=0)
+            groups = {k: round(t / 10, 4) for k, (n, t) in h.prof_read_groups().items()}
+            h.prof_disable()
+            nbytes = PASSES * C_ * T * d * 4
+            print(json.dumps(dict(config=f"spatial {grid} x {grid} (d={d}) T={T} nu=1, aux-Kalman order {order}, fp32, device sweep (batched scalar), resident chains",
+                                  chains=C_, delta=float(f"{delta:.3g}"), ms_per_sweep=round(ms, 4), sweeps_per_s=round(v, 1), accept=acc,
+                                  algorithm_bytes_per_sweep=nbytes, achieved_GBps=round(nbytes / ms / 1e6, 1), copy_GBps=round(copy_rate / 1e9, 1),
+                                  ms_per_sweep_by_kernel_group=groups)), flush=True)
+        # the host-factory path: the same methods, not recognisable as a device model; one chain
+        hinit, hkernel = get_kernel(lambda x: model.dynamics_factory(x), lambda x, u, dl: model.observations_factory(x, u, dl), lambda x: model.log_likelihood_fn(x), True)
+        st = hinit(x0[..., None])
+        keys = R.split(R.PRNGKey(3), host_reps + 1)
+        st = hkernel(keys[0], st, delta)
+        h.sync()
+        t0 = time.perf_counter()
+        for k in range(host_reps):
+            st = hkernel(keys[1 + k], st, delta)
+        h.sync()
+        print(json.dumps(dict(config=f"spatial {grid} x {grid} (d={d}) T={T} nu=1, aux-Kalman order {order}, fp32, host-factory path", chains=1,
+                              delta=float(f"{delta:.3g}"), ms_per_sweep=round((time.perf_counter() - t0) / host_reps * 1e3, 2))), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["c3k", "c4", "c5"]
+    if "spatial_kalman" in which:
+        spatial_kalman()
     if "sv30" in which:
         sv30()
     if "guided" in which:
