@@ -181,6 +181,7 @@ ScanPlan plan_scan(const auxssm_ctx* h, int S, int n, int parallel, int waves) {
 #define AX_DECL_UNIT(NAME) \
     const KalmanEntry* kalman_unit_##NAME(int P); \
     const SampleEntry* sample_unit_##NAME(); \
+    const SmoothEntry* smooth_unit_##NAME(); \
     const SweepLogpdfEntry* sweep_logpdf_unit_##NAME(int PO);
 AX_DECL_UNIT(f32_d1) AX_DECL_UNIT(f32_d2) AX_DECL_UNIT(f32_d3) AX_DECL_UNIT(f32_d4)
 AX_DECL_UNIT(f64_d1) AX_DECL_UNIT(f64_d2) AX_DECL_UNIT(f64_d3) AX_DECL_UNIT(f64_d4)
@@ -200,6 +201,7 @@ AX_DECL_UNIT(f64_d1) AX_DECL_UNIT(f64_d2) AX_DECL_UNIT(f64_d3) AX_DECL_UNIT(f64_
     } while (0)
 const KalmanEntry* kalman_entry(int dtype, int D, int P) { AX_UNIT_ENTRY(kalman, P); }
 const SampleEntry* sample_entry(int dtype, int D) { AX_UNIT_ENTRY(sample); }
+const SmoothEntry* smooth_entry(int dtype, int D) { AX_UNIT_ENTRY(smooth); }
 const SweepLogpdfEntry* sweep_logpdf_entry(int dtype, int D, int PO) { AX_UNIT_ENTRY(sweep_logpdf, PO); }
 
 static inline Arr cv(const auxssm_arr& a) { return Arr{a.ptr, (long long)a.sc, (long long)a.st, (long long)a.sb, 1}; }
@@ -1777,6 +1779,48 @@ int auxssm_kalman_sample(auxssm_handle h, int dtype, const auxssm_dims* dims, co
     a.eps = dense_arr(eps, kd, dims->dx); a.xs = dense_arr(xs, kd, dims->dx); a.elem = nullptr;
     a.lay = ScanLayout{1, 1, 1, 1, 0, kd.C * kd.B};
     return e->sample(h, a, parallel);
+}
+
+int auxssm_kalman_smooth(auxssm_handle h, int dtype, const auxssm_dims* dims, const auxssm_lgssm* lgssm,
+                         const void* ms, const void* Ps, int parallel, void* sms, void* sPs) {
+    AX_NEED_H(h);
+    int rc;
+    if ((rc = check_dtype(dtype)) || (rc = check_dims(dims, false))) return rc;
+    if (!lgssm || !ms || !Ps || !sms || !sPs || (dims->T > 1 && (!lgssm->Fs.ptr || !lgssm->Qs.ptr || !lgssm->bs.ptr))) {
+        set_error("lgssm(Fs,Qs,bs)/ms/Ps/sms/sPs must be non-NULL");
+        return AUXSSM_ERR_ARG;
+    }
+    if (dims->dx > MAX_D) {
+        set_error("the smoother is instantiated for dx <= %d (dx = %d); auxssm_kalman_sample covers wide states", MAX_D, dims->dx);
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    {  // the scan reads (ms, Ps) of every step while it writes (sms, sPs) of others: no output may overlap an input (or the other output)
+        const size_t rs = dtype == AUXSSM_F32 ? 4 : 8;
+        const size_t nm = (size_t)dims->C * dims->T * dims->B * dims->dx * rs, nP = nm * dims->dx;
+        const auto overlap = [](const void* p, size_t np, const void* q, size_t nq) {
+            const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+            return a < b + nq && b < a + np;
+        };
+        if (overlap(sms, nm, ms, nm) || overlap(sms, nm, Ps, nP) || overlap(sPs, nP, ms, nm) || overlap(sPs, nP, Ps, nP) || overlap(sms, nm, sPs, nP)) {
+            set_error("sms / sPs may not alias ms / Ps (or each other)");
+            return AUXSSM_ERR_ARG;
+        }
+    }
+    const SmoothEntry* e = smooth_entry(dtype, dims->dx);
+    if (!e) {
+        set_error("dx=%d is not instantiated in this build", dims->dx);
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    const KDims kd{dims->C, dims->T, dims->B};
+    if ((rc = ws_reserve(h, e->smooth_ws(h, kd, parallel) + 4096))) return rc;
+    SmoothArgs a;
+    a.d = kd;
+    a.Fs = cv(lgssm->Fs); a.Qs = cv(lgssm->Qs); a.bs = cv(lgssm->bs);
+    a.ms = dense_arr(ms, kd, dims->dx); a.Ps = dense_arr(Ps, kd, (long long)dims->dx * dims->dx);
+    a.sms = dense_arr(sms, kd, dims->dx); a.sPs = dense_arr(sPs, kd, (long long)dims->dx * dims->dx);
+    a.elem = nullptr;
+    a.lay = ScanLayout{1, 1, 1, 1, 0, kd.C * kd.B};
+    return e->smooth(h, a, parallel);
 }
 
 int auxssm_kalman_dnc_sample(auxssm_handle h, int dtype, const auxssm_dims* dims, const auxssm_lgssm* lgssm, const void* ms, const void* Ps, const void* eps, void* xs) {

@@ -301,12 +301,19 @@ struct SampleEntry {
     sv_logpdf_ws_fn sv_logpdf_ws = nullptr;
 };
 
+typedef int (*smooth_fn)(auxssm_ctx*, const SmoothArgs&, int parallel);
+struct SmoothEntry {
+    smooth_fn smooth;
+    sample_ws_fn smooth_ws;
+};
+
 constexpr int MAX_D = 4;
 constexpr int MAX_P = 8;
 
 // defined by the instantiation units (inst_*.hip); nullptr entries = not built
 const KalmanEntry* kalman_entry(int dtype, int D, int P);
 const SampleEntry* sample_entry(int dtype, int D);
+const SmoothEntry* smooth_entry(int dtype, int D);
 const SweepLogpdfEntry* sweep_logpdf_entry(int dtype, int D, int PO);
 
 // wide.hip: one workgroup per time step / scan element, matrices in LDS -- every (dx, dy) the register kernels do not cover.

@@ -925,6 +925,168 @@ template <typename R, int D> AX_HD void body_sample_shared_tab(const SampleArgs&
     sample_shared_row<R, D>(F, Q, bd, Pd, last, row);
     stv<R, T::N>((R*)a.tab + (long long)t * T::NPAD, row);
 }
+// ---- RTS smoother: smoothing marginals from the filtered moments ---------------------------------------------------------
+struct SmoothArgs {
+    KDims d;
+    Arr Fs, Qs, bs;
+    Arr ms, Ps;       // (C,T,B,D), (C,T,B,D,D) dense: the filter's outputs
+    Arr sms, sPs;     // outputs, same shapes
+    void* elem;       // scan elements (layout `lay`), scan position j = T-1-t
+    ScanLayout lay;
+    const int* memo = nullptr;  // (never set: the scan kernels ask every argument struct for it)
+};
+
+template <typename R_, int D> struct SmoothOp;
+
+// scan element j = jp + 1 <-> time t = T-2-jp, jp in [0, T-1); lanes walk DOWN in time (as body_sample_init)
+template <typename R, int D, class IO> AX_HD void body_smooth_init(const SmoothArgs& a, IO& io, int s, int jp, bool valid) {
+    const int c = s / a.d.B, b = s % a.d.B;
+    const long long t = (long long)a.d.T - 2 - jp;
+    R m[D], Pd[D * D], F[D * D], Q[D * D], bd[D];
+    io.template fetch<R, D>(at<R>(a.ms, c, t, b), -a.ms.st, a.ms.se, valid, m);
+    io.template fetch<R, D * D>(at<R>(a.Ps, c, t, b), -a.Ps.st, a.Ps.se, valid, Pd);
+    io.template fetch<R, D * D>(at<R>(a.Fs, c, t, b), -a.Fs.st, a.Fs.se, valid, F);
+    io.template fetch<R, D * D>(at<R>(a.Qs, c, t, b), -a.Qs.st, a.Qs.se, valid, Q);
+    io.template fetch<R, D>(at<R>(a.bs, c, t, b), -a.bs.st, a.bs.se, valid, bd);
+    io.template finish<R, D>(-a.ms.st, a.ms.se, valid, m);
+    io.template finish<R, D * D>(-a.Ps.st, a.Ps.se, valid, Pd);
+    io.template finish<R, D * D>(-a.Fs.st, a.Fs.se, valid, F);
+    io.template finish<R, D * D>(-a.Qs.st, a.Qs.se, valid, Q);
+    io.template finish<R, D>(-a.bs.st, a.bs.se, valid, bd);
+    if (!valid) return;
+    SmoothElem<R, D> e;
+    smooth_elem<R, D>(false, F, Q, bd, m, Pd, e);
+    SmoothOp<R, D>::store_elem(a, s, jp + 1, e);
+}
+// scan element 0 <-> t = T-1
+template <typename R, int D> AX_HD void body_smooth_last(const SmoothArgs& a, int s) {
+    const int c = s / a.d.B, b = s % a.d.B;
+    const long long tl = (long long)a.d.T - 1;
+    R m[D], Pd[D * D];
+    rd<R, D>(a.ms, c, tl, b, m);
+    rd<R, D * D>(a.Ps, c, tl, b, Pd);
+    SmoothElem<R, D> e;
+    smooth_elem<R, D>(true, nullptr, nullptr, nullptr, m, Pd, e);
+    SmoothOp<R, D>::store_elem(a, s, 0, e);
+}
+
+template <typename R_, int D> struct SmoothOp {
+    using R = R_;
+    using Full = SmoothElem<R, D>;
+    using Pre = SmoothPre<R, D>;
+    using Args = SmoothArgs;
+    static constexpr int DS = symsize(D);
+    static AX_HD int length(const Args& a) { return a.d.T; }
+    static AX_HD const ScanLayout& layout(const Args& a) { return a.lay; }
+    static AX_HD const R* row_ptr(const Args& a, int s, int grp, int k) {
+        return (const R*)a.elem + ((long long)s * a.lay.seq_records() + a.lay.row(grp, k)) * Full::NPAD;
+    }
+    static AX_HD void unpack(const R* t, Full& e) {
+#pragma unroll
+        for (int i = 0; i < D * D; ++i) e.G[i] = t[i];
+#pragma unroll
+        for (int i = 0; i < D; ++i) e.g[i] = t[D * D + i];
+#pragma unroll
+        for (int i = 0; i < DS; ++i) e.L[i] = t[D * D + D + i];
+    }
+    static AX_HD void pack(const Full& e, R* t) {
+#pragma unroll
+        for (int i = 0; i < D * D; ++i) t[i] = e.G[i];
+#pragma unroll
+        for (int i = 0; i < D; ++i) t[D * D + i] = e.g[i];
+#pragma unroll
+        for (int i = 0; i < DS; ++i) t[D * D + D + i] = e.L[i];
+    }
+    static AX_HD void load_rec(const R* p, Full& e) {
+        R t[Full::N];
+        ldv<R, Full::N>(p, t);
+        unpack(t, e);
+    }
+    static AX_HD void store_rec(R* p, const Full& e) {
+        R t[Full::N];
+        pack(e, t);
+        stv<R, Full::N>(p, t);
+    }
+    static AX_HD void identity(Full& e) {
+#pragma unroll
+        for (int i = 0; i < D * D; ++i) e.G[i] = (i / D == i % D) ? (R)1 : (R)0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) e.g[i] = 0;
+#pragma unroll
+        for (int i = 0; i < DS; ++i) e.L[i] = 0;
+    }
+    static AX_HD void combine(const Full& a1, const Full& a2, Full& o) { smooth_combine<R, D>(a1, a2, o); }
+    static AX_HD void to_pre(const Full& f, Pre& p) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) p.g[i] = f.g[i];
+#pragma unroll
+        for (int i = 0; i < DS; ++i) p.L[i] = f.L[i];
+    }
+    static AX_HD void store_pre(R* q, const Pre& p) {
+        R t[Pre::N];
+#pragma unroll
+        for (int i = 0; i < D; ++i) t[i] = p.g[i];
+#pragma unroll
+        for (int i = 0; i < DS; ++i) t[D + i] = p.L[i];
+        stv<R, Pre::N>(q, t);
+    }
+    static AX_HD void load_pre(const R* q, Pre& p) {
+        R t[Pre::N];
+        ldv<R, Pre::N>(q, t);
+#pragma unroll
+        for (int i = 0; i < D; ++i) p.g[i] = t[i];
+#pragma unroll
+        for (int i = 0; i < DS; ++i) p.L[i] = t[D + i];
+    }
+    static AX_HD void apply(const Pre& p, const Full& e, Pre& o) { smooth_apply<R, D>(p, e, o); }
+    // inclusive prefix j  ->  smoothed moments at time T-1-j; the covariance is mirrored from its packed upper triangle
+    static AX_HD void write_out(const Args& a, int s, int j, const Pre& p) {
+        const int c = s / a.d.B, b = s % a.d.B;
+        const long long t = (long long)a.d.T - 1 - j;
+        R Pd[D * D];
+        symunpack<R, D>(p.L, Pd);
+        wr<R, D>(a.sms, c, t, b, p.g);
+        wr<R, D * D>(a.sPs, c, t, b, Pd);
+    }
+    static AX_HD void store_elem(const Args& a, int s, int j, const Full& e) { store_rec((R*)a.elem + a.lay.eoff(s, j, Full::NPAD), e); }
+    static AX_HD void load_elem(const Args& a, int s, int j, Full& e) { load_rec((const R*)a.elem + a.lay.eoff(s, j, Full::NPAD), e); }
+    using Raw = Full;
+    static AX_HD void load_raw(const Args& a, int s, int j, Raw& r) { load_elem(a, s, j, r); }
+    static AX_HD void build(const Args&, int, int, const Raw& r, Full& e) { e = r; }
+    static constexpr bool kFold = false;
+};
+
+// SmoothOp that never materialises its elements (as SampleOpFly): the tile scan gives every element a lane, which builds it from
+// (ms, Ps, F, Q, b) in registers -- no init launch, no element buffer.
+template <typename R_, int D> struct SmoothOpFly : SmoothOp<R_, D> {
+    using R = R_;
+    using Full = typename SmoothOp<R_, D>::Full;
+    struct Raw {
+        R m[D], Pd[D * D], F[D * D], Q[D * D], bd[D];
+    };
+    static AX_HD void load_raw(const SmoothArgs& a, int s, int j, Raw& r) {
+        const int c = s / a.d.B, b = s % a.d.B;
+        const long long t = (long long)a.d.T - 1 - j;
+        rd<R, D>(a.ms, c, t, b, r.m);
+        rd<R, D * D>(a.Ps, c, t, b, r.Pd);
+        if (j != 0) {
+            rd<R, D * D>(a.Fs, c, t, b, r.F);
+            rd<R, D * D>(a.Qs, c, t, b, r.Q);
+            rd<R, D>(a.bs, c, t, b, r.bd);
+        }
+    }
+    static AX_HD void build(const SmoothArgs&, int, int j, const Raw& r, Full& e) {
+        smooth_elem<R, D>(j == 0, r.F, r.Q, r.bd, r.m, r.Pd, e);
+    }
+    static AX_HD void load_elem(const SmoothArgs& a, int s, int j, Full& e) {
+        Raw r;
+        load_raw(a, s, j, r);
+        Full t;
+        build(a, s, j, r, t);
+        e = t;
+    }
+};
+
 // ---- joint log-density of a trajectory: log_likelihood + prior_logpdf (base.py:99-166) ----------------
 struct LogpdfArgs {
     KDims d;

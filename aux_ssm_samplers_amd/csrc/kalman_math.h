@@ -1056,6 +1056,133 @@ AX_HD void sample_apply(const SampPre<R, D>& p, const SampElem<R, D>& cur, SampP
 }
 
 // ------------------------------------------------------------------------------------------------
+// RTS smoother: the smoothing marginals N(sm_t, sP_t) from the filtered moments, as a backward scan of the sampler's shape.
+// Scan element (G, g, L) = the map  (sm, sP) -> (G sm + g, G sP G^T + L);  L symmetric-packed.  Memory record [G (D*D) | g (D) | L (DS)] padded.
+//   t < T-1: G_t, L_t = the sampler's gain and increment covariance (smooth_gain_cov), g_t = m_t - G_t (F_t m_t + b_t);   t = T-1: (0, m, P).
+// The prefix carries (g, L) only: the smoothed mean and covariance themselves.
+// ------------------------------------------------------------------------------------------------
+template <typename R, int D> struct SmoothElem {
+    static constexpr int DS = symsize(D);
+    static constexpr int N = D * D + D + DS;
+    static constexpr int VEC = 16 / sizeof(R);
+    static constexpr int NPAD = (N + VEC - 1) / VEC * VEC;
+    R G[D * D];
+    R g[D];
+    R L[DS];
+};
+template <typename R, int D> struct SmoothPre {
+    static constexpr int DS = symsize(D);
+    static constexpr int N = D + DS;
+    static constexpr int VEC = 16 / sizeof(R);
+    static constexpr int NPAD = (N + VEC - 1) / VEC * VEC;
+    R g[D];
+    R L[DS];
+};
+// The sampler's gain and increment covariance (sample_gain_chol above, sampling.py:60-98) without the factorisation: G = P (S^-1 F)^T, S = sym(F P F^T + Q),
+// Sg = P - G S G^T dense (the caller symmetrises).  Same statements in the same order; a function of its own so that the sampler's kernels compile exactly as before.
+template <typename R, int D>
+AX_HD void smooth_gain_cov(const R* F, const R* Q, const R* Pd, R* G, R* Sg) {
+    R FP[D * D], Sd[D * D], S[symsize(D)];
+    mm<R, D, D, D>(F, Pd, FP);
+    mmt<R, D, D, D>(FP, F, Sd);
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) Sd[i] += Q[i];
+    sympack<R, D>(Sd, S);
+    if constexpr (D == 1) {
+        G[0] = Pd[0] * F[0] / S[0];
+    } else {
+        R L[symsize(D)], invd[D];
+        const bool ok = chol_packed<R, D>(S, L, invd, nullptr);
+        R X[D * D];  // S^-1 F
+#pragma unroll
+        for (int i = 0; i < D * D; ++i) X[i] = F[i];
+#pragma unroll
+        for (int j = 0; j < D; ++j) cho_solve_col<R, D, D>(L, invd, X, j);
+        mmt<R, D, D, D>(Pd, X, G);  // gain = P X^T
+        if (!ok) {
+#pragma unroll
+            for (int i = 0; i < D * D; ++i) G[i] = r_nan<R>();
+        }
+    }
+    // inc_Sig = sym(P - gain S gain^T)
+    R gS[D * D];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            R s = 0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) s += G[i * D + k] * S[sidx(D, k, j)];
+            gS[i * D + j] = s;
+        }
+    mmt<R, D, D, D>(gS, G, Sg);
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) Sg[i] = Pd[i] - Sg[i];
+}
+// element of time t: `last` (t = T-1; F, Q, b are not read) or a transition step.  One symmetrisation behind the branch: with one in each arm the compiler merged
+// their tails into a store through a selected pointer, which kept part of the element in scratch memory.
+template <typename R, int D>
+AX_HD void smooth_elem(bool last, const R* F, const R* Q, const R* b, const R* m, const R* Pd, SmoothElem<R, D>& e) {
+    R Sg[D * D];
+    if (last) {
+#pragma unroll
+        for (int i = 0; i < D * D; ++i) e.G[i] = 0, Sg[i] = Pd[i];
+#pragma unroll
+        for (int i = 0; i < D; ++i) e.g[i] = m[i];
+    } else {
+        smooth_gain_cov<R, D>(F, Q, Pd, e.G, Sg);
+        R pm[D], t[D];
+        mv<R, D, D>(F, m, pm);
+#pragma unroll
+        for (int i = 0; i < D; ++i) pm[i] += b[i];
+        mv<R, D, D>(e.G, pm, t);
+#pragma unroll
+        for (int i = 0; i < D; ++i) e.g[i] = m[i] - t[i];
+    }
+    sympack<R, D>(Sg, e.L);
+}
+// out = G S G^T + L0, all three symmetric-packed: only the upper triangle is evaluated, so the result is symmetric by construction
+template <typename R, int D> AX_HD void smooth_congruence(const R* G, const R* S, const R* L0, R* out) {
+    R GS[D * D];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            R s = 0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) s += G[i * D + k] * S[sidx(D, k, j)];
+            GS[i * D + j] = s;
+        }
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) {
+            R s = 0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) s += GS[i * D + k] * G[j * D + k];
+            out[sidx_u(D, i, j)] = s + L0[sidx_u(D, i, j)];
+        }
+}
+// acc = later times already composed, cur = this time step (as sample_combine)
+template <typename R, int D>
+AX_HD void smooth_combine(const SmoothElem<R, D>& acc, const SmoothElem<R, D>& cur, SmoothElem<R, D>& o) {
+    mm<R, D, D, D>(cur.G, acc.G, o.G);
+    R t[D];
+    mv<R, D, D>(cur.G, acc.g, t);
+#pragma unroll
+    for (int i = 0; i < D; ++i) o.g[i] = t[i] + cur.g[i];
+    smooth_congruence<R, D>(cur.G, acc.L, cur.L, o.L);
+}
+template <typename R, int D>
+AX_HD void smooth_apply(const SmoothPre<R, D>& p, const SmoothElem<R, D>& cur, SmoothPre<R, D>& o) {
+    R t[D];
+    mv<R, D, D>(cur.G, p.g, t);
+#pragma unroll
+    for (int i = 0; i < D; ++i) o.g[i] = t[i] + cur.g[i];
+    smooth_congruence<R, D>(cur.G, p.L, cur.L, o.L);
+}
+
+// ------------------------------------------------------------------------------------------------
 // mvn.logpdf of a residual r with covariance given densely (math/mvn/base.py:15-58), N = dimension.
 //   drop_nonfinite: a non-finite residual component makes the reference's result NaN, which its nansum
 //   then drops -> return 0.  `skip` (may be null) deletes components (MASKED policy).

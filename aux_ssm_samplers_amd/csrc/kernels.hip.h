@@ -236,6 +236,17 @@ template <typename R, int D> __global__ void __launch_bounds__(TB_ELEM) k_sample
     body_sample_init<R, D>(a, io, s, jp, true);
 }
 
+template <typename R, int D> __global__ void __launch_bounds__(TB_ELEM) k_smooth_init(SmoothArgs a) {
+    int tile, s;
+    decode_tile_seq(a.d.S(), tile, s);
+    const int n = a.d.T - 1;
+    if (tile == 0 && threadIdx.x == 0) body_smooth_last<R, D>(a, s);
+    const int jp = tile * TB_ELEM + threadIdx.x;
+    if (jp >= n) return;
+    DirectIO io;
+    body_smooth_init<R, D>(a, io, s, jp, true);
+}
+
 // ---- chain-minor mode: lanes <-> sequences -----------------------------------------------------------------------------
 // Used by the fused sweep when many chains run side by side.  Per-chain buffers are [t][e][s] (cm_arr), so every component
 // load/store of a wave is one contiguous 64-real run, and chain-shared model parameters are the same address in every lane
@@ -1416,6 +1427,37 @@ template <typename R, int D> int run_sample(auxssm_ctx* h, const SampleArgs& a_i
     return AUXSSM_OK;
 }
 
+// ---- RTS smoother (dense layout): the sampler's launch plan with SmoothOp.  The chunked scan reads materialised elements (k_smooth_init: the chunk kernels stream
+// stored records through the wave-cooperative LDS staging); the tile scan builds them in registers (SmoothOpFly).  T = 1 is one chunk of one element: a copy.
+// No ProfScope: the profiler's groups are the AUXSSM_K_* ids of include/auxssm.h, and a new id would move AUXSSM_K_COUNT, which this extension of the ABI leaves alone.
+template <typename R, int D> bool smooth_tiles(const auxssm_ctx* h, int S, int T, const ScanLayout& lay) {
+    // ONE decision for the workspace, the element buffer and run_scan: SmoothOp and SmoothOpFly share Full / Pre, so run_scan's own use_ks<SmoothOpFly> on the same
+    // layout agrees with it (if it did not, the chunk kernels would read a null element buffer)
+    static_assert(SmoothOpFly<R, D>::Full::NPAD == SmoothOp<R, D>::Full::NPAD, "run_scan<SmoothOpFly> must choose the tile scan exactly when run_smooth leaves elem null");
+    return use_ks<SmoothOp<R, D>>(h, S, T, lay.nchunk > 1);
+}
+template <typename R, int D> size_t smooth_ws(const auxssm_ctx* h, const KDims& d, int parallel) {
+    const int S = d.S();
+    const size_t scan = scan_ws_bytes<SmoothOp<R, D>>(h, S, d.T, parallel);
+    const ScanLayout lay = make_layout(plan_scan(h, S, d.T, parallel), 0, S);
+    if (smooth_tiles<R, D>(h, S, d.T, lay)) return scan;  // no element buffer
+    return (size_t)S * lay.seq_records() * SmoothElem<R, D>::NPAD * sizeof(R) + 256 + scan;
+}
+template <typename R, int D> int run_smooth(auxssm_ctx* h, const SmoothArgs& a_in, int parallel) {
+    SmoothArgs a = a_in;
+    const int S = a.d.S(), T = a.d.T;
+    a.lay = make_layout(plan_scan(h, S, T, parallel), 0, S);
+    if (smooth_tiles<R, D>(h, S, T, a.lay)) {
+        a.elem = nullptr;
+        return run_scan<SmoothOpFly<R, D>>(h, a, S, T);
+    }
+    a.elem = ws_take(h, (size_t)a.lay.total_reals(T, S, SmoothElem<R, D>::NPAD) * sizeof(R));
+    if (!a.elem) return AUXSSM_ERR_NOMEM;
+    const int nt = ntiles(T - 1) > 0 ? ntiles(T - 1) : 1;
+    hipLaunchKernelGGL((k_smooth_init<R, D>), dim3(grid_tile_seq(nt, S)), dim3(TB_ELEM), 0, h->stream, a);
+    return run_scan<SmoothOp<R, D>>(h, a, S, T);
+}
+
 template <typename R, int D, int P> size_t logpdf_ws(const auxssm_ctx*, const KDims& d) {
     return (size_t)d.S() * (ntiles(d.T) + 1) * sizeof(R) + 256;
 }
@@ -1526,7 +1568,7 @@ template <typename R, int D, int PO> constexpr sweep_logpdf_fn lorenz_logpdf_ent
 
 #include "fused_shared.h"
 
-// one instantiation unit = one (dtype, D): all P for the filter / logpdf, plus the sampler
+// one instantiation unit = one (dtype, D): all P for the filter / logpdf, plus the sampler and the smoother
 #define AX_KALMAN_ENTRY(R, D, P) \
     { &run_filter<R, D, P>, &filter_ws<R, D, P>, &run_logpdf<R, D, P>, &logpdf_ws<R, D, P> }
 
@@ -1548,6 +1590,10 @@ template <typename R, int D, int PO> constexpr sweep_logpdf_fn lorenz_logpdf_ent
     }                                                                                                \
     const SampleEntry* sample_unit_##NAME() {                                                        \
         static const SampleEntry e = {&run_sample<R, D>, &sample_ws<R, D>, &run_sv_logpdf<R, D>, &sv_logpdf_ws<R, D>};                          \
+        return &e;                                                                                   \
+    }                                                                                                \
+    const SmoothEntry* smooth_unit_##NAME() {                                                        \
+        static const SmoothEntry e = {&run_smooth<R, D>, &smooth_ws<R, D>};                          \
         return &e;                                                                                   \
     }                                                                                                \
     }

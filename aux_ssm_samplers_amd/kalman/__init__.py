@@ -1,4 +1,5 @@
 from .generic import get_kernel, KalmanSampler, DeviceChains
 from .models import LGConcatModel, SVModel, LorenzModel, MVTModel
+from .._primitives.kalman.smoothing import smoothing, filter_smoothing
 
-__all__ = ["get_kernel", "KalmanSampler", "DeviceChains", "LGConcatModel", "SVModel", "LorenzModel", "MVTModel"]
+__all__ = ["get_kernel", "KalmanSampler", "DeviceChains", "LGConcatModel", "SVModel", "LorenzModel", "MVTModel", "smoothing", "filter_smoothing"]

@@ -13,11 +13,13 @@ def rot(theta):
 def lg_model(T, d, seed=0, dtype=np.float64):
     """SURVEY 8(d) C1/C2 linear-Gaussian SSM: F = 0.95*blkdiag(Rot(pi/16)[, Rot(pi/7)]), Q = 0.1 I,
     y_t = x_t + N(0, 0.5 I), m0 = 0, P0 = I.  Data from numpy Generator(PCG64(seed))."""
-    assert d in (1, 2, 4)
+    assert d in (1, 2, 3, 4)
     if d == 1:
         F = np.array([[0.95]])
     elif d == 2:
         F = 0.95 * rot(np.pi / 16)
+    elif d == 3:  # (not a BASELINE shape: the smoother's benchmark leg) a third, unrotated component
+        F = 0.95 * block_diag(rot(np.pi / 16), np.eye(1))
     else:
         F = 0.95 * block_diag(rot(np.pi / 16), rot(np.pi / 7))
     Q = 0.1 * np.eye(d)

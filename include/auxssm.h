@@ -149,6 +149,17 @@ int auxssm_kalman_filter(auxssm_handle h, int dtype, const auxssm_dims* dims, co
 int auxssm_kalman_sample(auxssm_handle h, int dtype, const auxssm_dims* dims, const auxssm_lgssm* lgssm,
                          const void* ms, const void* Ps, const void* eps, int parallel, void* xs);
 
+/* auxssm_kalman_smooth: the smoothing marginals  sms[t] = E[x_t | y_{0:T-1}],  sPs[t] = Cov[x_t | y_{0:T-1}]  (Rauch-Tung-Striebel) from the filtered moments.
+ *   ms (C,T,B,dx), Ps (C,T,B,dx,dx) dense as auxssm_kalman_filter writes them -> sms, sPs of the same shapes; of the model only Fs, Qs, bs are read (any chain or
+ *   batch stride, 0 included).  With S_t = sym(F_t P_t F_t^T + Q_t), G_t = P_t F_t^T S_t^-1 (an SPD solve) -- the pathwise sampler's gain (sampling.py:86-98):
+ *     sms[t] = m_t + G_t (sms[t+1] - F_t m_t - b_t),   sPs[t] = G_t sPs[t+1] G_t^T + sym(P_t - G_t S_t G_t^T),   sms[T-1] = m_{T-1}, sPs[T-1] = P_{T-1},
+ *   run as a backward associative scan over the elements (G, g, L) of the map (sm, sP) -> (G sm + g, G sP G^T + L).  parallel != 0: the chunked or the tile scan,
+ *   chosen as for auxssm_kalman_sample; 0: one chunk per sequence, i.e. the sequential recursion.  sPs is symmetric bit for bit.  T = 1 copies.
+ *   Refused before anything is enqueued: NULL arguments and sms / sPs overlapping ms / Ps or each other (AUXSSM_ERR_ARG); dx > 4 (AUXSSM_ERR_UNSUPPORTED:
+ *   auxssm_kalman_sample covers wide states). */
+int auxssm_kalman_smooth(auxssm_handle h, int dtype, const auxssm_dims* dims, const auxssm_lgssm* lgssm,
+                         const void* ms, const void* Ps, int parallel, void* sms, void* sPs);
+
 /* auxssm_kalman_dnc_sample == dnc_sampling.sampling(key, ms, Ps, lgssm) (_primitives/kalman/dnc_sampling.py:17-77: the divide-and-conquer pathwise sampler --
  *   leaves _init_elems :128-137, pairwise combination _combination_operator_impl :104-118 with the odd interval carried up :140-169, the two ends :46-68, the
  *   mid-points level by level :70-86) with the N(0, I) draws given explicitly: eps (C,T,dx) dense, time index t is sampled with eps[:, t].  The reference calls it a

@@ -10,6 +10,8 @@
    spatial_kalman  the spatial example's default sampler: the auxiliary Kalman sampler on the batched 8 x 8 model (d = 64, T = 1024, nu = 1, fp32, both orders), device
              sweep at 1 / 16 / 256 chains beside the host-factory path
    pit30  the reference's SV experiment at its defaults (--parallel, D = 30, N = 25, T = 250): the parallel-in-time sweep beside the sequential wide sweep, 1 / 16 / 256 chains
+   smoother  the RTS smoother (auxssm_kalman_smooth) beside the pathwise sampler (auxssm_kalman_sample) on the same resident filtered moments: C2's model at
+             T = 65536, d = 4, fp64, 1 and 256 sequences, and T = 16384, d = 3, fp32, 64 sequences; parallel scan, at one sequence also the sequential recursion
    loop the MCMC loop around the sweeps (aux_ssm_samplers_amd.loop: running moments, acceptance averages, adaptation, Lorenz theta step) on C2 / C3 / C4
 Prints one JSON line per measurement.  Inputs are resident in HBM (DeviceChains) where the API allows it; device Threefry noise."""
 import json
@@ -481,10 +483,70 @@ def spatial_kalman(grid=8, T=1024, chains=(1, 16, 256), steps=50, host_reps=3):
                               delta=float(f"{delta:.3g}"), ms_per_sweep=round((time.perf_counter() - t0) / host_reps * 1e3, 2))), flush=True)
 
 
+def smoother(runs=5):
+    """auxssm_kalman_smooth beside auxssm_kalman_sample of the same process on the same resident (ms, Ps): the filter runs once on the device (chain-shared model and
+    data, dense layout), then the two entry points are timed in alternating batches of back-to-back calls (~0.2 s each, `runs` per entry point) that end in a stream synchronisation; best and
+    median batch.  Bytes: what the call must move, counted from the shapes -- smoother: ms, Ps in, sms, sPs out = 2 (d + d^2) reals per step and sequence; sampler:
+    ms, Ps, eps in, xs out = 3 d + d^2 -- over the best time (the model is chain-shared and time-invariant: its reads are not counted)."""
+    import ctypes as C
+    from aux_ssm_samplers_amd.workloads import lg_model
+    from aux_ssm_samplers_amd._primitives.kalman.base import DeviceLGSSM
+    h = _lib.default_handle()
+    bt = np.broadcast_to
+
+    def timed_pair(calls):
+        """best and median ms per call of each of `calls`, their batches alternating; a batch is as many back-to-back calls as fill ~0.2 s"""
+        reps = []
+        for call in calls:
+            for _ in range(3):
+                call()
+            h.sync()
+            t0 = time.perf_counter()
+            call()
+            h.sync()
+            reps.append(int(min(2000, max(10, 0.2 / (time.perf_counter() - t0)))))
+        ts = [[] for _ in calls]
+        for _ in range(runs):
+            for k, call in enumerate(calls):
+                t0 = time.perf_counter()
+                for _ in range(reps[k]):
+                    call()
+                h.sync()
+                ts[k].append((time.perf_counter() - t0) / reps[k] * 1e3)
+        return [(min(t), float(np.median(t))) for t in ts]
+
+    for T, d, dtype, seqs in ((65536, 4, np.float64, (1, 256)), (16384, 3, np.float32, (64,))):
+        m = lg_model(T, d, dtype=dtype)
+        lg = (m["m0"], m["P0"], bt(m["F"], (T - 1, d, d)), bt(m["Q"], (T - 1, d, d)), bt(m["b"], (T - 1, d)),
+              bt(m["Hobs"], (T, d, d)), bt(m["Robs"], (T, d, d)), bt(m["cobs"], (T, d)))
+        dl = DeviceLGSSM(h, lg, 1, T, 1, d, d, False, dtype)
+        yd = h.to_device(np.asarray(m["y"], dtype))
+        code, item = _lib.dtype_code(dtype), np.dtype(dtype).itemsize
+        for S in seqs:
+            dims = _lib.Dims(S, T, 1, d, d)
+            ms, Ps, ell = h.empty((S, T, 1, d), dtype), h.empty((S, T, 1, d, d), dtype), h.empty((S,), dtype)
+            yarr = yd.arr(0, d, 0)
+            _lib.check(h.lib.auxssm_kalman_filter(h.h, code, C.byref(dims), C.byref(dl.c), C.byref(yarr), 1, ms.ptr, Ps.ptr, ell.ptr))
+            eps = h.rng_normal(R.PRNGKey(S), 0, (S, T, 1, d), dtype)
+            xs, sms, sPs = h.empty((S, T, 1, d), dtype), h.empty((S, T, 1, d), dtype), h.empty((S, T, 1, d, d), dtype)
+            for parallel in ((1, 0) if S == 1 else (1,)):
+                sm, sa = timed_pair([
+                    lambda: _lib.check(h.lib.auxssm_kalman_smooth(h.h, code, C.byref(dims), C.byref(dl.c), ms.ptr, Ps.ptr, parallel, sms.ptr, sPs.ptr)),
+                    lambda: _lib.check(h.lib.auxssm_kalman_sample(h.h, code, C.byref(dims), C.byref(dl.c), ms.ptr, Ps.ptr, eps.ptr, parallel, xs.ptr))])
+                b_sm, b_sa = S * T * 2 * (d + d * d) * item, S * T * (3 * d + d * d) * item
+                print(json.dumps(dict(config=f"RTS smoother beside the pathwise sampler, T={T} d={d} {np.dtype(dtype).name}, dense layout, resident moments",
+                                      sequences=S, parallel=parallel, smooth_ms=round(sm[0], 4), smooth_ms_median=round(sm[1], 4), sample_ms=round(sa[0], 4),
+                                      sample_ms_median=round(sa[1], 4), smooth_over_sample=round(sm[0] / sa[0], 3), smooth_bytes=b_sm, sample_bytes=b_sa,
+                                      smooth_GBps=round(b_sm / sm[0] / 1e6, 1), sample_GBps=round(b_sa / sa[0] / 1e6, 1))), flush=True)
+            del ms, Ps, eps, xs, sms, sPs
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["c3k", "c4", "c5"]
     if "spatial_kalman" in which:
         spatial_kalman()
+    if "smoother" in which:
+        smoother()
     if "sv30" in which:
         sv30()
     if "guided" in which:
