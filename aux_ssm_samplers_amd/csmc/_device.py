@@ -7,12 +7,12 @@ import numpy as np
 
 from .. import _lib, random as _random
 from .models import (GaussianInit, LinearGaussianDynamics, FlatPotential, GaussianObsPotential, SVPotential, Lorenz63Dynamics,
-                     MaskedGaussianObsPotential, MultivariateTPotential, LinearGaussianPotential, DevicePotential,
+                     MaskedGaussianObsPotential, MultivariateTPotential, LinearGaussianPotential, PoissonPotential, DevicePotential,
                      DeviceGaussianDynamics)
 
 _UNSUPPORTED = ("{what} is a Python object the HIP kernels cannot evaluate. The cSMC kernels run the closed model family "
                 "of aux_ssm_samplers_amd.csmc.models (GaussianInit, LinearGaussianDynamics, Lorenz63Dynamics, FlatPotential, "
-                "GaussianObsPotential, MaskedGaussianObsPotential, SVPotential, MultivariateTPotential, LinearGaussianPotential) in-kernel; there is no CPU fallback.")
+                "GaussianObsPotential, MaskedGaussianObsPotential, SVPotential, MultivariateTPotential, LinearGaussianPotential, PoissonPotential) in-kernel; there is no CPU fallback.")
 
 
 class FkDesc:
@@ -86,7 +86,7 @@ def _potential(G0, Gt, d):
         raise NotImplementedError(_UNSUPPORTED.format(what=f"G0={type(G0).__name__} with Gt={type(Gt).__name__}"))
     if isinstance(Gt, FlatPotential):
         return dict(kind=_lib.POT_FLAT)
-    if not isinstance(Gt, (MultivariateTPotential, LinearGaussianPotential, MaskedGaussianObsPotential, GaussianObsPotential, SVPotential)):
+    if not isinstance(Gt, (MultivariateTPotential, LinearGaussianPotential, PoissonPotential, MaskedGaussianObsPotential, GaussianObsPotential, SVPotential)):
         raise NotImplementedError(_UNSUPPORTED.format(what=f"Gt={type(Gt).__name__}"))
     y0 = G0.m0 if isinstance(G0, GaussianInit) else G0.y
     if y0 is None or Gt.params is None:
@@ -108,6 +108,9 @@ def _potential(G0, Gt, d):
         return dict(kind=_lib.POT_LIN_GAUSS, y=yw, obs_H=Hw, obs_const=c_lin)
     if isinstance(Gt, SVPotential):
         return dict(kind=_lib.POT_SV, y=ys)
+    if isinstance(Gt, PoissonPotential):
+        PoissonPotential.check_counts(ys)  # (G0.y / Gt.params may have been assigned after construction)
+        return dict(kind=_lib.POT_POISSON, y=ys)
     masked = isinstance(Gt, MaskedGaussianObsPotential)
     s0 = G0.sig if masked else (float(np.sqrt(np.reshape(G0.P0, -1)[0])) if isinstance(G0, GaussianInit) else Gt.sig)
     if abs(s0 - Gt.sig) > 1e-12 * Gt.sig:

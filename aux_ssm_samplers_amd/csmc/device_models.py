@@ -1,6 +1,6 @@
 """Example models written as device code for DevicePotential / DeviceGaussianDynamics (csmc.models; contract in csrc/fk_user_pre.h).
 
-BUILTIN_*: the built-in potentials (Gaussian, stochastic volatility, multivariate Student-t, linear-Gaussian observation) / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc_host.h::k_csmc_potbound written as user source, in the
+BUILTIN_*: the built-in potentials (Gaussian, stochastic volatility, multivariate Student-t, linear-Gaussian observation, Poisson counts) / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc_host.h::k_csmc_potbound written as user source, in the
 built-in operation order (fma_, det_exp, det_log), so that a program sweep reproduces the closed-family sweep bit for bit (the tests and
 tools/fk_program_bench.py use them).  The constants the host computes for the built-ins (csmc_host.h::fk_model) are formed the same way on
 the device from theta = [sig].  RARE_EVENT, STUDENT_T, GROWTH: models the closed family cannot express.
@@ -103,6 +103,29 @@ template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R
     bool obs = true;
     for (int k = 0; k < D; ++k) obs = obs && (y[k] - y[k] == 0);
     return obs ? theta[0] : (R)0;
+}
+"""
+
+# Poisson counts with a log link y_k ~ Poisson(exp(x_k)) (AUXSSM_POT_POISSON), the -log y_k! constant left out; no theta.  The order of include/auxssm.h, restated:
+# e_k = det_exp(x_k);  v_k = fma_(y_k, x_k, -e_k);  v_k counts only if y_k - y_k == 0;  accumulated over k ascending from 0.  Gradient y_k - det_exp(x_k), 0 for a
+# missing component.  Bound (k_csmc_potbound): sum_k (y_k > 0 ? y_k (det_log(y_k) - 1) : 0).  One source with the derivative: it serves plain and gradient programs.
+BUILTIN_POISSON = r"""
+template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta) {
+    R acc = 0;
+    for (int k = 0; k < D; ++k) {
+        const R e = det_exp(x[k]);
+        const R v = fma_(y[k], x[k], -e);
+        acc += (y[k] - y[k] == 0) ? v : (R)0;
+    }
+    return acc;
+}
+template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta) {
+    R b = 0;
+    for (int k = 0; k < D; ++k) b += y[k] > (R)0 ? y[k] * (det_log(y[k]) - (R)1) : (R)0;
+    return b;
+}
+template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
+    for (int k = 0; k < D; ++k) gx[k] = (y[k] - y[k] == 0) ? y[k] - det_exp(x[k]) : (R)0;
 }
 """
 

@@ -224,6 +224,36 @@ class LinearGaussianPotential(UnivariatePotential, Potential):
         return np.where(np.isnan(v), 0.0, v)
 
 
+@dataclass
+class PoissonPotential(UnivariatePotential, Potential):
+    """Counts with a log link, y_{t,k} ~ Poisson(exp(x_{t,k})), independent over the components (AUXSSM_POT_POISSON):
+        log g_t(x) = sum_k [ y_{t,k} x_k - exp(x_k) ]   over the components whose y_{t,k} is finite
+    -- a NaN y_{t,k} drops component k of step t (per component, as SVPotential; not the whole-step rule of the coupled potentials).  Unnormalised: the
+    constant -sum_k log y_{t,k}! is left out (it does not depend on x and cancels in every normalisation of the weights).  Non-integer values >= 0 are accepted,
+    the formula is the same; a finite negative entry raises ValueError at construction.  An offset (a log-exposure o_{t,k}: y ~ Poisson(exp(o + x))) needs no
+    field: it is a shift of the state, z = x + o, through m0 and b.  As G0 give y = ys[0]; as Gt give params = ys[1:]."""
+    y: Optional[Any] = None
+    params: Optional[Any] = None
+
+    @staticmethod
+    def check_counts(a):
+        a = np.asarray(a, np.float64)
+        if np.any(a[np.isfinite(a)] < 0):
+            raise ValueError(f"PoissonPotential: counts must be >= 0 or NaN (missing); got a minimum of {float(np.nanmin(a))}")
+
+    def __post_init__(self):
+        for a in (self.y, self.params):
+            if a is not None:
+                self.check_counts(a)
+
+    def __call__(self, x, y):
+        """the NumPy formula (batched over the leading axes of x); a non-finite y_k drops its component"""
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            v = y * x - np.exp(x)
+        return np.sum(np.where(np.isfinite(y), v, 0.0), axis=-1)
+
+
 # ---- user-defined models: device code compiled when the kernel is built (csrc/fk_program.hip, include/auxssm.h auxssm_fk_program_compile) ----------
 @dataclass
 class DevicePotential(UnivariatePotential, Potential):

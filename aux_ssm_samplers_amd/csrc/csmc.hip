@@ -124,9 +124,9 @@ template <typename R, int D> static bool c3_shape(const FkDev<R>& m, const CsmcA
 
 // The forward pass of (model, sweep), nw = nw_class(N).  TV: time-varying transitions; GRAD: gradient-informed proposals; P = FkBuiltin<R, D, V>, V the variant of
 // the model's potential (csmc_sweep.h::with_pot).
-//   case                            k_csmc_fwd<R, D, ...>
-//   coupled potential, guided       <false, GRAD, 0, 2, P>
-//   coupled potential, otherwise    <TV, GRAD, 0, 0, P>                      the generic workgroup for every N
+//   case                            k_csmc_fwd<R, D, ...>                    ("own variant": a coupled potential or the Poisson potential, V != SEP)
+//   own variant, guided             <false, GRAD, 0, 2, P>
+//   own variant, otherwise          <TV, GRAD, 0, 0, P>                      the generic workgroup for every N
 //   guided, separable potentials    <false, GRAD, nw == 16 ? 16 : 0, 2, P>   N = 512 takes the generic one
 //   c3_shape                        <float, 1, false, false, 16, 1>
 //   everything else                 <TV, GRAD, nw, 0, P>

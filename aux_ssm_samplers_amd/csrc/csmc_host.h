@@ -30,10 +30,12 @@ static const PotKind POT_KINDS[] = {
     /* AUXSSM_POT_MVT */ {true, &auxssm_fk_model::prec, "the multivariate-t potential needs its precision matrix prec (host, dx x dx)", true},
     /* AUXSSM_POT_LIN_GAUSS */
     {true, &auxssm_fk_model::obs_H, "the linear-Gaussian observation potential needs its whitened observation matrix obs_H (host, dx x dx)", true},
+    /* AUXSSM_POT_POISSON */ {true, nullptr, nullptr, true},
 };
 constexpr int POT_NKINDS = sizeof(POT_KINDS) / sizeof(POT_KINDS[0]);
 static_assert(POT_FLAT == AUXSSM_POT_FLAT && POT_GAUSS_OBS == AUXSSM_POT_GAUSS_OBS && POT_SV == AUXSSM_POT_SV && POT_GAUSS_OBS_MASKED == AUXSSM_POT_GAUSS_OBS_MASKED &&
-                  POT_MVT == AUXSSM_POT_MVT && POT_LIN_GAUSS == AUXSSM_POT_LIN_GAUSS && POT_NKINDS == AUXSSM_POT_LIN_GAUSS + 1,
+                  POT_MVT == AUXSSM_POT_MVT && POT_LIN_GAUSS == AUXSSM_POT_LIN_GAUSS && POT_POISSON == AUXSSM_POT_POISSON && POT_NKINDS == 7 &&
+                  POT_NKINDS == AUXSSM_POT_POISSON + 1,
               "csmc_sweep.h restates the potential kinds of include/auxssm.h");
 static const PotKind& pot_kind(int kind) { return POT_KINDS[kind]; }  // (kind checked by check_fk_model)
 // the matrix of fk's potential (host, dx x dx), or null for a potential without one
@@ -199,6 +201,11 @@ template <typename R> __global__ void k_csmc_potbound(int T, int D, int potentia
             if (y2 - y2 == 0) v = y2 > (R)0 ? fma_((R)-0.5, (R)1 + det_log(y2), c_obs) : (R)INFINITY;
             b += v > (R)0 ? v : (R)0;
         }
+    } else if (potential == AUXSSM_POT_POISSON) {  // sum_k [y x - e^x] <= sum_k y (log y - 1), attained at x_k = log y_k; y_k = 0 and a missing y_k add 0: always finite
+        for (int k = 0; k < D; ++k) {
+            const R yk = y[(long long)t * D + k];
+            b += yk > (R)0 ? yk * (det_log(yk) - (R)1) : (R)0;
+        }
     }
     gb[t] = b;
 }
@@ -214,7 +221,8 @@ template <typename R, typename M> static void fk_guided(auxssm_ctx* h, const Csm
         with_pot(m.potential, [&](auto pv) {
             constexpr PotV V = decltype(pv)::value;
             const long long total = (long long)a.C * a.T;
-            if constexpr (V != PotV::SEP) hipLaunchKernelGGL((k_csmc_gshift_coupled<R, M, V>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, h->stream, a, m);
+            if constexpr (pot_has_matrix(V)) hipLaunchKernelGGL((k_csmc_gshift_coupled<R, M, V>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, h->stream, a, m);
+            else if constexpr (V == PotV::POIS) hipLaunchKernelGGL((k_csmc_gshift_pois<R>), dim3((unsigned)((total * m.D + 255) / 256)), dim3(256), 0, h->stream, a, m.D);
             else hipLaunchKernelGGL((k_csmc_gshift<R>), dim3((unsigned)((total * m.D + 255) / 256)), dim3(256), 0, h->stream, a, m.D, m.potential, m.inv_sig_y);
         });
     hipLaunchKernelGGL((k_csmc_gtab<R, M>), dim3(a.T), dim3(64), 0, h->stream, a.T, m, (const R*)a.shd, (R*)a.gtab);

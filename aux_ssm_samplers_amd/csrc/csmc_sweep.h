@@ -195,15 +195,21 @@ template <typename R, int D> AXD_HD void trans_mean(const FkDev<R>& m, const R* 
 // The kinds (the values of AUXSSM_POT_* of include/auxssm.h, which hipRTC cannot include: csmc_host.h asserts that they agree) and their compile-time VARIANT:
 // the separable kinds share one code path and are told apart at run time inside it; a potential that couples the components through a dx x dx matrix
 // (FkDev::pot_mat) is a variant of its own, so that the instantiations of the other potentials hold none of its code -- as a fifth run-time branch the
-// multivariate-t potential cost every forward instantiation twelve registers in fp64 and a wave of occupancy.
-enum { POT_FLAT = 0, POT_GAUSS_OBS = 1, POT_SV = 2, POT_GAUSS_OBS_MASKED = 3, POT_MVT = 4, POT_LIN_GAUSS = 5 };
-enum class PotV { SEP, MVT, LIN };  // separable (kinds 0 - 3) | multivariate Student-t | linear-Gaussian observation
+// multivariate-t potential cost every forward instantiation twelve registers in fp64 and a wave of occupancy.  The Poisson count potential is
+// separable like kinds 0 - 3 but a variant of its own for the same reason: the instantiations of the other potentials stay as they were.
+enum { POT_FLAT = 0, POT_GAUSS_OBS = 1, POT_SV = 2, POT_GAUSS_OBS_MASKED = 3, POT_MVT = 4, POT_LIN_GAUSS = 5, POT_POISSON = 6 };
+enum class PotV { SEP, MVT, LIN, POIS };  // separable (kinds 0 - 3) | multivariate Student-t | linear-Gaussian observation | Poisson counts
 template <PotV V> struct PotC { static constexpr PotV value = V; };
-AXD_HD constexpr PotV pot_variant(int kind) { return kind == POT_MVT ? PotV::MVT : (kind == POT_LIN_GAUSS ? PotV::LIN : PotV::SEP); }
+AXD_HD constexpr PotV pot_variant(int kind) {
+    return kind == POT_MVT ? PotV::MVT : (kind == POT_LIN_GAUSS ? PotV::LIN : (kind == POT_POISSON ? PotV::POIS : PotV::SEP));
+}
+// whether the variant carries a dx x dx matrix (FkDev / FkW::pot_mat; the wide kernels stage it in LDS): the coupled potentials
+AXD_HD constexpr bool pot_has_matrix(PotV v) { return v == PotV::MVT || v == PotV::LIN; }
 // f(PotC<V>{}) for the variant V of a run-time kind: the ONE place a kind becomes a template argument (host: the kernel choices; device: potential_rt)
 template <typename F> AXD_HD auto with_pot(int kind, F&& f) {
     if (pot_variant(kind) == PotV::MVT) return f(PotC<PotV::MVT>{});
     if (pot_variant(kind) == PotV::LIN) return f(PotC<PotV::LIN>{});
+    if (pot_variant(kind) == PotV::POIS) return f(PotC<PotV::POIS>{});
     return f(PotC<PotV::SEP>{});
 }
 
@@ -291,10 +297,31 @@ template <typename R> AXD_HD R sep_grad_term(int kind, R inv_sig_y, R xk, R yk) 
     }
     return v;
 }
+// The Poisson count potential y_k ~ Poisson(exp(x_k)), the ONE definition of its per-component arithmetic (include/auxssm.h: the order; the -log y_k! constant is
+// left out): the term y_k x_k - e^{x_k} and its derivative y_k - e^{x_k}, both 0 for a missing (non-finite) y_k.  Every kernel family sums the terms over k
+// ascending from 0 (the wide kernels from half-wave broadcasts: csmc_wide_shared.h::potential_half).
+template <typename R> AXD_HD R pois_term(R xk, R yk) {
+    const R e = det_exp(xk);
+    const R v = fma_(yk, xk, -e);
+    return (yk - yk == 0) ? v : (R)0;
+}
+template <typename R> AXD_HD R pois_grad_term(R xk, R yk) { return (yk - yk == 0) ? yk - det_exp(xk) : (R)0; }
+// d / dx_k of a potential that is a sum over the components, by variant (SEP: the run-time kind of sep_grad_term; POIS): k_cw_grad, k_csmc_gshift_pois
+template <typename R, PotV V> AXD_HD R comp_grad_term(int kind, R inv_sig_y, R xk, R yk) {
+    static_assert(!pot_has_matrix(V), "a coupled potential's gradient is not component by component (coupled_grad)");
+    if constexpr (V == PotV::POIS) return pois_grad_term<R>(xk, yk);
+    else return sep_grad_term<R>(kind, inv_sig_y, xk, yk);
+}
 // potential g_t(x_t) (csmc test fixtures test_csmc/common.py:52-75; SV examples/stochastic_volatility/auxiliary_csmc.py:40-46) of the variant V, chosen at
 // COMPILE time; potential_rt below is the run-time choice for the callers that are not register-bound
 template <typename R, int D, PotV V = PotV::SEP> AXD_HD R potential(const FkDev<R>& m, const R* x, const R* y) {
-    if constexpr (V != PotV::SEP) return coupled_value<R, V, D>(m, m.pot_mat, CS_MAXD, x, y);
+    if constexpr (pot_has_matrix(V)) return coupled_value<R, V, D>(m, m.pot_mat, CS_MAXD, x, y);
+    if constexpr (V == PotV::POIS) {
+        R acc = 0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) acc += pois_term<R>(x[k], y[k]);
+        return acc;
+    }
     if (m.potential == POT_FLAT) return (R)0;
     if (m.potential == POT_GAUSS_OBS) {  // y ~ N(x, sig_y^2 I)
         R q = 0;
@@ -331,11 +358,11 @@ template <typename R, int D, PotV V = PotV::SEP> AXD_HD R potential(const FkDev<
 }
 // gx = d potential / dx at x (the closed family's potentials do not read x_{t-1}); y = the D reals of row t, or nullptr
 template <typename R, int D, PotV V = PotV::SEP> __device__ __forceinline__ void potential_grad(const FkDev<R>& m, const R* x, const R* y, R* gx) {
-    if constexpr (V != PotV::SEP) {
+    if constexpr (pot_has_matrix(V)) {
         coupled_grad<R, V, D>(m, m.pot_mat, CS_MAXD, x, y, [&](int k, R v) { gx[k] = v; });
     } else {
 #pragma unroll
-        for (int k = 0; k < D; ++k) gx[k] = sep_grad_term<R>(m.potential, m.inv_sig_y, x[k], y ? y[k] : (R)0);
+        for (int k = 0; k < D; ++k) gx[k] = comp_grad_term<R, V>(m.potential, m.inv_sig_y, x[k], y ? y[k] : (R)0);
     }
 }
 // the potential kind of m at run time, the coupled variants included (the parallel-in-time kernels, a user program that keeps the built-in potential)

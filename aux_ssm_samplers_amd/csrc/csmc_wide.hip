@@ -194,7 +194,7 @@ template <typename R, int NW2, bool GD = false, PotV V = PotV::SEP> __global__ v
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, N = a.N, T = a.T, D = m.D;
     const bool hi = lane >= 32;
     const int k = lane & 31;
-    constexpr bool coupled = V != PotV::SEP;
+    constexpr bool coupled = pot_has_matrix(V);
     Cw2Lds<R> L(smem, D, GD, coupled);
     if constexpr (coupled) cw2_stage_pot_mat<R>(m, L, tid, NT_);  // (published by cw2_stage's barrier)
     cw2_stage<R>(m, L, tid, NT_);
@@ -506,7 +506,7 @@ template <typename R, int NW2> __global__ void __launch_bounds__(64 * NW2) k_cw2
 //   forward   guided                 k_cw2_fwd<R, 8, true, V>                    eight waves whatever the chain count
 //             otherwise              k_cw2_fwd<R, wide16 ? 16 : 8, false, V>
 //   backward                         k_cw2_bwd<R, wide16 ? 16 : 8>               the base LDS plan (Cw2Lds::bytes)
-// The forward pass's LDS is Cw2Lds::fwd_bytes(D, guided, V != PotV::SEP): the coupled potentials' matrices share one slot, so neither plan exceeds the other's.
+// The forward pass's LDS is Cw2Lds::fwd_bytes(D, guided, pot_has_matrix(V)): the coupled potentials' matrices share one slot, so neither plan exceeds the other's.
 // (guided: under the 128 registers of a 1024-lane workgroup the two extra row products and the second blocked density spill, 360 bytes per lane in fp32:
 // 7.47 ms against 5.11 ms per sweep of the SV protocol at 256 chains)
 template <typename R> using WideKernel = void (*)(CsmcArgs, FkW<R>);

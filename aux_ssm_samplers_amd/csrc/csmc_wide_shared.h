@@ -50,7 +50,8 @@ template <typename R> __device__ __forceinline__ void cho_solve_w(int D, const R
 }
 // the gradient of the model's joint log-density at u (csmc_sweep.h::k_csmc_grad, same operations in the same order; one thread per (chain, time step):
 // C T threads of O(dx^2) work, once per sweep -- 0.5 M multiply-adds at the SV protocol's size)
-// V: a coupled potential's gradient is a compile-time variant (its z[32] would otherwise add scratch to the kernel of the other potentials)
+// V: a coupled potential's gradient is a compile-time variant (its z[32] would otherwise add scratch to the kernel of the other potentials); so is the
+// Poisson potential's, which is component by component like the separable kinds' (csmc_sweep.h::comp_grad_term)
 template <typename R, PotV V = PotV::SEP> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)a.C * a.T) return;
@@ -59,10 +60,10 @@ template <typename R, PotV V = PotV::SEP> __global__ void k_cw_grad(CsmcArgs a, 
     const R* u = (const R*)a.u + g * D;
     R gr[CSW_MAXD], r[CSW_MAXD], w[CSW_MAXD];
     const R* yv = (const R*)a.y;
-    if constexpr (V != PotV::SEP) {
+    if constexpr (pot_has_matrix(V)) {
         coupled_grad<R, V, 0>(m, m.pot_mat, D, u, yv + t * D, [&](int k, R v) { gr[k] = v; });
     } else {
-        for (int k = 0; k < D; ++k) gr[k] = sep_grad_term<R>(m.potential, m.inv_sig_y, u[k], yv ? yv[t * D + k] : (R)0);
+        for (int k = 0; k < D; ++k) gr[k] = comp_grad_term<R, V>(m.potential, m.inv_sig_y, u[k], yv ? yv[t * D + k] : (R)0);
     }
     if (t == 0) {
         for (int k = 0; k < D; ++k) r[k] = u[k] - m.m0[k];
@@ -201,11 +202,17 @@ template <typename R, PotV V> __device__ __forceinline__ R coupled_half(const Fk
     if constexpr (MVT) return mvt_value<R>(m.mvt_hc, (R)1 + q * m.mvt_inv_nu);
     else return lin_value<R>(m.c_obs, q);
 }
-// g_t(x) of that particle, the potential's variant V chosen at compile time.  Separable: per-component terms in the lanes, summed in component order
-// (csmc_sweep.h::potential with a runtime dimension, same operations)
+// g_t(x) of that particle, the potential's variant V chosen at compile time.  Separable and Poisson: per-component terms in the lanes, summed in component order
+// (csmc_sweep.h::potential with a runtime dimension, same operations; components beyond D add + 0)
 template <typename R, PotV V> __device__ __forceinline__ R potential_half(const FkW<R>& m, int k, bool hi, R xk, R yk, const R* Mrow) {
-    if constexpr (V != PotV::SEP) return coupled_half<R, V>(m, k, xk, yk, Mrow);
+    if constexpr (pot_has_matrix(V)) return coupled_half<R, V>(m, k, xk, yk, Mrow);
     const int D = m.D;
+    if constexpr (V == PotV::POIS) {  // SV's shape: the term of this lane's component, then the half-wave broadcast sum in component order
+        const R v = k < D ? pois_term<R>(xk, yk) : (R)0;
+        R acc = 0;
+        static_for<0, CSW_MAXD>([&](auto jc) { acc += half_bcast<R, decltype(jc)::value>(v); });
+        return acc;
+    }
     if (m.potential == 0) return (R)0;
     if (m.potential == 1 || m.potential == 3) {
         const bool obs = m.potential == 1 || (yk - yk == 0);

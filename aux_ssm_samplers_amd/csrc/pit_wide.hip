@@ -11,7 +11,7 @@
 //            carried over line for line.  The N transition means and the N potentials are formed in the half-wave form; the N^2 densities are evaluated one pair
 //            per lane by a forward substitution unrolled to 32 rows, rows beyond dx skipped: the row-oriented order of csmc_sweep.h::gauss_chol_logpdf itself.
 //   trace    pit.hip::k_pit_trace (run-time dx).
-// Linear-Gaussian transitions (time-invariant, or time-varying: a stitch stages row mid - 1), the six built-in potentials, gradient proposals (the per-particle
+// Linear-Gaussian transitions (time-invariant, or time-varying: a stitch stages row mid - 1), the seven built-in potentials, gradient proposals (the per-particle
 // correction in either AUXSSM_GRAD_* mode, as for dx <= 4), fp32 and fp64, explicit and Threefry noise.
 #include "csmc_wide_shared.h"
 #include "pit_shared.h"
@@ -44,7 +44,7 @@ template <typename R> struct PwLeafLds {
 template <typename R, PotV V> __global__ void __launch_bounds__(PWL_NT) k_pitw_leaves(PitArgs a, FkW<R> m) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, N = a.N, T = a.T, D = m.D;
-    constexpr bool coupled = V != PotV::SEP;
+    constexpr bool coupled = pot_has_matrix(V);
     PwLeafLds<R> L(smem, D);
     const bool grad = a.lwt != nullptr;
     const long long ct = (long long)c * T + t;
@@ -159,7 +159,7 @@ template <typename R, PotV V> __global__ void __launch_bounds__(256) k_pitw_stit
     const int j = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, N = a.N, T = a.T, D = m.D;
     const long long s0 = (long long)j << (k + 1), mid = s0 + (1ll << k);
     if (mid >= T) return;  // passthrough node (uniform per workgroup)
-    constexpr bool coupled = V != PotV::SEP;
+    constexpr bool coupled = pot_has_matrix(V);
     const int NCH = blockDim.x, nw = NCH >> 6;
     PwStitchLds<R> L(smem, D, N, NCH);
     R *cs = L.cs, *red = L.red, *sub = L.sub, *pg = L.pg, *hh = L.hh;
@@ -346,7 +346,7 @@ template <typename R> static int run_pw(auxssm_ctx* h, const auxssm_fk_model* fk
     FkW<R> m;
     if (int rc = cw_model<R>(h, fk, m)) return rc;
     const int D = m.D;
-    const bool coupled = pot_variant(m.potential) != PotV::SEP;
+    const bool coupled = pot_has_matrix(pot_variant(m.potential));
     CsmcArgs ca{};
     ca.C = a.C; ca.T = a.T; ca.N = a.N;
     ca.y = a.y; ca.shd = a.shd; ca.x = a.x; ca.u = const_cast<void*>(a.u); ca.grad = const_cast<void*>(a.grad);

@@ -112,6 +112,26 @@ def lgssm_tracking_setup(T, dx, dy, seed=0):
     return M0, Mt, LinearGaussianPotential(H=H, R=R, y=y[0]), LinearGaussianPotential(H=H, R=R, params=y[1:]), x, y, H, R
 
 
+def poisson_setup(T, dx, seed=0):
+    """Multivariate counts with a log link: a stable linear-Gaussian log-intensity x_t = F x_{t-1} + b + eps_t with the banded F of lgssm_tracking_setup (0.9 on
+    the diagonal, 0.05 / -0.05 beside it), Q = 0.04 I, b = (I - F) 1 so that the stationary mean is 1 in every component, x_0 ~ N(1, P0) with P0 = 0.2 I (about
+    the stationary variance), and y_{t,k} ~ Poisson(exp(x_{t,k})): intensities around e, counts mostly 0 .. 30.
+    Returns (M0, Mt, G0, Gt, x, y): the model as the cSMC kernels take it (csmc.PoissonPotential), the simulated states and counts (float64)."""
+    from aux_ssm_samplers_amd.csmc import GaussianInit, LinearGaussianDynamics, PoissonPotential
+    rng = np.random.Generator(np.random.PCG64(seed))
+    F = 0.9 * np.eye(dx) + 0.05 * np.eye(dx, k=1) - 0.05 * np.eye(dx, k=-1)
+    m0 = np.ones(dx)
+    b = m0 - F @ m0
+    Q, P0 = 0.04 * np.eye(dx), 0.2 * np.eye(dx)
+    x = np.zeros((T, dx))
+    x[0] = m0 + np.sqrt(0.2) * rng.standard_normal(dx)
+    for t in range(1, T):
+        x[t] = F @ x[t - 1] + b + 0.2 * rng.standard_normal(dx)
+    y = rng.poisson(np.exp(x)).astype(np.float64)
+    M0, Mt = GaussianInit(m0=m0, P0=P0), LinearGaussianDynamics(F=F, b=b, Q=Q)
+    return M0, Mt, PoissonPotential(y=y[0]), PoissonPotential(params=y[1:]), x, y
+
+
 def lorenz_kalman_setup(T, every=8, dt=0.01, seed=0):
     """examples/lorenz: theta = (10, 28, 8/3), sigma_x = 3, m0 = (1.5, -1.5, 25), P0 = diag(400, 20, 20), (x2, x3) observed every `every`-th
     step with variance 5, NaN rows (ys AND Hs, as model.py:43-56) elsewhere."""

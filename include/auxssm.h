@@ -282,7 +282,8 @@ int auxssm_kalman_state_resolve(auxssm_handle h, int dtype, const auxssm_dims* d
  * A Python Mt/Gt object cannot run inside a kernel; the Feynman-Kac model is a closed family instead:
  *   transition  x_t | x_{t-1} ~ N(F x_{t-1} + b, Q)   (time-invariant), initial N(m0, P0)
  *   potential   FLAT: 0 | GAUSS_OBS: log N(y_t; x_t, sig_y^2 I) | SV: sum_k log N(y_{t,k}; 0, exp(x_{t,k})) | GAUSS_OBS_MASKED | MVT: multivariate Student-t
- *               with a precision matrix | LIN_GAUSS: log N(y_t; H x_t + c, R), dy <= dx (auxssm_fk_potential below)
+ *               with a precision matrix | LIN_GAUSS: log N(y_t; H x_t + c, R), dy <= dx | POISSON: sum_k [y_{t,k} x_{t,k} - exp(x_{t,k})]
+ *               (auxssm_fk_potential below)
  *   proposal    BOOTSTRAP_LG:    M0 = initial, Mt = transition, G0/Gt = potential          (test_csmc/common.py fixtures)
  *               AUX_INDEPENDENT: u = x + sqrt(delta_t/2) eps_aux; M0/Mt = N(u_t, delta_t/2 I);
  *                                G0 = log initial + potential, Gt = log transition + potential, Pt = transition
@@ -327,7 +328,7 @@ typedef enum {
                                         log g = (v == v) ? v : 0.  The constants (nu + dx)/2 and 1/nu are formed once on the host in the sweep's dtype.  Gradient (prec
                                         symmetric):  d log g / dx_k = (-((nu + dx)/2 + (nu + dx)/2) * (1/nu) / s) * z_k = -(nu + dx)/(nu + q) z_k to rounding, every component 0 when s is NaN.
                                         sup_x log g = 0, which is the forward pass's reduction-free bound at dx <= 4; the wide kernels (dx > 4) shift by the exact maximum of every step, the bound being tens of nats above the weights there. */
-    AUXSSM_POT_LIN_GAUSS = 5         /* the linear-Gaussian observation y_t ~ N(H x_t + c, R), H (dy,dx) dense, R (dy,dy) symmetric positive definite, 1 <= dy <= dx:
+    AUXSSM_POT_LIN_GAUSS = 5,        /* the linear-Gaussian observation y_t ~ N(H x_t + c, R), H (dy,dx) dense, R (dy,dy) symmetric positive definite, 1 <= dy <= dx:
                                           log g_t(x) = log N(y_t; H x + c, R),  the whole value 0 when it is NaN
                                         (any NaN component of y_t makes the step flat).  The CALLER whitens once, in double, with L = chol(R):
                                           Hw = L^-1 H,  yw_t = L^-1 (y_t - c),  c_lin = -sum_k log L_kk - (dy/2) log 2 pi,   log g_t(x) = c_lin - |yw_t - Hw x|^2 / 2
@@ -339,6 +340,19 @@ typedef enum {
                                         Gradient:  d log g / dx_j = sum_k fma(H_kj, z_k, .) with k ascending from 0, every component 0 when v is NaN.
                                         sup_x log g <= c_lin (0 on a NaN row), the forward pass's reduction-free bound at dx <= 4; the wide kernels (dx > 4) shift by the exact
                                         maximum of every step, as for AUXSSM_POT_MVT. */
+    AUXSSM_POT_POISSON = 6           /* counts with a log link, y_{t,k} ~ Poisson(exp(x_{t,k})), independent over the components:
+                                          log g_t(x) = sum_k [ y_{t,k} x_k - exp(x_k) ]   over the components whose y_{t,k} is finite
+                                        (a NaN y_{t,k} drops component k of step t, per component as for AUXSSM_POT_SV -- not the whole-step rule of the coupled kinds).
+                                        UNNORMALISED: the constant -sum_k log y_{t,k}! is left out, as the multivariate-t potential leaves out its normaliser; it does
+                                        not depend on x and cancels in every normalisation of the weights.  y is not checked on the device: the caller passes finite
+                                        entries >= 0 (non-integers are accepted: the formula is the same) or NaN.  An offset (log-exposure) needs no field: it is a
+                                        shift of the state, through m0 and b.
+                                        Arithmetic order (every kernel; explicit fma, det_exp, no contraction):  e_k = det_exp(x_k);  v_k = fma(y_k, x_k, -e_k);
+                                        v_k counts only if y_k - y_k == 0;  log g = sum of the counted v_k, accumulated over k ascending from 0 (from 0).
+                                        Gradient:  d log g / dx_k = y_k - det_exp(x_k), 0 for a missing component.
+                                        sup_x log g = sum_k (y_k > 0 ? y_k (det_log(y_k) - 1) : 0) (attained at x_k = log y_k; missing components and y_k = 0 add 0), always
+                                        finite: the forward pass's reduction-free bound at dx <= 4; the wide kernels (dx > 4) shift by the exact maximum of every step,
+                                        as for AUXSSM_POT_MVT and AUXSSM_POT_LIN_GAUSS. */
 } auxssm_fk_potential;
 /* transition x_{t+1} | x_t ~ N(mean(x_t), Q): LINEAR mean = F x + b; LORENZ63_EM mean = x + dt (phi_0(x) + theta * phi(x)), the
  * Euler-Maruyama step of examples/lorenz/model.py:10-25 (dx = 3; theta = F[0..2], dt = b[0], Q = chol_Q chol_Q^T = dt sigma_x^2 I) */
@@ -447,7 +461,7 @@ int auxssm_csmc_sweep_program(auxssm_handle h, auxssm_fk_program prog, int dtype
  * same flat indices).  x (C,T,dx) in/out; ancestors (C,T) int32 = the leaf particle index selected at each step (updated =
  * ancestors != 0).  T >= 2, 2 <= N <= 1024.  Reduction orders and exp/log are fixed (csrc/pit.hip): bit-exact vs oracle/csmc_ref.c.
  * Covered: dx <= 4 (csrc/pit.hip) -- every transition and potential of the family, gradient NONE / REFERENCE / EXACT (in the tree both are the per-particle
- * correction), N <= 1024; 4 < dx <= 32 (csrc/pit_wide.hip) -- AUXSSM_TRANS_LINEAR, time-invariant or time-varying, the six built-in potentials, the same
+ * correction), N <= 1024; 4 < dx <= 32 (csrc/pit_wide.hip) -- AUXSSM_TRANS_LINEAR, time-invariant or time-varying, the seven built-in potentials, the same
  * gradient modes, 2 <= N <= 64, fp32 and fp64, both noise modes, several chains per launch.  AUXSSM_ERR_UNSUPPORTED, with the limit in the message: dx > 32;
  * at dx > 4, N > 64 and AUXSSM_TRANS_LORENZ63_EM; guided proposals (AUXSSM_PROP_AUX_GUIDED) at any dx.  User programs have no parallel-in-time entry point. */
 int auxssm_csmc_pit_sweep(auxssm_handle h, int dtype, const auxssm_fk_model* model, int32_t C, int32_t T, int32_t N,
