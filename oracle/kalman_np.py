@@ -121,7 +121,7 @@ def tril_log_det(chol):
 def mvn_logpdf(x, m, chol):
     # base.py:49-58 ; _INF = 1e500 is +inf so the final clip is the identity
     cd = np.diagonal(chol, axis1=-2, axis2=-1)
-    dim = np.sum(np.isfinite(cd), axis=-1)
+    dim = np.sum(np.isfinite(cd), axis=-1).astype(chol.dtype)  # (an integer count would promote an fp32 log-density to fp64)
     chol_clip = np.where(np.isfinite(chol), chol, np.inf)
     with np.errstate(all="ignore"):
         y = solve_lower(chol_clip, x - m)
