@@ -231,7 +231,8 @@ class PoissonPotential(UnivariatePotential, Potential):
     -- a NaN y_{t,k} drops component k of step t (per component, as SVPotential; not the whole-step rule of the coupled potentials).  Unnormalised: the
     constant -sum_k log y_{t,k}! is left out (it does not depend on x and cancels in every normalisation of the weights).  Non-integer values >= 0 are accepted,
     the formula is the same; a finite negative entry raises ValueError at construction.  An offset (a log-exposure o_{t,k}: y ~ Poisson(exp(o + x))) needs no
-    field: it is a shift of the state, z = x + o, through m0 and b.  As G0 give y = ys[0]; as Gt give params = ys[1:]."""
+    field: it is a shift of the state, z = x + o, through m0 and b.  As G0 give y = ys[0]; as Gt give params = ys[1:].
+    The auxiliary Kalman sampler's twin is kalman.PoissonModel: same density, same conventions (constant, missing counts, validation)."""
     y: Optional[Any] = None
     params: Optional[Any] = None
 

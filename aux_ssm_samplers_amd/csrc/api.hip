@@ -564,6 +564,7 @@ struct SweepCall {
     int32_t* accepted;
     void* logs;
     int order = 0;          // sweep_sv: 1 or 2
+    int kind = 0;           // sweep_sv: the pointwise potential (kalman_bodies.h::PwKind)
     void* x_alt = nullptr;  // sweep_lg_concat_fused: the second state buffer and the lazy state's selector
     int32_t* sel = nullptr;
     int cm() const { return layout == AUXSSM_LAYOUT_CHAIN_MINOR ? 1 : 0; }
@@ -1008,11 +1009,13 @@ template <typename R> static int sweep_lg_concat_fused(const SweepCall& c) {
 
 // ---- stochastic-volatility device factories (examples/stochastic_volatility/auxiliary_kalman.py:22-48, model.py:56-82) ----------
 // potential log g_t(x) = sum_k log N(y_k; 0, exp(x_k)); grad_k = (y_k^2 e^{-x_k} - 1) / 2, hess_kk = -y_k^2 e^{-x_k} / 2.
+// The same factories serve every pointwise potential with a diagonal Hessian: value, grad and lam = -hess come from kalman_bodies.h::Pointwise<R, KIND>, the kind
+// a template argument of k_sv_obs and k_sv_terms (PW_POISSON: log g = sum_k y_k x_k - e^{x_k}, AUXSSM_KMODEL_POISSON_FIRST / _SECOND).
 //   first order  (:28-35): ys = u + delta/2 grad(x_lin),                      H = I, R = delta/2 I,  c = 0
 //   second order (:37-46): Om = (-hess + 2/delta I)^-1 (diagonal), ys = Om (2u/delta + grad - hess x_lin), H = I, R = Om, c = 0
 template <typename R> AX_HD R sv_nan_to_num(R v) { return nan_to_num<R>(v); }
 // pass 1 (eps != null): u = x + sqrt(delta/2) eps and the observations linearised at x; pass 2: linearised at xlin, u given
-template <typename R>
+template <typename R, int KIND>
 __global__ void k_sv_obs(long long total, int C, int T, int D, int order, int cfast, const R* __restrict__ xlin, const R* __restrict__ eps, R shd,
                          R delta, const double* dptr, Arr yobs, R* __restrict__ u, R* __restrict__ ys, R* __restrict__ Rs) {
     if (dptr) delta = (R)dptr[0], shd = (R)dptr[1];
@@ -1041,12 +1044,13 @@ __global__ void k_sv_obs(long long total, int C, int T, int D, int order, int cf
         uu = u[g];
     }
     const R y = at<R>(yobs, 0, t, 0)[k];
-    const R w = y * y * exp_(-x);
-    const R grad = nan_to_num<R>((R)0.5 * (w - (R)1));
+    using Pw = Pointwise<R, KIND>;
+    const R w = Pw::core(y, x);
+    const R grad = Pw::grad(y, w);
     if (order == 1) {
         ys[g] = uu + (R)0.5 * delta * grad;
     } else {
-        const R hess = (R)-0.5 * w;
+        const R hess = -Pw::lam(y, w);
         const R om = (R)1 / (-hess + (R)2 / delta);
         ys[g] = om * ((R)2 * uu / delta + grad - hess * x);
         // row k of the diagonal D x D record of (c, t): dense [c][t][k][j], chain-minor [t][k][j][c]
@@ -1066,7 +1070,7 @@ template <typename R> __global__ void k_fill(long long n, R v, R* out) {
 }
 // per chain (one workgroup): pot(xp), pot(x), la1 = sum_t log N(ys1_t; xp_t, R1_t), la2 = sum_t log N(ys2_t; x_t, R2_t) (R diagonal;
 // a step whose term is NaN is dropped, as the reference's nansum over time steps does), corr (generic.py:103-105).  out [5][C].
-template <typename R>
+template <typename R, int KIND>
 __global__ void __launch_bounds__(256) k_sv_terms(int C, int T, int D, R delta, const double* dptr, const R* __restrict__ x, const R* __restrict__ xp, const R* __restrict__ u,
                                                   Arr yobs, const R* __restrict__ ys1, const R* __restrict__ ys2, const R* __restrict__ R1,
                                                   const R* __restrict__ R2, R* __restrict__ out) {
@@ -1080,8 +1084,8 @@ __global__ void __launch_bounds__(256) k_sv_terms(int C, int T, int D, R delta, 
             const long long g = ((long long)c * T + t) * D + k;
             const R y = at<R>(yobs, 0, t, 0)[k];
             const R a = xp[g], b = x[g], uu = u[g];
-            pp += nan_to_num<R>((R)(-0.5 * LOG_2PI) - (R)0.5 * a - (R)0.5 * y * y * exp_(-a));
-            px += nan_to_num<R>((R)(-0.5 * LOG_2PI) - (R)0.5 * b - (R)0.5 * y * y * exp_(-b));
+            pp += Pointwise<R, KIND>::value(y, a);
+            px += Pointwise<R, KIND>::value(y, b);
             const R r1 = R1 ? R1[g * D + k] : (R)0.5 * delta, r2 = R2 ? R2[g * D + k] : (R)0.5 * delta;
             const R s1 = sqrt_(r1), s2 = sqrt_(r2);
             const R z1 = (ys1[g] - a) / s1, z2 = (ys2[g] - b) / s2;
@@ -1142,6 +1146,7 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
     const auxssm_lgssm* model = c.model;
     const auxssm_arr* yobs = c.yobs;
     const int dtype = c.dtype, order = c.order, parallel = c.parallel, nan_policy = c.nan_policy;
+    const bool pois = c.kind == PW_POISSON;
     const double delta = c.delta;
     const double* dptr = c.dptr;
     void* x = c.x;
@@ -1258,6 +1263,7 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
         if (second) fa.Rs = Rs;
         if (fly) {
             fa.sv_order = order;
+            fa.sv_kind = c.kind;
             fa.sv_delta = delta;
             set_aux_fly(fa, c, 0, xlin, eps, uA);
         }
@@ -1265,11 +1271,17 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
         if (wide_ps_once && wide_gtab) fa.pc = wide_gtab;
     };
 
+    // the pseudo-observations (second order: and their covariances) linearised at xlin; eps: the noise that forms u, or none when u exists
+    auto launch_obs = [&](const R* xlin, const R* eps, R shd, R* ys, R* Rs) {
+        if (pois)
+            hipLaunchKernelGGL((k_sv_obs<R, PW_POISSON>), dim3(gb), dim3(256), 0, h->stream, tot, C, T, D, order, cm, xlin, eps, shd, (R)delta, dptr, cv(*yobs), u, ys, Rs);
+        else
+            hipLaunchKernelGGL((k_sv_obs<R, PW_SV>), dim3(gb), dim3(256), 0, h->stream, tot, C, T, D, order, cm, xlin, eps, shd, (R)delta, dptr, cv(*yobs), u, ys, Rs);
+    };
     // proposal: observations linearised at x, filter, pathwise sample (generic.py:80-86)
     if (!fly) {
         ProfScope ps(h, AUXSSM_K_FACTORY);
-        hipLaunchKernelGGL((k_sv_obs<R>), dim3(gb), dim3(256), 0, h->stream, tot, C, T, D, order, cm, (const R*)x, (const R*)c.eps_aux,
-                           (R)c.shd(), (R)delta, dptr, cv(*yobs), u, ys1, Rs1);
+        launch_obs((const R*)x, (const R*)c.eps_aux, (R)c.shd(), ys1, Rs1);
     }
     FilterArgs fa;
     filter_args(fa, g1, y1A, R1A, xA, view(c.eps_aux, D));
@@ -1285,8 +1297,7 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
     // reverse move: observations linearised at x_prop, filter for its marginal likelihood (generic.py:67)
     if (!fly) {
         ProfScope ps(h, AUXSSM_K_FACTORY);
-        hipLaunchKernelGGL((k_sv_obs<R>), dim3(gb), dim3(256), 0, h->stream, tot, C, T, D, order, cm, (const R*)xp, (const R*)nullptr, (R)0,
-                           (R)delta, dptr, cv(*yobs), u, ys2, Rs2);
+        launch_obs((const R*)xp, (const R*)nullptr, (R)0, ys2, Rs2);
     }
     FilterArgs fr;
     filter_args(fr, g2, y2A, R2A, xpA, Arr{nullptr, 0, 0, 0, 1});
@@ -1311,6 +1322,7 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
         la.delta = delta;
         la.dptr = dptr;
         la.fly_order = fly ? order : 0;
+        la.kind = c.kind;
         rc = se->sv_logpdf(h, la, sums);  // [5][C] = jp_prop, jp_rev, lt_prop, lt_rev, corr
         if (rc) return rc;
         h->ws_off = mark;
@@ -1345,8 +1357,12 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
             if (rc) return rc;
             h->ws_off = mark;
         }
-        hipLaunchKernelGGL((k_sv_terms<R>), dim3(C), dim3(256), 0, h->stream, C, T, D, (R)delta, dptr, (const R*)x, (const R*)xp, (const R*)u,
-                           cv(*yobs), (const R*)ys1, (const R*)ys2, (const R*)Rs1, (const R*)Rs2, terms);
+        if (pois)
+            hipLaunchKernelGGL((k_sv_terms<R, PW_POISSON>), dim3(C), dim3(256), 0, h->stream, C, T, D, (R)delta, dptr, (const R*)x, (const R*)xp, (const R*)u,
+                               cv(*yobs), (const R*)ys1, (const R*)ys2, (const R*)Rs1, (const R*)Rs2, terms);
+        else
+            hipLaunchKernelGGL((k_sv_terms<R, PW_SV>), dim3(C), dim3(256), 0, h->stream, C, T, D, (R)delta, dptr, (const R*)x, (const R*)xp, (const R*)u,
+                               cv(*yobs), (const R*)ys1, (const R*)ys2, (const R*)Rs1, (const R*)Rs2, terms);
         hipLaunchKernelGGL((k_sv_accept<R>), dim3((C + 127) / 128), dim3(128), 0, h->stream, C, (const R*)j1, (const R*)j2, (const R*)ell1,
                            (const R*)ell2, (const R*)terms, (const R*)c.u_acc, c.accepted, (R*)c.logs);
     }
@@ -1933,7 +1949,9 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
     AX_NEED_H(h);
     int rc;
     if ((rc = check_dtype(dtype)) || (rc = check_dims(dims, true))) return rc;
-    const bool sv = model_kind == AUXSSM_KMODEL_SV_FIRST || model_kind == AUXSSM_KMODEL_SV_SECOND;
+    // (the Poisson model is the SV sweep with another pointwise potential: same arrays, same checks, same layouts)
+    const bool pois = model_kind == AUXSSM_KMODEL_POISSON_FIRST || model_kind == AUXSSM_KMODEL_POISSON_SECOND;
+    const bool sv = pois || model_kind == AUXSSM_KMODEL_SV_FIRST || model_kind == AUXSSM_KMODEL_SV_SECOND;
     const bool lorenz = model_kind == AUXSSM_KMODEL_LORENZ63_EXT;
     const bool mvt = model_kind == AUXSSM_KMODEL_MVT_FIRST || model_kind == AUXSSM_KMODEL_MVT_SECOND;
     if (model_kind != AUXSSM_KMODEL_LG_CONCAT && !sv && !lorenz && !mvt) {
@@ -1996,7 +2014,8 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
                                           const_cast<void*>(u_acc));
             return AUXSSM_OK;
         });
-    if (sv) c.order = model_kind == AUXSSM_KMODEL_SV_FIRST ? 1 : 2;
+    if (sv) c.order = (model_kind == AUXSSM_KMODEL_SV_FIRST || model_kind == AUXSSM_KMODEL_POISSON_FIRST) ? 1 : 2;
+    if (pois) c.kind = PW_POISSON;
     if (mvt) c.order = model_kind == AUXSSM_KMODEL_MVT_FIRST ? 1 : 2;
     return by_dtype(dtype, [&](auto r) {
         using R = decltype(r);

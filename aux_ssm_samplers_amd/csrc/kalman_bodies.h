@@ -143,6 +143,7 @@ struct FilterArgs {
     // step in information form (FilterOpFlySV below).  sv_delta = the step size; no_moments: the pass is run for its log-likelihood only (the reverse filter
     // of a sweep): ms / Ps rows t >= 1 are not written.
     int sv_order = 0;
+    int sv_kind = 0;  // which pointwise potential the factories linearise (PW_SV / PW_POISSON below)
     double sv_delta = 0;
     int no_moments = 0;
     int dx = 0, dy = 0;  // runtime sizes, read by the wide-state path (wide.hip) only
@@ -522,6 +523,36 @@ template <typename R, int D, int P> AX_HD void body_obs_info_tab(const FilterArg
     stv<R, T::NPAD>((R*)a.obs_tab + (long long)i * T::NPAD, row);
 }
 
+// ---- the pointwise potentials of the SV sweep: log g_t(x) = sum_k f(y_k, x_k), diagonal Hessian ------------------------------------------------------
+// ONE definition per kind of what the sweep's five sites need (api.hip::k_sv_obs, k_sv_terms; sv_step_info, body_filter_t0_sv, sv_step_terms below), chosen at
+// COMPILE time.  core() is the one transcendental of a component; value / grad / lam (= -hess >= 0) are formed from it.
+//   PW_SV       y ~ N(0, e^x):      w = y^2 e^{-x}, f = -log(2 pi)/2 - x/2 - w/2 (NaN -> 0), grad = (w - 1)/2 (NaN -> 0), lam = w/2.  A NaN datum leaves lam NaN:
+//               the second-order pseudo-observation of that component is NaN = unobserved (kMissingNaN).
+//   PW_POISSON  y ~ Poisson(e^x):   e = e^x, f = y x - e, grad = y - e, lam = e, all three 0 for a missing (non-finite) y (csmc_sweep.h::pois_term's rule; the
+//               -log y! constant is left out).  Nothing is ever NaN: a missing count leaves the component observed through u with variance delta/2 in both
+//               orders, so the sites' "unobserved component" branches are dead for this kind and are dropped at compile time.  e^x is not guarded against overflow.
+enum PwKind : int { PW_SV = 0, PW_POISSON = 1 };
+template <typename R, int KIND> struct Pointwise;
+template <typename R> struct Pointwise<R, PW_SV> {
+    static constexpr bool kMissingNaN = true;
+    static AX_HD R core(R y, R x) { return y * y * exp_(-x); }
+    static AX_HD R value(R, R x, R w) { return nan_to_num<R>((R)(-0.5 * LOG_2PI) - (R)0.5 * x - (R)0.5 * w); }
+    // (k_sv_terms' one-expression form: contraction places its multiply-add inside the product, so it is kept as a statement of its own)
+    static AX_HD R value(R y, R x) { return nan_to_num<R>((R)(-0.5 * LOG_2PI) - (R)0.5 * x - (R)0.5 * y * y * exp_(-x)); }
+    static AX_HD R grad(R, R w) { return nan_to_num<R>((R)0.5 * (w - (R)1)); }
+    static AX_HD R lam(R, R w) { return (R)0.5 * w; }
+    static AX_HD bool missing(R w) { return !finite_(w); }  // (k_sv_obs: ys = om (...) is NaN exactly when w is NaN or infinite)
+};
+template <typename R> struct Pointwise<R, PW_POISSON> {
+    static constexpr bool kMissingNaN = false;
+    static AX_HD R core(R, R x) { return exp_(x); }
+    static AX_HD R value(R y, R x, R e) { return finite_(y) ? y * x - e : (R)0; }
+    static AX_HD R value(R y, R x) { return value(y, x, core(y, x)); }
+    static AX_HD R grad(R y, R e) { return finite_(y) ? y - e : (R)0; }
+    static AX_HD R lam(R y, R e) { return finite_(y) ? e : (R)0; }
+    static AX_HD bool missing(R) { return false; }
+};
+
 // ---- the SV factories without observation arrays (FilterArgs::sv_order) -----------------------------------------------------------------
 // Per component k (the factories are diagonal: H = I, c = 0, R = diag): w = y^2 e^{-x}, grad = nan_to_num((w - 1) / 2), hess = -w / 2, a = 2 / delta.
 //   first order  (auxiliary_kalman.py:28-35): ys = u + (delta / 2) grad, R = delta / 2          -> precision a,        information a ys
@@ -530,18 +561,23 @@ template <typename R, int D, int P> AX_HD void body_obs_info_tab(const FilterArg
 // origin: first order u' = ys, Lam = 0; second order u' = u, Lam = diag(-hess), g0 = grad - hess x, q0 = ys^2 / Om - a u^2 in a form without the |u|^2 a
 // cancellation, ldR = -log(-hess + a) / 2.  A NaN datum (second order) makes that component's ys NaN = unobserved (k_sv_obs + the element path do the same
 // component by component): the step then takes the folded form with that component's precision and information zero.
-template <typename R, int D> AX_HD void sv_step_info(const FilterArgs& a, const R* x, const R* u, const R* y, StepInfo<R, D>& si) {
+// Other kinds (Pointwise above) go through the same split with their own grad / lam; a kind whose pseudo-observations are never NaN (!kMissingNaN) has
+// miss[] = false at compile time and the folded branch below is not compiled for it: every step has dim = D.
+template <typename R, int D, int KIND = PW_SV> AX_HD void sv_step_info(const FilterArgs& a, const R* x, const R* u, const R* y, StepInfo<R, D>& si) {
+    using Pw = Pointwise<R, KIND>;
     const R delta = (R)a.sv_delta, av = (R)2 / delta;
     const bool second = a.sv_order != 1;
     R lam[D], g[D], grad[D];
     bool miss[D], any = false;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
-        const R w = y[k] * y[k] * exp_(-x[k]);
-        grad[k] = nan_to_num<R>((R)0.5 * (w - (R)1));
-        lam[k] = second ? (R)0.5 * w : (R)0;
+        // (lam is taken outside the conditional: inside it the SV scan passes at D = 3, 4 allocate one register more, which at fp32 D = 3 costs a wave per SIMD)
+        const R yk = y[k], w = Pw::core(yk, x[k]), lw = Pw::lam(yk, w);
+        grad[k] = Pw::grad(yk, w);
+        lam[k] = second ? lw : (R)0;
         g[k] = second ? grad[k] + lam[k] * x[k] : (R)0;
-        miss[k] = second && !finite_(w);   // (k_sv_obs: ys = om (...) is NaN exactly when w is NaN or infinite)
+        if constexpr (Pw::kMissingNaN) miss[k] = second && Pw::missing(w);
+        else miss[k] = false;
         any = any || miss[k];
     }
     // (every field is assigned exactly once, outside the branches: written per branch, the struct went through scratch memory)
@@ -555,7 +591,7 @@ template <typename R, int D> AX_HD void sv_step_info(const FilterArgs& a, const 
             Ld[k] = 0, G0[k] = 0;
             U[k] = u[k] + (R)0.5 * delta * grad[k];
             dim += 1;
-        } else if (!any) {
+        } else if (!Pw::kMissingNaN || !any) {
             const R e = u[k] - x[k];
             Ld[k] = lam[k], G0[k] = g[k], U[k] = u[k];
             // (a u + g)^2 / (lam + a) - a u^2 = [2 a u grad + a lam (x^2 - (u - x)^2) + g^2] / (lam + a)
@@ -576,7 +612,7 @@ template <typename R, int D> AX_HD void sv_step_info(const FilterArgs& a, const 
     for (int k = 0; k < symsize(D); ++k) si.Lam[k] = 0;
 #pragma unroll
     for (int k = 0; k < D; ++k) si.Lam[sidx_u(D, k, k)] = Ld[k], si.g0[k] = G0[k], si.u[k] = U[k];
-    si.inv_hd = (second && any) ? (R)0 : av;
+    si.inv_hd = (Pw::kMissingNaN && second && any) ? (R)0 : av;
     si.q0 = q0;
     si.ldR = second ? (R)0 : (R)D * log_(sqrt_((R)0.5 * delta));
     si.rdet = rd;
@@ -584,7 +620,8 @@ template <typename R, int D> AX_HD void sv_step_info(const FilterArgs& a, const 
     si.ok = true;
 }
 // the t = 0 update of the same model: the pseudo-observation of (x_0, u_0) as k_sv_obs forms it, then the plain update (filtering.py:52)
-template <typename R, int D> AX_HD void body_filter_t0_sv(const FilterArgs& a, int s) {
+template <typename R, int D, int KIND = PW_SV> AX_HD void body_filter_t0_sv(const FilterArgs& a, int s) {
+    using Pw = Pointwise<R, KIND>;
     const int c = s / a.d.B, b = s % a.d.B;
     R m[D], Pd[D * D], H[D * D], cv[D], ys[D], Rm[D * D], x[D], u[D], y[D];
     rd<R, D>(a.m0, c, 0, b, m);
@@ -605,14 +642,14 @@ template <typename R, int D> AX_HD void body_filter_t0_sv(const FilterArgs& a, i
     for (int k = 0; k < D * D; ++k) H[k] = (k / D == k % D) ? (R)1 : (R)0, Rm[k] = 0;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
-        const R w = y[k] * y[k] * exp_(-x[k]);
-        const R grad = nan_to_num<R>((R)0.5 * (w - (R)1));
+        const R w = Pw::core(y[k], x[k]);
+        const R grad = Pw::grad(y[k], w);
         cv[k] = 0;
         if (a.sv_order == 1) {
             ys[k] = u[k] + (R)0.5 * delta * grad;
             Rm[k * D + k] = (R)0.5 * delta;
         } else {
-            const R hess = (R)-0.5 * w;
+            const R hess = -Pw::lam(y[k], w);
             const R om = (R)1 / (-hess + (R)2 / delta);
             ys[k] = om * ((R)2 * u[k] / delta + grad - hess * x[k]);
             Rm[k * D + k] = om;
@@ -624,7 +661,7 @@ template <typename R, int D> AX_HD void body_filter_t0_sv(const FilterArgs& a, i
     ((R*)a.ell0)[s] = ell;
 }
 // The folding operator: FilterOpFly's passes (init_acc / init_pre / write_zpart are its own) with the step's information built by sv_step_info.
-template <typename R_, int D, bool WRITE_U> struct FilterOpFlySV : FilterOpFly<R_, D, D + 1, false> {
+template <typename R_, int D, bool WRITE_U, int KIND = PW_SV> struct FilterOpFlySV : FilterOpFly<R_, D, D + 1, false> {
     using R = R_;
     using Base = FilterOpFly<R_, D, D + 1, false>;
     using Full = typename Base::Full;
@@ -651,7 +688,7 @@ template <typename R_, int D, bool WRITE_U> struct FilterOpFlySV : FilterOpFly<R
         if constexpr (WRITE_U) {
             if (a.aux_eps.ptr) wr<R, D>(a.aux_u, s / a.d.B, (long long)i + 1, s % a.d.B, u);
         }
-        sv_step_info<R, D>(a, r.x, u, r.y, si);
+        sv_step_info<R, D, KIND>(a, r.x, u, r.y, si);
     }
     static AX_HD void write_out(const Args& a, int s, int i, const Pre& p) {
         if (!a.no_moments) Base::write_out(a, s, i, p);
@@ -1481,6 +1518,7 @@ struct SvLogpdfArgs {
     double delta;
     const double* dptr = nullptr;  // device-resident {delta, sqrt(delta / 2)}; null: the host value
     int fly_order = 0;             // 1 / 2: ys1, ys2, R1, R2 do not exist (FilterArgs::sv_order): the pseudo-observations are re-formed from (x, xp, u, yobs)
+    int kind = 0;                  // the pointwise potential g (PwKind; FilterArgs::sv_kind)
 };
 // Kernels call resolve_step(a) on their by-value argument struct first: a device-resident step size (dptr) is read ONCE, into the host fields, and the
 // pointer cleared, so that arg_delta / arg_shd / arg_aux_shd are loop-invariant scalars in every per-step body.  (Left to the bodies, the conditional
@@ -1504,8 +1542,9 @@ AX_HD void resolve_step(SvLogpdfArgs& a) {
 // The logarithms of the step (the two auxiliary variances, the transition's determinant) are NOT taken here: fac[k] > 0 is the factor whose log / 2 ADDS to
 // o5[k] (k < 4; 1 where the term was dropped by the nansum rule) -- the chain-minor kernel multiplies them up over its time tile (kalman_math.h::LogProd), the
 // one-step-per-lane kernel takes the logarithm at once.
-template <typename R, int D>
+template <typename R, int D, int KIND = PW_SV>
 AX_HD void sv_step_terms(const SvLogpdfArgs& a, int c, long long t, const R* x, const R* xp, R* o5, R* fac) {
+    using Pw = Pointwise<R, KIND>;
     R u[D], y[D], y1[D], y2[D];
     rd<R, D>(a.u, c, t, 0, u);
     rd<R, D>(a.yobs, 0, t, 0, y);
@@ -1519,19 +1558,19 @@ AX_HD void sv_step_terms(const SvLogpdfArgs& a, int c, long long t, const R* x, 
     for (int k = 0; k < D; ++k) {
         const R av = xp[k], bv = x[k];
         // the two exponentials serve the potentials and (fly) the pseudo-observations: 0.5 * (y y e) is (0.5 y) y e bit for bit (scaling by a power of two)
-        const R wb = y[k] * y[k] * exp_(-bv), wa = y[k] * y[k] * exp_(-av);
-        pp += nan_to_num<R>((R)(-0.5 * LOG_2PI) - (R)0.5 * av - (R)0.5 * wa);
-        px += nan_to_num<R>((R)(-0.5 * LOG_2PI) - (R)0.5 * bv - (R)0.5 * wb);
+        const R wb = Pw::core(y[k], bv), wa = Pw::core(y[k], av);
+        pp += Pw::value(y[k], av, wa);
+        px += Pw::value(y[k], bv, wb);
         R t1, t2;   // the auxiliary precisions 1 / R1_kk, 1 / R2_kk
         if (a.fly_order) {
             // k_sv_obs's pseudo-observations, re-formed: the proposal's are linearised at x (and scored at xp), the reverse move's at xp
-            const R gb = nan_to_num<R>((R)0.5 * (wb - (R)1)), ga = nan_to_num<R>((R)0.5 * (wa - (R)1));
+            const R gb = Pw::grad(y[k], wb), ga = Pw::grad(y[k], wa);
             if (a.fly_order == 1) {
                 y1[k] = u[k] + (R)0.5 * delta * gb;
                 y2[k] = u[k] + (R)0.5 * delta * ga;
                 t1 = t2 = a2;
             } else {
-                const R hb = (R)-0.5 * wb, ha = (R)-0.5 * wa;
+                const R hb = -Pw::lam(y[k], wb), ha = -Pw::lam(y[k], wa);
                 t1 = -hb + a2;
                 t2 = -ha + a2;
                 const R iv = (R)1 / (t1 * t2);   // one division for the two variances Om = 1 / t
@@ -1573,7 +1612,7 @@ template <typename R> AX_HD void sv_add_prior(R pr_p, R pr_x, R fq, bool kp, boo
     fac[3] *= kx ? fq : (R)1;
 }
 // lanes indexed by i = t - 1 (t >= 1)
-template <typename R, int D> AX_HD void body_sv_logpdf(const SvLogpdfArgs& a, int c, int i, bool valid, R* out5, R* fac) {
+template <typename R, int D, int KIND = PW_SV> AX_HD void body_sv_logpdf(const SvLogpdfArgs& a, int c, int i, bool valid, R* out5, R* fac) {
 #pragma unroll
     for (int k = 0; k < 5; ++k) out5[k] = 0;
 #pragma unroll
@@ -1588,7 +1627,7 @@ template <typename R, int D> AX_HD void body_sv_logpdf(const SvLogpdfArgs& a, in
     rd<R, D * D>(a.Fs, c, i, 0, F);
     rd<R, D>(a.bs, c, i, 0, bd);
     rd<R, D * D>(a.Qs, c, i, 0, Q);
-    sv_step_terms<R, D>(a, c, t, x, xp, out5, fac);
+    sv_step_terms<R, D, KIND>(a, c, t, x, xp, out5, fac);
     R r1[D], r2[D], m1[D], m2[D], pr_p, pr_x, fq;
     bool kp, kx;
     mv<R, D, D>(F, xpq, m1);
@@ -1598,13 +1637,13 @@ template <typename R, int D> AX_HD void body_sv_logpdf(const SvLogpdfArgs& a, in
     gauss_logpdf2_lp<R, D>(r1, r2, Q, pr_p, pr_x, fq, kp, kx);
     sv_add_prior<R>(pr_p, pr_x, fq, kp, kx, out5, fac);
 }
-template <typename R, int D> AX_HD void body_sv_logpdf_head(const SvLogpdfArgs& a, int c, R* out5, R* fac) {
+template <typename R, int D, int KIND = PW_SV> AX_HD void body_sv_logpdf_head(const SvLogpdfArgs& a, int c, R* out5, R* fac) {
     R x[D], xp[D], m0[D], P0m[D * D];
     rd<R, D>(a.x, c, 0, 0, x);
     rd<R, D>(a.xp, c, 0, 0, xp);
     rd<R, D>(a.m0, c, 0, 0, m0);
     rd<R, D * D>(a.P0, c, 0, 0, P0m);
-    sv_step_terms<R, D>(a, c, 0, x, xp, out5, fac);
+    sv_step_terms<R, D, KIND>(a, c, 0, x, xp, out5, fac);
     R r1[D], r2[D], pr_p, pr_x, fq;
     bool kp, kx;
 #pragma unroll

@@ -114,10 +114,10 @@ template <typename R, int D, int P> __global__ void __launch_bounds__(TB_ELEM) k
     if (s < a.d.S()) body_filter_t0<R, D, P>(a, s);
 }
 
-template <typename R, int D> __global__ void __launch_bounds__(TB_ELEM) k_filter_t0_sv(FilterArgs a) {
+template <typename R, int D, int KIND> __global__ void __launch_bounds__(TB_ELEM) k_filter_t0_sv(FilterArgs a) {
     resolve_step(a);
     const int s = blockIdx.x * TB_ELEM + threadIdx.x;
-    if (s < a.d.S()) body_filter_t0_sv<R, D>(a, s);
+    if (s < a.d.S()) body_filter_t0_sv<R, D, KIND>(a, s);
 }
 
 // grid = ntile * S, sequence index fastest so that workgroups of different chains touching the same time
@@ -496,7 +496,7 @@ template <typename R, int PO> __global__ void __launch_bounds__(TB_CM) k_lorenz_
 }
 
 // the SV sweep's five per-chain sums (kalman_bodies.h::SvLogpdfArgs); part layout [5][C][ntile]
-template <typename R, int D> __global__ void __launch_bounds__(TB_ELEM) k_sv_logpdf(SvLogpdfArgs a, Acc* __restrict__ part, int ntile) {
+template <typename R, int D, int KIND> __global__ void __launch_bounds__(TB_ELEM) k_sv_logpdf(SvLogpdfArgs a, Acc* __restrict__ part, int ntile) {
     resolve_step(a);
     __shared__ Acc sh[TB_ELEM];
     const int C = a.d.C;
@@ -506,10 +506,10 @@ template <typename R, int D> __global__ void __launch_bounds__(TB_ELEM) k_sv_log
     const int n = a.d.T - 1;
     const int i = tile * TB_ELEM + threadIdx.x;
     R v[5], f[4];
-    body_sv_logpdf<R, D>(a, c, i, i < n, v, f);
+    body_sv_logpdf<R, D, KIND>(a, c, i, i < n, v, f);
     if (tile == 0 && threadIdx.x == 0) {
         R h[5], fh[4];
-        body_sv_logpdf_head<R, D>(a, c, h, fh);
+        body_sv_logpdf_head<R, D, KIND>(a, c, h, fh);
 #pragma unroll
         for (int k = 0; k < 5; ++k) v[k] += h[k];
 #pragma unroll
@@ -525,7 +525,7 @@ template <typename R, int D> __global__ void __launch_bounds__(TB_ELEM) k_sv_log
         if (threadIdx.x == 0) part[((long long)k * C + c) * ntile + tile] = tot;
     }
 }
-template <typename R, int D> __global__ void __launch_bounds__(TB_CM) k_sv_logpdf_cm(SvLogpdfArgs a, Acc* __restrict__ part, int ntile, int TI) {
+template <typename R, int D, int KIND> __global__ void __launch_bounds__(TB_CM) k_sv_logpdf_cm(SvLogpdfArgs a, Acc* __restrict__ part, int ntile, int TI) {
     resolve_step(a);
     const CmTile c = decode_cm(a.d.C, a.d.T - 1, TI);
     if (!c.live) return;
@@ -533,7 +533,7 @@ template <typename R, int D> __global__ void __launch_bounds__(TB_CM) k_sv_logpd
     LogProd<R> lp[4];   // the tile's determinants: one logarithm per sum and tile instead of three per step
     if (c.tt == 0) {
         R h[5], fh[4];
-        body_sv_logpdf_head<R, D>(a, c.s, h, fh);
+        body_sv_logpdf_head<R, D, KIND>(a, c.s, h, fh);
 #pragma unroll
         for (int k = 0; k < 5; ++k) v[k] = (Acc)h[k];
 #pragma unroll
@@ -542,7 +542,7 @@ template <typename R, int D> __global__ void __launch_bounds__(TB_CM) k_sv_logpd
 #pragma unroll 1
     for (int i = c.i0; i < c.i1; ++i) {
         R w[5], f[4];
-        body_sv_logpdf<R, D>(a, c.s, opaque_uniform(i), true, w, f);
+        body_sv_logpdf<R, D, KIND>(a, c.s, opaque_uniform(i), true, w, f);
 #pragma unroll
         for (int k = 0; k < 5; ++k) v[k] += (Acc)w[k];
 #pragma unroll
@@ -1236,6 +1236,12 @@ template <typename R, int D, int P> int run_filter_shared(auxssm_ctx* h, FilterA
     return AUXSSM_OK;
 }
 
+// the array-free scan passes of the SV sweep for one pointwise potential: the down pass writes u when the pass forms it from the noise
+template <typename R, int D, int KIND> int sv_scan_kind(auxssm_ctx* h, const FilterArgs& a, int S, int n) {
+    return a.aux_eps.ptr ? run_scan<FilterOp<R, D>, FilterOpFlySV<R, D, true, KIND>, FilterOpFlySV<R, D, false, KIND>>(h, a, S, n)
+                         : run_scan<FilterOp<R, D>, FilterOpFlySV<R, D, false, KIND>, FilterOpFlySV<R, D, false, KIND>>(h, a, S, n);
+}
+
 template <typename R, int D, int P> int run_filter(auxssm_ctx* h, const FilterArgs& a_in, int parallel, void* ell_out) {
     FilterArgs a = a_in;
     const int S = a.d.S(), n = a.d.n();
@@ -1258,14 +1264,16 @@ template <typename R, int D, int P> int run_filter(auxssm_ctx* h, const FilterAr
                 set_error("internal: the array-free SV filter needs the chain-minor layout");
                 return AUXSSM_ERR_ARG;
             }
-            hipLaunchKernelGGL((k_filter_t0_sv<R, D>), dim3((S + TB_ELEM - 1) / TB_ELEM), dim3(TB_ELEM), 0, h->stream, a);
+            // (the potential's kind is a template argument of the three kernels: sv_scan_kind)
+            const bool pois = a_in.sv_kind == PW_POISSON;
+            if (pois) hipLaunchKernelGGL((k_filter_t0_sv<R, D, PW_POISSON>), dim3((S + TB_ELEM - 1) / TB_ELEM), dim3(TB_ELEM), 0, h->stream, a);
+            else hipLaunchKernelGGL((k_filter_t0_sv<R, D, PW_SV>), dim3((S + TB_ELEM - 1) / TB_ELEM), dim3(TB_ELEM), 0, h->stream, a);
             if (n > 0) {
                 a.elem = nullptr;
                 a.ellz = ws_take(h, (size_t)S * a.lay.nchunk * sizeof(R));
                 if (!a.ellz) return AUXSSM_ERR_NOMEM;
                 ProfScope ps(h, AUXSSM_K_FILTER_SCAN);
-                const int rc = a.aux_eps.ptr ? run_scan<FilterOp<R, D>, FilterOpFlySV<R, D, true>, FilterOpFlySV<R, D, false>>(h, a, S, n)
-                                             : run_scan<FilterOp<R, D>, FilterOpFlySV<R, D, false>, FilterOpFlySV<R, D, false>>(h, a, S, n);
+                const int rc = pois ? sv_scan_kind<R, D, PW_POISSON>(h, a, S, n) : sv_scan_kind<R, D, PW_SV>(h, a, S, n);
                 if (rc) return rc;
             }
             hipLaunchKernelGGL((k_reduce_rows<R>), dim3(a.d.C), dim3(TB_ELEM), 0, h->stream, (const R*)a.ellz, (const R*)a.ell0, a.d.B, n > 0 ? a.lay.nchunk : 0, (R*)ell_out);
@@ -1532,8 +1540,11 @@ template <typename R, int D> int run_sv_logpdf(auxssm_ctx* h, const SvLogpdfArgs
     const int nt = cm ? ((n + TI - 1) / TI > 0 ? (n + TI - 1) / TI : 1) : (ntiles(n) > 0 ? ntiles(n) : 1);
     Acc* part = (Acc*)ws_take(h, (size_t)5 * C * nt * sizeof(Acc));
     ProfScope ps(h, AUXSSM_K_LOGPDF);
-    if (cm) hipLaunchKernelGGL((k_sv_logpdf_cm<R, D>), dim3(grid_cm(C, n, TI)), dim3(TB_CM), 0, h->stream, a, part, nt, TI);
-    else hipLaunchKernelGGL((k_sv_logpdf<R, D>), dim3(grid_tile_seq(nt, C)), dim3(TB_ELEM), 0, h->stream, a, part, nt);
+    const bool pois = a.kind == PW_POISSON;
+    if (cm && pois) hipLaunchKernelGGL((k_sv_logpdf_cm<R, D, PW_POISSON>), dim3(grid_cm(C, n, TI)), dim3(TB_CM), 0, h->stream, a, part, nt, TI);
+    else if (cm) hipLaunchKernelGGL((k_sv_logpdf_cm<R, D, PW_SV>), dim3(grid_cm(C, n, TI)), dim3(TB_CM), 0, h->stream, a, part, nt, TI);
+    else if (pois) hipLaunchKernelGGL((k_sv_logpdf<R, D, PW_POISSON>), dim3(grid_tile_seq(nt, C)), dim3(TB_ELEM), 0, h->stream, a, part, nt);
+    else hipLaunchKernelGGL((k_sv_logpdf<R, D, PW_SV>), dim3(grid_tile_seq(nt, C)), dim3(TB_ELEM), 0, h->stream, a, part, nt);
     hipLaunchKernelGGL((k_reduce_rows<Acc>), dim3(5 * C), dim3(TB_ELEM), 0, h->stream, (const Acc*)part, (const Acc*)nullptr, 1, nt, (Acc*)out);
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;

@@ -66,7 +66,51 @@ class LGConcatModel:
         return dev
 
 
-class SVModel:
+class _PointwiseModel:
+    """What SVModel and PoissonModel share: data ys (T, dx), time-invariant linear-Gaussian dynamics (m0, P0, F, Q, b) and a potential that is a sum over
+    the components, log g_t(x) = sum_k f(y_{t,k}, x_{t,k}), whose first- or second-order auxiliary observation set is therefore diagonal.  A subclass sets
+    KMODELS = (first-order kind, second-order kind) and gives log_potential and observations_factory."""
+    dense_only = False  # >= 32 chains run chain-minor (lanes over chains), as the LG_CONCAT sweep does
+    KMODELS = None
+
+    def __init__(self, ys, m0, P0, F, Q, b, order=1):
+        if order not in (1, 2):
+            raise ValueError("order must be 1 or 2")
+        self.yobs = np.asarray(ys)
+        self.T, self.dx = self.yobs.shape
+        self.p_obs = self.dx
+        self.m0, self.P0 = np.asarray(m0), np.asarray(P0)
+        self.F, self.Q, self.b = np.asarray(F), np.asarray(Q), np.asarray(b)
+        self.order = order
+        self.kmodel = self.KMODELS[order - 1]
+        n = self.T - 1
+        self.Fs = np.broadcast_to(self.F, (n,) + self.F.shape)
+        self.Qs = np.broadcast_to(self.Q, (n,) + self.Q.shape)
+        self.bs = np.broadcast_to(self.b, (n,) + self.b.shape)
+        self._dev = {}
+
+    def dynamics_factory(self, x):
+        return self.m0, self.P0, self.Fs, self.Qs, self.bs
+
+    def log_likelihood_fn(self, x):
+        from .._primitives.kalman.base import prior_logpdf, LGSSM
+        x = np.asarray(x)
+        prior = prior_logpdf(x, LGSSM(self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None))
+        return prior + self.log_potential(x)
+
+    def device(self, handle, dtype):
+        key = (id(handle), np.dtype(dtype).str)
+        dev = self._dev.get(key)
+        if dev is None:
+            T, d = self.T, self.dx
+            lg = (self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None)
+            dl = DeviceLGSSM(handle, lg, 1, T, 1, d, d, False, dtype)
+            ybuf, yarr = _upload_arr(handle, self.yobs, (d,), 1, T, 1, False, False, np.dtype(dtype), "ys")
+            dev = self._dev[key] = (dl, ybuf, yarr)
+        return dev
+
+
+class SVModel(_PointwiseModel):
     """Multivariate stochastic volatility  y_{t,k} ~ N(0, exp(x_{t,k}))  on linear-Gaussian dynamics
     x_{t+1} = F x_t + b + N(0, Q), with the first- or second-order auxiliary observation factories of
     examples/stochastic_volatility/auxiliary_kalman.py:22-48 (closed-form gradient / Hessian of the potential,
@@ -79,23 +123,7 @@ class SVModel:
 
     Pass the three bound methods to kalman.get_kernel: it runs the device sweep (auxssm_kalman_sweep, model kind SV_FIRST /
     SV_SECOND).  The same methods are NumPy factories for the host path and the oracle."""
-    dense_only = False  # >= 32 chains run chain-minor (lanes over chains), as the LG_CONCAT sweep does
-
-    def __init__(self, ys, m0, P0, F, Q, b, order=1):
-        if order not in (1, 2):
-            raise ValueError("order must be 1 or 2")
-        self.yobs = np.asarray(ys)
-        self.T, self.dx = self.yobs.shape
-        self.p_obs = self.dx
-        self.m0, self.P0 = np.asarray(m0), np.asarray(P0)
-        self.F, self.Q, self.b = np.asarray(F), np.asarray(Q), np.asarray(b)
-        self.order = order
-        self.kmodel = _lib.KMODEL_SV_FIRST if order == 1 else _lib.KMODEL_SV_SECOND
-        n = self.T - 1
-        self.Fs = np.broadcast_to(self.F, (n,) + self.F.shape)
-        self.Qs = np.broadcast_to(self.Q, (n,) + self.Q.shape)
-        self.bs = np.broadcast_to(self.b, (n,) + self.b.shape)
-        self._dev = {}
+    KMODELS = (_lib.KMODEL_SV_FIRST, _lib.KMODEL_SV_SECOND)
 
     # potential and its derivatives (model.py:56-82), NaN -> 0 as jnp.nan_to_num
     def _w(self, x):
@@ -106,9 +134,6 @@ class SVModel:
         with np.errstate(all="ignore"):
             val = -0.5 * np.log(2 * np.pi) - 0.5 * x - 0.5 * self._w(x)
         return float(np.sum(np.nan_to_num(val)))
-
-    def dynamics_factory(self, x):
-        return self.m0, self.P0, self.Fs, self.Qs, self.bs
 
     def observations_factory(self, x, u, delta):
         x, u = np.asarray(x), np.asarray(u)
@@ -128,22 +153,69 @@ class SVModel:
         Rs[:, np.arange(d), np.arange(d)] = om
         return ys.astype(dt), eyes, Rs, zeros
 
-    def log_likelihood_fn(self, x):
-        from .._primitives.kalman.base import prior_logpdf, LGSSM
-        x = np.asarray(x)
-        prior = prior_logpdf(x, LGSSM(self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None))
-        return prior + self.log_potential(x)
 
-    def device(self, handle, dtype):
-        key = (id(handle), np.dtype(dtype).str)
-        dev = self._dev.get(key)
-        if dev is None:
-            T, d = self.T, self.dx
-            lg = (self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None)
-            dl = DeviceLGSSM(handle, lg, 1, T, 1, d, d, False, dtype)
-            ybuf, yarr = _upload_arr(handle, self.yobs, (d,), 1, T, 1, False, False, np.dtype(dtype), "ys")
-            dev = self._dev[key] = (dl, ybuf, yarr)
-        return dev
+class PoissonModel(_PointwiseModel):
+    """Multivariate counts with a log link  y_{t,k} ~ Poisson(exp(x_{t,k}))  on linear-Gaussian dynamics x_{t+1} = F x_t + b + N(0, Q), x_0 ~ N(m0, P0),
+    under the first- or second-order auxiliary observation factories of examples/stochastic_volatility/auxiliary_kalman.py:22-48.  Arguments and shapes
+    are SVModel's: ys (T, dx), F and Q dense (dx, dx), order 1 or 2.  With mask = isfinite(y), per component
+
+        log g = where(mask, y x - e^x, 0)      grad = where(mask, y - e^x, 0)      lam = -hess = where(mask, e^x, 0)
+
+        dynamics_factory(x)           -> m0, P0, tile(F), tile(Q), tile(b)
+        observations_factory(x, u, d) -> order 1: ys = u + d/2 grad, H = I, R = d/2 I, c = 0
+                                         order 2: Om = 1 / (lam + 2/d) (diagonal), ys = Om (2u/d + grad + lam x), H = I, R = diag(Om), c = 0
+        log_likelihood_fn(x)          -> prior_logpdf(x) + sum log g
+
+    The conventions are csmc.PoissonPotential's, so both samplers target one density: the constant -log y! is left out, non-integer y >= 0 is accepted, a
+    finite negative entry raises ValueError, a NaN y_{t,k} drops that component's term alone, and a log-exposure is a shift of the state through m0 and b (no
+    field).  The potential is concave and -hess = e^x > 0, so the second-order factory is always well defined.  Unlike SVModel's, no pseudo-observation is
+    ever NaN: a missing count leaves its component observed through u with variance d/2, in both orders.  exp overflow (|x| beyond ~88 in float32, ~709 in
+    float64) is not guarded.
+
+    Pass the three bound methods to kalman.get_kernel: it runs the device sweep (model kind POISSON_FIRST / POISSON_SECOND: the SV sweep's kernels
+    instantiated for this potential, every layout and width SVModel has).  The same methods are NumPy factories for the host path and the oracle."""
+    KMODELS = (_lib.KMODEL_POISSON_FIRST, _lib.KMODEL_POISSON_SECOND)
+
+    def __init__(self, ys, m0, P0, F, Q, b, order=1):
+        ys = np.asarray(ys)
+        if ys.ndim != 2:
+            raise ValueError(f"PoissonModel: ys must be (T, dx), got shape {ys.shape}")
+        from ..csmc.models import PoissonPotential
+        PoissonPotential.check_counts(ys)
+        super().__init__(ys, m0, P0, F, Q, b, order)
+
+    def _terms(self, x):
+        """(mask, e^x) at x (T, dx)"""
+        with np.errstate(over="ignore"):
+            return np.isfinite(self.yobs), np.exp(x)
+
+    def log_potential(self, x):
+        x = np.asarray(x)
+        mask, e = self._terms(x)
+        with np.errstate(invalid="ignore"):
+            return float(np.sum(np.where(mask, self.yobs.astype(x.dtype) * x - e, 0.0)))
+
+    def grad_lam(self, x):
+        """(grad, lam) of log g, both (T, dx) and 0 where the count is missing"""
+        x = np.asarray(x)
+        mask, e = self._terms(x)
+        with np.errstate(invalid="ignore"):
+            return np.where(mask, self.yobs.astype(x.dtype) - e, 0.0), np.where(mask, e, 0.0)
+
+    def observations_factory(self, x, u, delta):
+        x, u = np.asarray(x), np.asarray(u)
+        T, d = self.T, self.dx
+        dt = u.dtype
+        eyes = np.broadcast_to(np.eye(d, dtype=dt), (T, d, d))
+        zeros = np.zeros((T, d), dt)
+        grad, lam = self.grad_lam(x)
+        if self.order == 1:
+            return (u + 0.5 * delta * grad).astype(dt), eyes, (0.5 * delta * eyes).astype(dt), zeros
+        om = 1.0 / (lam + 2.0 / delta)
+        ys = om * (2.0 * u / delta + grad + lam * x)
+        Rs = np.zeros((T, d, d), dt)
+        Rs[:, np.arange(d), np.arange(d)] = om
+        return ys.astype(dt), eyes, Rs, zeros
 
 
 class LorenzModel:

@@ -132,6 +132,14 @@ def poisson_setup(T, dx, seed=0):
     return M0, Mt, PoissonPotential(y=y[0]), PoissonPotential(params=y[1:]), x, y
 
 
+def poisson_kalman_setup(T, dx, seed=0, order=1):
+    """The model of poisson_setup for the auxiliary Kalman sampler (same recipe, same seed -> same x and y).
+    Returns (model, x0): a kalman.PoissonModel and a start state (T, dx) -- the simulated log-intensities."""
+    from aux_ssm_samplers_amd.kalman import PoissonModel
+    M0, Mt, _, _, x, y = poisson_setup(T, dx, seed)
+    return PoissonModel(y, M0.m0, M0.P0, Mt.F, Mt.Q, Mt.b, order=order), x
+
+
 def lorenz_kalman_setup(T, every=8, dt=0.01, seed=0):
     """examples/lorenz: theta = (10, 28, 8/3), sigma_x = 3, m0 = (1.5, -1.5, 25), P0 = diag(400, 20, 20), (x2, x3) observed every `every`-th
     step with variance 5, NaN rows (ys AND Hs, as model.py:43-56) elsewhere."""

@@ -226,7 +226,14 @@ typedef enum {
      * dims->dy = dx <= 64; dense layout and nan_policy 0 only (anything else: AUXSSM_ERR_UNSUPPORTED, nothing enqueued); `parallel` is ignored
      * (csrc/kalman_mvt.hip: C * dx scalar recursions of length T). */
     AUXSSM_KMODEL_MVT_FIRST = 5,
-    AUXSSM_KMODEL_MVT_SECOND = 6
+    AUXSSM_KMODEL_MVT_SECOND = 6,
+    /* Poisson counts y_{t,k} ~ Poisson(exp(x_{t,k})) on linear-Gaussian dynamics: the SV sweep above with the pointwise potential
+     * log g_t(x) = sum_k y_k x_k - exp(x_k) (the constant -log y_k! left out, as AUXSSM_POT_POISSON does), grad_k = y_k - exp(x_k), -hess_kk = exp(x_k),
+     * all three 0 where y_{t,k} is NaN: a missing count drops that component's term alone and leaves the component observed through u with variance d/2 in
+     * both orders (no pseudo-observation is ever NaN).  Same arrays, layouts, widths and checks as SV_FIRST / SV_SECOND; counts must be >= 0 (not
+     * checked here) and exp(x) is not guarded against overflow.  Second order is always well defined: -hess = exp(x) > 0. */
+    AUXSSM_KMODEL_POISSON_FIRST = 7,
+    AUXSSM_KMODEL_POISSON_SECOND = 8
 } auxssm_kalman_model;
 typedef enum { AUXSSM_LAYOUT_DENSE = 0, AUXSSM_LAYOUT_CHAIN_MINOR = 1 } auxssm_layout;
 int auxssm_kalman_sweep(auxssm_handle h, int dtype, int model_kind, const auxssm_dims* dims,

@@ -11,6 +11,8 @@
              chains: independent, gradient, guided and parallel-in-time sweeps
    spatial_kalman  the spatial example's default sampler: the auxiliary Kalman sampler on the batched 8 x 8 model (d = 64, T = 1024, nu = 1, fp32, both orders), device
              sweep at 1 / 16 / 256 chains beside the host-factory path
+   poisson_kalman  count data under the auxiliary Kalman sampler (kalman.PoissonModel, fp32, both orders) at T = 250, dx = 30 and T = 16384, dx = 1, 1 / 64 / 256 /
+             1024 chains, beside SVModel at the same shapes, the host-factory path and the Poisson cSMC sweep
    pit30  the reference's SV experiment at its defaults (--parallel, D = 30, N = 25, T = 250): the parallel-in-time sweep beside the sequential wide sweep, 1 / 16 / 256 chains
    smoother  the RTS smoother (auxssm_kalman_smooth) beside the pathwise sampler (auxssm_kalman_sample) on the same resident filtered moments: C2's model at
              T = 65536, d = 4, fp64, 1 and 256 sequences, and T = 16384, d = 3, fp32, 64 sequences; parallel scan, at one sequence also the sequential recursion
@@ -524,6 +526,91 @@ def spatial_kalman(grid=8, T=1024, chains=(1, 16, 256), steps=50, host_reps=3):
                               delta=float(f"{delta:.3g}"), ms_per_sweep=round((time.perf_counter() - t0) / host_reps * 1e3, 2))), flush=True)
 
 
+def poisson_kalman(shapes=((250, 30), (16384, 1)), chain_counts=(1, 64, 256, 1024), runs=5, host_reps=3, N=25):
+    """count data under the auxiliary Kalman sampler (kalman.PoissonModel on workloads.poisson_kalman_setup), fp32, both orders, resident chains, keyed noise, at the
+    cSMC Poisson leg's shape (T = 250, dx = 30: wide-state kernels, dense layout) and at the SV general-path shape (T = 16384, dx = 1: chain-minor from 32 chains).
+    Beside every row, in the same process: SVModel at the same shape (workloads.sv_setup's data, the same step size), the two models' batches alternating -- a batch
+    is as many back-to-back sweeps as fill ~0.2 s and ends in a stream synchronisation; best and median batch of `runs`.  Then, per shape and order, the
+    host-factory path of the same model (the same methods behind lambdas, one chain), and for the first shape the Poisson cSMC sweep with independent proposals
+    (N = 25, backward sampling) at the same chain counts."""
+    from aux_ssm_samplers_amd.workloads import poisson_kalman_setup, poisson_setup, sv_setup
+    h = _lib.default_handle()
+
+    def batches(calls):
+        reps = []
+        for call in calls:
+            for _ in range(2):
+                call()
+            h.sync()
+            t0 = time.perf_counter()
+            call()
+            h.sync()
+            reps.append(int(min(2000, max(3, 0.2 / (time.perf_counter() - t0)))))
+        ts = [[] for _ in calls]
+        for _ in range(runs):
+            for k, call in enumerate(calls):
+                t0 = time.perf_counter()
+                for _ in range(reps[k]):
+                    call()
+                h.sync()
+                ts[k].append((time.perf_counter() - t0) / reps[k] * 1e3)
+        return [(min(t), float(np.median(t)), max(t)) for t in ts]
+
+    for T, D in shapes:
+        delta = 0.02 if D > 4 else 0.05
+        for order in (1, 2):
+            pm, xp = poisson_kalman_setup(T, D, order=order)
+            ysv, xsv, (m0, P0, F, Q, b) = sv_setup(T, D)
+            sm = SVModel(ysv, m0, P0, F, Q, b, order=order)
+            kernels = [get_kernel(m.dynamics_factory, m.observations_factory, m.log_likelihood_fn, True)[1] for m in (pm, sm)]
+            for C_ in chain_counts:
+                chs = [DeviceChains(h, np.repeat(x[None], C_, axis=0).astype(np.float32)) for x in (xp, xsv)]
+                states = [KalmanSampler(x=c, updated=None) for c in chs]
+                count = [0]
+
+                def sweep(k):
+                    count[0] += 1
+                    kernels[k](R.PRNGKey(count[0]), states[k], delta)
+
+                (pb, pmed, pmax), (sb, smed, smax) = batches([lambda: sweep(0), lambda: sweep(1)])
+                print(json.dumps(dict(config=f"poisson_kalman T={T} dx={D}, aux-Kalman order {order}, fp32, {'chain-minor' if chs[0].chain_minor else 'dense'} layout, "
+                                             "resident chains", chains=C_, delta=delta,
+                                      ms_per_sweep=dict(Poisson=round(pb, 4), SV=round(sb, 4)), ms_per_sweep_median=dict(Poisson=round(pmed, 4), SV=round(smed, 4)),
+                                      ms_per_sweep_worst=dict(Poisson=round(pmax, 4), SV=round(smax, 4)),
+                                      sweeps_per_s=dict(Poisson=round(C_ / pb * 1e3, 1), SV=round(C_ / sb * 1e3, 1)), poisson_over_sv_rate=round(sb / pb, 3),
+                                      accept=dict(Poisson=float(chs[0].accepted.to_host().mean()), SV=float(chs[1].accepted.to_host().mean())))), flush=True)
+                del chs, states
+            hinit, hkernel = get_kernel(lambda x: pm.dynamics_factory(x), lambda x, u, dl: pm.observations_factory(x, u, dl), lambda x: pm.log_likelihood_fn(x), True)
+            st = hinit(xp.astype(np.float32))
+            keys = R.split(R.PRNGKey(3), host_reps + 1)
+            st = hkernel(keys[0], st, delta)
+            h.sync()
+            t0 = time.perf_counter()
+            for k in range(host_reps):
+                st = hkernel(keys[1 + k], st, delta)
+            h.sync()
+            print(json.dumps(dict(config=f"poisson_kalman T={T} dx={D}, aux-Kalman order {order}, fp32, host-factory path", chains=1, delta=delta,
+                                  ms_per_sweep=round((time.perf_counter() - t0) / host_reps * 1e3, 2))), flush=True)
+    from aux_ssm_samplers_amd.csmc import CsmcChains, CSMCState, get_independent_kernel
+    T, D = shapes[0]
+    M0, Mt, G0, Gt, x, y = poisson_setup(T, D)
+    init, kernel = get_independent_kernel(M0, G0, Mt, Gt, N, Pt=Mt, backward=True, gradient=False)
+    for C_ in chain_counts:
+        cc = CsmcChains(h, np.repeat(x[None], C_, axis=0).astype(np.float32))
+        st = CSMCState(x=cc, updated=None)
+        kernel(0, st, 0.01)
+        count = [0]
+
+        def csweep():
+            count[0] += 1
+            kernel(count[0], st, None)
+
+        (cb, cmed, cmax), = batches([csweep])
+        print(json.dumps(dict(config=f"poisson D={D} T={T}, aux-cSMC N={N} independent proposals + backward sampling, fp32, resident chains", chains=C_,
+                              ms_per_sweep=round(cb, 4), ms_per_sweep_median=round(cmed, 4), sweeps_per_s=round(C_ / cb * 1e3, 1))), flush=True)
+        del cc, st
+
+
 def smoother(runs=5):
     """auxssm_kalman_smooth beside auxssm_kalman_sample of the same process on the same resident (ms, Ps): the filter runs once on the device (chain-shared model and
     data, dense layout), then the two entry points are timed in alternating batches of back-to-back calls (~0.2 s each, `runs` per entry point) that end in a stream synchronisation; best and
@@ -588,6 +675,8 @@ if __name__ == "__main__":
         spatial_kalman()
     if "smoother" in which:
         smoother()
+    if "poisson_kalman" in which:
+        poisson_kalman()
     if "sv30" in which:
         sv30()
     if "guided" in which:
