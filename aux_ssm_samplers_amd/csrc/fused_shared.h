@@ -269,10 +269,12 @@ template <int D> __global__ void __launch_bounds__(256) k_fs_clog_sum(int T, int
     if (threadIdx.x == 0) *out = sh[0] + (Acc)T * (Acc)D * (Acc)(0.5 * LOG_2PI);
 }
 
-// workgroup = all (up to 256) chains of one chunk; consecutive blocks = the chain groups of one chunk
-__device__ __forceinline__ void fs_block(const FusedArgs& a, int& ch, int& c) {
+// workgroup = all (up to 256) chains of one chunk; consecutive blocks = the chain groups of one chunk; the chunks in ascending order of the block index, or (down)
+// from the last one
+__device__ __forceinline__ void fs_block(const FusedArgs& a, int& ch, int& c, bool down = false) {
     const int groups = (a.C + (int)blockDim.x - 1) / (int)blockDim.x;
-    ch = blockIdx.x / groups;
+    const int q = blockIdx.x / groups;
+    ch = down ? a.nchunk - 1 - q : q;
     c = (blockIdx.x % groups) * blockDim.x + threadIdx.x;
 }
 // copy rows [r0, r1) of a table with rows of N reals into LDS (N a multiple of 16 bytes): one burst of coalesced 16-byte loads
@@ -567,6 +569,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_WPE
 }
 
 // ---- pass E ---------------------------------------------------------------------------------------------------------------------------
+// The unpacked form (more than 128 chains) streams arrays far larger than the caches, each touched once per sweep: a record of inc0 or u is read exactly once, here,
+// and is dead afterwards; a line of x' is next touched by the following sweep's pass AC, a whole array later.  Its record loads and x' stores carry the
+// non-temporal hint, and its blocks walk the chunks from the LAST one down (pass AC wrote the last chunks' records last; the pass ends on chunk 0, where the next
+// pass AC starts).  Measured together: pass E 364 -> 336 us at 256 chains, T = 65536, d = 4, fp64; the sweep -3.4 % there, -3.8 % at 1024
+// chains.  What did NOT move the pass is listed there too: more records in flight per lane, two chains per lane with 16-byte accesses.  Same values, same
+// arithmetic: only the cache policy of the memory instructions and the order of the blocks differ from the packed form.
+template <bool ONCE, typename R> __device__ __forceinline__ R fs_ld_once(const R* p) {
+    if constexpr (ONCE) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+template <bool ONCE, typename R> __device__ __forceinline__ void fs_st_once(R* p, R v) {
+    if constexpr (ONCE) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
 template <typename R, int D, int PO, bool PK = false> __global__ void __launch_bounds__(256) k_fs_e(FusedArgs a, const R* __restrict__ rows) {
     using F = FsRows<R, D, PO>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -578,7 +594,7 @@ template <typename R, int D, int PO, bool PK = false> __global__ void __launch_b
         c = (int)threadIdx.x - sub * a.cp;
         ch = blockIdx.x * a.pack + sub;
     } else {
-        fs_block(a, ch, c);
+        fs_block(a, ch, c, true);
     }
     const long long C = a.C;
     const int t0 = ch * a.E, tb = min(a.T, t0 + a.E);
@@ -614,7 +630,7 @@ template <typename R, int D, int PO, bool PK = false> __global__ void __launch_b
     Acc v0 = 0, v1 = 0, v2 = 0;
     R incn[D], utn[D];  // the next (earlier) step's records, fetched one step ahead
 #pragma unroll
-    for (int k = 0; k < D; ++k) incn[k] = ip[((long long)(tb - 1) * D + k) * C], utn[k] = up[((long long)(tb - 1) * D + k) * C];
+    for (int k = 0; k < D; ++k) incn[k] = fs_ld_once<!PK>(ip + ((long long)(tb - 1) * D + k) * C), utn[k] = fs_ld_once<!PK>(up + ((long long)(tb - 1) * D + k) * C);
 #pragma unroll 1
     for (int t = tb - 1; t >= t0; --t) {
         const int tu = PK ? t : opaque_uniform(t);
@@ -625,7 +641,7 @@ template <typename R, int D, int PO, bool PK = false> __global__ void __launch_b
         if (t > t0) {
             const int tn = PK ? t - 1 : opaque_uniform(t - 1);
 #pragma unroll
-            for (int k = 0; k < D; ++k) incn[k] = ip[((long long)tn * D + k) * C], utn[k] = up[((long long)tn * D + k) * C];
+            for (int k = 0; k < D; ++k) incn[k] = fs_ld_once<!PK>(ip + ((long long)tn * D + k) * C), utn[k] = fs_ld_once<!PK>(up + ((long long)tn * D + k) * C);
         }
 #pragma unroll
         for (int i = 0; i < D; ++i) {
@@ -635,7 +651,7 @@ template <typename R, int D, int PO, bool PK = false> __global__ void __launch_b
 #pragma unroll
             for (int k = 0; k < D; ++k) v += row[F::eG + i * D + k] * h[k];
             xp[i] = v;
-            xw[((long long)tu * D + i) * C] = v;
+            fs_st_once<!PK>(xw + ((long long)tu * D + i) * C, v);
         }
         if (tu + 1 < a.T) {  // (wave-uniform) LogShared row tu: x'_{tu+1} = h given x'_tu = xp, observation and auxiliary terms at tu + 1
             R w[3];
