@@ -6,6 +6,7 @@
 
 #include "ctx.h"
 #include "kalman_mvt.h"
+#include "kalman_plin.h"
 #include "rng.h"
 
 namespace ax {
@@ -1395,6 +1396,102 @@ template <typename R> static int sweep_mvt(const SweepCall& c) {
     return AUXSSM_OK;
 }
 
+// AUXSSM_KMODEL_POISSON_LIN_FIRST / _SECOND: Poisson counts behind a loading matrix, y_{t,j} ~ Poisson(exp(h_j' x_t + c_j)), j = 1..dy (model->Hs = H (dy, dx)
+// row-major, model->cs = c (dy)).  sweep_sv's dense, materialised form with the factory and the terms of kalman_plin.hip: the pseudo-observations live in the
+// state space, so both filters, the sampler and the two joint densities are the dx <= 4 register kernels whatever dy is; second order gives every (chain, step)
+// its own dense R = Omega_t.
+template <typename R> static int sweep_plin(const SweepCall& c) {
+    auxssm_ctx* h = c.h;
+    const auxssm_lgssm* model = c.model;
+    const int dtype = c.dtype, parallel = c.parallel;
+    const int C = c.dims->C, T = c.dims->T, D = c.dims->dx, PO = c.dims->dy;
+    const bool second = c.order == 2;
+    const KalmanEntry* ke = need_kalman(dtype, D, D);
+    const SampleEntry* se = sample_entry(dtype, D);
+    if (!ke || !se) return AUXSSM_ERR_UNSUPPORTED;
+    const KDims kd{C, T, 1};
+    const size_t sR = sizeof(R), CT = (size_t)C * T;
+    R *u, *ys1, *ys2, *xp, *Rs1 = nullptr, *Rs2 = nullptr, *ms, *Ps, *eye, *Rc, *zero, *sc;
+    Acc *pot1, *pot2, *part;
+    WsPlan ws;
+    ws.add(u, CT * D * sR);
+    ws.add(ys1, CT * D * sR);
+    ws.add(ys2, CT * D * sR);
+    ws.add(xp, CT * D * sR);
+    if (second) ws.add(Rs1, CT * D * D * sR), ws.add(Rs2, CT * D * D * sR);
+    ws.add(ms, CT * D * sR);
+    ws.add(Ps, CT * D * D * sR);
+    ws.add(pot1, CT * sizeof(Acc));
+    ws.add(pot2, CT * sizeof(Acc));
+    ws.add(part, plin_terms_part_bytes(C, T));
+    ws.add(eye, (size_t)D * D * sR);
+    ws.add(Rc, (size_t)D * D * sR);
+    ws.add(zero, (size_t)D * sR);
+    ws.add(sc, (size_t)16 * C * sR);
+    ws.after(ke->filter_ws(h, kd, parallel));
+    ws.after(se->sample_ws(h, kd, parallel));
+    ws.after(ke->logpdf_ws(h, kd));
+    int rc = ws.reserve(h);
+    if (rc) return rc;
+    R* ell1 = sc; R* ell2 = sc + C; R* j1 = sc + 2 * C; R* j2 = sc + 3 * C; R* terms = sc + 4 * C;
+    const size_t mark = h->ws_off;
+    hipLaunchKernelGGL((k_scaled_eye<R>), dim3((D * D + 255) / 256), dim3(256), 0, h->stream, D, (R)1, eye);
+    hipLaunchKernelGGL((k_fill<R>), dim3(1), dim3(256), 0, h->stream, (long long)D, (R)0, zero);
+    if (!second) hipLaunchKernelGGL((k_scaled_eye<R>), dim3((D * D + 255) / 256), dim3(256), 0, h->stream, D, (R)(0.5 * c.delta), Rc, c.dptr);
+    AX_HIP(hipGetLastError());
+    // observation LGSSMs of the two linearisation points (H = I, c = 0; R = delta/2 I or the per-step dense Omega)
+    auxssm_lgssm g1 = *model;
+    g1.Hs = auxssm_arr{eye, 0, 0, 0};
+    g1.cs = auxssm_arr{zero, 0, 0, 0};
+    g1.Rs = second ? auxssm_arr{Rs1, (int64_t)T * D * D, (int64_t)D * D, 0} : auxssm_arr{Rc, 0, 0, 0};
+    auxssm_lgssm g2 = g1;
+    if (second) g2.Rs = auxssm_arr{Rs2, (int64_t)T * D * D, (int64_t)D * D, 0};
+    auxssm_dims dc = *c.dims;
+    dc.dy = D;
+    dc.B = 1;
+    const Arr xA = dense_arr(c.x, kd, D), xpA = dense_arr(xp, kd, D), y1A = dense_arr(ys1, kd, D), y2A = dense_arr(ys2, kd, D);
+    const Arr msA = dense_arr(ms, kd, D), PsA = dense_arr(Ps, kd, (long long)D * D);
+    auto launch_obs = [&](const R* xlin, const R* eps, R* ys, R* Rs, Acc* pot) {
+        ProfScope ps(h, AUXSSM_K_FACTORY);
+        const PlinObsArgs oa{C, T, D, PO, c.order, c.delta, c.dptr, model->Hs.ptr, model->cs.ptr, c.yobs->ptr, (long long)c.yobs->st, xlin, eps, u, ys, Rs, pot};
+        return run_plin_obs(h, dtype, oa);
+    };
+    // proposal: observations linearised at x (u formed on the way), filter, pathwise sample (generic.py:80-86)
+    if ((rc = launch_obs((const R*)c.x, (const R*)c.eps_aux, ys1, Rs1, pot1))) return rc;
+    FilterArgs fa;
+    sweep_filter_args(fa, dc, g1, y1A, msA, PsA, 0);
+    if ((rc = ke->filter(h, fa, parallel, ell1))) return rc;
+    h->ws_off = mark;
+    SampleArgs sa;
+    fill_sample_args(sa, kd, D, cv(model->Fs), cv(model->Qs), cv(model->bs), msA, PsA, dense_arr(c.eps_samp, kd, D), xpA, 0);
+    if ((rc = se->sample(h, sa, parallel))) return rc;
+    h->ws_off = mark;
+    // reverse move: observations linearised at x', filter for its marginal likelihood (generic.py:67)
+    if ((rc = launch_obs((const R*)xp, (const R*)nullptr, ys2, Rs2, pot2))) return rc;
+    FilterArgs fr;
+    sweep_filter_args(fr, dc, g2, y2A, msA, PsA, 0);
+    if ((rc = ke->filter(h, fr, parallel, ell2))) return rc;
+    h->ws_off = mark;
+    // joint log-densities of both auxiliary models (posterior_logpdf + ell, base.py:72-96), as sweep_sv's wide branch takes them
+    LogpdfArgs la;
+    fill_logpdf_args(la, &dc, &g1, y1A, xpA, c.nan_policy);
+    if ((rc = ke->logpdf(h, la, j1))) return rc;
+    h->ws_off = mark;
+    fill_logpdf_args(la, &dc, &g2, y2A, xA, c.nan_policy);
+    if ((rc = ke->logpdf(h, la, j2))) return rc;
+    h->ws_off = mark;
+    {
+        ProfScope ps(h, AUXSSM_K_LOGPDF);
+        const PlinTermsArgs ta{C, T, D, c.delta, c.dptr, c.x, xp, u, ys1, ys2, Rs1, Rs2, pot1, pot2, part, terms};
+        if ((rc = run_plin_terms(h, dtype, ta))) return rc;
+    }
+    hipLaunchKernelGGL((k_sv_accept<R>), dim3((C + 127) / 128), dim3(128), 0, h->stream, C, (const R*)j1, (const R*)j2, (const R*)ell1, (const R*)ell2,
+                       (const R*)terms, (const R*)c.u_acc, c.accepted, (R*)c.logs);
+    if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)c.accepted, xpA, xA, 0))) return rc;
+    AX_HIP(hipGetLastError());
+    return AUXSSM_OK;
+}
+
 // ---- Lorenz-63 device factories (examples/lorenz/auxiliary_kalman.py:14-52, model.py:10-25, linearisation.py:11-44) ------------
 // dynamics_factory(x) = first-order extended linearisation of mean(x) = x + dt (phi_0(x) + theta * phi(x)) at every x_t, with the
 // analytic Jacobian in place of jacfwd:  F_t = I + dt J(x_t),  b_t = mean(x_t) - F_t x_t,  Q = model Qs;
@@ -1954,7 +2051,8 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
     const bool sv = pois || model_kind == AUXSSM_KMODEL_SV_FIRST || model_kind == AUXSSM_KMODEL_SV_SECOND;
     const bool lorenz = model_kind == AUXSSM_KMODEL_LORENZ63_EXT;
     const bool mvt = model_kind == AUXSSM_KMODEL_MVT_FIRST || model_kind == AUXSSM_KMODEL_MVT_SECOND;
-    if (model_kind != AUXSSM_KMODEL_LG_CONCAT && !sv && !lorenz && !mvt) {
+    const bool plin = model_kind == AUXSSM_KMODEL_POISSON_LIN_FIRST || model_kind == AUXSSM_KMODEL_POISSON_LIN_SECOND;
+    if (model_kind != AUXSSM_KMODEL_LG_CONCAT && !sv && !lorenz && !mvt && !plin) {
         set_error("unknown model_kind %d", model_kind);
         return AUXSSM_ERR_ARG;
     }
@@ -1985,12 +2083,32 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
             set_error("the multivariate-t model observes every state component: dy (%d) must equal dx (%d)", dims->dy, dims->dx);
             return AUXSSM_ERR_ARG;
         }
+    } else if (plin) {
+        if (!model || !model->m0.ptr || !model->P0.ptr || (dims->T > 1 && (!model->Fs.ptr || !model->Qs.ptr || !model->bs.ptr)) || !model->Hs.ptr || !model->cs.ptr ||
+            !yobs || !yobs->ptr) {
+            set_error("Poisson-linear model needs m0, P0 (and Fs, Qs, bs with T > 1), Hs (= H (dy, dx) row-major on the device), cs (= c (dy) on the device) and yobs (T, dy)");
+            return AUXSSM_ERR_ARG;
+        }
     } else if ((rc = check_lgssm(model, dims->T))) {
         return rc;
     }
     if ((rc = check_sweep_common(false, dims, delta, delta_dev != nullptr, nan_policy, layout, yobs && yobs->ptr && x && eps_aux && eps_samp && u_acc && accepted, model,
-                                 yobs, !sv && !mvt)))
+                                 yobs, !sv && !mvt && !plin)))
         return rc;
+    if (plin) {  // (before anything is enqueued)
+        if (dims->dx > MAX_D) {
+            set_error("the Poisson-linear sweep covers dx <= %d (the register kernels): got dx = %d", MAX_D, dims->dx);
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+        if (dims->dy > PLIN_MAX_DY) {
+            set_error("the Poisson-linear sweep covers dy <= %d channels: got dy = %d", PLIN_MAX_DY, dims->dy);
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+        if (layout != AUXSSM_LAYOUT_DENSE) {
+            set_error("the Poisson-linear sweep (dx <= %d, dy <= %d) takes the dense (C, T, dx) layout only", MAX_D, PLIN_MAX_DY);
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+    }
     if (mvt) {  // (before anything is enqueued)
         if (dims->dx > 64) {
             set_error("the batched multivariate-t sweep covers dx <= 64 (one wave per time step, lane = component): got dx = %d", dims->dx);
@@ -2008,7 +2126,7 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
     const double* dptr;
     if ((rc = delta_block(h, dtype, delta_dev, &dptr))) return rc;
     SweepCall c{h, dtype, dims, model, yobs, delta, dptr, keys, parallel, nan_policy, layout, x, eps_aux, eps_samp, u_acc, accepted, logs};
-    if (keys && (lorenz || sv || mvt))  // these sweeps read the noise from the arrays: draw all of it first (auxssm_kalman_draw)
+    if (keys && (lorenz || sv || mvt || plin))  // these sweeps read the noise from the arrays: draw all of it first (auxssm_kalman_draw)
         by_dtype(dtype, [&](auto r) {
             launch_rng_sweep<decltype(r)>(h, keys, (long long)dims->C * dims->T * dims->dx, dims->C, const_cast<void*>(eps_aux), const_cast<void*>(eps_samp),
                                           const_cast<void*>(u_acc));
@@ -2017,9 +2135,11 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
     if (sv) c.order = (model_kind == AUXSSM_KMODEL_SV_FIRST || model_kind == AUXSSM_KMODEL_POISSON_FIRST) ? 1 : 2;
     if (pois) c.kind = PW_POISSON;
     if (mvt) c.order = model_kind == AUXSSM_KMODEL_MVT_FIRST ? 1 : 2;
+    if (plin) c.order = model_kind == AUXSSM_KMODEL_POISSON_LIN_FIRST ? 1 : 2;
     return by_dtype(dtype, [&](auto r) {
         using R = decltype(r);
         if (mvt) return sweep_mvt<R>(c);
+        if (plin) return sweep_plin<R>(c);
         return lorenz ? sweep_lorenz<R>(c) : sv ? sweep_sv<R>(c) : sweep_lg_concat<R>(c);
     });
 }

@@ -218,6 +218,136 @@ class PoissonModel(_PointwiseModel):
         return ys.astype(dt), eyes, Rs, zeros
 
 
+class PoissonLinearModel:
+    """Poisson counts through a loading matrix (the Poisson linear dynamical system, a dynamic Poisson factor model): a low-dimensional linear-Gaussian state
+    drives many count channels,
+
+        x_0 ~ N(m0, P0),   x_{t+1} = F x_t + b + N(0, Q),   y_{t,j} ~ Poisson(exp(h_j' x_t + c_j)),   j = 1..dy,
+
+    under the first- or second-order auxiliary observation factories of examples/stochastic_volatility/auxiliary_kalman.py:22-48.  ys (T, dy): counts >= 0, NaN =
+    missing; H (dy, dx) dense and finite; c (dy,) or a scalar; the dynamics arguments are SVModel's; 1 <= dx <= MAX_DX = 4, 1 <= dy <= MAX_DY = 1024.  With
+    mask = isfinite(y), eta_t = H x_t + c, e = where(mask, exp(eta), 0), yy = where(mask, y, 0):
+
+        log g_t = sum_j yy_j eta_j - e_j       grad_t = H' (yy - e)  (dx)       Lam_t = H' diag(e) H = -hess  (dx x dx, symmetric PSD)
+
+        dynamics_factory(x)           -> m0, P0, tile(F), tile(Q), tile(b)
+        observations_factory(x, u, d) -> order 1: ys = u + d/2 grad,                                            H_obs = I, R = d/2 I, c_obs = 0
+                                         order 2: Om = sym((Lam + 2/d I)^-1), ys = Om (2u/d + grad + Lam x),    H_obs = I, R = Om,    c_obs = 0
+        log_likelihood_fn(x)          -> prior_logpdf(x) + sum_t log g_t
+
+    The pseudo-observation of both orders lives in the state space, so the filter and the pathwise sampler are the dx <= 4 register kernels however large dy is;
+    the dy-dependent work is a reduction over the channels per (chain, step) (csrc/kalman_plin.hip).  The conventions are PoissonModel's, so the samplers share
+    one density: the constant -log y! is left out, non-integer y >= 0 is accepted, a finite negative entry raises ValueError, a NaN y_{t,j} drops that channel's
+    term alone.  Lam is PSD, so order 2 is always defined.  With H = I, c = 0, dy = dx the model is PoissonModel.  exp overflow (|eta| beyond ~88 in float32,
+    ~709 in float64) is not guarded.
+
+    The first-order proposal is only usable for delta * lambda_max(Lam_t) of order 1: at dy >= 65 with delta = 0.05 the oracle's own log alpha was -1e3 to
+    -1e70.  That is the linearisation, not a defect; the second order has no such limit.
+
+    Pass the three bound methods to kalman.get_kernel: it runs the device sweep (model kind POISSON_LIN_FIRST / _SECOND) on host states (T, dx) or (C, T, dx),
+    or on resident DeviceChains(handle, x (C, T, dx), chain_minor=False): the dense layout only.  The same methods are NumPy factories for the host path and
+    the oracle."""
+    dense_only = True
+    MAX_DX = 4
+    MAX_DY = 1024
+
+    def __init__(self, ys, H, c, m0, P0, F, Q, b, order=1):
+        if order not in (1, 2):
+            raise ValueError("order must be 1 or 2")
+        ys = np.asarray(ys)
+        if ys.ndim != 2:
+            raise ValueError(f"PoissonLinearModel: ys must be (T, dy), got shape {ys.shape}")
+        H = np.asarray(H, np.float64)
+        if H.ndim != 2 or H.shape[0] != ys.shape[1]:
+            raise ValueError(f"PoissonLinearModel: H must be (dy, dx) = ({ys.shape[1]}, dx), got shape {H.shape}")
+        T, dy = ys.shape
+        dx = H.shape[1]
+        if not 1 <= dx <= self.MAX_DX:
+            raise NotImplementedError(f"PoissonLinearModel: dx = {dx}: the sweep covers 1 <= dx <= {self.MAX_DX}")
+        if not 1 <= dy <= self.MAX_DY:
+            raise NotImplementedError(f"PoissonLinearModel: dy = {dy}: the sweep covers 1 <= dy <= {self.MAX_DY}")
+        if not np.all(np.isfinite(H)):
+            raise ValueError("PoissonLinearModel: H must be finite")
+        c = np.asarray(c, np.float64)
+        if c.ndim == 0:
+            c = np.full(dy, float(c))
+        if c.shape != (dy,) or not np.all(np.isfinite(c)):
+            raise ValueError(f"PoissonLinearModel: c must be a finite scalar or ({dy},) vector, got shape {c.shape}")
+        from ..csmc.models import PoissonPotential
+        PoissonPotential.check_counts(ys)
+        self.yobs, self.H, self.c = ys, H, c
+        self.T, self.dx, self.p_obs = T, dx, dy
+        self.m0, self.P0 = np.asarray(m0), np.asarray(P0)
+        self.F, self.Q, self.b = np.asarray(F), np.asarray(Q), np.asarray(b)
+        if self.m0.shape != (dx,) or self.b.shape != (dx,) or any(a.shape != (dx, dx) for a in (self.P0, self.F, self.Q)):
+            raise ValueError(f"PoissonLinearModel: m0, b must be ({dx},) and P0, F, Q ({dx}, {dx})")
+        self.order = order
+        self.kmodel = _lib.KMODEL_POISSON_LIN_FIRST if order == 1 else _lib.KMODEL_POISSON_LIN_SECOND
+        n = T - 1
+        self.Fs = np.broadcast_to(self.F, (n, dx, dx))
+        self.Qs = np.broadcast_to(self.Q, (n, dx, dx))
+        self.bs = np.broadcast_to(self.b, (n, dx))
+        self._dev = {}
+
+    def dynamics_factory(self, x):
+        return self.m0, self.P0, self.Fs, self.Qs, self.bs
+
+    def _terms(self, x):
+        """(mask, eta, e, yy) at x (T, dx), each (T, dy)"""
+        x = np.asarray(x)
+        eta = x @ self.H.astype(x.dtype).T + self.c.astype(x.dtype)
+        mask = np.isfinite(self.yobs)
+        with np.errstate(over="ignore"):
+            e = np.where(mask, np.exp(eta), 0.0)
+        return mask, eta, e, np.where(mask, self.yobs, 0.0).astype(x.dtype)
+
+    def log_potential(self, x):
+        _, eta, e, yy = self._terms(x)
+        return float(np.sum(yy * eta - e))
+
+    def grad_lam(self, x):
+        """(grad (T, dx), Lam (T, dx, dx)) of log g: H' (yy - e) and H' diag(e) H"""
+        _, _, e, yy = self._terms(x)
+        H = self.H.astype(e.dtype)
+        lam = np.einsum("tj,jk,jl->tkl", e, H, H)
+        return (yy - e) @ H, 0.5 * (lam + np.swapaxes(lam, -1, -2))   # (symmetric to the last bit)
+
+    def observations_factory(self, x, u, delta):
+        x, u = np.asarray(x), np.asarray(u)
+        T, d = self.T, self.dx
+        dt = u.dtype
+        eyes = np.broadcast_to(np.eye(d, dtype=dt), (T, d, d))
+        zeros = np.zeros((T, d), dt)
+        grad, lam = self.grad_lam(x)
+        if self.order == 1:
+            return (u + 0.5 * delta * grad).astype(dt), eyes, (0.5 * delta * eyes).astype(dt), zeros
+        om = np.linalg.inv(lam + (2.0 / delta) * np.eye(d))
+        om = 0.5 * (om + np.swapaxes(om, -1, -2))
+        ys = np.einsum("tkl,tl->tk", om, 2.0 * u / delta + grad + np.einsum("tkl,tl->tk", lam, x))
+        return ys.astype(dt), eyes, om.astype(dt), zeros
+
+    def log_likelihood_fn(self, x):
+        from .._primitives.kalman.base import prior_logpdf, LGSSM
+        x = np.asarray(x)
+        prior = prior_logpdf(x, LGSSM(self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None))
+        return prior + self.log_potential(x)
+
+    def device(self, handle, dtype):
+        key = (id(handle), np.dtype(dtype).str)
+        dev = self._dev.get(key)
+        if dev is None:
+            T, d, dy = self.T, self.dx, self.p_obs
+            lg = (self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None)
+            dl = DeviceLGSSM(handle, lg, 1, T, 1, d, d, False, dtype)
+            # include/auxssm.h, POISSON_LIN_FIRST / _SECOND: the loading matrix (dy, dx) row-major rides in the Hs slot, the offsets (dy) in the cs slot
+            for name, a in (("Hs", self.H), ("cs", self.c)):
+                buf = dl.bufs["plin_" + name] = handle.to_device(np.ascontiguousarray(a, np.float64), dtype)
+                setattr(dl.c, name, buf.arr(0, 0, 0))
+            ybuf, yarr = _upload_arr(handle, self.yobs, (dy,), 1, T, 1, False, False, np.dtype(dtype), "ys")
+            dev = self._dev[key] = (dl, ybuf, yarr)
+        return dev
+
+
 class LorenzModel:
     """Stochastic Lorenz-63 with Euler-Maruyama dynamics and sparse linear-Gaussian observations,
     examples/lorenz/auxiliary_kalman.py:14-52 (model.py:10-25; linearisation.py:11-44 with the analytic Jacobian in place of jacfwd):

@@ -140,6 +140,28 @@ def poisson_kalman_setup(T, dx, seed=0, order=1):
     return PoissonModel(y, M0.m0, M0.P0, Mt.F, Mt.Q, Mt.b, order=order), x
 
 
+def poisson_lin_setup(T, dx, dy, seed=0, order=1):
+    """Poisson counts through a loading matrix (a Poisson linear dynamical system): dy count channels on a dx-dimensional linear-Gaussian latent,
+    y_{t,j} ~ Poisson(exp(h_j' x_t + c_j)).  F = 0.9 I with 0.05 / -0.05 beside the diagonal (poisson_setup's), m0 = b = 0, Q = 0.04 I, P0 = 0.2 I (about
+    the stationary variance); H = N(0, 1) / sqrt(dx) with entries of magnitude below 0.1 set to 0.1, c ~ U(0, 2): rates around e, counts mostly 0 .. 30 with
+    occasional counts above 100 at large loadings.
+    Returns (model, x0, H, c): a kalman.PoissonLinearModel, a start state (T, dx) -- the simulated latent path --, the loading matrix and the offsets."""
+    from aux_ssm_samplers_amd.kalman import PoissonLinearModel
+    rng = np.random.Generator(np.random.PCG64(seed))
+    F = 0.9 * np.eye(dx) + 0.05 * np.eye(dx, k=1) - 0.05 * np.eye(dx, k=-1)
+    m0, b = np.zeros(dx), np.zeros(dx)
+    Q, P0 = 0.04 * np.eye(dx), 0.2 * np.eye(dx)
+    H = rng.standard_normal((dy, dx)) / np.sqrt(dx)
+    H = np.where(np.abs(H) < 0.1, 0.1, H)
+    c = 2.0 * rng.random(dy)
+    x = np.zeros((T, dx))
+    x[0] = np.sqrt(0.2) * rng.standard_normal(dx)
+    for t in range(1, T):
+        x[t] = F @ x[t - 1] + 0.2 * rng.standard_normal(dx)
+    y = rng.poisson(np.exp(x @ H.T + c)).astype(np.float64)
+    return PoissonLinearModel(y, H, c, m0, P0, F, Q, b, order=order), x, H, c
+
+
 def lorenz_kalman_setup(T, every=8, dt=0.01, seed=0):
     """examples/lorenz: theta = (10, 28, 8/3), sigma_x = 3, m0 = (1.5, -1.5, 25), P0 = diag(400, 20, 20), (x2, x3) observed every `every`-th
     step with variance 5, NaN rows (ys AND Hs, as model.py:43-56) elsewhere."""

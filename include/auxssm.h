@@ -233,7 +233,19 @@ typedef enum {
      * both orders (no pseudo-observation is ever NaN).  Same arrays, layouts, widths and checks as SV_FIRST / SV_SECOND; counts must be >= 0 (not
      * checked here) and exp(x) is not guarded against overflow.  Second order is always well defined: -hess = exp(x) > 0. */
     AUXSSM_KMODEL_POISSON_FIRST = 7,
-    AUXSSM_KMODEL_POISSON_SECOND = 8
+    AUXSSM_KMODEL_POISSON_SECOND = 8,
+    /* (9 and 10 are unassigned.)
+     * Poisson counts through a loading matrix (the Poisson linear dynamical system): y_{t,j} ~ Poisson(exp(h_j' x_t + c_j)), j = 1..dy, on linear-Gaussian
+     * dynamics.  With eta = H x_t + c, e = exp(eta) and every term of a NaN count dropped: log g_t = sum_j y_j eta_j - e_j (the constant -log y_j! left out),
+     * grad = H' (y - e), Lam = -hess = H' diag(e) H (symmetric PSD).  observations_factory(x, u, d) is the first-order (ys = u + d/2 grad, R = d/2 I) or
+     * second-order (Omega = sym((Lam + 2/d I)^-1), ys = Omega (2u/d + grad + Lam x), R = Omega: dense, one per chain and step) auxiliary observation set with
+     * H_obs = I, c_obs = 0; log_likelihood_fn(x) = prior_logpdf(x) + sum_t log g_t.  `model`: m0, P0, Fs, Qs, bs as usual; Hs.ptr -> H (dy, dx) row-major and
+     * cs.ptr -> c (dy), both DEVICE arrays of `dtype`, time-invariant and chain-shared (strides ignored; Rs unused).  yobs (T, dy) with NaN = missing, counts
+     * >= 0 (not checked here); exp is not guarded against overflow.  dims->dx <= 4, dims->dy <= 1024, dense layout only (anything else: AUXSSM_ERR_UNSUPPORTED;
+     * a NULL Hs / cs / yobs: AUXSSM_ERR_ARG; nothing enqueued).  auxssm_kalman_sweep, _dd and _keyed run them (csrc/kalman_plin.hip: one lane per (chain, step),
+     * the counts staged through LDS in blocks of 64 channels); auxssm_kalman_sweep_fused refuses them. */
+    AUXSSM_KMODEL_POISSON_LIN_FIRST = 11,
+    AUXSSM_KMODEL_POISSON_LIN_SECOND = 12
 } auxssm_kalman_model;
 typedef enum { AUXSSM_LAYOUT_DENSE = 0, AUXSSM_LAYOUT_CHAIN_MINOR = 1 } auxssm_layout;
 int auxssm_kalman_sweep(auxssm_handle h, int dtype, int model_kind, const auxssm_dims* dims,

@@ -13,6 +13,9 @@
              sweep at 1 / 16 / 256 chains beside the host-factory path
    poisson_kalman  count data under the auxiliary Kalman sampler (kalman.PoissonModel, fp32, both orders) at T = 250, dx = 30 and T = 16384, dx = 1, 1 / 64 / 256 /
              1024 chains, beside SVModel at the same shapes, the host-factory path and the Poisson cSMC sweep
+   poisson_lin_kalman  Poisson counts through a loading matrix under the auxiliary Kalman sampler (kalman.PoissonLinearModel, T = 16384, dx = 4, dy = 128, fp32, both
+             orders) at 1 / 64 / 256 dense resident chains, beside kalman.PoissonModel at T = 16384, dx = 4 on dense chains and the host-factory path of the new
+             model; then the library's kernel-group times of one sweep.  poisson_lin_trace: a few sweeps alone, for a kernel trace taken from outside
    pit30  the reference's SV experiment at its defaults (--parallel, D = 30, N = 25, T = 250): the parallel-in-time sweep beside the sequential wide sweep, 1 / 16 / 256 chains
    smoother  the RTS smoother (auxssm_kalman_smooth) beside the pathwise sampler (auxssm_kalman_sample) on the same resident filtered moments: C2's model at
              T = 65536, d = 4, fp64, 1 and 256 sequences, and T = 16384, d = 3, fp32, 64 sequences; parallel scan, at one sequence also the sequential recursion
@@ -526,6 +529,29 @@ def spatial_kalman(grid=8, T=1024, chains=(1, 16, 256), steps=50, host_reps=3):
                               delta=float(f"{delta:.3g}"), ms_per_sweep=round((time.perf_counter() - t0) / host_reps * 1e3, 2))), flush=True)
 
 
+def alternating_batches(h, calls, runs):
+    """(best, median, worst) ms per call of each of `calls`, their batches alternating: a batch is as many back-to-back calls as fill ~0.2 s and ends in a stream
+    synchronisation; `runs` batches each"""
+    reps = []
+    for call in calls:
+        for _ in range(2):
+            call()
+        h.sync()
+        t0 = time.perf_counter()
+        call()
+        h.sync()
+        reps.append(int(min(2000, max(3, 0.2 / (time.perf_counter() - t0)))))
+    ts = [[] for _ in calls]
+    for _ in range(runs):
+        for k, call in enumerate(calls):
+            t0 = time.perf_counter()
+            for _ in range(reps[k]):
+                call()
+            h.sync()
+            ts[k].append((time.perf_counter() - t0) / reps[k] * 1e3)
+    return [(min(t), float(np.median(t)), max(t)) for t in ts]
+
+
 def poisson_kalman(shapes=((250, 30), (16384, 1)), chain_counts=(1, 64, 256, 1024), runs=5, host_reps=3, N=25):
     """count data under the auxiliary Kalman sampler (kalman.PoissonModel on workloads.poisson_kalman_setup), fp32, both orders, resident chains, keyed noise, at the
     cSMC Poisson leg's shape (T = 250, dx = 30: wide-state kernels, dense layout) and at the SV general-path shape (T = 16384, dx = 1: chain-minor from 32 chains).
@@ -537,24 +563,7 @@ def poisson_kalman(shapes=((250, 30), (16384, 1)), chain_counts=(1, 64, 256, 102
     h = _lib.default_handle()
 
     def batches(calls):
-        reps = []
-        for call in calls:
-            for _ in range(2):
-                call()
-            h.sync()
-            t0 = time.perf_counter()
-            call()
-            h.sync()
-            reps.append(int(min(2000, max(3, 0.2 / (time.perf_counter() - t0)))))
-        ts = [[] for _ in calls]
-        for _ in range(runs):
-            for k, call in enumerate(calls):
-                t0 = time.perf_counter()
-                for _ in range(reps[k]):
-                    call()
-                h.sync()
-                ts[k].append((time.perf_counter() - t0) / reps[k] * 1e3)
-        return [(min(t), float(np.median(t)), max(t)) for t in ts]
+        return alternating_batches(h, calls, runs)
 
     for T, D in shapes:
         delta = 0.02 if D > 4 else 0.05
@@ -609,6 +618,88 @@ def poisson_kalman(shapes=((250, 30), (16384, 1)), chain_counts=(1, 64, 256, 102
         print(json.dumps(dict(config=f"poisson D={D} T={T}, aux-cSMC N={N} independent proposals + backward sampling, fp32, resident chains", chains=C_,
                               ms_per_sweep=round(cb, 4), ms_per_sweep_median=round(cmed, 4), sweeps_per_s=round(C_ / cb * 1e3, 1))), flush=True)
         del cc, st
+
+
+def _poisson_lin_models(T, dx, dy, order):
+    """(model, start state, delta = 1 / max_t lambda_max(Lam_t) on the simulated path)"""
+    from aux_ssm_samplers_amd.workloads import poisson_lin_setup
+    model, x, _, _ = poisson_lin_setup(T, dx, dy, order=order)
+    lam = model.grad_lam(x)[1]
+    return model, x, 1.0 / float(np.max(np.linalg.eigvalsh(lam)))
+
+
+def poisson_lin_kalman(T=16384, dx=4, dy=128, chain_counts=(1, 64, 256), runs=5, host_reps=3, prof_sweeps=10):
+    """Poisson counts through a loading matrix (kalman.PoissonLinearModel on workloads.poisson_lin_setup), fp32, both orders, dense resident chains, keyed noise,
+    step size 1 / max_t lambda_max(Lam_t) on the simulated path.  Beside every row, in the same process and in alternating batches (a batch is as many back-to-back
+    sweeps as fill ~0.2 s and ends in a stream synchronisation; best, median and worst batch of `runs`): kalman.PoissonModel at T, dx on dense chains -- the same
+    sweep without the channel reduction.  Per order the host-factory path of the new model (the same methods behind lambdas, one chain): what its users had
+    before.  Then `prof_sweeps` sweeps per chain count under the library's own event brackets (auxssm_prof_enable, all groups): `factory` is the two launches of
+    k_plin_obs and nothing else, `logpdf` the two joint densities and k_plin_terms; exp_per_s = 2 C T dy exponentials per sweep over the factory time."""
+    from aux_ssm_samplers_amd.workloads import poisson_kalman_setup
+    h = _lib.default_handle()
+
+    def batches(calls):
+        return alternating_batches(h, calls, runs)
+
+    for order in (1, 2):
+        lm, xl, delta = _poisson_lin_models(T, dx, dy, order)
+        pm, xp = poisson_kalman_setup(T, dx, order=order)
+        kernels = [get_kernel(m.dynamics_factory, m.observations_factory, m.log_likelihood_fn, True)[1] for m in (lm, pm)]
+        for C_ in chain_counts:
+            chs = [DeviceChains(h, np.repeat(x[None], C_, axis=0).astype(np.float32), chain_minor=False) for x in (xl, xp)]
+            states = [KalmanSampler(x=c, updated=None) for c in chs]
+            count = [0]
+
+            def sweep(k):
+                count[0] += 1
+                kernels[k](R.PRNGKey(count[0]), states[k], delta)
+
+            (lb, lmed, lmax), (pb, pmed, pmax) = batches([lambda: sweep(0), lambda: sweep(1)])
+            h.prof_enable(_lib.K_ALL, 64 * prof_sweeps)
+            for _ in range(prof_sweeps):
+                sweep(0)
+            h.sync()
+            groups = h.prof_read_groups()
+            h.prof_disable()
+            g_ms = {k: round(v[1] / prof_sweeps, 4) for k, v in groups.items()}
+            total = sum(g_ms.values())
+            fac = g_ms.get("factory", 0.0)
+            print(json.dumps(dict(config=f"poisson_lin_kalman T={T} dx={dx} dy={dy}, aux-Kalman order {order}, fp32, dense layout, resident chains", chains=C_,
+                                  delta=round(delta, 6), ms_per_sweep=dict(PoissonLinear=round(lb, 4), Poisson=round(pb, 4)),
+                                  ms_per_sweep_median=dict(PoissonLinear=round(lmed, 4), Poisson=round(pmed, 4)),
+                                  ms_per_sweep_worst=dict(PoissonLinear=round(lmax, 4), Poisson=round(pmax, 4)),
+                                  sweeps_per_s=dict(PoissonLinear=round(C_ / lb * 1e3, 1), Poisson=round(C_ / pb * 1e3, 1)), linear_over_pointwise_time=round(lb / pb, 3),
+                                  accept=dict(PoissonLinear=float(chs[0].accepted.to_host().mean()), Poisson=float(chs[1].accepted.to_host().mean())),
+                                  group_ms_per_sweep=g_ms, factory_share_of_groups=round(fac / total, 3) if total else None,
+                                  exp_per_s=round(2.0 * C_ * T * dy / (fac * 1e-3), 1) if fac else None)), flush=True)
+            del chs, states
+        hinit, hkernel = get_kernel(lambda x: lm.dynamics_factory(x), lambda x, u, dl: lm.observations_factory(x, u, dl), lambda x: lm.log_likelihood_fn(x), True)
+        st = hinit(xl.astype(np.float32))
+        keys = R.split(R.PRNGKey(3), host_reps + 1)
+        st = hkernel(keys[0], st, delta)
+        h.sync()
+        t0 = time.perf_counter()
+        for k in range(host_reps):
+            st = hkernel(keys[1 + k], st, delta)
+        h.sync()
+        print(json.dumps(dict(config=f"poisson_lin_kalman T={T} dx={dx} dy={dy}, aux-Kalman order {order}, fp32, host-factory path", chains=1, delta=round(delta, 6),
+                              ms_per_sweep=round((time.perf_counter() - t0) / host_reps * 1e3, 2))), flush=True)
+
+
+def poisson_lin_trace(T=16384, dx=4, dy=128, chains=64, sweeps=20):
+    """`sweeps` sweeps per order of poisson_lin_kalman's model at `chains` dense resident chains and nothing else: the process a kernel trace is taken of (per-kernel
+    times of k_plin_obs and k_plin_terms; a profile belongs in a run of its own)."""
+    h = _lib.default_handle()
+    for order in (1, 2):
+        lm, xl, delta = _poisson_lin_models(T, dx, dy, order)
+        kernel = get_kernel(lm.dynamics_factory, lm.observations_factory, lm.log_likelihood_fn, True)[1]
+        ch = DeviceChains(h, np.repeat(xl[None], chains, axis=0).astype(np.float32), chain_minor=False)
+        st = KalmanSampler(x=ch, updated=None)
+        for k in range(sweeps):
+            kernel(R.PRNGKey(k), st, delta)
+        h.sync()
+        print(json.dumps(dict(config=f"poisson_lin_trace T={T} dx={dx} dy={dy} order {order}", chains=chains, sweeps=sweeps, delta=round(delta, 6),
+                              exp_per_sweep=2 * chains * T * dy, accept=float(ch.accepted.to_host().mean()))), flush=True)
 
 
 def smoother(runs=5):
@@ -677,6 +768,10 @@ if __name__ == "__main__":
         smoother()
     if "poisson_kalman" in which:
         poisson_kalman()
+    if "poisson_lin_kalman" in which:
+        poisson_lin_kalman()
+    if "poisson_lin_trace" in which:
+        poisson_lin_trace()
     if "sv30" in which:
         sv30()
     if "guided" in which:
