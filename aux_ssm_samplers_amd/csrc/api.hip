@@ -549,7 +549,8 @@ template <typename R> __global__ void k_concat_carrier(int T, int D, int P, Arr 
 }
 
 // ---- the host side the Kalman sweep drivers share --------------------------------------------------------------------------------------------
-// One sweep call, as the entry points hand it to sweep_lg_concat, sweep_lg_concat_fused, sweep_sv and sweep_lorenz
+// One sweep call, as the entry points hand it to the drivers: sweep_lg_concat, sweep_lg_concat_fused, sweep_ss (SV, Poisson, Poisson-linear), sweep_mvt and
+// sweep_lorenz.  Which driver a model kind runs, with which order and potential, is KMODELS' to say (below, before kalman_sweep_impl)
 struct SweepCall {
     auxssm_ctx* h;
     int dtype;
@@ -564,8 +565,8 @@ struct SweepCall {
     const void *eps_aux, *eps_samp, *u_acc;
     int32_t* accepted;
     void* logs;
-    int order = 0;          // sweep_sv: 1 or 2
-    int kind = 0;           // sweep_sv: the pointwise potential (kalman_bodies.h::PwKind)
+    int order = 0;          // the model kind's row: 1 or 2 where the family has orders
+    int kind = 0;           // the model kind's row: the pointwise potential (kalman_bodies.h::PwKind)
     void* x_alt = nullptr;  // sweep_lg_concat_fused: the second state buffer and the lazy state's selector
     int32_t* sel = nullptr;
     int cm() const { return layout == AUXSSM_LAYOUT_CHAIN_MINOR ? 1 : 0; }
@@ -586,8 +587,17 @@ struct SweepViews {
     KDims kd;
     Arr operator()(const void* p, long long rec) const { return cm ? cm_arr(p, kd, rec) : dense_arr(p, kd, rec); }
 };
+// the end of one stage of a sweep (a filter, the sampler, a log-density pass): its status, and -- if it ran -- the workspace back at the sweep's own buffers (mark)
+struct StageEnd {
+    auxssm_ctx* h;
+    size_t mark;
+    int operator()(int rc) const {
+        if (!rc) h->ws_off = mark;
+        return rc;
+    }
+};
 
-// bytes of the side slab of a model stage (ctx.h::SideStage) of sweep_lg_concat and sweep_sv: per time step the `own` reals the driver itself takes there
+// bytes of the side slab of a model stage (ctx.h::SideStage) of sweep_lg_concat and sweep_ss: per time step the `own` reals the driver itself takes there
 // (its observation model), the shared covariances, what run_filter_shared takes (mask, gain rows, two sets of scan elements) and the sampler's / log-density's
 // tables; + chunk products
 static size_t side_stage_bytes(size_t sR, int T, size_t D, size_t P, size_t PO, size_t own) {
@@ -740,7 +750,7 @@ template <typename R> static int sweep_lg_concat(const SweepCall& c) {
     ws.after(wide ? wide_logpdf_ws(dtype, kd) : sl->ws(h, kd));
     int rc = ws.reserve(h);
     if (rc) return rc;
-    const size_t mark = h->ws_off;
+    const StageEnd done{h, h->ws_off};
     // Chain-shared sweep with a host step size: the MODEL STAGE (concatenated observation model here, matrix filter + gain table in
     // run_filter_shared) reads neither a chain nor anything the previous sweep wrote, so it goes to the side stream with its own double-buffered
     // slab (ctx.h::SideStage) and overlaps the chain passes of the sweep before; its products -- Hc, Rc, cc, the shared covariances, the gain
@@ -794,25 +804,19 @@ template <typename R> static int sweep_lg_concat(const SweepCall& c) {
         hipLaunchKernelGGL((k_concat_carrier<R>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, T, D, P, cv(*c.yobs), carrier);
         fa.mask_ys = Arr{carrier, 0, (long long)P, 0, 1};
     }
-    rc = ke->filter(h, fa, parallel, ell);
-    if (rc) return rc;
-    h->ws_off = mark;
+    if ((rc = done(ke->filter(h, fa, parallel, ell)))) return rc;
     SampleArgs sa;
     fill_sample_args(sa, kd, D, cv(model->Fs), cv(model->Qs), cv(model->bs), msA, PsA, epsA, xpA, cm);
     // the filtered covariances of this model do not depend on the chain when its parameters do not
     sa.ps_shared = shared_mode ? 1 : 0;
     sa.ps_packed = ps_pack ? 1 : 0;
     if (gen) sa.eps_gen = 1, sa.gen_k0 = keys[2], sa.gen_k1 = keys[3];
-    rc = se->sample(h, sa, parallel);
-    if (rc) return rc;
-    h->ws_off = mark;
+    if ((rc = done(se->sample(h, sa, parallel)))) return rc;
 
     // all proposal / target log-densities and the MH correction in one pass (generic.py:88-89, :103-105)
     SweepLogpdfArgs la;
     fill_sweep_logpdf_args(la, c, kd, *model, cv(*c.yobs), xA, xpA, uA, aux_fly ? 1 : 0, epsauxA);
-    rc = sl->run(h, la, sums);
-    if (rc) return rc;
-    h->ws_off = mark;
+    if ((rc = done(sl->run(h, la, sums)))) return rc;
     launch_accept<R>(c, sums, ell, ell);
     if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)c.accepted, xpA, xA, cm))) return rc;
     AX_HIP(hipGetLastError());
@@ -1140,15 +1144,72 @@ __global__ void k_sv_accept(int C, const R* j1, const R* j2, const R* ell1, cons
     }
 }
 
-// kernel(key, state, delta) of kalman/generic.py:53-76 with the SV factories: both linearisation points (x for the proposal,
+// ---- the two factories of state-space pseudo-observations: what sweep_ss asks of a model family -------------------------------------------------------
+// plan: the factory's own buffers; obs: the pseudo-observations ys (second order: and their covariances Rs) linearised at xlin -- eps: the noise that forms u
+// on the way, or null when u exists (the reverse move); terms [5][C]: pot(x'), pot(x), the two auxiliary log-likelihoods and the correction, for k_sv_accept.
+// one_pass: the register path has every log-density of the ratio in one kernel (SampleEntry::sv_logpdf), which is then taken instead of the joints + terms.
+
+// f(the pointwise potential as a compile-time constant)
+template <typename F> static void by_pointwise(int kind, F&& f) {
+    if (kind == PW_POISSON) f(std::integral_constant<int, PW_POISSON>{});
+    else f(std::integral_constant<int, PW_SV>{});
+}
+// SV_* / POISSON_*: log g_t = sum_k f(y_tk, x_tk), a diagonal Hessian (k_sv_obs, k_sv_terms above); every layout and width
+template <typename R> struct PointwiseFactory {
+    static constexpr bool one_pass = true;
+    void plan(WsPlan&, const SweepCall&) {}
+    int obs(const SweepCall& c, const R* xlin, const R* eps, R* u, R* ys, R* Rs) {
+        const int C = c.dims->C, T = c.dims->T, D = c.dims->dx;
+        const long long tot = (long long)C * T * D;
+        by_pointwise(c.kind, [&](auto kind) {
+            hipLaunchKernelGGL((k_sv_obs<R, decltype(kind)::value>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c.h->stream, tot, C, T, D, c.order, c.cm(), xlin, eps,
+                               eps ? (R)c.shd() : (R)0, (R)c.delta, c.dptr, cv(*c.yobs), u, ys, Rs);
+        });
+        return AUXSSM_OK;
+    }
+    int terms(const SweepCall& c, const R* xp, const R* u, const R* ys1, const R* ys2, const R* Rs1, const R* Rs2, R* out) {
+        const int C = c.dims->C;
+        by_pointwise(c.kind, [&](auto kind) {
+            hipLaunchKernelGGL((k_sv_terms<R, decltype(kind)::value>), dim3(C), dim3(256), 0, c.h->stream, C, c.dims->T, c.dims->dx, (R)c.delta, c.dptr, (const R*)c.x, xp, u,
+                               cv(*c.yobs), ys1, ys2, Rs1, Rs2, out);
+        });
+        return AUXSSM_OK;
+    }
+};
+// POISSON_LIN_*: Poisson counts behind a loading matrix, y_{t,j} ~ Poisson(exp(h_j' x_t + c_j)), j = 1..dy (model->Hs = H (dy, dx) row-major, model->cs = c (dy)):
+// kalman_plin.hip's reduction over the channels; second order gives every (chain, step) its own dense R = Omega_t.  The dense layout and dx <= 4 only (refused
+// before the driver: plin_limits), so the sweep is sweep_ss's dense, materialised form on the register kernels whatever dy is.
+template <typename R> struct PlinFactory {
+    static constexpr bool one_pass = false;
+    Acc *pot1, *pot2, *part;  // the potential per (chain, step) at either linearisation point, as obs leaves it for terms
+    void plan(WsPlan& ws, const SweepCall& c) {
+        const size_t CT = (size_t)c.dims->C * c.dims->T;
+        ws.add(pot1, CT * sizeof(Acc));
+        ws.add(pot2, CT * sizeof(Acc));
+        ws.add(part, plin_terms_part_bytes(c.dims->C, c.dims->T));
+    }
+    int obs(const SweepCall& c, const R* xlin, const R* eps, R* u, R* ys, R* Rs) {
+        const PlinObsArgs oa{c.dims->C, c.dims->T, c.dims->dx, c.dims->dy, c.order, c.delta, c.dptr, c.model->Hs.ptr, c.model->cs.ptr, c.yobs->ptr, (long long)c.yobs->st,
+                             xlin, eps, u, ys, Rs, eps ? pot1 : pot2};
+        return run_plin_obs(c.h, c.dtype, oa);
+    }
+    int terms(const SweepCall& c, const R* xp, const R* u, const R* ys1, const R* ys2, const R* Rs1, const R* Rs2, R* out) {
+        ProfScope ps(c.h, AUXSSM_K_LOGPDF);
+        const PlinTermsArgs ta{c.dims->C, c.dims->T, c.dims->dx, c.delta, c.dptr, c.x, xp, u, ys1, ys2, Rs1, Rs2, pot1, pot2, part, out};
+        return run_plin_terms(c.h, c.dtype, ta);
+    }
+};
+
+// kernel(key, state, delta) of kalman/generic.py:53-76 for the models whose auxiliary observation set lives in the state space (H = I, c = 0, R = delta/2 I or
+// Omega_t: the first- / second-order factories of examples/stochastic_volatility/auxiliary_kalman.py:22-48): both linearisation points (x for the proposal,
 // x_prop for the reverse move) get their own observation set and filter pass, as in the reference.
-template <typename R> static int sweep_sv(const SweepCall& c) {
+template <typename R, typename Factory> static int sweep_ss(const SweepCall& c) {
     auxssm_ctx* h = c.h;
     const auxssm_lgssm* model = c.model;
     const auxssm_arr* yobs = c.yobs;
     const int dtype = c.dtype, order = c.order, parallel = c.parallel, nan_policy = c.nan_policy;
-    const bool pois = c.kind == PW_POISSON;
     const double delta = c.delta;
+    Factory fac{};
     const double* dptr = c.dptr;
     void* x = c.x;
     const int C = c.dims->C, T = c.dims->T, D = c.dims->dx;
@@ -1174,7 +1235,7 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
     const bool fly = cm && !wide && T > 1 && !ps_shared;
     const bool wide_carrier = wide && !second && C >= 2 && h->share_model;  // (below: the observation pattern said to the chain-shared wide filter)
     R *u, *ys1, *ys2, *xp, *Rs1 = nullptr, *Rs2 = nullptr, *ms, *Ps, *eye, *Rc, *zero, *sc, *wide_mask = nullptr;
-    Acc* sums;
+    Acc* sums = nullptr;
     void* wide_gtab = nullptr;
     WsPlan ws;
     ws.add(u, CT * D * sR);
@@ -1183,25 +1244,24 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
     if (second && !fly) ws.add(Rs1, CT * D * D * sR), ws.add(Rs2, CT * D * D * sR);
     ws.add(ms, CT * D * sR);
     ws.add(Ps, CT * D * D * sR);
+    fac.plan(ws, c);
     ws.add(eye, (size_t)D * D * sR);
     ws.add(Rc, (size_t)D * D * sR);
     ws.add(zero, (size_t)D * sR);
     ws.add(sc, (size_t)16 * C * sR);
-    ws.add(sums, (size_t)5 * C * sizeof(Acc));
+    if (Factory::one_pass) ws.add(sums, (size_t)5 * C * sizeof(Acc));  // (its totals, and the wide path's shared joints)
     if (wide_carrier) {
         ws.add(wide_mask, (size_t)T * D * sR);
         ws.add(wide_gtab, wide_gain_tab_bytes(dtype, T, D, D));  // the gain rows: built by the proposal filter, reused by the reverse filter
     }
     ws.after(wide ? wide_filter_ws(h, dtype, kd, parallel, D, D) : ke->filter_ws(h, kd, parallel));
     ws.after(wide ? wide_sample_ws(h, dtype, kd, parallel, D) : se->sample_ws(h, kd, parallel));
-    ws.after(wide ? wide_logpdf_ws(dtype, kd) : std::max(ke->logpdf_ws(h, kd), se->sv_logpdf_ws(h, kd)));
+    ws.after(wide ? wide_logpdf_ws(dtype, kd) : Factory::one_pass ? std::max(ke->logpdf_ws(h, kd), se->sv_logpdf_ws(h, kd)) : ke->logpdf_ws(h, kd));
     int rc = ws.reserve(h);
     if (rc) return rc;
     if (fly) ys1 = ys2 = u;  // (never read)
     R* ell1 = sc; R* ell2 = sc + C; R* j1 = sc + 2 * C; R* j2 = sc + 3 * C; R* terms = sc + 4 * C;
-    const size_t mark = h->ws_off;
-    const long long tot = (long long)CT * D;
-    const unsigned gb = (unsigned)((tot + 255) / 256);
+    const StageEnd done{h, h->ws_off};
     const Arr xA = view(x, D), xpA = view(xp, D), uA = view(u, D), y1A = view(ys1, D), y2A = view(ys2, D);
     const Arr R1A = Rs1 ? view(Rs1, (long long)D * D) : Arr{nullptr, 0, 0, 0, 1};
     const Arr R2A = Rs2 ? view(Rs2, (long long)D * D) : Arr{nullptr, 0, 0, 0, 1};
@@ -1261,7 +1321,7 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
     // u exists), the mask carrier and the buffer the chain-shared wide filter leaves its gain rows in (pc)
     auto filter_args = [&](FilterArgs& fa, const auxssm_lgssm& g, const Arr& ys, const Arr& Rs, const Arr& xlin, const Arr& eps) {
         sweep_filter_args(fa, dc, g, ys, view(ms, D), PsA, cm);
-        if (second) fa.Rs = Rs;
+        if (second && Factory::one_pass) fa.Rs = Rs;  // (the layout's view of the per-chain covariances; a dense-only factory keeps g's own description of them)
         if (fly) {
             fa.sv_order = order;
             fa.sv_kind = c.kind;
@@ -1272,33 +1332,22 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
         if (wide_ps_once && wide_gtab) fa.pc = wide_gtab;
     };
 
-    // the pseudo-observations (second order: and their covariances) linearised at xlin; eps: the noise that forms u, or none when u exists
-    auto launch_obs = [&](const R* xlin, const R* eps, R shd, R* ys, R* Rs) {
-        if (pois)
-            hipLaunchKernelGGL((k_sv_obs<R, PW_POISSON>), dim3(gb), dim3(256), 0, h->stream, tot, C, T, D, order, cm, xlin, eps, shd, (R)delta, dptr, cv(*yobs), u, ys, Rs);
-        else
-            hipLaunchKernelGGL((k_sv_obs<R, PW_SV>), dim3(gb), dim3(256), 0, h->stream, tot, C, T, D, order, cm, xlin, eps, shd, (R)delta, dptr, cv(*yobs), u, ys, Rs);
-    };
-    // proposal: observations linearised at x, filter, pathwise sample (generic.py:80-86)
+    // proposal: observations linearised at x (u formed on the way), filter, pathwise sample (generic.py:80-86)
     if (!fly) {
         ProfScope ps(h, AUXSSM_K_FACTORY);
-        launch_obs((const R*)x, (const R*)c.eps_aux, (R)c.shd(), ys1, Rs1);
+        if ((rc = fac.obs(c, (const R*)x, (const R*)c.eps_aux, u, ys1, Rs1))) return rc;
     }
     FilterArgs fa;
     filter_args(fa, g1, y1A, R1A, xA, view(c.eps_aux, D));
-    rc = ke->filter(h, fa, parallel, ell1);
-    if (rc) return rc;
-    h->ws_off = mark;
+    if ((rc = done(ke->filter(h, fa, parallel, ell1)))) return rc;
     SampleArgs sa;
     fill_sample_args(sa, kd, D, cv(model->Fs), cv(model->Qs), cv(model->bs), view(ms, D), PsA, view(c.eps_samp, D), xpA, cm);
     sa.ps_shared = cm ? ps_shared : 0;
-    rc = se->sample(h, sa, parallel);
-    if (rc) return rc;
-    h->ws_off = mark;
+    if ((rc = done(se->sample(h, sa, parallel)))) return rc;
     // reverse move: observations linearised at x_prop, filter for its marginal likelihood (generic.py:67)
     if (!fly) {
         ProfScope ps(h, AUXSSM_K_FACTORY);
-        launch_obs((const R*)xp, (const R*)nullptr, (R)0, ys2, Rs2);
+        if ((rc = fac.obs(c, (const R*)xp, (const R*)nullptr, u, ys2, Rs2))) return rc;
     }
     FilterArgs fr;
     filter_args(fr, g2, y2A, R2A, xpA, Arr{nullptr, 0, 0, 0, 1});
@@ -1310,10 +1359,8 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
     // wide states: same model, same step size, same pattern -- pc holds the proposal filter's covariances and gain rows (if it took the shared form: it does
     // whenever this one would -- same sizes, same strides)
     if (wide_ps_once && wide_gtab && parallel && T >= 5) fr.tab_ready = 1;
-    rc = ke->filter(h, fr, parallel, ell2);
-    if (rc) return rc;
-    h->ws_off = mark;
-    if (!wide) {
+    if ((rc = done(ke->filter(h, fr, parallel, ell2)))) return rc;
+    if (!wide && Factory::one_pass) {
         // every log-density of the MH ratio in one pass over the chains (generic.py:88-89, :98-106)
         SvLogpdfArgs la;
         la.d = kd;
@@ -1324,12 +1371,10 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
         la.dptr = dptr;
         la.fly_order = fly ? order : 0;
         la.kind = c.kind;
-        rc = se->sv_logpdf(h, la, sums);  // [5][C] = jp_prop, jp_rev, lt_prop, lt_rev, corr
-        if (rc) return rc;
-        h->ws_off = mark;
+        if ((rc = done(se->sv_logpdf(h, la, sums)))) return rc;  // [5][C] = jp_prop, jp_rev, lt_prop, lt_rev, corr
         launch_accept<R>(c, sums, ell1, ell2);
     } else {
-        // wide-state path: joint log-densities of both auxiliary models (posterior_logpdf + ell, base.py:72-96), then the SV terms
+        // wide-state path, or a factory without that pass: joint log-densities of both auxiliary models (posterior_logpdf + ell, base.py:72-96), then its terms
         bool both = false;
         const SweepLogpdfEntry* wsl = wide_sweep_logpdf_entry(dtype);
         if (wide_ps_once && nan_policy == AUXSSM_NAN_REFERENCE && wsl && wsl->wide_shared) {
@@ -1345,25 +1390,17 @@ template <typename R> static int sweep_sv(const SweepCall& c) {
             } else if (rc != 1) {
                 return rc;
             }
-            h->ws_off = mark;
+            h->ws_off = done.mark;
         }
         if (!both) {
+            // (the pointwise sweep describes its pseudo-observations to the joints with batch stride 0, a dense-only factory with the dense view's: one batch)
             LogpdfArgs la;
-            fill_logpdf_args(la, &dc, &g1, cv(y1d), dense_arr(xp, kd, D), nan_policy);
-            rc = ke->logpdf(h, la, j1);
-            if (rc) return rc;
-            h->ws_off = mark;
-            fill_logpdf_args(la, &dc, &g2, cv(y2d), dense_arr(x, kd, D), nan_policy);
-            rc = ke->logpdf(h, la, j2);
-            if (rc) return rc;
-            h->ws_off = mark;
+            fill_logpdf_args(la, &dc, &g1, Factory::one_pass ? cv(y1d) : y1A, dense_arr(xp, kd, D), nan_policy);
+            if ((rc = done(ke->logpdf(h, la, j1)))) return rc;
+            fill_logpdf_args(la, &dc, &g2, Factory::one_pass ? cv(y2d) : y2A, dense_arr(x, kd, D), nan_policy);
+            if ((rc = done(ke->logpdf(h, la, j2)))) return rc;
         }
-        if (pois)
-            hipLaunchKernelGGL((k_sv_terms<R, PW_POISSON>), dim3(C), dim3(256), 0, h->stream, C, T, D, (R)delta, dptr, (const R*)x, (const R*)xp, (const R*)u,
-                               cv(*yobs), (const R*)ys1, (const R*)ys2, (const R*)Rs1, (const R*)Rs2, terms);
-        else
-            hipLaunchKernelGGL((k_sv_terms<R, PW_SV>), dim3(C), dim3(256), 0, h->stream, C, T, D, (R)delta, dptr, (const R*)x, (const R*)xp, (const R*)u,
-                               cv(*yobs), (const R*)ys1, (const R*)ys2, (const R*)Rs1, (const R*)Rs2, terms);
+        if ((rc = fac.terms(c, (const R*)xp, (const R*)u, (const R*)ys1, (const R*)ys2, (const R*)Rs1, (const R*)Rs2, terms))) return rc;
         hipLaunchKernelGGL((k_sv_accept<R>), dim3((C + 127) / 128), dim3(128), 0, h->stream, C, (const R*)j1, (const R*)j2, (const R*)ell1,
                            (const R*)ell2, (const R*)terms, (const R*)c.u_acc, c.accepted, (R*)c.logs);
     }
@@ -1392,102 +1429,6 @@ template <typename R> static int sweep_mvt(const SweepCall& c) {
     if ((rc = run_mvt(h, c.dtype, a))) return rc;
     launch_accept<R>(c, sums, ell0, ell0);
     if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)c.accepted, dense_arr(xp, kd, D), dense_arr(c.x, kd, D), 0))) return rc;
-    AX_HIP(hipGetLastError());
-    return AUXSSM_OK;
-}
-
-// AUXSSM_KMODEL_POISSON_LIN_FIRST / _SECOND: Poisson counts behind a loading matrix, y_{t,j} ~ Poisson(exp(h_j' x_t + c_j)), j = 1..dy (model->Hs = H (dy, dx)
-// row-major, model->cs = c (dy)).  sweep_sv's dense, materialised form with the factory and the terms of kalman_plin.hip: the pseudo-observations live in the
-// state space, so both filters, the sampler and the two joint densities are the dx <= 4 register kernels whatever dy is; second order gives every (chain, step)
-// its own dense R = Omega_t.
-template <typename R> static int sweep_plin(const SweepCall& c) {
-    auxssm_ctx* h = c.h;
-    const auxssm_lgssm* model = c.model;
-    const int dtype = c.dtype, parallel = c.parallel;
-    const int C = c.dims->C, T = c.dims->T, D = c.dims->dx, PO = c.dims->dy;
-    const bool second = c.order == 2;
-    const KalmanEntry* ke = need_kalman(dtype, D, D);
-    const SampleEntry* se = sample_entry(dtype, D);
-    if (!ke || !se) return AUXSSM_ERR_UNSUPPORTED;
-    const KDims kd{C, T, 1};
-    const size_t sR = sizeof(R), CT = (size_t)C * T;
-    R *u, *ys1, *ys2, *xp, *Rs1 = nullptr, *Rs2 = nullptr, *ms, *Ps, *eye, *Rc, *zero, *sc;
-    Acc *pot1, *pot2, *part;
-    WsPlan ws;
-    ws.add(u, CT * D * sR);
-    ws.add(ys1, CT * D * sR);
-    ws.add(ys2, CT * D * sR);
-    ws.add(xp, CT * D * sR);
-    if (second) ws.add(Rs1, CT * D * D * sR), ws.add(Rs2, CT * D * D * sR);
-    ws.add(ms, CT * D * sR);
-    ws.add(Ps, CT * D * D * sR);
-    ws.add(pot1, CT * sizeof(Acc));
-    ws.add(pot2, CT * sizeof(Acc));
-    ws.add(part, plin_terms_part_bytes(C, T));
-    ws.add(eye, (size_t)D * D * sR);
-    ws.add(Rc, (size_t)D * D * sR);
-    ws.add(zero, (size_t)D * sR);
-    ws.add(sc, (size_t)16 * C * sR);
-    ws.after(ke->filter_ws(h, kd, parallel));
-    ws.after(se->sample_ws(h, kd, parallel));
-    ws.after(ke->logpdf_ws(h, kd));
-    int rc = ws.reserve(h);
-    if (rc) return rc;
-    R* ell1 = sc; R* ell2 = sc + C; R* j1 = sc + 2 * C; R* j2 = sc + 3 * C; R* terms = sc + 4 * C;
-    const size_t mark = h->ws_off;
-    hipLaunchKernelGGL((k_scaled_eye<R>), dim3((D * D + 255) / 256), dim3(256), 0, h->stream, D, (R)1, eye);
-    hipLaunchKernelGGL((k_fill<R>), dim3(1), dim3(256), 0, h->stream, (long long)D, (R)0, zero);
-    if (!second) hipLaunchKernelGGL((k_scaled_eye<R>), dim3((D * D + 255) / 256), dim3(256), 0, h->stream, D, (R)(0.5 * c.delta), Rc, c.dptr);
-    AX_HIP(hipGetLastError());
-    // observation LGSSMs of the two linearisation points (H = I, c = 0; R = delta/2 I or the per-step dense Omega)
-    auxssm_lgssm g1 = *model;
-    g1.Hs = auxssm_arr{eye, 0, 0, 0};
-    g1.cs = auxssm_arr{zero, 0, 0, 0};
-    g1.Rs = second ? auxssm_arr{Rs1, (int64_t)T * D * D, (int64_t)D * D, 0} : auxssm_arr{Rc, 0, 0, 0};
-    auxssm_lgssm g2 = g1;
-    if (second) g2.Rs = auxssm_arr{Rs2, (int64_t)T * D * D, (int64_t)D * D, 0};
-    auxssm_dims dc = *c.dims;
-    dc.dy = D;
-    dc.B = 1;
-    const Arr xA = dense_arr(c.x, kd, D), xpA = dense_arr(xp, kd, D), y1A = dense_arr(ys1, kd, D), y2A = dense_arr(ys2, kd, D);
-    const Arr msA = dense_arr(ms, kd, D), PsA = dense_arr(Ps, kd, (long long)D * D);
-    auto launch_obs = [&](const R* xlin, const R* eps, R* ys, R* Rs, Acc* pot) {
-        ProfScope ps(h, AUXSSM_K_FACTORY);
-        const PlinObsArgs oa{C, T, D, PO, c.order, c.delta, c.dptr, model->Hs.ptr, model->cs.ptr, c.yobs->ptr, (long long)c.yobs->st, xlin, eps, u, ys, Rs, pot};
-        return run_plin_obs(h, dtype, oa);
-    };
-    // proposal: observations linearised at x (u formed on the way), filter, pathwise sample (generic.py:80-86)
-    if ((rc = launch_obs((const R*)c.x, (const R*)c.eps_aux, ys1, Rs1, pot1))) return rc;
-    FilterArgs fa;
-    sweep_filter_args(fa, dc, g1, y1A, msA, PsA, 0);
-    if ((rc = ke->filter(h, fa, parallel, ell1))) return rc;
-    h->ws_off = mark;
-    SampleArgs sa;
-    fill_sample_args(sa, kd, D, cv(model->Fs), cv(model->Qs), cv(model->bs), msA, PsA, dense_arr(c.eps_samp, kd, D), xpA, 0);
-    if ((rc = se->sample(h, sa, parallel))) return rc;
-    h->ws_off = mark;
-    // reverse move: observations linearised at x', filter for its marginal likelihood (generic.py:67)
-    if ((rc = launch_obs((const R*)xp, (const R*)nullptr, ys2, Rs2, pot2))) return rc;
-    FilterArgs fr;
-    sweep_filter_args(fr, dc, g2, y2A, msA, PsA, 0);
-    if ((rc = ke->filter(h, fr, parallel, ell2))) return rc;
-    h->ws_off = mark;
-    // joint log-densities of both auxiliary models (posterior_logpdf + ell, base.py:72-96), as sweep_sv's wide branch takes them
-    LogpdfArgs la;
-    fill_logpdf_args(la, &dc, &g1, y1A, xpA, c.nan_policy);
-    if ((rc = ke->logpdf(h, la, j1))) return rc;
-    h->ws_off = mark;
-    fill_logpdf_args(la, &dc, &g2, y2A, xA, c.nan_policy);
-    if ((rc = ke->logpdf(h, la, j2))) return rc;
-    h->ws_off = mark;
-    {
-        ProfScope ps(h, AUXSSM_K_LOGPDF);
-        const PlinTermsArgs ta{C, T, D, c.delta, c.dptr, c.x, xp, u, ys1, ys2, Rs1, Rs2, pot1, pot2, part, terms};
-        if ((rc = run_plin_terms(h, dtype, ta))) return rc;
-    }
-    hipLaunchKernelGGL((k_sv_accept<R>), dim3((C + 127) / 128), dim3(128), 0, h->stream, C, (const R*)j1, (const R*)j2, (const R*)ell1, (const R*)ell2,
-                       (const R*)terms, (const R*)c.u_acc, c.accepted, (R*)c.logs);
-    if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)c.accepted, xpA, xA, 0))) return rc;
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;
 }
@@ -1556,7 +1497,7 @@ template <typename R> static int sweep_lorenz(const SweepCall& c) {
     int rc = ws.reserve(h);
     if (rc) return rc;
     R* ell1 = sc; R* ell2 = sc + C;
-    const size_t mark = h->ws_off;
+    const StageEnd done{h, h->ws_off};
     const R* par = (const R*)model->Fs.ptr;  // [theta1, theta2, theta3, dt], chain stride model->Fs.sc (0 = one theta for all chains)
     const long long psc = model->Fs.sc;
     const Arr xA = view(c.x, D), xpA = view(xp, D), uA = view(u, D), yscA = view(ysc, P), epsauxA = view(c.eps_aux, D);
@@ -1592,14 +1533,10 @@ template <typename R> static int sweep_lorenz(const SweepCall& c) {
     }
     FilterArgs fa;
     filter_args(fa, g1, F1A, b1A);
-    rc = ke->filter(h, fa, parallel, ell1);
-    if (rc) return rc;
-    h->ws_off = mark;
+    if ((rc = done(ke->filter(h, fa, parallel, ell1)))) return rc;
     SampleArgs sa;
     fill_sample_args(sa, kd, D, cm ? F1A : cv(g1.Fs), cv(model->Qs), cm ? b1A : cv(g1.bs), view(ms, D), view(Ps, (long long)D * D), view(c.eps_samp, D), xpA, cm);
-    rc = se->sample(h, sa, parallel);
-    if (rc) return rc;
-    h->ws_off = mark;
+    if ((rc = done(se->sample(h, sa, parallel)))) return rc;
     // reverse move: dynamics linearised at x_prop (generic.py:67)
     if (T > 1) {
         ProfScope ps(h, AUXSSM_K_FACTORY);
@@ -1607,21 +1544,134 @@ template <typename R> static int sweep_lorenz(const SweepCall& c) {
     }
     FilterArgs fr;
     filter_args(fr, g2, F2A, b2A);
-    rc = ke->filter(h, fr, parallel, ell2);
-    if (rc) return rc;
-    h->ws_off = mark;
+    if ((rc = done(ke->filter(h, fr, parallel, ell2)))) return rc;
     // every log-density of the MH ratio in one pass (generic.py:88-89, :98-106); the linearised transitions are rebuilt from x / x_prop
     SweepLogpdfArgs la;
     fill_sweep_logpdf_args(la, c, kd, *model, cv(*c.yobs), xA, xpA, uA, aux_fly ? 1 : 0, epsauxA);
     la.Fs = Arr{nullptr, 0, 0, 0, 1}; la.bs = Arr{nullptr, 0, 0, 0, 1};
     la.lor_par = par; la.lor_psc = psc;
-    rc = sl->lorenz(h, la, sums);
-    if (rc) return rc;
-    h->ws_off = mark;
+    if ((rc = done(sl->lorenz(h, la, sums)))) return rc;
     launch_accept<R>(c, sums, ell1, ell2);
     if ((rc = launch_select<R>(h, C, T, D, (const int32_t*)c.accepted, xpA, xA, cm))) return rc;
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;
+}
+
+// ---- the model kinds of the auxiliary Kalman sweep: one table ------------------------------------------------------------------------------------------
+// A family is what its kinds have in common: args, what the model's slots must hold; limits (or null), what the driver covers -- refused before anything is
+// enqueued; the driver; and two facts kalman_sweep_impl acts on -- obs_model: Hs / Rs / cs are a real observation model, which the chains share
+// (check_sweep_common); noise_arrays: the driver reads its noise from the arrays, so a keyed call draws all of it first (auxssm_kalman_draw).
+// A kind is a family at an order (0: the family has none) with, where the family has one, a pointwise potential.  A new kind is a row of KMODELS; a new family is
+// its checks, a driver -- for pseudo-observations in the state space a factory of sweep_ss -- and a SweepFamily.  Values missing from KMODELS are unknown kinds.
+struct SweepFamily {
+    bool obs_model, noise_arrays;
+    int (*args)(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs);
+    int (*limits)(const auxssm_dims* dims, int layout, int nan_policy);
+    int (*driver)(const SweepCall& c);
+};
+#define AX_SWEEP_DRIVER(...) [](const SweepCall& c) -> int { return by_dtype(c.dtype, [&](auto r) { using R = decltype(r); return __VA_ARGS__(c); }); }
+
+static bool prior_and_dynamics(const auxssm_dims* dims, const auxssm_lgssm* m) {
+    return m && m->m0.ptr && m->P0.ptr && (dims->T <= 1 || (m->Fs.ptr && m->Qs.ptr && m->bs.ptr));
+}
+static int lg_concat_args(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr*) { return check_lgssm(model, dims->T); }
+static int pointwise_args(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr*) {
+    if (!prior_and_dynamics(dims, model)) {
+        set_error("model needs m0, P0 (and Fs, Qs, bs with T > 1)");
+        return AUXSSM_ERR_ARG;
+    }
+    if (dims->dy != dims->dx) {
+        set_error("stochastic-volatility models observe every state component: dy (%d) must equal dx (%d)", dims->dy, dims->dx);
+        return AUXSSM_ERR_ARG;
+    }
+    return AUXSSM_OK;
+}
+static int lorenz_args(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr*) {
+    if (!model || !model->m0.ptr || !model->P0.ptr || !model->Fs.ptr || !model->Qs.ptr || !model->Hs.ptr || !model->Rs.ptr || !model->cs.ptr) {
+        set_error("Lorenz model needs m0, P0, Fs (= [theta1, theta2, theta3, dt] on the device), Qs, Hs, Rs, cs");
+        return AUXSSM_ERR_ARG;
+    }
+    if (dims->dx != 3 || dims->dy < 1 || dims->dy > 3) {
+        set_error("Lorenz-63 has dx = 3 and 1..3 observed combinations (got dx=%d, dy=%d)", dims->dx, dims->dy);
+        return AUXSSM_ERR_ARG;
+    }
+    return AUXSSM_OK;
+}
+static int mvt_args(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr*) {
+    if (!model || !model->m0.ptr || !model->P0.ptr || !model->Fs.ptr || !model->Qs.ptr || !model->bs.ptr || !model->Rs.ptr || !model->cs.ptr) {
+        set_error("multivariate-t model needs m0, P0, Fs, Qs, bs as (dx) vectors, Rs (= prec (dx, dx) on the device) and cs (= [nu] on the device)");
+        return AUXSSM_ERR_ARG;
+    }
+    if (dims->dy != dims->dx) {
+        set_error("the multivariate-t model observes every state component: dy (%d) must equal dx (%d)", dims->dy, dims->dx);
+        return AUXSSM_ERR_ARG;
+    }
+    return AUXSSM_OK;
+}
+static int mvt_limits(const auxssm_dims* dims, int layout, int nan_policy) {
+    if (dims->dx > 64) {
+        set_error("the batched multivariate-t sweep covers dx <= 64 (one wave per time step, lane = component): got dx = %d", dims->dx);
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    if (layout != AUXSSM_LAYOUT_DENSE) {
+        set_error("the batched multivariate-t sweep (dx <= 64) takes the dense (C, T, dx) layout only");
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    if (nan_policy != AUXSSM_NAN_REFERENCE) {
+        set_error("the batched multivariate-t sweep runs nan_policy 0 (reference) only: its sequences observe one scalar, which the reference's nansum drops alone");
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    return AUXSSM_OK;
+}
+static int plin_args(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs) {
+    if (!prior_and_dynamics(dims, model) || !model->Hs.ptr || !model->cs.ptr || !yobs || !yobs->ptr) {
+        set_error("Poisson-linear model needs m0, P0 (and Fs, Qs, bs with T > 1), Hs (= H (dy, dx) row-major on the device), cs (= c (dy) on the device) and yobs (T, dy)");
+        return AUXSSM_ERR_ARG;
+    }
+    return AUXSSM_OK;
+}
+static int plin_limits(const auxssm_dims* dims, int layout, int) {
+    if (dims->dx > MAX_D) {
+        set_error("the Poisson-linear sweep covers dx <= %d (the register kernels): got dx = %d", MAX_D, dims->dx);
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    if (dims->dy > PLIN_MAX_DY) {
+        set_error("the Poisson-linear sweep covers dy <= %d channels: got dy = %d", PLIN_MAX_DY, dims->dy);
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    if (layout != AUXSSM_LAYOUT_DENSE) {
+        set_error("the Poisson-linear sweep (dx <= %d, dy <= %d) takes the dense (C, T, dx) layout only", MAX_D, PLIN_MAX_DY);
+        return AUXSSM_ERR_UNSUPPORTED;
+    }
+    return AUXSSM_OK;
+}
+
+//                                      obs_model  noise_arrays  args            limits       driver
+static const SweepFamily FAM_LG_CONCAT{true, false, lg_concat_args, nullptr, AX_SWEEP_DRIVER(sweep_lg_concat<R>)};
+static const SweepFamily FAM_POINTWISE{false, true, pointwise_args, nullptr, AX_SWEEP_DRIVER(sweep_ss<R, PointwiseFactory<R>>)};
+static const SweepFamily FAM_LORENZ{true, true, lorenz_args, nullptr, AX_SWEEP_DRIVER(sweep_lorenz<R>)};
+static const SweepFamily FAM_MVT{false, true, mvt_args, mvt_limits, AX_SWEEP_DRIVER(sweep_mvt<R>)};
+static const SweepFamily FAM_PLIN{false, true, plin_args, plin_limits, AX_SWEEP_DRIVER(sweep_ss<R, PlinFactory<R>>)};
+static const struct KModelRow {
+    int model_kind;
+    const SweepFamily* family;
+    int order, pointwise;
+} KMODELS[] = {
+    {AUXSSM_KMODEL_LG_CONCAT, &FAM_LG_CONCAT, 0, 0},
+    {AUXSSM_KMODEL_SV_FIRST, &FAM_POINTWISE, 1, PW_SV},
+    {AUXSSM_KMODEL_SV_SECOND, &FAM_POINTWISE, 2, PW_SV},
+    {AUXSSM_KMODEL_LORENZ63_EXT, &FAM_LORENZ, 0, 0},
+    {AUXSSM_KMODEL_MVT_FIRST, &FAM_MVT, 1, 0},
+    {AUXSSM_KMODEL_MVT_SECOND, &FAM_MVT, 2, 0},
+    {AUXSSM_KMODEL_POISSON_FIRST, &FAM_POINTWISE, 1, PW_POISSON},
+    {AUXSSM_KMODEL_POISSON_SECOND, &FAM_POINTWISE, 2, PW_POISSON},
+    {AUXSSM_KMODEL_POISSON_LIN_FIRST, &FAM_PLIN, 1, 0},
+    {AUXSSM_KMODEL_POISSON_LIN_SECOND, &FAM_PLIN, 2, 0},
+};
+static const KModelRow* kmodel_row(int model_kind) {
+    for (const KModelRow& r : KMODELS)
+        if (r.model_kind == model_kind) return &r;
+    return nullptr;
 }
 
 }  // namespace ax
@@ -2046,102 +2096,29 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
     AX_NEED_H(h);
     int rc;
     if ((rc = check_dtype(dtype)) || (rc = check_dims(dims, true))) return rc;
-    // (the Poisson model is the SV sweep with another pointwise potential: same arrays, same checks, same layouts)
-    const bool pois = model_kind == AUXSSM_KMODEL_POISSON_FIRST || model_kind == AUXSSM_KMODEL_POISSON_SECOND;
-    const bool sv = pois || model_kind == AUXSSM_KMODEL_SV_FIRST || model_kind == AUXSSM_KMODEL_SV_SECOND;
-    const bool lorenz = model_kind == AUXSSM_KMODEL_LORENZ63_EXT;
-    const bool mvt = model_kind == AUXSSM_KMODEL_MVT_FIRST || model_kind == AUXSSM_KMODEL_MVT_SECOND;
-    const bool plin = model_kind == AUXSSM_KMODEL_POISSON_LIN_FIRST || model_kind == AUXSSM_KMODEL_POISSON_LIN_SECOND;
-    if (model_kind != AUXSSM_KMODEL_LG_CONCAT && !sv && !lorenz && !mvt && !plin) {
+    const KModelRow* row = kmodel_row(model_kind);
+    if (!row) {
         set_error("unknown model_kind %d", model_kind);
         return AUXSSM_ERR_ARG;
     }
-    if (sv) {
-        if (!model || !model->m0.ptr || !model->P0.ptr || (dims->T > 1 && (!model->Fs.ptr || !model->Qs.ptr || !model->bs.ptr))) {
-            set_error("model needs m0, P0 (and Fs, Qs, bs with T > 1)");
-            return AUXSSM_ERR_ARG;
-        }
-        if (dims->dy != dims->dx) {
-            set_error("stochastic-volatility models observe every state component: dy (%d) must equal dx (%d)", dims->dy, dims->dx);
-            return AUXSSM_ERR_ARG;
-        }
-    } else if (lorenz) {
-        if (!model || !model->m0.ptr || !model->P0.ptr || !model->Fs.ptr || !model->Qs.ptr || !model->Hs.ptr || !model->Rs.ptr || !model->cs.ptr) {
-            set_error("Lorenz model needs m0, P0, Fs (= [theta1, theta2, theta3, dt] on the device), Qs, Hs, Rs, cs");
-            return AUXSSM_ERR_ARG;
-        }
-        if (dims->dx != 3 || dims->dy < 1 || dims->dy > 3) {
-            set_error("Lorenz-63 has dx = 3 and 1..3 observed combinations (got dx=%d, dy=%d)", dims->dx, dims->dy);
-            return AUXSSM_ERR_ARG;
-        }
-    } else if (mvt) {
-        if (!model || !model->m0.ptr || !model->P0.ptr || !model->Fs.ptr || !model->Qs.ptr || !model->bs.ptr || !model->Rs.ptr || !model->cs.ptr) {
-            set_error("multivariate-t model needs m0, P0, Fs, Qs, bs as (dx) vectors, Rs (= prec (dx, dx) on the device) and cs (= [nu] on the device)");
-            return AUXSSM_ERR_ARG;
-        }
-        if (dims->dy != dims->dx) {
-            set_error("the multivariate-t model observes every state component: dy (%d) must equal dx (%d)", dims->dy, dims->dx);
-            return AUXSSM_ERR_ARG;
-        }
-    } else if (plin) {
-        if (!model || !model->m0.ptr || !model->P0.ptr || (dims->T > 1 && (!model->Fs.ptr || !model->Qs.ptr || !model->bs.ptr)) || !model->Hs.ptr || !model->cs.ptr ||
-            !yobs || !yobs->ptr) {
-            set_error("Poisson-linear model needs m0, P0 (and Fs, Qs, bs with T > 1), Hs (= H (dy, dx) row-major on the device), cs (= c (dy) on the device) and yobs (T, dy)");
-            return AUXSSM_ERR_ARG;
-        }
-    } else if ((rc = check_lgssm(model, dims->T))) {
-        return rc;
-    }
+    const SweepFamily& fam = *row->family;
+    if ((rc = fam.args(dims, model, yobs))) return rc;
     if ((rc = check_sweep_common(false, dims, delta, delta_dev != nullptr, nan_policy, layout, yobs && yobs->ptr && x && eps_aux && eps_samp && u_acc && accepted, model,
-                                 yobs, !sv && !mvt && !plin)))
+                                 yobs, fam.obs_model)))
         return rc;
-    if (plin) {  // (before anything is enqueued)
-        if (dims->dx > MAX_D) {
-            set_error("the Poisson-linear sweep covers dx <= %d (the register kernels): got dx = %d", MAX_D, dims->dx);
-            return AUXSSM_ERR_UNSUPPORTED;
-        }
-        if (dims->dy > PLIN_MAX_DY) {
-            set_error("the Poisson-linear sweep covers dy <= %d channels: got dy = %d", PLIN_MAX_DY, dims->dy);
-            return AUXSSM_ERR_UNSUPPORTED;
-        }
-        if (layout != AUXSSM_LAYOUT_DENSE) {
-            set_error("the Poisson-linear sweep (dx <= %d, dy <= %d) takes the dense (C, T, dx) layout only", MAX_D, PLIN_MAX_DY);
-            return AUXSSM_ERR_UNSUPPORTED;
-        }
-    }
-    if (mvt) {  // (before anything is enqueued)
-        if (dims->dx > 64) {
-            set_error("the batched multivariate-t sweep covers dx <= 64 (one wave per time step, lane = component): got dx = %d", dims->dx);
-            return AUXSSM_ERR_UNSUPPORTED;
-        }
-        if (layout != AUXSSM_LAYOUT_DENSE) {
-            set_error("the batched multivariate-t sweep (dx <= 64) takes the dense (C, T, dx) layout only");
-            return AUXSSM_ERR_UNSUPPORTED;
-        }
-        if (nan_policy != AUXSSM_NAN_REFERENCE) {
-            set_error("the batched multivariate-t sweep runs nan_policy 0 (reference) only: its sequences observe one scalar, which the reference's nansum drops alone");
-            return AUXSSM_ERR_UNSUPPORTED;
-        }
-    }
+    if (fam.limits && (rc = fam.limits(dims, layout, nan_policy))) return rc;  // (before anything is enqueued)
     const double* dptr;
     if ((rc = delta_block(h, dtype, delta_dev, &dptr))) return rc;
     SweepCall c{h, dtype, dims, model, yobs, delta, dptr, keys, parallel, nan_policy, layout, x, eps_aux, eps_samp, u_acc, accepted, logs};
-    if (keys && (lorenz || sv || mvt || plin))  // these sweeps read the noise from the arrays: draw all of it first (auxssm_kalman_draw)
+    if (keys && fam.noise_arrays)  // (auxssm_kalman_draw)
         by_dtype(dtype, [&](auto r) {
             launch_rng_sweep<decltype(r)>(h, keys, (long long)dims->C * dims->T * dims->dx, dims->C, const_cast<void*>(eps_aux), const_cast<void*>(eps_samp),
                                           const_cast<void*>(u_acc));
             return AUXSSM_OK;
         });
-    if (sv) c.order = (model_kind == AUXSSM_KMODEL_SV_FIRST || model_kind == AUXSSM_KMODEL_POISSON_FIRST) ? 1 : 2;
-    if (pois) c.kind = PW_POISSON;
-    if (mvt) c.order = model_kind == AUXSSM_KMODEL_MVT_FIRST ? 1 : 2;
-    if (plin) c.order = model_kind == AUXSSM_KMODEL_POISSON_LIN_FIRST ? 1 : 2;
-    return by_dtype(dtype, [&](auto r) {
-        using R = decltype(r);
-        if (mvt) return sweep_mvt<R>(c);
-        if (plin) return sweep_plin<R>(c);
-        return lorenz ? sweep_lorenz<R>(c) : sv ? sweep_sv<R>(c) : sweep_lg_concat<R>(c);
-    });
+    c.order = row->order;
+    c.kind = row->pointwise;
+    return fam.driver(c);
 }
 
 int auxssm_kalman_sweep(auxssm_handle h, int dtype, int model_kind, const auxssm_dims* dims, const auxssm_lgssm* model,

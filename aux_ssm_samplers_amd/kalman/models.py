@@ -11,7 +11,51 @@ from .. import _lib
 from .._primitives.kalman.base import DeviceLGSSM, _upload_arr
 
 
-class LGConcatModel:
+class _BuiltinModel:
+    """What the built-in device models have in common, and what kalman.get_kernel knows one by (generic._same_device_model): the model kind `kmodel` of
+    include/auxssm.h, the sizes T, dx, p_obs, the data yobs (T, p_obs), and the uploads, made once per (handle, dtype): a subclass gives _upload(handle, dtype)
+    -> the model's C struct with the buffers it points at; the data is uploaded here."""
+    dense_only = False  # >= 32 chains run chain-minor (lanes over chains)
+    _yname = "ys"
+
+    def device(self, handle, dtype):
+        """-> (model, data buffer, data array descriptor) on the handle's device"""
+        key = (id(handle), np.dtype(dtype).str)
+        dev = self._dev.get(key)
+        if dev is None:
+            dl = self._upload(handle, dtype)
+            ybuf, yarr = _upload_arr(handle, self.yobs, (self.p_obs,), 1, self.T, 1, False, False, np.dtype(dtype), self._yname)
+            dev = self._dev[key] = (dl, ybuf, yarr)
+        return dev
+
+
+def _state_space_observations(order, x, u, delta, grad, lam):
+    """The auxiliary observation set of examples/stochastic_volatility/auxiliary_kalman.py:28-46 for a potential with gradient grad (T, d) and lam = -hess at x,
+    diagonal (T, d) or dense (T, d, d); it lives in the state space, H = I, c = 0:
+        order 1: ys = u + delta/2 grad,                               R = delta/2 I
+        order 2: Om = (lam + 2/delta I)^-1 (a dense one symmetrised), ys = Om (2u/delta + grad + lam x), R = Om
+    -> ys, Hs, Rs, cs in u's dtype"""
+    T, d = u.shape
+    dt = u.dtype
+    eyes = np.broadcast_to(np.eye(d, dtype=dt), (T, d, d))
+    zeros = np.zeros((T, d), dt)
+    if order == 1:
+        return (u + 0.5 * delta * grad).astype(dt), eyes, (0.5 * delta * eyes).astype(dt), zeros
+    hess = -lam  # (the reference's own terms, -hess + 2/delta and grad - hess x: the same numbers, and for SVModel's missing data the same NaN to the bit)
+    if lam.ndim == 2:
+        om = 1.0 / (-hess + 2.0 / delta)
+        ys = om * (2.0 * u / delta + grad - hess * x)
+        Rs = np.zeros((T, d, d), dt)
+        Rs[:, np.arange(d), np.arange(d)] = om
+    else:
+        om = np.linalg.inv(-hess + (2.0 / delta) * np.eye(d))
+        om = 0.5 * (om + np.swapaxes(om, -1, -2))
+        ys = np.einsum("tkl,tl->tk", om, 2.0 * u / delta + grad - np.einsum("tkl,tl->tk", hess, x))
+        Rs = om.astype(dt)
+    return ys.astype(dt), eyes, Rs, zeros
+
+
+class LGConcatModel(_BuiltinModel):
     """Linear-Gaussian SSM with the auxiliary observations concatenated to the real ones
     (the observation-factory pattern of examples/lorenz/auxiliary_kalman.py:26-35):
 
@@ -23,7 +67,7 @@ class LGConcatModel:
     The same methods are plain NumPy factories, so they also drive the generic host path (and the oracle)."""
 
     kmodel = _lib.KMODEL_LG_CONCAT
-    dense_only = False
+    _yname = "yobs"
 
     def __init__(self, m0, P0, Fs, Qs, bs, Hobs, Robs, cobs, yobs):
         self.m0, self.P0, self.Fs, self.Qs, self.bs = m0, P0, Fs, Qs, bs
@@ -54,31 +98,24 @@ class LGConcatModel:
         return joint_logpdf(self.yobs, x, LGSSM(self.m0, self.P0, self.Fs, self.Qs, self.bs, self.Hobs, self.Robs, self.cobs))
 
     # ---- device side ----
-    def device(self, handle, dtype):
-        key = (id(handle), np.dtype(dtype).str)
-        dev = self._dev.get(key)
-        if dev is None:
-            T, d, po = self.T, self.dx, self.p_obs
-            lg = (self.m0, self.P0, self.Fs, self.Qs, self.bs, self.Hobs, self.Robs, self.cobs)
-            dl = DeviceLGSSM(handle, lg, 1, T, 1, d, po, False, dtype)
-            ybuf, yarr = _upload_arr(handle, self.yobs, (po,), 1, T, 1, False, False, np.dtype(dtype), "yobs")
-            dev = self._dev[key] = (dl, ybuf, yarr)
-        return dev
+    def _upload(self, handle, dtype):
+        lg = (self.m0, self.P0, self.Fs, self.Qs, self.bs, self.Hobs, self.Robs, self.cobs)
+        return DeviceLGSSM(handle, lg, 1, self.T, 1, self.dx, self.p_obs, False, dtype)
 
 
-class _PointwiseModel:
-    """What SVModel and PoissonModel share: data ys (T, dx), time-invariant linear-Gaussian dynamics (m0, P0, F, Q, b) and a potential that is a sum over
-    the components, log g_t(x) = sum_k f(y_{t,k}, x_{t,k}), whose first- or second-order auxiliary observation set is therefore diagonal.  A subclass sets
-    KMODELS = (first-order kind, second-order kind) and gives log_potential and observations_factory."""
-    dense_only = False  # >= 32 chains run chain-minor (lanes over chains), as the LG_CONCAT sweep does
+class _StateSpaceModel(_BuiltinModel):
+    """What SVModel, PoissonModel and PoissonLinearModel share: data ys (T, p_obs), time-invariant linear-Gaussian dynamics (m0, P0, F, Q, b) on a state of dx
+    components (ys's width unless said) and a potential whose first- or second-order auxiliary observation set lives in the state space
+    (_state_space_observations).  A subclass sets KMODELS = (first-order kind, second-order kind) and gives log_potential(x) and grad_lam(x) -> (grad (T, dx),
+    lam = -hess: (T, dx) where the potential is a sum over the components, else (T, dx, dx))."""
     KMODELS = None
 
-    def __init__(self, ys, m0, P0, F, Q, b, order=1):
+    def __init__(self, ys, m0, P0, F, Q, b, order=1, dx=None):
         if order not in (1, 2):
             raise ValueError("order must be 1 or 2")
         self.yobs = np.asarray(ys)
-        self.T, self.dx = self.yobs.shape
-        self.p_obs = self.dx
+        self.T, self.p_obs = self.yobs.shape
+        self.dx = self.p_obs if dx is None else dx
         self.m0, self.P0 = np.asarray(m0), np.asarray(P0)
         self.F, self.Q, self.b = np.asarray(F), np.asarray(Q), np.asarray(b)
         self.order = order
@@ -98,19 +135,17 @@ class _PointwiseModel:
         prior = prior_logpdf(x, LGSSM(self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None))
         return prior + self.log_potential(x)
 
-    def device(self, handle, dtype):
-        key = (id(handle), np.dtype(dtype).str)
-        dev = self._dev.get(key)
-        if dev is None:
-            T, d = self.T, self.dx
-            lg = (self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None)
-            dl = DeviceLGSSM(handle, lg, 1, T, 1, d, d, False, dtype)
-            ybuf, yarr = _upload_arr(handle, self.yobs, (d,), 1, T, 1, False, False, np.dtype(dtype), "ys")
-            dev = self._dev[key] = (dl, ybuf, yarr)
-        return dev
+    def observations_factory(self, x, u, delta):
+        x, u = np.asarray(x), np.asarray(u)
+        with np.errstate(all="ignore"):
+            return _state_space_observations(self.order, x, u, delta, *self.grad_lam(x))
+
+    def _upload(self, handle, dtype):
+        lg = (self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None)
+        return DeviceLGSSM(handle, lg, 1, self.T, 1, self.dx, self.dx, False, dtype)
 
 
-class SVModel(_PointwiseModel):
+class SVModel(_StateSpaceModel):
     """Multivariate stochastic volatility  y_{t,k} ~ N(0, exp(x_{t,k}))  on linear-Gaussian dynamics
     x_{t+1} = F x_t + b + N(0, Q), with the first- or second-order auxiliary observation factories of
     examples/stochastic_volatility/auxiliary_kalman.py:22-48 (closed-form gradient / Hessian of the potential,
@@ -135,26 +170,14 @@ class SVModel(_PointwiseModel):
             val = -0.5 * np.log(2 * np.pi) - 0.5 * x - 0.5 * self._w(x)
         return float(np.sum(np.nan_to_num(val)))
 
-    def observations_factory(self, x, u, delta):
-        x, u = np.asarray(x), np.asarray(u)
-        T, d = self.T, self.dx
-        dt = u.dtype
-        eyes = np.broadcast_to(np.eye(d, dtype=dt), (T, d, d))
-        zeros = np.zeros((T, d), dt)
+    def grad_lam(self, x):
+        """(grad, lam) of log g, both (T, dx): grad NaN -> 0, lam = -hess NaN where y is"""
         with np.errstate(all="ignore"):
-            w = self._w(x)
-            grad = np.nan_to_num(0.5 * (w - 1.0))
-            if self.order == 1:
-                return (u + 0.5 * delta * grad).astype(dt), eyes, (0.5 * delta * eyes).astype(dt), zeros
-            hess = -0.5 * w
-            om = 1.0 / (-hess + 2.0 / delta)
-            ys = om * (2.0 * u / delta + grad - hess * x)
-        Rs = np.zeros((T, d, d), dt)
-        Rs[:, np.arange(d), np.arange(d)] = om
-        return ys.astype(dt), eyes, Rs, zeros
+            w = self._w(np.asarray(x))
+            return np.nan_to_num(0.5 * (w - 1.0)), -(-0.5 * w)   # (hess negated, as the reference writes it: w / 2, and the same NaN where y is missing)
 
 
-class PoissonModel(_PointwiseModel):
+class PoissonModel(_StateSpaceModel):
     """Multivariate counts with a log link  y_{t,k} ~ Poisson(exp(x_{t,k}))  on linear-Gaussian dynamics x_{t+1} = F x_t + b + N(0, Q), x_0 ~ N(m0, P0),
     under the first- or second-order auxiliary observation factories of examples/stochastic_volatility/auxiliary_kalman.py:22-48.  Arguments and shapes
     are SVModel's: ys (T, dx), F and Q dense (dx, dx), order 1 or 2.  With mask = isfinite(y), per component
@@ -202,23 +225,8 @@ class PoissonModel(_PointwiseModel):
         with np.errstate(invalid="ignore"):
             return np.where(mask, self.yobs.astype(x.dtype) - e, 0.0), np.where(mask, e, 0.0)
 
-    def observations_factory(self, x, u, delta):
-        x, u = np.asarray(x), np.asarray(u)
-        T, d = self.T, self.dx
-        dt = u.dtype
-        eyes = np.broadcast_to(np.eye(d, dtype=dt), (T, d, d))
-        zeros = np.zeros((T, d), dt)
-        grad, lam = self.grad_lam(x)
-        if self.order == 1:
-            return (u + 0.5 * delta * grad).astype(dt), eyes, (0.5 * delta * eyes).astype(dt), zeros
-        om = 1.0 / (lam + 2.0 / delta)
-        ys = om * (2.0 * u / delta + grad + lam * x)
-        Rs = np.zeros((T, d, d), dt)
-        Rs[:, np.arange(d), np.arange(d)] = om
-        return ys.astype(dt), eyes, Rs, zeros
 
-
-class PoissonLinearModel:
+class PoissonLinearModel(_StateSpaceModel):
     """Poisson counts through a loading matrix (the Poisson linear dynamical system, a dynamic Poisson factor model): a low-dimensional linear-Gaussian state
     drives many count channels,
 
@@ -247,6 +255,7 @@ class PoissonLinearModel:
     Pass the three bound methods to kalman.get_kernel: it runs the device sweep (model kind POISSON_LIN_FIRST / _SECOND) on host states (T, dx) or (C, T, dx),
     or on resident DeviceChains(handle, x (C, T, dx), chain_minor=False): the dense layout only.  The same methods are NumPy factories for the host path and
     the oracle."""
+    KMODELS = (_lib.KMODEL_POISSON_LIN_FIRST, _lib.KMODEL_POISSON_LIN_SECOND)
     dense_only = True
     MAX_DX = 4
     MAX_DY = 1024
@@ -275,22 +284,10 @@ class PoissonLinearModel:
             raise ValueError(f"PoissonLinearModel: c must be a finite scalar or ({dy},) vector, got shape {c.shape}")
         from ..csmc.models import PoissonPotential
         PoissonPotential.check_counts(ys)
-        self.yobs, self.H, self.c = ys, H, c
-        self.T, self.dx, self.p_obs = T, dx, dy
-        self.m0, self.P0 = np.asarray(m0), np.asarray(P0)
-        self.F, self.Q, self.b = np.asarray(F), np.asarray(Q), np.asarray(b)
+        super().__init__(ys, m0, P0, F, Q, b, order, dx=dx)
+        self.H, self.c = H, c
         if self.m0.shape != (dx,) or self.b.shape != (dx,) or any(a.shape != (dx, dx) for a in (self.P0, self.F, self.Q)):
             raise ValueError(f"PoissonLinearModel: m0, b must be ({dx},) and P0, F, Q ({dx}, {dx})")
-        self.order = order
-        self.kmodel = _lib.KMODEL_POISSON_LIN_FIRST if order == 1 else _lib.KMODEL_POISSON_LIN_SECOND
-        n = T - 1
-        self.Fs = np.broadcast_to(self.F, (n, dx, dx))
-        self.Qs = np.broadcast_to(self.Q, (n, dx, dx))
-        self.bs = np.broadcast_to(self.b, (n, dx))
-        self._dev = {}
-
-    def dynamics_factory(self, x):
-        return self.m0, self.P0, self.Fs, self.Qs, self.bs
 
     def _terms(self, x):
         """(mask, eta, e, yy) at x (T, dx), each (T, dy)"""
@@ -312,43 +309,16 @@ class PoissonLinearModel:
         lam = np.einsum("tj,jk,jl->tkl", e, H, H)
         return (yy - e) @ H, 0.5 * (lam + np.swapaxes(lam, -1, -2))   # (symmetric to the last bit)
 
-    def observations_factory(self, x, u, delta):
-        x, u = np.asarray(x), np.asarray(u)
-        T, d = self.T, self.dx
-        dt = u.dtype
-        eyes = np.broadcast_to(np.eye(d, dtype=dt), (T, d, d))
-        zeros = np.zeros((T, d), dt)
-        grad, lam = self.grad_lam(x)
-        if self.order == 1:
-            return (u + 0.5 * delta * grad).astype(dt), eyes, (0.5 * delta * eyes).astype(dt), zeros
-        om = np.linalg.inv(lam + (2.0 / delta) * np.eye(d))
-        om = 0.5 * (om + np.swapaxes(om, -1, -2))
-        ys = np.einsum("tkl,tl->tk", om, 2.0 * u / delta + grad + np.einsum("tkl,tl->tk", lam, x))
-        return ys.astype(dt), eyes, om.astype(dt), zeros
-
-    def log_likelihood_fn(self, x):
-        from .._primitives.kalman.base import prior_logpdf, LGSSM
-        x = np.asarray(x)
-        prior = prior_logpdf(x, LGSSM(self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None))
-        return prior + self.log_potential(x)
-
-    def device(self, handle, dtype):
-        key = (id(handle), np.dtype(dtype).str)
-        dev = self._dev.get(key)
-        if dev is None:
-            T, d, dy = self.T, self.dx, self.p_obs
-            lg = (self.m0, self.P0, self.Fs, self.Qs, self.bs, None, None, None)
-            dl = DeviceLGSSM(handle, lg, 1, T, 1, d, d, False, dtype)
-            # include/auxssm.h, POISSON_LIN_FIRST / _SECOND: the loading matrix (dy, dx) row-major rides in the Hs slot, the offsets (dy) in the cs slot
-            for name, a in (("Hs", self.H), ("cs", self.c)):
-                buf = dl.bufs["plin_" + name] = handle.to_device(np.ascontiguousarray(a, np.float64), dtype)
-                setattr(dl.c, name, buf.arr(0, 0, 0))
-            ybuf, yarr = _upload_arr(handle, self.yobs, (dy,), 1, T, 1, False, False, np.dtype(dtype), "ys")
-            dev = self._dev[key] = (dl, ybuf, yarr)
-        return dev
+    def _upload(self, handle, dtype):
+        dl = super()._upload(handle, dtype)
+        # include/auxssm.h, POISSON_LIN_FIRST / _SECOND: the loading matrix (dy, dx) row-major rides in the Hs slot, the offsets (dy) in the cs slot
+        for name, a in (("Hs", self.H), ("cs", self.c)):
+            buf = dl.bufs["plin_" + name] = handle.to_device(np.ascontiguousarray(a, np.float64), dtype)
+            setattr(dl.c, name, buf.arr(0, 0, 0))
+        return dl
 
 
-class LorenzModel:
+class LorenzModel(_BuiltinModel):
     """Stochastic Lorenz-63 with Euler-Maruyama dynamics and sparse linear-Gaussian observations,
     examples/lorenz/auxiliary_kalman.py:14-52 (model.py:10-25; linearisation.py:11-44 with the analytic Jacobian in place of jacfwd):
 
@@ -359,7 +329,6 @@ class LorenzModel:
     ys (T, po) with NaN rows where nothing is observed; Hs (T, po, 3) may carry NaN rows there too (model.py:43-56).
     Pass the three bound methods to kalman.get_kernel: it runs the device sweep (model kind LORENZ63_EXT)."""
     kmodel = _lib.KMODEL_LORENZ63_EXT
-    dense_only = False
 
     def __init__(self, ys, Hs, Rs, cs, m0, P0, theta, sigma_x, dt):
         self.yobs, self.Hobs, self.Robs, self.cobs = np.asarray(ys), np.asarray(Hs), np.asarray(Rs), np.asarray(cs)
@@ -413,23 +382,17 @@ class LorenzModel:
             ll = mvn(np.asarray(self.yobs, np.float64) - pred, np.asarray(self.Robs, np.float64))
         return float(out + np.nansum(ll))
 
-    def device(self, handle, dtype):
-        key = (id(handle), np.dtype(dtype).str)
-        dev = self._dev.get(key)
-        if dev is None:
-            T, po = self.T, self.p_obs
-            # rides in the Fs slot of the C struct (include/auxssm.h, LORENZ63_EXT): rows [theta1, theta2, theta3, dt]
-            par = np.concatenate([self.theta_rows, np.full((self.theta_rows.shape[0], 1), self.dt)], axis=1)
-            n = T - 1
-            lg = (self.m0, self.P0, np.broadcast_to(np.eye(3), (n, 3, 3)), self.Qs, np.broadcast_to(np.zeros(3), (n, 3)),
-                  self.Hobs, self.Robs, self.cobs)
-            dl = DeviceLGSSM(handle, lg, 1, T, 1, 3, po, False, dtype)
-            pbuf = handle.to_device(par, dtype)
-            dl.bufs["lorenz_par"] = pbuf
-            dl.c.Fs = pbuf.arr(4 if par.shape[0] > 1 else 0, 0, 0)
-            ybuf, yarr = _upload_arr(handle, self.yobs, (po,), 1, T, 1, False, False, np.dtype(dtype), "ys")
-            dev = self._dev[key] = (dl, ybuf, yarr)
-        return dev
+    def _upload(self, handle, dtype):
+        # rides in the Fs slot of the C struct (include/auxssm.h, LORENZ63_EXT): rows [theta1, theta2, theta3, dt]
+        par = np.concatenate([self.theta_rows, np.full((self.theta_rows.shape[0], 1), self.dt)], axis=1)
+        n = self.T - 1
+        lg = (self.m0, self.P0, np.broadcast_to(np.eye(3), (n, 3, 3)), self.Qs, np.broadcast_to(np.zeros(3), (n, 3)),
+              self.Hobs, self.Robs, self.cobs)
+        dl = DeviceLGSSM(handle, lg, 1, self.T, 1, 3, self.p_obs, False, dtype)
+        pbuf = handle.to_device(par, dtype)
+        dl.bufs["lorenz_par"] = pbuf
+        dl.c.Fs = pbuf.arr(4 if par.shape[0] > 1 else 0, 0, 0)
+        return dl
 
     def par_device(self, handle, dtype, C):
         """the device rows [theta, dt] the sweep reads, one per chain (C, 4): a single theta is replicated on first use, so that a theta
@@ -452,7 +415,7 @@ class _DeviceModel:
         self.bufs = {}
 
 
-class MVTModel:
+class MVTModel(_BuiltinModel):
     """The spatial example's batched model (examples/spatial/auxiliary_kalman.py:10-66, model.py:103-124): d independent scalar LGSSMs
     x_{t+1,k} = F_k x_{t,k} + b_k + N(0, Q_k), x_{0,k} ~ N(m0_k, P0_k), coupled only through the multivariate Student-t potential
     log g_t(x) = -(nu + d) / 2 log(1 + (y_t - x)^T prec (y_t - x) / nu) (NaN -> 0), in the reference's batched shapes: the state is (T, d, 1),
@@ -578,15 +541,10 @@ class MVTModel:
         return float(out) + self.log_potential(x)
 
     # ---- device side ----
-    def device(self, handle, dtype):
-        key = (id(handle), np.dtype(dtype).str)
-        dev = self._dev.get(key)
-        if dev is None:
-            dl = _DeviceModel()
-            # include/auxssm.h, MVT_FIRST / MVT_SECOND: the diagonal model as (d) vectors; prec rides in the Rs slot, [nu] in the cs slot
-            for name, a in (("m0", self.m0v), ("P0", self.P0v), ("Fs", self.Fv), ("Qs", self.Qv), ("bs", self.bv), ("Rs", self.prec), ("cs", [self.nu])):
-                buf = dl.bufs[name] = handle.to_device(np.asarray(a, np.float64), dtype)
-                setattr(dl.c, name, buf.arr(0, 0, 0))
-            ybuf, yarr = _upload_arr(handle, self.yobs, (self.dx,), 1, self.T, 1, False, False, np.dtype(dtype), "ys")
-            dev = self._dev[key] = (dl, ybuf, yarr)
-        return dev
+    def _upload(self, handle, dtype):
+        dl = _DeviceModel()
+        # include/auxssm.h, MVT_FIRST / MVT_SECOND: the diagonal model as (d) vectors; prec rides in the Rs slot, [nu] in the cs slot
+        for name, a in (("m0", self.m0v), ("P0", self.P0v), ("Fs", self.Fv), ("Qs", self.Qv), ("bs", self.bv), ("Rs", self.prec), ("cs", [self.nu])):
+            buf = dl.bufs[name] = handle.to_device(np.asarray(a, np.float64), dtype)
+            setattr(dl.c, name, buf.arr(0, 0, 0))
+        return dl

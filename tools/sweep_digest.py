@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the bytes of (x, accepted, logs) after consecutive keyed sweeps of a fixed list of small problems: every branch a driver of
-the auxiliary Kalman sweep can take (csrc/api.hip: sweep_lg_concat, sweep_lg_concat_fused, sweep_sv, sweep_lorenz), in both dtypes.  For comparing two builds
-of the library bit for bit:   AUXSSM_LIB=/path/to/libauxssm.so python tools/sweep_digest.py out.json   once per build, then compare the files.
-A case that raises is recorded with the error's text."""
+the auxiliary Kalman sweep can take (csrc/api.hip: sweep_lg_concat, sweep_lg_concat_fused, sweep_lorenz, sweep_mvt and sweep_ss -- the state-space driver of the
+SV, Poisson and Poisson-linear kinds), every model kind of include/auxssm.h (1-8, 11, 12), in both dtypes.  For comparing two builds of the library bit for bit:
+    AUXSSM_LIB=/path/to/libauxssm.so python tools/sweep_digest.py out.json        once per build, then compare the files.
+A case that raises is recorded with the error's text, and the exit status is 1: two equal error strings compare equal and prove nothing.
+
+    python tools/sweep_digest.py --host out.json        needs no GPU: one SHA-256 per built-in model class, order and dtype over everything dynamics_factory,
+observations_factory and log_likelihood_fn return at a fixed (x, u, delta) on data with missing entries -- the NumPy factories the host path and the oracle run.
+The two densities the models take from the device primitives (prior_logpdf, joint_logpdf) are the NumPy oracle's there.  Run it from a checkout of each of the
+two trees to compare (it imports the package beside it)."""
 import hashlib
 import json
 import os
@@ -12,8 +18,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from aux_ssm_samplers_amd import _lib, random as R  # noqa: E402
-from aux_ssm_samplers_amd.kalman import DeviceChains, KalmanSampler, LGConcatModel, LorenzModel, SVModel, get_kernel  # noqa: E402
-from aux_ssm_samplers_amd.workloads import lg_model, lorenz_kalman_setup, sv_setup  # noqa: E402
+from aux_ssm_samplers_amd.kalman import (DeviceChains, KalmanSampler, LGConcatModel, LorenzModel, MVTModel, PoissonLinearModel, PoissonModel, SVModel,  # noqa: E402
+                                         get_kernel)
+from aux_ssm_samplers_amd.workloads import lg_model, lorenz_kalman_setup, poisson_lin_setup, poisson_setup, sv_setup  # noqa: E402
 
 
 def lg(T, d, tinv=False):
@@ -50,6 +57,43 @@ def lorenz(T, C=None):
     return LorenzModel(base.yobs[:T], base.Hobs[:T], base.Robs[:T], base.cobs[:T], base.m0, base.P0, theta, base.sigma_x, base.dt), 1e-3
 
 
+def holes(y, channel=None):
+    """missing entries: one at t = 0, a whole middle row and one at T - 1 where T > 3; channel: that column everywhere"""
+    y = np.array(y, np.float64)
+    T = y.shape[0]
+    y[0, 0] = np.nan
+    if T > 3:
+        y[T // 2] = np.nan
+        y[T - 1, -1] = np.nan
+    if channel is not None:
+        y[:, channel] = np.nan
+    return y
+
+
+def pois(T, d, order):
+    M0, Mt, _, _, _, y = poisson_setup(T, d)
+    return PoissonModel(holes(y), M0.m0, M0.P0, Mt.F, Mt.Q, Mt.b, order=order), 0.05
+
+
+def plin(T, dx, dy, order, delta):
+    """delta: of the order of 1 / lambda_max(H' diag(e) H), which the first-order proposal needs (PoissonLinearModel's docstring)"""
+    base, _, H, c = poisson_lin_setup(T, dx, dy)
+    y = holes(base.yobs, channel=dy - 2) if dy > 2 else base.yobs
+    return PoissonLinearModel(y, H, c, base.m0, base.P0, base.F, base.Q, base.b, order=order), delta
+
+
+def mvt(T, d, order):
+    """a dense precision, nu = 3, diagonal dynamics that differ by component"""
+    rng = np.random.default_rng(10 * d + T)
+    A = rng.standard_normal((d, d))
+    prec = 1.5 * np.eye(d) + 0.8 * (A @ A.T) / d
+    y = np.cumsum(0.3 * rng.standard_normal((T, d)), axis=0) + 0.5 * rng.standard_normal((T, d))
+    if T > 3:
+        y[T // 2, (d - 1) // 2] = np.nan
+    return MVTModel(y, 0.1 * rng.standard_normal(d), 0.5 + rng.random(d), 0.9 + 0.1 * rng.random(d), 0.1 * (0.5 + rng.random(d)), 0.05 * rng.standard_normal(d),
+                    3.0, prec, order=order), 0.1
+
+
 # name: (model, chains, chain-minor, options {share, overlap, parallel, fused, moments, sweeps, nan_policy})
 CASES = {
     "lg_dense_parallel": (lambda: lg(40, 2), 3, False, {}),
@@ -78,6 +122,20 @@ for o in (1, 2):
     CASES[f"sv{o}_cm_shared"] = (lambda o=o: sv(40, 2, o), 64, True, {})
     CASES[f"sv{o}_cm_array_free"] = (lambda o=o: sv(40, 2, o), 64, True, dict(share=0))
     CASES[f"sv{o}_wide_one_chain"] = (lambda o=o: sv(12, 6, o), 1, False, {})
+    CASES[f"pois{o}_dense"] = (lambda o=o: pois(40, 2, o), 3, False, {})
+    CASES[f"pois{o}_cm_shared"] = (lambda o=o: pois(40, 2, o), 64, True, {})
+    CASES[f"pois{o}_cm_array_free"] = (lambda o=o: pois(40, 2, o), 64, True, dict(share=0))
+    CASES[f"pois{o}_wide_one_chain"] = (lambda o=o: pois(12, 6, o), 1, False, {})
+    CASES[f"plin{o}_dense"] = (lambda o=o: plin(40, 2, 3, o, 0.05), 3, False, {})
+    CASES[f"plin{o}_second_staging_block_ragged_chains"] = (lambda o=o: plin(40, 4, 70, o, 0.005), 5, False, {})
+    CASES[f"plin{o}_one_step"] = (lambda o=o: plin(1, 2, 3, o, 0.05), 3, False, {})
+    CASES[f"mvt{o}_d3"] = (lambda o=o: mvt(40, 3, o), 3, False, {})
+    CASES[f"mvt{o}_d5"] = (lambda o=o: mvt(40, 5, o), 3, False, {})
+    CASES[f"mvt{o}_one_step"] = (lambda o=o: mvt(1, 3, o), 3, False, {})
+CASES["pois1_wide_gain_rows_reused"] = (lambda: pois(12, 6, 1), 3, False, {})
+CASES["pois1_cm_shared_overlap"] = (lambda: pois(40, 2, 1), 64, True, dict(overlap=1, sweeps=5))
+CASES["pois2_dense_sequential"] = (lambda: pois(40, 2, 2), 3, False, dict(parallel=False))
+CASES["plin2_dense_sequential"] = (lambda: plin(40, 2, 3, 2, 0.05), 3, False, dict(parallel=False))
 
 
 def digest(make, Cn, chain_minor, opt, dtype):
@@ -90,7 +148,7 @@ def digest(make, Cn, chain_minor, opt, dtype):
             _, kernel = _get_device_kernel(model, opt.get("parallel", True), nan_policy=opt["nan_policy"])
         else:
             _, kernel = get_kernel(model.dynamics_factory, model.observations_factory, model.log_likelihood_fn, opt.get("parallel", True))
-        x0 = (0.3 * np.random.default_rng(1).standard_normal((Cn, model.T, model.dx))).astype(dtype)
+        x0 = start_state(model, Cn, dtype)
         ch = DeviceChains(h, x0, chain_minor=chain_minor, fused=opt.get("fused", False))
         stats = tuple(h.zeros(ch._x.shape, dtype) for _ in range(3)) if opt.get("moments") else ()
         if stats:
@@ -108,14 +166,59 @@ def digest(make, Cn, chain_minor, opt, dtype):
         h.close()
 
 
+def start_state(model, Cn, dtype):
+    return (0.3 * np.random.default_rng(1).standard_normal((Cn, model.T, model.dx))).astype(dtype)
+
+
+# ---- host mode ----
+HOST_MODELS = {
+    "LGConcatModel": lambda: lg_missing(False)[0],
+    "LorenzModel": lambda: lorenz(12)[0],
+    "MVTModel:order1": lambda: mvt(12, 3, 1)[0], "MVTModel:order2": lambda: mvt(12, 3, 2)[0],
+    "PoissonLinearModel:order1": lambda: plin(12, 2, 3, 1, 0.05)[0], "PoissonLinearModel:order2": lambda: plin(12, 2, 3, 2, 0.05)[0],
+    "PoissonModel:order1": lambda: pois(12, 2, 1)[0], "PoissonModel:order2": lambda: pois(12, 2, 2)[0],
+    "SVModel:order1": lambda: SVModel(holes(sv(12, 2, 1)[0].yobs), *sv_setup(12, 2)[2], order=1),
+    "SVModel:order2": lambda: SVModel(holes(sv(12, 2, 2)[0].yobs), *sv_setup(12, 2)[2], order=2),
+}
+
+
+def host_digest(model, dtype):
+    rng = np.random.default_rng(2)
+    x = start_state(model, 1, dtype)[0]
+    u = (x + 0.1 * rng.standard_normal(x.shape)).astype(dtype)
+    if getattr(model, "batched_state", False):
+        x, u = x[..., None], u[..., None]
+    sha = hashlib.sha256()
+    with np.errstate(all="ignore"):
+        parts = tuple(model.dynamics_factory(x)) + tuple(model.observations_factory(x, u, 0.05)) + (model.log_likelihood_fn(x),)
+    for a in parts:
+        a = np.ascontiguousarray(a)
+        sha.update(f"{a.dtype.str}{a.shape}".encode())
+        sha.update(a.tobytes())
+    return sha.hexdigest()
+
+
+def densities_on_the_host():
+    """the two densities the models' log_likelihood_fn take from the device primitives (they import them when called), as the NumPy oracle computes them"""
+    from aux_ssm_samplers_amd._primitives.kalman import base
+    from oracle import kalman_np as K
+    base.prior_logpdf = lambda xs, lgssm, handle=None: K.prior_logpdf(np.asarray(xs), tuple(lgssm))
+    base.joint_logpdf = lambda ys, xs, lgssm, *a, **k: K.log_likelihood(np.asarray(ys), np.asarray(xs), tuple(lgssm)) + K.prior_logpdf(np.asarray(xs), tuple(lgssm))
+
+
 if __name__ == "__main__":
-    out = {}
-    for name, (make, Cn, cm, opt) in sorted(CASES.items()):
-        for dtype in (np.float64, np.float32):
-            try:
-                out[f"{name}:{np.dtype(dtype).name}"] = digest(make, Cn, cm, opt, dtype)
-            except Exception as e:  # noqa: BLE001 -- part of the record: both builds must fail alike
-                out[f"{name}:{np.dtype(dtype).name}"] = f"{type(e).__name__}: {e}"
-    with open(sys.argv[1], "w") as f:
+    host = sys.argv[1] == "--host"
+    path = sys.argv[2 if host else 1]
+    if host:
+        densities_on_the_host()
+    out, raised = {}, []
+    for name, case, dtype in ((f"{n}:{np.dtype(dt).name}", c, dt) for n, c in sorted((HOST_MODELS if host else CASES).items()) for dt in (np.float64, np.float32)):
+        try:
+            out[name] = host_digest(case(), dtype) if host else digest(*case, dtype)
+        except Exception as e:  # noqa: BLE001 -- recorded, and the run fails: an error's text is no digest
+            out[name] = f"{type(e).__name__}: {e}"
+            raised.append(name)
+    with open(path, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
-    print(f"{len(out)} cases -> {sys.argv[1]}")
+    print(f"{len(out)} cases -> {path}" + (f"; RAISED: {', '.join(raised)}" if raised else ""))
+    sys.exit(1 if raised else 0)
