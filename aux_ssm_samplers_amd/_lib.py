@@ -18,6 +18,7 @@ KMODEL_LG_CONCAT, KMODEL_SV_FIRST, KMODEL_SV_SECOND, KMODEL_LORENZ63_EXT = 1, 2,
 KMODEL_MVT_FIRST, KMODEL_MVT_SECOND = 5, 6
 KMODEL_POISSON_FIRST, KMODEL_POISSON_SECOND = 7, 8
 KMODEL_POISSON_LIN_FIRST, KMODEL_POISSON_LIN_SECOND = 11, 12   # (9 and 10 are unassigned)
+KMODEL_LOGISTIC_FIRST, KMODEL_LOGISTIC_SECOND = 13, 14
 LAYOUT_DENSE, LAYOUT_CHAIN_MINOR = 0, 1
 OPT_SHARE_MODEL = 1
 OPT_OVERLAP_MODEL_STAGE = 2

@@ -1015,7 +1015,8 @@ template <typename R> static int sweep_lg_concat_fused(const SweepCall& c) {
 // ---- stochastic-volatility device factories (examples/stochastic_volatility/auxiliary_kalman.py:22-48, model.py:56-82) ----------
 // potential log g_t(x) = sum_k log N(y_k; 0, exp(x_k)); grad_k = (y_k^2 e^{-x_k} - 1) / 2, hess_kk = -y_k^2 e^{-x_k} / 2.
 // The same factories serve every pointwise potential with a diagonal Hessian: value, grad and lam = -hess come from kalman_bodies.h::Pointwise<R, KIND>, the kind
-// a template argument of k_sv_obs and k_sv_terms (PW_POISSON: log g = sum_k y_k x_k - e^{x_k}, AUXSSM_KMODEL_POISSON_FIRST / _SECOND).
+// a template argument of k_sv_obs and k_sv_terms (PW_POISSON: log g = sum_k y_k x_k - e^{x_k}, AUXSSM_KMODEL_POISSON_FIRST / _SECOND; PW_LOGISTIC: log g = sum_k
+// y_k x_k - m_k softplus(x_k), AUXSSM_KMODEL_LOGISTIC_FIRST / _SECOND, whose size m (T, D) is batch 1 of yobs: kalman_bodies.h::PwSize).
 //   first order  (:28-35): ys = u + delta/2 grad(x_lin),                      H = I, R = delta/2 I,  c = 0
 //   second order (:37-46): Om = (-hess + 2/delta I)^-1 (diagonal), ys = Om (2u/delta + grad - hess x_lin), H = I, R = Om, c = 0
 template <typename R> AX_HD R sv_nan_to_num(R v) { return nan_to_num<R>(v); }
@@ -1050,12 +1051,14 @@ __global__ void k_sv_obs(long long total, int C, int T, int D, int order, int cf
     }
     const R y = at<R>(yobs, 0, t, 0)[k];
     using Pw = Pointwise<R, KIND>;
+    R m = 0;
+    if constexpr (Pw::kHasSize) m = at<R>(yobs, 0, t, 1)[k];
     const R w = Pw::core(y, x);
-    const R grad = Pw::grad(y, w);
+    const R grad = Pw::grad(y, m, x, w);
     if (order == 1) {
         ys[g] = uu + (R)0.5 * delta * grad;
     } else {
-        const R hess = -Pw::lam(y, w);
+        const R hess = -Pw::lam(y, m, x, w);
         const R om = (R)1 / (-hess + (R)2 / delta);
         ys[g] = om * ((R)2 * uu / delta + grad - hess * x);
         // row k of the diagonal D x D record of (c, t): dense [c][t][k][j], chain-minor [t][k][j][c]
@@ -1089,8 +1092,10 @@ __global__ void __launch_bounds__(256) k_sv_terms(int C, int T, int D, R delta, 
             const long long g = ((long long)c * T + t) * D + k;
             const R y = at<R>(yobs, 0, t, 0)[k];
             const R a = xp[g], b = x[g], uu = u[g];
-            pp += Pointwise<R, KIND>::value(y, a);
-            px += Pointwise<R, KIND>::value(y, b);
+            R m = 0;
+            if constexpr (Pointwise<R, KIND>::kHasSize) m = at<R>(yobs, 0, t, 1)[k];
+            pp += Pointwise<R, KIND>::value(y, m, a);
+            px += Pointwise<R, KIND>::value(y, m, b);
             const R r1 = R1 ? R1[g * D + k] : (R)0.5 * delta, r2 = R2 ? R2[g * D + k] : (R)0.5 * delta;
             const R s1 = sqrt_(r1), s2 = sqrt_(r2);
             const R z1 = (ys1[g] - a) / s1, z2 = (ys2[g] - b) / s2;
@@ -1145,25 +1150,29 @@ __global__ void k_sv_accept(int C, const R* j1, const R* j2, const R* ell1, cons
 }
 
 // ---- the two factories of state-space pseudo-observations: what sweep_ss asks of a model family -------------------------------------------------------
-// plan: the factory's own buffers; obs: the pseudo-observations ys (second order: and their covariances Rs) linearised at xlin -- eps: the noise that forms u
+// data: the descriptor of the data the array-free passes and the one-pass log-density read; plan: the factory's own buffers; obs: the pseudo-observations ys (second order: and their covariances Rs) linearised at xlin -- eps: the noise that forms u
 // on the way, or null when u exists (the reverse move); terms [5][C]: pot(x'), pot(x), the two auxiliary log-likelihoods and the correction, for k_sv_accept.
 // one_pass: the register path has every log-density of the ratio in one kernel (SampleEntry::sv_logpdf), which is then taken instead of the joints + terms.
 
-// f(the pointwise potential as a compile-time constant)
-template <typename F> static void by_pointwise(int kind, F&& f) {
-    if (kind == PW_POISSON) f(std::integral_constant<int, PW_POISSON>{});
-    else f(std::integral_constant<int, PW_SV>{});
-}
-// SV_* / POISSON_*: log g_t = sum_k f(y_tk, x_tk), a diagonal Hessian (k_sv_obs, k_sv_terms above); every layout and width
+// SV_* / POISSON_* / LOGISTIC_*: log g_t = sum_k f(y_tk, [m_tk,] x_tk), a diagonal Hessian (k_sv_obs, k_sv_terms above); every layout and width
 template <typename R> struct PointwiseFactory {
     static constexpr bool one_pass = true;
     void plan(WsPlan&, const SweepCall&) {}
+    // the data as the kernels of a kind read it.  A kind with a size array (model->cs = m (T, dx) with yobs's time stride: pointwise_size_args) finds it as batch 1
+    // of the data's descriptor: the batch stride, free on chain-shared unbatched data, is the distance from y to m in reals (kalman_bodies.h::PwSize)
+    static Arr data(const SweepCall& c) {
+        Arr y = cv(*c.yobs);
+        by_pointwise(c.kind, [&](auto kind) {
+            if (Pointwise<R, decltype(kind)::value>::kHasSize) y.sb = ((const R*)c.model->cs.ptr - (const R*)c.yobs->ptr);
+        });
+        return y;
+    }
     int obs(const SweepCall& c, const R* xlin, const R* eps, R* u, R* ys, R* Rs) {
         const int C = c.dims->C, T = c.dims->T, D = c.dims->dx;
         const long long tot = (long long)C * T * D;
         by_pointwise(c.kind, [&](auto kind) {
             hipLaunchKernelGGL((k_sv_obs<R, decltype(kind)::value>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c.h->stream, tot, C, T, D, c.order, c.cm(), xlin, eps,
-                               eps ? (R)c.shd() : (R)0, (R)c.delta, c.dptr, cv(*c.yobs), u, ys, Rs);
+                               eps ? (R)c.shd() : (R)0, (R)c.delta, c.dptr, data(c), u, ys, Rs);
         });
         return AUXSSM_OK;
     }
@@ -1171,7 +1180,7 @@ template <typename R> struct PointwiseFactory {
         const int C = c.dims->C;
         by_pointwise(c.kind, [&](auto kind) {
             hipLaunchKernelGGL((k_sv_terms<R, decltype(kind)::value>), dim3(C), dim3(256), 0, c.h->stream, C, c.dims->T, c.dims->dx, (R)c.delta, c.dptr, (const R*)c.x, xp, u,
-                               cv(*c.yobs), ys1, ys2, Rs1, Rs2, out);
+                               data(c), ys1, ys2, Rs1, Rs2, out);
         });
         return AUXSSM_OK;
     }
@@ -1182,6 +1191,7 @@ template <typename R> struct PointwiseFactory {
 template <typename R> struct PlinFactory {
     static constexpr bool one_pass = false;
     Acc *pot1, *pot2, *part;  // the potential per (chain, step) at either linearisation point, as obs leaves it for terms
+    static Arr data(const SweepCall& c) { return cv(*c.yobs); }
     void plan(WsPlan& ws, const SweepCall& c) {
         const size_t CT = (size_t)c.dims->C * c.dims->T;
         ws.add(pot1, CT * sizeof(Acc));
@@ -1327,6 +1337,7 @@ template <typename R, typename Factory> static int sweep_ss(const SweepCall& c) 
             fa.sv_kind = c.kind;
             fa.sv_delta = delta;
             set_aux_fly(fa, c, 0, xlin, eps, uA);
+            fa.aux_yobs = Factory::data(c);
         }
         if (overlap || wide_carrier) fa.mask_ys = Arr{mask_carrier, 0, (long long)D, 0, 1};
         if (wide_ps_once && wide_gtab) fa.pc = wide_gtab;
@@ -1365,7 +1376,7 @@ template <typename R, typename Factory> static int sweep_ss(const SweepCall& c) 
         SvLogpdfArgs la;
         la.d = kd;
         la.m0 = cv(model->m0); la.P0 = cv(model->P0); la.Fs = cv(model->Fs); la.Qs = cv(model->Qs); la.bs = cv(model->bs);
-        la.yobs = cv(*yobs);
+        la.yobs = Factory::data(c);
         la.x = xA; la.xp = xpA; la.u = uA; la.ys1 = y1A; la.ys2 = y2A; la.R1 = R1A; la.R2 = R2A;
         la.delta = delta;
         la.dptr = dptr;
@@ -1586,6 +1597,21 @@ static int pointwise_args(const auxssm_dims* dims, const auxssm_lgssm* model, co
     }
     return AUXSSM_OK;
 }
+// LOGISTIC_*: the pointwise checks, and the size array m (T, dx) in the cs slot: shared by the chains and laid out as the data is (PointwiseFactory::data)
+static int pointwise_size_args(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs) {
+    const int rc = pointwise_args(dims, model, yobs);
+    if (rc) return rc;
+    if (!model->cs.ptr || model->cs.sc != 0) {
+        set_error("the logistic (binomial / negative-binomial) model needs its size array m (T, dx) in the cs slot, shared by the chains (chain stride 0)");
+        return AUXSSM_ERR_ARG;
+    }
+    if (yobs && model->cs.st != yobs->st) {
+        set_error("the size array m (T, dx) in the cs slot is laid out as yobs is: its time stride (%lld) must equal yobs's (%lld)", (long long)model->cs.st,
+                  (long long)yobs->st);
+        return AUXSSM_ERR_ARG;
+    }
+    return AUXSSM_OK;
+}
 static int lorenz_args(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr*) {
     if (!model || !model->m0.ptr || !model->P0.ptr || !model->Fs.ptr || !model->Qs.ptr || !model->Hs.ptr || !model->Rs.ptr || !model->cs.ptr) {
         set_error("Lorenz model needs m0, P0, Fs (= [theta1, theta2, theta3, dt] on the device), Qs, Hs, Rs, cs");
@@ -1649,6 +1675,7 @@ static int plin_limits(const auxssm_dims* dims, int layout, int) {
 //                                      obs_model  noise_arrays  args            limits       driver
 static const SweepFamily FAM_LG_CONCAT{true, false, lg_concat_args, nullptr, AX_SWEEP_DRIVER(sweep_lg_concat<R>)};
 static const SweepFamily FAM_POINTWISE{false, true, pointwise_args, nullptr, AX_SWEEP_DRIVER(sweep_ss<R, PointwiseFactory<R>>)};
+static const SweepFamily FAM_POINTWISE_SIZE{false, true, pointwise_size_args, nullptr, AX_SWEEP_DRIVER(sweep_ss<R, PointwiseFactory<R>>)};
 static const SweepFamily FAM_LORENZ{true, true, lorenz_args, nullptr, AX_SWEEP_DRIVER(sweep_lorenz<R>)};
 static const SweepFamily FAM_MVT{false, true, mvt_args, mvt_limits, AX_SWEEP_DRIVER(sweep_mvt<R>)};
 static const SweepFamily FAM_PLIN{false, true, plin_args, plin_limits, AX_SWEEP_DRIVER(sweep_ss<R, PlinFactory<R>>)};
@@ -1667,6 +1694,8 @@ static const struct KModelRow {
     {AUXSSM_KMODEL_POISSON_SECOND, &FAM_POINTWISE, 2, PW_POISSON},
     {AUXSSM_KMODEL_POISSON_LIN_FIRST, &FAM_PLIN, 1, 0},
     {AUXSSM_KMODEL_POISSON_LIN_SECOND, &FAM_PLIN, 2, 0},
+    {AUXSSM_KMODEL_LOGISTIC_FIRST, &FAM_POINTWISE_SIZE, 1, PW_LOGISTIC},
+    {AUXSSM_KMODEL_LOGISTIC_SECOND, &FAM_POINTWISE_SIZE, 2, PW_LOGISTIC},
 };
 static const KModelRow* kmodel_row(int model_kind) {
     for (const KModelRow& r : KMODELS)

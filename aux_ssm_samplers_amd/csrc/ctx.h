@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/auxssm.h"
@@ -12,6 +13,15 @@ namespace ax {
 
 void set_error(const char* fmt, ...);
 void fk_modules_release(auxssm_ctx* h);  // fk_program.hip
+
+// f(the pointwise potential of the SV sweep as a compile-time constant: kalman_bodies.h::PwKind) -- the one place a run-time kind chooses an instantiation
+template <typename F> void by_pointwise(int kind, F&& f) {
+    switch (kind) {
+        case PW_POISSON: f(std::integral_constant<int, PW_POISSON>{}); break;
+        case PW_LOGISTIC: f(std::integral_constant<int, PW_LOGISTIC>{}); break;
+        default: f(std::integral_constant<int, PW_SV>{}); break;
+    }
+}
 
 #define AX_HIP(expr)                                                                         \
     do {                                                                                     \

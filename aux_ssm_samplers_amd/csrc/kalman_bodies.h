@@ -143,7 +143,7 @@ struct FilterArgs {
     // step in information form (FilterOpFlySV below).  sv_delta = the step size; no_moments: the pass is run for its log-likelihood only (the reverse filter
     // of a sweep): ms / Ps rows t >= 1 are not written.
     int sv_order = 0;
-    int sv_kind = 0;  // which pointwise potential the factories linearise (PW_SV / PW_POISSON below)
+    int sv_kind = 0;  // which pointwise potential the factories linearise (PwKind below)
     double sv_delta = 0;
     int no_moments = 0;
     int dx = 0, dy = 0;  // runtime sizes, read by the wide-state path (wide.hip) only
@@ -531,26 +531,62 @@ template <typename R, int D, int P> AX_HD void body_obs_info_tab(const FilterArg
 //   PW_POISSON  y ~ Poisson(e^x):   e = e^x, f = y x - e, grad = y - e, lam = e, all three 0 for a missing (non-finite) y (csmc_sweep.h::pois_term's rule; the
 //               -log y! constant is left out).  Nothing is ever NaN: a missing count leaves the component observed through u with variance delta/2 in both
 //               orders, so the sites' "unobserved component" branches are dead for this kind and are dropped at compile time.  e^x is not guarded against overflow.
-enum PwKind : int { PW_SV = 0, PW_POISSON = 1 };
+//   PW_LOGISTIC y successes of m trials at probability sigma(x) (binomial, m = n), or y ~ NB(r, p = sigma(x)) (negative binomial, m = y + r): one function,
+//               f = y x - m softplus(x), grad = y - m sigma(x), lam = m sigma(x) (1 - sigma(x)), all three 0 for a missing (non-finite) y whatever m is; the
+//               combinatorial constants are left out.  The SIZE m is a second per-observation number (kHasSize): a chain-shared (T, D) array with y's
+//               strides, which the data's own descriptor carries as its batch 1 (PwSize below), loaded under `if constexpr` only.  core() is e = exp(-|x|) <= 1, so nothing
+//               overflows at any x: r = 1 / (1 + e), sigma = x >= 0 ? r : e r, 1 - sigma the mirrored form (never a subtraction), so sigma (1 - sigma) =
+//               (e r) r on either side; softplus = max(x, 0) + log1p(e), the logarithm paid by the value sites alone.  Never NaN, as PW_POISSON.
+enum PwKind : int { PW_SV = 0, PW_POISSON = 1, PW_LOGISTIC = 2 };
 template <typename R, int KIND> struct Pointwise;
 template <typename R> struct Pointwise<R, PW_SV> {
-    static constexpr bool kMissingNaN = true;
+    static constexpr bool kMissingNaN = true, kHasSize = false;
     static AX_HD R core(R y, R x) { return y * y * exp_(-x); }
-    static AX_HD R value(R, R x, R w) { return nan_to_num<R>((R)(-0.5 * LOG_2PI) - (R)0.5 * x - (R)0.5 * w); }
+    static AX_HD R value(R, R, R x, R w) { return nan_to_num<R>((R)(-0.5 * LOG_2PI) - (R)0.5 * x - (R)0.5 * w); }
     // (k_sv_terms' one-expression form: contraction places its multiply-add inside the product, so it is kept as a statement of its own)
-    static AX_HD R value(R y, R x) { return nan_to_num<R>((R)(-0.5 * LOG_2PI) - (R)0.5 * x - (R)0.5 * y * y * exp_(-x)); }
-    static AX_HD R grad(R, R w) { return nan_to_num<R>((R)0.5 * (w - (R)1)); }
-    static AX_HD R lam(R, R w) { return (R)0.5 * w; }
+    static AX_HD R value(R y, R, R x) { return nan_to_num<R>((R)(-0.5 * LOG_2PI) - (R)0.5 * x - (R)0.5 * y * y * exp_(-x)); }
+    static AX_HD R grad(R, R, R, R w) { return nan_to_num<R>((R)0.5 * (w - (R)1)); }
+    static AX_HD R lam(R, R, R, R w) { return (R)0.5 * w; }
     static AX_HD bool missing(R w) { return !finite_(w); }  // (k_sv_obs: ys = om (...) is NaN exactly when w is NaN or infinite)
 };
 template <typename R> struct Pointwise<R, PW_POISSON> {
-    static constexpr bool kMissingNaN = false;
+    static constexpr bool kMissingNaN = false, kHasSize = false;
     static AX_HD R core(R, R x) { return exp_(x); }
-    static AX_HD R value(R y, R x, R e) { return finite_(y) ? y * x - e : (R)0; }
-    static AX_HD R value(R y, R x) { return value(y, x, core(y, x)); }
-    static AX_HD R grad(R y, R e) { return finite_(y) ? y - e : (R)0; }
-    static AX_HD R lam(R y, R e) { return finite_(y) ? e : (R)0; }
+    static AX_HD R value(R y, R, R x, R e) { return finite_(y) ? y * x - e : (R)0; }
+    static AX_HD R value(R y, R m, R x) { return value(y, m, x, core(y, x)); }
+    static AX_HD R grad(R y, R, R, R e) { return finite_(y) ? y - e : (R)0; }
+    static AX_HD R lam(R y, R, R, R e) { return finite_(y) ? e : (R)0; }
     static AX_HD bool missing(R) { return false; }
+};
+template <typename R> struct Pointwise<R, PW_LOGISTIC> {
+    static constexpr bool kMissingNaN = false, kHasSize = true;
+    static AX_HD R core(R, R x) { return exp_(-abs_(x)); }
+    static AX_HD R value(R y, R m, R x, R e) { return finite_(y) ? y * x - m * (max_(x, (R)0) + log1p_(e)) : (R)0; }
+    static AX_HD R value(R y, R m, R x) { return value(y, m, x, core(y, x)); }
+    static AX_HD R grad(R y, R m, R x, R e) {
+        const R r = (R)1 / ((R)1 + e);
+        return finite_(y) ? y - m * (x >= (R)0 ? r : e * r) : (R)0;
+    }
+    static AX_HD R lam(R y, R m, R, R e) {
+        const R r = (R)1 / ((R)1 + e);
+        return finite_(y) ? m * ((e * r) * r) : (R)0;
+    }
+    static AX_HD bool missing(R) { return false; }
+};
+// Row t of a kind's size array in registers; a kind without one holds nothing, loads nothing and reads as 0 (an argument its Pointwise functions ignore).
+// The array has no field of its own in the argument structs: the data y (T, D) is chain-shared and unbatched, so its descriptor's batch stride is free, and the
+// sweep sets it to the distance from y to m in reals (api.hip::PointwiseFactory::data) -- m is batch 1 of y's descriptor, with y's time stride.  (A trailing Arr
+// in FilterArgs was tried first: the larger kernel argument moved the registers of 114 kernels that never read it, k_scan_reduce of every filter among them.)
+// This struct is for the scan operator's Raw record and sv_step_info; body_filter_t0_sv and sv_step_terms hold a plain array under `if constexpr` instead: a
+// local PwSize there, empty as it is for SV and Poisson, moved the registers of k_filter_t0_sv<float, 3 | 4> and k_sv_logpdf<float, 1, PW_SV>.
+template <typename R, int D, bool HAS> struct PwSize {
+    AX_HD void load(const Arr&, long long) {}
+    AX_HD R operator[](int) const { return (R)0; }
+};
+template <typename R, int D> struct PwSize<R, D, true> {
+    R v[D];
+    AX_HD void load(const Arr& y, long long t) { rd<R, D>(y, 0, t, 1, v); }
+    AX_HD R operator[](int k) const { return v[k]; }
 };
 
 // ---- the SV factories without observation arrays (FilterArgs::sv_order) -----------------------------------------------------------------
@@ -563,7 +599,8 @@ template <typename R> struct Pointwise<R, PW_POISSON> {
 // component by component): the step then takes the folded form with that component's precision and information zero.
 // Other kinds (Pointwise above) go through the same split with their own grad / lam; a kind whose pseudo-observations are never NaN (!kMissingNaN) has
 // miss[] = false at compile time and the folded branch below is not compiled for it: every step has dim = D.
-template <typename R, int D, int KIND = PW_SV> AX_HD void sv_step_info(const FilterArgs& a, const R* x, const R* u, const R* y, StepInfo<R, D>& si) {
+template <typename R, int D, int KIND = PW_SV>
+AX_HD void sv_step_info(const FilterArgs& a, const R* x, const R* u, const R* y, const PwSize<R, D, Pointwise<R, KIND>::kHasSize>& m, StepInfo<R, D>& si) {
     using Pw = Pointwise<R, KIND>;
     const R delta = (R)a.sv_delta, av = (R)2 / delta;
     const bool second = a.sv_order != 1;
@@ -572,8 +609,8 @@ template <typename R, int D, int KIND = PW_SV> AX_HD void sv_step_info(const Fil
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         // (lam is taken outside the conditional: inside it the SV scan passes at D = 3, 4 allocate one register more, which at fp32 D = 3 costs a wave per SIMD)
-        const R yk = y[k], w = Pw::core(yk, x[k]), lw = Pw::lam(yk, w);
-        grad[k] = Pw::grad(yk, w);
+        const R yk = y[k], w = Pw::core(yk, x[k]), lw = Pw::lam(yk, m[k], x[k], w);
+        grad[k] = Pw::grad(yk, m[k], x[k], w);
         lam[k] = second ? lw : (R)0;
         g[k] = second ? grad[k] + lam[k] * x[k] : (R)0;
         if constexpr (Pw::kMissingNaN) miss[k] = second && Pw::missing(w);
@@ -628,6 +665,8 @@ template <typename R, int D, int KIND = PW_SV> AX_HD void body_filter_t0_sv(cons
     rd<R, D * D>(a.P0, c, 0, b, Pd);
     rd<R, D>(a.aux_x, c, 0, b, x);
     rd<R, D>(a.aux_yobs, 0, 0, 0, y);
+    R sz[Pw::kHasSize ? D : 1];   // (PwSize's note: a plain array under `if constexpr` here)
+    if constexpr (Pw::kHasSize) rd<R, D>(a.aux_yobs, 0, 0, 1, sz);
     if (a.aux_eps.ptr) {
         R eps[D];
         rd<R, D>(a.aux_eps, c, 0, b, eps);
@@ -642,14 +681,16 @@ template <typename R, int D, int KIND = PW_SV> AX_HD void body_filter_t0_sv(cons
     for (int k = 0; k < D * D; ++k) H[k] = (k / D == k % D) ? (R)1 : (R)0, Rm[k] = 0;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
+        R mk = 0;
+        if constexpr (Pw::kHasSize) mk = sz[k];
         const R w = Pw::core(y[k], x[k]);
-        const R grad = Pw::grad(y[k], w);
+        const R grad = Pw::grad(y[k], mk, x[k], w);
         cv[k] = 0;
         if (a.sv_order == 1) {
             ys[k] = u[k] + (R)0.5 * delta * grad;
             Rm[k * D + k] = (R)0.5 * delta;
         } else {
-            const R hess = -Pw::lam(y[k], w);
+            const R hess = -Pw::lam(y[k], mk, x[k], w);
             const R om = (R)1 / (-hess + (R)2 / delta);
             ys[k] = om * ((R)2 * u[k] / delta + grad - hess * x[k]);
             Rm[k * D + k] = om;
@@ -669,6 +710,7 @@ template <typename R_, int D, bool WRITE_U, int KIND = PW_SV> struct FilterOpFly
     using Args = FilterArgs;
     struct Raw {
         R F[D * D], Q[D * D], bd[D], x[D], ue[D], y[D];
+        PwSize<R, D, Pointwise<R, KIND>::kHasSize> m;
     };
     static AX_HD void load_raw(const Args& a, int s, int i, Raw& r) {
         const int c = s / a.d.B, b = s % a.d.B;
@@ -677,6 +719,7 @@ template <typename R_, int D, bool WRITE_U, int KIND = PW_SV> struct FilterOpFly
         if (a.aux_eps.ptr) rd<R, D>(a.aux_eps, c, t, b, r.ue);
         else rd<R, D>(a.aux_u, c, t, b, r.ue);
         rd<R, D>(a.aux_yobs, 0, t, 0, r.y);
+        r.m.load(a.aux_yobs, t);
         rd<R, D * D>(a.Fs, c, i, b, r.F);
         rd<R, D>(a.bs, c, i, b, r.bd);
         rd<R, D * D>(a.Qs, c, i, b, r.Q);
@@ -688,7 +731,7 @@ template <typename R_, int D, bool WRITE_U, int KIND = PW_SV> struct FilterOpFly
         if constexpr (WRITE_U) {
             if (a.aux_eps.ptr) wr<R, D>(a.aux_u, s / a.d.B, (long long)i + 1, s % a.d.B, u);
         }
-        sv_step_info<R, D, KIND>(a, r.x, u, r.y, si);
+        sv_step_info<R, D, KIND>(a, r.x, u, r.y, r.m, si);
     }
     static AX_HD void write_out(const Args& a, int s, int i, const Pre& p) {
         if (!a.no_moments) Base::write_out(a, s, i, p);
@@ -1512,7 +1555,7 @@ template <typename R, int PO> AX_HD void body_lorenz_logpdf_head(const SweepLogp
 struct SvLogpdfArgs {
     KDims d;
     Arr m0, P0, Fs, Qs, bs;  // linear-Gaussian dynamics
-    Arr yobs;                // (T, D), chain-shared
+    Arr yobs;                // (T, D), chain-shared; a pointwise kind with a size array (Pointwise::kHasSize) reads it as batch 1 of this descriptor (PwSize)
     Arr x, xp, u, ys1, ys2;  // (C, T, D)
     Arr R1, R2;              // (C, T, D, D), ptr null for the first-order factory
     double delta;
@@ -1548,6 +1591,8 @@ AX_HD void sv_step_terms(const SvLogpdfArgs& a, int c, long long t, const R* x, 
     R u[D], y[D], y1[D], y2[D];
     rd<R, D>(a.u, c, t, 0, u);
     rd<R, D>(a.yobs, 0, t, 0, y);
+    R m[Pw::kHasSize ? D : 1];
+    if constexpr (Pw::kHasSize) rd<R, D>(a.yobs, 0, t, 1, m);
     if (!a.fly_order) {
         rd<R, D>(a.ys1, c, t, 0, y1);
         rd<R, D>(a.ys2, c, t, 0, y2);
@@ -1557,20 +1602,22 @@ AX_HD void sv_step_terms(const SvLogpdfArgs& a, int c, long long t, const R* x, 
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         const R av = xp[k], bv = x[k];
+        R mk = 0;
+        if constexpr (Pw::kHasSize) mk = m[k];
         // the two exponentials serve the potentials and (fly) the pseudo-observations: 0.5 * (y y e) is (0.5 y) y e bit for bit (scaling by a power of two)
         const R wb = Pw::core(y[k], bv), wa = Pw::core(y[k], av);
-        pp += Pw::value(y[k], av, wa);
-        px += Pw::value(y[k], bv, wb);
+        pp += Pw::value(y[k], mk, av, wa);
+        px += Pw::value(y[k], mk, bv, wb);
         R t1, t2;   // the auxiliary precisions 1 / R1_kk, 1 / R2_kk
         if (a.fly_order) {
             // k_sv_obs's pseudo-observations, re-formed: the proposal's are linearised at x (and scored at xp), the reverse move's at xp
-            const R gb = Pw::grad(y[k], wb), ga = Pw::grad(y[k], wa);
+            const R gb = Pw::grad(y[k], mk, bv, wb), ga = Pw::grad(y[k], mk, av, wa);
             if (a.fly_order == 1) {
                 y1[k] = u[k] + (R)0.5 * delta * gb;
                 y2[k] = u[k] + (R)0.5 * delta * ga;
                 t1 = t2 = a2;
             } else {
-                const R hb = -Pw::lam(y[k], wb), ha = -Pw::lam(y[k], wa);
+                const R hb = -Pw::lam(y[k], mk, bv, wb), ha = -Pw::lam(y[k], mk, av, wa);
                 t1 = -hb + a2;
                 t2 = -ha + a2;
                 const R iv = (R)1 / (t1 * t2);   // one division for the two variances Om = 1 / t

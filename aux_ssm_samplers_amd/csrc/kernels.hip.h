@@ -1265,17 +1265,21 @@ template <typename R, int D, int P> int run_filter(auxssm_ctx* h, const FilterAr
                 return AUXSSM_ERR_ARG;
             }
             // (the potential's kind is a template argument of the three kernels: sv_scan_kind)
-            const bool pois = a_in.sv_kind == PW_POISSON;
-            if (pois) hipLaunchKernelGGL((k_filter_t0_sv<R, D, PW_POISSON>), dim3((S + TB_ELEM - 1) / TB_ELEM), dim3(TB_ELEM), 0, h->stream, a);
-            else hipLaunchKernelGGL((k_filter_t0_sv<R, D, PW_SV>), dim3((S + TB_ELEM - 1) / TB_ELEM), dim3(TB_ELEM), 0, h->stream, a);
             if (n > 0) {
                 a.elem = nullptr;
                 a.ellz = ws_take(h, (size_t)S * a.lay.nchunk * sizeof(R));
                 if (!a.ellz) return AUXSSM_ERR_NOMEM;
-                ProfScope ps(h, AUXSSM_K_FILTER_SCAN);
-                const int rc = pois ? sv_scan_kind<R, D, PW_POISSON>(h, a, S, n) : sv_scan_kind<R, D, PW_SV>(h, a, S, n);
-                if (rc) return rc;
             }
+            int rc = AUXSSM_OK;
+            by_pointwise(a_in.sv_kind, [&](auto kind) {
+                constexpr int K = decltype(kind)::value;
+                hipLaunchKernelGGL((k_filter_t0_sv<R, D, K>), dim3((S + TB_ELEM - 1) / TB_ELEM), dim3(TB_ELEM), 0, h->stream, a);
+                if (n > 0) {
+                    ProfScope ps(h, AUXSSM_K_FILTER_SCAN);
+                    rc = sv_scan_kind<R, D, K>(h, a, S, n);
+                }
+            });
+            if (rc) return rc;
             hipLaunchKernelGGL((k_reduce_rows<R>), dim3(a.d.C), dim3(TB_ELEM), 0, h->stream, (const R*)a.ellz, (const R*)a.ell0, a.d.B, n > 0 ? a.lay.nchunk : 0, (R*)ell_out);
             AX_HIP(hipGetLastError());
             return AUXSSM_OK;
@@ -1540,11 +1544,11 @@ template <typename R, int D> int run_sv_logpdf(auxssm_ctx* h, const SvLogpdfArgs
     const int nt = cm ? ((n + TI - 1) / TI > 0 ? (n + TI - 1) / TI : 1) : (ntiles(n) > 0 ? ntiles(n) : 1);
     Acc* part = (Acc*)ws_take(h, (size_t)5 * C * nt * sizeof(Acc));
     ProfScope ps(h, AUXSSM_K_LOGPDF);
-    const bool pois = a.kind == PW_POISSON;
-    if (cm && pois) hipLaunchKernelGGL((k_sv_logpdf_cm<R, D, PW_POISSON>), dim3(grid_cm(C, n, TI)), dim3(TB_CM), 0, h->stream, a, part, nt, TI);
-    else if (cm) hipLaunchKernelGGL((k_sv_logpdf_cm<R, D, PW_SV>), dim3(grid_cm(C, n, TI)), dim3(TB_CM), 0, h->stream, a, part, nt, TI);
-    else if (pois) hipLaunchKernelGGL((k_sv_logpdf<R, D, PW_POISSON>), dim3(grid_tile_seq(nt, C)), dim3(TB_ELEM), 0, h->stream, a, part, nt);
-    else hipLaunchKernelGGL((k_sv_logpdf<R, D, PW_SV>), dim3(grid_tile_seq(nt, C)), dim3(TB_ELEM), 0, h->stream, a, part, nt);
+    by_pointwise(a.kind, [&](auto kind) {
+        constexpr int K = decltype(kind)::value;
+        if (cm) hipLaunchKernelGGL((k_sv_logpdf_cm<R, D, K>), dim3(grid_cm(C, n, TI)), dim3(TB_CM), 0, h->stream, a, part, nt, TI);
+        else hipLaunchKernelGGL((k_sv_logpdf<R, D, K>), dim3(grid_tile_seq(nt, C)), dim3(TB_ELEM), 0, h->stream, a, part, nt);
+    });
     hipLaunchKernelGGL((k_reduce_rows<Acc>), dim3(5 * C), dim3(TB_ELEM), 0, h->stream, (const Acc*)part, (const Acc*)nullptr, 1, nt, (Acc*)out);
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;

@@ -30,6 +30,8 @@ AX_HD float sqrt_(float x) { return sqrtf(x); }
 AX_HD double sqrt_(double x) { return sqrt(x); }
 AX_HD float log_(float x) { return logf(x); }
 AX_HD double log_(double x) { return log(x); }
+AX_HD float log1p_(float x) { return log1pf(x); }
+AX_HD double log1p_(double x) { return log1p(x); }
 AX_HD float exp_(float x) { return expf(x); }
 AX_HD double exp_(double x) { return exp(x); }
 AX_HD float abs_(float x) { return fabsf(x); }

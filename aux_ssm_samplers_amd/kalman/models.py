@@ -318,6 +318,122 @@ class PoissonLinearModel(_StateSpaceModel):
         return dl
 
 
+class _LogisticModel(_StateSpaceModel):
+    """What BinomialModel and NegBinomialModel share: one potential with a logit link and a SIZE m (T, dx) beside the data.  With mask = isfinite(y),
+    e = exp(-|x|), r = 1 / (1 + e), sigma = where(x >= 0, r, e r) and 1 - sigma its mirror image (never a subtraction), per component
+
+        log g = where(mask, y x - m softplus(x), 0)      grad = where(mask, y - m sigma, 0)      lam = -hess = where(mask, m (e r) r, 0) >= 0
+
+    with softplus(x) = max(x, 0) + log1p(e): the device's form (csrc/kalman_bodies.h, Pointwise<R, PW_LOGISTIC>), finite at every x.  A subclass validates its
+    data and hands in m; where y is missing, m is never looked at."""
+    KMODELS = (_lib.KMODEL_LOGISTIC_FIRST, _lib.KMODEL_LOGISTIC_SECOND)
+
+    def __init__(self, ys, size, m0, P0, F, Q, b, order):
+        super().__init__(ys, m0, P0, F, Q, b, order)
+        self.size = np.asarray(size, np.float64)
+
+    @staticmethod
+    def _per_observation(a, shape, name):
+        """a scalar, (dx,) or (T, dx) parameter as a (T, dx) float64 array"""
+        a = np.asarray(a, np.float64)
+        if a.ndim > 2 or (a.ndim == 2 and a.shape != shape) or (a.ndim == 1 and a.shape != shape[1:]):
+            raise ValueError(f"{name} must be a scalar, ({shape[1]},) or {shape}, got shape {a.shape}")
+        return np.array(np.broadcast_to(a, shape))
+
+    def _terms(self, x):
+        """(mask, y, m, e, r) at x (T, dx), the data in x's dtype"""
+        e = np.exp(-np.abs(x))
+        return np.isfinite(self.yobs), self.yobs.astype(x.dtype), self.size.astype(x.dtype), e, 1.0 / (1.0 + e)
+
+    def log_potential(self, x):
+        x = np.asarray(x)
+        mask, y, m, e, _ = self._terms(x)
+        with np.errstate(invalid="ignore"):
+            return float(np.sum(np.where(mask, y * x - m * (np.maximum(x, 0.0) + np.log1p(e)), 0.0)))
+
+    def grad_lam(self, x):
+        """(grad, lam) of log g, both (T, dx) and 0 where the observation is missing"""
+        x = np.asarray(x)
+        mask, y, m, e, r = self._terms(x)
+        with np.errstate(invalid="ignore"):
+            return np.where(mask, y - m * np.where(x >= 0, r, e * r), 0.0), np.where(mask, m * ((e * r) * r), 0.0)
+
+    def _upload(self, handle, dtype):
+        dl = super()._upload(handle, dtype)
+        # include/auxssm.h, LOGISTIC_FIRST / _SECOND: the size array (T, dx), laid out as the data is (time stride dx), rides in the cs slot
+        buf = dl.bufs["logistic_size"] = handle.to_device(np.ascontiguousarray(self.size, np.float64), dtype)
+        dl.c.cs = buf.arr(0, self.dx, 0)
+        return dl
+
+
+class BinomialModel(_LogisticModel):
+    """Binomial data with a logit link  y_{t,k} ~ Binomial(trials_{t,k}, sigma(x_{t,k}))  on linear-Gaussian dynamics x_{t+1} = F x_t + b + N(0, Q),
+    x_0 ~ N(m0, P0), under the first- or second-order auxiliary observation factories of examples/stochastic_volatility/auxiliary_kalman.py:22-48.  ys (T, dx):
+    successes; trials: a scalar, (dx,) or (T, dx), > 0; binary data (spike / no spike, rain / no rain) is trials = 1.  The other arguments are SVModel's.
+
+        log g = where(mask, y x - trials softplus(x), 0)   grad = where(mask, y - trials sigma(x), 0)   lam = -hess = where(mask, trials sigma (1 - sigma), 0)
+
+        dynamics_factory(x)           -> m0, P0, tile(F), tile(Q), tile(b)
+        observations_factory(x, u, d) -> order 1: ys = u + d/2 grad, H = I, R = d/2 I, c = 0
+                                         order 2: Om = 1 / (lam + 2/d) (diagonal), ys = Om (2u/d + grad + lam x), H = I, R = diag(Om), c = 0
+        log_likelihood_fn(x)          -> prior_logpdf(x) + sum log g
+
+    The conventions are PoissonModel's: the constant log C(trials, y) is left out, non-integer values are accepted, a NaN y_{t,k} drops that component's term
+    alone (trials may then be anything), and no pseudo-observation is ever NaN.  A finite y outside [0, trials], trials <= 0, or a non-finite trials under a
+    finite y raises ValueError.  The potential is concave and evaluated through exp(-|x|), so both orders are defined and finite at every x.
+
+    Pass the three bound methods to kalman.get_kernel: it runs the device sweep (model kind LOGISTIC_FIRST / LOGISTIC_SECOND: the SV sweep's kernels
+    instantiated for this potential, every layout and width SVModel has).  The same methods are NumPy factories for the host path and the oracle."""
+
+    def __init__(self, ys, trials, m0, P0, F, Q, b, order=1):
+        ys = np.asarray(ys)
+        if ys.ndim != 2:
+            raise ValueError(f"BinomialModel: ys must be (T, dx), got shape {ys.shape}")
+        n = self._per_observation(trials, ys.shape, "BinomialModel: trials")
+        seen = np.isfinite(np.asarray(ys, np.float64))
+        if np.any(seen & ~np.isfinite(n)):
+            raise ValueError("BinomialModel: trials must be finite wherever y is observed")
+        if np.any(n[np.isfinite(n)] <= 0):
+            raise ValueError(f"BinomialModel: trials must be > 0; got a minimum of {float(np.nanmin(n))}")
+        yv = np.asarray(ys, np.float64)
+        if np.any(seen & ((yv < 0) | (yv > np.where(seen, n, np.inf)))):
+            raise ValueError("BinomialModel: every observed y must lie in [0, trials]")
+        super().__init__(ys, n, m0, P0, F, Q, b, order)
+        self.trials = n
+
+
+class NegBinomialModel(_LogisticModel):
+    """Overdispersed counts  y_{t,k} ~ NB(r_{t,k}, p = sigma(x_{t,k})),  pmf proportional to p^y (1 - p)^r: mean r e^x, variance mean (1 + e^x), on
+    linear-Gaussian dynamics x_{t+1} = F x_t + b + N(0, Q), x_0 ~ N(m0, P0), under the first- or second-order auxiliary observation factories of
+    examples/stochastic_volatility/auxiliary_kalman.py:22-48.  ys (T, dx): counts >= 0; r: a scalar, (dx,) or (T, dx), > 0.  The other arguments are SVModel's.
+
+        log g = where(mask, y x - (y + r) softplus(x), 0)   grad = where(mask, y - (y + r) sigma(x), 0)   lam = -hess = where(mask, (y + r) sigma (1 - sigma), 0)
+
+    and the factories are BinomialModel's with trials = y + r: on the device the two families are one model kind.  The state is the log-odds; the log-mean is
+    x + log r, so a log-mean parametrisation (or an exposure) is a shift of the state by log r through m0 and b -- there is no field for it.  The conventions are
+    PoissonModel's: the constant log Gamma(y + r) - log Gamma(r) - log y! is left out, non-integer counts are accepted, a finite negative count raises
+    ValueError, as does r <= 0 or a non-finite r under a finite y; a NaN y_{t,k} drops that component's term alone; no pseudo-observation is ever NaN.
+
+    Pass the three bound methods to kalman.get_kernel: it runs the device sweep (model kind LOGISTIC_FIRST / LOGISTIC_SECOND).  The same methods are NumPy
+    factories for the host path and the oracle."""
+
+    def __init__(self, ys, r, m0, P0, F, Q, b, order=1):
+        ys = np.asarray(ys)
+        if ys.ndim != 2:
+            raise ValueError(f"NegBinomialModel: ys must be (T, dx), got shape {ys.shape}")
+        rr = self._per_observation(r, ys.shape, "NegBinomialModel: r")
+        yv = np.asarray(ys, np.float64)
+        seen = np.isfinite(yv)
+        if np.any(seen & ~np.isfinite(rr)):
+            raise ValueError("NegBinomialModel: r must be finite wherever y is observed")
+        if np.any(rr[np.isfinite(rr)] <= 0):
+            raise ValueError(f"NegBinomialModel: r must be > 0; got a minimum of {float(np.nanmin(rr))}")
+        if np.any(yv[seen] < 0):
+            raise ValueError(f"NegBinomialModel: counts must be >= 0 or NaN (missing); got a minimum of {float(np.nanmin(yv))}")
+        super().__init__(ys, yv + rr, m0, P0, F, Q, b, order)
+        self.r = rr
+
+
 class LorenzModel(_BuiltinModel):
     """Stochastic Lorenz-63 with Euler-Maruyama dynamics and sparse linear-Gaussian observations,
     examples/lorenz/auxiliary_kalman.py:14-52 (model.py:10-25; linearisation.py:11-44 with the analytic Jacobian in place of jacfwd):

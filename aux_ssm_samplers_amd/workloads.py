@@ -140,6 +140,30 @@ def poisson_kalman_setup(T, dx, seed=0, order=1):
     return PoissonModel(y, M0.m0, M0.P0, Mt.F, Mt.Q, Mt.b, order=order), x
 
 
+def logistic_kalman_setup(T, dx, family="binomial", seed=0, order=1):
+    """Binomial or negative-binomial data with a logit link for the auxiliary Kalman sampler: AR(1) log-odds x_t = 0.9 x_{t-1} + eps_t per component, Q = 0.04 I,
+    m0 = b = 0, P0 = 0.2 I (about the stationary variance).  family "binomial": trials drawn from 1 .. 40 per observation, component 0 binary (trials = 1),
+    y ~ Binomial(trials, sigma(x)); "negbinomial": r = 3, y ~ NB(3, p = sigma(x)) (mean 3 e^x), drawn as a Gamma-Poisson mixture.
+    Returns (model, x0): a kalman.BinomialModel or kalman.NegBinomialModel and a start state (T, dx) -- the simulated log-odds."""
+    from aux_ssm_samplers_amd.kalman import BinomialModel, NegBinomialModel
+    rng = np.random.Generator(np.random.PCG64(seed))
+    F, Q, P0 = 0.9 * np.eye(dx), 0.04 * np.eye(dx), 0.2 * np.eye(dx)
+    m0, b = np.zeros(dx), np.zeros(dx)
+    x = np.zeros((T, dx))
+    x[0] = np.sqrt(0.2) * rng.standard_normal(dx)
+    for t in range(1, T):
+        x[t] = 0.9 * x[t - 1] + 0.2 * rng.standard_normal(dx)
+    if family == "binomial":
+        trials = rng.integers(1, 41, size=(T, dx)).astype(np.float64)
+        trials[:, 0] = 1.0
+        y = rng.binomial(trials.astype(np.int64), 1.0 / (1.0 + np.exp(-x))).astype(np.float64)
+        return BinomialModel(y, trials, m0, P0, F, Q, b, order=order), x
+    if family == "negbinomial":
+        y = rng.poisson(rng.gamma(3.0, np.exp(x))).astype(np.float64)
+        return NegBinomialModel(y, 3.0, m0, P0, F, Q, b, order=order), x
+    raise ValueError(f"family must be 'binomial' or 'negbinomial', got {family!r}")
+
+
 def poisson_lin_setup(T, dx, dy, seed=0, order=1):
     """Poisson counts through a loading matrix (a Poisson linear dynamical system): dy count channels on a dx-dimensional linear-Gaussian latent,
     y_{t,j} ~ Poisson(exp(h_j' x_t + c_j)).  F = 0.9 I with 0.05 / -0.05 beside the diagonal (poisson_setup's), m0 = b = 0, Q = 0.04 I, P0 = 0.2 I (about

@@ -245,7 +245,18 @@ typedef enum {
      * a NULL Hs / cs / yobs: AUXSSM_ERR_ARG; nothing enqueued).  auxssm_kalman_sweep, _dd and _keyed run them (csrc/kalman_plin.hip: one lane per (chain, step),
      * the counts staged through LDS in blocks of 64 channels); auxssm_kalman_sweep_fused refuses them. */
     AUXSSM_KMODEL_POISSON_LIN_FIRST = 11,
-    AUXSSM_KMODEL_POISSON_LIN_SECOND = 12
+    AUXSSM_KMODEL_POISSON_LIN_SECOND = 12,
+    /* Binomial and negative-binomial counts with a logit link on linear-Gaussian dynamics: the SV sweep above with the pointwise potential
+     * log g_t(x) = sum_k y_k x_k - m_k softplus(x_k), grad_k = y_k - m_k sigma(x_k), -hess_kk = m_k sigma(x_k) (1 - sigma(x_k)) >= 0, where the SIZE m_k is
+     * the number of trials n (binomial: y successes of n at probability sigma(x); binary data is n = 1) or y + r (negative binomial: y ~ NB(r, p = sigma(x)),
+     * mean r e^x).  The combinatorial constants are left out.  All three are 0 where y_{t,k} is NaN, whatever m is: a missing entry drops that component's
+     * term alone and leaves the component observed through u with variance d/2 in both orders (no pseudo-observation is ever NaN).  `model`: m0, P0, Fs, Qs,
+     * bs as usual; cs -> m (T, dx), a DEVICE array of `dtype` laid out as yobs is (the same time stride st, components contiguous), shared by the chains (chain stride 0; a
+     * NULL cs.ptr, another chain stride or a time stride that is not yobs's: AUXSSM_ERR_ARG, nothing enqueued); Hs, Rs unused.  Same layouts, widths and other checks as SV_FIRST / SV_SECOND;
+     * 0 <= y <= m is not checked here.  Evaluated through exp(-|x|): nothing overflows at any x.  auxssm_kalman_sweep, _dd and _keyed run them;
+     * auxssm_kalman_sweep_fused refuses them. */
+    AUXSSM_KMODEL_LOGISTIC_FIRST = 13,
+    AUXSSM_KMODEL_LOGISTIC_SECOND = 14
 } auxssm_kalman_model;
 typedef enum { AUXSSM_LAYOUT_DENSE = 0, AUXSSM_LAYOUT_CHAIN_MINOR = 1 } auxssm_layout;
 int auxssm_kalman_sweep(auxssm_handle h, int dtype, int model_kind, const auxssm_dims* dims,

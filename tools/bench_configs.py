@@ -13,6 +13,8 @@
              sweep at 1 / 16 / 256 chains beside the host-factory path
    poisson_kalman  count data under the auxiliary Kalman sampler (kalman.PoissonModel, fp32, both orders) at T = 250, dx = 30 and T = 16384, dx = 1, 1 / 64 / 256 /
              1024 chains, beside SVModel at the same shapes, the host-factory path and the Poisson cSMC sweep
+   logistic_kalman  binomial and negative-binomial data under the auxiliary Kalman sampler (kalman.BinomialModel / NegBinomialModel, fp32) at T = 16384, dx = 1 (both
+             orders) and T = 250, dx = 30 (first order), 1 / 64 / 256 / 1024 chains, beside PoissonModel at the same shapes and the host-factory path
    poisson_lin_kalman  Poisson counts through a loading matrix under the auxiliary Kalman sampler (kalman.PoissonLinearModel, T = 16384, dx = 4, dy = 128, fp32, both
              orders) at 1 / 64 / 256 dense resident chains, beside kalman.PoissonModel at T = 16384, dx = 4 on dense chains and the host-factory path of the new
              model; then the library's kernel-group times of one sweep.  poisson_lin_trace: a few sweeps alone, for a kernel trace taken from outside
@@ -620,6 +622,53 @@ def poisson_kalman(shapes=((250, 30), (16384, 1)), chain_counts=(1, 64, 256, 102
         del cc, st
 
 
+def logistic_kalman(shapes=((16384, 1, (1, 2)), (250, 30, (1,))), chain_counts=(1, 64, 256, 1024), runs=5, host_reps=3):
+    """binomial and negative-binomial data under the auxiliary Kalman sampler (kalman.BinomialModel / NegBinomialModel on workloads.logistic_kalman_setup), fp32,
+    resident chains, keyed noise, at the SV general-path shape (T = 16384, dx = 1, both orders: chain-minor from 32 chains) and at T = 250, dx = 30 (first order:
+    wide-state kernels, dense layout).  Beside every row, in the same process: PoissonModel at the same shape and step size (workloads.poisson_kalman_setup), the
+    three models' batches alternating -- a batch is as many back-to-back sweeps as fill ~0.2 s and ends in a stream synchronisation; best, median and worst batch
+    of `runs`.  Then, per shape and order, the host-factory path of the binomial model (the same methods behind lambdas, one chain).  Run the leg in several
+    processes and take the median of their medians."""
+    from aux_ssm_samplers_amd.workloads import logistic_kalman_setup, poisson_kalman_setup
+    h = _lib.default_handle()
+    names = ("Binomial", "NegBinomial", "Poisson")
+    for T, D, orders in shapes:
+        delta = 0.02 if D > 4 else 0.05
+        for order in orders:
+            models = [logistic_kalman_setup(T, D, "binomial", order=order), logistic_kalman_setup(T, D, "negbinomial", order=order), poisson_kalman_setup(T, D, order=order)]
+            kernels = [get_kernel(m.dynamics_factory, m.observations_factory, m.log_likelihood_fn, True)[1] for m, _ in models]
+            for C_ in chain_counts:
+                chs = [DeviceChains(h, np.repeat(x[None], C_, axis=0).astype(np.float32)) for _, x in models]
+                states = [KalmanSampler(x=c, updated=None) for c in chs]
+                count = [0]
+
+                def sweep(k):
+                    count[0] += 1
+                    kernels[k](R.PRNGKey(count[0]), states[k], delta)
+
+                ts = alternating_batches(h, [lambda: sweep(0), lambda: sweep(1), lambda: sweep(2)], runs)
+                print(json.dumps(dict(config=f"logistic_kalman T={T} dx={D}, aux-Kalman order {order}, fp32, {'chain-minor' if chs[0].chain_minor else 'dense'} layout, "
+                                             "resident chains", chains=C_, delta=delta,
+                                      ms_per_sweep={n: round(t[0], 4) for n, t in zip(names, ts)}, ms_per_sweep_median={n: round(t[1], 4) for n, t in zip(names, ts)},
+                                      ms_per_sweep_worst={n: round(t[2], 4) for n, t in zip(names, ts)},
+                                      sweeps_per_s_median={n: round(C_ / t[1] * 1e3, 1) for n, t in zip(names, ts)},
+                                      rate_over_poisson_median={n: round(ts[2][1] / t[1], 3) for n, t in zip(names[:2], ts)},
+                                      accept={n: float(c.accepted.to_host().mean()) for n, c in zip(names, chs)})), flush=True)
+                del chs, states
+            bm, xb = models[0]
+            hinit, hkernel = get_kernel(lambda x: bm.dynamics_factory(x), lambda x, u, dl: bm.observations_factory(x, u, dl), lambda x: bm.log_likelihood_fn(x), True)
+            st = hinit(xb.astype(np.float32))
+            keys = R.split(R.PRNGKey(3), host_reps + 1)
+            st = hkernel(keys[0], st, delta)
+            h.sync()
+            t0 = time.perf_counter()
+            for k in range(host_reps):
+                st = hkernel(keys[1 + k], st, delta)
+            h.sync()
+            print(json.dumps(dict(config=f"logistic_kalman T={T} dx={D}, aux-Kalman order {order}, fp32, binomial, host-factory path", chains=1, delta=delta,
+                                  ms_per_sweep=round((time.perf_counter() - t0) / host_reps * 1e3, 2))), flush=True)
+
+
 def _poisson_lin_models(T, dx, dy, order):
     """(model, start state, delta = 1 / max_t lambda_max(Lam_t) on the simulated path)"""
     from aux_ssm_samplers_amd.workloads import poisson_lin_setup
@@ -768,6 +817,8 @@ if __name__ == "__main__":
         smoother()
     if "poisson_kalman" in which:
         poisson_kalman()
+    if "logistic_kalman" in which:
+        logistic_kalman()
     if "poisson_lin_kalman" in which:
         poisson_lin_kalman()
     if "poisson_lin_trace" in which:

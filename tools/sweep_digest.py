@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One SHA-256 per case over the bytes of (x, accepted, logs) after consecutive keyed sweeps of a fixed list of small problems: every branch a driver of
 the auxiliary Kalman sweep can take (csrc/api.hip: sweep_lg_concat, sweep_lg_concat_fused, sweep_lorenz, sweep_mvt and sweep_ss -- the state-space driver of the
-SV, Poisson and Poisson-linear kinds), every model kind of include/auxssm.h (1-8, 11, 12), in both dtypes.  For comparing two builds of the library bit for bit:
+SV, Poisson, logistic and Poisson-linear kinds), every model kind of include/auxssm.h (1-8, 11-14), in both dtypes.  For comparing two builds of the library bit for bit:
     AUXSSM_LIB=/path/to/libauxssm.so python tools/sweep_digest.py out.json        once per build, then compare the files.
 A case that raises is recorded with the error's text, and the exit status is 1: two equal error strings compare equal and prove nothing.
 
@@ -18,9 +18,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from aux_ssm_samplers_amd import _lib, random as R  # noqa: E402
-from aux_ssm_samplers_amd.kalman import (DeviceChains, KalmanSampler, LGConcatModel, LorenzModel, MVTModel, PoissonLinearModel, PoissonModel, SVModel,  # noqa: E402
-                                         get_kernel)
-from aux_ssm_samplers_amd.workloads import lg_model, lorenz_kalman_setup, poisson_lin_setup, poisson_setup, sv_setup  # noqa: E402
+from aux_ssm_samplers_amd.kalman import (BinomialModel, DeviceChains, KalmanSampler, LGConcatModel, LorenzModel, MVTModel, NegBinomialModel,  # noqa: E402
+                                         PoissonLinearModel, PoissonModel, SVModel, get_kernel)
+from aux_ssm_samplers_amd.workloads import lg_model, logistic_kalman_setup, lorenz_kalman_setup, poisson_lin_setup, poisson_setup, sv_setup  # noqa: E402
 
 
 def lg(T, d, tinv=False):
@@ -75,6 +75,16 @@ def pois(T, d, order):
     return PoissonModel(holes(y), M0.m0, M0.P0, Mt.F, Mt.Q, Mt.b, order=order), 0.05
 
 
+def logit(T, d, order, family):
+    """binomial (trials 1 .. 40, a binary component) or negative-binomial (r = 3) data with missing entries; the size under a missing entry is NaN"""
+    base, _ = logistic_kalman_setup(T, d, family)
+    y = holes(base.yobs)
+    dyn = (base.m0, base.P0, base.F, base.Q, base.b)
+    if family == "binomial":
+        return BinomialModel(y, np.where(np.isnan(y), np.nan, base.trials), *dyn, order=order), 0.05
+    return NegBinomialModel(y, base.r, *dyn, order=order), 0.05
+
+
 def plin(T, dx, dy, order, delta):
     """delta: of the order of 1 / lambda_max(H' diag(e) H), which the first-order proposal needs (PoissonLinearModel's docstring)"""
     base, _, H, c = poisson_lin_setup(T, dx, dy)
@@ -126,6 +136,11 @@ for o in (1, 2):
     CASES[f"pois{o}_cm_shared"] = (lambda o=o: pois(40, 2, o), 64, True, {})
     CASES[f"pois{o}_cm_array_free"] = (lambda o=o: pois(40, 2, o), 64, True, dict(share=0))
     CASES[f"pois{o}_wide_one_chain"] = (lambda o=o: pois(12, 6, o), 1, False, {})
+    for fam, tag in (("binomial", "binom"), ("negbinomial", "negbin")):
+        CASES[f"{tag}{o}_dense"] = (lambda o=o, fam=fam: logit(40, 2, o, fam), 3, False, {})
+        CASES[f"{tag}{o}_cm_shared"] = (lambda o=o, fam=fam: logit(40, 2, o, fam), 64, True, {})
+        CASES[f"{tag}{o}_cm_array_free"] = (lambda o=o, fam=fam: logit(40, 2, o, fam), 64, True, dict(share=0))
+        CASES[f"{tag}{o}_wide_one_chain"] = (lambda o=o, fam=fam: logit(12, 6, o, fam), 1, False, {})
     CASES[f"plin{o}_dense"] = (lambda o=o: plin(40, 2, 3, o, 0.05), 3, False, {})
     CASES[f"plin{o}_second_staging_block_ragged_chains"] = (lambda o=o: plin(40, 4, 70, o, 0.005), 5, False, {})
     CASES[f"plin{o}_one_step"] = (lambda o=o: plin(1, 2, 3, o, 0.05), 3, False, {})
@@ -134,6 +149,9 @@ for o in (1, 2):
     CASES[f"mvt{o}_one_step"] = (lambda o=o: mvt(1, 3, o), 3, False, {})
 CASES["pois1_wide_gain_rows_reused"] = (lambda: pois(12, 6, 1), 3, False, {})
 CASES["pois1_cm_shared_overlap"] = (lambda: pois(40, 2, 1), 64, True, dict(overlap=1, sweeps=5))
+CASES["binom1_wide_gain_rows_reused"] = (lambda: logit(12, 6, 1, "binomial"), 3, False, {})
+CASES["negbin1_cm_shared_overlap"] = (lambda: logit(40, 2, 1, "negbinomial"), 64, True, dict(overlap=1, sweeps=5))
+CASES["binom2_dense_sequential"] = (lambda: logit(40, 2, 2, "binomial"), 3, False, dict(parallel=False))
 CASES["pois2_dense_sequential"] = (lambda: pois(40, 2, 2), 3, False, dict(parallel=False))
 CASES["plin2_dense_sequential"] = (lambda: plin(40, 2, 3, 2, 0.05), 3, False, dict(parallel=False))
 
@@ -176,6 +194,8 @@ HOST_MODELS = {
     "LorenzModel": lambda: lorenz(12)[0],
     "MVTModel:order1": lambda: mvt(12, 3, 1)[0], "MVTModel:order2": lambda: mvt(12, 3, 2)[0],
     "PoissonLinearModel:order1": lambda: plin(12, 2, 3, 1, 0.05)[0], "PoissonLinearModel:order2": lambda: plin(12, 2, 3, 2, 0.05)[0],
+    "BinomialModel:order1": lambda: logit(12, 2, 1, "binomial")[0], "BinomialModel:order2": lambda: logit(12, 2, 2, "binomial")[0],
+    "NegBinomialModel:order1": lambda: logit(12, 2, 1, "negbinomial")[0], "NegBinomialModel:order2": lambda: logit(12, 2, 2, "negbinomial")[0],
     "PoissonModel:order1": lambda: pois(12, 2, 1)[0], "PoissonModel:order2": lambda: pois(12, 2, 2)[0],
     "SVModel:order1": lambda: SVModel(holes(sv(12, 2, 1)[0].yobs), *sv_setup(12, 2)[2], order=1),
     "SVModel:order2": lambda: SVModel(holes(sv(12, 2, 2)[0].yobs), *sv_setup(12, 2)[2], order=2),
