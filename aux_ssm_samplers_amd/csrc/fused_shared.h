@@ -10,13 +10,15 @@
 //                                         chain-shared prefix product Phi_t of the chunk's Mb (k_fs_fprod); and, in the same walk, the sampler's LOCAL increments
 //                                         inc0_t = M1_t h_t - gb_t + Lc_t eps_t (sampling.py:108-112; draws eps_samp) with their chunk aggregate
 //                                         e0 = sum_t (G_ta ... G_{t-1}) inc0_t against the table of within-chunk gain products (k_fs_gpre)
-//   --  (k_aff_aggs, k_fs_esfix)          m_start of every (chain, chunk) by the aggregate scan of the folds; the sampler's aggregates completed by the part that is
-//                                         linear in m_start: e = e0 + Psi_chunk m_start, Psi = sum_t (G_ta ... G_{t-1}) M1_t Phi_t (chain-shared, k_fs_psi)
+//   --  (k_fs_mid)                        one workgroup per chain: m_start of every (chain, chunk) by the aggregate scan of the folds; the sampler's aggregates
+//                                         completed by the part that is linear in m_start, e = e0 + Psi_chunk m_start, Psi = sum_t (G_ta ... G_{t-1}) M1_t Phi_t
+//                                         (chain-shared, k_fs_psi), and scanned in turn.  Both scans carry the chain's D-vector offsets only: the matrices of the
+//                                         aggregates are chain-shared, and the one a Kogge-Stone stage needs comes from a table of the model stage (k_fs_gtab)
 //   E  (k_fs_e)  r inc0, r u    w x'      sampler walk (descending) x'_t = G_t x'_{t+1} + inc0_t + N_t m_start, N_t = M1_t Phi_t (in the pass's coefficient row), and the MH
 //                                         terms of the PROPOSAL x' where it is in registers
 // The filtered means never go to memory, u is written once and read once, and the chain passes are two kernels bound by HBM (AC: 3 d at 615 instructions per
 // chain-step; E: 3 d) instead of three.
-// plus the two aggregate scans (k_aff_aggs, unchanged), one lane per chain for the t = 0 terms (k_fs_head) and the accept step (k_fs_accept).
+// plus the kernel between them (k_fs_mid: the values of k_aff_aggs' scans bit for bit), one lane per chain for the t = 0 terms (k_fs_head) and the accept step (k_fs_accept).
 // There is no select pass: with a `sel` array the state is LAZY -- chain c lives in buffer sel[c] of a ping-pong pair, reads its x from there, writes
 // its proposal to the other buffer, and acceptance flips sel[c] (auxssm_kalman_sweep_lazy); without one, x' goes to a scratch buffer and the
 // caller runs the usual select.  Same tables as affine_shared.h / kalman_bodies.h (GainRow, SampShared, LogShared), same per-term arithmetic and NaN
@@ -141,26 +143,198 @@ template <typename R, int D> __global__ void __launch_bounds__(TB_CM) k_fs_psi(F
 #pragma unroll
     for (int k = 0; k < D * D; ++k) psi[(long long)ch * D * D + k] = Ps[k];
 }
-// the sampler's chunk aggregates completed: e(chain, chunk) += Psi_chunk m_start(chain, chunk) (the scan position of the sampler is reversed time)
-template <typename R, int D> __global__ void __launch_bounds__(256) k_fs_esfix(int C, int nchunk, const R* __restrict__ psi, const R* __restrict__ pre_f, R* __restrict__ agg_s) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= (long long)C * nchunk) return;
-    const int c = (int)(g / nchunk), ch = (int)(g % nchunk);  // (consecutive lanes: consecutive chunks of one chain -- the records of a chain are contiguous)
-    if (ch == 0) return;  // (Psi_0 = 0)
-    R m[D], e[D], Ps[D * D];
-    ldv<R, D>(pre_f + ((long long)c * nchunk + ch) * SampPre<R, D>::NPAD, m);
-    R* q = agg_s + ((long long)c * nchunk + (nchunk - 1 - ch)) * SampPre<R, D>::NPAD;
-    ldv<R, D>(q, e);
+// ---- between the passes: the two aggregate scans of a chain in ONE workgroup, offsets only ------------------------------------------------------------------
+// The aggregate of (chain, chunk) is the affine map (G_chunk, e): G_chunk is chain-shared (cprod), only e is the chain's.  k_aff_aggs (kernels.hip.h) scans
+// the full elements, so every chain's workgroup repeats the same chain of matrix products.  The only matrix the offset half of a combine reads is the RIGHT
+// operand's, o.e = G_right e_left + e_right (kalman_math.h::sample_offset): in the serial and down phases that is cprod[j]; in Kogge-Stone stage s it is the lane's
+// own accumulated matrix as it stands at the start of the stage, which depends on the model alone.  k_fs_gtab (model stage, memoised with cprod) runs k_aff_aggs'
+// schedule on the matrices -- the same mm calls in the same operand order -- and records that matrix per (stage, lane); k_fs_mid scans D reals per record with
+// the matrix from the table: every offset is produced by the same multiply-adds on the same inputs as k_aff_aggs produces it (tests/test_fused_mid_host.py).
+// LANE-MINOR TABLES.  A lane owns E2 consecutive chunks, so at step i of its serial walk the lanes of a wave read records E2 records apart: with cprod's
+// record layout every 16-byte load instruction of a wave touches 64 different cache lines, and the kernel is bound by the address rate of the CU's one texture
+// path, not by latency (measured: 100 us with record-layout tables against 92 us for the three launches it replaces).  k_fs_gtab therefore also lays the
+// matrices the serial and down phases read (cprod[j], and Psi of the sampler's scan) out the way the lanes walk them: element k of step i for all 256 lanes side
+// by side, tab[(i D^2 + k) 256 + lane] -- a wave's load is 512 contiguous bytes.  Same values; only where they are read from differs.
+constexpr int FS_MID_STAGES = 8;
+static_assert((1 << FS_MID_STAGES) == TB_AGGS, "one table row per Kogge-Stone stage of the aggregate scan");
+// reals of the three tables of one scan: stage matrices | the lanes' serial matrices | (sampler's scan) the lanes' Psi
+template <int D> AX_HD size_t fs_mid_ks_reals() { return (size_t)FS_MID_STAGES * D * D * TB_AGGS; }
+template <int D> AX_HD size_t fs_mid_ser_reals(int nchunk) { return (size_t)((nchunk + TB_AGGS - 1) / TB_AGGS) * D * D * TB_AGGS; }
+// psi: null for the filter's scan; scan position j of the sampler is chunk nchunk - 1 - j
+template <typename R, int D>
+__global__ void __launch_bounds__(TB_AGGS) k_fs_gtab(FusedArgs a, const R* __restrict__ cprod, const R* __restrict__ psi, R* __restrict__ gks, R* __restrict__ gser,
+                                                     R* __restrict__ pser) {
+    if (memo_skip(a)) return;
+    constexpr int DD = D * D;
+    __shared__ R sh[TB_AGGS * DD];
+    const int tid = threadIdx.x, nchunk = a.nchunk;
+    const int E2 = (nchunk + TB_AGGS - 1) / TB_AGGS;
+    const int j0 = min(nchunk, tid * E2), j1 = min(nchunk, j0 + E2);
+    for (int i = 0; i < E2; ++i) {  // (slots past the lane's range are never read: zeros)
+        const int j = j0 + i;
 #pragma unroll
-    for (int k = 0; k < D * D; ++k) Ps[k] = psi[(long long)ch * D * D + k];
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-        R v = e[i];
-#pragma unroll
-        for (int k = 0; k < D; ++k) v += Ps[i * D + k] * m[k];
-        e[i] = v;
+        for (int k = 0; k < DD; ++k) {
+            gser[((long long)i * DD + k) * TB_AGGS + tid] = j < j1 ? cprod[(long long)j * DD + k] : (R)0;
+            if (psi) pser[((long long)i * DD + k) * TB_AGGS + tid] = j < j1 ? psi[(long long)(nchunk - 1 - j) * DD + k] : (R)0;
+        }
     }
-    stv<R, D>(q, e);
+    R G[DD];
+#pragma unroll
+    for (int k = 0; k < DD; ++k) G[k] = (k / D == k % D) ? (R)1 : (R)0;
+    if (j0 < j1) ld<R, DD>(cprod + (long long)j0 * DD, G);
+    for (int j = j0 + 1; j < j1; ++j) {
+        R e[DD], o[DD];
+        ld<R, DD>(cprod + (long long)j * DD, e);
+        mm<R, D, D, D>(e, G, o);  // sample_combine(acc, e)
+#pragma unroll
+        for (int k = 0; k < DD; ++k) G[k] = o[k];
+    }
+    for (int s = 0; s < FS_MID_STAGES; ++s) {
+        const int off = 1 << s;
+#pragma unroll
+        for (int k = 0; k < DD; ++k) gks[((long long)s * DD + k) * TB_AGGS + tid] = G[k];
+        st<R, DD>(sh + tid * DD, G);
+        __syncthreads();
+        R L[DD];
+        if (tid >= off) ld<R, DD>(sh + (tid - off) * DD, L);
+        __syncthreads();
+        if (tid >= off) {
+            R o[DD];
+            mm<R, D, D, D>(G, L, o);  // sample_combine(left, acc)
+#pragma unroll
+            for (int k = 0; k < DD; ++k) G[k] = o[k];
+        }
+    }
+}
+// one scan of k_fs_mid: the aggregates agg[j] of the workgroup's chain -> their exclusive prefixes pre[j], with k_aff_aggs' lane ranges, phases and association
+// order.  FIX (the sampler's scan; position j = chunk nchunk - 1 - j): an aggregate is completed on load by the part linear in the chunk's first mean,
+// e += Psi_ch m_start(ch) (Psi_0 = 0; m_start = the first scan's prefixes, which this workgroup has just written) -- wherever it is loaded, with the same loop.
+// A lane's loads do not depend on its running offset: the records of a block of NR chunks are fetched side by side (every load unconditional, at a clamped
+// index: a load under a lane's condition costs a branch and a full wait each), then folded in order; with at most NR chunks per lane (nchunk <= 2048) the down
+// phase finds the serial phase's records still in registers and reloads only the chain-shared matrices.
+template <typename R, int D, bool FIX>
+__device__ __forceinline__ void fs_mid_scan(R* lds, int nchunk, const R* agg, R* pre, const R* __restrict__ gks, const R* __restrict__ gser,
+                                            const R* __restrict__ pser, const R* mst) {
+    using Pre = SampPre<R, D>;
+    constexpr int DD = D * D, NR = 8, NG = 4;
+    const int tid = threadIdx.x;
+    const int E2 = (nchunk + TB_AGGS - 1) / TB_AGGS;
+    const int j0 = min(nchunk, tid * E2), j1 = min(nchunk, j0 + E2), jlast = j1 - 1;
+    auto ldmat = [&](const R* tab, int i, R* G) {  // lane-minor table: row i, this lane's matrix
+#pragma unroll
+        for (int k = 0; k < DD; ++k) G[k] = tab[((long long)i * DD + k) * TB_AGGS + tid];
+    };
+    R e[NR][D];
+    auto load_block = [&](int jb) {  // e[q] = the (completed) aggregate of chunk min(jb + q, jlast)
+        if constexpr (FIX) {
+#pragma unroll
+            for (int h = 0; h < NR; h += NG) {
+                R m[NG][D], Ps[NG][DD];
+#pragma unroll
+                for (int q = 0; q < NG; ++q) {
+                    const int j = min(jb + h + q, jlast);
+                    ldv<R, D>(agg + (long long)j * Pre::NPAD, e[h + q]);
+                    ldv<R, D>(mst + (long long)(nchunk - 1 - j) * Pre::NPAD, m[q]);
+                    ldmat(pser, j - j0, Ps[q]);
+                }
+#pragma unroll
+                for (int q = 0; q < NG; ++q) {
+                    const bool fix = nchunk - 1 - min(jb + h + q, jlast) != 0;
+#pragma unroll
+                    for (int i = 0; i < D; ++i) {
+                        R v = e[h + q][i];
+#pragma unroll
+                        for (int k = 0; k < D; ++k) v += Ps[q][i * D + k] * m[q][k];
+                        e[h + q][i] = fix ? v : e[h + q][i];
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < NR; ++q) ldv<R, D>(agg + (long long)min(jb + q, jlast) * Pre::NPAD, e[q]);
+        }
+    };
+    R acc[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) acc[i] = 0;
+    for (int jb = j0; jb < j1; jb += NR) {
+        load_block(jb);
+#pragma unroll
+        for (int h = 0; h < NR; h += NG) {
+            R G[NG][DD];
+#pragma unroll
+            for (int q = 0; q < NG; ++q) ldmat(gser, min(jb + h + q, jlast) - j0, G[q]);
+#pragma unroll
+            for (int q = 0; q < NG; ++q) {
+                const int j = jb + h + q;
+                if (j < j1) {
+                    R o[D];
+                    sample_offset<R, D>(G[q], acc, e[h + q], o);  // sample_combine(acc, e)
+#pragma unroll
+                    for (int i = 0; i < D; ++i) acc[i] = j == j0 ? e[h + q][i] : o[i];  // (the lane's first chunk is taken as it is)
+                }
+            }
+        }
+    }
+    R Gs[DD];
+    ldmat(gks, 0, Gs);
+#pragma unroll
+    for (int s = 0; s < FS_MID_STAGES; ++s) {  // Kogge-Stone inclusive scan of the per-lane totals
+        const int off = 1 << s;
+        R Gn[DD];
+        ldmat(gks, s + 1 < FS_MID_STAGES ? s + 1 : s, Gn);  // (the next stage's matrix)
+        stv<R, D>(lds + tid * Pre::NPAD, acc);
+        __syncthreads();
+        R left[D];
+        ldv<R, D>(lds + max(tid - off, 0) * Pre::NPAD, left);
+        __syncthreads();
+        R o[D];
+        sample_offset<R, D>(Gs, left, acc, o);  // sample_combine(left, acc)
+#pragma unroll
+        for (int i = 0; i < D; ++i) acc[i] = tid >= off ? o[i] : acc[i];
+#pragma unroll
+        for (int k = 0; k < DD; ++k) Gs[k] = Gn[k];
+    }
+    stv<R, D>(lds + tid * Pre::NPAD, acc);
+    __syncthreads();
+    R p[D];
+    ldv<R, D>(lds + max(tid - 1, 0) * Pre::NPAD, p);
+#pragma unroll
+    for (int i = 0; i < D; ++i) p[i] = tid > 0 ? p[i] : (R)0;
+    for (int jb = j0; jb < j1; jb += NR) {
+        if (E2 > NR) load_block(jb);  // (else: the one block of the serial phase)
+#pragma unroll
+        for (int h = 0; h < NR; h += NG) {
+            R G[NG][DD];
+#pragma unroll
+            for (int q = 0; q < NG; ++q) ldmat(gser, min(jb + h + q, jlast) - j0, G[q]);
+#pragma unroll
+            for (int q = 0; q < NG; ++q) {
+                const int j = jb + h + q;
+                if (j < j1) {
+                    stv<R, D>(pre + (long long)j * Pre::NPAD, p);
+                    R o[D];
+                    sample_offset<R, D>(G[q], p, e[h + q], o);  // sample_apply(p, e): the last chunk's result is not used
+#pragma unroll
+                    for (int i = 0; i < D; ++i) p[i] = o[i];
+                }
+            }
+        }
+    }
+}
+// One workgroup per chain, TB_AGGS lanes.  Scan 1: the folds' aggregates -> the first filtered mean of every chunk (pre_f; pass E reads it too).  Barrier: the
+// chain's pre_f records are this workgroup's own stores.  Scan 2: the sampler's aggregates, completed on load by Psi m_start -> the sampler's chunk starts (pre_s).
+// No lane leaves before the last barrier and no loop waits for another workgroup: any nchunk >= 1 terminates.
+template <typename R, int D>
+__global__ void __launch_bounds__(TB_AGGS) k_fs_mid(FusedArgs a, const R* __restrict__ gtab_f, const R* __restrict__ gtab_s) {
+    using Pre = SampPre<R, D>;
+    __shared__ __attribute__((aligned(16))) R lds[TB_AGGS * Pre::NPAD];
+    const long long base = (long long)blockIdx.x * a.nchunk * Pre::NPAD;
+    R* pre_f = (R*)a.pre_f + base;
+    const size_t nks = fs_mid_ks_reals<D>(), nser = fs_mid_ser_reals<D>(a.nchunk);  // [stage matrices | serial matrices | Psi] of each scan (k_fs_gtab)
+    fs_mid_scan<R, D, false>(lds, a.nchunk, (const R*)a.agg_f + base, pre_f, gtab_f, gtab_f + nks, nullptr, nullptr);
+    __syncthreads();  // pre_f of this chain is complete and visible to the workgroup; the LDS records of scan 1 are dead
+    fs_mid_scan<R, D, true>(lds, a.nchunk, (const R*)a.agg_s + base, (R*)a.pre_s + base, gtab_s, gtab_s + nks, gtab_s + nks + nser, pre_f);
 }
 
 // ---- compact per-pass rows (model stage) ----------------------------------------------------------------------------------------------------
@@ -819,6 +993,7 @@ template <typename R, int D, int PO> size_t fused_ws(const auxssm_ctx* h, const 
     b += filter_ws<R, D, P>(h, KDims{1, d.T, 1}, 1);
     b += (size_t)d.T * (SampShared<R, D>::NPAD + LogShared<R, D, PO>::NPAD + (size_t)D * D) * sizeof(R) + (size_t)2 * nchunk * D * D * sizeof(R) + 10 * 256 + ((size_t)d.T / 256 + 2) * sizeof(Acc);
     b += (size_t)d.T * (FsRows<R, D, PO>::NC + FsRows<R, D, PO>::NE + 2 * (size_t)D * D) * sizeof(R) + (size_t)nchunk * D * D * sizeof(R) + 8 * 256;
+    b += (2 * fs_mid_ks_reals<D>() + 3 * fs_mid_ser_reals<D>(nchunk)) * sizeof(R) + 2 * 256;  // the lane-minor tables of the two aggregate scans (k_fs_gtab)
     return b;
 }
 template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHost& f) {
@@ -840,7 +1015,7 @@ template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHo
     a.delta = f.la.delta; a.shd = f.la.shd; a.dptr = f.la.dptr; a.nan_policy = f.la.nan_policy;
     a.memo = f.memo;
     f.fa.memo = f.sa.memo = f.la.memo = f.memo;  // the model stage below; cleared before the chain passes (k_filter_t0 serves both)
-    R *cprod_f, *cprod_s, *rows_c, *rows_e, *psi;
+    R *cprod_f, *cprod_s, *rows_c, *rows_e, *psi, *gtab_f, *gtab_s;
     {
         // MODEL STAGE (ctx.h::SideStage when the sweep opened one): everything that reads the model and the step size only
         {
@@ -858,9 +1033,12 @@ template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHo
         R* fpre = (R*)ws_take(h, (size_t)T * D * D * sizeof(R));
         R* ntab = (R*)ws_take(h, (size_t)T * D * D * sizeof(R));
         psi = (R*)ws_take(h, (size_t)a.nchunk * D * D * sizeof(R));
+        const size_t nks = fs_mid_ks_reals<D>(), nser = fs_mid_ser_reals<D>(a.nchunk);
+        gtab_f = (R*)ws_take(h, (nks + nser) * sizeof(R));
+        gtab_s = (R*)ws_take(h, (nks + 2 * nser) * sizeof(R));
         const int nclb = (T + 255) / 256;
         Acc* clog = (Acc*)ws_take(h, 256 + (size_t)nclb * sizeof(Acc));  // [0] the sum, [32 ...) the partial sums
-        if (!f.sa.tab || !f.la.tab || !gpre || !cprod_f || !cprod_s || !rows_c || !rows_e || !fpre || !ntab || !psi || !clog) return AUXSSM_ERR_NOMEM;
+        if (!f.sa.tab || !f.la.tab || !gpre || !cprod_f || !cprod_s || !rows_c || !rows_e || !fpre || !ntab || !psi || !gtab_f || !gtab_s || !clog) return AUXSSM_ERR_NOMEM;
         a.clog = clog;
         int* nanrow = (int*)(clog + 16);  // (in the sum's 256-byte header: lives and is memoised with the tables)
         a.nanrow = nanrow;
@@ -874,6 +1052,8 @@ template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHo
             hipLaunchKernelGGL((k_fs_fprod<R, D, P>), dim3((a.nchunk + TB_CM - 1) / TB_CM), dim3(TB_CM), 0, h->stream, a, cprod_f, fpre);
             hipLaunchKernelGGL((k_fs_gpre<R, D>), dim3((a.nchunk + TB_CM - 1) / TB_CM), dim3(TB_CM), 0, h->stream, a, gpre, cprod_s);
             hipLaunchKernelGGL((k_fs_psi<R, D>), dim3((a.nchunk + TB_CM - 1) / TB_CM), dim3(TB_CM), 0, h->stream, a, (const R*)gpre, (const R*)fpre, ntab, psi);
+            hipLaunchKernelGGL((k_fs_gtab<R, D>), dim3(1), dim3(TB_AGGS), 0, h->stream, a, (const R*)cprod_f, (const R*)nullptr, gtab_f, gtab_f + nks, (R*)nullptr);
+            hipLaunchKernelGGL((k_fs_gtab<R, D>), dim3(1), dim3(TB_AGGS), 0, h->stream, a, (const R*)cprod_s, (const R*)psi, gtab_s, gtab_s + nks, gtab_s + nks + nser);
             {
                 using F = FsRows<R, D, PO>;
                 const long long nmax = (long long)T * (F::NC > F::NE ? F::NC : F::NE);
@@ -903,7 +1083,6 @@ template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHo
     const int TBF = C >= 256 ? 256 : (C + 63) / 64 * 64;
     const unsigned grid = (unsigned)a.nchunk * (unsigned)((C + TBF - 1) / TBF);
     const unsigned grid_pk = (unsigned)((a.nchunk + a.pack - 1) / a.pack);
-    const size_t lds = (size_t)TB_AGGS * SampElem<R, D>::NPAD * sizeof(R);
     if (a.pack > 1) {
         const size_t lds_ac = (size_t)a.pack * fs_pk_block<R, F::NC>(a.E) * sizeof(R) + FsNormTabSel<R>::BYTES;
         if (lds_ac > 64 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_fs_ac<R, D, PO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ac));
@@ -917,10 +1096,7 @@ template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHo
     }
     {
         ProfScope ps(h, AUXSSM_K_SAMPLE_SCAN);  // the two aggregate scans: first means of the chunks, then (completed by Psi m_start) the sampler's chunk starts
-        hipLaunchKernelGGL((k_aff_aggs<R, D>), dim3(C), dim3(TB_AGGS), lds, h->stream, ScanBufs{a.agg_f, a.pre_f}, (const R*)cprod_f, a.nchunk);
-        hipLaunchKernelGGL((k_fs_esfix<R, D>), dim3((unsigned)(((long long)C * a.nchunk + 255) / 256)), dim3(256), 0, h->stream, C, a.nchunk, (const R*)psi, (const R*)a.pre_f,
-                           (R*)a.agg_s);
-        hipLaunchKernelGGL((k_aff_aggs<R, D>), dim3(C), dim3(TB_AGGS), lds, h->stream, ScanBufs{a.agg_s, a.pre_s}, (const R*)cprod_s, a.nchunk);
+        hipLaunchKernelGGL((k_fs_mid<R, D>), dim3(C), dim3(TB_AGGS), 0, h->stream, a, (const R*)gtab_f, (const R*)gtab_s);
     }
     {
         ProfScope ps(h, AUXSSM_K_LOGPDF);

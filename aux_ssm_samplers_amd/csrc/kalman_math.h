@@ -1039,20 +1039,22 @@ template <typename R, int D> AX_HD void sample_last(const R* m, const R* Pd, con
     }
 }
 // _sampling_op_impl (sampling.py:51-55): acc = later times already composed, cur = this time step
+// the offset half of both: o = G e_in + e_cur (G, e_cur = this element's; e_in = the offset composed so far).  Also called on its own where the matrices are
+// chain-shared and come from a table (fused_shared.h::k_fs_mid): same operations, same order.
+template <typename R, int D> AX_HD void sample_offset(const R* G, const R* e_in, const R* e_cur, R* o) {
+    R t[D];
+    mv<R, D, D>(G, e_in, t);
+#pragma unroll
+    for (int i = 0; i < D; ++i) o[i] = t[i] + e_cur[i];
+}
 template <typename R, int D>
 AX_HD void sample_combine(const SampElem<R, D>& acc, const SampElem<R, D>& cur, SampElem<R, D>& o) {
     mm<R, D, D, D>(cur.G, acc.G, o.G);
-    R t[D];
-    mv<R, D, D>(cur.G, acc.e, t);
-#pragma unroll
-    for (int i = 0; i < D; ++i) o.e[i] = t[i] + cur.e[i];
+    sample_offset<R, D>(cur.G, acc.e, cur.e, o.e);
 }
 template <typename R, int D>
 AX_HD void sample_apply(const SampPre<R, D>& p, const SampElem<R, D>& cur, SampPre<R, D>& o) {
-    R t[D];
-    mv<R, D, D>(cur.G, p.e, t);
-#pragma unroll
-    for (int i = 0; i < D; ++i) o.e[i] = t[i] + cur.e[i];
+    sample_offset<R, D>(cur.G, p.e, cur.e, o.e);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -12,7 +12,8 @@ import re
 import subprocess
 import sys
 
-KEEP = re.compile(r"^k_fs_(ac|e|esfix|head|accept)<|^k_aff_aggs<|^k_filter_t0<|^k_rng|^k_fs_stats<")
+# (k_fs_esfix and k_aff_aggs: the three launches k_fs_mid replaced -- kept so that a trace of an older library reads the same way)
+KEEP = re.compile(r"^k_fs_(ac|e|mid|esfix|head|accept)<|^k_aff_aggs<|^k_filter_t0<|^k_rng|^k_fs_stats<")
 
 
 def find(d, pat):

@@ -34,9 +34,9 @@ STAGE_FILTER = [r"^k_filter_t0<", r"^k_filter_init<", r"^k_scan_reduce<ax::Filte
                 r"^k_ks_down<ax::FilterOp", r"^k_gain_tab<", r"^k_mask_obs<", r"^k_copy_cov<", r"^k_memo_"]
 FUSED = {
     "filter_tab": STAGE_FILTER,
-    "sample_init": [r"^k_sample_shared_tab<", r"^k_sweep_logpdf_tab<", r"^k_fs_fprod<", r"^k_fs_gpre<", r"^k_fs_psi<", r"^k_fs_rows<", r"^k_fs_clog"],
+    "sample_init": [r"^k_sample_shared_tab<", r"^k_sweep_logpdf_tab<", r"^k_fs_fprod<", r"^k_fs_gpre<", r"^k_fs_psi<", r"^k_fs_gtab<", r"^k_fs_rows<", r"^k_fs_clog"],
     "filter_scan": [r"^k_fs_ac<"],
-    "sample_scan": [r"^k_aff_aggs<", r"^k_fs_esfix<"],
+    "sample_scan": [r"^k_fs_mid<", r"^k_aff_aggs<", r"^k_fs_esfix<"],  # (the last two: the launches k_fs_mid replaced, for a profile of an older library)
     "logpdf": [r"^k_fs_e<"],
     "select": [r"^k_fs_head<", r"^k_fs_accept<"],
     "factory": [r"^k_concat_model<", r"^k_fs_concat0<"],

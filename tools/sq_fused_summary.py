@@ -30,7 +30,7 @@ for f in sorted(glob.glob(f"{src}/p*/*/*counter_collection.csv")):
     dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
     for n, d in zip(names, dem):
         d = re.sub(r"\(.*$", "", re.sub(r"^void ax::", "", d))
-        if not re.match(r"k_fs_(ac|e|head|accept)<|k_aff_aggs<|k_fs_esfix<", d):
+        if not re.match(r"k_fs_(ac|e|mid|head|accept)<|k_aff_aggs<|k_fs_esfix<", d):
             continue
         for cn, (k, tot, dur) in sorted(acc[n].items()):
             vals[d][cn] = tot / k
