@@ -50,7 +50,7 @@ class FkModel(C.Structure):
 
 
 class FkModelObs(FkModel):
-    """auxssm_fk_model in full: FkModel (the struct up to nu / prec, which the library reads alone for the potential kinds 0-4 and 6, so a caller that builds that
+    """auxssm_fk_model in full: FkModel (the struct up to nu / prec, which the library reads alone for the potential kinds 0-4, 6 and 8, so a caller that builds that
     head keeps working) followed by the fields of AUXSSM_POT_LIN_GAUSS, obs_H and obs_const.  csmc/_device.py::FkDesc.struct builds this one."""
     _fields_ = [("obs_H", C.c_void_p), ("obs_const", C.c_double)]
 
@@ -67,6 +67,7 @@ class FkUser(C.Structure):
 FK_USER_POTENTIAL, FK_USER_MEAN, FK_USER_GRADIENT = 1, 2, 4
 PROP_BOOTSTRAP_LG, PROP_AUX_INDEPENDENT, PROP_AUX_GUIDED = 0, 1, 2
 POT_FLAT, POT_GAUSS_OBS, POT_SV, POT_GAUSS_OBS_MASKED, POT_MVT, POT_LIN_GAUSS, POT_POISSON = 0, 1, 2, 3, 4, 5, 6
+POT_LOGISTIC = 8  # (7 is unassigned)
 TRANS_LINEAR, TRANS_LORENZ63_EM = 0, 1
 NOISE_EXPLICIT, NOISE_THREEFRY = 0, 1
 GRAD_NONE, GRAD_REFERENCE, GRAD_EXACT = 0, 1, 2

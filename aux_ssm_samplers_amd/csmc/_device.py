@@ -7,12 +7,12 @@ import numpy as np
 
 from .. import _lib, random as _random
 from .models import (GaussianInit, LinearGaussianDynamics, FlatPotential, GaussianObsPotential, SVPotential, Lorenz63Dynamics,
-                     MaskedGaussianObsPotential, MultivariateTPotential, LinearGaussianPotential, PoissonPotential, DevicePotential,
-                     DeviceGaussianDynamics)
+                     MaskedGaussianObsPotential, MultivariateTPotential, LinearGaussianPotential, PoissonPotential, BinomialPotential,
+                     NegBinomialPotential, DevicePotential, DeviceGaussianDynamics)
 
 _UNSUPPORTED = ("{what} is a Python object the HIP kernels cannot evaluate. The cSMC kernels run the closed model family "
                 "of aux_ssm_samplers_amd.csmc.models (GaussianInit, LinearGaussianDynamics, Lorenz63Dynamics, FlatPotential, "
-                "GaussianObsPotential, MaskedGaussianObsPotential, SVPotential, MultivariateTPotential, LinearGaussianPotential, PoissonPotential) in-kernel; there is no CPU fallback.")
+                "GaussianObsPotential, MaskedGaussianObsPotential, SVPotential, MultivariateTPotential, LinearGaussianPotential, PoissonPotential, BinomialPotential, NegBinomialPotential) in-kernel; there is no CPU fallback.")
 
 
 class FkDesc:
@@ -62,8 +62,9 @@ class FkDesc:
                          None if self.obs_H is None else self.obs_H.ctypes.data, self.obs_const)
         yd = self.ydev(handle, dtype)
         if yd is not None:
-            if yd.shape[0] != T:
-                raise ValueError(f"observations have {yd.shape[0]} time steps, state has {T}")
+            nt = yd.shape[1] if self.potential == _lib.POT_LOGISTIC else yd.shape[0]  # (POT_LOGISTIC: (2, T, dx), the data and the sizes)
+            if nt != T:
+                raise ValueError(f"observations have {nt} time steps, state has {T}")
             m.y = yd.ptr.value
         tv = self.tvdev(handle, dtype, T)
         if tv is not None:
@@ -81,12 +82,13 @@ class FkDesc:
 
 
 def _potential(G0, Gt, d):
-    """everything FkDesc needs about the potential: dict(kind, y = the device's observation array (T, dx) [, sig_y] [, the kind's own parameters])"""
+    """everything FkDesc needs about the potential: dict(kind, y = the device's observation array (T, dx) -- (2, T, dx) for POT_LOGISTIC -- [, sig_y] [, the
+    kind's own parameters])"""
     if type(G0) is not type(Gt) and not (isinstance(G0, GaussianInit) and isinstance(Gt, GaussianObsPotential)):
         raise NotImplementedError(_UNSUPPORTED.format(what=f"G0={type(G0).__name__} with Gt={type(Gt).__name__}"))
     if isinstance(Gt, FlatPotential):
         return dict(kind=_lib.POT_FLAT)
-    if not isinstance(Gt, (MultivariateTPotential, LinearGaussianPotential, PoissonPotential, MaskedGaussianObsPotential, GaussianObsPotential, SVPotential)):
+    if not isinstance(Gt, (MultivariateTPotential, LinearGaussianPotential, PoissonPotential, BinomialPotential, NegBinomialPotential, MaskedGaussianObsPotential, GaussianObsPotential, SVPotential)):
         raise NotImplementedError(_UNSUPPORTED.format(what=f"Gt={type(Gt).__name__}"))
     y0 = G0.m0 if isinstance(G0, GaussianInit) else G0.y
     if y0 is None or Gt.params is None:
@@ -111,6 +113,9 @@ def _potential(G0, Gt, d):
     if isinstance(Gt, PoissonPotential):
         PoissonPotential.check_counts(ys)  # (G0.y / Gt.params may have been assigned after construction)
         return dict(kind=_lib.POT_POISSON, y=ys)
+    if isinstance(Gt, (BinomialPotential, NegBinomialPotential)):
+        # the one kind whose device array has two planes: [the data | the sizes], (2, T, dx); sizes() validates (y / params may have been assigned later)
+        return dict(kind=_lib.POT_LOGISTIC, y=np.stack([ys, np.concatenate([G0.sizes(), Gt.sizes()], axis=0)]))
     masked = isinstance(Gt, MaskedGaussianObsPotential)
     s0 = G0.sig if masked else (float(np.sqrt(np.reshape(G0.P0, -1)[0])) if isinstance(G0, GaussianInit) else Gt.sig)
     if abs(s0 - Gt.sig) > 1e-12 * Gt.sig:

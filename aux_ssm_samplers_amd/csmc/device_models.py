@@ -1,6 +1,6 @@
 """Example models written as device code for DevicePotential / DeviceGaussianDynamics (csmc.models; contract in csrc/fk_user_pre.h).
 
-BUILTIN_*: the built-in potentials (Gaussian, stochastic volatility, multivariate Student-t, linear-Gaussian observation, Poisson counts) / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc_host.h::k_csmc_potbound written as user source, in the
+BUILTIN_*: the built-in potentials (Gaussian, stochastic volatility, multivariate Student-t, linear-Gaussian observation, Poisson counts, logistic counts) / bounds / linear mean of csrc/csmc_sweep.h + csrc/csmc_host.h::k_csmc_potbound written as user source, in the
 built-in operation order (fma_, det_exp, det_log), so that a program sweep reproduces the closed-family sweep bit for bit (the tests and
 tools/fk_program_bench.py use them).  The constants the host computes for the built-ins (csmc_host.h::fk_model) are formed the same way on
 the device from theta = [sig].  RARE_EVENT, STUDENT_T, GROWTH: models the closed family cannot express.
@@ -126,6 +126,42 @@ template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R
 }
 template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
     for (int k = 0; k < D; ++k) gx[k] = (y[k] - y[k] == 0) ? y[k] - det_exp(x[k]) : (R)0;
+}
+"""
+
+# Binomial / negative-binomial counts with a logit link (AUXSSM_POT_LOGISTIC), the combinatorial constant left out; no theta.  The observation rows are
+# [y (D) | m (D)], p = 2 D: the data, then the sizes (the built-in kind reads the sizes from plane 1 of its (2, T, D) array).  The order of include/auxssm.h,
+# restated:  e = det_exp(-|x_k|);  l = det_log(1 + e);  sp = max(x_k, 0) + l;  v_k = fma_(y_k, x_k, -(m_k sp)), counted only if y_k - y_k == 0, accumulated over
+# k ascending from 0.  Gradient: r = 1 / (1 + e), s = x_k >= 0 ? r : e r, fma_(-m_k, s, y_k), 0 for a missing component.  Bound (k_csmc_potbound): the binomial
+# log-likelihood at p = y / m without cancellation.  One source with the derivative: it serves plain and gradient programs.
+BUILTIN_LOGISTIC = r"""
+template <typename R, int D> __device__ R log_g(int t, const R* x, const R* xprev, const R* y, const R* theta) {
+    R acc = 0;
+    for (int k = 0; k < D; ++k) {
+        const R e = det_exp(-(x[k] < (R)0 ? -x[k] : x[k]));
+        const R l = det_log((R)1 + e);
+        const R sp = (x[k] > (R)0 ? x[k] : (R)0) + l;
+        const R v = fma_(y[k], x[k], -(y[D + k] * sp));
+        acc += (y[k] - y[k] == 0) ? v : (R)0;
+    }
+    return acc;
+}
+template <typename R, int D> __device__ R log_g_bound(int t, const R* y, const R* theta) {
+    R b = 0;
+    for (int k = 0; k < D; ++k) {
+        const R yk = y[k], mk = y[D + k], nk = mk - yk;
+        const R v = (yk > (R)0 ? yk * det_log(yk / mk) : (R)0) + (nk > (R)0 ? nk * det_log(nk / mk) : (R)0);
+        b += (yk - yk == 0) ? v : (R)0;
+    }
+    return b;
+}
+template <typename R, int D> __device__ void grad_log_g(int t, const R* x, const R* xprev, const R* y, const R* theta, R* gx, R* gxprev) {
+    for (int k = 0; k < D; ++k) {
+        const R e = det_exp(-(x[k] < (R)0 ? -x[k] : x[k]));
+        const R r = (R)1 / ((R)1 + e);
+        const R s = x[k] >= (R)0 ? r : e * r;
+        gx[k] = (y[k] - y[k] == 0) ? fma_(-y[D + k], s, y[k]) : (R)0;
+    }
 }
 """
 

@@ -7,6 +7,7 @@ from typing import Any, Optional
 
 import numpy as np
 
+from .. import _logistic
 from .._primitives.csmc.base import Distribution, UnivariatePotential, Dynamics, Potential
 
 
@@ -253,6 +254,76 @@ class PoissonPotential(UnivariatePotential, Potential):
         with np.errstate(invalid="ignore", over="ignore"):
             v = y * x - np.exp(x)
         return np.sum(np.where(np.isfinite(y), v, 0.0), axis=-1)
+
+
+class _LogisticPotential(UnivariatePotential, Potential):
+    """What BinomialPotential and NegBinomialPotential share (AUXSSM_POT_LOGISTIC): one potential with a logit link and a SIZE m beside every observation,
+        log g_t(x) = sum_k [ y_{t,k} x_k - m_{t,k} softplus(x_k) ]   over the components whose y_{t,k} is finite
+    -- a NaN y_{t,k} drops component k of step t whatever its size is.  A subclass names its parameter (trials / r), whose (n, dx) form `sizes(ys)` validates
+    against the data and turns into m (the data rules are the Kalman models', _logistic.py).  As G0 give y = ys[0] with a scalar or (dx,) parameter; as Gt give
+    params = ys[1:] with a scalar, (dx,) or (T - 1, dx) parameter."""
+
+    def _data(self):
+        """the observations this object holds as (n, dx): y as one row, or params"""
+        a = self.y if self.y is not None else self.params
+        return None if a is None else np.atleast_2d(np.asarray(a, np.float64))
+
+    def __post_init__(self):
+        if self._data() is not None:
+            self.sizes()
+
+    def __call__(self, x, y, size=None):
+        """the NumPy formula (batched over the leading axes of x); a non-finite y_k drops its component.  size: the sizes m beside y (same shape); by default
+        those this object's parameter gives for y -- a scalar or (dx,) parameter, or y = all the rows this object holds"""
+        if size is None:
+            y2 = np.atleast_2d(np.asarray(y, np.float64))
+            size = np.reshape(self._size_of(y2, self._parameter()), np.shape(y))
+        return _logistic.log_g(x, y, size)
+
+    def sizes(self):
+        """the sizes m (n, dx) of the held observations, validated; 0 where the observation is missing"""
+        ys = self._data()
+        m = self._size_of(ys, self._parameter())
+        return np.where(np.isfinite(ys), m, 0.0)
+
+
+@dataclass
+class BinomialPotential(_LogisticPotential):
+    """Binomial data with a logit link, y_{t,k} ~ Binomial(trials_{t,k}, sigma(x_{t,k})), independent over the components (AUXSSM_POT_LOGISTIC with m = trials):
+        log g_t(x) = sum_k [ y_{t,k} x_k - trials_{t,k} softplus(x_k) ]   over the components whose y_{t,k} is finite
+    Binary data is trials = 1.  Unnormalised: the constant log C(trials, y) is left out; non-integers are accepted; a NaN y_{t,k} is a missing observation
+    (its trials may be anything).  A finite y outside [0, trials], trials <= 0 or a non-finite trials under a finite y raises ValueError (kalman.BinomialModel's
+    rules).  As G0: BinomialPotential(trials, y=ys[0]); as Gt: BinomialPotential(trials, params=ys[1:]), trials a scalar, (dx,) or (T - 1, dx)."""
+    trials: Any = 1.0
+    y: Optional[Any] = None
+    params: Optional[Any] = None
+
+    def _parameter(self):
+        return self.trials
+
+    @staticmethod
+    def _size_of(ys, trials):
+        return _logistic.binomial_size(ys, trials, "BinomialPotential")
+
+
+@dataclass
+class NegBinomialPotential(_LogisticPotential):
+    """Overdispersed counts y_{t,k} ~ NB(r_{t,k}, p = sigma(x_{t,k})) (pmf proportional to p^y (1 - p)^r: mean r e^x), independent over the components
+    (AUXSSM_POT_LOGISTIC with m = y + r):
+        log g_t(x) = sum_k [ y_{t,k} x_k - (y_{t,k} + r_{t,k}) softplus(x_k) ]   over the components whose y_{t,k} is finite
+    Unnormalised; non-integer counts are accepted; a NaN y_{t,k} is a missing observation.  A finite negative count, r <= 0 or a non-finite r under a finite y
+    raises ValueError (kalman.NegBinomialModel's rules).  As G0: NegBinomialPotential(r, y=ys[0]); as Gt: NegBinomialPotential(r, params=ys[1:]), r a scalar,
+    (dx,) or (T - 1, dx)."""
+    r: Any = 1.0
+    y: Optional[Any] = None
+    params: Optional[Any] = None
+
+    def _parameter(self):
+        return self.r
+
+    @staticmethod
+    def _size_of(ys, r):
+        return ys + _logistic.negbinomial_r(ys, r, "NegBinomialPotential")
 
 
 # ---- user-defined models: device code compiled when the kernel is built (csrc/fk_program.hip, include/auxssm.h auxssm_fk_program_compile) ----------

@@ -124,7 +124,7 @@ template <typename R, int D> static bool c3_shape(const FkDev<R>& m, const CsmcA
 
 // The forward pass of (model, sweep), nw = nw_class(N).  TV: time-varying transitions; GRAD: gradient-informed proposals; P = FkBuiltin<R, D, V>, V the variant of
 // the model's potential (csmc_sweep.h::with_pot).
-//   case                            k_csmc_fwd<R, D, ...>                    ("own variant": a coupled potential or the Poisson potential, V != SEP)
+//   case                            k_csmc_fwd<R, D, ...>                    ("own variant": a coupled, the Poisson or the logistic potential, V != SEP)
 //   own variant, guided             <false, GRAD, 0, 2, P>
 //   own variant, otherwise          <TV, GRAD, 0, 0, P>                      the generic workgroup for every N
 //   guided, separable potentials    <false, GRAD, nw == 16 ? 16 : 0, 2, P>   N = 512 takes the generic one

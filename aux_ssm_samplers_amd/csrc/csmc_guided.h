@@ -128,6 +128,16 @@ template <typename R> __global__ void k_csmc_gshift_pois(CsmcArgs a, int D) {
     ((R*)a.grad)[g] = fma_(s * s, pois_grad_term<R>(u, ((const R*)a.y)[t * D + k]), u);
 }
 
+// the same for the logistic potential (csmc_sweep.h::logi_grad_term; the size of (t, k) is plane 1 of y), again a kernel of its own
+template <typename R> __global__ void k_csmc_gshift_logi(CsmcArgs a, int D) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (long long)a.C * a.T * D) return;
+    const long long t = (g / D) % a.T;
+    const int k = (int)(g % D);
+    const R u = ((const R*)a.u)[g], s = ((const R*)a.shd)[t];
+    ((R*)a.grad)[g] = fma_(s * s, logi_grad_term<R>(u, ((const R*)a.y)[t * D + k], size_at<R>((const R*)a.y, a.T, t, D, k)), u);
+}
+
 // the same for a coupled potential (variant V: csmc_sweep.h::coupled_grad with the run-time dimension m.D), whose gradient is not component by component: one
 // thread per (chain, t).  M: FkDev or csmc_wide.hip's FkW
 template <typename R, typename M, PotV V> __global__ void k_csmc_gshift_coupled(CsmcArgs a, M m) {

@@ -21,6 +21,7 @@ struct PotKind {
     const double* auxssm_fk_model::*matrix;     // the ABI field of the dx x dx matrix a coupled potential carries (FkDev / FkW::pot_mat), or null
     const char* matrix_missing;                 // check_fk_model's message when that field is NULL
     bool wide_no_bound;                         // the wide-state sweep drops the bound array and shifts every step by its exact maximum (csmc.hip::csmc_sweep_impl)
+    bool unassigned = false;                    // a number no kind has: check_fk_model refuses it as it refuses one beyond the table
 };
 static const PotKind POT_KINDS[] = {
     /* AUXSSM_POT_FLAT */ {false, nullptr, nullptr, false},
@@ -31,11 +32,13 @@ static const PotKind POT_KINDS[] = {
     /* AUXSSM_POT_LIN_GAUSS */
     {true, &auxssm_fk_model::obs_H, "the linear-Gaussian observation potential needs its whitened observation matrix obs_H (host, dx x dx)", true},
     /* AUXSSM_POT_POISSON */ {true, nullptr, nullptr, true},
+    /* 7: unassigned */ {false, nullptr, nullptr, false, true},
+    /* AUXSSM_POT_LOGISTIC: y is (2, T, dx), the sizes in plane 1 */ {true, nullptr, nullptr, true},
 };
 constexpr int POT_NKINDS = sizeof(POT_KINDS) / sizeof(POT_KINDS[0]);
 static_assert(POT_FLAT == AUXSSM_POT_FLAT && POT_GAUSS_OBS == AUXSSM_POT_GAUSS_OBS && POT_SV == AUXSSM_POT_SV && POT_GAUSS_OBS_MASKED == AUXSSM_POT_GAUSS_OBS_MASKED &&
-                  POT_MVT == AUXSSM_POT_MVT && POT_LIN_GAUSS == AUXSSM_POT_LIN_GAUSS && POT_POISSON == AUXSSM_POT_POISSON && POT_NKINDS == 7 &&
-                  POT_NKINDS == AUXSSM_POT_POISSON + 1,
+                  POT_MVT == AUXSSM_POT_MVT && POT_LIN_GAUSS == AUXSSM_POT_LIN_GAUSS && POT_POISSON == AUXSSM_POT_POISSON && POT_LOGISTIC == AUXSSM_POT_LOGISTIC &&
+                  POT_NKINDS == 9 && POT_NKINDS == AUXSSM_POT_LOGISTIC + 1,
               "csmc_sweep.h restates the potential kinds of include/auxssm.h");
 static const PotKind& pot_kind(int kind) { return POT_KINDS[kind]; }  // (kind checked by check_fk_model)
 // the matrix of fk's potential (host, dx x dx), or null for a potential without one
@@ -52,7 +55,7 @@ template <typename... P, typename... A> static int launch(auxssm_ctx* h, void (*
 // the model checks auxssm_csmc_sweep(_program) and auxssm_csmc_pit_sweep share; each entry point adds its own (proposals, dimensions, the explicit noise
 // arrays it reads).  user_potential: the potential is a program's, which brings its own observations
 static int check_fk_model(const auxssm_fk_model* fk, const auxssm_csmc_noise* noise, bool user_potential) {
-    if (fk->potential < 0 || fk->potential >= POT_NKINDS) {
+    if (fk->potential < 0 || fk->potential >= POT_NKINDS || POT_KINDS[fk->potential].unassigned) {
         set_error("unknown potential kind %d", fk->potential);
         return AUXSSM_ERR_ARG;
     }
@@ -206,6 +209,14 @@ template <typename R> __global__ void k_csmc_potbound(int T, int D, int potentia
             const R yk = y[(long long)t * D + k];
             b += yk > (R)0 ? yk * (det_log(yk) - (R)1) : (R)0;
         }
+    } else if (potential == AUXSSM_POT_LOGISTIC) {
+        // sum_k [y x - m softplus(x)] <= the binomial log-likelihood at p = y / m, y log(y / m) + (m - y) log((m - y) / m), without cancellation; <= 0, always
+        // finite; 0 at y = 0 and y = m (approached, not attained) and for a missing y_k
+        for (int k = 0; k < D; ++k) {
+            const R yk = y[(long long)t * D + k], mk = y[((long long)T + t) * D + k], nk = mk - yk;
+            const R v = (yk > (R)0 ? yk * det_log(yk / mk) : (R)0) + (nk > (R)0 ? nk * det_log(nk / mk) : (R)0);
+            b += (yk - yk == 0) ? v : (R)0;
+        }
     }
     gb[t] = b;
 }
@@ -223,6 +234,7 @@ template <typename R, typename M> static void fk_guided(auxssm_ctx* h, const Csm
             const long long total = (long long)a.C * a.T;
             if constexpr (pot_has_matrix(V)) hipLaunchKernelGGL((k_csmc_gshift_coupled<R, M, V>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, h->stream, a, m);
             else if constexpr (V == PotV::POIS) hipLaunchKernelGGL((k_csmc_gshift_pois<R>), dim3((unsigned)((total * m.D + 255) / 256)), dim3(256), 0, h->stream, a, m.D);
+            else if constexpr (V == PotV::LOGI) hipLaunchKernelGGL((k_csmc_gshift_logi<R>), dim3((unsigned)((total * m.D + 255) / 256)), dim3(256), 0, h->stream, a, m.D);
             else hipLaunchKernelGGL((k_csmc_gshift<R>), dim3((unsigned)((total * m.D + 255) / 256)), dim3(256), 0, h->stream, a, m.D, m.potential, m.inv_sig_y);
         });
     hipLaunchKernelGGL((k_csmc_gtab<R, M>), dim3(a.T), dim3(64), 0, h->stream, a.T, m, (const R*)a.shd, (R*)a.gtab);

@@ -196,13 +196,20 @@ template <typename R, int D> AXD_HD void trans_mean(const FkDev<R>& m, const R* 
 // the separable kinds share one code path and are told apart at run time inside it; a potential that couples the components through a dx x dx matrix
 // (FkDev::pot_mat) is a variant of its own, so that the instantiations of the other potentials hold none of its code -- as a fifth run-time branch the
 // multivariate-t potential cost every forward instantiation twelve registers in fp64 and a wave of occupancy.  The Poisson count potential is
-// separable like kinds 0 - 3 but a variant of its own for the same reason: the instantiations of the other potentials stay as they were.
-enum { POT_FLAT = 0, POT_GAUSS_OBS = 1, POT_SV = 2, POT_GAUSS_OBS_MASKED = 3, POT_MVT = 4, POT_LIN_GAUSS = 5, POT_POISSON = 6 };
-enum class PotV { SEP, MVT, LIN, POIS };  // separable (kinds 0 - 3) | multivariate Student-t | linear-Gaussian observation | Poisson counts
+// separable like kinds 0 - 3 but a variant of its own for the same reason: the instantiations of the other potentials stay as they were.  So is the logistic
+// potential (binomial / negative-binomial counts), the one kind with a second per-observation number, the size m_{t,k}: for it CsmcArgs::y is (2, T, D),
+// plane 0 the data and plane 1 the sizes, and the kernels read plane 1 at y[(T + t) D + k] under `V == PotV::LOGI` alone (size_at below).  Kind 7 is unassigned.
+enum { POT_FLAT = 0, POT_GAUSS_OBS = 1, POT_SV = 2, POT_GAUSS_OBS_MASKED = 3, POT_MVT = 4, POT_LIN_GAUSS = 5, POT_POISSON = 6, POT_LOGISTIC = 8 };
+// separable (kinds 0 - 3) | multivariate Student-t | linear-Gaussian observation | Poisson counts | logistic (binomial / negative-binomial) counts
+enum class PotV { SEP, MVT, LIN, POIS, LOGI };
 template <PotV V> struct PotC { static constexpr PotV value = V; };
 AXD_HD constexpr PotV pot_variant(int kind) {
-    return kind == POT_MVT ? PotV::MVT : (kind == POT_LIN_GAUSS ? PotV::LIN : (kind == POT_POISSON ? PotV::POIS : PotV::SEP));
+    return kind == POT_MVT ? PotV::MVT : (kind == POT_LIN_GAUSS ? PotV::LIN : (kind == POT_POISSON ? PotV::POIS : (kind == POT_LOGISTIC ? PotV::LOGI : PotV::SEP)));
 }
+// whether the variant reads a size beside every observation (plane 1 of y)
+AXD_HD constexpr bool pot_has_size(PotV v) { return v == PotV::LOGI; }
+// the size m_{t,k} of the logistic potential: plane 1 of the (2, T, D) array y
+template <typename R> AXD_HD R size_at(const R* y, long long T, long long t, int D, int k) { return y[(T + t) * D + k]; }
 // whether the variant carries a dx x dx matrix (FkDev / FkW::pot_mat; the wide kernels stage it in LDS): the coupled potentials
 AXD_HD constexpr bool pot_has_matrix(PotV v) { return v == PotV::MVT || v == PotV::LIN; }
 // f(PotC<V>{}) for the variant V of a run-time kind: the ONE place a kind becomes a template argument (host: the kernel choices; device: potential_rt)
@@ -210,6 +217,7 @@ template <typename F> AXD_HD auto with_pot(int kind, F&& f) {
     if (pot_variant(kind) == PotV::MVT) return f(PotC<PotV::MVT>{});
     if (pot_variant(kind) == PotV::LIN) return f(PotC<PotV::LIN>{});
     if (pot_variant(kind) == PotV::POIS) return f(PotC<PotV::POIS>{});
+    if (pot_variant(kind) == PotV::LOGI) return f(PotC<PotV::LOGI>{});
     return f(PotC<PotV::SEP>{});
 }
 
@@ -306,16 +314,42 @@ template <typename R> AXD_HD R pois_term(R xk, R yk) {
     return (yk - yk == 0) ? v : (R)0;
 }
 template <typename R> AXD_HD R pois_grad_term(R xk, R yk) { return (yk - yk == 0) ? yk - det_exp(xk) : (R)0; }
-// d / dx_k of a potential that is a sum over the components, by variant (SEP: the run-time kind of sep_grad_term; POIS): k_cw_grad, k_csmc_gshift_pois
-template <typename R, PotV V> AXD_HD R comp_grad_term(int kind, R inv_sig_y, R xk, R yk) {
+// The logistic potential (binomial counts with m_k trials, y_k ~ Bin(m_k, sigma(x_k)); negative-binomial counts y_k ~ NB(r, p = sigma(x_k)) with m_k = y_k + r),
+// the ONE definition of its per-component arithmetic (include/auxssm.h: the order; the combinatorial constant is left out): the term y_k x_k - m_k softplus(x_k)
+// and its derivative y_k - m_k sigma(x_k), both 0 for a missing (non-finite) y_k whatever m_k is.  e = det_exp(-|x_k|) <= 1, so nothing overflows at any x_k.
+// There is no det_log1p: det_log(1 + e) rounds 1 + e first, an ABSOLUTE error of at most half an ulp of 1 in softplus (2^-24 in fp32, 2^-53 in fp64), i.e. of
+// m_k ulp / 2 in a log-weight (DESIGN 4q holds the measurement against logaddexp).
+template <typename R> AXD_HD R logi_term(R xk, R yk, R mk) {
+    const R e = det_exp(-(xk < (R)0 ? -xk : xk));
+    const R l = det_log((R)1 + e);
+    const R sp = (xk > (R)0 ? xk : (R)0) + l;
+    const R v = fma_(yk, xk, -(mk * sp));
+    return (yk - yk == 0) ? v : (R)0;
+}
+template <typename R> AXD_HD R logi_grad_term(R xk, R yk, R mk) {
+    const R e = det_exp(-(xk < (R)0 ? -xk : xk));
+    const R r = (R)1 / ((R)1 + e);
+    const R s = xk >= (R)0 ? r : e * r;
+    return (yk - yk == 0) ? fma_(-mk, s, yk) : (R)0;
+}
+// d / dx_k of a potential that is a sum over the components, by variant (SEP: the run-time kind of sep_grad_term; POIS; LOGI, the one that reads the size mk):
+// k_cw_grad, k_csmc_gshift_pois / _logi
+template <typename R, PotV V> AXD_HD R comp_grad_term(int kind, R inv_sig_y, R xk, R yk, R mk = (R)0) {
     static_assert(!pot_has_matrix(V), "a coupled potential's gradient is not component by component (coupled_grad)");
     if constexpr (V == PotV::POIS) return pois_grad_term<R>(xk, yk);
+    else if constexpr (V == PotV::LOGI) return logi_grad_term<R>(xk, yk, mk);
     else return sep_grad_term<R>(kind, inv_sig_y, xk, yk);
 }
 // potential g_t(x_t) (csmc test fixtures test_csmc/common.py:52-75; SV examples/stochastic_volatility/auxiliary_csmc.py:40-46) of the variant V, chosen at
-// COMPILE time; potential_rt below is the run-time choice for the callers that are not register-bound
-template <typename R, int D, PotV V = PotV::SEP> AXD_HD R potential(const FkDev<R>& m, const R* x, const R* y) {
+// COMPILE time; potential_rt below is the run-time choice for the callers that are not register-bound.  sz: the D sizes of row t, read by the logistic variant alone
+template <typename R, int D, PotV V = PotV::SEP> AXD_HD R potential(const FkDev<R>& m, const R* x, const R* y, const R* sz = nullptr) {
     if constexpr (pot_has_matrix(V)) return coupled_value<R, V, D>(m, m.pot_mat, CS_MAXD, x, y);
+    if constexpr (V == PotV::LOGI) {
+        R acc = 0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) acc += logi_term<R>(x[k], y[k], sz[k]);
+        return acc;
+    }
     if constexpr (V == PotV::POIS) {
         R acc = 0;
 #pragma unroll
@@ -356,21 +390,30 @@ template <typename R, int D, PotV V = PotV::SEP> AXD_HD R potential(const FkDev<
     }
     return acc;
 }
-// gx = d potential / dx at x (the closed family's potentials do not read x_{t-1}); y = the D reals of row t, or nullptr
-template <typename R, int D, PotV V = PotV::SEP> __device__ __forceinline__ void potential_grad(const FkDev<R>& m, const R* x, const R* y, R* gx) {
+// gx = d potential / dx at x (the closed family's potentials do not read x_{t-1}); y = the D reals of row t, or nullptr; sz = the D sizes of row t (logistic only)
+template <typename R, int D, PotV V = PotV::SEP>
+__device__ __forceinline__ void potential_grad(const FkDev<R>& m, const R* x, const R* y, R* gx, const R* sz = nullptr) {
     if constexpr (pot_has_matrix(V)) {
         coupled_grad<R, V, D>(m, m.pot_mat, CS_MAXD, x, y, [&](int k, R v) { gx[k] = v; });
+    } else if constexpr (V == PotV::LOGI) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) gx[k] = logi_grad_term<R>(x[k], y[k], sz[k]);
     } else {
 #pragma unroll
         for (int k = 0; k < D; ++k) gx[k] = comp_grad_term<R, V>(m.potential, m.inv_sig_y, x[k], y ? y[k] : (R)0);
     }
 }
 // the potential kind of m at run time, the coupled variants included (the parallel-in-time kernels, a user program that keeps the built-in potential)
-template <typename R, int D> __device__ __forceinline__ R potential_rt(const FkDev<R>& m, const R* x, const R* y) {
-    return with_pot(m.potential, [&](auto pv) { return potential<R, D, decltype(pv)::value>(m, x, y); });
+template <typename R, int D> __device__ __forceinline__ R potential_rt(const FkDev<R>& m, const R* x, const R* y, const R* sz) {
+    return with_pot(m.potential, [&](auto pv) { return potential<R, D, decltype(pv)::value>(m, x, y, sz); });
 }
-template <typename R, int D> __device__ __forceinline__ void potential_grad_rt(const FkDev<R>& m, const R* x, const R* y, R* gx) {
-    with_pot(m.potential, [&](auto pv) { potential_grad<R, D, decltype(pv)::value>(m, x, y, gx); });
+template <typename R, int D> __device__ __forceinline__ void potential_grad_rt(const FkDev<R>& m, const R* x, const R* y, R* gx, const R* sz) {
+    with_pot(m.potential, [&](auto pv) { potential_grad<R, D, decltype(pv)::value>(m, x, y, gx, sz); });
+}
+// sz <- the D sizes of step t when the model's potential is the logistic one (the callers whose kind is a run-time value), zeros otherwise
+template <typename R, int D> __device__ __forceinline__ void size_row_rt(const FkDev<R>& m, const R* y, long long T, long long t, R* sz) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) sz[k] = m.potential == POT_LOGISTIC ? size_at<R>(y, T, t, D, k) : (R)0;
 }
 // out = J^T v, J = d mean / d xp of the transition tr (trans_mean_t): F^T, or the Lorenz-63 step's I + dt dphi/dx (examples/lorenz/model.py:10-25)
 template <typename R, int D> __device__ __forceinline__ void trans_mean_vjp_t(const FkDev<R>& m, const TransT<R>& tr, const R* xp, const R* v, R* out) {
@@ -734,10 +777,11 @@ template <typename R> struct FkUser {
 
 // ---- the model policy of the sweep bodies (compile time) ------------------------------------------------------------------------------------------
 // The bodies below ask a policy object for the two model functions of a step:
-//   pol.log_g(m, t, x, xprev, y)     log G_t(x_t) (xprev = x_{t-1}, nullptr at t = 0; y = the D reals of row t of CsmcArgs::y)
+//   pol.log_g(m, t, x, xprev, y, sz) log G_t(x_t) (xprev = x_{t-1}, nullptr at t = 0; y = the D reals of row t of CsmcArgs::y; sz = the D sizes of row t, plane 1
+//                                    of y, filled by pol.size_row when P::size_row says that the policy may read them and nullptr otherwise)
 //   pol.mean(m, tr, t, xprev, mu)    the mean of x_t | x_{t-1} = xprev under the transition tr (t = the index of x_t)
 // and the gradient kernel (k_csmc_grad) for their derivatives:
-//   pol.grad_log_g(m, t, x, xprev, y, gx, gxprev)   gx = d log G_t / dx, gxprev = d log G_t / dxprev (nullptr at t = 0); both zero-filled by the caller
+//   pol.grad_log_g(m, t, x, xprev, y, gx, gxprev, sz)   gx = d log G_t / dx, gxprev = d log G_t / dxprev (nullptr at t = 0); both zero-filled by the caller
 //   pol.mean_vjp(m, tr, t, xprev, v, out)           out = J^T v, J = d pol.mean(m, tr, t, xprev) / d xprev
 //   P::grad_xprev                                   whether log G_t may depend on xprev (false: k_csmc_grad adds no d / dxprev term)
 // FkBuiltin is the closed family of include/auxssm.h, dispatched on the integers of FkDev (the kernels of csmc.hip), FkBuiltin<R, D, V> the same with a coupled
@@ -745,9 +789,16 @@ template <typename R> struct FkUser {
 // pass evaluates the Gaussian transition density around pol.mean.
 template <typename R, int D, PotV V = PotV::SEP> struct FkBuiltin {
     static constexpr bool grad_xprev = false;
-    __device__ __forceinline__ R log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y) const { return potential<R, D, V>(m, x, y); }
+    static constexpr bool size_row = pot_has_size(V);
+    __device__ __forceinline__ void load_sizes(const FkDev<R>&, const R* y, long long T, long long t, R* sz) const {
+#pragma unroll
+        for (int k = 0; k < D; ++k) sz[k] = size_at<R>(y, T, t, D, k);
+    }
+    __device__ __forceinline__ R log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y, const R* sz = nullptr) const { return potential<R, D, V>(m, x, y, sz); }
     __device__ __forceinline__ void mean(const FkDev<R>& m, const TransT<R>& tr, int, const R* xp, R* mu) const { trans_mean_t<R, D>(m, tr, xp, mu); }
-    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y, R* gx, R*) const { potential_grad<R, D, V>(m, x, y, gx); }
+    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int, const R* x, const R*, const R* y, R* gx, R*, const R* sz = nullptr) const {
+        potential_grad<R, D, V>(m, x, y, gx, sz);
+    }
     __device__ __forceinline__ void mean_vjp(const FkDev<R>& m, const TransT<R>& tr, int, const R* xp, const R* v, R* out) const {
         trans_mean_vjp_t<R, D>(m, tr, xp, v, out);
     }
@@ -772,7 +823,13 @@ template <typename R, int D, typename P = FkBuiltin<R, D>, typename... PA> __glo
         R gp[D];
 #pragma unroll
         for (int k = 0; k < D; ++k) gr[k] = gp[k] = (R)0;
-        pol.grad_log_g(m, (int)t, ut, t > 0 ? u - D : nullptr, yv ? yv + t * D : nullptr, gr, t > 0 ? gp : nullptr);
+        if constexpr (P::size_row) {
+            R sz[D];
+            pol.load_sizes(m, yv, a.T, t, sz);
+            pol.grad_log_g(m, (int)t, ut, t > 0 ? u - D : nullptr, yv ? yv + t * D : nullptr, gr, t > 0 ? gp : nullptr, sz);
+        } else {
+            pol.grad_log_g(m, (int)t, ut, t > 0 ? u - D : nullptr, yv ? yv + t * D : nullptr, gr, t > 0 ? gp : nullptr);
+        }
         if constexpr (P::grad_xprev) {
             if (t + 1 < a.T) {  // log G_{t+1}(u_{t+1}, u_t) as a function of u_t
                 R gn[D], gq[D];
@@ -863,6 +920,9 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
     const bool gen = a.noise_mode != 0 && !a.pregen;
     const long long T2 = (T + 1) >> 1;
     R x[D], eps[D], eps_nx[D], ycur[D], pm[D], un_nx = 0;
+    R szcur[P::size_row ? D : 1];  // the sizes of the step (the logistic potential); unused otherwise
+    const R* szp = P::size_row ? szcur : nullptr;
+    if constexpr (P::size_row) pol.load_sizes(m, yv, T, 0, szcur);
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         eps_nx[k] = 0;
@@ -903,7 +963,7 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
     }
     R lw;
     {
-        R g = pol.log_g(m, 0, x, nullptr, ycur);
+        R g = pol.log_g(m, 0, x, nullptr, ycur, szp);
         if constexpr (SP == 2) {
             g = g + gauss_chol_logpdf<R, D>(x, m.m0, m.LP0, m.iLP0, m.c_init);
             g = guided_weight<R, D>(guided_at<R>(a.gtab, D, 0), g, x, uaux, pm);
@@ -932,6 +992,7 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
         const R gbt = bmode ? gbp[t] : (R)0;
 #pragma unroll
         for (int k = 0; k < D; ++k) ycur[k] = yv ? yv[(long long)t * D + k] : (R)0;
+        if constexpr (P::size_row) pol.load_sizes(m, yv, T, t, szcur);
         if (!gen) {
 #pragma unroll
             for (int k = 0; k < D; ++k) eps[k] = live ? ((const R*)a.eps_prop)[eps_base + ((long long)t * N + tid) * D + k] : (R)0;
@@ -999,7 +1060,7 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
             for (int k = 0; k < D; ++k) x[k] = xstar[(long long)t * D + k];
         }
         // weights (csmc.py:95-96)
-        R g = pol.log_g(m, t, x, xp, ycur);
+        R g = pol.log_g(m, t, x, xp, ycur, szp);
         if constexpr (SP == 2) {
             R mu[D];
             pol.mean(m, tr, t, xp, mu);

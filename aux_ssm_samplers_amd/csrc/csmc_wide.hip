@@ -258,7 +258,9 @@ template <typename R, int NW2, bool GD = false, PotV V = PotV::SEP> __global__ v
             acc0 = xk - m.m0[k];
         }
         const R yk = (yv && k < D) ? yv[k] : (R)0;
-        R g = potential_half<R, V>(m, k, hi, xk, yk, Mrow);
+        R g;
+        if constexpr (V == PotV::LOGI) g = logistic_half<R>(D, k, xk, yk, yv, T, 0);
+        else g = potential_half<R, V>(m, k, hi, xk, yk, Mrow);
         if (m.proposal == 1) g = g + gauss_half<R>(D, k, hi, acc0, m.LP0 + (long long)(k < D ? k : 0) * D, k < D ? m.iLP0[k] : (R)0, m.c_init);  // AuxiliaryG0
         if constexpr (GD) {  // log g + log N(x; m0, P0) + sum_k log N(x_k; u_k, s^2) - log N(x; mu, Lambda_0)
             const GuidedT<R> gd = guided_at<R>(a.gtab, D, 0);
@@ -361,7 +363,9 @@ template <typename R, int NW2, bool GD = false, PotV V = PotV::SEP> __global__ v
                 if (i == 0) xk = xsk;
             }
             // weights (csmc.py:95-96)
-            R g = potential_half<R, V>(m, k, hi, xk, yk, Mrow);
+            R g;
+            if constexpr (V == PotV::LOGI) g = logistic_half<R>(D, k, xk, yk, yv, T, t);
+            else g = potential_half<R, V>(m, k, hi, xk, yk, Mrow);
             if (m.proposal == 1) g = gauss_half_blk<R>(D, k, xk - mu, Lrow, L.blk, ctr) + g;  // AuxiliaryGt = Mt.logpdf + Gt (independent.py:238-248)
             // GradientAuxiliaryGt (:252-268): summed over the particles in the reference, i.e. a constant of the step (AUXSSM_GRAD_REFERENCE: nothing to add);
             // AUXSSM_GRAD_EXACT applies it per particle

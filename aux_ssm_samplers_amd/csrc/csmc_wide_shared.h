@@ -51,7 +51,7 @@ template <typename R> __device__ __forceinline__ void cho_solve_w(int D, const R
 // the gradient of the model's joint log-density at u (csmc_sweep.h::k_csmc_grad, same operations in the same order; one thread per (chain, time step):
 // C T threads of O(dx^2) work, once per sweep -- 0.5 M multiply-adds at the SV protocol's size)
 // V: a coupled potential's gradient is a compile-time variant (its z[32] would otherwise add scratch to the kernel of the other potentials); so is the
-// Poisson potential's, which is component by component like the separable kinds' (csmc_sweep.h::comp_grad_term)
+// Poisson and the logistic potentials', which are component by component like the separable kinds' (csmc_sweep.h::comp_grad_term)
 template <typename R, PotV V = PotV::SEP> __global__ void k_cw_grad(CsmcArgs a, FkW<R> m) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)a.C * a.T) return;
@@ -62,6 +62,8 @@ template <typename R, PotV V = PotV::SEP> __global__ void k_cw_grad(CsmcArgs a, 
     const R* yv = (const R*)a.y;
     if constexpr (pot_has_matrix(V)) {
         coupled_grad<R, V, 0>(m, m.pot_mat, D, u, yv + t * D, [&](int k, R v) { gr[k] = v; });
+    } else if constexpr (pot_has_size(V)) {
+        for (int k = 0; k < D; ++k) gr[k] = comp_grad_term<R, V>(m.potential, m.inv_sig_y, u[k], yv[t * D + k], size_at<R>(yv, a.T, t, D, k));
     } else {
         for (int k = 0; k < D; ++k) gr[k] = comp_grad_term<R, V>(m.potential, m.inv_sig_y, u[k], yv ? yv[t * D + k] : (R)0);
     }
@@ -202,9 +204,19 @@ template <typename R, PotV V> __device__ __forceinline__ R coupled_half(const Fk
     if constexpr (MVT) return mvt_value<R>(m.mvt_hc, (R)1 + q * m.mvt_inv_nu);
     else return lin_value<R>(m.c_obs, q);
 }
+// The logistic potential of that particle (PotV::LOGI), the Poisson shape: the term of this lane's component with its size m_{t,k} -- plane 1 of y,
+// csmc_sweep.h::size_at -- then the half-wave broadcast sum in component order.  A function of its own, called under `if constexpr (V == PotV::LOGI)`: the
+// call sites of the other variants stay token for token what they were, and so do their kernels' registers.
+template <typename R> __device__ __forceinline__ R logistic_half(int D, int k, R xk, R yk, const void* y, int T, long long t) {
+    const R v = k < D ? logi_term<R>(xk, yk, size_at<R>((const R*)y, T, t, D, k)) : (R)0;
+    R acc = 0;
+    static_for<0, CSW_MAXD>([&](auto jc) { acc += half_bcast<R, decltype(jc)::value>(v); });
+    return acc;
+}
 // g_t(x) of that particle, the potential's variant V chosen at compile time.  Separable and Poisson: per-component terms in the lanes, summed in component order
 // (csmc_sweep.h::potential with a runtime dimension, same operations; components beyond D add + 0)
 template <typename R, PotV V> __device__ __forceinline__ R potential_half(const FkW<R>& m, int k, bool hi, R xk, R yk, const R* Mrow) {
+    static_assert(!pot_has_size(V), "the logistic potential reads a size beside yk: logistic_half");
     if constexpr (pot_has_matrix(V)) return coupled_half<R, V>(m, k, xk, yk, Mrow);
     const int D = m.D;
     if constexpr (V == PotV::POIS) {  // SV's shape: the term of this lane's component, then the half-wave broadcast sum in component order

@@ -46,9 +46,12 @@ template <typename R, int D, bool UG, bool UM> struct FkUserPolicy {
     static_assert(!UM || fk_has_mean<R, D>::value,
                   "the dynamics source must define  template <typename R, int D> __device__ void mean(int t, const R* xprev, const R* theta, R* mu)");
     FkUser<R> u;
-    __device__ __forceinline__ R log_g(const FkDev<R>& m, int t, const R* x, const R* xprev, const R* y) const {
+    // a program that keeps the built-in potential may meet the logistic one, whose sizes are plane 1 of CsmcArgs::y: a run-time question here (size_row_rt)
+    static constexpr bool size_row = !UG;
+    __device__ __forceinline__ void load_sizes(const FkDev<R>& m, const R* y, long long T, long long t, R* sz) const { size_row_rt<R, D>(m, y, T, t, sz); }
+    __device__ __forceinline__ R log_g(const FkDev<R>& m, int t, const R* x, const R* xprev, const R* y, const R* sz = nullptr) const {
         if constexpr (UG) return ::log_g<R, D>(t, x, xprev, u.y ? u.y + (long long)t * u.p : nullptr, u.theta_g);
-        else return potential_rt<R, D>(m, x, y);
+        else return potential_rt<R, D>(m, x, y, sz);
     }
     __device__ __forceinline__ void mean(const FkDev<R>& m, const TransT<R>& tr, int t, const R* xp, R* mu) const {
         if constexpr (UM) ::mean<R, D>(t, xp, u.theta_m, mu);
@@ -57,11 +60,11 @@ template <typename R, int D, bool UG, bool UM> struct FkUserPolicy {
     // the derivatives (k_csmc_grad).  A user part without its derivative compiles to nothing here: fk_program.hip refuses such a gradient program
     // before any launch (k_fk_probe below)
     static constexpr bool grad_xprev = UG;
-    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int t, const R* x, const R* xprev, const R* y, R* gx, R* gxprev) const {
+    __device__ __forceinline__ void grad_log_g(const FkDev<R>& m, int t, const R* x, const R* xprev, const R* y, R* gx, R* gxprev, const R* sz = nullptr) const {
         if constexpr (UG) {
             if constexpr (fk_has_grad_log_g<R, D>::value) ::grad_log_g<R, D>(t, x, xprev, u.y ? u.y + (long long)t * u.p : nullptr, u.theta_g, gx, gxprev);
         } else {
-            potential_grad_rt<R, D>(m, x, y, gx);
+            potential_grad_rt<R, D>(m, x, y, gx, sz);
         }
     }
     __device__ __forceinline__ void mean_vjp(const FkDev<R>& m, const TransT<R>& tr, int t, const R* xp, const R* v, R* out) const {

@@ -61,10 +61,11 @@ template <typename R, int D, bool GRAD> __global__ void __launch_bounds__(1024) 
     R g = 0;
     if constexpr (GRAD) g = grad_correction<R, D>(x, uu, pm, sh);  // qt.logpdf(x) - mt.logpdf(x) (pit/csmc.py:84-85), slot 0 included
     if (t == 0) {
-        R y0[D];
+        R y0[D], sz0[D];
 #pragma unroll
         for (int k = 0; k < D; ++k) y0[k] = a.y ? ((const R*)a.y)[k] : (R)0;
-        R g0 = potential_rt<R, D>(m, x, y0);
+        size_row_rt<R, D>(m, (const R*)a.y, T, 0, sz0);
+        R g0 = potential_rt<R, D>(m, x, y0, sz0);
         g0 = g0 + gauss_chol_logpdf<R, D>(x, m.m0, m.LP0, m.iLP0, m.c_init);  // AuxiliaryG0 (independent.py:163-169)
         g = GRAD ? g + g0 : g0;                                               // log_wts.at[0].add(log_w0) (pit/csmc.py:90-91)
     }
@@ -109,13 +110,14 @@ template <typename R, int D> __global__ void __launch_bounds__(1024) k_pit_stitc
         const int ib = fi_right ? fi_right[tid] : tid;
         const R* xa = (const R*)a.xs + (((long long)c * T + mid - 1) * N + ia) * D;
         const R* xv = (const R*)a.xs + (((long long)c * T + mid) * N + ib) * D;
-        R xr[D], xl[D], mm[D], yv[D];
+        R xr[D], xl[D], mm[D], yv[D], sz[D];
 #pragma unroll
         for (int q = 0; q < D; ++q) {
             xl[q] = xa[q];
             xr[q] = xv[q];
             yv[q] = a.y ? ((const R*)a.y)[mid * D + q] : (R)0;
         }
+        size_row_rt<R, D>(m, (const R*)a.y, T, mid, sz);
         trans_mean_t<R, D>(m, tr, xl, mm);
 #pragma unroll
         for (int q = 0; q < D; ++q) {
@@ -131,7 +133,7 @@ template <typename R, int D> __global__ void __launch_bounds__(1024) k_pit_stitc
         } else if (mid == 1) {
             wl = ((const R*)a.lw0)[(long long)c * N + ia];
         }
-        pg[tid] = potential_rt<R, D>(m, xr, yv) + wr;
+        pg[tid] = potential_rt<R, D>(m, xr, yv, sz) + wr;
         hh[tid] = wl;
     }
     __syncthreads();

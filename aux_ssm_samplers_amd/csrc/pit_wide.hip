@@ -11,7 +11,7 @@
 //            carried over line for line.  The N transition means and the N potentials are formed in the half-wave form; the N^2 densities are evaluated one pair
 //            per lane by a forward substitution unrolled to 32 rows, rows beyond dx skipped: the row-oriented order of csmc_sweep.h::gauss_chol_logpdf itself.
 //   trace    pit.hip::k_pit_trace (run-time dx).
-// Linear-Gaussian transitions (time-invariant, or time-varying: a stitch stages row mid - 1), the seven built-in potentials, gradient proposals (the per-particle
+// Linear-Gaussian transitions (time-invariant, or time-varying: a stitch stages row mid - 1), the eight built-in potentials, gradient proposals (the per-particle
 // correction in either AUXSSM_GRAD_* mode, as for dx <= 4), fp32 and fp64, explicit and Threefry noise.
 #include "csmc_wide_shared.h"
 #include "pit_shared.h"
@@ -95,7 +95,9 @@ template <typename R, PotV V> __global__ void __launch_bounds__(PWL_NT) k_pitw_l
         if (grad) g = grad_corr_half<R>(D, k, xk, uk, pmk, sh);  // qt.logpdf(x) - mt.logpdf(x) (pit/csmc.py:84-85), slot 0 included
         if (t == 0) {
             const R yk = (a.y && k < D) ? ((const R*)a.y)[k] : (R)0;
-            R g0 = potential_half<R, V>(m, k, hi, xk, yk, Mrow);
+            R g0;
+            if constexpr (V == PotV::LOGI) g0 = logistic_half<R>(D, k, xk, yk, a.y, T, 0);
+            else g0 = potential_half<R, V>(m, k, hi, xk, yk, Mrow);
             g0 = g0 + gauss_half<R>(D, k, hi, k < D ? xk - m.m0[k] : (R)0, m.LP0 + (long long)kk * D, k < D ? m.iLP0[k] : (R)0, m.c_init);  // AuxiliaryG0
             g = grad ? g + g0 : g0;  // log_wts.at[0].add(log_w0) (pit/csmc.py:90-91)
         }
@@ -219,7 +221,9 @@ template <typename R, PotV V> __global__ void __launch_bounds__(256) k_pitw_stit
 #pragma unroll
             for (int p = 0; p < CSW_MAXD; ++p) mq = fma_(Frow[p], xl[p], mq);  // (columns beyond D are zeros on both sides: fma(0, 0, mq) = mq)
             __builtin_amdgcn_wave_barrier();
-            const R g = potential_half<R, V>(m, q, hi, xv, yq, Mrow);
+            R g;
+            if constexpr (V == PotV::LOGI) g = logistic_half<R>(D, q, xv, yq, a.y, T, mid);
+            else g = potential_half<R, V>(m, q, hi, xv, yq, Mrow);
             if (pl && q < D) {
                 L.mu[i * PW_S + q] = mq;
                 L.xb[i * PW_S + q] = xv;

@@ -7,7 +7,7 @@ kalman.get_kernel.
 """
 import numpy as np
 
-from .. import _lib
+from .. import _lib, _logistic
 from .._primitives.kalman.base import DeviceLGSSM, _upload_arr
 
 
@@ -332,14 +332,6 @@ class _LogisticModel(_StateSpaceModel):
         super().__init__(ys, m0, P0, F, Q, b, order)
         self.size = np.asarray(size, np.float64)
 
-    @staticmethod
-    def _per_observation(a, shape, name):
-        """a scalar, (dx,) or (T, dx) parameter as a (T, dx) float64 array"""
-        a = np.asarray(a, np.float64)
-        if a.ndim > 2 or (a.ndim == 2 and a.shape != shape) or (a.ndim == 1 and a.shape != shape[1:]):
-            raise ValueError(f"{name} must be a scalar, ({shape[1]},) or {shape}, got shape {a.shape}")
-        return np.array(np.broadcast_to(a, shape))
-
     def _terms(self, x):
         """(mask, y, m, e, r) at x (T, dx), the data in x's dtype"""
         e = np.exp(-np.abs(x))
@@ -389,15 +381,7 @@ class BinomialModel(_LogisticModel):
         ys = np.asarray(ys)
         if ys.ndim != 2:
             raise ValueError(f"BinomialModel: ys must be (T, dx), got shape {ys.shape}")
-        n = self._per_observation(trials, ys.shape, "BinomialModel: trials")
-        seen = np.isfinite(np.asarray(ys, np.float64))
-        if np.any(seen & ~np.isfinite(n)):
-            raise ValueError("BinomialModel: trials must be finite wherever y is observed")
-        if np.any(n[np.isfinite(n)] <= 0):
-            raise ValueError(f"BinomialModel: trials must be > 0; got a minimum of {float(np.nanmin(n))}")
-        yv = np.asarray(ys, np.float64)
-        if np.any(seen & ((yv < 0) | (yv > np.where(seen, n, np.inf)))):
-            raise ValueError("BinomialModel: every observed y must lie in [0, trials]")
+        n = _logistic.binomial_size(ys, trials, "BinomialModel")
         super().__init__(ys, n, m0, P0, F, Q, b, order)
         self.trials = n
 
@@ -421,16 +405,8 @@ class NegBinomialModel(_LogisticModel):
         ys = np.asarray(ys)
         if ys.ndim != 2:
             raise ValueError(f"NegBinomialModel: ys must be (T, dx), got shape {ys.shape}")
-        rr = self._per_observation(r, ys.shape, "NegBinomialModel: r")
-        yv = np.asarray(ys, np.float64)
-        seen = np.isfinite(yv)
-        if np.any(seen & ~np.isfinite(rr)):
-            raise ValueError("NegBinomialModel: r must be finite wherever y is observed")
-        if np.any(rr[np.isfinite(rr)] <= 0):
-            raise ValueError(f"NegBinomialModel: r must be > 0; got a minimum of {float(np.nanmin(rr))}")
-        if np.any(yv[seen] < 0):
-            raise ValueError(f"NegBinomialModel: counts must be >= 0 or NaN (missing); got a minimum of {float(np.nanmin(yv))}")
-        super().__init__(ys, yv + rr, m0, P0, F, Q, b, order)
+        rr = _logistic.negbinomial_r(ys, r, "NegBinomialModel")
+        super().__init__(ys, np.asarray(ys, np.float64) + rr, m0, P0, F, Q, b, order)
         self.r = rr
 
 

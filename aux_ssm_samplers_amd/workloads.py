@@ -140,12 +140,13 @@ def poisson_kalman_setup(T, dx, seed=0, order=1):
     return PoissonModel(y, M0.m0, M0.P0, Mt.F, Mt.Q, Mt.b, order=order), x
 
 
-def logistic_kalman_setup(T, dx, family="binomial", seed=0, order=1):
-    """Binomial or negative-binomial data with a logit link for the auxiliary Kalman sampler: AR(1) log-odds x_t = 0.9 x_{t-1} + eps_t per component, Q = 0.04 I,
-    m0 = b = 0, P0 = 0.2 I (about the stationary variance).  family "binomial": trials drawn from 1 .. 40 per observation, component 0 binary (trials = 1),
-    y ~ Binomial(trials, sigma(x)); "negbinomial": r = 3, y ~ NB(3, p = sigma(x)) (mean 3 e^x), drawn as a Gamma-Poisson mixture.
-    Returns (model, x0): a kalman.BinomialModel or kalman.NegBinomialModel and a start state (T, dx) -- the simulated log-odds."""
-    from aux_ssm_samplers_amd.kalman import BinomialModel, NegBinomialModel
+def logistic_setup(T, dx, family="binomial", seed=0):
+    """Binomial or negative-binomial data with a logit link: AR(1) log-odds x_t = 0.9 x_{t-1} + eps_t per component, Q = 0.04 I, m0 = b = 0, P0 = 0.2 I (about
+    the stationary variance).  family "binomial": trials drawn from 1 .. 40 per observation, component 0 binary (trials = 1), y ~ Binomial(trials, sigma(x));
+    "negbinomial": r = 3, y ~ NB(3, p = sigma(x)) (mean 3 e^x), drawn as a Gamma-Poisson mixture.
+    Returns (M0, Mt, G0, Gt, x, y, par): the model as the cSMC kernels take it (csmc.BinomialPotential / NegBinomialPotential), the simulated log-odds and data
+    (float64) and the family's parameter -- the trials (T, dx), or r = 3.0."""
+    from aux_ssm_samplers_amd.csmc import GaussianInit, LinearGaussianDynamics, BinomialPotential, NegBinomialPotential
     rng = np.random.Generator(np.random.PCG64(seed))
     F, Q, P0 = 0.9 * np.eye(dx), 0.04 * np.eye(dx), 0.2 * np.eye(dx)
     m0, b = np.zeros(dx), np.zeros(dx)
@@ -157,11 +158,22 @@ def logistic_kalman_setup(T, dx, family="binomial", seed=0, order=1):
         trials = rng.integers(1, 41, size=(T, dx)).astype(np.float64)
         trials[:, 0] = 1.0
         y = rng.binomial(trials.astype(np.int64), 1.0 / (1.0 + np.exp(-x))).astype(np.float64)
-        return BinomialModel(y, trials, m0, P0, F, Q, b, order=order), x
-    if family == "negbinomial":
+        G0, Gt, par = BinomialPotential(trials[0], y=y[0]), BinomialPotential(trials[1:], params=y[1:]), trials
+    elif family == "negbinomial":
         y = rng.poisson(rng.gamma(3.0, np.exp(x))).astype(np.float64)
-        return NegBinomialModel(y, 3.0, m0, P0, F, Q, b, order=order), x
-    raise ValueError(f"family must be 'binomial' or 'negbinomial', got {family!r}")
+        G0, Gt, par = NegBinomialPotential(3.0, y=y[0]), NegBinomialPotential(3.0, params=y[1:]), 3.0
+    else:
+        raise ValueError(f"family must be 'binomial' or 'negbinomial', got {family!r}")
+    return GaussianInit(m0=m0, P0=P0), LinearGaussianDynamics(F=F, b=b, Q=Q), G0, Gt, x, y, par
+
+
+def logistic_kalman_setup(T, dx, family="binomial", seed=0, order=1):
+    """The model of logistic_setup for the auxiliary Kalman sampler (same recipe, same seed -> same x and y).
+    Returns (model, x0): a kalman.BinomialModel or kalman.NegBinomialModel and a start state (T, dx) -- the simulated log-odds."""
+    from aux_ssm_samplers_amd.kalman import BinomialModel, NegBinomialModel
+    M0, Mt, _, _, x, y, par = logistic_setup(T, dx, family, seed)
+    model = BinomialModel if family == "binomial" else NegBinomialModel
+    return model(y, par, M0.m0, M0.P0, Mt.F, Mt.Q, Mt.b, order=order), x
 
 
 def poisson_lin_setup(T, dx, dy, seed=0, order=1):

@@ -313,12 +313,12 @@ int auxssm_kalman_state_resolve(auxssm_handle h, int dtype, const auxssm_dims* d
  *   transition  x_t | x_{t-1} ~ N(F x_{t-1} + b, Q)   (time-invariant), initial N(m0, P0)
  *   potential   FLAT: 0 | GAUSS_OBS: log N(y_t; x_t, sig_y^2 I) | SV: sum_k log N(y_{t,k}; 0, exp(x_{t,k})) | GAUSS_OBS_MASKED | MVT: multivariate Student-t
  *               with a precision matrix | LIN_GAUSS: log N(y_t; H x_t + c, R), dy <= dx | POISSON: sum_k [y_{t,k} x_{t,k} - exp(x_{t,k})]
- *               (auxssm_fk_potential below)
+ *               | LOGISTIC: sum_k [y_{t,k} x_{t,k} - m_{t,k} softplus(x_{t,k})], binomial / negative-binomial counts (auxssm_fk_potential below)
  *   proposal    BOOTSTRAP_LG:    M0 = initial, Mt = transition, G0/Gt = potential          (test_csmc/common.py fixtures)
  *               AUX_INDEPENDENT: u = x + sqrt(delta_t/2) eps_aux; M0/Mt = N(u_t, delta_t/2 I);
  *                                G0 = log initial + potential, Gt = log transition + potential, Pt = transition
  * m0, chol_P0 (lower), F, b, chol_Q (lower) are small HOST arrays of doubles; y (T, dx) is a DEVICE array of `dtype`
- * shared by all chains; sqrt_half_delta (T) is a DEVICE array of `dtype` (AUX_INDEPENDENT only).
+ * shared by all chains ((2, T, dx) for AUXSSM_POT_LOGISTIC: the data, then the sizes); sqrt_half_delta (T) is a DEVICE array of `dtype` (AUX_INDEPENDENT only).
  *
  * Noise: EXPLICIT device arrays (the parity contract): eps_aux (C,T,dx) [AUX only], eps_prop (C,T,N,dx) ~ N(0,1) (row t
  * feeds M0 / Mt.sample at time t), u_res (C,T-1,N) ~ U[0,1) (row t-1 resamples into time t), u_bwd (C,T) (entry t draws
@@ -370,7 +370,7 @@ typedef enum {
                                         Gradient:  d log g / dx_j = sum_k fma(H_kj, z_k, .) with k ascending from 0, every component 0 when v is NaN.
                                         sup_x log g <= c_lin (0 on a NaN row), the forward pass's reduction-free bound at dx <= 4; the wide kernels (dx > 4) shift by the exact
                                         maximum of every step, as for AUXSSM_POT_MVT. */
-    AUXSSM_POT_POISSON = 6           /* counts with a log link, y_{t,k} ~ Poisson(exp(x_{t,k})), independent over the components:
+    AUXSSM_POT_POISSON = 6,          /* counts with a log link, y_{t,k} ~ Poisson(exp(x_{t,k})), independent over the components:
                                           log g_t(x) = sum_k [ y_{t,k} x_k - exp(x_k) ]   over the components whose y_{t,k} is finite
                                         (a NaN y_{t,k} drops component k of step t, per component as for AUXSSM_POT_SV -- not the whole-step rule of the coupled kinds).
                                         UNNORMALISED: the constant -sum_k log y_{t,k}! is left out, as the multivariate-t potential leaves out its normaliser; it does
@@ -383,6 +383,23 @@ typedef enum {
                                         sup_x log g = sum_k (y_k > 0 ? y_k (det_log(y_k) - 1) : 0) (attained at x_k = log y_k; missing components and y_k = 0 add 0), always
                                         finite: the forward pass's reduction-free bound at dx <= 4; the wide kernels (dx > 4) shift by the exact maximum of every step,
                                         as for AUXSSM_POT_MVT and AUXSSM_POT_LIN_GAUSS. */
+    /* 7 is unassigned: "unknown potential kind 7" */
+    AUXSSM_POT_LOGISTIC = 8          /* counts with a logit link and a SIZE m_{t,k} > 0 beside every observation, independent over the components:
+                                          log g_t(x) = sum_k [ y_{t,k} x_k - m_{t,k} softplus(x_k) ]   over the components whose y_{t,k} is finite
+                                        -- binomial y ~ Bin(m, sigma(x)) with m = the trials (binary data: m = 1); negative binomial y ~ NB(r, p = sigma(x)) with
+                                        m = y + r.  A NaN y_{t,k} drops component k of step t whatever m_{t,k} is; UNNORMALISED (the combinatorial constant is left
+                                        out); non-integers are accepted; nothing is checked on the device.
+                                        The size adds no field: for THIS kind y is a device array of shape (2, T, dx), plane 0 the data and plane 1 the sizes (0 where
+                                        the data is missing), so m_{t,k} = y[(T + t) dx + k].
+                                        Arithmetic order (every kernel; explicit fma, det_exp, det_log, no contraction):  e = det_exp(-|x_k|) (<= 1: nothing overflows
+                                        at any x);  l = det_log(1 + e);  sp = max(x_k, 0) + l;  v_k = fma(y_k, x_k, -(m_k sp)), counted only if y_k - y_k == 0;
+                                        log g = sum of the counted v_k, accumulated over k ascending from 0 (from 0).  There is no det_log1p: det_log(1 + e) carries
+                                        an absolute error of at most half an ulp of 1 in softplus, i.e. m_k ulp / 2 in a log-weight.
+                                        Gradient:  r = 1 / (1 + e);  s = (x_k >= 0) ? r : e r;  d log g / dx_k = fma(-m_k, s, y_k), 0 for a missing component.
+                                        sup_x log g = sum_k b_k over the finite y_k, the binomial log-likelihood at p = y / m written without cancellation,
+                                          b_k = (y_k > 0 ? y_k det_log(y_k / m_k) : 0) + (m_k - y_k > 0 ? (m_k - y_k) det_log((m_k - y_k) / m_k) : 0)
+                                        (<= 0, always finite; 0 at y = 0 and y = m, where it is approached, not attained): the forward pass's reduction-free bound at
+                                        dx <= 4; the wide kernels (dx > 4) shift by the exact maximum of every step, as for AUXSSM_POT_POISSON. */
 } auxssm_fk_potential;
 /* transition x_{t+1} | x_t ~ N(mean(x_t), Q): LINEAR mean = F x + b; LORENZ63_EM mean = x + dt (phi_0(x) + theta * phi(x)), the
  * Euler-Maruyama step of examples/lorenz/model.py:10-25 (dx = 3; theta = F[0..2], dt = b[0], Q = chol_Q chol_Q^T = dt sigma_x^2 I) */
@@ -491,7 +508,7 @@ int auxssm_csmc_sweep_program(auxssm_handle h, auxssm_fk_program prog, int dtype
  * same flat indices).  x (C,T,dx) in/out; ancestors (C,T) int32 = the leaf particle index selected at each step (updated =
  * ancestors != 0).  T >= 2, 2 <= N <= 1024.  Reduction orders and exp/log are fixed (csrc/pit.hip): bit-exact vs oracle/csmc_ref.c.
  * Covered: dx <= 4 (csrc/pit.hip) -- every transition and potential of the family, gradient NONE / REFERENCE / EXACT (in the tree both are the per-particle
- * correction), N <= 1024; 4 < dx <= 32 (csrc/pit_wide.hip) -- AUXSSM_TRANS_LINEAR, time-invariant or time-varying, the seven built-in potentials, the same
+ * correction), N <= 1024; 4 < dx <= 32 (csrc/pit_wide.hip) -- AUXSSM_TRANS_LINEAR, time-invariant or time-varying, the eight built-in potentials, the same
  * gradient modes, 2 <= N <= 64, fp32 and fp64, both noise modes, several chains per launch.  AUXSSM_ERR_UNSUPPORTED, with the limit in the message: dx > 32;
  * at dx > 4, N > 64 and AUXSSM_TRANS_LORENZ63_EM; guided proposals (AUXSSM_PROP_AUX_GUIDED) at any dx.  User programs have no parallel-in-time entry point. */
 int auxssm_csmc_pit_sweep(auxssm_handle h, int dtype, const auxssm_fk_model* model, int32_t C, int32_t T, int32_t N,

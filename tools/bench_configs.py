@@ -9,6 +9,8 @@
              at the same shape, 256 chains
    poisson  multivariate counts with a log link (Poisson potential) beside SVPotential at the SV protocol's shape (D = 30, T = 250, N = 25, fp32), 1 / 16 / 256
              chains: independent, gradient, guided and parallel-in-time sweeps
+   logistic  binomial data with a logit link (logistic potential) beside PoissonPotential at the SV protocol's shape (D = 30, T = 250, N = 25, fp32), 1 / 16 / 256
+             chains: independent, gradient, guided and parallel-in-time sweeps
    spatial_kalman  the spatial example's default sampler: the auxiliary Kalman sampler on the batched 8 x 8 model (d = 64, T = 1024, nu = 1, fp32, both orders), device
              sweep at 1 / 16 / 256 chains beside the host-factory path
    poisson_kalman  count data under the auxiliary Kalman sampler (kalman.PoissonModel, fp32, both orders) at T = 250, dx = 30 and T = 16384, dx = 1, 1 / 64 / 256 /
@@ -455,6 +457,44 @@ def poisson(D=30, T=250, N=25, chain_counts=(1, 16, 256), reps=5, runs=3):
                                   poisson_over_sv_rate=round(best["SV"] / best["Poisson"], 3), updated=upd)), flush=True)
 
 
+def logistic(D=30, T=250, N=25, chain_counts=(1, 16, 256), reps=5, runs=3, family="binomial"):
+    """binomial data with a logit link (workloads.logistic_setup) through the wide cSMC kernels with the logistic potential at the SV protocol's shape (D = 30,
+    T = 250, N = 25, fp32, resident chains, Threefry noise): independent proposals, independent with gradient, guided proposals (backward sampling) and the
+    parallel-in-time sweep -- each beside the SAME sweep with PoissonPotential on the same dynamics and a data array of the same shape (per component and particle
+    the logistic term is one det_exp, one det_log and an fma where Poisson's is one det_exp and an fma).  `runs` measurements per leg, potentials alternating."""
+    from aux_ssm_samplers_amd.workloads import logistic_setup
+    from aux_ssm_samplers_amd.csmc import CsmcChains, CSMCState, get_independent_kernel, get_guided_kernel, PoissonPotential
+    h = _lib.default_handle()
+    M0, Mt, G0, Gt, x, y, _ = logistic_setup(T, D, family)
+    yp = np.random.Generator(np.random.PCG64(1)).poisson(np.exp(x)).astype(np.float64)
+    pots = (("logistic", G0, Gt), ("Poisson", PoissonPotential(y=yp[0]), PoissonPotential(params=yp[1:])))
+    legs = (("independent", get_independent_kernel, dict(backward=True, gradient=False)), ("independent", get_independent_kernel, dict(backward=True, gradient=True)),
+            ("guided", get_guided_kernel, dict(backward=True, gradient=False)), ("parallel-in-time", get_independent_kernel, dict(parallel=True)))
+    for name, get, kw in legs:
+        for chains in chain_counts:
+            ms = {p[0]: [] for p in pots}
+            upd = {}
+            for run in range(runs):
+                for pname, g0, gt in pots:
+                    init, kernel = get(M0, g0, Mt, gt, N, Pt=Mt, **kw)
+                    cc = CsmcChains(h, np.repeat(x[None], chains, axis=0).astype(np.float32))
+                    st = CSMCState(x=cc, updated=None)
+                    kernel(0, st, 0.01)
+                    h.sync()
+                    t0 = time.perf_counter()
+                    for k in range(reps):
+                        kernel(1 + k, st, None)
+                    h.sync()
+                    ms[pname].append((time.perf_counter() - t0) / reps * 1e3)
+                    upd[pname] = float((cc.ancestors.to_host() != 0).mean())
+                    del cc, st
+            best = {k: min(v) for k, v in ms.items()}
+            print(json.dumps(dict(config=f"logistic ({family}) D={D} T={T}, aux-cSMC N={N} {name} proposals ({', '.join(f'{k}={v}' for k, v in kw.items())}), fp32, resident chains",
+                                  chains=chains, ms_per_sweep_call={k: [round(v_, 3) for v_ in v] for k, v in ms.items()},
+                                  sweeps_per_s={k: round(chains / v * 1e3, 1) for k, v in best.items()},
+                                  logistic_over_poisson_rate=round(best["Poisson"] / best["logistic"], 3), updated=upd)), flush=True)
+
+
 def sv30_kalman(T=250, D=30, chains=(1, 16, 64)):
     """the other sampler of the same protocol: the auxiliary Kalman sampler with first / second order linearisation of the SV observation model at D = 30
     (examples/stochastic_volatility/auxiliary_kalman.py:22-48), fp64 as the reference runs it, parallel scan; wide-state kernels (dx = 30)"""
@@ -833,6 +873,8 @@ if __name__ == "__main__":
         lingauss()
     if "poisson" in which:
         poisson()
+    if "logistic" in which:
+        logistic()
     if "sv30k" in which:
         sv30_kalman()
     if "pit" in which:
