@@ -1,19 +1,14 @@
-"""The linear-Gaussian observation potential (AUXSSM_POT_LIN_GAUSS) as GENERIC protocol objects for the literal NumPy cSMC (oracle/csmc_np.py), the cases the
-tests of this potential share, and the exact posterior of the whole (linear-Gaussian) model.  Test infrastructure only, written independently of the package:
+"""The linear-Gaussian observation potential (AUXSSM_POT_LIN_GAUSS) for the literal NumPy cSMC (tests/potential_np.py on oracle/csmc_np.py), the cases the tests
+of this potential share, and the exact posterior of the whole (linear-Gaussian) model.  Test infrastructure only, written independently of the package:
 
     log g_t(x) = log N(y_t; H x + c, R),   NaN -> 0
 
-with np.linalg.solve on the UNWHITENED residual and slogdet -- neither the kernels' whitened form nor their operation order: agreement is to rounding.
-
-The literal independent sampler with gradient proposals differentiates the joint log-density by central differences (oracle/csmc_np.py), whose error is far
-above the 1e-12 the particles are held to; `independent_kernel` builds the same sampler from the same oracle classes with the gradient in closed form
-(`joint_grad`), which tests/test_lingauss_potential.py holds against those central differences (the arrangement of tests/mvt_np.py)."""
-import functools
-
+with np.linalg.solve on the UNWHITENED residual and slogdet -- neither the kernels' whitened form nor their operation order: agreement is to rounding."""
 import numpy as np
 
 from oracle import csmc_np as L
-from tests import guided_np as G
+from tests import pit_cases as PC
+from tests import potential_np as P
 
 
 def log_g(x, y, H, R, c):
@@ -36,79 +31,6 @@ def grad_log_g(x, y, H, R, c):
         g = np.linalg.solve(R, r.T).T @ H
     g = np.where(np.isnan(g), 0.0, g)
     return g if x.ndim > 1 else g[0]
-
-
-class LinGaussPotential:
-    """g_t as a `Potential` with params = y[1:] and as the `UnivariatePotential` of y[0] (oracle.csmc_np.ObsPotential's two roles)"""
-
-    def __init__(self, H, R, c, y, first=False):
-        self.H, self.R, self.c, self.first = np.asarray(H, np.float64), np.asarray(R, np.float64), np.asarray(c, np.float64), first
-        self.params = None if first else np.asarray(y)
-        self.y0 = np.asarray(y) if first else None
-
-    def __call__(self, *a):
-        return log_g(a[0], self.y0 if self.first else a[2], self.H, self.R, self.c)
-
-
-class Model(G.Model):
-    """tests/guided_np.py's model record with this potential (time-invariant transitions)"""
-
-    def __init__(self, m0, P0, dyn, Q, H, R, c, y):
-        super().__init__(m0, P0, dyn, Q, LinGaussPotential(H, R, c, y[0], first=True), LinGaussPotential(H, R, c, y[1:]), "lingauss", y)
-        self.H, self.R, self.c = np.asarray(H, np.float64), np.asarray(R, np.float64), np.asarray(c, np.float64)
-        self.F, self.b = np.asarray(dyn.params[0][0], float), np.asarray(dyn.params[1][0], float)
-
-    def literal(self):
-        """(M0, G0, Mt, Gt) of the literal sampler"""
-        return L.GaussianInit(self.m0, self.LP0), self.G0, self.dyn, self.Gt
-
-
-def joint_grad(m, u):
-    """the gradient at u (T, d) of log M0(u_0) + G0(u_0) + sum_t [log Mt(u_{t+1} | u_t) + Gt(u_{t+1})] (csmc/independent.py:121-134), in closed form"""
-    T = u.shape[0]
-    g = np.stack([grad_log_g(u[t], m.y[t], m.H, m.R, m.c) for t in range(T)])
-    g[0] -= np.linalg.solve(m.P0, u[0] - m.m0)
-    for t in range(1, T):
-        w = np.linalg.solve(m.Q, u[t] - (m.F @ u[t - 1] + m.b))
-        g[t] -= w
-        g[t - 1] += m.F.T @ w
-    return g
-
-
-def guided_kernel(m, N, backward=False, gradient=False):
-    """the literal guided sampler of tests/guided_np.py; its gradient variant shifts u by s^2 grad log g_t(u_t)"""
-    def shifted(u, scale):
-        if not gradient:
-            return u
-        return u + (scale * scale)[:, None] * np.stack([grad_log_g(u[t], m.y[t], m.H, m.R, m.c) for t in range(u.shape[0])])
-
-    def f(u, scale):
-        T = u.shape[0]
-        tab = [G.tables(m.P0 if t == 0 else m.Q, float(scale[t])) for t in range(T)]
-        Ks, Cs = np.stack([a for a, _ in tab]), np.stack([b for _, b in tab])
-        ut = shifted(u, scale)
-        return (G.GuidedM0(m, ut[0], Ks[0], Cs[0]), G.GuidedG0(m, u[0], scale[0], ut[0], Ks[0], Cs[0]),
-                G.GuidedMt(m, (ut[1:], Ks[1:], Cs[1:], m.dyn.params)),
-                G.GuidedGt(m, (u[1:], scale[1:], ut[1:], Ks[1:], Cs[1:], m.dyn.params, m.Gt.params)))
-    return L.get_generic_kernel(f, N, backward, m.dyn)
-
-
-def independent_kernel(m, N, backward=False, gradient=False):
-    """oracle.csmc_np.get_independent_kernel on this model; gradient: False, True (the reference's weighting) or "exact", with joint_grad for jax.grad"""
-    M0, G0, Mt, Gt = m.literal()
-    if not gradient:
-        return L.get_independent_kernel(M0, G0, Mt, Gt, N, backward=backward, Pt=Mt)
-
-    def f(u, scale):
-        gp = joint_grad(m, u)
-        return (L.AuxiliaryM0(u[0], scale[0], gp[0]), L.GradientAuxiliaryG0(M0, G0, u[0], scale[0], gp[0]),
-                L.AuxiliaryMtDynamics((u[1:], scale[1:], gp[1:])), L.GradientAuxiliaryGt(Mt, Gt, (u[1:], scale[1:], gp[1:]), gradient == "exact"))
-    return L.get_generic_kernel(f, N, backward, Mt)
-
-
-def bootstrap_kernel(m, N, backward=False):
-    M0, G0, Mt, Gt = m.literal()
-    return L.get_kernel(M0, G0, Mt, Gt, N, backward=backward, Pt=Mt)
 
 
 def exact_posterior(m):
@@ -152,21 +74,16 @@ def build(m0, P0, F, b, Q, H, R, c, y):
     T = y.shape[0]
     M0, Mt = GaussianInit(m0=m0, P0=P0), LinearGaussianDynamics(F=F, b=b, Q=Q)
     dev = (M0, LinearGaussianPotential(H=H, R=R, c=c, y=y[0]), Mt, LinearGaussianPotential(H=H, R=R, c=c, params=y[1:]))
-    return dev, Model(m0, P0, L.LinearGaussianDynamics(F, b, np.linalg.cholesky(Q), T), Q, H, R, c, y)
+    H, R, c = np.asarray(H, np.float64), np.asarray(R, np.float64), np.asarray(c, np.float64)
+    return dev, P.Model(KIND, m0, P0, L.LinearGaussianDynamics(F, b, np.linalg.cholesky(Q), T), Q, y, (H, R, c), H=H, R=R, c=c)
 
 
 def case(d, dy, T, rng, nan_rows=()):
-    """tests/guided_np.py::sv_case's linear-Gaussian dynamics observed through `observation`.  nan_rows: time steps whose observation has a NaN component (the
-    step is flat).  Returns (device objects (M0, G0, Mt, Gt), literal Model, a trajectory, delta in [0.2, 0.8] / d: proposals that N <= 64 particles can
-    follow at every d)."""
-    F = 0.9 * np.eye(d) + 0.02 * rng.standard_normal((d, d)) / np.sqrt(d)
-    b = 0.05 * rng.standard_normal(d)
-    Q, P0, m0 = G.spd(d, rng), G.spd(d, rng, 0.5), 0.1 * rng.standard_normal(d)
+    """tests/potential_np.py::dynamics observed through `observation`.  nan_rows: time steps whose observation has a NaN component (the step is flat).  Returns
+    (device objects (M0, G0, Mt, Gt), literal Model, a trajectory, delta in [0.2, 0.8] / d: proposals that N <= 64 particles can follow at every d)."""
+    m0, P0, F, b, Q = P.dynamics(d, rng)
     H, R, c = observation(d, dy, rng)
-    x = np.zeros((T, d))
-    x[0] = m0 + np.linalg.cholesky(P0) @ rng.standard_normal(d)
-    for t in range(1, T):
-        x[t] = F @ x[t - 1] + b + np.linalg.cholesky(Q) @ rng.standard_normal(d)
+    x = P.trajectory(m0, P0, F, b, Q, T, rng)
     y = x @ H.T + c + rng.standard_normal((T, dy)) @ np.linalg.cholesky(R).T
     for i, t in enumerate(nan_rows):
         y[t, i % dy] = np.nan
@@ -190,68 +107,38 @@ PROGRAM_SHAPES = [(1, 1, 1024, 40, 5), (2, 1, 100, 40, 5), (4, 2, 64, 24, 3), (4
 LITERAL_CASES = dict(r1=(1, 1, 1024, 40), r3=(3, 2, 100, 33), r4=(4, 1, 64, 24),
                      w5=(5, 3, 33, 20), w9=(9, 9, 25, 20), w25=(25, 12, 25, 25), w32a=(32, 1, 64, 12), w32b=(32, 32, 64, 12))  # (d, dy, N, T)
 REGISTER, WIDE = ("r1", "r3", "r4"), ("w5", "w9", "w25", "w32a", "w32b")
-LITERAL_CELLS = ([("independent", g, bw) for g in (False, True, "exact") for bw in (False, True)]
-                 + [("guided", g, bw) for g in (False, True) for bw in (False, True)])
 BOOTSTRAP_CASES = ("r3", "w9")
 
 
-# (cell, case) -> how often its seed was advanced until no draw of the literal sweep lay within 1e-8 of a cumulative-sum edge (wellposedness below; at N = 1024
-# and T = 40 some forty thousand draws meet a thousand edges, so a first seed fails about every other time)
+# (cell, case) -> how often its seed was advanced until no draw of the literal sweep lay within 1e-8 of a cumulative-sum edge (tests/potential_np.py::draw_gap; at
+# N = 1024 and T = 40 some forty thousand draws meet a thousand edges, so a first seed fails about every other time).  The advances are recorded here, not searched
+# again: a cell has the one seed, and tests/test_lingauss_potential.py checks that it still holds.
 SEED_BUMPS = {("independent", False, False, "r1"): 12, ("independent", False, True, "r1"): 6, ("independent", True, False, "r1"): 6,
               ("independent", True, True, "r1"): 11, ("independent", "exact", True, "r1"): 13, ("guided", False, False, "r1"): 2,
               ("guided", False, True, "r1"): 16, ("guided", True, True, "r1"): 21}
 
 
-def literal_seed(style, gradient, backward, name):
-    """the seed of one (cell, case) of the literal comparison (tests/test_lingauss_potential.py checks that no draw of it lies on a cumulative-sum edge)"""
-    si = dict(independent=0, guided=1, bootstrap=2)[style]
-    gi = {False: 0, True: 1, "exact": 2}[gradient]
-    return 9000 + 1000 * si + 100 * gi + 50 * int(backward) + list(LITERAL_CASES).index(name) + 7919 * SEED_BUMPS.get((style, gradient, backward, name), 0)
+def _seeds(style, gradient, backward, name):
+    return [9000 + P.seed_index(style, gradient, backward) + list(LITERAL_CASES).index(name) + 7919 * SEED_BUMPS.get((style, gradient, backward, name), 0)]
 
 
-def literal_case(name, seed):
-    """(d, N, T, device objects, Model, reference trajectory, delta, noise) of one literal case: NaN rows at t = 0, mid-series and T - 1"""
+def _literal_model(name, rng):
+    """NaN rows at t = 0, mid-series and T - 1"""
     d, dy, N, T = LITERAL_CASES[name]
-    rng = np.random.default_rng(seed)
-    dev, m, xtrue, delta = case(d, dy, T, rng, nan_rows=(0, T // 2, T - 1))
-    x0 = xtrue + 0.3 * rng.standard_normal((T, d))
-    nz = dict(eps_aux=rng.standard_normal((T, d)), eps_prop=rng.standard_normal((T, N, d)), u_res=rng.random((T - 1, N)), u_bwd=rng.random(T))
-    return d, N, T, dev, m, x0, delta, nz
+    return (d, N, T) + case(d, dy, T, rng, nan_rows=(0, T // 2, T - 1))
 
 
-@functools.lru_cache(maxsize=None)
-def literal_sweep(style, gradient, backward, name):
-    """the literal sampler's sweep of one (cell, case): ((x, ancestors, history), the case); computed once per process and shared, never modified by a test"""
-    cs = literal_case(name, literal_seed(style, gradient, backward, name))
-    d, N, T, dev, m, x0, delta, nz = cs
-    nz = dict(nz)
-    if style == "bootstrap":
-        nz.pop("eps_aux")
-        return bootstrap_kernel(m, N, backward)[1](L.Noise(**nz), x0), cs
-    if style == "guided":
-        return guided_kernel(m, N, backward, gradient)[1](L.Noise(**nz), x0, delta), cs
-    return independent_kernel(m, N, backward, gradient)[1](L.Noise(**nz), x0, delta), cs
+# ---- parallel in time ----------------------------------------------------------------------------------------------------------------------------------------
+PIT_CELLS = ((1, 1, 32, 25), (3, 2, 100, 33), (3, 1, 32, 33), (1, 1, 100, 25), (3, 2, 32, 25))  # (d, dy, N, T)
 
 
-def wellposedness(style, gradient, backward, name):
-    """of the literal sweep of one (cell, case): the smallest distance of a resampling or backward draw r = c[-1] (1 - u) from a cumulative-weight edge c[j]
-    (weights normalised to sum 1) -- tests/user_models.py::wellposedness's gap -- and the share of time steps whose new ancestor is not the reference particle"""
-    (x, B, h), (d, N, T, dev, m, x0, delta, nz) = literal_sweep(style, gradient, backward, name)
-
-    def gap(w, u):
-        c = np.cumsum(w)
-        r = c[-1] * (1 - np.atleast_1d(u))
-        return float(np.min(np.abs(r[:, None] - c[None, :])))
-    gaps = [gap(L.normalize(h["log_ws"][t]), nz["u_res"][t][1:]) for t in range(T - 1)]
-    gaps.append(gap(h["w_T"], nz["u_bwd"][T - 1]))
-    if backward:
-        for t in range(T - 2, -1, -1):
-            lw = m.dyn.logpdf(x[t + 1], h["xs"][t], L._tree_index(m.dyn.params, t)) + h["log_ws"][t]
-            gaps.append(gap(L.normalize(lw), nz["u_bwd"][t]))
-    return dict(gap=min(gaps), moved=float(np.mean(B != 0)))
+def _pit_model(cell, rng):
+    """flat steps at t = 0, on the top-level stitch boundary and at the last step"""
+    d, dy, N, T = cell
+    return (d, N, T) + case(d, dy, T, rng, nan_rows=(0, PC.top_boundary(T), T - 1))
 
 
-def literal_cells():
-    """every (style, gradient, backward, case name) of the fp64 literal comparison"""
-    out = [(s, g, bw, n) for s, g, bw in LITERAL_CELLS for n in REGISTER + WIDE]
-    return out + [("bootstrap", False, bw, n) for bw in (False, True) for n in BOOTSTRAP_CASES]
+KIND = P.Kind("lingauss", 5, log_g, grad_log_g,
+              cells=lambda style, gradient, backward: BOOTSTRAP_CASES if style == "bootstrap" else REGISTER + WIDE,
+              literal_model=_literal_model, seeds=_seeds, label=lambda name: "{} (d={} dy={} N={} T={})".format(name, *LITERAL_CASES[name]),
+              pit_cells=PIT_CELLS, pit_model=_pit_model, pit_seeds=lambda cell, gradient: [[11, *cell, int(gradient)]], program=program)

@@ -293,8 +293,8 @@ class MvtCase(_Sides):
         return self.m.literal()
 
     def joint_grad(self, u):
-        from tests import mvt_np as MV
-        return MV.joint_grad(self.m, u)
+        from tests import potential_np
+        return potential_np.joint_grad(self.m, u)
 
     def device_objects(self):
         return self.dev

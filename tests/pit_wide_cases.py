@@ -46,7 +46,7 @@ class CoupledCase(PC._Sides):
     observation potential (dy = ceil(d / 3)), with a flat step -- the whole observation row NaN -- at t = 0, on the stitch boundary of the top level and at T - 1"""
 
     def __init__(self, cell):
-        from tests import mvt_np as MV, lingauss_np as LG
+        from tests import mvt_np as MV, lingauss_np as LG, potential_np
         from aux_ssm_samplers_amd import workloads
         kind, d, N, T, gradient, seed = cell
         self.cell, self.kind, self.d, self.N, self.T, self.gradient = cell, kind, d, N, T, bool(gradient)
@@ -59,14 +59,13 @@ class CoupledCase(PC._Sides):
             y = m.y.copy()
             y[self.flat_rows] = np.nan
             self.dev = (dev[0], MultivariateTPotential(nu=m.nu, prec=m.prec, y=y[0]), dev[2], MultivariateTPotential(nu=m.nu, prec=m.prec, params=y[1:]))
-            self.m = MV.Model(m.m0, m.P0, m.dyn, m.Q, m.nu, m.prec, y)
-            self._grad = MV.joint_grad
+            self.m = MV.model(m.m0, m.P0, m.dyn, m.Q, m.nu, m.prec, y)
         else:
             _, m, xtrue, self.delta = LG.case(d, (d + 2) // 3, T, rng)
             y = m.y.copy()
             y[self.flat_rows] = np.nan
             self.dev, self.m = LG.build(m.m0, m.P0, m.F, m.b, m.Q, m.H, m.R, m.c, y)
-            self._grad = LG.joint_grad
+        self._grad = potential_np.joint_grad
         self.x0 = xtrue + 0.3 * rng.standard_normal((T, d))
         self.noise = dict(eps_aux=rng.standard_normal((T, d)), eps_prop=rng.standard_normal((T, N, d)), u_res=rng.random((T, N)))
 

@@ -15,8 +15,6 @@ in fp32 (sixteen waves) or is fp64; here C_hi = CUs + 3 chains in fp32, the CU c
 4. in-kernel draws (keyed == explicit, and the first chains of a C_hi-chain keyed sweep == a keyed sweep of those chains alone) and chain batching with offsets
    beyond the CU count."""
 import functools
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -25,59 +23,13 @@ from oracle import csmc as O
 from tests import guided_np as G
 from tests import lingauss_np as LG
 from tests import mvt_np as MV
+from tests import potential_gpu as GP
 from tests.test_csmc_gradient_timevarying import _tv_model
 from tests.test_gpu_csmc import _masked_obs, _models, _pot
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("xs", "log_ws", "As", "ancestors", "x")
-
-
-@functools.lru_cache(maxsize=None)
-def _cu():
-    """the CU count of the default handle's device: hipDeviceProp_t::multiProcessorCount, what the library's kernel selection compares the chain count with, read
-    as torch.cuda.get_device_properties(device).multi_processor_count -- once, in a child process: torch ships a HIP runtime of its own, and loaded into this
-    process it would stand beside the one the library is linked to (tests/test_gpu_device_delta.py resolves its ctypes calls by the runtime's name)"""
-    from aux_ssm_samplers_amd import _lib
-    code = f"import torch; print(torch.cuda.get_device_properties({_lib.default_handle().device}).multi_processor_count)"
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    cu = int(out.stdout.split()[-1])
-    assert cu > 0
-    return cu
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(seed, Cn, T, N, d):
-    """x0 and explicit noise of Cn chains in fp32, every chain its own; chain c's arrays depend on (seed, c) alone (shared between tests: never modified)"""
-    per = []
-    for c in range(Cn):
-        rng = np.random.default_rng([seed, c])
-        per.append(dict(x0=rng.standard_normal((T, d)), eps_aux=rng.standard_normal((T, d)), eps_prop=rng.standard_normal((T, N, d)),
-                        u_res=rng.random((T - 1, N)), u_bwd=rng.random(T)))
-    out = {k: np.stack([p[k] for p in per]).astype(np.float32) for k in per[0]}
-    for v in out.values():
-        v.setflags(write=False)
-    return out
-
-
-def _assert_same(got, want, what):
-    """bit-identical arrays with a leading chain axis; a mismatch names the first differing (chain, step[, particle[, component]])"""
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    if got.tobytes() == want.tobytes():
-        return
-    bad = np.argwhere(~((got == want) | ((got != got) & (want != want))))
-    if len(bad) == 0:  # (only the sign of a zero differs)
-        bad = np.argwhere(np.signbit(got) != np.signbit(want))
-    i = tuple(int(v) for v in bad[0])
-    raise AssertionError(f"{what}: {len(bad)} of {got.size} entries differ, the first at (chain, step, ...) = {i}: {got[i]!r} against {want[i]!r}")
-
-
-def _sweep(fk, x0, N, backward, noise, delta, **kw):
-    """_device.sweep with its history, as one dict of the five compared fields"""
-    from aux_ssm_samplers_amd.csmc import _device
-    x, anc, hist = _device.sweep(fk, x0, N, backward, noise=noise, delta=delta, want_history=True, **kw)
-    return dict(xs=hist["xs"], log_ws=hist["log_ws"], As=hist["As"], ancestors=anc, x=x)
+FIELDS, _cu, _inputs, _assert_same, _sweep = GP.FIELDS, GP.cu_count, GP.chain_inputs, GP.assert_same, GP.sweep_fields
 
 
 # ---- 1. against the contract oracle ------------------------------------------------------------------------------------------------------------------------
@@ -181,18 +133,6 @@ def test_more_chains_than_cus_fp32_bit_exact_vs_oracle(cell):
 SPLIT_STYLES = [("bootstrap", False, False), ("independent", False, True), ("independent", False, False), ("independent", "exact", True), ("guided", True, True)]
 
 
-def _describe(style, dev, gradient=False):
-    from aux_ssm_samplers_amd import _lib
-    from aux_ssm_samplers_amd.csmc import _device
-    M0, G0, Mt, Gt = dev
-    gmode = _lib.GRAD_NONE if not gradient else (_lib.GRAD_EXACT if gradient == "exact" else _lib.GRAD_REFERENCE)
-    if style == "bootstrap":
-        return _device.describe_bootstrap(M0, G0, Mt, Gt, Mt)
-    if style == "guided":
-        return _device.describe_guided(M0, G0, Mt, Gt, Mt, gmode)
-    return _device.describe_independent(M0, G0, Mt, Gt, Mt, gmode)
-
-
 @functools.lru_cache(maxsize=None)
 def _coupled_case(kind, d, dy, T):
     rng = np.random.default_rng([3, d, T])
@@ -208,23 +148,9 @@ def _coupled_case(kind, d, dy, T):
 
 def _one_launch_equals_split_launches(kind, d, dy, N, T, style, gradient, backward):
     """-> the number of trajectory entries that moved"""
-    cu = _cu()
-    Cn = cu + 3
     dev, xtrue, delta = _coupled_case(kind, d, dy, T)
-    nz = dict(_inputs(300 + d, Cn, T, N, d))
-    x0 = (xtrue[None] + np.float32(0.3) * nz.pop("x0")).astype(np.float32)
-    if style == "bootstrap":
-        nz.pop("eps_aux")
-        delta = None
-    fk = _describe(style, dev, gradient)
-    one = _sweep(fk, x0, N, backward, nz, delta)
-    parts = [_sweep(fk, x0[a:b], N, backward, {k: v[a:b] for k, v in nz.items()}, delta) for a, b in ((0, cu), (cu, Cn))]
     what = f"{kind} d={d} N={N} T={T} {style} gradient={gradient} backward={backward}"
-    for name in FIELDS:
-        _assert_same(one[name], np.concatenate([p[name] for p in parts]), f"{what} {name}, one launch of {Cn} chains against launches of {cu} and 3")
-    assert one["xs"].dtype == np.float32 and np.all(np.isfinite(one["log_ws"]))
-    assert np.all(one["As"][:, :, 0] == 0) and np.array_equal(one["xs"][:, :, 0], x0)
-    return int((one["ancestors"] != 0).sum())
+    return GP.one_launch_equals_sixteen_wave(GP.describe(style, dev, gradient), style, xtrue, delta, N, backward, what)
 
 
 @pytest.mark.parametrize("style,gradient,backward", SPLIT_STYLES)

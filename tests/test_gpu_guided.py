@@ -14,6 +14,7 @@ import pytest
 
 from oracle import csmc_np as L
 from tests import guided_np as G
+from tests import potential_gpu as GP
 
 pytestmark = pytest.mark.gpu
 
@@ -136,25 +137,6 @@ def test_resident_chains_equal_host_sweeps_and_rebuild_their_tables(d, N):
     assert not np.array_equal(chains.to_host(), same.x)
 
 
-def _tie_rate(hist, u_res):
-    """device fp32 ancestors vs the literal fp32 resampling redone from the DEVICE's stored log-weights and the same uniforms, step by step (teacher-forced);
-    -> (misses, draws, misses farther than one visible particle): the construction of tests/test_gpu_csmc_literal.py"""
-    bad = far = tot = 0
-    for c in range(hist["As"].shape[0]):
-        T, N = hist["log_ws"][c].shape
-        for t in range(1, T):
-            w = L.normalize(hist["log_ws"][c, t - 1])
-            assert w.dtype == np.float32
-            A = L.multinomial(u_res[c, t - 1], w)
-            miss = np.nonzero(A != hist["As"][c, t - 1])[0]
-            bad, tot = bad + len(miss), tot + N - 1
-            for i in miss:
-                a, b = sorted((int(A[i]), int(hist["As"][c, t - 1][i])))
-                if b - a > 1 and float(np.sum(w[a + 1:b], dtype=np.float64)) > 8 * np.finfo(np.float32).eps:
-                    far += 1
-    return bad, tot, far
-
-
 @pytest.mark.parametrize("d,N,T,Cn", [(1, 1024, 1600, 1), (30, 25, 250, 4)])
 def test_fp32_ancestors_against_the_literal_order_tie_rate(d, N, T, Cn):
     """the rule of tests/test_gpu_csmc_literal.py (cumsum rounding only, whatever the proposal): rate <= 2e-4 per draw, no miss farther than one visible particle;
@@ -167,7 +149,7 @@ def test_fp32_ancestors_against_the_literal_order_tie_rate(d, N, T, Cn):
     nz = {k: v.astype(np.float32) for k, v in nz.items()}
     _, _, hist = _device.sweep(_fk(dev), x0, N, False, noise=nz, delta=0.5, want_history=True)
     assert hist["log_ws"].dtype == np.float32
-    bad, tot, far = _tie_rate(hist, nz["u_res"])
+    bad, tot, far = GP.tie_rate(hist, nz["u_res"])
     print(f"d={d} N={N}: {bad} of {tot} fp32 draws differ from the literal order ({bad / tot:.2e}), {far} farther than one visible particle")
     assert bad / tot <= 2e-4, (bad, tot)
     assert far == 0

@@ -465,13 +465,13 @@ def _pg_model(family):
 def _pg_particle_gibbs(family):
     """posterior means and their standard errors (T, d) from sequential particle Gibbs (auxiliary cSMC, independent proposals, backward sampling) on the user program"""
     from aux_ssm_samplers_amd.csmc import DevicePotential, GaussianInit, LinearGaussianDynamics, get_independent_kernel
-    from tests.test_gpu_mvt import _gibbs_moments
+    from tests.potential_gpu import gibbs_moments
     y, par, size, (m0, P0, F, Q, b), delta = _pg_model(family)
     rows = np.concatenate([y, np.nan_to_num(size)], axis=1)
     M0, Mt = GaussianInit(m0=m0, P0=P0), LinearGaussianDynamics(F=F, b=b, Q=Q)
     G0, Gt = DevicePotential(LOGISTIC_PROGRAM, y=rows[0], p=2 * PG_D), DevicePotential(LOGISTIC_PROGRAM, params=rows[1:], p=2 * PG_D)
     kernel = get_independent_kernel(M0, G0, Mt, Gt, 32, backward=True, Pt=Mt)[1]
-    m1, se1, _, _ = _gibbs_moments(kernel, PG_T, PG_D, delta, 7000, Cn=PG_C, burn=200, iters=240)
+    m1, se1, _, _ = gibbs_moments(kernel, PG_T, PG_D, delta, 7000, Cn=PG_C, burn=200, iters=240)
     return m1, se1
 
 

@@ -9,37 +9,18 @@ guided proposals, resident chains.
 4. The parallel-in-time sweep and resident chains.
 5. Ground truth by quadrature, no restatement in the loop: a scalar model with T = 3 for every sampler style, and a two-dimensional model with a
    non-diagonal precision matrix, which pins the coupling of the components itself.
-6. The C entry point's refusals."""
-import ctypes as C
+6. The C entry point's refusals.
 
+The shared assertion blocks are those of tests/potential_gpu.py, run with this kind's record."""
 import numpy as np
 import numpy.testing as npt
 import pytest
 
-from oracle import csmc_np as L
 from tests import mvt_np as MV
+from tests import potential_gpu as GP
 
 pytestmark = pytest.mark.gpu
-
-
-def _gmode(gradient):
-    from aux_ssm_samplers_amd import _lib
-    return _lib.GRAD_NONE if not gradient else (_lib.GRAD_EXACT if gradient == "exact" else _lib.GRAD_REFERENCE)
-
-
-def _describe(style, dev, gradient=False):
-    from aux_ssm_samplers_amd.csmc import _device
-    M0, G0, Mt, Gt = dev
-    if style == "bootstrap":
-        return _device.describe_bootstrap(M0, G0, Mt, Gt, Mt)
-    if style == "guided":
-        return _device.describe_guided(M0, G0, Mt, Gt, Mt, _gmode(gradient))
-    return _device.describe_independent(M0, G0, Mt, Gt, Mt, _gmode(gradient))
-
-
-def _noise(Cn, T, N, d, rng, dtype=np.float64):
-    nz = dict(eps_aux=rng.standard_normal((Cn, T, d)), eps_prop=rng.standard_normal((Cn, T, N, d)), u_res=rng.random((Cn, T - 1, N)), u_bwd=rng.random((Cn, T)))
-    return {k: v.astype(dtype) for k, v in nz.items()}
+KIND = MV.KIND
 
 
 # ---- 1. the built-in against the program ----------------------------------------------------------------------------------------------------------------
@@ -48,104 +29,25 @@ def _noise(Cn, T, N, d, rng, dtype=np.float64):
 def test_builtin_potential_equals_the_user_program_bit_for_bit(dtype, d, N, T, Cn):
     """bootstrap and independent proposals, gradient False / True / "exact", both backward modes, explicit and Threefry noise; two observation rows carry a NaN"""
     from aux_ssm_samplers_amd import random as R
-    from aux_ssm_samplers_amd.csmc import _device
     rng = np.random.default_rng(100 * d + N)
     dev, m, xtrue, delta = MV.case(d, T, rng, nan_rows=(3, T - 2))
     x0 = (xtrue[None] + 0.3 * rng.standard_normal((Cn, T, d))).astype(dtype)
-    nz = _noise(Cn, T, N, d, rng, dtype)
-    for style, gradient in (("bootstrap", False), ("independent", False), ("independent", True), ("independent", "exact")):
-        fb, fu = _describe(style, dev, gradient), _describe(style, MV.program(dev, bool(gradient)), gradient)
-        assert fb.potential == 4 and fb.user is None and fu.user is not None
-        for backward in (False, True):
-            for keyed in (False, True):
-                kw = dict(key=R.PRNGKey(31 + d)) if keyed else dict(noise=nz)
-                xb, ab, hb = _device.sweep(fb, x0, N, backward, delta=delta, want_history=True, **kw)
-                xu, au, hu = _device.sweep(fu, x0, N, backward, delta=delta, want_history=True, **kw)
-                npt.assert_array_equal(ab, au)
-                npt.assert_array_equal(xb, xu)
-                for name in ("xs", "log_ws", "As"):
-                    npt.assert_array_equal(hb[name], hu[name])
-                assert xb.dtype == dtype and np.all(np.isfinite(hb["log_ws"])) and (ab != 0).any(), (style, gradient, backward, keyed)
+    seen = GP.assert_program_equality(KIND, dev, x0, N, delta, GP.noise(Cn, T, N, d, rng, dtype), R.PRNGKey(31 + d))
+    assert all((s[4] != 0).any() for s in seen)
 
 
-# ---- 2. literal parity -----------------------------------------------------------------------------------------------------------------------------------
-def _literal_case(name, rng):
-    """(d, N, T) and the model: register path (1, 1024, 40), (3, 100, 33); wide path (5, 33, 20), the 3 x 3 and 5 x 5 grids of the spatial example
-    (random walk, its precision matrix; nu = 1 on the 5 x 5 grid, the example's own value) and (32, 64, 12); time-varying transitions on the register path at
-    N = 65, 512 and 1024 (a partial last wave, eight and sixteen full waves: this potential runs the generic workgroup at every N), three steps"""
-    from aux_ssm_samplers_amd.workloads import spatial_precision
-    d, N, T = dict(r1=(1, 1024, 40), r3=(3, 100, 33), w5=(5, 33, 20), grid3=(9, 25, 20), grid5=(25, 25, 25), w32=(32, 64, 12),
-                   tv65=(1, 65, 3), tv512=(1, 512, 3), tv1024=(1, 1024, 3))[name]
-    if name.startswith("tv"):
-        dev, m, xtrue, delta = MV.case(d, T, rng, tv=True)
-    elif name.startswith("grid"):
-        dev, m, xtrue, delta = MV.case(d, T, rng, nu=1.0 if name == "grid5" else 3.0, prec=spatial_precision(int(name[-1])), walk=True, nan_rows=(4,))
-    else:
-        dev, m, xtrue, delta = MV.case(d, T, rng, nan_rows=(2, T - 1))
-    return d, N, T, dev, m, xtrue + 0.3 * rng.standard_normal((T, d)), delta
-
-
-def _against_literal(style, gradient, backward, name, seed):
-    """one fp64 sweep on explicit noise next to the literal sampler; returns (ancestors, max particle error, max log-weight error)"""
-    from aux_ssm_samplers_amd.csmc import _device
-    rng = np.random.default_rng(seed)
-    d, N, T, dev, m, x0, delta = _literal_case(name, rng)
-    nz = {k: v[0] for k, v in _noise(1, T, N, d, rng).items()}
-    if style == "bootstrap":
-        nz.pop("eps_aux")
-    x, anc, hist = _device.sweep(_describe(style, dev, gradient), x0, N, backward, noise={k: v[None] for k, v in nz.items()},
-                                 delta=None if style == "bootstrap" else delta, want_history=True)
-    if style == "bootstrap":
-        xl, Bl, lh = MV.bootstrap_kernel(m, N, backward)[1](L.Noise(**nz), x0)
-    elif style == "guided":
-        xl, Bl, lh = MV.guided_kernel(m, N, backward, gradient)[1](L.Noise(**nz), x0, delta)
-    else:
-        xl, Bl, lh = MV.independent_kernel(m, N, backward, gradient)[1](L.Noise(**nz), x0, delta)
-    ex, el = float(np.max(np.abs(hist["xs"] - lh["xs"]))), float(np.max(np.abs(hist["log_ws"] - lh["log_ws"])))
-    print(f"{style} gradient={gradient} backward={backward} {name} (d={d} N={N} T={T}): max |xs - literal| = {ex:.1e}, max |log_ws - literal| = {el:.1e}, "
-          f"updated {int((anc != 0).sum())} of {T}")
-    npt.assert_array_equal(hist["As"], lh["As"])
-    npt.assert_array_equal(anc, Bl)
-    npt.assert_allclose(x, xl, rtol=1e-12, atol=1e-12)
-    npt.assert_allclose(hist["xs"], lh["xs"], rtol=1e-12, atol=1e-12)
-    lw_lit = lh["log_ws"]
-    if style == "independent" and gradient is True:
-        # the reference's weighting: GradientAuxiliaryGt adds its correction summed over ALL particles (csmc/independent.py:265-266), one constant per step that
-        # cancels in every normalisation and that the device does not add (include/auxssm.h, AUXSSM_GRAD_REFERENCE): compared up to that constant, read off particle 0
-        lw_lit = lw_lit - (lw_lit[:, :1] - hist["log_ws"][:, :1])
-        el = float(np.max(np.abs(hist["log_ws"] - lw_lit)))
-        print(f"    up to the reference's per-step constant: max |log_ws - literal| = {el:.1e}")
-    npt.assert_allclose(hist["log_ws"], lw_lit, rtol=1e-10, atol=1e-10)
-    assert np.all(hist["As"][:, 0] == 0) and np.array_equal(hist["xs"][:, 0], x0)  # row 0 of every step is the reference trajectory
-    if style == "independent" and not gradient:
-        # the direct identity: the stored log-weights are log g_t + log initial / log transition themselves (the kernels store them before any shift: shift 0)
-        for t in range(T):
-            g = MV.log_g(hist["xs"][t], m.y[t], m.nu, m.prec)
-            if t == 0:
-                dens = L._mvn_chol_logpdf(hist["xs"][0], m.m0, m.LP0)
-            else:
-                F, b, _, LQ = m.trans(t)
-                dens = L._mvn_chol_logpdf(hist["xs"][t], hist["xs"][t - 1][hist["As"][t - 1]] @ F.T + b, LQ)
-            npt.assert_allclose(hist["log_ws"][t], g + dens, rtol=1e-10, atol=1e-10)
-    return anc, ex, el
-
-
+# ---- 2. literal parity (the cases: tests/mvt_np.py::LITERAL_CASES) -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("backward", [False, True])
 @pytest.mark.parametrize("style,gradient", [("independent", False), ("independent", True), ("independent", "exact"), ("guided", False), ("guided", True)])
 def test_sweep_fp64_equals_the_literal_sampler(style, gradient, backward):
     """register and wide path; a single case may update nothing, over the set every (style, gradient, backward) cell moves the trajectory somewhere"""
-    moved = 0
-    names = ("r1", "r3", "w5", "grid3", "grid5", "w32") + (() if style == "guided" else ("tv65", "tv512", "tv1024"))  # (guided: time-invariant transitions only)
-    for i, name in enumerate(names):
-        moved += int((_against_literal(style, gradient, backward, name, 7000 + 10 * i + backward)[0] != 0).sum())
-    assert moved > 0
+    GP.literal_cell_moves(KIND, style, gradient, backward)
 
 
 @pytest.mark.parametrize("backward", [False, True])
-@pytest.mark.parametrize("name", ["r3", "grid3"])
+@pytest.mark.parametrize("name", MV.BOOTSTRAP_CASES)
 def test_bootstrap_sweep_fp64_equals_the_literal_sampler(name, backward):
-    anc, _, _ = _against_literal("bootstrap", False, backward, name, 7100 + backward)
-    assert (anc != 0).any()
+    assert (GP.against_literal(KIND, "bootstrap", False, backward, name) != 0).any()
 
 
 # ---- 3. fp32 on the wide path ------------------------------------------------------------------------------------------------------------------------------
@@ -155,20 +57,13 @@ def test_fp32_ancestors_against_the_literal_order_tie_rate(style, grid, N):
     """the spatial example on the 5 x 5 grid at its own N = 25, T = 250, 4 chains (the wide path, which no contract oracle covers in fp32), and on the 2 x 2 grid
     (the register path at dx = 4): the literal left-to-right draw on the device's own stored fp32 log-weights (tests/test_gpu_csmc_literal.py's rule):
     disagreeing draws <= 2e-4 of all draws, none farther than one visible particle"""
-    from aux_ssm_samplers_amd.csmc import _device
     from aux_ssm_samplers_amd.workloads import spatial_setup
-    from tests.test_gpu_guided import _tie_rate
     d, T, Cn = grid * grid, 250, 4
     rng = np.random.default_rng(77)
     M0, Mt, G0, Gt, xtrue, y, prec = spatial_setup(T, grid, seed=3)
     x0 = (xtrue[None] + 0.3 * rng.standard_normal((Cn, T, d))).astype(np.float32)
-    nz = _noise(Cn, T, N, d, rng, np.float32)
-    _, _, hist = _device.sweep(_describe(style, (M0, G0, Mt, Gt)), x0, N, False, noise=nz, delta=0.1, want_history=True)
-    assert hist["log_ws"].dtype == np.float32 and np.all(np.isfinite(hist["log_ws"]))
-    bad, tot, far = _tie_rate(hist, nz["u_res"])
-    print(f"{style} d={d} N={N}: {bad} of {tot} fp32 draws differ from the literal order ({bad / tot:.2e}), {far} farther than one visible particle")
-    assert bad / tot <= 2e-4, (bad, tot)
-    assert far == 0
+    nz = GP.noise(Cn, T, N, d, rng, np.float32)
+    GP.tie_rate_within_the_bar(GP.describe(style, (M0, G0, Mt, Gt)), x0, N, nz, 0.1, f"{style} d={d} N={N}")
 
 
 # ---- 4. parallel in time, resident chains ----------------------------------------------------------------------------------------------------------------
@@ -184,7 +79,7 @@ def test_parallel_in_time_sweep_runs_and_returns_consistent_paths(dtype, d, N, T
     rng = np.random.default_rng(10 * d + N)
     dev, m, xtrue, _ = MV.case(d, T, rng, nan_rows=(5,))
     Cn, delta = 3, 0.4
-    fk = _device.describe_independent(dev[0], dev[1], dev[2], dev[3], None, _gmode("exact" if gradient else False), parallel=True)
+    fk = _device.describe_independent(dev[0], dev[1], dev[2], dev[3], None, GP.gmode("exact" if gradient else False), parallel=True)
     x0 = (xtrue[None] + 0.3 * rng.standard_normal((Cn, T, d))).astype(dtype)
     h, key = _lib.default_handle(), R.PRNGKey(5 + d)
     noise = dict(eps_aux=h.rng_normal(key, 1, (Cn, T, d), dtype).to_host(), eps_prop=h.rng_normal(key, 2, (Cn, T, N, d), dtype).to_host(),
@@ -208,23 +103,9 @@ def test_parallel_in_time_sweep_runs_and_returns_consistent_paths(dtype, d, N, T
 @pytest.mark.parametrize("style", ["independent", "guided", "pit"])
 def test_resident_chains_equal_host_state_sweeps(style, dtype, d, N, T):
     """three sweeps on CsmcChains equal three host-state sweeps with the same keys, bit for bit"""
-    from aux_ssm_samplers_amd import _lib, random as R
-    from aux_ssm_samplers_amd.csmc import CsmcChains, CSMCState, get_guided_kernel, get_independent_kernel
     rng = np.random.default_rng(5 + d)
     dev, m, xtrue, delta = MV.case(d, T, rng, nan_rows=(1,))
-    Cn = 4
-    x0 = (xtrue[None] + 0.3 * rng.standard_normal((Cn, T, d))).astype(dtype)
-    if style == "guided":
-        init, kern = get_guided_kernel(*dev, N, backward=True, gradient=True)
-    else:
-        init, kern = get_independent_kernel(*dev, N, backward=True, gradient="exact", parallel=style == "pit")
-    chains = CsmcChains(_lib.default_handle(), x0, delta=delta, dtype=dtype)
-    rs, hs = CSMCState(x=chains, updated=None), init(x0)
-    for it in range(3):
-        rs, hs = kern(R.PRNGKey(40 + it), rs, None), kern(R.PRNGKey(40 + it), hs, delta)
-    assert hs.x.dtype == dtype and (hs.ancestors != 0).any()
-    npt.assert_array_equal(chains.to_host(), hs.x)
-    npt.assert_array_equal(chains.ancestors.to_host(), hs.ancestors)
+    GP.resident_equals_host(dev, (xtrue[None] + 0.3 * rng.standard_normal((4, T, d))).astype(dtype), delta, N, style)
 
 
 # ---- 5. ground truth by quadrature ---------------------------------------------------------------------------------------------------------------------
@@ -279,40 +160,11 @@ def _scalar_model():
     return (M0, MultivariateTPotential(nu=nu, prec=[[lam]], y=y[0]), Mt, MultivariateTPotential(nu=nu, prec=[[lam]], params=y[1:])), _truth["scalar"]
 
 
-def _gibbs_moments(kernel, T, d, delta, seed, Cn=1024, burn=60, iters=240, with_delta=True):
-    """per-chain time averages of x and of the products x_i x_j over `iters` sweeps of 1024 resident chains: (means, second moments) with their empirical
-    standard errors across the chains, which are independent"""
-    from aux_ssm_samplers_amd import _lib, random as R
-    from aux_ssm_samplers_amd.csmc import CsmcChains, CSMCState
-    chains = CsmcChains(_lib.default_handle(), np.zeros((Cn, T, d)), delta=delta if with_delta else None, dtype=np.float64)
-    state = CSMCState(x=chains, updated=None)
-    s1, s2 = np.zeros((Cn, T, d)), np.zeros((Cn, T, d, d))
-    for it in range(burn + iters):
-        state = kernel(R.PRNGKey(seed + it), state, None) if with_delta else kernel(R.PRNGKey(seed + it), state)
-        if it >= burn:
-            xh = chains.to_host()
-            s1 += xh
-            s2 += xh[..., :, None] * xh[..., None, :]
-    m1, m2 = s1 / iters, s2 / iters
-    return m1.mean(0), m1.std(0, ddof=1) / np.sqrt(Cn), m2.mean(0), m2.std(0, ddof=1) / np.sqrt(Cn)
-
-
 @pytest.mark.parametrize("sampler", ["independent-trace", "independent-backward", "exact", "guided", "guided-gradient", "bootstrap", "pit", "pit-gradient"])
 def test_particle_gibbs_matches_the_posterior_by_quadrature(sampler):
     """1024 resident chains: every posterior mean and second moment within 5 of its empirical standard errors"""
-    from aux_ssm_samplers_amd._primitives.csmc import get_kernel as get_bootstrap_kernel
-    from aux_ssm_samplers_amd.csmc import get_guided_kernel, get_independent_kernel
     dev, truth = _scalar_model()
-    N = 16
-    if sampler == "bootstrap":
-        kernel = get_bootstrap_kernel(*dev, N, backward=True, Pt=dev[2])[1]
-    elif sampler.startswith("guided"):
-        kernel = get_guided_kernel(*dev, N, backward=True, gradient=sampler.endswith("gradient"))[1]
-    elif sampler.startswith("pit"):
-        kernel = get_independent_kernel(*dev, N, gradient=sampler.endswith("gradient"), parallel=True)[1]
-    else:
-        kernel = get_independent_kernel(*dev, N, backward=sampler != "independent-trace", Pt=dev[2], gradient="exact" if sampler == "exact" else False)[1]
-    m1, se1, m2, se2 = _gibbs_moments(kernel, 3, 1, 1.0, 2000, with_delta=sampler != "bootstrap")
+    m1, se1, m2, se2 = GP.gibbs_moments(GP.kernel_of(sampler, dev, 16), 3, 1, 1.0, 2000, with_delta=sampler != "bootstrap")
     z1, z2 = np.abs(m1[:, 0] - truth[:, 0]) / se1[:, 0], np.abs(m2[:, 0, 0] - truth[:, 1]) / se2[:, 0, 0]
     print(f"{sampler}: means {m1[:, 0]} (truth {truth[:, 0]}), worst z {z1.max():.2f}; second moments {m2[:, 0, 0]} (truth {truth[:, 1]}), worst z {z2.max():.2f}")
     assert z1.max() < 5 and z2.max() < 5
@@ -347,7 +199,7 @@ def test_coupled_components_match_the_posterior_by_quadrature():
     M0, Mt = GaussianInit(m0=np.zeros(2), P0=np.eye(2)), LinearGaussianDynamics(F=np.eye(2), b=np.zeros(2), Q=np.eye(2))
     dev = (M0, MultivariateTPotential(nu=nu, prec=prec, y=y[0]), Mt, MultivariateTPotential(nu=nu, prec=prec, params=y[1:]))
     kernel = get_independent_kernel(*dev, 16, backward=True, Pt=Mt)[1]
-    m1, se1, m2, se2 = _gibbs_moments(kernel, 2, 2, 1.0, 3000)
+    m1, se1, m2, se2 = GP.gibbs_moments(kernel, 2, 2, 1.0, 3000)
     est = np.concatenate([m1, m2.reshape(2, 4)], axis=1)
     z = np.abs(est - truth) / np.concatenate([se1, se2.reshape(2, 4)], axis=1)
     print(f"estimates {est}\ntruth {truth}\nworst z {z.max():.2f}")
@@ -356,22 +208,14 @@ def test_coupled_components_match_the_posterior_by_quadrature():
 
 # ---- 6. the C entry point ----------------------------------------------------------------------------------------------------------------------------------
 def test_c_entry_point_refuses_a_missing_precision_matrix_and_a_bad_nu():
-    from aux_ssm_samplers_amd import _lib
-    from aux_ssm_samplers_amd.csmc import _device
-    h = _lib.default_handle()
-    T, N, d, dt = 6, 64, 2, np.float64
+    T, N, d = 6, 64, 2
     dev, m, xtrue, _ = MV.case(d, T, np.random.default_rng(0))
-    fk = _device.describe_independent(dev[0], dev[1], dev[2], dev[3], dev[2])
-    x, anc, shd = h.to_device(np.zeros((1, T, d)), dt), h.zeros((1, T), np.int32), h.to_device(np.full(T, 0.5), dt)
-    nz = _lib.CsmcNoise()
-    nz.mode, nz.key0, nz.key1 = _lib.NOISE_THREEFRY, 1, 2
-    tail = (1, T, N, 1, shd.ptr, x.ptr, C.byref(nz), anc.ptr, None, None, None)
+    ep = GP.EntryPoints(dev, T, N, d, x=0.0, sqrt_half_delta=0.5)
     for fields, msg in ((dict(prec=None), "prec"), (dict(nu=0.0), "nu > 0"), (dict(nu=-2.0), "nu > 0"), (dict(nu=float("nan")), "nu > 0")):
-        ms = fk.struct(h, dt, T)
+        ms = ep.struct()
         for name, value in fields.items():
             setattr(ms, name, value)
-        assert h.lib.auxssm_csmc_sweep(h.h, _lib.dtype_code(dt), C.byref(ms), *tail) == _lib.ERR_ARG
-        assert msg in h.lib.auxssm_last_error().decode()
-        assert h.lib.auxssm_csmc_pit_sweep(h.h, _lib.dtype_code(dt), C.byref(ms), 1, T, N, shd.ptr, x.ptr, C.byref(nz), anc.ptr) == _lib.ERR_ARG
-    ms = fk.struct(h, dt, T)
-    assert h.lib.auxssm_csmc_sweep(h.h, _lib.dtype_code(dt), C.byref(ms), *tail) == 0  # and the untampered description runs
+        assert ep.sweep(ms) == ep.ERR_ARG
+        assert msg in ep.error()
+        assert ep.pit_sweep(ms) == ep.ERR_ARG
+    assert ep.sweep(ep.struct()) == 0  # and the untampered description runs

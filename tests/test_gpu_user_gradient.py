@@ -29,13 +29,9 @@ def _with_derivatives(m):
     return tuple(dataclasses.replace(o, source=_WITH_DERIVATIVES[o.source]) if hasattr(o, "source") else o for o in m)
 
 
-def _gmode(gradient):
-    return _lib.GRAD_EXACT if gradient == "exact" else _lib.GRAD_REFERENCE
-
-
 def _describe(m, gradient):
     from aux_ssm_samplers_amd.csmc import _device
-    return _device.describe_independent(m[0], m[1], m[2], m[3], m[2], _gmode(gradient))
+    return _device.describe_independent(m[0], m[1], m[2], m[3], m[2], _lib.GRAD_EXACT if gradient == "exact" else _lib.GRAD_REFERENCE)
 
 
 def _assert_same_sweeps(fb, fu, x0, N, delta, rng, C, T, d, dtype):

@@ -1,5 +1,5 @@
 """The linear-Gaussian observation potential of the cSMC family (AUXSSM_POT_LIN_GAUSS, csmc.LinearGaussianPotential) without a GPU: known answers, the whitening
-identity the device's residual form rests on, the closed-form gradient of the helper (tests/lingauss_np.py) against central differences, validation at
+identity the device's residual form rests on, the closed-form gradient of the helpers (tests/lingauss_np.py, tests/potential_np.py) against central differences, validation at
 construction, the model description, the compilation of the potential as a user program (hipRTC needs no device), and the well-posedness of the exact
 ancestor comparison tests/test_gpu_lingauss.py makes."""
 import numpy as np
@@ -8,6 +8,7 @@ import pytest
 
 from oracle import csmc_np as L
 from tests import lingauss_np as LG
+from tests import potential_np as P
 
 HALF_LOG_2PI = 0.5 * np.log(2.0 * np.pi)
 
@@ -76,8 +77,8 @@ def test_whitened_residual_form_equals_the_unwhitened_formula_on_every_gpu_case(
     """every particle of every case of tests/test_gpu_lingauss.py's lists (the literal sweeps' own particle systems; the program shapes' start trajectories and a
     cloud around them): within 1e-11 absolute, a decade inside the GPU file's 1e-10 on log-weights"""
     worst = 0.0
-    for cell in LG.literal_cells():
-        (x, B, h), (d, N, T, dev, m, x0, delta, nz) = LG.literal_sweep(*cell)
+    for cell in P.literal_cells(LG.KIND):
+        (x, B, h), (d, N, T, dev, m, x0, delta, nz), _, _ = P.literal_sweep(LG.KIND, *cell)
         worst = max(worst, _whitening_error(dev, m, h["xs"]))
     for d, dy, N, T, Cn in LG.PROGRAM_SHAPES:
         rng = np.random.default_rng(100 * d + N)
@@ -98,14 +99,14 @@ def test_closed_form_gradient_equals_central_differences():
 
 
 def test_joint_gradient_of_the_helper_equals_the_oracles_central_differences():
-    """tests/lingauss_np.py::joint_grad replaces the central differences of oracle.csmc_np.get_independent_kernel(gradient=True): the same quantity"""
+    """tests/potential_np.py::joint_grad replaces the central differences of oracle.csmc_np.get_independent_kernel(gradient=True): the same quantity"""
     rng = np.random.default_rng(4)
     for d, dy in ((2, 1), (3, 3)):
         dev, m, x, _ = LG.case(d, dy, 6, rng, nan_rows=(3,))
         u = x + 0.3 * rng.standard_normal(x.shape)
         M0, G0, Mt, Gt = m.literal()
         fd = L.grad_fd(lambda v: float(L._log_pdf(v, M0, G0, Mt, Gt)), u)
-        npt.assert_allclose(LG.joint_grad(m, u), fd, rtol=0, atol=1e-6)
+        npt.assert_allclose(P.joint_grad(m, u), fd, rtol=0, atol=1e-6)
 
 
 def test_exact_posterior_of_the_helper_on_a_model_solved_by_hand():
@@ -197,12 +198,13 @@ def test_the_potential_compiles_as_a_user_program(dtype, dx):
 
 
 # ---- 6. well-posedness of the exact ancestor comparison ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("cell", LG.literal_cells(), ids=lambda c: f"{c[0]}-g{c[1]}-bw{int(c[2])}-{c[3]}")
+@pytest.mark.parametrize("cell", P.literal_cells(LG.KIND), ids=lambda c: f"{c[0]}-g{c[1]}-bw{int(c[2])}-{c[3]}")
 def test_exact_ancestor_comparison_is_well_posed(cell):
     """tests/test_gpu_lingauss.py demands EQUAL ancestors of the device and the fp64 literal while their log-weights agree to 1e-10: fair only if no draw
     r = c[-1] (1 - u) lies within rounding of a cumulative-weight edge c[j].  From the literal sweep of every (cell, case): the smallest |r - c[j]| over all
     resampling and backward draws is >= 1e-8 (weights normalised to sum 1; the rule and number of tests/test_user_model_literals.py).  The seeds of
     tests/lingauss_np.py::SEED_BUMPS were advanced until it held with a factor 3 to spare: smallest gap over the list 3.0e-8 (N = 1024, T = 40)."""
-    w = LG.wellposedness(*cell)
-    print(cell, w)
-    assert w["gap"] >= 1e-8
+    (x, B, h), cs, _, _ = P.literal_sweep(LG.KIND, *cell)
+    gap = P.draw_gap((x, B, h), cs[7], cs[4].dyn, cell[2])
+    print(cell, dict(gap=gap, moved=float(np.mean(B != 0))))
+    assert gap >= 1e-8

@@ -1,5 +1,5 @@
 """The logistic potential of the cSMC family (AUXSSM_POT_LOGISTIC, csmc.BinomialPotential / NegBinomialPotential) without a GPU: known answers, the NaN rule per
-component, the closed-form gradient of the helper (tests/logistic_np.py) against central differences, the kernels' softplus formula against np.logaddexp, the bound
+component, the closed-form gradient of the helpers (tests/logistic_np.py, tests/potential_np.py) against central differences, the kernels' softplus formula against np.logaddexp, the bound
 of the forward pass's shift, validation at construction, the model description, the workload, the compilation of the potential as a user program (hipRTC needs
 no device), the quadrature helper on cases with known answers, and the well-posedness of the exact ancestor comparisons tests/test_gpu_logistic.py makes."""
 import numpy as np
@@ -9,6 +9,7 @@ import pytest
 from oracle import csmc_np as L
 from tests import pit_cases as PC
 from tests import logistic_np as LN
+from tests import potential_np as P
 
 
 def _sp(x):
@@ -52,8 +53,8 @@ def test_known_answers_by_hand_and_the_nan_rule_per_component():
     # the protocol object's two roles
     ys, ms = np.array([[1.0, 2.0], [3.0, np.nan]]), np.array([[1.0, 5.0], [4.0, 0.0]])
     xx = np.array([[0.1, 0.2]])
-    assert LN.LogisticPotential(ys[0], ms[0], first=True)(xx)[0] == LN.log_g(xx, ys[0], ms[0])[0]
-    assert LN.LogisticPotential(ys[1:], ms[1:])(xx, None, np.concatenate([ys[1], ms[1]]))[0] == LN.log_g(xx, ys[1], ms[1])[0]
+    assert LN.potential(ys[0], ms[0], first=True)(xx)[0] == LN.log_g(xx, ys[0], ms[0])[0]
+    assert LN.potential(ys[1:], ms[1:])(xx, None, np.concatenate([ys[1], ms[1]]))[0] == LN.log_g(xx, ys[1], ms[1])[0]
 
 
 # ---- 2. gradients ----------------------------------------------------------------------------------------------------------------------------------------
@@ -69,14 +70,14 @@ def test_closed_form_gradient_equals_central_differences():
 
 @pytest.mark.parametrize("family", LN.FAMILIES)
 def test_joint_gradient_of_the_helper_equals_the_oracles_central_differences(family):
-    """tests/logistic_np.py::joint_grad replaces the central differences of oracle.csmc_np.get_independent_kernel(gradient=True): the same quantity"""
+    """tests/potential_np.py::joint_grad replaces the central differences of oracle.csmc_np.get_independent_kernel(gradient=True): the same quantity"""
     rng = np.random.default_rng(4)
     for d in (1, 3):
         dev, m, x, _ = LN.case(d, 6, rng, family, nan_steps=(0, 3, 5))
         u = x + 0.3 * rng.standard_normal(x.shape)
         M0, G0, Mt, Gt = m.literal()
         fd = L.grad_fd(lambda v: float(L._log_pdf(v, M0, G0, Mt, Gt)), u)
-        npt.assert_allclose(LN.joint_grad(m, u), fd, rtol=0, atol=1e-5)
+        npt.assert_allclose(P.joint_grad(m, u), fd, rtol=0, atol=1e-5)
 
 
 # ---- 3. the formula --------------------------------------------------------------------------------------------------------------------------------------
@@ -230,7 +231,7 @@ def test_quadrature_on_cases_with_known_answers():
     """no observation at all: the posterior is the Gaussian prior's marginals, known in closed form.  One step, y observed: against a direct one-dimensional
     quadrature on another grid."""
     m0, P0, F, Q, b = 0.3, 0.5, 0.8, 0.3, 0.1
-    out = LN.posterior_by_quadrature([np.nan] * 4, [0.0] * 4, m0, P0, F, Q, b)
+    out = P.posterior_by_quadrature(LN.scalar_steps([np.nan] * 4, [0.0] * 4), m0, P0, F, Q, b)
     mu, var = m0, P0
     for t in range(4):
         if t:
@@ -240,23 +241,23 @@ def test_quadrature_on_cases_with_known_answers():
     w = np.exp(-0.5 * (g - m0) ** 2 / P0 + 3.0 * g - 5.0 * np.logaddexp(0.0, g))
     w /= w.sum()
     mean = float(w @ g)
-    one = LN.posterior_by_quadrature([3.0], [5.0], m0, P0, F, Q, b)
+    one = P.posterior_by_quadrature(LN.scalar_steps([3.0], [5.0]), m0, P0, F, Q, b)
     assert abs(one[0, 0] - mean) < 1e-9 and abs(one[0, 1] - float(w @ (g - mean) ** 2)) < 1e-9
     # and a later observation moves the earlier steps (the backward pass)
-    two = LN.posterior_by_quadrature([np.nan, 19.0], [0.0, 20.0], m0, P0, F, Q, b)
+    two = P.posterior_by_quadrature(LN.scalar_steps([np.nan, 19.0], [0.0, 20.0]), m0, P0, F, Q, b)
     assert two[0, 0] > m0 + 0.1 and two[1, 0] > F * m0 + b + 0.3
 
 
 # ---- 8. well-posedness of the exact ancestor comparisons ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("cell", LN.literal_cells(), ids=lambda c: f"{c[0]}-g{c[1]}-bw{int(c[2])}-d{c[3][0]}-N{c[3][1]}")
+@pytest.mark.parametrize("cell", P.literal_cells(LN.KIND), ids=lambda c: f"{c[0]}-g{c[1]}-bw{int(c[2])}-d{c[3][0]}-N{c[3][1]}")
 def test_exact_ancestor_comparison_is_well_posed(cell):
     """tests/test_gpu_logistic.py demands EQUAL ancestors of the device and the fp64 literal while their log-weights agree to 1e-10: fair only if no draw
     r = c[-1] (1 - u) lies within rounding of a cumulative-weight edge c[j].  From the literal sweep of every (cell, shape): the smallest |r - c[j]| over all
-    resampling and backward draws is >= 1e-8 (weights normalised to sum 1); tests/logistic_np.py::literal_sweep advances the seed until it holds, from the literal
+    resampling and backward draws is >= 1e-8 (weights normalised to sum 1); tests/potential_np.py::literal_sweep advances the seed until it holds, from the literal
     alone.  The data of every case hold a missing entry, a wholly missing row, y = 0 and a size of 1, and no size above 40."""
-    (x, B, h), cs, gap, bump = LN.literal_sweep(*cell)
+    (x, B, h), cs, gap, bump = P.literal_sweep(LN.KIND, *cell)
     print(cell, gap, bump)
-    assert gap >= LN.GAP_BAR and bump < LN.MAX_BUMPS
+    assert gap >= P.GAP_BAR and bump < P.MAX_BUMPS
     m = cs[4]
     T = cs[2]
     assert LN.has_every_feature(m)
@@ -269,15 +270,15 @@ def test_both_families_go_through_every_group_and_binomial_data_reach_y_equal_tr
     for group in (LN.REGISTER, LN.WIDE, LN.PIT_CELLS):
         assert {LN.family_of(s) for s in group} == set(LN.FAMILIES)
     for shape in LN.REGISTER + LN.WIDE:
-        m = LN.literal_sweep("independent", False, False, shape)[1][4]
+        m = P.literal_sweep(LN.KIND, "independent", False, False, shape)[1][4]
         if LN.family_of(shape) == "binomial":
             ok = np.isfinite(m.y)
             assert (m.y[ok] == m.size[ok]).any() and (m.size[ok] == 1).any()
 
 
-@pytest.mark.parametrize("style,gradient,backward", LN.LITERAL_CELLS)
+@pytest.mark.parametrize("style,gradient,backward", P.LITERAL_CELLS + P.BOOTSTRAP_CELLS)
 def test_every_literal_cell_moves_the_trajectory_somewhere(style, gradient, backward):
-    moved = sum(int((LN.literal_sweep(style, gradient, backward, shape)[0][1] != 0).sum()) for shape in LN.REGISTER + LN.WIDE)
+    moved = sum(int((P.literal_sweep(LN.KIND, style, gradient, backward, shape)[0][1] != 0).sum()) for shape in LN.REGISTER + LN.WIDE)
     print(style, gradient, backward, moved)
     assert moved > 0
 
@@ -286,7 +287,7 @@ def test_every_literal_cell_moves_the_trajectory_somewhere(style, gradient, back
 @pytest.mark.parametrize("d,N,T", LN.PIT_CELLS)
 def test_tree_comparison_is_well_posed(d, N, T, gradient):
     """the smallest draw margin of the literal tree is at least tests/pit_cases.py::margin_threshold(N), and the sweep moves the trajectory"""
-    c, (xl, origins, hist) = LN.pit_literal(d, N, T, gradient)
+    c, (xl, origins, hist) = P.pit_literal(LN.KIND, (d, N, T), gradient)
     print(d, N, T, gradient, hist["min_margin"], int((origins != 0).sum()))
     assert hist["min_margin"] >= PC.margin_threshold(N)
     assert (origins != 0).any()

@@ -7,6 +7,7 @@ import pytest
 
 from oracle import csmc_np as L
 from tests import mvt_np as MV
+from tests import potential_np as P
 
 
 def test_scalar_known_answer_and_nan_rule():
@@ -40,14 +41,14 @@ def test_closed_form_gradient_equals_central_differences():
 
 
 def test_joint_gradient_of_the_helper_equals_the_oracles_central_differences():
-    """tests/mvt_np.py::joint_grad replaces the central differences of oracle.csmc_np.get_independent_kernel(gradient=True): the same quantity"""
+    """tests/potential_np.py::joint_grad replaces the central differences of oracle.csmc_np.get_independent_kernel(gradient=True): the same quantity"""
     rng = np.random.default_rng(4)
     for tv in (False, True):  # (time-varying: every transition its own F_t, b_t, Q_t)
         dev, m, x, _ = MV.case(2, 6, rng, nan_rows=(3,), tv=tv)
         u = x + 0.3 * rng.standard_normal(x.shape)
         M0, G0, Mt, Gt = m.literal()
         fd = L.grad_fd(lambda v: float(L._log_pdf(v, M0, G0, Mt, Gt)), u)
-        npt.assert_allclose(MV.joint_grad(m, u), fd, rtol=0, atol=1e-6)
+        npt.assert_allclose(P.joint_grad(m, u), fd, rtol=0, atol=1e-6)
 
 
 def test_spatial_precision_of_the_two_by_two_grid():

@@ -159,10 +159,10 @@ def test_student_t_literal_reads_y_the_transition_and_the_whole_precision_matrix
             return np.zeros(np.shape(x_t_p_1)[:-1])
 
     npt.assert_array_equal(run(G0, Mt, Gt), origins)
-    assert np.any(run(G0, Mt, MV.MvtPotential(nu, prec, y[:-1])) != origins)
+    assert np.any(run(G0, Mt, MV.potential(nu, prec, y[:-1])) != origins)
     assert np.any(run(G0, NoTransition(c.m.F, c.m.b, c.m.LQ, c.T), Gt) != origins)
     diag = np.diag(np.diag(prec))
-    assert np.any(run(MV.MvtPotential(nu, diag, y[0], first=True), Mt, MV.MvtPotential(nu, diag, y[1:])) != origins)
+    assert np.any(run(MV.potential(nu, diag, y[0], first=True), Mt, MV.potential(nu, diag, y[1:])) != origins)
 
 
 # ---- init() ------------------------------------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """The Poisson count potential of the cSMC family (AUXSSM_POT_POISSON, csmc.PoissonPotential) without a GPU: known answers, the NaN rule per component, the
-closed-form gradient of the helper (tests/poisson_np.py) against central differences, the bound of the forward pass's shift, validation at construction, the model
+closed-form gradient of the helpers (tests/poisson_np.py, tests/potential_np.py) against central differences, the bound of the forward pass's shift, validation at construction, the model
 description, the compilation of the potential as a user program (hipRTC needs no device), the quadrature helper on a case solved by hand, and the well-posedness
 of the exact ancestor comparisons tests/test_gpu_poisson.py makes."""
 import numpy as np
@@ -9,6 +9,7 @@ import pytest
 from oracle import csmc_np as L
 from tests import pit_cases as PC
 from tests import poisson_np as PN
+from tests import potential_np as P
 
 
 # ---- 1. known answers ------------------------------------------------------------------------------------------------------------------------------------
@@ -39,8 +40,8 @@ def test_known_answers_by_hand_zero_counts_and_the_nan_rule_per_component():
     # the protocol object's two roles
     ys = np.array([[1.0, 2.0], [3.0, np.nan]])
     xx = np.array([[0.1, 0.2]])
-    assert PN.PoissonPotential(ys[0], first=True)(xx)[0] == PN.log_g(xx, ys[0])[0]
-    assert PN.PoissonPotential(ys[1:])(xx, None, ys[1])[0] == PN.log_g(xx, ys[1])[0]
+    assert PN.potential(ys[0], first=True)(xx)[0] == PN.log_g(xx, ys[0])[0]
+    assert PN.potential(ys[1:])(xx, None, ys[1])[0] == PN.log_g(xx, ys[1])[0]
 
 
 # ---- 2. gradients ----------------------------------------------------------------------------------------------------------------------------------------
@@ -54,14 +55,14 @@ def test_closed_form_gradient_equals_central_differences():
 
 
 def test_joint_gradient_of_the_helper_equals_the_oracles_central_differences():
-    """tests/poisson_np.py::joint_grad replaces the central differences of oracle.csmc_np.get_independent_kernel(gradient=True): the same quantity"""
+    """tests/potential_np.py::joint_grad replaces the central differences of oracle.csmc_np.get_independent_kernel(gradient=True): the same quantity"""
     rng = np.random.default_rng(4)
     for d in (1, 3):
         dev, m, x, _ = PN.case(d, 6, rng, nan_steps=(0, 3, 5))
         u = x + 0.3 * rng.standard_normal(x.shape)
         M0, G0, Mt, Gt = m.literal()
         fd = L.grad_fd(lambda v: float(L._log_pdf(v, M0, G0, Mt, Gt)), u)
-        npt.assert_allclose(PN.joint_grad(m, u), fd, rtol=0, atol=1e-5)
+        npt.assert_allclose(P.joint_grad(m, u), fd, rtol=0, atol=1e-5)
 
 
 # ---- 3. the bound ------------------------------------------------------------------------------------------------------------------------------------------
@@ -142,7 +143,7 @@ def test_quadrature_on_cases_with_known_answers():
     """no observation at all: the posterior is the Gaussian prior's marginals, known in closed form.  One step, y observed: against a direct one-dimensional
     quadrature on another grid."""
     m0, P0, F, Q, b = 0.7, 0.5, 0.8, 0.3, 0.1
-    out = PN.posterior_by_quadrature([np.nan] * 4, m0, P0, F, Q, b)
+    out = P.posterior_by_quadrature(PN.scalar_steps([np.nan] * 4), m0, P0, F, Q, b)
     mu, var = m0, P0
     for t in range(4):
         if t:
@@ -152,21 +153,21 @@ def test_quadrature_on_cases_with_known_answers():
     w = np.exp(-0.5 * (g - m0) ** 2 / P0 + 3.0 * g - np.exp(g))
     w /= w.sum()
     mean = float(w @ g)
-    one = PN.posterior_by_quadrature([3.0], m0, P0, F, Q, b)
+    one = P.posterior_by_quadrature(PN.scalar_steps([3.0]), m0, P0, F, Q, b)
     assert abs(one[0, 0] - mean) < 1e-9 and abs(one[0, 1] - float(w @ (g - mean) ** 2)) < 1e-9
     # and a later observation moves the earlier steps (the backward pass)
-    two = PN.posterior_by_quadrature([np.nan, 9.0], m0, P0, F, Q, b)
+    two = P.posterior_by_quadrature(PN.scalar_steps([np.nan, 9.0]), m0, P0, F, Q, b)
     assert two[0, 0] > m0 + 0.1 and two[1, 0] > F * m0 + b + 0.3
 
 
 # ---- 7. well-posedness of the exact ancestor comparisons ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("cell", PN.literal_cells(), ids=lambda c: f"{c[0]}-g{c[1]}-bw{int(c[2])}-d{c[3][0]}-N{c[3][1]}")
+@pytest.mark.parametrize("cell", P.literal_cells(PN.KIND), ids=lambda c: f"{c[0]}-g{c[1]}-bw{int(c[2])}-d{c[3][0]}-N{c[3][1]}")
 def test_exact_ancestor_comparison_is_well_posed(cell):
     """tests/test_gpu_poisson.py demands EQUAL ancestors of the device and the fp64 literal while their log-weights agree to 1e-10: fair only if no draw
     r = c[-1] (1 - u) lies within rounding of a cumulative-weight edge c[j].  From the literal sweep of every (cell, shape): the smallest |r - c[j]| over all
-    resampling and backward draws is >= 1e-8 (weights normalised to sum 1; the bar of tests/test_lingauss_potential.py); tests/poisson_np.py::literal_sweep
+    resampling and backward draws is >= 1e-8 (weights normalised to sum 1; the bar of tests/test_lingauss_potential.py); tests/potential_np.py::literal_sweep
     advances the seed until it holds, from the literal alone."""
-    (x, B, h), cs, gap, bump = PN.literal_sweep(*cell)
+    (x, B, h), cs, gap, bump = P.literal_sweep(PN.KIND, *cell)
     print(cell, gap, bump)
     assert gap >= 1e-8
     m = cs[4]
@@ -176,9 +177,9 @@ def test_exact_ancestor_comparison_is_well_posed(cell):
         assert np.isfinite(m.y[0, 1:]).all() and np.isfinite(m.y[T - 1, -1])  # rows that are partly NaN
 
 
-@pytest.mark.parametrize("style,gradient,backward", PN.LITERAL_CELLS)
+@pytest.mark.parametrize("style,gradient,backward", P.LITERAL_CELLS + P.BOOTSTRAP_CELLS)
 def test_every_literal_cell_moves_the_trajectory_somewhere(style, gradient, backward):
-    moved = sum(int((PN.literal_sweep(style, gradient, backward, shape)[0][1] != 0).sum()) for shape in PN.REGISTER + PN.WIDE)
+    moved = sum(int((P.literal_sweep(PN.KIND, style, gradient, backward, shape)[0][1] != 0).sum()) for shape in PN.REGISTER + PN.WIDE)
     print(style, gradient, backward, moved)
     assert moved > 0
 
@@ -187,7 +188,7 @@ def test_every_literal_cell_moves_the_trajectory_somewhere(style, gradient, back
 @pytest.mark.parametrize("d,N,T", PN.PIT_CELLS)
 def test_tree_comparison_is_well_posed(d, N, T, gradient):
     """the smallest draw margin of the literal tree is at least tests/pit_cases.py::margin_threshold(N), and the sweep moves the trajectory"""
-    c, (xl, origins, hist) = PN.pit_literal(d, N, T, gradient)
+    c, (xl, origins, hist) = P.pit_literal(PN.KIND, (d, N, T), gradient)
     print(d, N, T, gradient, hist["min_margin"], int((origins != 0).sum()))
     assert hist["min_margin"] >= PC.margin_threshold(N)
     assert (origins != 0).any()

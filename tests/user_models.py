@@ -22,6 +22,7 @@ import numpy as np
 
 from oracle import csmc_np as L
 from aux_ssm_samplers_amd.csmc import device_models as U
+from tests import potential_np
 from tests.test_gpu_user_model import _MeanDyn
 
 HALF_LOG_2PI = 0.91893853320467274178
@@ -590,7 +591,7 @@ def exact_bound(spec):
 
 def wellposedness(case):
     """of the literal sweep of a case: gap = the smallest distance of a resampling / backward draw r = c[-1] (1 - u) from a cumulative-weight boundary c[j] (weights
-    normalised to sum 1); ess = the smallest effective sample size over t; moved = the share of time steps whose new ancestor is not the reference particle;
+    normalised to sum 1: tests/potential_np.py::draw_gap); ess = the smallest effective sample size over t; moved = the share of time steps whose new ancestor is not the reference particle;
     underflow32 / underflow64 = the number of steps 1 <= t < T - 1 at which every weight shifted by the exact bound (+ the transition density's log-normaliser for the
     auxiliary proposals), exp(log_w - bound), is zero in that precision"""
     sp, T = case.spec, case.spec.T
@@ -598,22 +599,8 @@ def wellposedness(case):
     lit = literal(sp)
     _, _, nz = inputs(case)
 
-    def gap(w, u):
-        c = np.cumsum(w)
-        r = c[-1] * (1 - np.atleast_1d(u))
-        return float(np.min(np.abs(r[:, None] - c[None, :])))
-    gaps, ess = [], []
-    for t in range(T):
-        w = L.normalize(h["log_ws"][t])
-        ess.append(1 / np.sum(w * w))
-        if t < T - 1 and case.N > 1:
-            gaps.append(gap(w, nz["u_res"][t][1:]))
-    gaps.append(gap(h["w_T"], nz["u_bwd"][T - 1]))
-    if case.backward:
-        for t in range(T - 2, -1, -1):
-            lw = lit[2].logpdf(x[t + 1], h["xs"][t], L._tree_index(lit[2].params, t)) + h["log_ws"][t]
-            gaps.append(gap(L.normalize(lw), nz["u_bwd"][t]))
-    out = dict(gap=min(gaps), ess=float(min(ess)), moved=float(np.mean(B != 0)))
+    ess = [1 / np.sum(w * w) for w in map(L.normalize, h["log_ws"])]
+    out = dict(gap=potential_np.draw_gap((x, B, h), nz, lit[2], case.backward), ess=float(min(ess)), moved=float(np.mean(B != 0)))
     if T > 2:
         LQ = L._tree_index(lit[2].params, 0)[2] if isinstance(lit[2].params, tuple) else lit[2].L
         c_trans = -np.sum(np.log(np.diag(LQ))) - 0.5 * sp.dx * L.LOG_2PI if case.proposal == "independent" else 0.0
