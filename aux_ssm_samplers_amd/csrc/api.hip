@@ -745,9 +745,9 @@ template <typename R> static int sweep_lg_concat(const SweepCall& c) {
     ws.add(ell, C * sR);
     ws.add(sums, (size_t)5 * C * sizeof(Acc));  // the five totals
     if (wide_shared) ws.add(carrier, (size_t)T * P * sR);  // the observation-pattern carrier of the chain-shared wide filter
-    ws.after(wide ? wide_filter_ws(h, dtype, kd, parallel, D, P) : ke->filter_ws(h, kd, parallel));
-    ws.after(wide ? wide_sample_ws(h, dtype, kd, parallel, D) : se->sample_ws(h, kd, parallel));
-    ws.after(wide ? wide_logpdf_ws(dtype, kd) : sl->ws(h, kd));
+    ws.after(ke->filter_ws(h, kd, parallel, D, P));
+    ws.after(se->sample_ws(h, kd, parallel, D));
+    ws.after(sl->ws(h, kd, D, PO));
     int rc = ws.reserve(h);
     if (rc) return rc;
     const StageEnd done{h, h->ws_off};
@@ -1226,6 +1226,7 @@ template <typename R, typename Factory> static int sweep_ss(const SweepCall& c) 
     const bool wide = is_wide(D, D);
     const KalmanEntry* ke = need_kalman(dtype, D, D);
     const SampleEntry* se = wide ? wide_sample_entry(dtype) : sample_entry(dtype, D);
+    const SweepLogpdfEntry* wsl = wide ? wide_sweep_logpdf_entry(dtype) : nullptr;  // (wide states: both joints from the chains-as-columns form, below)
     if (!ke || !se) return AUXSSM_ERR_UNSUPPORTED;
     // layout 1 (register kernels only): state, noise and every internal per-chain buffer chain-minor, lanes <-> chains
     const int cm = c.cm();
@@ -1264,9 +1265,9 @@ template <typename R, typename Factory> static int sweep_ss(const SweepCall& c) 
         ws.add(wide_mask, (size_t)T * D * sR);
         ws.add(wide_gtab, wide_gain_tab_bytes(dtype, T, D, D));  // the gain rows: built by the proposal filter, reused by the reverse filter
     }
-    ws.after(wide ? wide_filter_ws(h, dtype, kd, parallel, D, D) : ke->filter_ws(h, kd, parallel));
-    ws.after(wide ? wide_sample_ws(h, dtype, kd, parallel, D) : se->sample_ws(h, kd, parallel));
-    ws.after(wide ? wide_logpdf_ws(dtype, kd) : Factory::one_pass ? std::max(ke->logpdf_ws(h, kd), se->sv_logpdf_ws(h, kd)) : ke->logpdf_ws(h, kd));
+    ws.after(ke->filter_ws(h, kd, parallel, D, D));
+    ws.after(se->sample_ws(h, kd, parallel, D));
+    ws.after(std::max(ke->logpdf_ws(h, kd, D, D), wsl ? wsl->ws(h, kd, D, D) : Factory::one_pass ? se->sv_logpdf_ws(h, kd, D) : (size_t)0));
     int rc = ws.reserve(h);
     if (rc) return rc;
     if (fly) ys1 = ys2 = u;  // (never read)
@@ -1387,7 +1388,6 @@ template <typename R, typename Factory> static int sweep_ss(const SweepCall& c) 
     } else {
         // wide-state path, or a factory without that pass: joint log-densities of both auxiliary models (posterior_logpdf + ell, base.py:72-96), then its terms
         bool both = false;
-        const SweepLogpdfEntry* wsl = wide_sweep_logpdf_entry(dtype);
         if (wide_ps_once && nan_policy == AUXSSM_NAN_REFERENCE && wsl && wsl->wide_shared) {
             // first order on one model: both joints from ONE launch pair -- Q_t^-1, R^-1 and their determinants once per time step, the chains as columns, ys1 scored
             // against x' and ys2 against x (wide_shared.h::wk_lp_cols); sums [2] / [3] = observation + transition terms of x' / x
@@ -1502,9 +1502,9 @@ template <typename R> static int sweep_lorenz(const SweepCall& c) {
     ws.add(bs2, (size_t)C * n * 3 * sR);
     ws.add(sc, (size_t)16 * C * sR);
     ws.add(sums, (size_t)5 * C * sizeof(Acc));
-    ws.after(ke->filter_ws(h, kd, parallel));
-    ws.after(se->sample_ws(h, kd, parallel));
-    ws.after(sl->ws(h, kd));
+    ws.after(ke->filter_ws(h, kd, parallel, D, P));
+    ws.after(se->sample_ws(h, kd, parallel, D));
+    ws.after(sl->ws(h, kd, D, PO));
     int rc = ws.reserve(h);
     if (rc) return rc;
     R* ell1 = sc; R* ell2 = sc + C;
@@ -1930,7 +1930,7 @@ int auxssm_kalman_filter(auxssm_handle h, int dtype, const auxssm_dims* dims, co
     const KalmanEntry* e = need_kalman(dtype, dims->dx, dims->dy);
     if (!e) return AUXSSM_ERR_UNSUPPORTED;
     const KDims kd{dims->C, dims->T, dims->B};
-    const size_t wsb = is_wide(dims->dx, dims->dy) ? wide_filter_ws(h, dtype, kd, parallel, dims->dx, dims->dy) : e->filter_ws(h, kd, parallel);
+    const size_t wsb = e->filter_ws(h, kd, parallel, dims->dx, dims->dy);
     if ((rc = ws_reserve(h, wsb + 4096))) return rc;
     FilterArgs a;
     fill_filter_args(a, dims, lgssm, ys, ms, Ps);
@@ -1961,7 +1961,7 @@ int auxssm_kalman_sample(auxssm_handle h, int dtype, const auxssm_dims* dims, co
         return AUXSSM_ERR_UNSUPPORTED;
     }
     const KDims kd{dims->C, dims->T, dims->B};
-    const size_t wsb = wide ? wide_sample_ws(h, dtype, kd, parallel, dims->dx) : e->sample_ws(h, kd, parallel);
+    const size_t wsb = e->sample_ws(h, kd, parallel, dims->dx);
     if ((rc = ws_reserve(h, wsb + 4096))) return rc;
     SampleArgs a;
     a.d = kd;
@@ -2004,7 +2004,7 @@ int auxssm_kalman_smooth(auxssm_handle h, int dtype, const auxssm_dims* dims, co
         return AUXSSM_ERR_UNSUPPORTED;
     }
     const KDims kd{dims->C, dims->T, dims->B};
-    if ((rc = ws_reserve(h, e->smooth_ws(h, kd, parallel) + 4096))) return rc;
+    if ((rc = ws_reserve(h, e->smooth_ws(h, kd, parallel, dims->dx) + 4096))) return rc;
     SmoothArgs a;
     a.d = kd;
     a.Fs = cv(lgssm->Fs); a.Qs = cv(lgssm->Qs); a.bs = cv(lgssm->bs);
@@ -2052,7 +2052,7 @@ int auxssm_kalman_joint_logpdf(auxssm_handle h, int dtype, const auxssm_dims* di
     const KalmanEntry* e = need_kalman(dtype, dims->dx, dims->dy);
     if (!e) return AUXSSM_ERR_UNSUPPORTED;
     const KDims kd{dims->C, dims->T, dims->B};
-    const size_t wsb = is_wide(dims->dx, dims->dy) ? wide_logpdf_ws(dtype, kd) : e->logpdf_ws(h, kd);
+    const size_t wsb = e->logpdf_ws(h, kd, dims->dx, dims->dy);
     if ((rc = ws_reserve(h, wsb + 4096))) return rc;
     LogpdfArgs a;
     fill_logpdf_args(a, dims, lgssm, cv(*ys), cv(*xs), nan_policy);

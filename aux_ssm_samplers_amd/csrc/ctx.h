@@ -155,6 +155,9 @@ void* ws_take(auxssm_ctx* h, size_t bytes);
 // will take behind the registered buffers (the drivers reset the bump offset to their mark between callees, and still reserve the SUM of the callees' own
 // estimates), total() is what the registered buffers occupy as ws_take lays them out (each on a 256-byte boundary, in the order of registration) plus that tail,
 // reserve() sizes the handle's workspace to it and fills the pointers.  Fixed capacity, no heap.
+// A callee that carves behind its caller's mark (the wide-state drivers, wide.hip) calls take() instead -- the same buffers from the slab as it stands -- and
+// kept() on its way out: what it and the callees it announced with after() carved, against total().  Neither looks at ws_bytes, so the head-room of ws_reserve
+// cannot hide a plan that says less than its driver takes.
 struct WsPlan {
     struct Entry {
         size_t bytes;
@@ -165,6 +168,8 @@ struct WsPlan {
     Entry e[CAP];
     int n = 0;
     size_t tail = 0;
+    WsPlan() = default;
+    WsPlan(const WsPlan&) = delete;  // (a plan holds addresses: of the caller's pointers, or of the members of the struct it is a member of)
     template <typename T> void add(T*& slot, size_t bytes) {
         if (n < CAP) e[n] = Entry{bytes, &slot, [](void* s, void* p) { *(T**)s = (T*)p; }};
         ++n;
@@ -176,18 +181,30 @@ struct WsPlan {
         for (int i = 0; i < n && i < CAP; ++i) off = ((off + 255) & ~(size_t)255) + e[i].bytes;
         return off + tail;
     }
-    int reserve(auxssm_ctx* h) const {
+    size_t mark = 0;  // the bump offset take() found
+    int take(auxssm_ctx* h) {
         if (n > CAP) {
             set_error("internal: workspace plan of %d buffers (capacity %d)", n, CAP);
             return AUXSSM_ERR_ARG;
         }
-        if (int rc = ws_reserve(h, total())) return rc;
+        mark = h->ws_off;
         for (int i = 0; i < n; ++i) {
             void* p = ws_take(h, e[i].bytes);
             if (!p) return AUXSSM_ERR_NOMEM;
             e[i].set(e[i].slot, p);
         }
         return AUXSSM_OK;
+    }
+    int reserve(auxssm_ctx* h) {
+        if (n <= CAP)
+            if (int rc = ws_reserve(h, total())) return rc;
+        return take(h);
+    }
+    int kept(const auxssm_ctx* h, const char* who) const {
+        const size_t first = (mark + 255) & ~(size_t)255, carved = h->ws_off > first ? h->ws_off - first : 0;
+        if (carved <= total()) return AUXSSM_OK;
+        set_error("internal: %s carved %zu bytes of workspace, its plan says %zu", who, carved, total());
+        return AUXSSM_ERR_NOMEM;
     }
 };
 
@@ -263,9 +280,10 @@ AffPlan plan_aff(const auxssm_ctx* h, int S, int N, int parallel, int waves = 8)
 typedef int (*filter_fn)(auxssm_ctx*, const FilterArgs&, int parallel, void* ell_out /*[C]*/);
 typedef int (*sample_fn)(auxssm_ctx*, const SampleArgs&, int parallel);
 typedef int (*logpdf_fn)(auxssm_ctx*, const LogpdfArgs&, void* out /*[C]*/);
-typedef size_t (*filter_ws_fn)(const auxssm_ctx*, const KDims&, int parallel);
-typedef size_t (*sample_ws_fn)(const auxssm_ctx*, const KDims&, int parallel);
-typedef size_t (*logpdf_ws_fn)(const auxssm_ctx*, const KDims&);
+// (the sizes: the state and observation dimensions last -- template parameters of the register units, which ignore them; the wide-state entries size by them)
+typedef size_t (*filter_ws_fn)(const auxssm_ctx*, const KDims&, int parallel, int dx, int dy);
+typedef size_t (*sample_ws_fn)(const auxssm_ctx*, const KDims&, int parallel, int dx);
+typedef size_t (*logpdf_ws_fn)(const auxssm_ctx*, const KDims&, int dx, int dy);
 
 struct KalmanEntry {
     filter_fn filter;
@@ -274,7 +292,7 @@ struct KalmanEntry {
     logpdf_ws_fn logpdf_ws;
 };
 typedef int (*sweep_logpdf_fn)(auxssm_ctx*, const SweepLogpdfArgs&, void* out /*[5][C]*/);
-typedef size_t (*sweep_logpdf_ws_fn)(const auxssm_ctx*, const KDims&);
+typedef size_t (*sweep_logpdf_ws_fn)(const auxssm_ctx*, const KDims&, int dx, int po);
 // host-side description of one fused chain-shared sweep (fused_shared.h::run_fused_shared; built by api.hip)
 struct FusedHost {
     FilterArgs fa;        // the concatenated model; ys = row 0 of [u_0 ; yobs_0] (chain-minor, one row), ms = the (D, C) slot of the t = 0 mean, Ps shared
@@ -303,7 +321,7 @@ struct SweepLogpdfEntry {
     sweep_logpdf_fn wide_shared = nullptr;  // wide-state entry only: the chains-as-columns form alone (returns 1 when it does not apply, nothing enqueued)
 };
 typedef int (*sv_logpdf_fn)(auxssm_ctx*, const SvLogpdfArgs&, void* out /*[5][C]*/);
-typedef size_t (*sv_logpdf_ws_fn)(const auxssm_ctx*, const KDims&);
+typedef size_t (*sv_logpdf_ws_fn)(const auxssm_ctx*, const KDims&, int dx);
 struct SampleEntry {
     sample_fn sample;
     sample_ws_fn sample_ws;
@@ -332,10 +350,6 @@ const KalmanEntry* wide_kalman_entry(int dtype);
 const SampleEntry* wide_sample_entry(int dtype);
 const SweepLogpdfEntry* wide_sweep_logpdf_entry(int dtype);
 bool wide_fits(int dtype, int dx, int dy, std::string* why);
-// the wide entries' *_ws members return 0 (the table signatures carry no sizes): api.hip asks through these instead
-size_t wide_filter_ws(const auxssm_ctx* h, int dtype, const KDims& kd, int parallel, int d, int p);
-size_t wide_sample_ws(const auxssm_ctx* h, int dtype, const KDims& kd, int parallel, int d);
-size_t wide_logpdf_ws(int dtype, const KDims& kd);
 size_t wide_gain_tab_bytes(int dtype, int T, int d, int p);  // the chain-shared wide filter's per-step gain rows (FilterArgs::pc)
 
 }  // namespace ax

@@ -1129,7 +1129,7 @@ int run_scan(auxssm_ctx* h, const typename Op::Args& a, int S, int n) {
 // ---- launchers ---------------------------------------------------------------------------------------------------
 inline int ntiles(int n) { return (n + TB_ELEM - 1) / TB_ELEM; }
 
-template <typename R, int D, int P> size_t filter_ws(const auxssm_ctx* h, const KDims& d, int parallel) {
+template <typename R, int D, int P> size_t filter_ws(const auxssm_ctx* h, const KDims& d, int parallel, int = D, int = P) {
     const int S = d.S(), n = d.n();
     const ScanLayout lay = make_layout(plan_scan(h, S, n, parallel), 0, S);
     size_t b = 0;
@@ -1373,7 +1373,7 @@ template <typename R, int D, int P> int run_filter(auxssm_ctx* h, const FilterAr
     return AUXSSM_OK;
 }
 
-template <typename R, int D> size_t sample_ws(const auxssm_ctx* h, const KDims& d, int parallel) {
+template <typename R, int D> size_t sample_ws(const auxssm_ctx* h, const KDims& d, int parallel, int = D) {
     const int S = d.S();
     const ScanLayout lay = make_layout(plan_scan(h, S, d.T, parallel), 0, S);
     return (size_t)S * lay.seq_records() * SampElem<R, D>::NPAD * sizeof(R) + 256 + scan_ws_bytes<SampleOp<R, D>>(h, S, d.T, parallel) +
@@ -1448,7 +1448,7 @@ template <typename R, int D> bool smooth_tiles(const auxssm_ctx* h, int S, int T
     static_assert(SmoothOpFly<R, D>::Full::NPAD == SmoothOp<R, D>::Full::NPAD, "run_scan<SmoothOpFly> must choose the tile scan exactly when run_smooth leaves elem null");
     return use_ks<SmoothOp<R, D>>(h, S, T, lay.nchunk > 1);
 }
-template <typename R, int D> size_t smooth_ws(const auxssm_ctx* h, const KDims& d, int parallel) {
+template <typename R, int D> size_t smooth_ws(const auxssm_ctx* h, const KDims& d, int parallel, int = D) {
     const int S = d.S();
     const size_t scan = scan_ws_bytes<SmoothOp<R, D>>(h, S, d.T, parallel);
     const ScanLayout lay = make_layout(plan_scan(h, S, d.T, parallel), 0, S);
@@ -1470,7 +1470,7 @@ template <typename R, int D> int run_smooth(auxssm_ctx* h, const SmoothArgs& a_i
     return run_scan<SmoothOp<R, D>>(h, a, S, T);
 }
 
-template <typename R, int D, int P> size_t logpdf_ws(const auxssm_ctx*, const KDims& d) {
+template <typename R, int D, int P> size_t logpdf_ws(const auxssm_ctx*, const KDims& d, int = D, int = P) {
     return (size_t)d.S() * (ntiles(d.T) + 1) * sizeof(R) + 256;
 }
 
@@ -1486,7 +1486,7 @@ template <typename R, int D, int P> int run_logpdf(auxssm_ctx* h, const LogpdfAr
     return AUXSSM_OK;
 }
 
-template <typename R, int D, int PO> size_t sweep_logpdf_ws(const auxssm_ctx*, const KDims& d) {
+template <typename R, int D, int PO> size_t sweep_logpdf_ws(const auxssm_ctx*, const KDims& d, int = D, int = PO) {
     const int ti = std::min(TI_CM, TI_SHARED);
     return (size_t)5 * d.C * (std::max(ntiles(d.T), (d.T + ti - 1) / ti) + 1) * sizeof(Acc) + 256 +
            (size_t)d.T * LogShared<R, D, PO>::NPAD * sizeof(R) + 256;
@@ -1533,7 +1533,7 @@ template <typename R, int D, int PO> int run_sweep_logpdf(auxssm_ctx* h, const S
     return AUXSSM_OK;
 }
 
-template <typename R, int D> size_t sv_logpdf_ws(const auxssm_ctx*, const KDims& d) {
+template <typename R, int D> size_t sv_logpdf_ws(const auxssm_ctx*, const KDims& d, int = D) {
     return (size_t)5 * d.C * (std::max(ntiles(d.T), (d.T + TI_CM - 1) / TI_CM) + 1) * sizeof(Acc) + 256;
 }
 // out: [5][C] of Acc

@@ -2328,13 +2328,24 @@ static bool fold_enabled() {
     return on;
 }
 template <typename R> static bool use_fold(int d, int p) { return fold_enabled() && fold_fits(sizeof(R), d) && lds_obs_info(sizeof(R), d, p) <= LDS_BUDGET; }
-template <typename R> static size_t filter_ws_one(const auxssm_ctx* h, int S, int n, int parallel, int d) {
-    const WPlan p = plan(h, S, n, parallel);
-    const size_t ne = (size_t)fe_size(d);
-    size_t nagg = 0;
-    for (int l = 0; l <= p.nlev; ++l) nagg += p.cnt[l];
-    return ((size_t)S * std::max(n, 1) * ne + (size_t)S * nagg * (ne + (size_t)pre_size(d)) + (size_t)S * (std::max(n, 1) + 2)) * sizeof(R) + 8192 + 256 * (2 * (WMAXLEV + 1) + 4);
-}
+// ---- workspaces.  A driver's buffers are said once, by a struct that holds their pointers beside the chunking decisions their sizes follow from and registers
+// them with its WsPlan (ctx.h).  The entry tables' *_ws functions return that plan's total(), the driver take()s it and checks it with kept() on its way out, so
+// sizing and running cannot disagree.  A driver that falls back from a shared form to the per-sequence one is sized by the larger of the two plans; `fits`
+// of a shared form: the shape tries it and every kernel of it has its LDS and register plan there (the shared filter is not even described on a shape that
+// does not try it: shared_plan wants n >= 1).
+template <typename Own, typename Sh> static size_t larger(const Own& own, const Sh& sh) { return sh.fits ? std::max(own.ws.total(), sh.ws.total()) : own.ws.total(); }
+// run_filter's per-sequence path: one element per step (fold: one InfoRow), the chunk aggregates and prefixes of every tree level, the two ell terms
+template <typename R> struct FilterWs {
+    WsPlan ws;
+    const WPlan pl;
+    const bool fold;
+    R *elem, *aggs[WMAXLEV + 1], *pre[WMAXLEV + 1], *ell0, *ellz;
+    FilterWs(const auxssm_ctx* h, int S, int n, int parallel, int d, int p) : pl(plan(h, S, n, parallel)), fold(use_fold<R>(d, p)) {
+        ws.add(elem, (size_t)S * std::max(n, 1) * (fold ? info_size(d) : fe_size(d)) * sizeof(R));
+        for (int l = 0; l <= pl.nlev; ++l) ws.add(aggs[l], (size_t)S * pl.cnt[l] * fe_size(d) * sizeof(R)), ws.add(pre[l], (size_t)S * pl.cnt[l] * pre_size(d) * sizeof(R));
+        ws.add(ell0, (size_t)S * sizeof(R)), ws.add(ellz, (size_t)S * sizeof(R));
+    }
+};
 // the chain-shared filter (wide_shared.h): blocks of CB sequences ride as matrix columns; chunks of E transitions
 struct SPlan {
     int CB, ncb, E, nchunk;
@@ -2350,48 +2361,61 @@ static SPlan shared_plan(const auxssm_ctx* h, int S, int n, int d, int p, size_t
     sp.nchunk = (n + sp.E - 1) / sp.E;
     return sp;
 }
-template <typename R> static size_t shared_ws(const auxssm_ctx* h, int S, int n, int d, int p) {
-    const SPlan sp = shared_plan(h, S, n, d, p, sizeof(R));
-    const GRow g(d, p);
-    const size_t Spad = (size_t)sp.ncb * sp.CB;
-    return ((size_t)n * g.size + 2 * (size_t)sp.nchunk * d * ldp_(d) + 4 * (size_t)sp.nchunk * d * Spad + (size_t)S * sp.nchunk + 2 * (size_t)S + 64) * sizeof(R) + 20 * 256;
-}
-template <typename R> static size_t filter_ws_d(const auxssm_ctx* h, const KDims& kd, int parallel, int d, int p) {
-    const int S = kd.S(), n = kd.n();
-    size_t need = filter_ws_one<R>(h, S, n, parallel, d);
-    if (S >= 2 && parallel && n >= 4 && p > 0) need = std::max(need, filter_ws_one<R>(h, 1, n, parallel, d) + shared_ws<R>(h, S, n, d, p));
-    return need;
+template <typename R> static size_t gain_tab_bytes(int n, int d, int p) { return (size_t)n * GRow(d, p).size * sizeof(R); }  // one GRow per transition
+// run_filter_shared: the read-back word of the pattern check, the gain rows unless the caller keeps them (FilterArgs::pc), the chunk composites and their prefixes -- with
+// a second level over groups of GRP when there are 2 GRP chunks or more -- and the ell terms; then, unless the rows are `ready`, the nested matrix filter on one sequence
+template <typename R> struct SharedFilterWs {
+    WsPlan ws;
+    static constexpr int GRP = 16;
+    static bool tries(int S, int n, int parallel, int p) { return S >= 2 && parallel && n >= 4 && p >= 1; }
+    const SPlan sp;
+    const int nsup;
+    const size_t l_tab, l_red, l_agg, l_down, l_grp;
+    const bool fits;
+    int* flag;
+    R *tab, *aggA, *aggG, *pre, *supA = nullptr, *supG = nullptr, *presup = nullptr, *ellpart, *ell0, *ell_seq0;
+    SharedFilterWs(const auxssm_ctx* h, int S, int n, int d, int p, void* pc, bool ready)
+        : sp(shared_plan(h, S, n, d, p, sizeof(R))), nsup(sp.nchunk >= 2 * GRP ? (sp.nchunk + GRP - 1) / GRP : 1), l_tab(lds_gain_tab(sizeof(R), d, p)),
+          l_red(lds_mean_reduce(sizeof(R), d, p, sp.CB)), l_agg(lds_mean_aggs(sizeof(R), d, sp.CB)), l_down(lds_mean_down(sizeof(R), d, p, sp.CB)),
+          l_grp(lds_mean_group(sizeof(R), d, sp.CB)),
+          fits(!((long long)p * sp.CB > (long long)SH_NY * NT || (long long)d * sp.CB > 6ll * NT ||
+                 (long long)std::max(d, p) * ldp_(std::max(d, p)) > (long long)SH_NR * NT || d + 2 * p + 2 > 3 * NT || !spd_fits(p, 2 * p + d)) &&
+               std::max({l_tab, l_red, l_agg, l_down, nsup > 1 ? l_grp : (size_t)0}) <= LDS_BUDGET) {
+        const size_t Spad = (size_t)sp.ncb * sp.CB, sq = (size_t)d * ldp_(d) * sizeof(R), cols = d * Spad * sizeof(R);
+        ws.add(flag, 256);
+        if (pc) tab = (R*)pc;  // (the caller's buffer: a sweep's second filter reuses the rows)
+        else ws.add(tab, gain_tab_bytes<R>(n, d, p));
+        ws.add(aggA, sp.nchunk * sq);
+        ws.add(aggG, sp.nchunk * cols), ws.add(pre, sp.nchunk * cols);
+        if (nsup > 1) ws.add(supA, nsup * sq), ws.add(supG, nsup * cols), ws.add(presup, nsup * cols);
+        ws.add(ellpart, (size_t)S * sp.nchunk * sizeof(R));
+        ws.add(ell0, (size_t)S * sizeof(R));
+        ws.add(ell_seq0, 256);
+        if (!ready) ws.after(FilterWs<R>(h, 1, n, 1, d, p).ws.total());
+    }
+};
+template <typename R> static size_t filter_ws(const auxssm_ctx* h, const KDims& kd, int parallel, int d, int p) {
+    const FilterWs<R> own(h, kd.S(), kd.n(), parallel, d, p);
+    return SharedFilterWs<R>::tries(kd.S(), kd.n(), parallel, p) ? larger(own, SharedFilterWs<R>(h, kd.S(), kd.n(), d, p, nullptr, false)) : own.ws.total();
 }
 template <typename R> static int run_filter_shared(auxssm_ctx* h, const FilterArgs& a, void* ell_out);
 
 template <typename R> int run_filter(auxssm_ctx* h, const FilterArgs& a, int parallel, void* ell_out) {
     const int S = a.d.S(), n = a.d.n(), d = a.dx, p = a.dy;
-    if (S >= 2 && parallel && n >= 4) {  // sequences that share every model parameter: one matrix recursion, the means as columns (wide_shared.h)
-        const int rc = run_filter_shared<R>(h, a, ell_out);
-        if (rc != 1) return rc;  // 1: not applicable (strides, option, observation patterns, LDS), nothing written -- the per-sequence path below
-    }
-    const WPlan pl = plan(h, S, n, parallel);
-    const bool fold = use_fold<R>(d, p);
-    const size_t ne = (size_t)fe_size(d), np = (size_t)pre_size(d);
-    R* elem = (R*)ws_take(h, (size_t)S * std::max(n, 1) * (fold ? (size_t)info_size(d) : ne) * sizeof(R));  // fold: one InfoRow per step
-    R *aggs[WMAXLEV + 1], *pre[WMAXLEV + 1];
-    for (int l = 0; l <= pl.nlev; ++l) {
-        aggs[l] = (R*)ws_take(h, (size_t)S * pl.cnt[l] * ne * sizeof(R));
-        pre[l] = (R*)ws_take(h, (size_t)S * pl.cnt[l] * np * sizeof(R));
-        if (!aggs[l] || !pre[l]) return AUXSSM_ERR_NOMEM;
-    }
-    R* ell0 = (R*)ws_take(h, (size_t)S * sizeof(R));
-    R* ellz = (R*)ws_take(h, (size_t)S * sizeof(R));
-    if (!elem || !ell0 || !ellz) return AUXSSM_ERR_NOMEM;
+    if (SharedFilterWs<R>::tries(S, n, parallel, p))  // sequences that share every model parameter: one matrix recursion, the means as columns (wide_shared.h)
+        if (const int rc = run_filter_shared<R>(h, a, ell_out); rc != 1) return rc;  // 1: not applicable (strides, option, observation patterns, LDS), nothing written
+    FilterWs<R> b(h, S, n, parallel, d, p);
+    if (int rc = b.ws.take(h)) return rc;
+    const WPlan& pl = b.pl;
     FilterArgs fa = a;
-    fa.ell0 = ell0;
-    fa.ellz = ellz;
+    fa.ell0 = b.ell0;
+    fa.ellz = b.ellz;
     {
         ProfScope ps(h, AUXSSM_K_FILTER_INIT);
         WK_LAUNCH((wk_filter_t0<R>), S, lds_filter_t0(sizeof(R), d, p), fa);
         if (n > 0) {
-            if (fold) WK_LAUNCH((wk_obs_info<R>), (long long)S * n, lds_obs_info(sizeof(R), d, p), fa, elem);
-            else WK_LAUNCH((wk_filter_init<R>), (long long)S * n, lds_filter_init(sizeof(R), d, p), fa, elem);
+            if (b.fold) WK_LAUNCH((wk_obs_info<R>), (long long)S * n, lds_obs_info(sizeof(R), d, p), fa, b.elem);
+            else WK_LAUNCH((wk_filter_init<R>), (long long)S * n, lds_filter_init(sizeof(R), d, p), fa, b.elem);
         }
     }
     if (n > 0) {
@@ -2399,23 +2423,23 @@ template <typename R> int run_filter(auxssm_ctx* h, const FilterArgs& a, int par
         {
             ProfScope ps(h, AUXSSM_K_FILTER_SCAN);
             if (pl.nchunk > 1) {
-                if (fold) WK_LAUNCH((wk_fold_reduce<R>), (long long)S * pl.nchunk, lds_fold(sizeof(R), d, true), fa, (const R*)elem, aggs[0], pl.E, pl.nchunk);
-                else WK_LAUNCH((wk_scan_reduce<R>), (long long)S * pl.nchunk, lc, (const R*)elem, aggs[0], n, pl.E, pl.nchunk, d);
+                if (b.fold) WK_LAUNCH((wk_fold_reduce<R>), (long long)S * pl.nchunk, lds_fold(sizeof(R), d, true), fa, (const R*)b.elem, b.aggs[0], pl.E, pl.nchunk);
+                else WK_LAUNCH((wk_scan_reduce<R>), (long long)S * pl.nchunk, lc, (const R*)b.elem, b.aggs[0], n, pl.E, pl.nchunk, d);
                 // the tree over the chunk aggregates: up (group aggregates), top (one workgroup per sequence), down ((b, C) prefixes per group)
                 for (int l = 0; l < pl.nlev; ++l)
-                    WK_LAUNCH((wk_scan_reduce<R>), (long long)S * pl.cnt[l + 1], lc, (const R*)aggs[l], aggs[l + 1], pl.cnt[l], pl.El[l], pl.cnt[l + 1], d);
-                WK_LAUNCH((wk_scan_aggs<R>), S, lc, (const R*)aggs[pl.nlev], pre[pl.nlev], pl.cnt[pl.nlev], d);
+                    WK_LAUNCH((wk_scan_reduce<R>), (long long)S * pl.cnt[l + 1], lc, (const R*)b.aggs[l], b.aggs[l + 1], pl.cnt[l], pl.El[l], pl.cnt[l + 1], d);
+                WK_LAUNCH((wk_scan_aggs<R>), S, lc, (const R*)b.aggs[pl.nlev], b.pre[pl.nlev], pl.cnt[pl.nlev], d);
                 for (int l = pl.nlev - 1; l >= 0; --l)
-                    WK_LAUNCH((wk_scan_down_pre<R>), (long long)S * pl.cnt[l + 1], lc, (const R*)aggs[l], (const R*)pre[l + 1], pre[l], pl.cnt[l], pl.El[l], pl.cnt[l + 1], d);
+                    WK_LAUNCH((wk_scan_down_pre<R>), (long long)S * pl.cnt[l + 1], lc, (const R*)b.aggs[l], (const R*)b.pre[l + 1], b.pre[l], pl.cnt[l], pl.El[l], pl.cnt[l + 1], d);
             }
-            if (fold) WK_LAUNCH((wk_fold_down<R>), (long long)S * pl.nchunk, lds_fold(sizeof(R), d, false), fa, (const R*)elem, (const R*)pre[0], pl.E, pl.nchunk);
-            else WK_LAUNCH((wk_scan_down<R>), (long long)S * pl.nchunk, lc, fa, (const R*)elem, (const R*)pre[0], pl.E, pl.nchunk);
+            if (b.fold) WK_LAUNCH((wk_fold_down<R>), (long long)S * pl.nchunk, lds_fold(sizeof(R), d, false), fa, (const R*)b.elem, (const R*)b.pre[0], pl.E, pl.nchunk);
+            else WK_LAUNCH((wk_scan_down<R>), (long long)S * pl.nchunk, lc, fa, (const R*)b.elem, (const R*)b.pre[0], pl.E, pl.nchunk);
         }
     }
     // ell = t = 0 term + the scan's log-scale (the reference's second pass, filtering.py:60-62, is not needed)
-    hipLaunchKernelGGL((wk_reduce<R>), dim3(a.d.C), dim3(NT), 0, h->stream, (const R*)ellz, (const R*)ell0, a.d.B, (long long)(n > 0 ? 1 : 0), (R*)ell_out);
+    hipLaunchKernelGGL((wk_reduce<R>), dim3(a.d.C), dim3(NT), 0, h->stream, (const R*)b.ellz, (const R*)b.ell0, a.d.B, (long long)(n > 0 ? 1 : 0), (R*)ell_out);
     AX_HIP(hipGetLastError());
-    return AUXSSM_OK;
+    return b.ws.kept(h, "wide::run_filter");
 }
 
 // returns 1 when the shared form does not apply (the caller runs the per-sequence path), else a status
@@ -2425,57 +2449,27 @@ template <typename R> static int run_filter_shared(auxssm_ctx* h, const FilterAr
     if (a.pc && a.tab_ready && !a.mask_ys.ptr) return 1;  // (a reused table was built on the carrier's pattern)
     for (const Arr* q : {&a.P0, &a.Fs, &a.Qs, &a.bs, &a.Hs, &a.Rs, &a.cs})
         if (q->sc != 0 || q->sb != 0) return 1;
-    const SPlan sp = shared_plan(h, S, n, d, p, sizeof(R));
-    if ((long long)p * sp.CB > (long long)SH_NY * NT || (long long)d * sp.CB > 6ll * NT || (long long)std::max(d, p) * ldp_(std::max(d, p)) > (long long)SH_NR * NT ||
-        d + 2 * p + 2 > 3 * NT || !spd_fits(p, 2 * p + d))
-        return 1;
-    const size_t l_tab = lds_gain_tab(sizeof(R), d, p), l_red = lds_mean_reduce(sizeof(R), d, p, sp.CB), l_agg = lds_mean_aggs(sizeof(R), d, sp.CB),
-                 l_down = lds_mean_down(sizeof(R), d, p, sp.CB);
-    if (std::max({l_tab, l_red, l_agg, l_down}) > LDS_BUDGET) return 1;
-    const GRow g(d, p);
-    const size_t Spad = (size_t)sp.ncb * sp.CB;
-    const size_t mark = h->ws_off;
-    int* flag = (int*)ws_take(h, 256);
-    R* tab = a.pc ? (R*)a.pc : (R*)ws_take(h, (size_t)n * g.size * sizeof(R));  // (the caller's buffer: a sweep's second filter reuses the rows)
     const bool reuse = a.pc && a.tab_ready;
-    R* aggA = (R*)ws_take(h, (size_t)sp.nchunk * d * ldp_(d) * sizeof(R));
-    R* aggG = (R*)ws_take(h, (size_t)sp.nchunk * d * Spad * sizeof(R));
-    R* pre = (R*)ws_take(h, (size_t)sp.nchunk * d * Spad * sizeof(R));
-    // second level of the chunk-composite scan: groups of GRP composites (none below 2 GRP chunks)
-    constexpr int GRP = 16;
-    const int nsup = sp.nchunk >= 2 * GRP ? (sp.nchunk + GRP - 1) / GRP : 1;
-    const size_t l_grp = lds_mean_group(sizeof(R), d, sp.CB);
-    R *supA = nullptr, *supG = nullptr, *presup = nullptr;
-    if (nsup > 1) {
-        if (l_grp > LDS_BUDGET) {
-            h->ws_off = mark;
-            return 1;
-        }
-        supA = (R*)ws_take(h, (size_t)nsup * d * ldp_(d) * sizeof(R));
-        supG = (R*)ws_take(h, (size_t)nsup * d * Spad * sizeof(R));
-        presup = (R*)ws_take(h, (size_t)nsup * d * Spad * sizeof(R));
-        if (!supA || !supG || !presup) return AUXSSM_ERR_NOMEM;
-    }
-    R* ellpart = (R*)ws_take(h, (size_t)S * sp.nchunk * sizeof(R));
-    R* ell0 = (R*)ws_take(h, (size_t)S * sizeof(R));
-    R* ell_seq0 = (R*)ws_take(h, 256);
-    if (!flag || !tab || !aggA || !aggG || !pre || !ellpart || !ell0 || !ell_seq0) return AUXSSM_ERR_NOMEM;
+    SharedFilterWs<R> b(h, S, n, d, p, a.pc, reuse);
+    if (!b.fits) return 1;
+    if (int rc = b.ws.take(h)) return rc;
+    const SPlan& sp = b.sp;
     // the one decision that needs the data: do all sequences miss the same observations?  4 bytes back to the host and one stream synchronisation -- for
     // auxssm_kalman_filter only (documented there).  A SWEEP never takes it: its caller passes the pattern as a chain-independent carrier (mask_ys; the first-order
     // SV factory's pseudo-observations are finite by construction), so the sweeps of a sampling loop stay asynchronous.
     if (!a.mask_ys.ptr) {
-        AX_HIP(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
-        hipLaunchKernelGGL((wk_mask_check<R>), dim3(std::min<long long>(1024, ((long long)a.d.T * p + 255) / 256)), dim3(256), 0, h->stream, a, flag);
+        AX_HIP(hipMemsetAsync(b.flag, 0, sizeof(int), h->stream));
+        hipLaunchKernelGGL((wk_mask_check<R>), dim3(std::min<long long>(1024, ((long long)a.d.T * p + 255) / 256)), dim3(256), 0, h->stream, a, b.flag);
         int differ = 0;
-        AX_HIP(hipMemcpyAsync(&differ, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        AX_HIP(hipMemcpyAsync(&differ, b.flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         AX_HIP(hipStreamSynchronize(h->stream));
         if (differ) {
-            h->ws_off = mark;
+            h->ws_off = b.ws.mark;
             return 1;
         }
     }
     FilterArgs fa = a;
-    fa.ell0 = ell0;
+    fa.ell0 = b.ell0;
     if (!reuse) {   // the matrix filter: sequence 0's slots through the per-sequence path, on sequence 0's observations or on the caller's pattern carrier (its Ps rows are
         // final; its means and its ell are recomputed below with the others')
         FilterArgs a1 = a;
@@ -2484,7 +2478,7 @@ template <typename R> static int run_filter_shared(auxssm_ctx* h, const FilterAr
         a1.d = KDims{1, a.d.T, 1};
         if (a.mask_ys.ptr) a1.ys = a.mask_ys;
         a1.mask_ys = Arr{nullptr, 0, 0, 0, 1};
-        const int rc = run_filter<R>(h, a1, 1, ell_seq0);
+        const int rc = run_filter<R>(h, a1, 1, b.ell_seq0);
         if (rc) return rc;
     }
     {
@@ -2515,30 +2509,30 @@ template <typename R> static int run_filter_shared(auxssm_ctx* h, const FilterAr
     }
     if (!reuse) {
         ProfScope ps(h, AUXSSM_K_FILTER_TAB);
-        WK_LAUNCH((wk_gain_tab<R>), n, l_tab, fa, tab);
+        WK_LAUNCH((wk_gain_tab<R>), n, b.l_tab, fa, b.tab);
     }
     {
         ProfScope ps(h, AUXSSM_K_FILTER_ELL);
-#define AX_MEAN(NRI)                                                                                                                                                         \
-    do {                                                                                                                                                                  \
-        if (sp.nchunk > 1) WK_LAUNCH((wk_mean_reduce<R, NRI>), (long long)sp.nchunk * sp.ncb, l_red, fa, (const R*)tab, aggA, aggG, sp.E, sp.ncb, sp.CB);                  \
-        if (nsup > 1) {  /* two levels: group composites, their sequential pass, then every group's chunk starts in parallel */                                         \
-            WK_LAUNCH((wk_mean_group<R, NRI>), (long long)nsup * sp.ncb, l_grp, fa, (const R*)aggA, (const R*)aggG, supA, supG, sp.nchunk, sp.ncb, sp.CB, GRP);            \
-            WK_LAUNCH((wk_mean_aggs<R, NRI>), sp.ncb, l_agg, fa, (const R*)supA, (const R*)supG, presup, nsup, sp.ncb, sp.CB, nsup, (const R*)nullptr);                    \
-            WK_LAUNCH((wk_mean_aggs<R, NRI>), (long long)nsup * sp.ncb, l_agg, fa, (const R*)aggA, (const R*)aggG, pre, sp.nchunk, sp.ncb, sp.CB, GRP, (const R*)presup);  \
-        } else {                                                                                                                                                          \
-            WK_LAUNCH((wk_mean_aggs<R, NRI>), sp.ncb, l_agg, fa, (const R*)aggA, (const R*)aggG, pre, sp.nchunk, sp.ncb, sp.CB, sp.nchunk, (const R*)nullptr);            \
-        }                                                                                                                                                                 \
-        WK_LAUNCH((wk_mean_down<R, NRI>), (long long)sp.nchunk * sp.ncb, l_down, fa, (const R*)tab, (const R*)pre, ellpart, sp.E, sp.nchunk, sp.ncb, sp.CB);              \
+#define AX_MEAN(NRI)                                                                                                                                                                     \
+    do {                                                                                                                                                                                 \
+        if (sp.nchunk > 1) WK_LAUNCH((wk_mean_reduce<R, NRI>), (long long)sp.nchunk * sp.ncb, b.l_red, fa, (const R*)b.tab, b.aggA, b.aggG, sp.E, sp.ncb, sp.CB);                        \
+        if (b.nsup > 1) {  /* two levels: group composites, their sequential pass, then every group's chunk starts in parallel */                                                        \
+            WK_LAUNCH((wk_mean_group<R, NRI>), (long long)b.nsup * sp.ncb, b.l_grp, fa, (const R*)b.aggA, (const R*)b.aggG, b.supA, b.supG, sp.nchunk, sp.ncb, sp.CB, b.GRP);            \
+            WK_LAUNCH((wk_mean_aggs<R, NRI>), sp.ncb, b.l_agg, fa, (const R*)b.supA, (const R*)b.supG, b.presup, b.nsup, sp.ncb, sp.CB, b.nsup, (const R*)nullptr);                      \
+            WK_LAUNCH((wk_mean_aggs<R, NRI>), (long long)b.nsup * sp.ncb, b.l_agg, fa, (const R*)b.aggA, (const R*)b.aggG, b.pre, sp.nchunk, sp.ncb, sp.CB, b.GRP, (const R*)b.presup);  \
+        } else {                                                                                                                                                                         \
+            WK_LAUNCH((wk_mean_aggs<R, NRI>), sp.ncb, b.l_agg, fa, (const R*)b.aggA, (const R*)b.aggG, b.pre, sp.nchunk, sp.ncb, sp.CB, sp.nchunk, (const R*)nullptr);                   \
+        }                                                                                                                                                                                \
+        WK_LAUNCH((wk_mean_down<R, NRI>), (long long)sp.nchunk * sp.ncb, b.l_down, fa, (const R*)b.tab, (const R*)b.pre, b.ellpart, sp.E, sp.nchunk, sp.ncb, sp.CB);                     \
     } while (0)
         if ((long long)std::max(d, p) * ldp_(std::max(d, p)) <= 5ll * NT) AX_MEAN(5);
         else AX_MEAN(SH_NR);
 #undef AX_MEAN
     }
-    hipLaunchKernelGGL((wk_reduce<R>), dim3(a.d.C), dim3(NT), 0, h->stream, (const R*)ellpart, (const R*)ell0, a.d.B, (long long)sp.nchunk, (R*)ell_out);
+    hipLaunchKernelGGL((wk_reduce<R>), dim3(a.d.C), dim3(NT), 0, h->stream, (const R*)b.ellpart, (const R*)b.ell0, a.d.B, (long long)sp.nchunk, (R*)ell_out);
     if (forked) AX_HIP(hipStreamWaitEvent(h->stream, h->join_ev, 0));
     AX_HIP(hipGetLastError());
-    return AUXSSM_OK;
+    return b.ws.kept(h, "wide::run_filter_shared");
 }
 
 // chunks of the shared sampler's vector scan: the chunk walks (twice E = T / nchunk dependent products) against the one-workgroup pass over the nchunk
@@ -2561,168 +2555,172 @@ static int samp_cb(const auxssm_ctx* h, int S, int nchunk) {
     while (CB > 16 && (long long)((S + CB - 1) / CB) * nchunk < 2ll * h->num_cu && CB / 2 >= 8) CB /= 2;
     return std::min(CB, std::max(S, 1));
 }
+// run_sample_shared: the gain and factor tables of one sequence, every sequence's increments, the chunk composites of both and the chunk-start prefixes
+template <typename R> struct SharedSampleWs {
+    WsPlan ws;
+    const WPlan pl;
+    const int CB, ncb;
+    const size_t l_e, l_s;
+    const bool fits;
+    R *gtab, *ltab, *ec, *gagg, *eagg, *pre;
+    SharedSampleWs(const auxssm_ctx* h, int S, int T, int parallel, int d)
+        : pl(samp_plan(T, parallel)), CB(samp_cb(h, S, pl.nchunk)), ncb((S + CB - 1) / CB), l_e(lds_samp_evec(sizeof(R), d, CB)),
+          l_s(lds_samp_scan(sizeof(R), d, CB)), fits(S >= 2 && T >= 2 && std::max(l_e, l_s) <= LDS_BUDGET) {
+        const size_t ne = ((size_t)d * d + d) * sizeof(R), cols = (size_t)S * d * sizeof(R);
+        ws.add(gtab, T * ne);
+        ws.add(ltab, (size_t)T * d * d * sizeof(R));
+        ws.add(ec, T * cols);
+        ws.add(gagg, pl.nchunk * ne);
+        ws.add(eagg, pl.nchunk * cols), ws.add(pre, pl.nchunk * cols);
+    }
+};
+// run_sample's per-sequence path: one (G, e) element per step, the chunk composites, the chunk-start prefixes
+template <typename R> struct SampleWs {
+    WsPlan ws;
+    const WPlan pl;
+    R *elem, *aggs, *pre;
+    SampleWs(const auxssm_ctx* h, int S, int T, int parallel, int d) : pl(plan(h, S, T, parallel)) {
+        const size_t ne = ((size_t)d * d + d) * sizeof(R);
+        ws.add(elem, (size_t)S * T * ne);
+        ws.add(aggs, (size_t)S * pl.nchunk * ne);
+        ws.add(pre, (size_t)S * pl.nchunk * d * sizeof(R));
+    }
+};
+template <typename R> static size_t sample_ws(const auxssm_ctx* h, const KDims& kd, int parallel, int d) {
+    return larger(SampleWs<R>(h, kd.S(), kd.T, parallel, d), SharedSampleWs<R>(h, kd.S(), kd.T, parallel, d));
+}
 // sequences sharing the model AND the filtered covariances (Ps with chain / batch stride 0: what the shared filter leaves when its caller asks for one copy):
 // the gain / factor tables once, the sequences as columns (wide_shared.h).  Returns 1 when not applicable.
 template <typename R> static int run_sample_shared(auxssm_ctx* h, const SampleArgs& a, int parallel) {
     const int S = a.d.S(), T = a.d.T, d = a.dx;
-    if (!h->share_model || S < 2 || T < 2) return 1;
+    if (!h->share_model) return 1;
     for (const Arr* q : {&a.Ps, &a.Fs, &a.Qs, &a.bs})
         if (q->sc != 0 || q->sb != 0) return 1;
-    const WPlan pl = samp_plan(T, parallel);
-    const int CB = samp_cb(h, S, pl.nchunk), ncb = (S + CB - 1) / CB;
-    const size_t l_e = lds_samp_evec(sizeof(R), d, CB), l_s = lds_samp_scan(sizeof(R), d, CB);
-    if (std::max(l_e, l_s) > LDS_BUDGET) return 1;
-    const size_t ne = (size_t)d * d + d;
-    R* gtab = (R*)ws_take(h, (size_t)T * ne * sizeof(R));
-    R* ltab = (R*)ws_take(h, (size_t)T * d * d * sizeof(R));
-    R* ec = (R*)ws_take(h, (size_t)T * S * d * sizeof(R));
-    R* gagg = (R*)ws_take(h, (size_t)pl.nchunk * ne * sizeof(R));
-    R* eagg = (R*)ws_take(h, (size_t)pl.nchunk * S * d * sizeof(R));
-    R* pre = (R*)ws_take(h, (size_t)pl.nchunk * S * d * sizeof(R));
-    if (!gtab || !ltab || !ec || !gagg || !eagg || !pre) return AUXSSM_ERR_NOMEM;
+    SharedSampleWs<R> b(h, S, T, parallel, d);
+    if (!b.fits) return 1;
+    if (int rc = b.ws.take(h)) return rc;
+    const WPlan& pl = b.pl;
     {
         ProfScope ps(h, AUXSSM_K_SAMPLE_INIT);
         SampleArgs a1 = a;  // the tables: sequence 0's records (its own increments come out of the column pass like everybody's)
         a1.d = KDims{1, T, 1};
-        WK_LAUNCH((wk_sample_init<R>), (long long)T, lds_sample_init(sizeof(R), d), a1, gtab, ltab);
-        WK_LAUNCH((wk_samp_evec<R>), (long long)T * ncb, l_e, a, (const R*)gtab, (const R*)ltab, ec, ncb, CB);
+        WK_LAUNCH((wk_sample_init<R>), (long long)T, lds_sample_init(sizeof(R), d), a1, b.gtab, b.ltab);
+        WK_LAUNCH((wk_samp_evec<R>), (long long)T * b.ncb, b.l_e, a, (const R*)b.gtab, (const R*)b.ltab, b.ec, b.ncb, b.CB);
     }
     ProfScope ps(h, AUXSSM_K_SAMPLE_SCAN);
     if (pl.nchunk > 1) {
-        WK_LAUNCH((wk_sscan_reduce<R>), (long long)pl.nchunk, lds_sample_scan(sizeof(R), d), (const R*)gtab, gagg, T, pl.E, pl.nchunk, d);
-        WK_LAUNCH((wk_samp_reduce<R>), (long long)pl.nchunk * ncb, l_s, (const R*)gtab, (const R*)ec, eagg, T, pl.E, pl.nchunk, d, S, ncb, CB);
-        WK_LAUNCH((wk_samp_aggs<R>), (long long)ncb, l_s, (const R*)gagg, (const R*)eagg, pre, pl.nchunk, d, S, CB);
+        WK_LAUNCH((wk_sscan_reduce<R>), (long long)pl.nchunk, lds_sample_scan(sizeof(R), d), (const R*)b.gtab, b.gagg, T, pl.E, pl.nchunk, d);
+        WK_LAUNCH((wk_samp_reduce<R>), (long long)pl.nchunk * b.ncb, b.l_s, (const R*)b.gtab, (const R*)b.ec, b.eagg, T, pl.E, pl.nchunk, d, S, b.ncb, b.CB);
+        WK_LAUNCH((wk_samp_aggs<R>), (long long)b.ncb, b.l_s, (const R*)b.gagg, (const R*)b.eagg, b.pre, pl.nchunk, d, S, b.CB);
     }
-    WK_LAUNCH((wk_samp_down<R>), (long long)pl.nchunk * ncb, l_s, a, (const R*)gtab, (const R*)ec, (const R*)pre, pl.E, pl.nchunk, ncb, CB);
+    WK_LAUNCH((wk_samp_down<R>), (long long)pl.nchunk * b.ncb, b.l_s, a, (const R*)b.gtab, (const R*)b.ec, (const R*)b.pre, pl.E, pl.nchunk, b.ncb, b.CB);
     AX_HIP(hipGetLastError());
-    return AUXSSM_OK;
+    return b.ws.kept(h, "wide::run_sample_shared");
 }
 
 template <typename R> int run_sample(auxssm_ctx* h, const SampleArgs& a, int parallel) {
     const int S = a.d.S(), T = a.d.T, d = a.dx;
-    if (S >= 2) {
-        const int rc = run_sample_shared<R>(h, a, parallel);
-        if (rc != 1) return rc;
-    }
-    const WPlan pl = plan(h, S, T, parallel);
-    const size_t ne = (size_t)d * d + d;
-    R* elem = (R*)ws_take(h, (size_t)S * T * ne * sizeof(R));
-    R* aggs = (R*)ws_take(h, (size_t)S * pl.nchunk * ne * sizeof(R));
-    R* pre = (R*)ws_take(h, (size_t)S * pl.nchunk * d * sizeof(R));
-    if (!elem || !aggs || !pre) return AUXSSM_ERR_NOMEM;
+    if (const int rc = run_sample_shared<R>(h, a, parallel); rc != 1) return rc;
+    SampleWs<R> b(h, S, T, parallel, d);
+    if (int rc = b.ws.take(h)) return rc;
+    const WPlan& pl = b.pl;
     {
         ProfScope ps(h, AUXSSM_K_SAMPLE_INIT);
-        WK_LAUNCH((wk_sample_init<R>), (long long)S * T, lds_sample_init(sizeof(R), d), a, elem, (R*)nullptr);
+        WK_LAUNCH((wk_sample_init<R>), (long long)S * T, lds_sample_init(sizeof(R), d), a, b.elem, (R*)nullptr);
     }
     ProfScope ps(h, AUXSSM_K_SAMPLE_SCAN);
     const size_t ls = lds_sample_scan(sizeof(R), d);
     if (pl.nchunk > 1) {
-        WK_LAUNCH((wk_sscan_reduce<R>), (long long)S * pl.nchunk, ls, (const R*)elem, aggs, T, pl.E, pl.nchunk, d);
-        WK_LAUNCH((wk_sscan_aggs<R>), S, ls, (const R*)aggs, pre, pl.nchunk, d);
+        WK_LAUNCH((wk_sscan_reduce<R>), (long long)S * pl.nchunk, ls, (const R*)b.elem, b.aggs, T, pl.E, pl.nchunk, d);
+        WK_LAUNCH((wk_sscan_aggs<R>), S, ls, (const R*)b.aggs, b.pre, pl.nchunk, d);
     }
-    WK_LAUNCH((wk_sscan_down<R>), (long long)S * pl.nchunk, ls, a, (const R*)elem, (const R*)pre, pl.E, pl.nchunk);
+    WK_LAUNCH((wk_sscan_down<R>), (long long)S * pl.nchunk, ls, a, (const R*)b.elem, (const R*)b.pre, pl.E, pl.nchunk);
     AX_HIP(hipGetLastError());
-    return AUXSSM_OK;
+    return b.ws.kept(h, "wide::run_sample");
+}
+
+// run_logpdf and run_sweep_logpdf's per-chain path: the per-step terms (one, or the sweep's five, per sequence and time step)
+template <typename R> struct TermsWs {
+    WsPlan ws;
+    R* part;
+    TermsWs(int nterm, int S, int T) { ws.add(part, (size_t)nterm * S * T * sizeof(R)); }
+};
+// run_sweep_logpdf_shared: the five terms and one table row per time step; CB columns per workgroup, as many as the column kernel's LDS plan holds
+template <typename R> struct SharedSweepLogpdfWs {
+    WsPlan ws;
+    int CB;
+    size_t l_tab, l_cols;
+    bool fits;
+    R *part, *tab;
+    SharedSweepLogpdfWs(int C, int T, int dx, int po) : CB(std::min(64, C)), l_tab(lds_lp_tab(sizeof(R), dx, po)) {
+        while (CB > 8 && lds_lp_cols(sizeof(R), dx, po, CB) > LDS_BUDGET) CB /= 2;
+        l_cols = lds_lp_cols(sizeof(R), dx, po, CB);
+        fits = C >= 2 && spd_fits(std::max(dx, po), 2 * std::max(dx, po)) && l_tab <= LDS_BUDGET && l_cols <= LDS_BUDGET;
+        ws.add(part, (size_t)5 * C * T * sizeof(R));
+        ws.add(tab, (size_t)T * lp_row(dx, po) * sizeof(R));
+    }
+};
+template <typename R> static size_t logpdf_ws(const auxssm_ctx*, const KDims& kd, int, int) { return TermsWs<R>(1, kd.S(), kd.T).ws.total(); }
+template <typename R> static size_t sweep_logpdf_ws(const auxssm_ctx*, const KDims& kd, int dx, int po) {
+    return larger(TermsWs<R>(5, kd.C, kd.T), SharedSweepLogpdfWs<R>(kd.C, kd.T, dx, po));
 }
 
 template <typename R> int run_logpdf(auxssm_ctx* h, const LogpdfArgs& a, void* out) {
     const int S = a.d.S(), T = a.d.T;
-    R* part = (R*)ws_take(h, (size_t)S * T * sizeof(R));
-    if (!part) return AUXSSM_ERR_NOMEM;
+    TermsWs<R> b(1, S, T);
+    if (int rc = b.ws.take(h)) return rc;
     ProfScope ps(h, AUXSSM_K_LOGPDF);
-    WK_LAUNCH((wk_logpdf<R>), (long long)S * T, lds_logpdf(sizeof(R), a.dx, a.dy), a, part);
-    hipLaunchKernelGGL((wk_reduce<R>), dim3(a.d.C), dim3(NT), 0, h->stream, (const R*)part, (const R*)nullptr, a.d.B, (long long)T, (R*)out);
+    WK_LAUNCH((wk_logpdf<R>), (long long)S * T, lds_logpdf(sizeof(R), a.dx, a.dy), a, b.part);
+    hipLaunchKernelGGL((wk_reduce<R>), dim3(a.d.C), dim3(NT), 0, h->stream, (const R*)b.part, (const R*)nullptr, a.d.B, (long long)T, (R*)out);
     AX_HIP(hipGetLastError());
-    return AUXSSM_OK;
+    return b.ws.kept(h, "wide::run_logpdf");
 }
 // chains on one model: the covariances' inverses and log-determinants once per time step, the chains as columns (wide_shared.h::wk_lp_tab / wk_lp_cols).
 // The observations may be per chain under the reference NaN policy (SweepLogpdfArgs::ys_x).  Returns 1 when the form does not apply (nothing enqueued).
 template <typename R> int run_sweep_logpdf_shared(auxssm_ctx* h, const SweepLogpdfArgs& a, void* out) {
     const int C = a.d.C, T = a.d.T;
-    if (!h->share_model || C < 2 || a.u_fly || !spd_fits(std::max(a.dx, a.po), 2 * std::max(a.dx, a.po))) return 1;
+    if (!h->share_model || a.u_fly) return 1;
     for (const Arr* q : {&a.m0, &a.P0, &a.Fs, &a.Qs, &a.bs, &a.Hs, &a.Rs, &a.cs})
         if (q->sc != 0 || q->sb != 0) return 1;
     if ((a.ys.sc != 0 || a.ys_x.ptr) && a.nan_policy != 0) return 1;
-    int CB = std::min(64, C);
-    while (CB > 8 && lds_lp_cols(sizeof(R), a.dx, a.po, CB) > LDS_BUDGET) CB /= 2;
-    const size_t l_tab = lds_lp_tab(sizeof(R), a.dx, a.po), l_cols = lds_lp_cols(sizeof(R), a.dx, a.po, CB);
-    if (l_tab > LDS_BUDGET || l_cols > LDS_BUDGET) return 1;
-    const size_t mark = h->ws_off;
-    R* part = (R*)ws_take(h, (size_t)5 * C * T * sizeof(R));
-    R* tab = (R*)ws_take(h, (size_t)T * lp_row(a.dx, a.po) * sizeof(R));
-    if (!part || !tab) {
-        h->ws_off = mark;
-        return 1;
-    }
+    SharedSweepLogpdfWs<R> b(C, T, a.dx, a.po);
+    if (!b.fits) return 1;
+    if (int rc = b.ws.take(h)) return rc;
     ProfScope ps(h, AUXSSM_K_LOGPDF);
-    const int ncb = (C + CB - 1) / CB;
-    WK_LAUNCH((wk_lp_tab<R>), (long long)T, l_tab, a, tab);
-    WK_LAUNCH((wk_lp_cols<R>), (long long)T * ncb, l_cols, a, (const R*)tab, part, ncb, CB);
-    hipLaunchKernelGGL((wk_reduce<R, Acc>), dim3(5 * C), dim3(NT), 0, h->stream, (const R*)part, (const R*)nullptr, 1, (long long)T, (Acc*)out);
+    const int ncb = (C + b.CB - 1) / b.CB;
+    WK_LAUNCH((wk_lp_tab<R>), (long long)T, b.l_tab, a, b.tab);
+    WK_LAUNCH((wk_lp_cols<R>), (long long)T * ncb, b.l_cols, a, (const R*)b.tab, b.part, ncb, b.CB);
+    hipLaunchKernelGGL((wk_reduce<R, Acc>), dim3(5 * C), dim3(NT), 0, h->stream, (const R*)b.part, (const R*)nullptr, 1, (long long)T, (Acc*)out);
     AX_HIP(hipGetLastError());
-    return AUXSSM_OK;
+    return b.ws.kept(h, "wide::run_sweep_logpdf_shared");
 }
 template <typename R> int run_sweep_logpdf(auxssm_ctx* h, const SweepLogpdfArgs& a, void* out) {
     const int C = a.d.C, T = a.d.T;
-    {
-        const int rc = run_sweep_logpdf_shared<R>(h, a, out);
-        if (rc != 1) return rc;
-    }
-    R* part = (R*)ws_take(h, (size_t)5 * C * T * sizeof(R));
-    if (!part) return AUXSSM_ERR_NOMEM;
+    if (const int rc = run_sweep_logpdf_shared<R>(h, a, out); rc != 1) return rc;
+    TermsWs<R> b(5, C, T);
+    if (int rc = b.ws.take(h)) return rc;
     ProfScope ps(h, AUXSSM_K_LOGPDF);
-    WK_LAUNCH((wk_sweep_logpdf<R>), (long long)C * T, lds_sweep_logpdf(sizeof(R), a.dx, a.po), a, part);
-    hipLaunchKernelGGL((wk_reduce<R, Acc>), dim3(5 * C), dim3(NT), 0, h->stream, (const R*)part, (const R*)nullptr, 1, (long long)T, (Acc*)out);
+    WK_LAUNCH((wk_sweep_logpdf<R>), (long long)C * T, lds_sweep_logpdf(sizeof(R), a.dx, a.po), a, b.part);
+    hipLaunchKernelGGL((wk_reduce<R, Acc>), dim3(5 * C), dim3(NT), 0, h->stream, (const R*)b.part, (const R*)nullptr, 1, (long long)T, (Acc*)out);
     AX_HIP(hipGetLastError());
-    return AUXSSM_OK;
+    return b.ws.kept(h, "wide::run_sweep_logpdf");
 }
 
 }  // namespace wide
 
-// ---- workspace sizes: the entry-table signatures carry no (dx, dy), so api.hip asks through these ---------------------------
-size_t wide_filter_ws(const auxssm_ctx* h, int dtype, const KDims& kd, int parallel, int d, int p) {
-    return dtype == AUXSSM_F32 ? wide::filter_ws_d<float>(h, kd, parallel, d, p) : wide::filter_ws_d<double>(h, kd, parallel, d, p);
+size_t wide_gain_tab_bytes(int dtype, int T, int d, int p) {
+    return dtype == AUXSSM_F32 ? wide::gain_tab_bytes<float>(std::max(T - 1, 1), d, p) : wide::gain_tab_bytes<double>(std::max(T - 1, 1), d, p);
 }
-size_t wide_gain_tab_bytes(int dtype, int T, int d, int p) { return (size_t)std::max(T - 1, 1) * (size_t)wide::GRow(d, p).size * (dtype == AUXSSM_F32 ? 4 : 8) + 256; }
-size_t wide_sample_ws(const auxssm_ctx* h, int dtype, const KDims& kd, int parallel, int d) {
-    const size_t s = dtype == AUXSSM_F32 ? 4 : 8;
-    const wide::WPlan p = wide::plan(h, kd.S(), kd.T, parallel);
-    const size_t ne = (size_t)d * d + d;
-    const size_t per_seq = ((size_t)kd.S() * kd.T * ne + (size_t)kd.S() * p.nchunk * (ne + d)) * s + 4096;
-    const wide::WPlan p1 = wide::samp_plan(kd.T, parallel);  // shared form: two tables, the increments, the chunk composites
-    const size_t shared = ((size_t)kd.T * (ne + (size_t)d * d + (size_t)kd.S() * d) + (size_t)p1.nchunk * (ne + 2 * (size_t)kd.S() * d)) * s + 8 * 256;
-    return std::max(per_seq, shared);
-}
-size_t wide_logpdf_ws(int dtype, const KDims& kd) {  // (+ the shared form's table: Q^-1 of at most 85 x 85 and R^-1 of at most 128 x 128 per time step -- wide_fits)
-    return ((size_t)5 * kd.S() * kd.T + (size_t)kd.T * (85 * 85 + 128 * 128 + 8)) * (dtype == AUXSSM_F32 ? 4 : 8) + 4096;
-}
-
-static size_t ws_unused_f(const auxssm_ctx*, const KDims&, int) { return 0; }
-static size_t ws_unused_l(const auxssm_ctx*, const KDims&) { return 0; }
-
-const KalmanEntry* wide_kalman_entry(int dtype) {
-    static const KalmanEntry f32{&wide::run_filter<float>, &ws_unused_f, &wide::run_logpdf<float>, &ws_unused_l};
-    static const KalmanEntry f64{&wide::run_filter<double>, &ws_unused_f, &wide::run_logpdf<double>, &ws_unused_l};
-    return dtype == AUXSSM_F32 ? &f32 : &f64;
-}
-const SampleEntry* wide_sample_entry(int dtype) {
-    static const SampleEntry f32{&wide::run_sample<float>, &ws_unused_f};
-    static const SampleEntry f64{&wide::run_sample<double>, &ws_unused_f};
-    return dtype == AUXSSM_F32 ? &f32 : &f64;
-}
-const SweepLogpdfEntry* wide_sweep_logpdf_entry(int dtype) {
-    static const SweepLogpdfEntry f32 = [] {
-        SweepLogpdfEntry e{&wide::run_sweep_logpdf<float>, &ws_unused_l};
-        e.wide_shared = &wide::run_sweep_logpdf_shared<float>;
-        return e;
-    }();
-    static const SweepLogpdfEntry f64 = [] {
-        SweepLogpdfEntry e{&wide::run_sweep_logpdf<double>, &ws_unused_l};
-        e.wide_shared = &wide::run_sweep_logpdf_shared<double>;
-        return e;
-    }();
-    return dtype == AUXSSM_F32 ? &f32 : &f64;
-}
+template <typename R> static const KalmanEntry wide_kalman{&wide::run_filter<R>, &wide::filter_ws<R>, &wide::run_logpdf<R>, &wide::logpdf_ws<R>};
+template <typename R> static const SampleEntry wide_sample{&wide::run_sample<R>, &wide::sample_ws<R>};
+template <typename R> static const SweepLogpdfEntry wide_sweep_logpdf = [] {
+    SweepLogpdfEntry e{&wide::run_sweep_logpdf<R>, &wide::sweep_logpdf_ws<R>};
+    e.wide_shared = &wide::run_sweep_logpdf_shared<R>;
+    return e;
+}();
+const KalmanEntry* wide_kalman_entry(int dtype) { return dtype == AUXSSM_F32 ? &wide_kalman<float> : &wide_kalman<double>; }
+const SampleEntry* wide_sample_entry(int dtype) { return dtype == AUXSSM_F32 ? &wide_sample<float> : &wide_sample<double>; }
+const SweepLogpdfEntry* wide_sweep_logpdf_entry(int dtype) { return dtype == AUXSSM_F32 ? &wide_sweep_logpdf<float> : &wide_sweep_logpdf<double>; }
 bool wide_fits(int dtype, int dx, int dy, std::string* why) {
     const size_t s = dtype == AUXSSM_F32 ? 4 : 8;
     size_t need = std::max(wide::lds_combine(s, dx), wide::lds_sample_init(s, dx));
