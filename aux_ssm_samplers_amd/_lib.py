@@ -19,6 +19,7 @@ KMODEL_MVT_FIRST, KMODEL_MVT_SECOND = 5, 6
 KMODEL_POISSON_FIRST, KMODEL_POISSON_SECOND = 7, 8
 KMODEL_POISSON_LIN_FIRST, KMODEL_POISSON_LIN_SECOND = 11, 12   # (9 and 10 are unassigned)
 KMODEL_LOGISTIC_FIRST, KMODEL_LOGISTIC_SECOND = 13, 14
+KMODEL_LOGISTIC_LIN_FIRST, KMODEL_LOGISTIC_LIN_SECOND = 15, 16
 LAYOUT_DENSE, LAYOUT_CHAIN_MINOR = 0, 1
 OPT_SHARE_MODEL = 1
 OPT_OVERLAP_MODEL_STAGE = 2

@@ -1188,7 +1188,9 @@ template <typename R> struct PointwiseFactory {
 // POISSON_LIN_*: Poisson counts behind a loading matrix, y_{t,j} ~ Poisson(exp(h_j' x_t + c_j)), j = 1..dy (model->Hs = H (dy, dx) row-major, model->cs = c (dy)):
 // kalman_plin.hip's reduction over the channels; second order gives every (chain, step) its own dense R = Omega_t.  The dense layout and dx <= 4 only (refused
 // before the driver: plin_limits), so the sweep is sweep_ss's dense, materialised form on the register kernels whatever dy is.
-template <typename R> struct PlinFactory {
+// LOGISTIC_LIN_* (LINK = PLIN_LOGISTIC): the same factory under the logit link -- binomial and negative-binomial channels, model->cs = [c; s; w] (3, dy) with the
+// size m_{t,j} = s_j + w_j y_{t,j}; the launch takes the kernel of that channel body, and the terms, the workspace and the driver are the Poisson twin's.
+template <typename R, int LINK = PLIN_POISSON> struct PlinFactory {
     static constexpr bool one_pass = false;
     Acc *pot1, *pot2, *part;  // the potential per (chain, step) at either linearisation point, as obs leaves it for terms
     static Arr data(const SweepCall& c) { return cv(*c.yobs); }
@@ -1199,7 +1201,7 @@ template <typename R> struct PlinFactory {
         ws.add(part, plin_terms_part_bytes(c.dims->C, c.dims->T));
     }
     int obs(const SweepCall& c, const R* xlin, const R* eps, R* u, R* ys, R* Rs) {
-        const PlinObsArgs oa{c.dims->C, c.dims->T, c.dims->dx, c.dims->dy, c.order, c.delta, c.dptr, c.model->Hs.ptr, c.model->cs.ptr, c.yobs->ptr, (long long)c.yobs->st,
+        const PlinObsArgs oa{LINK, c.dims->C, c.dims->T, c.dims->dx, c.dims->dy, c.order, c.delta, c.dptr, c.model->Hs.ptr, c.model->cs.ptr, c.yobs->ptr, (long long)c.yobs->st,
                              xlin, eps, u, ys, Rs, eps ? pot1 : pot2};
         return run_plin_obs(c.h, c.dtype, oa);
     }
@@ -1649,28 +1651,35 @@ static int mvt_limits(const auxssm_dims* dims, int layout, int nan_policy) {
     }
     return AUXSSM_OK;
 }
-static int plin_args(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs) {
+// POISSON_LIN_* / LOGISTIC_LIN_*: one set of checks, the messages naming the model
+static int plin_args_of(const char* who, const char* cs_is, const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs) {
     if (!prior_and_dynamics(dims, model) || !model->Hs.ptr || !model->cs.ptr || !yobs || !yobs->ptr) {
-        set_error("Poisson-linear model needs m0, P0 (and Fs, Qs, bs with T > 1), Hs (= H (dy, dx) row-major on the device), cs (= c (dy) on the device) and yobs (T, dy)");
+        set_error("%s model needs m0, P0 (and Fs, Qs, bs with T > 1), Hs (= H (dy, dx) row-major on the device), cs (= %s on the device) and yobs (T, dy)", who, cs_is);
         return AUXSSM_ERR_ARG;
     }
     return AUXSSM_OK;
 }
-static int plin_limits(const auxssm_dims* dims, int layout, int) {
+static int plin_limits_of(const char* who, const auxssm_dims* dims, int layout) {
     if (dims->dx > MAX_D) {
-        set_error("the Poisson-linear sweep covers dx <= %d (the register kernels): got dx = %d", MAX_D, dims->dx);
+        set_error("the %s sweep covers dx <= %d (the register kernels): got dx = %d", who, MAX_D, dims->dx);
         return AUXSSM_ERR_UNSUPPORTED;
     }
     if (dims->dy > PLIN_MAX_DY) {
-        set_error("the Poisson-linear sweep covers dy <= %d channels: got dy = %d", PLIN_MAX_DY, dims->dy);
+        set_error("the %s sweep covers dy <= %d channels: got dy = %d", who, PLIN_MAX_DY, dims->dy);
         return AUXSSM_ERR_UNSUPPORTED;
     }
     if (layout != AUXSSM_LAYOUT_DENSE) {
-        set_error("the Poisson-linear sweep (dx <= %d, dy <= %d) takes the dense (C, T, dx) layout only", MAX_D, PLIN_MAX_DY);
+        set_error("the %s sweep (dx <= %d, dy <= %d) takes the dense (C, T, dx) layout only", who, MAX_D, PLIN_MAX_DY);
         return AUXSSM_ERR_UNSUPPORTED;
     }
     return AUXSSM_OK;
 }
+static int plin_args(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs) { return plin_args_of("Poisson-linear", "c (dy)", dims, model, yobs); }
+static int plin_limits(const auxssm_dims* dims, int layout, int) { return plin_limits_of("Poisson-linear", dims, layout); }
+static int llin_args(const auxssm_dims* dims, const auxssm_lgssm* model, const auxssm_arr* yobs) {
+    return plin_args_of("logistic-linear (binomial / negative-binomial)", "[c; s; w] (3, dy), the size m = s + w y", dims, model, yobs);
+}
+static int llin_limits(const auxssm_dims* dims, int layout, int) { return plin_limits_of("logistic-linear", dims, layout); }
 
 //                                      obs_model  noise_arrays  args            limits       driver
 static const SweepFamily FAM_LG_CONCAT{true, false, lg_concat_args, nullptr, AX_SWEEP_DRIVER(sweep_lg_concat<R>)};
@@ -1679,6 +1688,7 @@ static const SweepFamily FAM_POINTWISE_SIZE{false, true, pointwise_size_args, nu
 static const SweepFamily FAM_LORENZ{true, true, lorenz_args, nullptr, AX_SWEEP_DRIVER(sweep_lorenz<R>)};
 static const SweepFamily FAM_MVT{false, true, mvt_args, mvt_limits, AX_SWEEP_DRIVER(sweep_mvt<R>)};
 static const SweepFamily FAM_PLIN{false, true, plin_args, plin_limits, AX_SWEEP_DRIVER(sweep_ss<R, PlinFactory<R>>)};
+static const SweepFamily FAM_LLIN{false, true, llin_args, llin_limits, AX_SWEEP_DRIVER(sweep_ss<R, PlinFactory<R, PLIN_LOGISTIC>>)};
 static const struct KModelRow {
     int model_kind;
     const SweepFamily* family;
@@ -1696,6 +1706,8 @@ static const struct KModelRow {
     {AUXSSM_KMODEL_POISSON_LIN_SECOND, &FAM_PLIN, 2, 0},
     {AUXSSM_KMODEL_LOGISTIC_FIRST, &FAM_POINTWISE_SIZE, 1, PW_LOGISTIC},
     {AUXSSM_KMODEL_LOGISTIC_SECOND, &FAM_POINTWISE_SIZE, 2, PW_LOGISTIC},
+    {AUXSSM_KMODEL_LOGISTIC_LIN_FIRST, &FAM_LLIN, 1, 0},
+    {AUXSSM_KMODEL_LOGISTIC_LIN_SECOND, &FAM_LLIN, 2, 0},
 };
 static const KModelRow* kmodel_row(int model_kind) {
     for (const KModelRow& r : KMODELS)

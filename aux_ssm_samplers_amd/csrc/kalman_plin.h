@@ -2,7 +2,8 @@
 //
 //     y_{t,j} ~ Poisson(exp(h_j' x_t + c_j)),  j = 1..dy,      log g_t = sum_j y_j eta_j - e_j,  grad_t = H' (y - e),  Lam_t = H' diag(e) H = -hess
 //
-// with eta = H x + c, e = exp(eta), every term of a missing (NaN) count dropped.  The first half of this header is the per-step arithmetic as AX_HD functions:
+// with eta = H x + c, e = exp(eta), every term of a missing (NaN) count dropped -- and its twin under the logit link (AUXSSM_KMODEL_LOGISTIC_LIN_FIRST / _SECOND:
+// binomial and negative-binomial channels, plin_accum_logistic below), which shares everything but the channel body.  The first half of this header is the per-step arithmetic as AX_HD functions:
 // the kernels of kalman_plin.hip and the CPU harness of tests/hostsim_plin compile the same text.  The second half (HIP builds only) is what api.hip hands to
 // kalman_plin.hip.
 #pragma once
@@ -50,6 +51,44 @@ template <typename R, int D> AX_HD void plin_accum(PlinAcc<R, D>& a, const R* x,
             const R eh = e * h[k];
 #pragma unroll
             for (int l = k; l < D; ++l) a.lam[sidx_u(D, k, l)] += eh * h[l];
+        }
+    }
+    a.val += (Acc)v;
+}
+// The same block under the logit link (AUXSSM_KMODEL_LOGISTIC_LIN_*): channel j has the size m = sb[j] + wb[j] yy (binomial: sb = trials, wb = 0; negative
+// binomial: sb = r, wb = 1 -- no branch), and with e = exp(-|eta|) <= 1, r = 1 / (1 + e):  sigma = eta >= 0 ? r : e r,  sigma (1 - sigma) = (e r) r on either
+// side (never a subtraction),  softplus = max(eta, 0) + log1p(e):
+//     log g += yy eta - m softplus,      g += h (yy - m sigma),      lam += (m sigma (1 - sigma)) h h'
+// One exponential, one reciprocal and one logarithm per channel; nothing overflows at any eta.  A missing channel has yy = m = 0 by selection: its size (which may
+// be anything, NaN included) is never part of a sum.
+template <typename R, int D> AX_HD void plin_accum_logistic(PlinAcc<R, D>& a, const R* x, const R* y, const R* Hb, const R* cb, const R* sb, const R* wb, int n) {
+    R v = 0;
+    for (int j = 0; j < n; ++j) {
+        R h[D];
+        R eta = cb[j];
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            h[k] = Hb[j * D + k];
+            eta += h[k] * x[k];
+        }
+        const R yj = y[j];
+        const bool on = finite_(yj);
+        const R yy = on ? yj : (R)0;
+        const R m = on ? sb[j] + wb[j] * yy : (R)0;
+        const R e = exp_(-abs_(eta));
+        const R u = (R)1 + e, r = (R)1 / u, er = e * r;
+        // log1p(e) = log(u) + log(1 + (e - (u - 1)) / u): u - 1 is exact (u in (1, 2]), so e - (u - 1) is what rounding u lost, and its first-order term restores
+        // it -- accurate to an ulp however small e is, on the reciprocal the body has anyway (the library's log1pf alone is about 100 instructions)
+        const R l1p = log_(u) + (e - (u - (R)1)) * r;
+        v += yy * eta - m * (max_(eta, (R)0) + l1p);
+        const R res = yy - m * (eta >= (R)0 ? r : er);
+        const R w = m * (er * r);
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            a.g[k] += h[k] * res;
+            const R wh = w * h[k];
+#pragma unroll
+            for (int l = k; l < D; ++l) a.lam[sidx_u(D, k, l)] += wh * h[l];
         }
     }
     a.val += (Acc)v;
@@ -106,6 +145,16 @@ template <typename R, int D> AX_HD void plin_step(const R* x, const R* u, const 
     value = a.val;
     plin_finish<R, D>(a, x, u, delta, order, ys, Om);
 }
+// The same step under the logit link: csw (3, dy) = [c; s; w], the array the model's cs slot carries (include/auxssm.h, LOGISTIC_LIN_*)
+template <typename R, int D>
+AX_HD void plin_step_logistic(const R* x, const R* u, const R* y, const R* H, const R* csw, int dy, R delta, int order, Acc& value, R* ys, R* Om) {
+    PlinAcc<R, D> a;
+    plin_zero(a);
+    for (int j0 = 0; j0 < dy; j0 += PLIN_JB)
+        plin_accum_logistic<R, D>(a, x, y + j0, H + (long long)j0 * D, csw + j0, csw + dy + j0, csw + 2 * (long long)dy + j0, dy - j0 < PLIN_JB ? dy - j0 : PLIN_JB);
+    value = a.val;
+    plin_finish<R, D>(a, x, u, delta, order, ys, Om);
+}
 // log N(y; x, Om) with Om dense symmetric (upper triangle, packed), by Cholesky in registers; NaN when the factorisation fails
 template <typename R, int D> AX_HD R plin_norm_logpdf(const R* y, const R* x, const R* Om) {
     R L[symsize(D)], invd[D], z[D];
@@ -131,11 +180,13 @@ namespace ax {
 
 // The factory launch at one linearisation point, everything per-chain dense (C, T, D).  eps != null (pass 1): u = xlin + sqrt(delta/2) eps is formed and
 // written; eps == null (pass 2): u is read.  Writes ys (C, T, D), for order 2 the full dense Rs (C, T, D, D), and pot (C, T): log g_t(xlin_t) in Acc.
+enum PlinLink : int { PLIN_POISSON = 0, PLIN_LOGISTIC = 1 };  // the channel body: plin_accum | plin_accum_logistic (then c is [c; s; w] (3, dy))
 struct PlinObsArgs {
+    int link;
     int C, T, D, dy, order;
     double delta;        // host step size (a placeholder when dptr is set)
     const double* dptr;  // device-resident {delta, sqrt(delta / 2)}, or null
-    const void *H, *c;   // (dy, D) row-major, (dy)
+    const void *H, *c;   // (dy, D) row-major, (dy) -- PLIN_LOGISTIC: (3, dy)
     const void* yobs;    // (T, dy), time stride y_st elements
     long long y_st;
     const void *xlin, *eps;

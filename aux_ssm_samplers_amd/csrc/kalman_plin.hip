@@ -9,6 +9,9 @@
 //                 steps on different banks) and every lane the same H_j, c_j (broadcast).  A staged tile serves all the workgroup's chains before the next one
 //                 is fetched; one exponential per (chain, step, channel).  Then the auxiliary observation of the sweep's order (plin_finish), the step's potential
 //                 value to pot (C, T) in Acc, and at the first linearisation point u = x + sqrt(delta / 2) eps.
+//   k_plin_obs_logistic   the same kernel with the channel body of the logit link (AUXSSM_KMODEL_LOGISTIC_LIN_*: plin_accum_logistic): it stages the two further
+//                 dy-rows s and w of the size m = s + w y beside c (+ 2 x 64 reals of LDS) and spends one exponential, one reciprocal and one logarithm per (chain,
+//                 step, channel).  A __global__ function of its own, so that k_plin_obs keeps its registers.
 //   k_plin_terms  one workgroup per (chain, segment of PLIN_SEG steps): the potentials of x' and x summed from what the two factory launches left (no exponential),
 //                 the Gaussian terms of the auxiliary observations under dense R (Cholesky in registers) or delta/2 I, and the correction sum -- lanes stride
 //                 over the segment's steps, each in Acc, then a tree over the workgroup; k_plin_totals adds a chain's segments in ascending order.  The
@@ -23,7 +26,9 @@ constexpr int PLIN_CG = 4;    // chains per workgroup: how often a staged y tile
 constexpr int PLIN_LD = PLIN_JB + 1;
 constexpr int PLIN_SEG = 2048;  // steps per workgroup of k_plin_terms (8 per lane): one chain of T = 16384 keeps 8 CUs busy, not 1
 
-template <typename R> size_t plin_lds_bytes(int D) { return ((size_t)PLIN_TT * PLIN_LD + (size_t)PLIN_JB * D + PLIN_JB) * sizeof(R); }
+template <typename R> size_t plin_lds_bytes(int D, int link) {
+    return ((size_t)PLIN_TT * PLIN_LD + (size_t)PLIN_JB * D + (size_t)PLIN_JB * (link == PLIN_LOGISTIC ? 3 : 1)) * sizeof(R);
+}
 
 template <typename R, int D>
 __global__ void __launch_bounds__(PLIN_TT)
@@ -63,6 +68,77 @@ k_plin_obs(int C, int T, int dy, int order, int ntile, double delta_h, const dou
 #pragma unroll
         for (int i = 0; i < PLIN_CG; ++i)
             if (c0 + i < C) plin_accum<R, D>(acc[i], x[i], sy + tid * PLIN_LD, sH, sc, n);
+    }
+#pragma unroll
+    for (int i = 0; i < PLIN_CG; ++i) {
+        if (!active || c0 + i >= C) continue;
+        const long long ct = (long long)(c0 + i) * T + t, off = ct * D;
+        R uu[D], yv[D], Om[symsize(D)];
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            if (eps) {
+                uu[k] = x[i][k] + shd * eps[off + k];
+                u[off + k] = uu[k];
+            } else {
+                uu[k] = u[off + k];
+            }
+        }
+        plin_finish<R, D>(acc[i], x[i], uu, delta, order, yv, Om);
+#pragma unroll
+        for (int k = 0; k < D; ++k) ys[off + k] = yv[k];
+        if (order == 2) {
+#pragma unroll
+            for (int k = 0; k < D; ++k)
+#pragma unroll
+                for (int l = 0; l < D; ++l) Rs[off * D + k * D + l] = Om[sidx(D, k, l)];
+        }
+        pot[ct] = acc[i].val;
+    }
+}
+
+// k_plin_obs under the logit link: the block's three rows of [c; s; w] staged where k_plin_obs has c, and plin_accum_logistic for plin_accum.  (One body under a
+// compile-time link, inlined into both kernels, was tried first: it moved k_plin_obs's registers -- fp32 D = 4 140 -> 134 VGPRs, six SGPRs in four of the eight.)
+template <typename R, int D>
+__global__ void __launch_bounds__(PLIN_TT)
+k_plin_obs_logistic(int C, int T, int dy, int order, int ntile, double delta_h, const double* __restrict__ dptr, const R* __restrict__ H, const R* __restrict__ csw,
+           const R* __restrict__ yobs, long long y_st, const R* __restrict__ xlin, const R* __restrict__ eps, R* __restrict__ u, R* __restrict__ ys,
+           R* __restrict__ Rs, Acc* __restrict__ pot) {
+    extern __shared__ __align__(16) unsigned char plin_smem[];
+    R* sy = reinterpret_cast<R*>(plin_smem);  // [PLIN_TT][PLIN_LD]
+    R* sH = sy + PLIN_TT * PLIN_LD;           // [PLIN_JB][D]
+    R* sc = sH + PLIN_JB * D;                 // [3][PLIN_JB]: the block's c, s and w
+    const int tid = threadIdx.x;
+    const long long t0 = (long long)(blockIdx.x % ntile) * PLIN_TT, t = t0 + tid;
+    const int c0 = (int)(blockIdx.x / ntile) * PLIN_CG;
+    const bool active = t < T;
+    const R delta = (R)(dptr ? dptr[0] : delta_h);
+    const R shd = (R)(dptr ? dptr[1] : sqrt(0.5 * delta_h));
+    R x[PLIN_CG][D];
+    PlinAcc<R, D> acc[PLIN_CG];
+#pragma unroll
+    for (int i = 0; i < PLIN_CG; ++i) {
+        plin_zero(acc[i]);
+        const bool on = active && c0 + i < C;  // (c0 + i < C is uniform over the workgroup)
+#pragma unroll
+        for (int k = 0; k < D; ++k) x[i][k] = on ? xlin[((long long)(c0 + i) * T + t) * D + k] : (R)0;
+    }
+    for (int j0 = 0; j0 < dy; j0 += PLIN_JB) {
+        const int n = dy - j0 < PLIN_JB ? dy - j0 : PLIN_JB;  // (the last block may be ragged)
+        __syncthreads();  // the block before has been read by every lane
+        for (int idx = tid; idx < PLIN_TT * PLIN_JB; idx += PLIN_TT) {  // 64 consecutive lanes fetch one row's 64 consecutive channels
+            const int row = idx / PLIN_JB, col = idx % PLIN_JB;
+            const long long tt = t0 + row;
+            sy[row * PLIN_LD + col] = (tt < T && col < n) ? yobs[tt * y_st + j0 + col] : r_nan<R>();
+        }
+        for (int idx = tid; idx < n * D; idx += PLIN_TT) sH[idx] = H[(long long)j0 * D + idx];
+        for (int idx = tid; idx < 3 * n; idx += PLIN_TT) {  // (3 n <= 192 < PLIN_TT: one pass)
+            const int q = idx / n, col = idx % n;
+            sc[q * PLIN_JB + col] = csw[(long long)q * dy + j0 + col];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < PLIN_CG; ++i)
+            if (c0 + i < C) plin_accum_logistic<R, D>(acc[i], x[i], sy + tid * PLIN_LD, sH, sc, sc + PLIN_JB, sc + 2 * PLIN_JB, n);
     }
 #pragma unroll
     for (int i = 0; i < PLIN_CG; ++i) {
@@ -163,12 +239,13 @@ template <typename R> __global__ void k_plin_totals(int n, int nseg, const Acc* 
 template <typename R, int D> int run_obs_t(auxssm_ctx* h, const PlinObsArgs& a) {
     const long long ntile = ((long long)a.T + PLIN_TT - 1) / PLIN_TT, ngroup = ((long long)a.C + PLIN_CG - 1) / PLIN_CG;
     if (ntile * ngroup > 0x7fffffffLL) {
-        set_error("Poisson-linear sweep: %lld x %lld workgroups is beyond one launch", ntile, ngroup);
+        set_error("%s sweep: %lld x %lld workgroups is beyond one launch", a.link == PLIN_LOGISTIC ? "logistic-linear" : "Poisson-linear", ntile, ngroup);
         return AUXSSM_ERR_UNSUPPORTED;
     }
-    const size_t lds = plin_lds_bytes<R>(D);
-    if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_plin_obs<R, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_plin_obs<R, D>), dim3((unsigned)(ntile * ngroup)), dim3(PLIN_TT), lds, h->stream, a.C, a.T, a.dy, a.order, (int)ntile, a.delta, a.dptr,
+    const size_t lds = plin_lds_bytes<R>(D, a.link);
+    const auto kernel = a.link == PLIN_LOGISTIC ? k_plin_obs_logistic<R, D> : k_plin_obs<R, D>;
+    if (lds > 48 * 1024) AX_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(ntile * ngroup)), dim3(PLIN_TT), lds, h->stream, a.C, a.T, a.dy, a.order, (int)ntile, a.delta, a.dptr,
                        (const R*)a.H, (const R*)a.c, (const R*)a.yobs, a.y_st, (const R*)a.xlin, (const R*)a.eps, (R*)a.u, (R*)a.ys, (R*)a.Rs, a.pot);
     AX_HIP(hipGetLastError());
     return AUXSSM_OK;

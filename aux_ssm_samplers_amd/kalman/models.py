@@ -226,6 +226,39 @@ class PoissonModel(_StateSpaceModel):
             return np.where(mask, self.yobs.astype(x.dtype) - e, 0.0), np.where(mask, e, 0.0)
 
 
+def _loading_arguments(who, ys, H, c, order, max_dx, max_dy):
+    """What the models behind a loading matrix check first: order, ys (T, dy), H (dy, dx) finite, c a finite scalar or (dy,), 1 <= dx <= max_dx, 1 <= dy <= max_dy
+    -> ys as an array, H and c (dy,) in float64; who: the class named in the messages"""
+    if order not in (1, 2):
+        raise ValueError("order must be 1 or 2")
+    ys = np.asarray(ys)
+    if ys.ndim != 2:
+        raise ValueError(f"{who}: ys must be (T, dy), got shape {ys.shape}")
+    H = np.asarray(H, np.float64)
+    if H.ndim != 2 or H.shape[0] != ys.shape[1]:
+        raise ValueError(f"{who}: H must be (dy, dx) = ({ys.shape[1]}, dx), got shape {H.shape}")
+    T, dy = ys.shape
+    dx = H.shape[1]
+    if not 1 <= dx <= max_dx:
+        raise NotImplementedError(f"{who}: dx = {dx}: the sweep covers 1 <= dx <= {max_dx}")
+    if not 1 <= dy <= max_dy:
+        raise NotImplementedError(f"{who}: dy = {dy}: the sweep covers 1 <= dy <= {max_dy}")
+    if not np.all(np.isfinite(H)):
+        raise ValueError(f"{who}: H must be finite")
+    c = np.asarray(c, np.float64)
+    if c.ndim == 0:
+        c = np.full(dy, float(c))
+    if c.shape != (dy,) or not np.all(np.isfinite(c)):
+        raise ValueError(f"{who}: c must be a finite scalar or ({dy},) vector, got shape {c.shape}")
+    return ys, H, c
+
+
+def _check_dynamics_shapes(who, model):
+    dx = model.dx
+    if model.m0.shape != (dx,) or model.b.shape != (dx,) or any(a.shape != (dx, dx) for a in (model.P0, model.F, model.Q)):
+        raise ValueError(f"{who}: m0, b must be ({dx},) and P0, F, Q ({dx}, {dx})")
+
+
 class PoissonLinearModel(_StateSpaceModel):
     """Poisson counts through a loading matrix (the Poisson linear dynamical system, a dynamic Poisson factor model): a low-dimensional linear-Gaussian state
     drives many count channels,
@@ -261,33 +294,12 @@ class PoissonLinearModel(_StateSpaceModel):
     MAX_DY = 1024
 
     def __init__(self, ys, H, c, m0, P0, F, Q, b, order=1):
-        if order not in (1, 2):
-            raise ValueError("order must be 1 or 2")
-        ys = np.asarray(ys)
-        if ys.ndim != 2:
-            raise ValueError(f"PoissonLinearModel: ys must be (T, dy), got shape {ys.shape}")
-        H = np.asarray(H, np.float64)
-        if H.ndim != 2 or H.shape[0] != ys.shape[1]:
-            raise ValueError(f"PoissonLinearModel: H must be (dy, dx) = ({ys.shape[1]}, dx), got shape {H.shape}")
-        T, dy = ys.shape
-        dx = H.shape[1]
-        if not 1 <= dx <= self.MAX_DX:
-            raise NotImplementedError(f"PoissonLinearModel: dx = {dx}: the sweep covers 1 <= dx <= {self.MAX_DX}")
-        if not 1 <= dy <= self.MAX_DY:
-            raise NotImplementedError(f"PoissonLinearModel: dy = {dy}: the sweep covers 1 <= dy <= {self.MAX_DY}")
-        if not np.all(np.isfinite(H)):
-            raise ValueError("PoissonLinearModel: H must be finite")
-        c = np.asarray(c, np.float64)
-        if c.ndim == 0:
-            c = np.full(dy, float(c))
-        if c.shape != (dy,) or not np.all(np.isfinite(c)):
-            raise ValueError(f"PoissonLinearModel: c must be a finite scalar or ({dy},) vector, got shape {c.shape}")
+        ys, H, c = _loading_arguments("PoissonLinearModel", ys, H, c, order, self.MAX_DX, self.MAX_DY)
         from ..csmc.models import PoissonPotential
         PoissonPotential.check_counts(ys)
-        super().__init__(ys, m0, P0, F, Q, b, order, dx=dx)
+        super().__init__(ys, m0, P0, F, Q, b, order, dx=H.shape[1])
         self.H, self.c = H, c
-        if self.m0.shape != (dx,) or self.b.shape != (dx,) or any(a.shape != (dx, dx) for a in (self.P0, self.F, self.Q)):
-            raise ValueError(f"PoissonLinearModel: m0, b must be ({dx},) and P0, F, Q ({dx}, {dx})")
+        _check_dynamics_shapes("PoissonLinearModel", self)
 
     def _terms(self, x):
         """(mask, eta, e, yy) at x (T, dx), each (T, dy)"""
@@ -408,6 +420,130 @@ class NegBinomialModel(_LogisticModel):
         rr = _logistic.negbinomial_r(ys, r, "NegBinomialModel")
         super().__init__(ys, np.asarray(ys, np.float64) + rr, m0, P0, F, Q, b, order)
         self.r = rr
+
+
+class _LogisticLinearModel(_StateSpaceModel):
+    """What BinomialLinearModel and NegBinomialLinearModel share: the logit link behind a loading matrix, PoissonLinearModel's twin.  A latent of dx <= MAX_DX = 4
+    components drives dy <= MAX_DY = 1024 channels with a SIZE m_{t,j} = s_j + w_j yy_{t,j} beside the data (binomial: s = trials, w = 0; negative binomial:
+    s = r, w = 1).  With mask = isfinite(y), eta_t = H x_t + c, yy = where(mask, y, 0), e = exp(-|eta|), r = 1 / (1 + e), sigma = where(eta >= 0, r, e r) and
+    s1 = (e r) r = sigma (1 - sigma) (never a subtraction):
+
+        log g_t = sum_j mask (yy eta - m (max(eta, 0) + log1p(e)))      grad_t = H' (mask (yy - m sigma))  (dx)      Lam_t = H' diag(mask m s1) H = -hess  (dx x dx, PSD)
+
+        dynamics_factory(x)           -> m0, P0, tile(F), tile(Q), tile(b)
+        observations_factory(x, u, d) -> order 1: ys = u + d/2 grad,                                            H_obs = I, R = d/2 I, c_obs = 0
+                                         order 2: Om = sym((Lam + 2/d I)^-1), ys = Om (2u/d + grad + Lam x),    H_obs = I, R = Om,    c_obs = 0
+        log_likelihood_fn(x)          -> prior_logpdf(x) + sum_t log g_t
+
+    These are _LogisticModel's formulas and conventions: the combinatorial constants are left out, non-integers are accepted, a NaN y_{t,j} drops that channel's
+    term alone (its size is never looked at), and everything goes through the one exp(-|eta|), so nothing overflows at any eta.  With H = I, c = 0, dy = dx the
+    models are BinomialModel / NegBinomialModel.  Lam is PSD, so order 2 is always defined.
+
+    Unlike the Poisson twin's, the curvature is bounded before any sweep: s1 <= 1/4, so Lam_t <= H' diag(m_t / 4) H at every x and
+    delta <= 4 / lambda_max(H' diag(m) H) (the largest over t: first_order_delta()) is the a-priori step size of the first order, for which delta lambda_max(Lam_t)
+    <= 1 wherever the chain is.  The second order has no such limit.
+
+    The size is per channel: a scalar or (dy,).  A (T, dy) size is refused (NotImplementedError): the factory kernel stages the step's data as an fp64 tile that
+    already takes 133 of the 160 KB of LDS, and a second staged tile would not fit beside it.
+
+    Pass the three bound methods to kalman.get_kernel: it runs the device sweep (model kind LOGISTIC_LIN_FIRST / _SECOND: both families are one device kind) on
+    host states (T, dx) or (C, T, dx), or on resident DeviceChains(handle, x (C, T, dx), chain_minor=False): the dense layout only.  The same methods are NumPy
+    factories for the host path and the oracle."""
+    KMODELS = (_lib.KMODEL_LOGISTIC_LIN_FIRST, _lib.KMODEL_LOGISTIC_LIN_SECOND)
+    dense_only = True
+    MAX_DX = 4
+    MAX_DY = 1024
+
+    def __init__(self, who, ys, H, c, s, w, m0, P0, F, Q, b, order):
+        super().__init__(ys, m0, P0, F, Q, b, order, dx=H.shape[1])
+        self.H, self.c = H, c
+        self.size_s, self.size_w = np.asarray(s, np.float64), np.full(self.p_obs, float(w))
+        _check_dynamics_shapes(who, self)
+
+    @staticmethod
+    def _per_channel(who, name, ys, a):
+        """the (T, dy) form refused with its reason, before the shared data rules see the parameter"""
+        if np.ndim(a) == 2:
+            raise NotImplementedError(f"{who}: {name} must be a scalar or ({np.shape(ys)[1]},), one per channel: a (T, dy) size is not covered -- the factory "
+                                      f"kernel stages the step's data as an fp64 tile that already takes 133 of the 160 KB of LDS, and a second staged tile "
+                                      f"would not fit beside it")
+
+    @property
+    def size(self):
+        """m (T, dy) = s + w yy (yy = 0 where y is missing: the size there is never looked at)"""
+        return self.size_s + self.size_w * np.where(np.isfinite(self.yobs), self.yobs, 0.0)
+
+    def first_order_delta(self):
+        """4 / max_t lambda_max(H' diag(m_t) H): the a-priori step size of the first order (Lam_t <= H' diag(m_t / 4) H at every x)"""
+        m = np.where(np.isfinite(self.yobs), self.size, 0.0)
+        lam = np.einsum("tj,jk,jl->tkl", m, self.H, self.H)
+        return 4.0 / float(np.max(np.linalg.eigvalsh(0.5 * (lam + np.swapaxes(lam, -1, -2)))))
+
+    def _terms(self, x):
+        """(mask, eta, yy, m, e, r) at x (T, dx), each (T, dy), m = 0 where y is missing"""
+        x = np.asarray(x)
+        eta = x @ self.H.astype(x.dtype).T + self.c.astype(x.dtype)
+        mask = np.isfinite(self.yobs)
+        yy = np.where(mask, self.yobs, 0.0).astype(x.dtype)
+        with np.errstate(invalid="ignore"):
+            m = np.where(mask, self.size_s.astype(x.dtype) + self.size_w.astype(x.dtype) * yy, 0.0).astype(x.dtype)
+        e = np.exp(-np.abs(eta))
+        return mask, eta, yy, m, e, 1.0 / (1.0 + e)
+
+    def log_potential(self, x):
+        _, eta, yy, m, e, _ = self._terms(x)
+        return float(np.sum(yy * eta - m * (np.maximum(eta, 0.0) + np.log1p(e))))
+
+    def grad_lam(self, x):
+        """(grad (T, dx), Lam (T, dx, dx)) of log g: H' (yy - m sigma) and H' diag(m sigma (1 - sigma)) H"""
+        _, eta, yy, m, e, r = self._terms(x)
+        H = self.H.astype(e.dtype)
+        lam = np.einsum("tj,jk,jl->tkl", m * ((e * r) * r), H, H)
+        return (yy - m * np.where(eta >= 0, r, e * r)) @ H, 0.5 * (lam + np.swapaxes(lam, -1, -2))   # (symmetric to the last bit)
+
+    def _upload(self, handle, dtype):
+        dl = super()._upload(handle, dtype)
+        # include/auxssm.h, LOGISTIC_LIN_FIRST / _SECOND: the loading matrix (dy, dx) row-major rides in the Hs slot, [c; s; w] (3, dy) in the cs slot
+        for name, a in (("Hs", self.H), ("cs", np.stack([self.c, self.size_s, self.size_w]))):
+            buf = dl.bufs["llin_" + name] = handle.to_device(np.ascontiguousarray(a, np.float64), dtype)
+            setattr(dl.c, name, buf.arr(0, 0, 0))
+        return dl
+
+
+class BinomialLinearModel(_LogisticLinearModel):
+    """Binomial channels through a loading matrix: a low-dimensional linear-Gaussian state drives many binary or binomial channels,
+
+        x_0 ~ N(m0, P0),   x_{t+1} = F x_t + b + N(0, Q),   y_{t,j} ~ Binomial(trials_j, sigma(h_j' x_t + c_j)),   j = 1..dy,
+
+    (spike / no-spike bins of many neurons on a few latents, item-response panels, multi-site presence / absence: binary data is trials = 1).  ys (T, dy):
+    successes, NaN = missing; trials: a scalar or (dy,), > 0; H (dy, dx) dense and finite; c (dy,) or a scalar; the dynamics arguments are SVModel's;
+    1 <= dx <= 4, 1 <= dy <= 1024.  The potential, the factories, the conventions and the a-priori first-order step size delta <= 4 / lambda_max(H' diag(trials) H)
+    are _LogisticLinearModel's with m = trials; the data rules are BinomialModel's (a finite y outside [0, trials], trials <= 0 or a (T, dy) trials are refused).
+    With H = I, c = 0, dy = dx the model is BinomialModel."""
+
+    def __init__(self, ys, trials, H, c, m0, P0, F, Q, b, order=1):
+        who = "BinomialLinearModel"
+        ys, H, c = _loading_arguments(who, ys, H, c, order, self.MAX_DX, self.MAX_DY)
+        self._per_channel(who, "trials", ys, trials)
+        n = _logistic.binomial_size(ys, trials, who)
+        super().__init__(who, ys, H, c, n[0], 0.0, m0, P0, F, Q, b, order)
+        self.trials = n[0]
+
+
+class NegBinomialLinearModel(_LogisticLinearModel):
+    """Overdispersed counts through a loading matrix:  y_{t,j} ~ NB(r_j, p = sigma(h_j' x_t + c_j)),  mean r_j e^eta and variance mean (1 + e^eta), on the
+    dynamics of BinomialLinearModel.  ys (T, dy): counts >= 0, NaN = missing; r: a scalar or (dy,), > 0.  The potential, the factories and the conventions are
+    _LogisticLinearModel's with m = y + r (so the a-priori first-order step size is delta <= 4 / max_t lambda_max(H' diag(y_t + r) H)); the data rules are
+    NegBinomialModel's (a finite negative count, r <= 0 or a (T, dy) r are refused).  The log-mean of channel j is eta_j + log r_j: a log-mean parametrisation
+    or an exposure is a shift of c.  With H = I, c = 0, dy = dx the model is NegBinomialModel."""
+
+    def __init__(self, ys, r, H, c, m0, P0, F, Q, b, order=1):
+        who = "NegBinomialLinearModel"
+        ys, H, c = _loading_arguments(who, ys, H, c, order, self.MAX_DX, self.MAX_DY)
+        self._per_channel(who, "r", ys, r)
+        rr = _logistic.negbinomial_r(ys, r, who)
+        super().__init__(who, ys, H, c, rr[0], 1.0, m0, P0, F, Q, b, order)
+        self.r = rr[0]
 
 
 class LorenzModel(_BuiltinModel):

@@ -198,6 +198,37 @@ def poisson_lin_setup(T, dx, dy, seed=0, order=1):
     return PoissonLinearModel(y, H, c, m0, P0, F, Q, b, order=order), x, H, c
 
 
+def logistic_lin_setup(T, dx, dy, family="binomial", seed=0, order=1):
+    """Binomial or negative-binomial channels through a loading matrix: poisson_lin_setup's latent (the same F, m0 = b = 0, Q = 0.04 I, P0 = 0.2 I) and loading
+    matrix H = N(0, 1) / sqrt(dx) with entries of magnitude below 0.1 set to 0.1; the offsets are log-odds, c ~ U(-1, 1).  family "binomial": trials per channel
+    drawn from 1 .. 40, channel 0 binary (trials = 1), y ~ Binomial(trials, sigma(eta)); "negbinomial": r = 3, y ~ NB(3, p = sigma(eta)) (mean 3 e^eta), drawn
+    as a Gamma-Poisson mixture.
+    Returns (model, x0, H, c, par): a kalman.BinomialLinearModel or kalman.NegBinomialLinearModel, a start state (T, dx) -- the simulated latent path --, the
+    loading matrix, the offsets and the family's parameter -- the trials (dy,), or r = 3.0."""
+    from aux_ssm_samplers_amd.kalman import BinomialLinearModel, NegBinomialLinearModel
+    if family not in ("binomial", "negbinomial"):
+        raise ValueError(f"family must be 'binomial' or 'negbinomial', got {family!r}")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    F = 0.9 * np.eye(dx) + 0.05 * np.eye(dx, k=1) - 0.05 * np.eye(dx, k=-1)
+    m0, b = np.zeros(dx), np.zeros(dx)
+    Q, P0 = 0.04 * np.eye(dx), 0.2 * np.eye(dx)
+    H = rng.standard_normal((dy, dx)) / np.sqrt(dx)
+    H = np.where(np.abs(H) < 0.1, 0.1, H)
+    c = 2.0 * rng.random(dy) - 1.0
+    x = np.zeros((T, dx))
+    x[0] = np.sqrt(0.2) * rng.standard_normal(dx)
+    for t in range(1, T):
+        x[t] = F @ x[t - 1] + 0.2 * rng.standard_normal(dx)
+    eta = x @ H.T + c
+    if family == "binomial":
+        par = rng.integers(1, 41, size=dy).astype(np.float64)
+        par[0] = 1.0
+        y = rng.binomial(np.broadcast_to(par, eta.shape).astype(np.int64), 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
+        return BinomialLinearModel(y, par, H, c, m0, P0, F, Q, b, order=order), x, H, c, par
+    y = rng.poisson(rng.gamma(3.0, np.exp(eta))).astype(np.float64)
+    return NegBinomialLinearModel(y, 3.0, H, c, m0, P0, F, Q, b, order=order), x, H, c, 3.0
+
+
 def lorenz_kalman_setup(T, every=8, dt=0.01, seed=0):
     """examples/lorenz: theta = (10, 28, 8/3), sigma_x = 3, m0 = (1.5, -1.5, 25), P0 = diag(400, 20, 20), (x2, x3) observed every `every`-th
     step with variance 5, NaN rows (ys AND Hs, as model.py:43-56) elsewhere."""

@@ -256,7 +256,19 @@ typedef enum {
      * 0 <= y <= m is not checked here.  Evaluated through exp(-|x|): nothing overflows at any x.  auxssm_kalman_sweep, _dd and _keyed run them;
      * auxssm_kalman_sweep_fused refuses them. */
     AUXSSM_KMODEL_LOGISTIC_FIRST = 13,
-    AUXSSM_KMODEL_LOGISTIC_SECOND = 14
+    AUXSSM_KMODEL_LOGISTIC_SECOND = 14,
+    /* Binomial and negative-binomial channels through a loading matrix: POISSON_LIN_* under the logit link of LOGISTIC_*.  With eta = H x_t + c,
+     * yy = y where it is finite and 0 where it is NaN, the SIZE m_{t,j} = s_j + w_j yy_{t,j} (binomial: s = trials, w = 0; negative binomial y ~ NB(r, p = sigma(eta)):
+     * s = r, w = 1 -- one kind, no branch), e = exp(-|eta|), r = 1 / (1 + e), sigma = eta >= 0 ? r : e r, and every term of a NaN y_{t,j} dropped whatever its
+     * size is: log g_t = sum_j yy_j eta_j - m_j (max(eta_j, 0) + log1p(e_j)) (the combinatorial constants left out), grad = H' (yy - m sigma),
+     * Lam = -hess = H' diag(m (e r) r) H (symmetric PSD, and Lam <= H' diag(m / 4) H at every x: d <= 4 / lambda_max(H' diag(m) H) is the first order's a-priori
+     * step size).  The factories, log_likelihood_fn, the limits (dims->dx <= 4, dims->dy <= 1024, dense layout only: anything else AUXSSM_ERR_UNSUPPORTED), the
+     * entries that run them and the fused entry's refusal are POISSON_LIN_*'s.  `model`: m0, P0, Fs, Qs, bs as usual; Hs.ptr -> H (dy, dx) row-major and
+     * cs.ptr -> [c; s; w] (3, dy) row-major, both DEVICE arrays of `dtype`, time-invariant and chain-shared (strides ignored; Rs unused; a NULL Hs / cs / yobs:
+     * AUXSSM_ERR_ARG, nothing enqueued).  yobs (T, dy) with NaN = missing; 0 <= y (<= trials) and s > 0 are not checked here.  Nothing overflows at any eta.
+     * (csrc/kalman_plin.hip::k_plin_obs_logistic: one exponential, one reciprocal and one logarithm per chain, step and channel.) */
+    AUXSSM_KMODEL_LOGISTIC_LIN_FIRST = 15,
+    AUXSSM_KMODEL_LOGISTIC_LIN_SECOND = 16
 } auxssm_kalman_model;
 typedef enum { AUXSSM_LAYOUT_DENSE = 0, AUXSSM_LAYOUT_CHAIN_MINOR = 1 } auxssm_layout;
 int auxssm_kalman_sweep(auxssm_handle h, int dtype, int model_kind, const auxssm_dims* dims,

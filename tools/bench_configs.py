@@ -20,6 +20,8 @@
    poisson_lin_kalman  Poisson counts through a loading matrix under the auxiliary Kalman sampler (kalman.PoissonLinearModel, T = 16384, dx = 4, dy = 128, fp32, both
              orders) at 1 / 64 / 256 dense resident chains, beside kalman.PoissonModel at T = 16384, dx = 4 on dense chains and the host-factory path of the new
              model; then the library's kernel-group times of one sweep.  poisson_lin_trace: a few sweeps alone, for a kernel trace taken from outside
+   logistic_lin_kalman  binomial / negative-binomial channels through a loading matrix (kalman.BinomialLinearModel / NegBinomialLinearModel), poisson_lin_kalman's
+             shape and protocol, beside PoissonLinearModel in the same process; then the library's kernel-group times of one sweep of either new model
    pit30  the reference's SV experiment at its defaults (--parallel, D = 30, N = 25, T = 250): the parallel-in-time sweep beside the sequential wide sweep, 1 / 16 / 256 chains
    smoother  the RTS smoother (auxssm_kalman_smooth) beside the pathwise sampler (auxssm_kalman_sample) on the same resident filtered moments: C2's model at
              T = 65536, d = 4, fp64, 1 and 256 sequences, and T = 16384, d = 3, fp32, 64 sequences; parallel scan, at one sequence also the sequential recursion
@@ -791,6 +793,69 @@ def poisson_lin_trace(T=16384, dx=4, dy=128, chains=64, sweeps=20):
                               exp_per_sweep=2 * chains * T * dy, accept=float(ch.accepted.to_host().mean()))), flush=True)
 
 
+def logistic_lin_kalman(T=16384, dx=4, dy=128, chain_counts=(1, 64, 256), runs=5, host_reps=3, prof_sweeps=10):
+    """Binomial and negative-binomial channels through a loading matrix (kalman.BinomialLinearModel / NegBinomialLinearModel on workloads.logistic_lin_setup), fp32,
+    both orders, dense resident chains, keyed noise, each at its a-priori first-order step size 4 / max_t lambda_max(H' diag(m_t) H) -- poisson_lin_kalman's
+    protocol.  Beside every row, in the same process and in alternating batches (a batch is as many back-to-back sweeps as fill ~0.2 s and ends in a stream
+    synchronisation; best, median and worst batch of `runs`): kalman.PoissonLinearModel at the same T, dx, dy and its own step size -- the same sweep with the
+    Poisson channel body.  Per order the host-factory path of the binomial model (the same methods behind lambdas, one chain).  Then `prof_sweeps` sweeps of
+    either new model per chain count under the library's own event brackets (auxssm_prof_enable, all groups): `factory` is the two launches of
+    k_plin_obs_logistic and nothing else; channel_evals_per_s = 2 C T dy channel bodies (one exp, one reciprocal, one log each) per sweep over the factory time."""
+    from aux_ssm_samplers_amd.workloads import logistic_lin_setup
+    h = _lib.default_handle()
+    names = ("BinomialLinear", "NegBinomialLinear", "PoissonLinear")
+    for order in (1, 2):
+        models, xs, deltas = [], [], []
+        for family in ("binomial", "negbinomial"):
+            m, x = logistic_lin_setup(T, dx, dy, family, order=order)[:2]
+            models.append(m), xs.append(x), deltas.append(m.first_order_delta())
+        pm, xp, pdelta = _poisson_lin_models(T, dx, dy, order)
+        models.append(pm), xs.append(xp), deltas.append(pdelta)
+        kernels = [get_kernel(m.dynamics_factory, m.observations_factory, m.log_likelihood_fn, True)[1] for m in models]
+        for C_ in chain_counts:
+            chs = [DeviceChains(h, np.repeat(x[None], C_, axis=0).astype(np.float32), chain_minor=False) for x in xs]
+            states = [KalmanSampler(x=c, updated=None) for c in chs]
+            count = [0]
+
+            def sweep(k):
+                count[0] += 1
+                kernels[k](R.PRNGKey(count[0]), states[k], deltas[k])
+
+            ts = alternating_batches(h, [lambda: sweep(0), lambda: sweep(1), lambda: sweep(2)], runs)
+            g_ms, share, rate = {}, {}, {}
+            for k in (0, 1):
+                h.prof_enable(_lib.K_ALL, 64 * prof_sweeps)
+                for _ in range(prof_sweeps):
+                    sweep(k)
+                h.sync()
+                groups = h.prof_read_groups()
+                h.prof_disable()
+                g_ms[names[k]] = {n: round(v[1] / prof_sweeps, 4) for n, v in groups.items()}
+                total, fac = sum(g_ms[names[k]].values()), g_ms[names[k]].get("factory", 0.0)
+                share[names[k]] = round(fac / total, 3) if total else None
+                rate[names[k]] = round(2.0 * C_ * T * dy / (fac * 1e-3), 1) if fac else None
+            print(json.dumps(dict(config=f"logistic_lin_kalman T={T} dx={dx} dy={dy}, aux-Kalman order {order}, fp32, dense layout, resident chains", chains=C_,
+                                  delta={n: round(d, 6) for n, d in zip(names, deltas)}, ms_per_sweep={n: round(t[0], 4) for n, t in zip(names, ts)},
+                                  ms_per_sweep_median={n: round(t[1], 4) for n, t in zip(names, ts)}, ms_per_sweep_worst={n: round(t[2], 4) for n, t in zip(names, ts)},
+                                  sweeps_per_s={n: round(C_ / t[0] * 1e3, 1) for n, t in zip(names, ts)},
+                                  time_over_poisson_linear={n: round(t[0] / ts[2][0], 3) for n, t in zip(names[:2], ts)},
+                                  accept={n: float(c.accepted.to_host().mean()) for n, c in zip(names, chs)}, group_ms_per_sweep=g_ms,
+                                  factory_share_of_groups=share, channel_evals_per_s=rate)), flush=True)
+            del chs, states
+        bm, xb, bdelta = models[0], xs[0], deltas[0]
+        hinit, hkernel = get_kernel(lambda x: bm.dynamics_factory(x), lambda x, u, dl: bm.observations_factory(x, u, dl), lambda x: bm.log_likelihood_fn(x), True)
+        st = hinit(xb.astype(np.float32))
+        keys = R.split(R.PRNGKey(3), host_reps + 1)
+        st = hkernel(keys[0], st, bdelta)
+        h.sync()
+        t0 = time.perf_counter()
+        for k in range(host_reps):
+            st = hkernel(keys[1 + k], st, bdelta)
+        h.sync()
+        print(json.dumps(dict(config=f"logistic_lin_kalman T={T} dx={dx} dy={dy}, aux-Kalman order {order}, fp32, binomial, host-factory path", chains=1,
+                              delta=round(bdelta, 6), ms_per_sweep=round((time.perf_counter() - t0) / host_reps * 1e3, 2))), flush=True)
+
+
 def smoother(runs=5):
     """auxssm_kalman_smooth beside auxssm_kalman_sample of the same process on the same resident (ms, Ps): the filter runs once on the device (chain-shared model and
     data, dense layout), then the two entry points are timed in alternating batches of back-to-back calls (~0.2 s each, `runs` per entry point) that end in a stream synchronisation; best and
@@ -863,6 +928,8 @@ if __name__ == "__main__":
         poisson_lin_kalman()
     if "poisson_lin_trace" in which:
         poisson_lin_trace()
+    if "logistic_lin_kalman" in which:
+        logistic_lin_kalman()
     if "sv30" in which:
         sv30()
     if "guided" in which:
