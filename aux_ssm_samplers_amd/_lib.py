@@ -74,6 +74,11 @@ NOISE_EXPLICIT, NOISE_THREEFRY = 0, 1
 GRAD_NONE, GRAD_REFERENCE, GRAD_EXACT = 0, 1, 2
 
 
+class MniwPrior(C.Structure):
+    """auxssm_mniw_prior: the (dx, dx + 1), (dx + 1, dx + 1), (dx, dx) matrices row-major in the leading entries of their arrays"""
+    _fields_ = [("M0", C.c_double * 20), ("K0", C.c_double * 25), ("nu0", C.c_double), ("Psi0", C.c_double * 16), ("chi_scale", C.c_double)]
+
+
 class Dims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("C", "T", "B", "dx", "dy")]
 
@@ -144,6 +149,10 @@ def load():
         "auxssm_rng_jax": ([vp, i32, i32, i64, i64, vp, dbl, dbl, vp, i64, i64], C.c_int),
         "auxssm_rng_normal": ([vp, i32, u32, u32, u32, i64, vp], C.c_int),
         "auxssm_rng_uniform": ([vp, i32, u32, u32, u32, i64, vp], C.c_int),
+        "auxssm_rng_gamma": ([vp, i32, u32, u32, u32, i64, C.c_int32, P(dbl), vp], C.c_int),
+        "auxssm_dynamics_stats": ([vp, i32, C.c_int32, C.c_int32, C.c_int32, i32, vp, vp], C.c_int),
+        "auxssm_dynamics_theta_update": ([vp, i32, C.c_int32, C.c_int32, C.c_int32, i32, vp, P(MniwPrior), vp, vp, vp, P(Arr), P(Arr), P(Arr), vp, vp],
+                                         C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the .so does not export what include/auxssm.h declares
@@ -292,6 +301,35 @@ class Handle:
             Cn, T, _ = x.shape
         check(self.lib.auxssm_lorenz_theta_update(self.h, dtype_code(x.dtype), Cn, T, int(layout), x.ptr, float(sigma_theta), float(sigma_x),
                                                   eps.ptr, par.ptr, mean_chol.ptr if mean_chol is not None else None))
+
+    # ---- theta | x for linear-Gaussian dynamics (include/auxssm.h: the conjugate step on (F, b, Q)) ----
+    @staticmethod
+    def _state_dims(x, layout):
+        if layout == LAYOUT_CHAIN_MINOR:
+            T, d, Cn = x.shape
+        else:
+            Cn, T, d = x.shape
+        return Cn, T, d
+
+    def dynamics_stats(self, x, layout=LAYOUT_DENSE):
+        """x (C, T, dx) [dense] or (T, dx, C) [chain-minor] DeviceArray -> (C, n n + dx n + dx dx) float64 DeviceArray [S_zz | S_xz | S_xx], n = dx + 1"""
+        Cn, T, d = self._state_dims(x, layout)
+        out = self.empty((Cn, (d + 1) * (d + 1) + d * (d + 1) + d * d), np.float64)
+        check(self.lib.auxssm_dynamics_stats(self.h, dtype_code(x.dtype), Cn, T, d, int(layout), x.ptr, out.ptr))
+        return out
+
+    def dynamics_theta_update(self, x, prior, chi, eps_w, eps_a, F, b, Q, flags, post_out=None, layout=LAYOUT_DENSE):
+        """prior a MniwPrior; chi (C, dx), eps_w (C, dx, dx), eps_a (C, dx, dx + 1) DeviceArrays of x's dtype; F, b, Q: Arr descriptors of the model's
+        per-chain dynamics (time stride 0); flags (C,) int32; post_out (C, dx n + n n + 1 + dx dx) float64 or None"""
+        Cn, T, d = self._state_dims(x, layout)
+        check(self.lib.auxssm_dynamics_theta_update(self.h, dtype_code(x.dtype), Cn, T, d, int(layout), x.ptr, C.byref(prior), chi.ptr, eps_w.ptr, eps_a.ptr,
+                                                    C.byref(F), C.byref(b), C.byref(Q), post_out.ptr if post_out is not None else None, flags.ptr))
+
+    def rng_gamma_into(self, key, stream, shapes, out):
+        """out (n, m) <- Gamma(shapes[i], 1), m = len(shapes) <= 8 host doubles"""
+        sh = (C.c_double * len(shapes))(*[float(s) for s in shapes])
+        check(self.lib.auxssm_rng_gamma(self.h, dtype_code(out.dtype), int(key[0]), int(key[1]), int(stream), out.size // max(len(shapes), 1), len(shapes), sh,
+                                        out.ptr))
 
     # ---- RNG fill ----
     def rng_normal(self, key, stream, shape, dtype):

@@ -56,10 +56,155 @@ class LorenzThetaStep:
         return self.model.par_device(chains.handle, chains.dtype, chains.C).to_host()[:, :3]
 
 
+class MNIWPrior:
+    """The conjugate prior of linear-Gaussian dynamics x_{t+1} = F x_t + b + N(0, Q), with A = [F b] (d, d + 1):
+        Q ~ IW(nu0, Psi0),   A | Q ~ MN(M0, Q, K0^-1)
+    M0 (d, d + 1), K0 (d + 1, d + 1) symmetric positive definite (a precision: the rows of A have covariance K0^-1 up to Q), nu0 > d - 1, Psi0 (d, d)
+    symmetric positive definite.  Validated here, so that a DynamicsThetaStep never meets an inadmissible prior on the device."""
+
+    def __init__(self, M0, K0, nu0, Psi0):
+        M0, K0, Psi0 = (np.array(a, np.float64, ndmin=2) for a in (M0, K0, Psi0))
+        d = Psi0.shape[0]
+        if Psi0.shape != (d, d) or M0.shape != (d, d + 1) or K0.shape != (d + 1, d + 1):
+            raise ValueError(f"MNIWPrior: need M0 (d, d + 1), K0 (d + 1, d + 1), Psi0 (d, d); got {M0.shape}, {K0.shape}, {Psi0.shape}")
+        nu0 = float(nu0)
+        if not (np.all(np.isfinite(M0)) and np.all(np.isfinite(K0)) and np.all(np.isfinite(Psi0)) and np.isfinite(nu0)):
+            raise ValueError("MNIWPrior: M0, K0, nu0 and Psi0 must be finite")
+        if not nu0 > d - 1:
+            raise ValueError(f"MNIWPrior: nu0 must exceed d - 1 = {d - 1} (got {nu0})")
+        for name, a in (("K0", K0), ("Psi0", Psi0)):
+            dg = np.abs(np.diag(a))
+            if not np.all(np.abs(a - a.T) <= 1e-12 * (dg[:, None] + dg[None, :])):
+                raise ValueError(f"MNIWPrior: {name} must be symmetric")
+            try:
+                np.linalg.cholesky(0.5 * (a + a.T))
+            except np.linalg.LinAlgError:
+                raise ValueError(f"MNIWPrior: {name} must be positive definite") from None
+        self.d, self.M0, self.K0, self.nu0, self.Psi0 = d, M0, 0.5 * (K0 + K0.T), nu0, 0.5 * (Psi0 + Psi0.T)
+
+    def struct(self, chi_scale=2.0):
+        """-> _lib.MniwPrior (auxssm_mniw_prior); chi_scale 2: the chi buffer holds Gamma((nu_n - i) / 2, 1) draws"""
+        if self.d > 4:
+            raise ValueError(f"the device step covers dx <= 4 (this prior has d = {self.d})")
+        p = _lib.MniwPrior()
+        for name in ("M0", "K0", "Psi0"):
+            flat = getattr(self, name).ravel()
+            arr = getattr(p, name)
+            for k, v in enumerate(flat):
+                arr[k] = float(v)
+        p.nu0, p.chi_scale = self.nu0, float(chi_scale)
+        return p
+
+
+def _time_invariant(a):
+    a = np.asarray(a)
+    return a.shape[0] <= 1 or a.strides[0] == 0 or bool(np.all(a == a[:1]))
+
+
+class DynamicsThetaStep:
+    """(F, b, Q) | x for the linear-Gaussian dynamics of a Kalman-sampler model: one conjugate matrix-normal inverse-Wishart draw per chain and sweep, on the
+    device (auxssm_dynamics_theta_update), written into per-chain parameter buffers the next sweep reads:
+
+        step = DynamicsThetaStep(model, MNIWPrior(M0, K0, nu0, Psi0));   loop(key, delta, state, kernel, None, n_iter, theta_step=step)
+
+    model: LGConcatModel, SVModel, PoissonModel, BinomialModel, NegBinomialModel, PoissonLinearModel, BinomialLinearModel or NegBinomialLinearModel with
+    time-invariant Fs / Qs / bs (a broadcast view, or equal rows) and dx <= 4.  On its first call the step replaces the device model's Fs, Qs, bs with per-chain
+    buffers (C, d, d), (C, d, d), (C, d) of time stride 0 that start as copies of the model's values (LorenzModel.par_device's pattern); from then on the model
+    serves chains of that count only (a sweep with another count is refused, kalman/generic.py::_check_per_chain_dynamics).  With per-chain parameters an LGConcatModel leaves the fused chain-shared sweep (and its memoised model stage) for the general
+    path.  x_0's prior (m0, P0) takes no part and stationarity is not imposed.  Every call: the key is split in three, chi <- auxssm_rng_gamma at shapes
+    (nu_n - i) / 2 (the update doubles them to chi-squares), the two normal buffers are filled, the update runs on chains.x in chains.layout; no host synchronisation.
+    A chain whose posterior cannot be factorised keeps its parameters and raises its flag (flags(chains)).
+    Keys: the call's key is split by random.split, which is jax.random.split under random.set_compat("jax") -- as loop() splits its own; the three fills are the
+    package's Threefry streams in either mode (the reference has no such step, so there are no jax.random draws to reproduce)."""
+
+    def __init__(self, model, prior):
+        from .kalman import models as M
+        who = type(model).__name__
+        if isinstance(model, M.LorenzModel):
+            raise ValueError("DynamicsThetaStep: LorenzModel is parameterised by its drift (theta, dt), not by (F, b, Q): use LorenzThetaStep")
+        if isinstance(model, M.MVTModel):
+            raise ValueError("DynamicsThetaStep: MVTModel holds d independent scalar dynamics (diagonal F, Q): a dense (F, b, Q) draw would leave its "
+                             "parameterisation")
+        if not isinstance(model, (M.LGConcatModel, M._StateSpaceModel)):
+            raise ValueError(f"DynamicsThetaStep: {who} is not a model with linear-Gaussian dynamics (Fs, Qs, bs) the Kalman sampler runs on the device")
+        if not isinstance(prior, MNIWPrior):
+            raise ValueError("DynamicsThetaStep: prior must be an MNIWPrior")
+        if model.dx > 4:
+            raise ValueError(f"DynamicsThetaStep: the device step covers dx <= 4 (the model has dx = {model.dx})")
+        if prior.d != model.dx:
+            raise ValueError(f"DynamicsThetaStep: the prior is for d = {prior.d}, the model has dx = {model.dx}")
+        if model.T < 2:
+            raise ValueError("DynamicsThetaStep: the model has no transition (T < 2)")
+        for name in ("Fs", "Qs", "bs"):
+            if not _time_invariant(getattr(model, name)):
+                raise ValueError(f"DynamicsThetaStep: the model's {name} varies in time; the step draws ONE (F, b, Q) per chain")
+        self.model, self.prior = model, prior
+        self._prior_c = prior.struct(2.0)
+        self._shapes = [0.5 * (prior.nu0 + model.T - 1 - i) for i in range(model.dx)]
+        self._work = {}
+
+    # ---- the model's per-chain parameter buffers ----
+    def _params(self, handle, dtype, C):
+        """-> (F (C, d, d), b (C, d), Q (C, d, d)) DeviceArrays the device model points at, made per-chain on first use"""
+        dl = self.model.device(handle, dtype)[0]
+        d = self.model.dx
+        own = dl.bufs.get("dynamics_theta")
+        if own is None:
+            host = [np.repeat(np.asarray(getattr(self.model, n))[:1], C, axis=0) for n in ("Fs", "bs", "Qs")]
+            own = dl.bufs["dynamics_theta"] = tuple(handle.to_device(a, dtype) for a in host)
+            F, b, Q = own
+            sc = 1 if C > 1 else 0
+            dl.c.Fs, dl.c.bs, dl.c.Qs = F.arr(sc * d * d, 0, 0), b.arr(sc * d, 0, 0), Q.arr(sc * d * d, 0, 0)
+            dl.bufs["Fs"], dl.bufs["bs"], dl.bufs["Qs"] = F, b, Q
+        if own[0].shape[0] != C:
+            raise ValueError(f"DynamicsThetaStep: the model holds per-chain parameters of {own[0].shape[0]} chains, the chains are {C}")
+        return own
+
+    def _check_chains(self, chains):
+        from .kalman.generic import DeviceChains
+        if not isinstance(chains, DeviceChains):
+            raise ValueError("DynamicsThetaStep: cSMC chains carry their transition parameters in the Feynman-Kac model; the step needs kalman.DeviceChains")
+        if (chains.T, chains.dx) != (self.model.T, self.model.dx):
+            raise ValueError(f"DynamicsThetaStep: the chains are (T, dx) = ({chains.T}, {chains.dx}), the model ({self.model.T}, {self.model.dx})")
+
+    def __call__(self, key, chains):
+        self._check_chains(chains)
+        handle, dtype, Cn, d = chains.handle, chains.dtype, chains.C, self.model.dx
+        F, b, Q = self._params(handle, dtype, Cn)
+        wk = (id(handle), np.dtype(dtype).str, Cn)
+        work = self._work.get(wk)
+        if work is None:
+            self._work.clear()
+            work = self._work[wk] = (handle.empty((Cn, d), dtype), handle.empty((Cn, d, d), dtype), handle.empty((Cn, d, d + 1), dtype),
+                                     handle.zeros((Cn,), np.int32))
+        chi, eps_w, eps_a, flags = work
+        chains.disable_fused()   # per-chain parameters: the fused chain-shared sweep no longer applies
+        k_chi, k_w, k_a = _random.split(key, 3)
+        handle.rng_gamma_into(k_chi, 0, self._shapes, chi)
+        handle.rng_normal_into(k_w, 0, eps_w)
+        handle.rng_normal_into(k_a, 0, eps_a)
+        sc = 1 if Cn > 1 else 0
+        handle.dynamics_theta_update(chains.x, self._prior_c, chi, eps_w, eps_a, F.arr(sc * d * d, 0, 0), b.arr(sc * d, 0, 0), Q.arr(sc * d * d, 0, 0), flags,
+                                     layout=chains.layout)
+
+    def params(self, chains):
+        """-> (F (C, d, d), b (C, d), Q (C, d, d)) as host arrays (synchronises)"""
+        self._check_chains(chains)
+        F, b, Q = self._params(chains.handle, chains.dtype, chains.C)
+        return F.to_host(), b.to_host(), Q.to_host()
+
+    def flags(self, chains):
+        """-> (C,) int32: 0, or why the last call left chain c unchanged (include/auxssm.h: auxssm_dynamics_theta_update)"""
+        work = self._work.get((id(chains.handle), np.dtype(chains.dtype).str, chains.C))
+        return work[3].to_host() if work is not None else np.zeros(chains.C, np.int32)
+
+
 def loop(key, init_delta, init_state, kernel_fn, delta_fn, n_iter, target_alpha=None, lr=None, beta=0.01, theta_step=None,
          callback=None):
     """See module docstring.  init_state.x: DeviceChains (kernel_fn(key, state, delta) from kalman.get_kernel) or CsmcChains (from
-    csmc.get_kernel / get_independent_kernel).  theta_step: a LorenzThetaStep run after every sweep (Kalman chains).
+    csmc.get_kernel / get_independent_kernel).  theta_step: called as theta_step(key, chains) after every sweep (Kalman chains) with the second child of the sweep's key -- a LorenzThetaStep (the Lorenz drift
+    parameters) or a DynamicsThetaStep ((F, b, Q) of linear-Gaussian dynamics under an MNIWPrior: a Gibbs sampler over (x, F, b, Q)); both write the model's
+    device parameters in place, one set per chain, without a host synchronisation.
     callback(i, state) is called after every sweep (e.g. to keep thinned samples; it may synchronise).
 
     Returns (n_iter, stats, state, delta, window_avg_acceptance, avg_acceptance): stats = (sq_jump, mean, sq_mean) as DeviceArrays

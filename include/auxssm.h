@@ -623,6 +623,44 @@ int auxssm_rng_normal(auxssm_handle h, int dtype, uint32_t key0, uint32_t key1, 
  * kalman/generic.py:58); eps_aux, eps_samp (n) <- auxssm_rng_normal(key, stream 0), u_acc (nu) <- auxssm_rng_uniform(key, stream 0): the same values. */
 int auxssm_kalman_draw(auxssm_handle h, int dtype, const uint32_t* keys, int64_t n, int64_t nu, void* eps_aux, void* eps_samp, void* u_acc);
 int auxssm_rng_uniform(auxssm_handle h, int dtype, uint32_t key0, uint32_t key1, uint32_t stream, int64_t n, void* out);
+/* out (n, m), out[j, i] ~ Gamma(shapes[i], 1): Marsaglia & Tsang (2000), shape < 1 through the draw of shape + 1 times U^(1 / shape).  shapes: m <= 8 HOST
+ * doubles, positive.  Draw g = j m + i is a pure function of (key0, key1, stream, g): attempt k < 16 takes its normal from Threefry block 2 (16 g + k) of the
+ * stream (the cos branch of the fp64 Box-Muller transform, both dtypes) and its two uniforms (b + 1/2) 2^-32 from the two words of the next block; the first
+ * accepted attempt is the draw, NaN if none is (probability < 1e-20).  Arithmetic in double for both dtypes, the acceptance test on csrc/det_math.h's
+ * logarithm (the same decision on a host that runs csrc/dynamics_theta.h); the result is rounded to `dtype`.  n m <= 2^42. */
+int auxssm_rng_gamma(auxssm_handle h, int dtype, uint32_t key0, uint32_t key1, uint32_t stream, int64_t n, int32_t m, const double* shapes, void* out);
+
+/* ---- theta | x for linear-Gaussian dynamics x_{t+1} = F x_t + b + N(0, Q): the conjugate step on (F, b, Q) (csrc/dynamics_theta.hip) -----------------
+ * With z_t = [x_t; 1] (n = dx + 1), A = [F b] (dx x n) and the T - 1 transitions of each chain (x_0's prior takes no part; stationarity is not imposed):
+ *   prior       Q ~ IW(nu0, Psi0),  A | Q ~ MN(M0, Q, K0^-1)        K0 (n, n), Psi0 (dx, dx) symmetric positive definite, nu0 > dx - 1
+ *   statistics  S_zz = sum z_t z_t^T,  S_xz = sum x_{t+1} z_t^T,  S_xx = sum x_{t+1} x_{t+1}^T
+ *   posterior   K_n = K0 + S_zz,  M_n = (M0 K0 + S_xz) K_n^-1,  nu_n = nu0 + T - 1,  Psi_n = sym(Psi0 + S_xx + M0 K0 M0^T - M_n K_n M_n^T)
+ *   draw        L = chol(Psi_n), U = chol(K_n), B lower triangular with B_ii = sqrt(chi_scale chi[c, i]), B_ij = eps_w[c, i, j] (i > j):
+ *               Q = L B^-T B^-1 L^T (symmetric bit for bit),  A = M_n + chol(Q) eps_a[c] U^-1
+ * x: the resident state, (C, T, dx) [AUXSSM_LAYOUT_DENSE] or (T, dx, C) [AUXSSM_LAYOUT_CHAIN_MINOR] of `dtype`; dx <= 4, T >= 2.  Products and sums are formed
+ * in double whatever `dtype`; a chain's sums are added in an order that depends on T and the layout alone (segments of the time axis in ascending order, no
+ * atomics), so a chain's result is the same alone and inside any batch.
+ * auxssm_dynamics_stats: stats_out (C, n n + dx n + dx dx) DEVICE doubles, per chain [S_zz (n, n) | S_xz (dx, n) | S_xx (dx, dx)], each row-major.
+ * auxssm_dynamics_theta_update: the noise is explicit -- chi (C, dx) with chi_scale chi[c, i] ~ chi^2(nu_n - i), eps_w (C, dx, dx) (the strict lower triangle
+ *   is read) and eps_a (C, dx, n) ~ N(0, 1), DEVICE arrays of `dtype`.  F, b, Q: where chain c's (dx, dx), (dx), (dx, dx) are written, rounded to `dtype`, at
+ *   ptr + c * chain stride (time stride 0: time-invariant dynamics; with C > 1 the chain strides must keep the chains apart) -- the arrays model->Fs / bs / Qs of
+ *   the next sweep point at.  post_out (C, dx n + n n + 1 + dx dx) DEVICE doubles [M_n | K_n | nu_n | Psi_n], may be NULL.  flags (C) DEVICE int32: 0, or why
+ *   chain c was left UNCHANGED -- 1 chol(K_n) failed, 2 chol(Psi_n) failed (or Psi_n's diagonal is rounding noise of the terms it is the difference of),
+ *   3 a chi that is not positive and finite, 4 chol(Q) failed or a result is not finite in `dtype`.  A pivot below 2^-46 of its diagonal entry counts as failed.
+ *   Nothing non-finite is ever written into F, b, Q.
+ * Refused before anything is enqueued: dx > 4 (AUXSSM_ERR_UNSUPPORTED), T < 2, NULL arguments, a prior that is not finite, symmetric, positive definite or has
+ * nu0 <= dx - 1, and what one launch cannot hold: C x ceil((T - 1) / 512) > 2^31 - 1, or, chain-minor, C > 65535 x 64 = 4194240 chains. */
+typedef struct auxssm_mniw_prior {
+    double M0[20];    /* (dx, dx + 1) row-major in the leading entries */
+    double K0[25];    /* (dx + 1, dx + 1) row-major in the leading entries */
+    double nu0;
+    double Psi0[16];  /* (dx, dx) row-major in the leading entries */
+    double chi_scale; /* 1: chi holds chi-square draws; 2: chi holds Gamma((nu_n - i) / 2, 1) draws as auxssm_rng_gamma writes them */
+} auxssm_mniw_prior;
+int auxssm_dynamics_stats(auxssm_handle h, int dtype, int32_t C, int32_t T, int32_t dx, int layout, const void* x, double* stats_out);
+int auxssm_dynamics_theta_update(auxssm_handle h, int dtype, int32_t C, int32_t T, int32_t dx, int layout, const void* x, const auxssm_mniw_prior* prior,
+                                 const void* chi, const void* eps_w, const void* eps_a, const auxssm_arr* F, const auxssm_arr* b, const auxssm_arr* Q,
+                                 double* post_out, int32_t* flags);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,8 @@
    pit30  the reference's SV experiment at its defaults (--parallel, D = 30, N = 25, T = 250): the parallel-in-time sweep beside the sequential wide sweep, 1 / 16 / 256 chains
    smoother  the RTS smoother (auxssm_kalman_smooth) beside the pathwise sampler (auxssm_kalman_sample) on the same resident filtered moments: C2's model at
              T = 65536, d = 4, fp64, 1 and 256 sequences, and T = 16384, d = 3, fp32, 64 sequences; parallel scan, at one sequence also the sequential recursion
+   dynamics_theta  the conjugate step on (F, b, Q) (loop.DynamicsThetaStep) beside one keyed sweep of the same LGConcatModel with per-chain parameters: C2's shape
+             (T = 65536, d = 4, fp64) at 1 / 16 / 256 chains and T = 16384, d = 1, fp32 at 1024 chains; the statistics pass alone as bytes/s beside a device copy
    loop the MCMC loop around the sweeps (aux_ssm_samplers_amd.loop: running moments, acceptance averages, adaptation, Lorenz theta step) on C2 / C3 / C4
 Prints one JSON line per measurement.  Inputs are resident in HBM (DeviceChains) where the API allows it; device Threefry noise."""
 import json
@@ -914,12 +916,67 @@ def smoother(runs=5):
             del ms, Ps, eps, xs, sms, sPs
 
 
+def dynamics_theta(runs=5):
+    """loop.DynamicsThetaStep (gamma + two normal fills + statistics, reduce and finish kernels) beside one keyed sweep of the same LGConcatModel once its dynamics
+    are per-chain (the general path: the fused chain-shared sweep no longer applies), auxssm_dynamics_stats alone, and a device-to-device copy of the state, all in
+    one process in alternating batches (alternating_batches); best batch.  stats_GBps: the state's bytes (read once) over the statistics time; copy_GBps: twice
+    the state's bytes (read + write) over the copy time -- an HBM rate only where the state exceeds the 256 MB last-level cache (the 256-chain row), a cache rate below that."""
+    import ctypes as C
+    from aux_ssm_samplers_amd.kalman import LGConcatModel
+    from aux_ssm_samplers_amd.loop import DynamicsThetaStep, MNIWPrior
+    from aux_ssm_samplers_amd.workloads import lg_model
+    h = _lib.default_handle()
+    bt = np.broadcast_to
+    for T, d, dtype, counts in ((65536, 4, np.float64, (1, 16, 256)), (16384, 1, np.float32, (1024,))):
+        m = lg_model(T, d, dtype=dtype)
+        for chains_n in counts:
+            model = LGConcatModel(m["m0"], m["P0"], bt(m["F"], (T - 1, d, d)), bt(m["Q"], (T - 1, d, d)), bt(m["b"], (T - 1, d)), bt(m["Hobs"], (T, d, d)),
+                                  bt(m["Robs"], (T, d, d)), bt(m["cobs"], (T, d)), m["y"])
+            init, kernel = get_kernel(model.dynamics_factory, model.observations_factory, model.log_likelihood_fn, True)
+            rng = np.random.default_rng(chains_n)
+            x0 = (np.asarray(m["x_true"])[None] + 0.1 * rng.standard_normal((chains_n, T, d))).astype(dtype)
+            chains = DeviceChains(h, x0, dtype)
+            del x0
+            state = init(chains)
+            prior = MNIWPrior(np.zeros((d, d + 1)), np.eye(d + 1), d + 2.0, np.eye(d))
+            step = DynamicsThetaStep(model, prior)
+            keys = R.split(R.PRNGKey(3), 4096)
+            it = [0]
+
+            def nk():
+                it[0] = (it[0] + 1) % 4096
+                return keys[it[0]]
+
+            step(nk(), chains)   # the model's dynamics become per-chain here
+            spare = h.empty(chains.x.shape, dtype)
+            stats = h.empty((chains_n, (d + 1) * (d + 1) + d * (d + 1) + d * d), np.float64)
+            code = _lib.dtype_code(dtype)
+
+            def sweep():
+                nonlocal state
+                state = kernel(nk(), state, 0.5)
+
+            def stats_only():
+                _lib.check(h.lib.auxssm_dynamics_stats(h.h, code, chains_n, T, d, chains.layout, chains.x.ptr, stats.ptr))
+
+            st, sw, ss, cp = alternating_batches(h, [lambda: step(nk(), chains), sweep, stats_only, lambda: spare.copy_from(chains.x)], runs)
+            nbytes = chains.x.nbytes
+            print(json.dumps(dict(config=f"dynamics theta step beside one keyed sweep, LGConcatModel T={T} d={d} {np.dtype(dtype).name}, per-chain (F, b, Q)",
+                                  chains=chains_n, layout="chain-minor" if chains.chain_minor else "dense", step_ms=round(st[0], 4), step_ms_median=round(st[1], 4),
+                                  sweep_ms=round(sw[0], 4), sweep_ms_median=round(sw[1], 4), step_over_sweep=round(st[0] / sw[0], 4), stats_ms=round(ss[0], 4),
+                                  stats_GBps=round(nbytes / ss[0] / 1e6, 1), copy_ms=round(cp[0], 4), copy_GBps=round(2 * nbytes / cp[0] / 1e6, 1),
+                                  flagged=int(step.flags(chains).any()))), flush=True)
+            del chains, spare, state, step, model
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["c3k", "c4", "c5"]
     if "spatial_kalman" in which:
         spatial_kalman()
     if "smoother" in which:
         smoother()
+    if "dynamics_theta" in which:
+        dynamics_theta()
     if "poisson_kalman" in which:
         poisson_kalman()
     if "logistic_kalman" in which:
