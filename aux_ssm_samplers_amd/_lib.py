@@ -153,6 +153,8 @@ def load():
         "auxssm_dynamics_stats": ([vp, i32, C.c_int32, C.c_int32, C.c_int32, i32, vp, vp], C.c_int),
         "auxssm_dynamics_theta_update": ([vp, i32, C.c_int32, C.c_int32, C.c_int32, i32, vp, P(MniwPrior), vp, vp, vp, P(Arr), P(Arr), P(Arr), vp, vp],
                                          C.c_int),
+        "auxssm_kalman_smooth_stats": ([vp, i32, P(Dims), P(Lgssm), P(Arr), vp, vp, vp, vp, vp, vp], C.c_int),
+        "auxssm_lgssm_em_mstep": ([vp, i32, C.c_int32, C.c_int32, C.c_int32, vp, P(dbl), P(MniwPrior), i32] + [P(Arr)] * 8 + [vp], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the .so does not export what include/auxssm.h declares

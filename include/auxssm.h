@@ -662,6 +662,40 @@ int auxssm_dynamics_theta_update(auxssm_handle h, int dtype, int32_t C, int32_t 
                                  const void* chi, const void* eps_w, const void* eps_a, const auxssm_arr* F, const auxssm_arr* b, const auxssm_arr* Q,
                                  double* post_out, int32_t* flags);
 
+/* ---- EM for a time-invariant linear-Gaussian state-space model: the E-step's expected sufficient statistics and the M-step (csrc/lgssm_em.hip) ------------
+ * x_0 ~ N(m0, P0), x_{t+1} = F x_t + b + N(0, Q), y_t = H x_t + c + N(0, R); z_t = [x_t; 1], n = dx + 1; dx <= 4, dy <= 8 (the narrow filter's range), T >= 2.
+ * auxssm_kalman_smooth_stats: from ys (C,T,B,dy), the filtered covariances Ps and the smoothed moments sms, sPs (dense (C,T,B,.) as auxssm_kalman_filter /
+ *   auxssm_kalman_smooth write them; ms is accepted beside them and not read) and the model's Fs, Qs (any chain or batch stride; time stride 0 on Fs, Qs, bs),
+ *   for each of the C B sequences
+ *     lag one       S_t = sym(F P_t F^T + Q), G_t = P_t F^T S_t^-1 (auxssm_kalman_smooth's gain, recomputed from P_t in double: Cholesky + two triangular solves),
+ *                   X_t = Cov[x_{t+1}, x_t | y_{0:T-1}] = sPs[t+1] G_t^T,  t = 0 .. T-2      -> cross_out (C,T-1,B,dx,dx) of `dtype`, or NULL
+ *     dynamics      S_zz = sum_{t<T-1} E[z_t z_t^T], S_xz = sum E[x_{t+1} z_t^T], S_xx = sum E[x_{t+1} x_{t+1}^T] with E[x_t x_t^T] = sPs[t] + sms[t] sms[t]^T and
+ *                   E[x_{t+1} x_t^T] = X_t + sms[t+1] sms[t]^T: auxssm_dynamics_stats' sums in expectation (S_zz[dx, dx] is the number of transitions, exactly)
+ *     observations  over the steps whose row of ys is entirely finite: So_zz = sum E[z_t z_t^T], S_yz = sum y_t E[z_t]^T
+ *   -> stats_out (C B, NS) DEVICE doubles, per sequence [S_zz (n,n) | S_xz (dx,n) | S_xx (dx,dx) | So_zz (n,n) | S_yz (dy,n) | sms[0] (dx) | sPs[0] (dx,dx)],
+ *   NS = 2 n n + dx n + dx dx + dy n + dx + dx dx.  Products and sums in double whatever `dtype`; a sequence's sums are added in an order that depends on T
+ *   alone (lanes over 512-transition segments, a fixed tree inside the workgroup, the segments in ascending order; no atomics): the same bits alone and in a batch.
+ *   A step whose S_t cannot be factorised (auxssm_dynamics_theta_update's pivot rule) puts NaN into its X_t and the sums it enters, which the M-step refuses.
+ *   Refused before anything is enqueued: NULL arguments, dx > 4 or dy > 8 (AUXSSM_ERR_UNSUPPORTED), T < 2, a time stride other than 0 on Fs, Qs, bs, outputs
+ *   overlapping inputs or each other, C B ceil((T-1)/512) > 2^31 - 1.
+ * auxssm_lgssm_em_mstep: one small launch.  stats (nseq, NS) as above, added over the sequences in ascending order; syy_nobs: dy dy + 1 HOST doubles
+ *   [S_yy = sum y_t y_t^T over the observed steps of all sequences | n_obs, their number]; prior NULL (maximum likelihood) or the matrix-normal inverse-Wishart
+ *   prior of the dynamics (its chi_scale is not read).  update_mask: 1 dynamics, 2 observations, 4 initial state.
+ *     dynamics      [F b] = S_xz S_zz^-1, Q = sym(S_xx - [F b] S_xz^T) / N_tr;  with a prior the joint mode of auxssm_dynamics_theta_update's posterior:
+ *                   [F b] = M_n, Q = Psi_n / (nu_n + dx + n + 1)
+ *     observations  [H c] = S_yz So_zz^-1, R = sym(S_yy - [H c] S_yz^T) / n_obs
+ *     initial state m0 = mean_s sms_s[0], P0 = mean_s [sPs_s[0] + (sms_s[0] - m0)(sms_s[0] - m0)^T]
+ *   Cholesky and triangular solves, no inverse; Q, R, P0 symmetric bit for bit.  F .. P0: where the parameters are written, rounded to `dtype` (->ptr; time stride
+ *   0; arrays of blocks outside update_mask may be NULL) -- the arrays the next auxssm_kalman_filter reads.  flags: 4 DEVICE int32 [dynamics, observations,
+ *   initial state, reserved = 0]: 0, or why the block was left UNCHANGED -- 1 the Gram matrix (S_zz, K_n, So_zz) could not be factorised or the block has no step,
+ *   2 the residual covariance (Q, R, P0) is not positive definite, 3 a result is not finite in `dtype`.  A pivot below 2^-46 of its diagonal entry counts as
+ *   failed.  Nothing non-finite is ever written into a model. */
+int auxssm_kalman_smooth_stats(auxssm_handle h, int dtype, const auxssm_dims* dims, const auxssm_lgssm* lgssm, const auxssm_arr* ys, const void* ms, const void* Ps,
+                               const void* sms, const void* sPs, void* cross_out, double* stats_out);
+int auxssm_lgssm_em_mstep(auxssm_handle h, int dtype, int32_t dx, int32_t dy, int32_t nseq, const double* stats, const double* syy_nobs,
+                          const auxssm_mniw_prior* prior, int update_mask, const auxssm_arr* F, const auxssm_arr* b, const auxssm_arr* Q, const auxssm_arr* H,
+                          const auxssm_arr* c, const auxssm_arr* R, const auxssm_arr* m0, const auxssm_arr* P0, int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif

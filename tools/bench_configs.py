@@ -27,6 +27,9 @@
              T = 65536, d = 4, fp64, 1 and 256 sequences, and T = 16384, d = 3, fp32, 64 sequences; parallel scan, at one sequence also the sequential recursion
    dynamics_theta  the conjugate step on (F, b, Q) (loop.DynamicsThetaStep) beside one keyed sweep of the same LGConcatModel with per-chain parameters: C2's shape
              (T = 65536, d = 4, fp64) at 1 / 16 / 256 chains and T = 16384, d = 1, fp32 at 1024 chains; the statistics pass alone as bytes/s beside a device copy
+   em   one EM iteration of a time-invariant LGSSM (_primitives.kalman.fit_em's four calls: filter, smoother, auxssm_kalman_smooth_stats, auxssm_lgssm_em_mstep)
+             beside the statistics entry alone, filter + smoother alone and a device copy of the bytes the statistics pass reads: C2's shape (T = 65536, dx = dy = 4,
+             fp64) at 1 and 16 sequences, and T = 16384, d = 1, fp32 at 64 sequences
    loop the MCMC loop around the sweeps (aux_ssm_samplers_amd.loop: running moments, acceptance averages, adaptation, Lorenz theta step) on C2 / C3 / C4
 Prints one JSON line per measurement.  Inputs are resident in HBM (DeviceChains) where the API allows it; device Threefry noise."""
 import json
@@ -969,6 +972,48 @@ def dynamics_theta(runs=5):
             del chains, spare, state, step, model
 
 
+def em(runs=5):
+    """One EM iteration as fit_em enqueues it (filter, smoother, statistics, M-step of all three blocks; no host synchronisation inside) beside
+    auxssm_kalman_smooth_stats alone, filter + smoother alone, and a device-to-device copy of as many bytes as the statistics pass reads once (ys, Ps, sms, sPs), all in
+    one process in alternating batches (alternating_batches); best batch.  stats_share: the statistics entry's part of the iteration; stats_GBps: those bytes over
+    the statistics time; copy_GBps: twice those bytes (read + write) over the copy time -- an HBM rate only where they exceed the 256 MB last-level cache."""
+    import ctypes as C
+    from aux_ssm_samplers_amd._primitives.kalman.em import _Fit, NAMES
+    from aux_ssm_samplers_amd.workloads import lg_model
+    h = _lib.default_handle()
+    for T, d, dtype, counts in ((65536, 4, np.float64, (1, 16)), (16384, 1, np.float32, (64,))):
+        m = lg_model(T, d, dtype=dtype)
+        start = dict(m0=m["m0"], P0=m["P0"], F=m["F"], b=m["b"], Q=m["Q"], H=m["Hobs"], c=m["cobs"], R=m["Robs"])
+        for S in counts:
+            rng = np.random.default_rng(S)
+            ys = (np.asarray(m["y"])[None] + 0.05 * rng.standard_normal((S, T, d))).astype(dtype)
+            fit = _Fit(h, ys, start, dtype, True, 1)
+            y64 = ys.astype(np.float64).reshape(S * T, d)
+            syy = np.concatenate([(y64.T @ y64).ravel(), [float(S * T)]])
+            syy_c = (C.c_double * len(syy))(*[float(v) for v in syy])
+            nbytes = fit.ybuf.nbytes + fit.Ps.nbytes + fit.sms.nbytes + fit.sPs.nbytes
+            src, dst = h.zeros((nbytes,), np.uint8), h.empty((nbytes,), np.uint8)
+
+            def iteration():
+                fit.filter(0)
+                fit.smooth()
+                fit.statistics()
+                fit.mstep(0, syy_c, None, 7)
+
+            def filter_smooth():
+                fit.filter(0)
+                fit.smooth()
+
+            iteration()
+            it, ss, fs, cp = alternating_batches(h, [iteration, fit.statistics, filter_smooth, lambda: dst.copy_from(src)], runs)
+            print(json.dumps(dict(config=f"EM iteration of a time-invariant LGSSM, T={T} dx={d} dy={d} {np.dtype(dtype).name}", sequences=S,
+                                  iteration_ms=round(it[0], 4), iteration_ms_median=round(it[1], 4), stats_ms=round(ss[0], 4), stats_ms_median=round(ss[1], 4),
+                                  filter_smooth_ms=round(fs[0], 4), filter_smooth_ms_median=round(fs[1], 4), stats_share=round(ss[0] / it[0], 4),
+                                  iteration_over_filter_smooth=round(it[0] / fs[0], 4), stats_bytes=nbytes, stats_GBps=round(nbytes / ss[0] / 1e6, 1),
+                                  copy_ms=round(cp[0], 4), copy_GBps=round(2 * nbytes / cp[0] / 1e6, 1), flags=fit.flags.to_host()[0].tolist())), flush=True)
+            del fit, src, dst
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["c3k", "c4", "c5"]
     if "spatial_kalman" in which:
@@ -977,6 +1022,8 @@ if __name__ == "__main__":
         smoother()
     if "dynamics_theta" in which:
         dynamics_theta()
+    if "em" in which:
+        em()
     if "poisson_kalman" in which:
         poisson_kalman()
     if "logistic_kalman" in which:
