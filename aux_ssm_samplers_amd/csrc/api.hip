@@ -895,7 +895,7 @@ template <typename R> static int sweep_lg_concat_fused(const SweepCall& c) {
     const size_t stage[4] = {(size_t)T * P * D * sR, (size_t)T * P * P * sR, (size_t)T * P * sR, (size_t)T * D * D * sR};  // Hc, Rc, cc, Ps
     R *u, *inc, *ysc0, *m0p, *eps0a, *eps0s;
     WsPlan ws;
-    ws.add(u, CT * D * sR);
+    ws.add(u, (size_t)C * D * sR);  // row 0 of u alone (the t = 0 terms read it): the passes keep u_t, t >= 1, in registers and rebuild it where it is needed again
     ws.add(inc, CT * D * sR);
     ws.add(ysc0, (size_t)C * P * sR);
     ws.add(m0p, (size_t)C * D * sR);

@@ -18,6 +18,9 @@
 //                                         terms of the PROPOSAL x' where it is in registers
 // The filtered means never go to memory, u is written once and read once, and the chain passes are two kernels bound by HBM (AC: 3 d at 615 instructions per
 // chain-step; E: 3 d) instead of three.
+// FIVE ARRAY PASSES (5 d): u is not stored at all.  AC (r x, w inc0) keeps u in registers for the fold and forms no MH terms; E (r inc0, r x, w x') rebuilds
+// u_{t+1} = x_{t+1} + sqrt(delta / 2) eps_aux_{t+1} from the keyed draw (fs_aux_u, the helper pass AC calls: the same bits) and forms the MH terms of BOTH states, x and x',
+// from one read of its log-density row (fs_terms_fast2).  Pass AC was short of issue slots and pass E had them idle.
 // plus the kernel between them (k_fs_mid: the values of k_aff_aggs' scans bit for bit), one lane per chain for the t = 0 terms (k_fs_head) and the accept step (k_fs_accept).
 // There is no select pass: with a `sel` array the state is LAZY -- chain c lives in buffer sel[c] of a ping-pong pair, reads its x from there, writes
 // its proposal to the other buffer, and acceptance flips sel[c] (auxssm_kalman_sweep_lazy); without one, x' goes to a scratch buffer and the
@@ -34,7 +37,7 @@ struct FusedArgs {
     const void* xa;      // (T, D, C) chain-minor; chain c reads its state from xa (sel null or sel[c] == 0) or xb,
     void* xb;            //                         and writes its proposal to the other one
     const int32_t* sel;
-    void* u;             // (T, D, C): row 0 written by the caller, rows >= 1 by k_fs_ac
+    void* u;             // (D, C): u_0, written by the caller (the t = 0 terms; fs_dropped_joint).  u_t, t >= 1, is never stored: see k_fs_e
     void* inc;           // (T, D, C)
     const void* gain;    // n rows GainRow<R, D, P>      (transition i -> i + 1)
     const void* samp;    // T rows SampShared<R, D>
@@ -347,19 +350,18 @@ template <typename R, int D, int PO> struct FsRows {
     using TL = LogShared<R, D, PO>;
     static constexpr int VEC = 16 / sizeof(R);
     static constexpr int pad(int n) { return (n + VEC - 1) / VEC * VEC; }
-    // pass AC, row t (t >= 0): [Mb | kc | K[:, :D] of transition t - 1 -> t | M1_t | gb_t | Lc_t (lower, packed) | gpre_t | LogShared row t - 1]; the filter and
-    // log-density parts of row 0 are zero (no transition into t = 0)
-    static constexpr int cM = 0, cKc = D * D, cK = cKc + D, cM1 = cK + D * D, cGb = cM1 + D * D, cL = cGb + D, cGp = cL + symsize(D), cLg = cGp + D * D,
-                         NC = pad(cLg + TL::N);
-    // pass E, row t: [G_t | N_t = M1_t Phi_t | LogShared row t (transition t -> t + 1, observation at t + 1; zero for t = T - 1)]
+    // pass AC, row t (t >= 0): [Mb | kc | K[:, :D] of transition t - 1 -> t | M1_t | gb_t | Lc_t (lower, packed) | gpre_t]; the filter part of row 0 is zero
+    // (no transition into t = 0).  The pass forms no MH terms, so it carries no log-density row.
+    static constexpr int cM = 0, cKc = D * D, cK = cKc + D, cM1 = cK + D * D, cGb = cM1 + D * D, cL = cGb + D, cGp = cL + symsize(D), NC = pad(cGp + D * D);
+    // pass E, row t: [G_t | N_t = M1_t Phi_t | LogShared row t (transition t -> t + 1, observation at t + 1; zero for t = T - 1)]: the one log-density row serves
+    // the terms of both states, x and x'
     static constexpr int eG = 0, eN = D * D, eL = 2 * D * D, NE = pad(eL + TL::N);
 };
-// where element k of a compact row comes from: {table (0 gain row t - 1, 1 sampler row t, 2 log-density row t - 1, 3 gpre row t, 4 log-density row t,
-// 5 N row t, -1 zero), offset}.  Evaluated per element by one thread, so that consecutive threads write consecutive reals of the destination rows.
+// where element k of a compact row comes from: {table (0 gain row t - 1, 1 sampler row t, 3 gpre row t, 4 log-density row t, 5 N row t, -1 zero), offset}.  Evaluated per element by one thread, so that consecutive threads write consecutive reals of the destination rows.
 struct FsSrc { int tab, off; };
 template <typename R, int D, int PO> __device__ __forceinline__ FsSrc fs_src_c(int k) {
     constexpr int P = D + PO;
-    using F = FsRows<R, D, PO>; using TG = GainRow<R, D, P>; using TS = SampShared<R, D>; using TL = LogShared<R, D, PO>;
+    using F = FsRows<R, D, PO>; using TG = GainRow<R, D, P>; using TS = SampShared<R, D>;
     if (k < F::cKc) return {0, TG::oM + k};
     if (k < F::cK) return {0, TG::oKc + (k - F::cKc)};
     if (k < F::cM1) { const int q = k - F::cK; return {0, TG::oK + (q / D) * P + (q % D)}; }
@@ -371,8 +373,7 @@ template <typename R, int D, int PO> __device__ __forceinline__ FsSrc fs_src_c(i
         while (lidx(i + 1, 0) <= q) ++i;
         return {1, TS::oL + i * D + (q - lidx(i, 0))};
     }
-    if (k < F::cLg) return {3, k - F::cGp};
-    if (k < F::cLg + TL::N) return {2, k - F::cLg};
+    if (k < F::cGp + D * D) return {3, k - F::cGp};
     return {-1, 0};
 }
 template <typename R, int D, int PO> __device__ __forceinline__ FsSrc fs_src_e(int k) {
@@ -397,12 +398,11 @@ template <typename R, int D, int PO> __global__ void __launch_bounds__(256) k_fs
     R v = 0;
     if (sc.tab == 0) { if (t >= 1) v = ((const R*)a.gain)[(long long)(t - 1) * TG::NPAD + sc.off]; }
     else if (sc.tab == 1) v = ((const R*)a.samp)[(long long)t * TS::NPAD + sc.off];
-    else if (sc.tab == 2) { if (t >= 1) v = ((const R*)a.logt)[(long long)(t - 1) * TL::NPAD + sc.off]; }
     else if (sc.tab == 3) v = ((const R*)a.gpre)[(long long)t * D * D + sc.off];
     else if (sc.tab == 4) { if (t + 1 < a.T) v = ((const R*)a.logt)[(long long)t * TL::NPAD + sc.off]; }
     else if (sc.tab == 5) v = ntab[(long long)t * D * D + sc.off];
     (fam == 0 ? rc : re)[g] = v;
-    if ((sc.tab == 2 || sc.tab == 4) && !finite_(v)) *nanrow = 1;  // (every writer stores the same value; zeroed by k_fs_clog_sum, earlier on the stream)
+    if (sc.tab == 4 && !finite_(v)) *nanrow = 1;  // (every writer stores the same value; zeroed by k_fs_clog_sum, earlier on the stream)
 }
 
 // the chain-shared part of log q(x' | u): x'_t | x'_{t+1} = G_t x'_{t+1} + M1_t m_t - gb_t + Lc_t eps_t, so log q = sum_t (-1/2 |eps_t|^2 - sum_i log Lc_t[i][i] - D/2 log 2 pi).
@@ -603,10 +603,81 @@ __device__ __forceinline__ bool fs_terms_fast(const R* row, const R* v, const R*
     out3[2] = qa * inv_delta;
     return !finite_(out3[0]);
 }
+// fs_terms_fast for TWO states that share the row and the auxiliary variable u -- the current pair (vx, wx) and the proposed pair (vp, wp) -- with every coefficient
+// read from LDS ONCE.  Per state the operations and their order are those of fs_terms_fast: the same bits.  The flags are the two calls' return values.
+template <typename R, int D, int PO>
+__device__ __forceinline__ void fs_terms_fast2(const R* row, const R* vx, const R* wx, const R* vp, const R* wp, const R* u, R inv_delta, R cst, R* ox3, R* op3, bool& badx,
+                                               bool& badp) {
+    using TL = LogShared<R, D, PO>;
+    R qox = 0, qop = 0;
+#pragma unroll
+    for (int k = 0; k < PO; ++k) {
+        R zx = row[TL::oYw + k], zp = zx;
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            const R cf = row[TL::oWH + k * D + j];
+            zx -= cf * vx[j];
+            zp -= cf * vp[j];
+        }
+        qox += zx * zx;
+        qop += zp * zp;
+    }
+    const R cr = row[TL::oCR];
+    const R obx = (R)-0.5 * qox + cr, obp = (R)-0.5 * qop + cr;
+    asm volatile("" ::: "memory");  // (the blocks read disjoint parts of the row: keep their LDS reads apart)
+    R qax = 0, qap = 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const R dx = u[k] - vx[k], dp = u[k] - vp[k];
+        qax += dx * dx;
+        qap += dp * dp;
+    }
+    const R axx = -qax * inv_delta + cst, axp = -qap * inv_delta + cst;
+    asm volatile("" ::: "memory");
+    R qpx = 0, qpp = 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        R zx = -row[TL::oWb + k], zp = zx;
+#pragma unroll
+        for (int l = 0; l <= k; ++l) {
+            const R cf = row[TL::oWQ + lidx(k, l)];
+            zx += cf * vx[l];
+            zp += cf * vp[l];
+        }
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            const R cf = row[TL::oWF + k * D + j];
+            zx -= cf * wx[j];
+            zp -= cf * wp[j];
+        }
+        qpx += zx * zx;
+        qpp += zp * zp;
+    }
+    const R cq = row[TL::oCQ];
+    const R prx = (R)-0.5 * qpx + cq, prp = (R)-0.5 * qpp + cq;
+    ox3[0] = (axx + obx) + prx;
+    ox3[1] = obx + prx;
+    ox3[2] = qax * inv_delta;
+    op3[0] = (axp + obp) + prp;
+    op3[1] = obp + prp;
+    op3[2] = qap * inv_delta;
+    badx = !finite_(ox3[0]);
+    badp = !finite_(op3[0]);
+}
 __device__ __forceinline__ bool fs_wave_any(bool flag) { return __builtin_amdgcn_ballot_w64(flag) != 0; }
 
+// the auxiliary variable u_t = x_t + sqrt(delta / 2) eps_aux_t, one fused multiply-add per component.  Pass AC folds it into the filter and pass E rebuilds it for
+// the MH terms instead of reading it back: both call THIS, on the same x, step and draw, so the two passes hold the same bits.
+template <typename R, int D> __device__ __forceinline__ void fs_aux_u(const R* x, R shd, const R* eps, R* u) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        if constexpr (sizeof(R) == 8) u[k] = __builtin_fma(shd, eps[k], x[k]);
+        else u[k] = __builtin_fmaf(shd, eps[k], x[k]);
+    }
+}
+
 // ---- pass AC --------------------------------------------------------------------------------------------------------------------------
-constexpr int FS_WPE_A = 2;  // waves per EU of pass A (3 or 4: 200 VGPRs spill, 0.55 -> 1.2 / 2.1 ms)
+constexpr int FS_WPE_A = 2;  // least waves per EU of pass AC: the compiler's own choice of registers (DESIGN.md section 4 has 3 and 4 measured against it)
 // PK (few chains, one wave per workgroup): lane = sub * cp + chain walks chunk blockIdx.x * pack + sub -- the time index is per lane, everything else is the same code
 template <typename R, int D, int PO, bool PK = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_WPE_A))) k_fs_ac(FusedArgs a, const R* __restrict__ rows) {
@@ -635,18 +706,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_WPE
     }
     if (c >= a.C) return;
     const R* xr = (const R*)((a.sel && a.sel[c]) ? (const void*)a.xb : a.xa) + c;
-    R* up = (R*)a.u + c;
     R* ip = (R*)a.inc + c;
-    R h[D], xq[D], es[D];
+    R h[D], es[D];
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         h[k] = ch == 0 ? ((const R*)a.m0p)[k * C + c] : (R)0;  // chunk 0 folds from the true m_0; the others from zero (their first mean comes from the aggregate scan)
-        xq[k] = xr[((long long)(ta - 1) * D + k) * C];
         es[k] = 0;
     }
-    const R shd = (R)a.shd, inv_delta = (R)1 / (R)a.delta;
-    const R cst = (R)-0.5 * (R)D * log_((R)(0.5 * a.delta)) - (R)(0.5 * LOG_2PI) * (R)D;
-    Acc v0 = 0, v1 = 0, v2 = 0;
+    const R shd = (R)a.shd;
     R se = 0;  // sum |eps_samp|^2 over the chunk's steps: the data part of log q(x' | u)
     // one LOCAL sampler increment: inc0 = M1 h - gb + Lc eps (SampleAffOp::step without the G term, with the chunk-local mean h), stored, and folded into the chunk aggregate
     auto emit = [&](int tu, const R* row, const R* eps) {
@@ -693,26 +760,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_WPE
             for (int k = 0; k < D; ++k) xn[k] = xr[((long long)tn * D + k) * C];
         }
         normals_cm<R, D>(a.ka0, a.ka1, (long long)tu * D * C + c, C, ev, ntab);
+        fs_aux_u<R, D>(x, shd, ev, u);  // (kept in registers: pass E rebuilds it from x and the same draw)
+        // the fold takes a non-finite component of u as zero (FilterMeanOp's masking).  One test per step: a non-finite component makes the sum non-finite, and
+        // the rare wave that sees one masks component by component (a finite u whose sum overflows gets there too, and is left as it is).
+        R um[D], us = u[0];
 #pragma unroll
-        for (int k = 0; k < D; ++k) {
-            u[k] = x[k] + shd * ev[k];
-            up[((long long)tu * D + k) * C] = u[k];
-        }
-        asm volatile("" ::: "memory");
-        // the MH terms of the current state; the rare wave with a non-finite value anywhere redoes them under the per-term policy and masks u for the fold
-        R w[3], um[D];
-        const bool bad = fs_terms_fast<R, D, PO>(row + F::cLg, x, xq, u, inv_delta, cst, w);
+        for (int k = 1; k < D; ++k) us += u[k];
 #pragma unroll
         for (int k = 0; k < D; ++k) um[k] = u[k];
-        if (fs_wave_any(bad)) {
-            fs_terms<R, D, PO>(a, row + F::cLg, x, xq, u, inv_delta, cst, w);
+        if (fs_wave_any(!finite_(us))) {
 #pragma unroll
             for (int k = 0; k < D; ++k) um[k] = finite_(u[k]) ? u[k] : (R)0;
         }
-        v0 += (Acc)w[0];
-        v1 += (Acc)w[1];
-        v2 += (Acc)w[2];
-        asm volatile("" ::: "memory");  // keep the fold's LDS reads behind the log-density row's: hoisted together they cost 200 registers
         {  // filter fold (FilterMeanOp::fold, folded rows): h <- Mb h + kc + K[:, :D] u -- the chunk aggregate at the end, the chunk-local filtered mean on the way
             R o[D];
 #pragma unroll
@@ -731,14 +790,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_WPE
         R eps[D];
         normals_cm<R, D>(a.ks0, a.ks1, (long long)tu * D * C + c, C, eps, ntab);
         emit(tu, row, eps);
-#pragma unroll
-        for (int k = 0; k < D; ++k) xq[k] = x[k];
     }
     stv<R, D>((R*)a.agg_f + ((long long)c * a.nchunk + ch) * SampPre<R, D>::NPAD, h);
     stv<R, D>((R*)a.agg_s + ((long long)c * a.nchunk + (a.nchunk - 1 - ch)) * SampPre<R, D>::NPAD, es);
-    a.pa[((long long)0 * C + c) * a.nchunk + ch] = v0;
-    a.pa[((long long)1 * C + c) * a.nchunk + ch] = v1;
-    a.pa[((long long)2 * C + c) * a.nchunk + ch] = v2;
     ((R*)a.pell)[(long long)c * a.nchunk + ch] = (R)-0.5 * se;
 }
 
@@ -757,7 +811,15 @@ template <bool ONCE, typename R> __device__ __forceinline__ void fs_st_once(R* p
     if constexpr (ONCE) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
-template <typename R, int D, int PO, bool PK = false> __global__ void __launch_bounds__(256) k_fs_e(FusedArgs a, const R* __restrict__ rows) {
+// The pass also forms the MH terms of the CURRENT state x.  They need x and u only, and the pass has the issue slots pass AC lacks: it reads x (the bytes it used
+// to read of u) from the chain's current buffer -- x' goes to the other one, so the two never alias -- rebuilds u_{t+1} = x_{t+1} + sqrt(delta / 2) eps_aux_{t+1} from the
+// keyed draw with pass AC's own helper (fs_aux_u: the bits pass AC folded), and evaluates the pair (x_{t+1}, x_t) beside (x'_{t+1}, x'_t) from the same LDS row
+// reads (fs_terms_fast2).  The pair (t + 1, t) is summed into the chunk of t for both states; k_fs_accept adds the chunks of a chain, whichever chunk a pair is in.
+// x is loaded plainly (it is read again by the next sweep; non-temporal loads measured inside the noise: 273.5k-277.0k against 269.3k-273.8k sweeps/s at 256 chains,
+// equal at 1024); inc0 is dead after its one read and stays non-temporal.
+constexpr int FS_WPE_E = 2;  // two waves per EU: with two states' terms in flight the widest instantiations otherwise take a few registers more than half the file
+template <typename R, int D, int PO, bool PK = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_WPE_E))) k_fs_e(FusedArgs a, const R* __restrict__ rows) {
     using F = FsRows<R, D, PO>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     R* lds = (R*)smem;
@@ -772,6 +834,7 @@ template <typename R, int D, int PO, bool PK = false> __global__ void __launch_b
     }
     const long long C = a.C;
     const int t0 = ch * a.E, tb = min(a.T, t0 + a.E);
+    const FsNormTab<R> ntab = fs_stage_normtab<R>(lds + (PK ? (size_t)a.pack * fs_pk_block<R, F::NE>(a.E) : (size_t)a.E * F::NE));
     if constexpr (PK) {
         const int c0 = blockIdx.x * a.pack;
         fs_stage_pk<R, F::NE>(rows, c0 * a.E, min(a.T, (c0 + a.pack) * a.E), a.E, lds);
@@ -781,10 +844,11 @@ template <typename R, int D, int PO, bool PK = false> __global__ void __launch_b
         fs_stage<R, F::NE>(rows, t0, tb, lds);
     }
     if (c >= a.C) return;
-    R* xw = (R*)((a.sel && a.sel[c]) ? const_cast<void*>(a.xa) : a.xb) + c;
-    const R* up = (const R*)a.u + c;
+    const bool sw = a.sel && a.sel[c];
+    const R* xr = (const R*)(sw ? (const void*)a.xb : a.xa) + c;  // the chain's current state, as pass AC read it
+    R* xw = (R*)(sw ? const_cast<void*>(a.xa) : a.xb) + c;
     const R* ip = (const R*)a.inc + c;
-    R h[D], uq[D], mst[D];  // mst: the chunk's first filtered mean (aggregate scan of the folds): the part of the increments pass AC could not know
+    R h[D], xh[D], uq[D], mst[D];  // x'_{t+1}, x_{t+1}, u_{t+1}; mst: the chunk's first filtered mean (aggregate scan of the folds): the part of the increments pass AC could not know
     if (ch > 0) {
         ldv<R, D>((const R*)a.pre_f + ((long long)c * a.nchunk + ch) * SampPre<R, D>::NPAD, mst);
     } else {
@@ -793,29 +857,31 @@ template <typename R, int D, int PO, bool PK = false> __global__ void __launch_b
     }
     if (ch == a.nchunk - 1) {
 #pragma unroll
-        for (int k = 0; k < D; ++k) h[k] = 0, uq[k] = 0;  // G_{T-1} = 0: the first position ignores the incoming state
+        for (int k = 0; k < D; ++k) h[k] = 0, xh[k] = 0;  // G_{T-1} = 0: the first position ignores the incoming state, and there is no pair above T - 1
     } else {
         ldv<R, D>((const R*)a.pre_s + ((long long)c * a.nchunk + (a.nchunk - 1 - ch)) * SampPre<R, D>::NPAD, h);  // x'_{tb}
 #pragma unroll
-        for (int k = 0; k < D; ++k) uq[k] = up[((long long)tb * D + k) * C];
+        for (int k = 0; k < D; ++k) xh[k] = xr[((long long)tb * D + k) * C];  // x_{tb}: the one load of the chunk above
     }
-    const R inv_delta = (R)1 / (R)a.delta;
-    const R cst = (R)-0.5 * (R)D * log_((R)(0.5 * a.delta)) - (R)(0.5 * LOG_2PI) * (R)D;
-    Acc v0 = 0, v1 = 0, v2 = 0;
-    R incn[D], utn[D];  // the next (earlier) step's records, fetched one step ahead
 #pragma unroll
-    for (int k = 0; k < D; ++k) incn[k] = fs_ld_once<!PK>(ip + ((long long)(tb - 1) * D + k) * C), utn[k] = fs_ld_once<!PK>(up + ((long long)(tb - 1) * D + k) * C);
+    for (int k = 0; k < D; ++k) uq[k] = 0;
+    const R shd = (R)a.shd, inv_delta = (R)1 / (R)a.delta;
+    const R cst = (R)-0.5 * (R)D * log_((R)(0.5 * a.delta)) - (R)(0.5 * LOG_2PI) * (R)D;
+    Acc v0 = 0, v1 = 0, v2 = 0, s0 = 0, s1 = 0, s2 = 0;  // the chunk's sums of x' (v) and of x (s)
+    R incn[D], xn[D];  // the next (earlier) step's records, fetched one step ahead
+#pragma unroll
+    for (int k = 0; k < D; ++k) incn[k] = fs_ld_once<!PK>(ip + ((long long)(tb - 1) * D + k) * C), xn[k] = xr[((long long)(tb - 1) * D + k) * C];
 #pragma unroll 1
     for (int t = tb - 1; t >= t0; --t) {
         const int tu = PK ? t : opaque_uniform(t);
         const R* row = lds + (tu - t0) * F::NE;
-        R inc[D], ut[D], xp[D];
+        R inc[D], xt[D], xp[D];
 #pragma unroll
-        for (int k = 0; k < D; ++k) inc[k] = incn[k], ut[k] = utn[k];
+        for (int k = 0; k < D; ++k) inc[k] = incn[k], xt[k] = xn[k];
         if (t > t0) {
             const int tn = PK ? t - 1 : opaque_uniform(t - 1);
 #pragma unroll
-            for (int k = 0; k < D; ++k) incn[k] = fs_ld_once<!PK>(ip + ((long long)tn * D + k) * C), utn[k] = fs_ld_once<!PK>(up + ((long long)tn * D + k) * C);
+            for (int k = 0; k < D; ++k) incn[k] = fs_ld_once<!PK>(ip + ((long long)tn * D + k) * C), xn[k] = xr[((long long)tn * D + k) * C];
         }
 #pragma unroll
         for (int i = 0; i < D; ++i) {
@@ -827,16 +893,36 @@ template <typename R, int D, int PO, bool PK = false> __global__ void __launch_b
             xp[i] = v;
             fs_st_once<!PK>(xw + ((long long)tu * D + i) * C, v);
         }
-        if (tu + 1 < a.T) {  // (wave-uniform) LogShared row tu: x'_{tu+1} = h given x'_tu = xp, observation and auxiliary terms at tu + 1
-            R w[3];
-            if (fs_wave_any(fs_terms_fast<R, D, PO>(row + F::eL, h, xp, uq, inv_delta, cst, w))) fs_terms<R, D, PO>(a, row + F::eL, h, xp, uq, inv_delta, cst, w);
-            v0 += (Acc)w[0];
-            v1 += (Acc)w[1];
-            v2 += (Acc)w[2];
+        asm volatile("" ::: "memory");  // (the log-density row's LDS reads stay behind the walk's: hoisted together they do not fit two waves' registers)
+        if (tu + 1 < a.T) {  // (wave-uniform; per lane pair in the packed form) LogShared row tu: the states at tu + 1 given those at tu, observation and auxiliary terms at tu + 1
+            R ev[D];
+            normals_cm<R, D>(a.ka0, a.ka1, (long long)(tu + 1) * D * C + c, C, ev, ntab);
+            fs_aux_u<R, D>(xh, shd, ev, uq);
+            asm volatile("" ::: "memory");
+            R wx[3], wp[3];
+            bool badx, badp;
+            fs_terms_fast2<R, D, PO>(row + F::eL, xh, xt, h, xp, uq, inv_delta, cst, wx, wp, badx, badp);
+            // the rare wave with a non-finite value in either state redoes both under the per-term policy (finite terms come out as the fast path's, bit for
+            // bit).  One branch for the two: a branch per state costs sixty registers and spills at two waves per EU.
+            if (fs_wave_any(badx || badp)) {
+                asm volatile("" ::: "memory");
+                fs_terms<R, D, PO>(a, row + F::eL, xh, xt, uq, inv_delta, cst, wx);
+                asm volatile("" ::: "memory");
+                fs_terms<R, D, PO>(a, row + F::eL, h, xp, uq, inv_delta, cst, wp);
+            }
+            v0 += (Acc)wp[0];
+            v1 += (Acc)wp[1];
+            v2 += (Acc)wp[2];
+            s0 += (Acc)wx[0];
+            s1 += (Acc)wx[1];
+            s2 += (Acc)wx[2];
         }
 #pragma unroll
-        for (int k = 0; k < D; ++k) h[k] = xp[k], uq[k] = ut[k];
+        for (int k = 0; k < D; ++k) h[k] = xp[k], xh[k] = xt[k];
     }
+    a.pa[((long long)0 * C + c) * a.nchunk + ch] = s0;
+    a.pa[((long long)1 * C + c) * a.nchunk + ch] = s1;
+    a.pa[((long long)2 * C + c) * a.nchunk + ch] = s2;
     a.pe[((long long)0 * C + c) * a.nchunk + ch] = v0;
     a.pe[((long long)1 * C + c) * a.nchunk + ch] = v1;
     a.pe[((long long)2 * C + c) * a.nchunk + ch] = v2;
@@ -865,8 +951,11 @@ template <typename R, int D, int PO> __device__ __forceinline__ Acc fs_dropped_j
     Acc s = 0;
     const long long C = a.C;
     const R* xp = (const R*)((sel && sel[c]) ? a.xa : (const void*)a.xb) + c;  // the proposal: the buffer the chain does not live in
-    const R* up = (const R*)a.u + c;
-    const R inv_delta = (R)1 / (R)a.delta;
+    // u is not kept: row 0 is the caller's (a.u holds that row alone); u_t, t >= 1, is rebuilt as the passes build it, from the chain's current state and the number
+    // normals_cm puts at (t, k, c) -- here one whole block per number (stream_normal: the same bits), for the few steps with a missing observation
+    const R* xc = (const R*)((sel && sel[c]) ? (const void*)a.xb : a.xa) + c;
+    const R* u0 = (const R*)a.u + c;
+    const R shd = (R)a.shd, inv_delta = (R)1 / (R)a.delta;
     const R cst = (R)-0.5 * (R)D * log_((R)(0.5 * a.delta)) - (R)(0.5 * LOG_2PI) * (R)D;
     for (int t = threadIdx.x; t < a.T; t += TB_ELEM) {
         R y[PO];
@@ -880,10 +969,23 @@ template <typename R, int D, int PO> __device__ __forceinline__ Acc fs_dropped_j
         rd<R, PO * D>(la.Hs, c, t, 0, H);
         rd<R, PO>(la.cs, c, t, 0, cv);
         rd_upper<R, PO>(la.Rs, c, t, 0, Rm);
+        R ut[D];
+        if (t == 0) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) ut[k] = u0[k * C];
+        } else {
+            R xt[D], ev[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                xt[k] = xc[((long long)t * D + k) * C];
+                ev[k] = stream_normal<R>(a.ka0, a.ka1, 0, (unsigned long long)(((long long)t * D + k) * C + c));
+            }
+            fs_aux_u<R, D>(xt, shd, ev, ut);
+        }
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             v[k] = xp[((long long)t * D + k) * C];
-            const R d = up[((long long)t * D + k) * C] - v[k];
+            const R d = ut[k] - v[k];
             b = b || !finite_(d);
             q += d * d;
         }
@@ -978,6 +1080,9 @@ inline int fs_chunk_len(const auxssm_ctx* h, int C, int T) {
     if (E > 32) E = 32;
     // measured at T = 65536, d = 4, fp64 once pass C stopped walking the innovations (rows of 88 / 84 / 68 reals: 64 steps = 45 KB of LDS at most): 64 chains 16 (81k
     // sweeps/s; 32: 76k), 96 chains 32 (100k; 16: 96k), 128 chains 32 (125k; 16: 118k), 256 chains 32 or 64 (175k; 24: 172k), 1024 chains 64 (228k; 32: 220k)
+    // with u out of memory (pass AC's rows 82 reals, pass E's 84 + the normal tables) 64 steps at 256 chains measured 278.2k-282.6k sweeps/s against 269.3k-273.8k
+    // for 32 (profiles/r19_tuning_variants_bench.txt).  Not taken here: the chunk length sets the association of the two aggregate scans, so x would leave the
+    // bits it has had since the chunked sweep; that is a change of its own ("Five array passes").
     if (C >= 1024) E = 64;
     else if (C >= 96) E = 32;
     if (E > T) E = T > 2 ? T : 2;
@@ -1101,11 +1206,14 @@ template <typename R, int D, int PO> int run_fused_shared(auxssm_ctx* h, FusedHo
     {
         ProfScope ps(h, AUXSSM_K_LOGPDF);
         if (a.pack > 1) {
-            const size_t lds_e = (size_t)a.pack * fs_pk_block<R, F::NE>(a.E) * sizeof(R);
+            const size_t lds_e = (size_t)a.pack * fs_pk_block<R, F::NE>(a.E) * sizeof(R) + FsNormTabSel<R>::BYTES;
             if (lds_e > 64 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_fs_e<R, D, PO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_e));
             hipLaunchKernelGGL((k_fs_e<R, D, PO, true>), dim3(grid_pk), dim3(a.pack * a.cp), lds_e, h->stream, a, (const R*)rows_e);
-        } else
-            hipLaunchKernelGGL((k_fs_e<R, D, PO>), dim3(grid), dim3(TBF), (size_t)a.E * F::NE * sizeof(R), h->stream, a, (const R*)rows_e);
+        } else {
+            const size_t lds_e = (size_t)a.E * F::NE * sizeof(R) + FsNormTabSel<R>::BYTES;
+            if (lds_e > 64 * 1024) AX_HIP(hipFuncSetAttribute((const void*)k_fs_e<R, D, PO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_e));
+            hipLaunchKernelGGL((k_fs_e<R, D, PO>), dim3(grid), dim3(TBF), lds_e, h->stream, a, (const R*)rows_e);
+        }
     }
     {
         ProfScope ps(h, AUXSSM_K_SELECT);
