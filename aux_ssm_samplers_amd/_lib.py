@@ -155,6 +155,9 @@ def load():
                                          C.c_int),
         "auxssm_kalman_smooth_stats": ([vp, i32, P(Dims), P(Lgssm), P(Arr), vp, vp, vp, vp, vp, vp], C.c_int),
         "auxssm_lgssm_em_mstep": ([vp, i32, C.c_int32, C.c_int32, C.c_int32, vp, P(dbl), P(MniwPrior), i32] + [P(Arr)] * 8 + [vp], C.c_int),
+        "auxssm_observation_stats": ([vp, i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32, vp, P(Arr), vp], C.c_int),
+        "auxssm_observation_theta_update": ([vp, i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32, vp, P(Arr), P(dbl), P(MniwPrior), i32, vp, vp, vp,
+                                             P(Arr), P(Arr), P(Arr), vp, vp], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the .so does not export what include/auxssm.h declares
@@ -326,6 +329,28 @@ class Handle:
         Cn, T, d = self._state_dims(x, layout)
         check(self.lib.auxssm_dynamics_theta_update(self.h, dtype_code(x.dtype), Cn, T, d, int(layout), x.ptr, C.byref(prior), chi.ptr, eps_w.ptr, eps_a.ptr,
                                                     C.byref(F), C.byref(b), C.byref(Q), post_out.ptr if post_out is not None else None, flags.ptr))
+
+    # ---- theta | x, y for the linear-Gaussian observation model (include/auxssm.h: the conjugate step on (H, c, R)) ----
+    def observation_stats(self, x, yobs, dy, layout=LAYOUT_DENSE):
+        """x (C, T, dx) [dense] or (T, dx, C) [chain-minor] DeviceArray, yobs an Arr descriptor of the data (T, dy) (chain stride 0)
+        -> (C, n n + dy n) float64 DeviceArray [So_zz | S_yz], n = dx + 1"""
+        Cn, T, d = self._state_dims(x, layout)
+        out = self.empty((Cn, (d + 1) * (d + 1) + int(dy) * (d + 1)), np.float64)
+        check(self.lib.auxssm_observation_stats(self.h, dtype_code(x.dtype), Cn, T, d, int(dy), int(layout), x.ptr, C.byref(yobs), out.ptr))
+        return out
+
+    def observation_theta_update(self, x, yobs, dy, syy_nobs, prior, mask, chi, eps_w, eps_a, H, c, R, flags, post_out=None, layout=LAYOUT_DENSE):
+        """yobs an Arr descriptor of the data (T, dy); syy_nobs dy dy + 1 host doubles [S_yy | n_obs]; prior a MniwPrior; mask 1 (H, c, R jointly) or 2 (R alone);
+        chi (C, dy), eps_w (C, dy, dy), eps_a (C, dy, dx + 1) DeviceArrays of x's dtype (eps_a may be None with mask 2); H, c, R: Arr descriptors of the model's
+        per-chain observation model (time stride 0); flags (C,) int32; post_out (C, dy n + n n + 1 + dy dy) float64 or None"""
+        Cn, T, d = self._state_dims(x, layout)
+        sn = np.ascontiguousarray(syy_nobs, np.float64).ravel()
+        if sn.size != int(dy) * int(dy) + 1:
+            raise ValueError(f"syy_nobs must hold dy dy + 1 = {int(dy) * int(dy) + 1} doubles (got {sn.size})")
+        check(self.lib.auxssm_observation_theta_update(self.h, dtype_code(x.dtype), Cn, T, d, int(dy), int(layout), x.ptr, C.byref(yobs),
+                                                       sn.ctypes.data_as(C.POINTER(C.c_double)), C.byref(prior), int(mask), chi.ptr, eps_w.ptr,
+                                                       eps_a.ptr if eps_a is not None else None, C.byref(H), C.byref(c), C.byref(R),
+                                                       post_out.ptr if post_out is not None else None, flags.ptr))
 
     def rng_gamma_into(self, key, stream, shapes, out):
         """out (n, m) <- Gamma(shapes[i], 1), m = len(shapes) <= 8 host doubles"""

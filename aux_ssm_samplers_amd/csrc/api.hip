@@ -609,7 +609,9 @@ static size_t side_stage_bytes(size_t sR, int T, size_t D, size_t P, size_t PO, 
 // stage: on the side stream when a stage is open), then -- obs set -- rows [0, Tc) of u = x + sqrt(delta/2) eps and of the observations [u ; yobs].  Returns the
 // model and the sizes the filter sees.  tinv: the real observation model is time-invariant (time stride 0 on Hs, Rs, cs: the broadcast views of a constant
 // model), so the concatenated one is ONE record with time stride 0 instead of T of them (C2 at one chain: 54 MB written and read back per sweep, 27 of its
-// 240 us)
+// 240 us).  per_chain: the real observation model is time-invariant and differs by chain (chain strides on Hs, Rs, cs: the buffers a conjugate observation step
+// writes) -- one concatenated record per CHAIN, C x (P D + P P + P) reals, built by the same kernel with the chain index in the place of the time index; the
+// filter gets them with their chain strides.
 struct ConcatObs {
     int Tc;
     Arr x, eps, u, ysc;
@@ -619,16 +621,19 @@ struct ConcatModel {
     auxssm_dims d;
 };
 static bool obs_model_time_invariant(const auxssm_lgssm* m) { return m->Hs.st == 0 && m->Rs.st == 0 && m->cs.st == 0; }
-template <typename R> static ConcatModel concat_model(const SweepCall& c, bool tinv, R* Hc, R* Rc, R* cc, const int* memo, const ConcatObs* obs) {
+template <typename R>
+static ConcatModel concat_model(const SweepCall& c, bool tinv, R* Hc, R* Rc, R* cc, const int* memo, const ConcatObs* obs, bool per_chain = false) {
     auxssm_ctx* h = c.h;
-    const int C = c.dims->C, D = c.dims->dx, PO = c.dims->dy, P = D + PO, Tm = tinv ? 1 : c.dims->T;
+    const int C = c.dims->C, D = c.dims->dx, PO = c.dims->dy, P = D + PO, Tm = per_chain ? C : tinv ? 1 : c.dims->T;
+    Arr Hs = cv(c.model->Hs), Rs = cv(c.model->Rs), cs = cv(c.model->cs);
+    if (per_chain) Hs.st = Hs.sc, Rs.st = Rs.sc, cs.st = cs.sc;  // (record r of the kernel = chain r)
     {
         ProfScope ps(h, AUXSSM_K_FACTORY);
         const long long n1 = (long long)Tm * (P * D + P * P + P);
         {
             SideScope sc(h);  // (model stage)
-            hipLaunchKernelGGL((k_concat_model<R>), dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, h->stream, Tm, D, PO, cv(c.model->Hs), cv(c.model->Rs),
-                               cv(c.model->cs), (R)(0.5 * c.delta), c.dptr, Hc, Rc, cc, memo);
+            hipLaunchKernelGGL((k_concat_model<R>), dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, h->stream, Tm, D, PO, Hs, Rs, cs,
+                               (R)(0.5 * c.delta), c.dptr, Hc, Rc, cc, memo);
         }
         if (obs) {
             const long long n2 = (long long)C * obs->Tc * P;
@@ -640,6 +645,11 @@ template <typename R> static ConcatModel concat_model(const SweepCall& c, bool t
     m.g.Hs = auxssm_arr{Hc, 0, tinv ? 0 : (int64_t)P * D, 0};
     m.g.Rs = auxssm_arr{Rc, 0, tinv ? 0 : (int64_t)P * P, 0};
     m.g.cs = auxssm_arr{cc, 0, tinv ? 0 : (int64_t)P, 0};
+    if (per_chain) {
+        m.g.Hs = auxssm_arr{Hc, (int64_t)P * D, 0, 0};
+        m.g.Rs = auxssm_arr{Rc, (int64_t)P * P, 0, 0};
+        m.g.cs = auxssm_arr{cc, (int64_t)P, 0, 0};
+    }
     m.d.dy = P;
     m.d.B = 1;
     return m;
@@ -722,9 +732,13 @@ template <typename R> static int sweep_lg_concat(const SweepCall& c) {
     const size_t sR = sizeof(R);
     const size_t CT = (size_t)C * T;
     // chain-shared parameters: the filtered covariances do not depend on the chain and are stored once, (T, D, D) dense with chain stride 0
-    const bool shared_mode = !wide && chain_shared_mode(h, cm, C, T, dynamics_chain_shared(model));
+    const bool shared_mode = !wide && chain_shared_mode(h, cm, C, T, dynamics_chain_shared(model) && obs_model_chain_shared(model));
     const bool aux_fly = cm && T > 1 && !wide;  // u and the concatenated observations of t >= 1 are formed inside the filter
     const bool tinv = obs_model_time_invariant(model);
+    // a per-chain (time-invariant) observation model, as a conjugate observation step leaves it: the entry point admits it on the register path in the dense
+    // layout only (per_chain_obs_refusal); one concatenated record per chain
+    const bool obs_pc = !obs_model_chain_shared(model);
+    const size_t nrec = obs_pc ? (size_t)(C > T ? C : T) : (size_t)T;
     // general chain-minor sweep: the filtered covariances are an internal buffer the sampler reads twice -- kept symmetric-packed (10 instead of 16
     // reals at d = 4)
     const bool ps_pack = cm && !shared_mode && !wide;
@@ -735,9 +749,9 @@ template <typename R> static int sweep_lg_concat(const SweepCall& c) {
     Acc* sums;
     WsPlan ws;
     ws.add(ysc, CT * P * sR);
-    ws.add(Hc, (size_t)T * P * D * sR);
-    ws.add(Rc, (size_t)T * P * P * sR);
-    ws.add(cc, (size_t)T * P * sR);
+    ws.add(Hc, nrec * P * D * sR);
+    ws.add(Rc, nrec * P * P * sR);
+    ws.add(cc, nrec * P * sR);
     ws.add(u, CT * D * sR);
     ws.add(ms, CT * D * sR);
     ws.add(Ps, CT * D * D * sR);
@@ -787,7 +801,7 @@ template <typename R> static int sweep_lg_concat(const SweepCall& c) {
                             const_cast<void*>(c.u_acc));
     }
     const ConcatObs obs{aux_fly ? 1 : T, xA, epsauxA, uA, yscA};
-    const ConcatModel cmod = concat_model<R>(c, tinv, Hc, Rc, cc, nullptr, &obs);
+    const ConcatModel cmod = concat_model<R>(c, tinv, Hc, Rc, cc, nullptr, &obs, obs_pc);
 
     // proposal LGSSM: filter + pathwise sample (generic.py:80-86).  The factories of this model do not depend on the
     // linearisation point, so the reverse LGSSM (generic.py:67) is the same one and its filter pass is not repeated.
@@ -2075,8 +2089,23 @@ int auxssm_kalman_joint_logpdf(auxssm_handle h, int dtype, const auxssm_dims* di
 // nan_policy, NULL arrays (ptrs_ok: the entry point's own list, yobs and yobs->ptr among them) and per-chain copies of the data or -- obs_model -- of the real
 // observation model.  Each entry point keeps the order and the words it always had: `fused` refuses the first four in one message and has no layout check of
 // its own (fused_refusal speaks about the layout).
+// Per-chain copies of the real observation model (chain strides on Hs, Rs, cs) are what a conjugate observation step (auxssm_observation_theta_update) leaves
+// behind: the LG_CONCAT sweep reads them on its register path in the dense layout, one concatenated record per chain (concat_model).  -> why not, or null
+static const char* per_chain_obs_refusal(bool fused, int model_kind, const auxssm_dims* dims, const auxssm_lgssm* model, int layout) {
+    if (fused) return "the fused sweep needs a chain-shared observation model";
+    if (model_kind != AUXSSM_KMODEL_LG_CONCAT)
+        return "only AUXSSM_KMODEL_LG_CONCAT reads a per-chain observation model (the Lorenz sweep builds its concatenated model once per time step; the "
+               "state-space kinds have none)";
+    if (!obs_model_time_invariant(model)) return "a per-chain observation model must be time-invariant (time stride 0 on Hs, Rs, cs)";
+    if (dims->dx > MAX_D || dims->dy > 4 || is_wide(dims->dx, dims->dx + dims->dy))
+        return "a per-chain observation model is read on the register path only (dx <= 4, dy <= 4), not by the wide-state kernels";
+    if (layout != AUXSSM_LAYOUT_DENSE)
+        return "the chain-minor filter forms the concatenated observations on the fly from ONE chain-shared table per time step: sweep a per-chain observation "
+               "model in the dense layout (AUXSSM_LAYOUT_DENSE)";
+    return nullptr;
+}
 static int check_sweep_common(bool fused, const auxssm_dims* dims, double delta, bool delta_on_device, int nan_policy, int layout, bool ptrs_ok,
-                              const auxssm_lgssm* model, const auxssm_arr* yobs, bool obs_model) {
+                              const auxssm_lgssm* model, const auxssm_arr* yobs, bool obs_model, int model_kind) {
     const bool b_ok = dims->B == 1, delta_ok = delta_on_device || delta > 0;
     const bool nan_ok = nan_policy == AUXSSM_NAN_REFERENCE || nan_policy == AUXSSM_NAN_MASKED;
     if (fused) {
@@ -2108,10 +2137,16 @@ static int check_sweep_common(bool fused, const auxssm_dims* dims, double delta,
     }
     // The data and the REAL observation model are what the chains have in common (the reference's factories close over them,
     // examples/lorenz/auxiliary_kalman.py:26-35): the concatenated model is built once per time step, so per-chain copies are refused
-    // rather than silently read at chain 0.
-    if (yobs->sc != 0 || (obs_model && !obs_model_chain_shared(model))) {
-        set_error("yobs and the observation model (Hs, Rs, cs) are shared by the chains of a sweep: their chain strides must be 0");
+    // rather than silently read at chain 0 -- except the one form per_chain_obs_refusal admits.
+    if (yobs->sc != 0) {
+        set_error("yobs is shared by the chains of a sweep: its chain stride must be 0 (per-chain data is not supported)");
         return AUXSSM_ERR_ARG;
+    }
+    if (obs_model && !obs_model_chain_shared(model)) {
+        if (const char* why = per_chain_obs_refusal(fused, model_kind, dims, model, layout)) {
+            set_error("the observation model (Hs, Rs, cs) has chain strides: %s", why);
+            return AUXSSM_ERR_ARG;
+        }
     }
     return AUXSSM_OK;
 }
@@ -2145,7 +2180,7 @@ static int kalman_sweep_impl(auxssm_handle h, int dtype, int model_kind, const a
     const SweepFamily& fam = *row->family;
     if ((rc = fam.args(dims, model, yobs))) return rc;
     if ((rc = check_sweep_common(false, dims, delta, delta_dev != nullptr, nan_policy, layout, yobs && yobs->ptr && x && eps_aux && eps_samp && u_acc && accepted, model,
-                                 yobs, fam.obs_model)))
+                                 yobs, fam.obs_model, model_kind)))
         return rc;
     if (fam.limits && (rc = fam.limits(dims, layout, nan_policy))) return rc;  // (before anything is enqueued)
     const double* dptr;
@@ -2200,7 +2235,8 @@ int auxssm_kalman_sweep_fused(auxssm_handle h, int dtype, int model_kind, const 
         return AUXSSM_ERR_UNSUPPORTED;
     }
     if ((rc = check_lgssm(model, dims->T))) return rc;
-    if ((rc = check_sweep_common(true, dims, delta, delta_dev != nullptr, nan_policy, layout, keys && yobs && yobs->ptr && x && x_alt && u_acc && accepted, model, yobs, true)))
+    if ((rc = check_sweep_common(true, dims, delta, delta_dev != nullptr, nan_policy, layout, keys && yobs && yobs->ptr && x && x_alt && u_acc && accepted, model, yobs, true,
+                                 model_kind)))
         return rc;
     if (const char* why = fused_refusal(h, dims, model, parallel, layout)) {  // (nothing has been enqueued: the caller runs auxssm_kalman_sweep_keyed instead)
         set_error("auxssm_kalman_sweep_fused: %s", why);

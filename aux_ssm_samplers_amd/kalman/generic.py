@@ -190,14 +190,18 @@ class DeviceChains:
         return np.ascontiguousarray(a.transpose(2, 0, 1)) if self.chain_minor else a
 
 
-def _check_per_chain_dynamics(dl, C):
-    """a model whose Fs / bs / Qs a loop.DynamicsThetaStep has re-pointed at per-chain buffers (dl.bufs["dynamics_theta"], chain strides d d, d, d d) serves chains
-    of that count only: a sweep of more chains would read past the end of the (rows, d, d) / (rows, d) allocations, one of fewer would pair chains with
-    parameters the step never drew for them.  One row is shared by every chain (chain stride 0)."""
-    own = dl.bufs.get("dynamics_theta")
-    if own is not None and own[0].shape[0] not in (1, C):
-        raise ValueError(f"the model holds per-chain dynamics (F, b, Q) of {own[0].shape[0]} chains (a loop.DynamicsThetaStep made them per-chain), the chains "
-                         f"are {C}: sweep it with chains of that count, or build a fresh model")
+def _check_per_chain_params(dl, C):
+    """a model whose Fs / bs / Qs a loop.DynamicsThetaStep, or whose Hs / cs / Rs a loop.ObservationThetaStep, has re-pointed at per-chain buffers
+    (dl.bufs["dynamics_theta"] / dl.bufs["observation_theta"]) serves chains of that count only: a sweep of more chains would read past the end of the per-chain
+    allocations, one of fewer would pair chains with parameters the step never drew for them.  One row is shared by every chain (chain stride 0)."""
+    for name, what, step in (("dynamics_theta", "dynamics (F, b, Q)", "DynamicsThetaStep"), ("observation_theta", "observation model (H, c, R)", "ObservationThetaStep")):
+        own = dl.bufs.get(name)
+        if own is not None and own[0].shape[0] not in (1, C):
+            raise ValueError(f"the model holds per-chain {what} of {own[0].shape[0]} chains (a loop.{step} made them per-chain), the chains "
+                             f"are {C}: sweep it with chains of that count, or build a fresh model")
+
+
+_check_per_chain_dynamics = _check_per_chain_params
 
 
 def _get_device_kernel(model, parallel, nan_policy="reference"):
@@ -209,7 +213,7 @@ def _get_device_kernel(model, parallel, nan_policy="reference"):
         dl, ybuf, yarr = model.device(handle, chains.dtype)
         if "lorenz_par" in dl.bufs and dl.bufs["lorenz_par"].shape[0] not in (1, chains.C):
             raise ValueError(f"the model holds {dl.bufs['lorenz_par'].shape[0]} theta rows, the chains are {chains.C}")
-        _check_per_chain_dynamics(dl, chains.C)
+        _check_per_chain_params(dl, chains.C)
         dims = _lib.Dims(chains.C, chains.T, 1, chains.dx, model.p_obs)
         if keys is not None:
             dev = isinstance(delta, _lib.DeviceArray)

@@ -199,12 +199,189 @@ class DynamicsThetaStep:
         return work[3].to_host() if work is not None else np.zeros(chains.C, np.int32)
 
 
+class ObsMNIWPrior:
+    """The conjugate prior of a linear-Gaussian observation model y_t = H x_t + c + N(0, R), with A = [H c] (dy, dx + 1):
+        R ~ IW(nu0, Psi0),   A | R ~ MN(M0, R, K0^-1)
+    M0 (dy, dx + 1), K0 (dx + 1, dx + 1) symmetric positive definite (a precision: the rows of A have covariance K0^-1 up to R), nu0 > dy - 1, Psi0 (dy, dy)
+    symmetric positive definite.  Validated here as MNIWPrior validates its own, so that an ObservationThetaStep never meets an inadmissible prior on the device."""
+
+    def __init__(self, M0, K0, nu0, Psi0):
+        M0, K0, Psi0 = (np.array(a, np.float64, ndmin=2) for a in (M0, K0, Psi0))
+        dy, n = Psi0.shape[0], K0.shape[0]
+        if Psi0.shape != (dy, dy) or K0.shape != (n, n) or n < 2 or M0.shape != (dy, n):
+            raise ValueError(f"ObsMNIWPrior: need M0 (dy, dx + 1), K0 (dx + 1, dx + 1), Psi0 (dy, dy); got {M0.shape}, {K0.shape}, {Psi0.shape}")
+        nu0 = float(nu0)
+        if not (np.all(np.isfinite(M0)) and np.all(np.isfinite(K0)) and np.all(np.isfinite(Psi0)) and np.isfinite(nu0)):
+            raise ValueError("ObsMNIWPrior: M0, K0, nu0 and Psi0 must be finite")
+        if not nu0 > dy - 1:
+            raise ValueError(f"ObsMNIWPrior: nu0 must exceed dy - 1 = {dy - 1} (got {nu0})")
+        for name, a in (("K0", K0), ("Psi0", Psi0)):
+            dg = np.abs(np.diag(a))
+            if not np.all(np.abs(a - a.T) <= 1e-12 * (dg[:, None] + dg[None, :])):
+                raise ValueError(f"ObsMNIWPrior: {name} must be symmetric")
+            try:
+                np.linalg.cholesky(0.5 * (a + a.T))
+            except np.linalg.LinAlgError:
+                raise ValueError(f"ObsMNIWPrior: {name} must be positive definite") from None
+        self.dx, self.dy, self.M0, self.K0, self.nu0, self.Psi0 = n - 1, dy, M0, 0.5 * (K0 + K0.T), nu0, 0.5 * (Psi0 + Psi0.T)
+
+    def struct(self, chi_scale=2.0):
+        """-> _lib.MniwPrior (auxssm_mniw_prior, its arrays holding (dy, dx + 1), (dx + 1, dx + 1), (dy, dy)); chi_scale 2: the chi buffer holds
+        Gamma((nu_n - i) / 2, 1) draws"""
+        if self.dx > 4 or self.dy > 4:
+            raise ValueError(f"the device step covers dx <= 4 and dy <= 4 (this prior has dx = {self.dx}, dy = {self.dy})")
+        p = _lib.MniwPrior()
+        for name in ("M0", "K0", "Psi0"):
+            arr = getattr(p, name)
+            for k, v in enumerate(getattr(self, name).ravel()):
+                arr[k] = float(v)
+        p.nu0, p.chi_scale = self.nu0, float(chi_scale)
+        return p
+
+
+class ObservationThetaStep:
+    """(H, c, R) | x, y for the observation model y_t = H x_t + c + N(0, R) of an LGConcatModel: one conjugate matrix-normal inverse-Wishart draw per chain and
+    sweep, on the device (auxssm_observation_theta_update), written into per-chain parameter buffers the next sweep reads:
+
+        step = ObservationThetaStep(model, ObsMNIWPrior(M0, K0, nu0, Psi0));   loop(key, delta, state, kernel, None, n_iter, theta_step=step)
+
+    update=("H", "c", "R") draws the three jointly, update=("R",) draws R alone with every chain's H and c fixed (the prior's M0 and K0 are then not read); other
+    subsets are not conjugate blocks and are refused.  model: an LGConcatModel with time-invariant Hobs / Robs / cobs (a broadcast view, or equal rows), dx <= 4,
+    dy <= 4, T >= 2.  Rows of yobs that are wholly NaN are missing and skipped; a partly missing row is refused (under a dense R it is not conjugate, as in fit_em).
+    On its first call the step replaces the device model's Hs, cs, Rs with per-chain buffers (C, dy, dx), (C, dy), (C, dy, dy) of time stride 0 that start as copies
+    of the model's values; from then on the model serves chains of that count only (kalman/generic.py::_check_per_chain_params).  The LG_CONCAT sweep reads a
+    per-chain observation model in the DENSE layout only (the chain-minor filter forms the concatenated observations from one chain-shared table): the step refuses
+    chain-minor chains -- build them with DeviceChains(handle, x, chain_minor=False).  Every call: chains.disable_fused(), the key is split in three by
+    random.split, chi <- auxssm_rng_gamma at shapes (nu_n - i) / 2, two normal fills, the update on chains.x; no host synchronisation.  A chain whose posterior
+    cannot be factorised keeps its parameters and raises its flag (flags(chains))."""
+
+    def __init__(self, model, prior, update=("H", "c", "R")):
+        from .kalman import models as M
+        if not isinstance(model, M.LGConcatModel):
+            raise ValueError(f"ObservationThetaStep: {type(model).__name__} has no linear-Gaussian observation model (Hobs, cobs, Robs) to draw: the step covers "
+                             "LGConcatModel (the count, loading-matrix and Student-t models are not conjugate; LorenzModel rebuilds its model every sweep)")
+        if not isinstance(prior, ObsMNIWPrior):
+            raise ValueError("ObservationThetaStep: prior must be an ObsMNIWPrior")
+        up = tuple(update) if not isinstance(update, str) else (update,)
+        if sorted(up) == ["H", "R", "c"]:
+            self.mask = 1
+        elif up == ("R",):
+            self.mask = 2
+        else:
+            raise ValueError(f"ObservationThetaStep: update must be ('H', 'c', 'R') (drawn jointly) or ('R',) (R alone); {up!r} is not a conjugate block")
+        dx, dy = model.dx, model.p_obs
+        if dx > 4 or dy > 4:
+            raise ValueError(f"ObservationThetaStep: the device step covers dx <= 4 and dy <= 4 (the model has dx = {dx}, dy = {dy})")
+        if (prior.dx, prior.dy) != (dx, dy):
+            raise ValueError(f"ObservationThetaStep: the prior is for (dx, dy) = ({prior.dx}, {prior.dy}), the model has ({dx}, {dy})")
+        if model.T < 2:
+            raise ValueError("ObservationThetaStep: the model needs T >= 2")
+        for name, core in (("Hobs", (dy, dx)), ("Robs", (dy, dy)), ("cobs", (dy,))):
+            a = np.asarray(getattr(model, name))
+            if a.ndim == len(core) + 1 and not _time_invariant(a):
+                raise ValueError(f"ObservationThetaStep: the model's {name} varies in time; the step draws ONE (H, c, R) per chain")
+        y = np.asarray(model.yobs, np.float64).reshape(model.T, dy)
+        fin = np.isfinite(y)
+        if np.any(fin.any(axis=1) & ~fin.all(axis=1)):
+            raise ValueError("ObservationThetaStep: a row of yobs is partly missing; under a dense R only wholly missing (all-NaN) rows are conjugate")
+        self.model, self.prior = model, prior
+        self._prior_c = prior.struct(2.0)
+        self._observed = fin.all(axis=1)
+        self._shapes = [0.5 * (prior.nu0 + int(self._observed.sum()) - i) for i in range(dy)]
+        self._syy = {}
+        self._work = {}
+
+    def _syy_nobs(self, dtype):
+        """[S_yy | n_obs] in double from the data as the device holds it (rounded to the chains' dtype)"""
+        k = np.dtype(dtype).str
+        if k not in self._syy:
+            y = np.asarray(self.model.yobs).reshape(self.model.T, self.model.p_obs).astype(dtype).astype(np.float64)[self._observed]
+            self._syy[k] = np.concatenate([(y.T @ y).ravel(), [float(y.shape[0])]])
+        return self._syy[k]
+
+    # ---- the model's per-chain parameter buffers ----
+    def _params(self, handle, dtype, C):
+        """-> (H (C, dy, dx), c (C, dy), R (C, dy, dy)) DeviceArrays the device model points at, made per-chain on first use"""
+        dl = self.model.device(handle, dtype)[0]
+        dx, dy = self.model.dx, self.model.p_obs
+        own = dl.bufs.get("observation_theta")
+        if own is None:
+            host = [np.repeat(np.asarray(getattr(self.model, n)).reshape((-1,) + core)[:1], C, axis=0)
+                    for n, core in (("Hobs", (dy, dx)), ("cobs", (dy,)), ("Robs", (dy, dy)))]
+            own = dl.bufs["observation_theta"] = tuple(handle.to_device(a, dtype) for a in host)
+            H, c, R = own
+            sc = 1 if C > 1 else 0
+            dl.c.Hs, dl.c.cs, dl.c.Rs = H.arr(sc * dy * dx, 0, 0), c.arr(sc * dy, 0, 0), R.arr(sc * dy * dy, 0, 0)
+            dl.bufs["Hs"], dl.bufs["cs"], dl.bufs["Rs"] = H, c, R
+        if own[0].shape[0] != C:
+            raise ValueError(f"ObservationThetaStep: the model holds per-chain parameters of {own[0].shape[0]} chains, the chains are {C}")
+        return own
+
+    def _check_chains(self, chains):
+        from .kalman.generic import DeviceChains
+        if not isinstance(chains, DeviceChains):
+            raise ValueError("ObservationThetaStep: cSMC chains carry their potential in the Feynman-Kac model; the step needs kalman.DeviceChains")
+        if (chains.T, chains.dx) != (self.model.T, self.model.dx):
+            raise ValueError(f"ObservationThetaStep: the chains are (T, dx) = ({chains.T}, {chains.dx}), the model ({self.model.T}, {self.model.dx})")
+        if chains.chain_minor and chains.C > 1:
+            raise ValueError("ObservationThetaStep: the sweep reads a per-chain observation model in the dense layout only (the chain-minor filter forms the "
+                             "concatenated observations from one chain-shared table): build the chains with DeviceChains(handle, x, chain_minor=False)")
+
+    def __call__(self, key, chains):
+        self._check_chains(chains)
+        handle, dtype, Cn, dx, dy = chains.handle, chains.dtype, chains.C, self.model.dx, self.model.p_obs
+        H, c, R = self._params(handle, dtype, Cn)
+        wk = (id(handle), np.dtype(dtype).str, Cn)
+        work = self._work.get(wk)
+        if work is None:
+            self._work.clear()
+            work = self._work[wk] = (handle.empty((Cn, dy), dtype), handle.empty((Cn, dy, dy), dtype), handle.empty((Cn, dy, dx + 1), dtype),
+                                     handle.zeros((Cn,), np.int32))
+        chi, eps_w, eps_a, flags = work
+        chains.disable_fused()   # per-chain parameters: the fused chain-shared sweep no longer applies
+        k_chi, k_w, k_a = _random.split(key, 3)
+        handle.rng_gamma_into(k_chi, 0, self._shapes, chi)
+        handle.rng_normal_into(k_w, 0, eps_w)
+        handle.rng_normal_into(k_a, 0, eps_a)
+        sc = 1 if Cn > 1 else 0
+        yarr = self.model.device(handle, dtype)[2]
+        handle.observation_theta_update(chains.x, yarr, dy, self._syy_nobs(dtype), self._prior_c, self.mask, chi, eps_w, eps_a, H.arr(sc * dy * dx, 0, 0),
+                                        c.arr(sc * dy, 0, 0), R.arr(sc * dy * dy, 0, 0), flags, layout=chains.layout)
+
+    def params(self, chains):
+        """-> (H (C, dy, dx), c (C, dy), R (C, dy, dy)) as host arrays (synchronises)"""
+        self._check_chains(chains)
+        H, c, R = self._params(chains.handle, chains.dtype, chains.C)
+        return H.to_host(), c.to_host(), R.to_host()
+
+    def flags(self, chains):
+        """-> (C,) int32: 0, or why the last call left chain c unchanged (include/auxssm.h: auxssm_observation_theta_update)"""
+        work = self._work.get((id(chains.handle), np.dtype(chains.dtype).str, chains.C))
+        return work[3].to_host() if work is not None else np.zeros(chains.C, np.int32)
+
+
+class ThetaSteps:
+    """Several theta steps as one: ThetaSteps(step_a, step_b, ...)(key, chains) splits its key by random.split into one child per step and calls the steps in
+    order, each with its own child.  loop(..., theta_step=ThetaSteps(DynamicsThetaStep(...), ObservationThetaStep(...))) is the Gibbs sampler over
+    (x, F, b, Q, H, c, R) of an LGConcatModel."""
+
+    def __init__(self, *steps):
+        if not steps or not all(callable(s) for s in steps):
+            raise ValueError("ThetaSteps: give at least one step, each callable as step(key, chains)")
+        self.steps = tuple(steps)
+
+    def __call__(self, key, chains):
+        for k, step in zip(_random.split(key, len(self.steps)), self.steps):
+            step(k, chains)
+
+
 def loop(key, init_delta, init_state, kernel_fn, delta_fn, n_iter, target_alpha=None, lr=None, beta=0.01, theta_step=None,
          callback=None):
     """See module docstring.  init_state.x: DeviceChains (kernel_fn(key, state, delta) from kalman.get_kernel) or CsmcChains (from
     csmc.get_kernel / get_independent_kernel).  theta_step: called as theta_step(key, chains) after every sweep (Kalman chains) with the second child of the sweep's key -- a LorenzThetaStep (the Lorenz drift
-    parameters) or a DynamicsThetaStep ((F, b, Q) of linear-Gaussian dynamics under an MNIWPrior: a Gibbs sampler over (x, F, b, Q)); both write the model's
-    device parameters in place, one set per chain, without a host synchronisation.
+    parameters), a DynamicsThetaStep ((F, b, Q) of linear-Gaussian dynamics under an MNIWPrior: a Gibbs sampler over (x, F, b, Q)), an ObservationThetaStep
+    ((H, c, R) of an LGConcatModel's observation model under an ObsMNIWPrior) or a ThetaSteps of several (both of the latter: a Gibbs sampler over
+    (x, F, b, Q, H, c, R)); all write the model's device parameters in place, one set per chain, without a host synchronisation.
     callback(i, state) is called after every sweep (e.g. to keep thinned samples; it may synchronise).
 
     Returns (n_iter, stats, state, delta, window_avg_acceptance, avg_acceptance): stats = (sq_jump, mean, sq_mean) as DeviceArrays

@@ -183,6 +183,10 @@ int auxssm_kalman_joint_logpdf(auxssm_handle h, int dtype, const auxssm_dims* di
  *   observations_factory(x,u,d)  -> ys = [u_t ; y_t], Hs = [I ; Hobs_t], Rs = blkdiag(d/2 I, Robs_t), cs = [0 ; cobs_t]
  *   log_likelihood_fn(x)         -> prior_logpdf(x) + sum_t log N(y_t; Hobs_t x_t + cobs_t, Robs_t)
  * `model` holds the dynamics and the REAL observation model (dy = dims->dy = p_obs); yobs (T, p_obs).
+ * yobs is shared by the chains (chain stride 0).  So is the observation model (Hs, Rs, cs), with one exception: AUXSSM_KMODEL_LG_CONCAT on the register path
+ * (dx <= 4, dy <= 4) in AUXSSM_LAYOUT_DENSE reads a per-chain, time-invariant one (chain strides on Hs, Rs, cs, their time strides 0) -- the buffers
+ * auxssm_observation_theta_update writes.  Chain strides there in any other case (the chain-minor layout, a time-varying model, the wide-state path, another
+ * model kind, auxssm_kalman_sweep_fused) are AUXSSM_ERR_ARG with the reason, nothing enqueued.
  *
  * Noise is explicit (the parity contract): eps_aux, eps_samp (C,T,dx) ~ N(0,I), u_acc (C) ~ U[0,1).
  * x (C,T,dx) is updated in place; accepted (C) int32; logs (C,5) = log_alpha, lp_prop, lp_rev, lt_prop, lt_rev
@@ -695,6 +699,41 @@ int auxssm_kalman_smooth_stats(auxssm_handle h, int dtype, const auxssm_dims* di
 int auxssm_lgssm_em_mstep(auxssm_handle h, int dtype, int32_t dx, int32_t dy, int32_t nseq, const double* stats, const double* syy_nobs,
                           const auxssm_mniw_prior* prior, int update_mask, const auxssm_arr* F, const auxssm_arr* b, const auxssm_arr* Q, const auxssm_arr* H,
                           const auxssm_arr* c, const auxssm_arr* R, const auxssm_arr* m0, const auxssm_arr* P0, int32_t* flags);
+
+/* ---- theta | x, y for the linear-Gaussian observation model y_t = H x_t + c + N(0, R): the conjugate step on (H, c, R) (csrc/observation_theta.hip) --------
+ * With z_t = [x_t; 1] (n = dx + 1), A = [H c] (dy x n) and the steps t = 0 .. T - 1 whose row of yobs is entirely finite (a row with any non-finite entry is
+ * skipped whole; n_obs rows remain):
+ *   prior       R ~ IW(nu0, Psi0),  A | R ~ MN(M0, R, K0^-1)        K0 (n, n), Psi0 (dy, dy) symmetric positive definite, nu0 > dy - 1; auxssm_mniw_prior
+ *               holds them as M0 (dy, n), K0 (n, n), Psi0 (dy, dy) row-major in the leading entries, chi_scale as in auxssm_dynamics_theta_update
+ *   statistics  So_zz = sum z_t z_t^T,  S_yz = sum y_t z_t^T  (per chain, on the device: auxssm_kalman_smooth_stats' sums of the same names, without the expectation)
+ *   data terms  S_yy = sum y_t y_t^T and n_obs: syy_nobs, dy dy + 1 HOST doubles, as auxssm_lgssm_em_mstep takes them
+ *   update_mask 1 (H, c, R jointly)  K_n = K0 + So_zz,  M_n = (M0 K0 + S_yz) K_n^-1,  nu_n = nu0 + n_obs,  Psi_n = sym(Psi0 + S_yy + M0 K0 M0^T - M_n K_n M_n^T)
+ *   update_mask 2 (R alone)          nu_n = nu0 + n_obs,  Psi_n = sym(Psi0 + S_yy - A S_yz^T - S_yz A^T + A So_zz A^T) with A the chain's present [H c]; M0 and
+ *                                    K0 are neither checked nor read, eps_a may be NULL, H and c keep their bits
+ *   draw        L = chol(Psi_n), U = chol(K_n), B lower triangular with B_ii = sqrt(chi_scale chi[c, i]), B_ij = eps_w[c, i, j] (i > j):
+ *               R = L B^-T B^-1 L^T (symmetric bit for bit),  A = M_n + chol(R) eps_a[c] U^-1
+ * x: the resident state, (C, T, dx) [AUXSSM_LAYOUT_DENSE] or (T, dx, C) [AUXSSM_LAYOUT_CHAIN_MINOR] of `dtype`; yobs (T, dy) of `dtype`, shared by the chains
+ * (chain stride 0, time stride >= dy); dx, dy <= 4, T >= 2.  Products and sums are formed in double whatever `dtype`; a chain's sums are added in an order that
+ * depends on T and the layout alone (512-step segments of the time axis in ascending order, no atomics): the same bits alone and inside any batch.
+ * auxssm_observation_stats: stats_out (C, n n + dy n) DEVICE doubles, per chain [So_zz (n, n) | S_yz (dy, n)], each row-major.
+ * auxssm_observation_theta_update: chi (C, dy), eps_w (C, dy, dy) (the strict lower triangle is read), eps_a (C, dy, n): DEVICE arrays of `dtype`.  H, c, R: where
+ *   chain c's (dy, dx), (dy), (dy, dy) are written, rounded to `dtype`, at ptr + c * chain stride (time stride 0; with C > 1 the chain strides must keep the chains
+ *   apart) -- the arrays model->Hs / cs / Rs of the next AUXSSM_KMODEL_LG_CONCAT sweep point at.  post_out (C, dy n + n n + 1 + dy dy) DEVICE doubles
+ *   [M_n | K_n | nu_n | Psi_n] (R alone: [A | So_zz | nu_n | Psi_n]), may be NULL.  flags (C) DEVICE int32: 0, or why chain c was left UNCHANGED -- 1 chol(K_n)
+ *   failed or no row is observed, 2 chol(Psi_n) failed (or Psi_n's diagonal is rounding noise of the terms it is the difference of), 3 a chi that is not positive
+ *   and finite, 4 chol(R) failed or a result is not finite in `dtype`.  A pivot below 2^-46 of its diagonal entry counts as failed.  Nothing non-finite is ever
+ *   written into H, c, R.
+ * Refused before anything is enqueued: dx > 4 or dy > 4 (AUXSSM_ERR_UNSUPPORTED), T < 2, NULL arguments, an unknown layout or update_mask, a prior or data
+ * terms that are not finite, a prior that is not symmetric, positive definite or has nu0 <= dy - 1 (M0 and K0: update_mask 1 only), yobs with a chain stride
+ * other than 0, a time stride other than 0 on H, c, R, chain strides below dy dx, dy, dy dy at C > 1, and what one launch cannot hold:
+ * C x ceil(T / 512) > 2^31 - 1, or, chain-minor, C > 65535 x 64 = 4194240 chains.
+ * The LG_CONCAT sweep reads such a per-chain observation model (chain strides on Hs, Rs, cs; time stride 0; yobs shared) on its register path
+ * (dx <= 4, dy <= 4) in the dense layout; see auxssm_kalman_sweep. */
+int auxssm_observation_stats(auxssm_handle h, int dtype, int32_t C, int32_t T, int32_t dx, int32_t dy, int layout, const void* x, const auxssm_arr* yobs,
+                             double* stats_out);
+int auxssm_observation_theta_update(auxssm_handle h, int dtype, int32_t C, int32_t T, int32_t dx, int32_t dy, int layout, const void* x, const auxssm_arr* yobs,
+                                    const double* syy_nobs, const auxssm_mniw_prior* prior, int update_mask, const void* chi, const void* eps_w,
+                                    const void* eps_a, const auxssm_arr* H, const auxssm_arr* c, const auxssm_arr* R, double* post_out, int32_t* flags);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,8 @@
    pit30  the reference's SV experiment at its defaults (--parallel, D = 30, N = 25, T = 250): the parallel-in-time sweep beside the sequential wide sweep, 1 / 16 / 256 chains
    smoother  the RTS smoother (auxssm_kalman_smooth) beside the pathwise sampler (auxssm_kalman_sample) on the same resident filtered moments: C2's model at
              T = 65536, d = 4, fp64, 1 and 256 sequences, and T = 16384, d = 3, fp32, 64 sequences; parallel scan, at one sequence also the sequential recursion
+   observation_theta  the conjugate step on (H, c, R) (loop.ObservationThetaStep) beside one keyed sweep of the same LGConcatModel with a per-chain observation
+                   model, the statistics entry alone in both layouts, auxssm_dynamics_stats on the same state and a device copy: dynamics_theta's four rows
    dynamics_theta  the conjugate step on (F, b, Q) (loop.DynamicsThetaStep) beside one keyed sweep of the same LGConcatModel with per-chain parameters: C2's shape
              (T = 65536, d = 4, fp64) at 1 / 16 / 256 chains and T = 16384, d = 1, fp32 at 1024 chains; the statistics pass alone as bytes/s beside a device copy
    em   one EM iteration of a time-invariant LGSSM (_primitives.kalman.fit_em's four calls: filter, smoother, auxssm_kalman_smooth_stats, auxssm_lgssm_em_mstep)
@@ -972,6 +974,71 @@ def dynamics_theta(runs=5):
             del chains, spare, state, step, model
 
 
+def observation_theta(runs=5):
+    """loop.ObservationThetaStep (gamma + two normal fills + statistics, reduce and finish kernels) beside one keyed sweep of the same LGConcatModel once its
+    observation model is per-chain (the dense general path, one concatenated record per chain), auxssm_observation_stats alone (on the dense state the step runs
+    on, and on a chain-minor copy of it), auxssm_dynamics_stats on the same state, and a device-to-device copy of the bytes the statistics pass reads (the state;
+    yobs is T dy reals beside it), all in one process in alternating batches (alternating_batches); best batch.  stats_GBps: the state's bytes (read once) over
+    the statistics time; copy_GBps: twice the state's bytes (read + write) over the copy time -- an HBM rate only where the state exceeds the 256 MB last-level
+    cache (the 256-chain row), a cache rate below that."""
+    import ctypes as C
+    from aux_ssm_samplers_amd.kalman import LGConcatModel
+    from aux_ssm_samplers_amd.loop import ObservationThetaStep, ObsMNIWPrior
+    from aux_ssm_samplers_amd.workloads import lg_model
+    h = _lib.default_handle()
+    bt = np.broadcast_to
+    for T, d, dtype, counts in ((65536, 4, np.float64, (1, 16, 256)), (16384, 1, np.float32, (1024,))):
+        m = lg_model(T, d, dtype=dtype)
+        dy = d
+        for chains_n in counts:
+            model = LGConcatModel(m["m0"], m["P0"], bt(m["F"], (T - 1, d, d)), bt(m["Q"], (T - 1, d, d)), bt(m["b"], (T - 1, d)), bt(m["Hobs"], (T, dy, d)),
+                                  bt(m["Robs"], (T, dy, dy)), bt(m["cobs"], (T, dy)), m["y"])
+            init, kernel = get_kernel(model.dynamics_factory, model.observations_factory, model.log_likelihood_fn, True)
+            rng = np.random.default_rng(chains_n)
+            x0 = (np.asarray(m["x_true"])[None] + 0.1 * rng.standard_normal((chains_n, T, d))).astype(dtype)
+            chains = DeviceChains(h, x0, dtype, chain_minor=False)   # (the per-chain sweep serves the dense layout)
+            x_cm = h.to_device(np.ascontiguousarray(x0.transpose(1, 2, 0)), dtype)
+            del x0
+            state = init(chains)
+            step = ObservationThetaStep(model, ObsMNIWPrior(np.zeros((dy, d + 1)), np.eye(d + 1), dy + 2.0, np.eye(dy)))
+            keys = R.split(R.PRNGKey(3), 4096)
+            it = [0]
+
+            def nk():
+                it[0] = (it[0] + 1) % 4096
+                return keys[it[0]]
+
+            step(nk(), chains)   # the model's observation parameters become per-chain here
+            spare = h.empty(chains.x.shape, dtype)
+            yarr = model.device(h, dtype)[2]
+            ostats = h.empty((chains_n, (d + 1) * (d + 1) + dy * (d + 1)), np.float64)
+            dstats = h.empty((chains_n, (d + 1) * (d + 1) + d * (d + 1) + d * d), np.float64)
+            code = _lib.dtype_code(dtype)
+
+            def sweep():
+                nonlocal state
+                state = kernel(nk(), state, 0.5)
+
+            def stats_only():
+                _lib.check(h.lib.auxssm_observation_stats(h.h, code, chains_n, T, d, dy, _lib.LAYOUT_DENSE, chains.x.ptr, C.byref(yarr), ostats.ptr))
+
+            def stats_cm():
+                _lib.check(h.lib.auxssm_observation_stats(h.h, code, chains_n, T, d, dy, _lib.LAYOUT_CHAIN_MINOR, x_cm.ptr, C.byref(yarr), ostats.ptr))
+
+            def dyn_stats():
+                _lib.check(h.lib.auxssm_dynamics_stats(h.h, code, chains_n, T, d, _lib.LAYOUT_DENSE, chains.x.ptr, dstats.ptr))
+
+            st, sw, ss, sc, ds, cp = alternating_batches(h, [lambda: step(nk(), chains), sweep, stats_only, stats_cm, dyn_stats, lambda: spare.copy_from(chains.x)], runs)
+            nbytes = chains.x.nbytes
+            print(json.dumps(dict(config=f"observation theta step beside one keyed sweep, LGConcatModel T={T} dx={d} dy={dy} {np.dtype(dtype).name}, per-chain (H, c, R)",
+                                  chains=chains_n, layout="dense", step_ms=round(st[0], 4), step_ms_median=round(st[1], 4), sweep_ms=round(sw[0], 4),
+                                  sweep_ms_median=round(sw[1], 4), step_over_sweep=round(st[0] / sw[0], 4), stats_ms=round(ss[0], 4),
+                                  stats_GBps=round(nbytes / ss[0] / 1e6, 1), stats_chain_minor_ms=round(sc[0], 4), stats_chain_minor_GBps=round(nbytes / sc[0] / 1e6, 1),
+                                  dynamics_stats_ms=round(ds[0], 4), dynamics_stats_GBps=round(nbytes / ds[0] / 1e6, 1), copy_ms=round(cp[0], 4),
+                                  copy_GBps=round(2 * nbytes / cp[0] / 1e6, 1), state_bytes=nbytes, flagged=int(step.flags(chains).any()))), flush=True)
+            del chains, spare, state, step, model, x_cm
+
+
 def em(runs=5):
     """One EM iteration as fit_em enqueues it (filter, smoother, statistics, M-step of all three blocks; no host synchronisation inside) beside
     auxssm_kalman_smooth_stats alone, filter + smoother alone, and a device-to-device copy of as many bytes as the statistics pass reads once (ys, Ps, sms, sPs), all in
@@ -1022,6 +1089,8 @@ if __name__ == "__main__":
         smoother()
     if "dynamics_theta" in which:
         dynamics_theta()
+    if "observation_theta" in which:
+        observation_theta()
     if "em" in which:
         em()
     if "poisson_kalman" in which:
