@@ -31,6 +31,7 @@
 // both NaN policies, rejected chains and a non-finite chain in the wave, for every (D, PO)).
 #pragma once
 // (included inside namespace ax by kernels.hip.h)
+#include "fs_chunk.h"  // the chunk rule: a plain integer function, also checked on the CPU (tests/test_fused_chunk_host.py)
 
 struct FusedArgs {
     int C, T, E, nchunk;
@@ -1070,24 +1071,8 @@ inline int fs_pack(int C, int* cp_out) {
     constexpr int cap = 8;   // (LDS: pack blocks of E coefficient rows)
     return pack > cap ? cap : pack;
 }
-inline int fs_chunk_len(const auxssm_ctx* h, int C, int T) {
-    constexpr int waves = 10;
-    const long long stiles = (C + TB_CM - 1) / TB_CM;
-    long long want = (long long)h->num_cu * 4 * waves / stiles;
-    if (want < 1) want = 1;
-    long long E = (T + want - 1) / want;
-    if (E < 16) E = 16;
-    if (E > 32) E = 32;
-    // measured at T = 65536, d = 4, fp64 once pass C stopped walking the innovations (rows of 88 / 84 / 68 reals: 64 steps = 45 KB of LDS at most): 64 chains 16 (81k
-    // sweeps/s; 32: 76k), 96 chains 32 (100k; 16: 96k), 128 chains 32 (125k; 16: 118k), 256 chains 32 or 64 (175k; 24: 172k), 1024 chains 64 (228k; 32: 220k)
-    // with u out of memory (pass AC's rows 82 reals, pass E's 84 + the normal tables) 64 steps at 256 chains measured 278.2k-282.6k sweeps/s against 269.3k-273.8k
-    // for 32 (profiles/r19_tuning_variants_bench.txt).  Not taken here: the chunk length sets the association of the two aggregate scans, so x would leave the
-    // bits it has had since the chunked sweep; that is a change of its own ("Five array passes").
-    if (C >= 1024) E = 64;
-    else if (C >= 96) E = 32;
-    if (E > T) E = T > 2 ? T : 2;
-    return (int)E;
-}
+static_assert(FS_RULE_TILE == TB_CM, "fs_chunk_rule counts the chain tiles of the affine passes");
+inline int fs_chunk_len(const auxssm_ctx* h, int C, int T) { return fs_chunk_rule(h->num_cu, C, T); }  // (the rule and what it was measured on: fs_chunk.h)
 template <typename R, int D, int PO> size_t fused_ws(const auxssm_ctx* h, const KDims& d) {
     constexpr int P = D + PO;
     const int E = fs_chunk_len(h, d.C, d.T), nchunk = (d.T + E - 1) / E;
