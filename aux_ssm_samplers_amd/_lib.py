@@ -65,6 +65,11 @@ class FkUser(C.Structure):
     _fields_ = [("y", C.c_void_p), ("theta_g", C.c_void_p), ("theta_m", C.c_void_p), ("p", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FkChainDynamics(C.Structure):
+    """auxssm_fk_chain_dynamics: the per-chain transition arrays of auxssm_csmc_sweep_chain_dynamics, device (C, dx, dx), (C, dx), (C, dx, dx) lower"""
+    _fields_ = [("F", C.c_void_p), ("b", C.c_void_p), ("chol_Q", C.c_void_p)]
+
+
 FK_USER_POTENTIAL, FK_USER_MEAN, FK_USER_GRADIENT = 1, 2, 4
 PROP_BOOTSTRAP_LG, PROP_AUX_INDEPENDENT, PROP_AUX_GUIDED = 0, 1, 2
 POT_FLAT, POT_GAUSS_OBS, POT_SV, POT_GAUSS_OBS_MASKED, POT_MVT, POT_LIN_GAUSS, POT_POISSON = 0, 1, 2, 3, 4, 5, 6
@@ -128,6 +133,9 @@ def load():
         "auxssm_kalman_sweep_fused": ([vp, i32, i32, P(Dims), P(Lgssm), P(Arr), dbl, vp, P(C.c_uint32), i32, i32, i32, vp, vp, vp, vp, vp, vp], C.c_int),
         "auxssm_kalman_state_resolve": ([vp, i32, P(Dims), vp, vp, vp], C.c_int),
         "auxssm_csmc_sweep": ([vp, i32, P(FkModel), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, P(CsmcNoise), vp, vp, vp, vp], C.c_int),
+        "auxssm_csmc_sweep_chain_dynamics": ([vp, i32, P(FkModel), P(FkChainDynamics), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, P(CsmcNoise), vp, vp, vp,
+                                              vp], C.c_int),
+        "auxssm_csmc_dynamics_commit": ([vp, i32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "auxssm_fk_program_compile": ([C.c_char_p, C.c_char_p, i32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t, P(vp)], C.c_int),
         "auxssm_fk_program_free": ([vp], C.c_int),
         "auxssm_fk_program_info": ([vp, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32)], C.c_int),
@@ -329,6 +337,13 @@ class Handle:
         Cn, T, d = self._state_dims(x, layout)
         check(self.lib.auxssm_dynamics_theta_update(self.h, dtype_code(x.dtype), Cn, T, d, int(layout), x.ptr, C.byref(prior), chi.ptr, eps_w.ptr, eps_a.ptr,
                                                     C.byref(F), C.byref(b), C.byref(Q), post_out.ptr if post_out is not None else None, flags.ptr))
+
+    def csmc_dynamics_commit(self, F_new, b_new, Q_new, step_flags, F, b, Q, chol_Q, flags):
+        """auxssm_csmc_dynamics_commit: staging (F_new (C, dx, dx), b_new (C, dx), Q_new (C, dx, dx)) as auxssm_dynamics_theta_update left them, with its
+        step_flags (C,) int32 -> the live quadruple (F, b, Q, chol_Q) of the chains that pass and flags (C,) int32 (0, the update's 1 - 4, or 5)"""
+        Cn, d = b.shape
+        check(self.lib.auxssm_csmc_dynamics_commit(self.h, dtype_code(F.dtype), Cn, d, F_new.ptr, b_new.ptr, Q_new.ptr, step_flags.ptr, F.ptr, b.ptr, Q.ptr,
+                                                   chol_Q.ptr, flags.ptr))
 
     # ---- theta | x, y for the linear-Gaussian observation model (include/auxssm.h: the conjugate step on (H, c, R)) ----
     def observation_stats(self, x, yobs, dy, layout=LAYOUT_DENSE):

@@ -392,6 +392,7 @@ class CsmcChains:
         self.x = handle.to_device(x, self.dtype)
         self.ancestors = handle.zeros((self.C, self.T), np.int32)
         self.delta = self.sqrt_half_delta = None
+        self.dynamics = None  # ChainDynamics: per-chain (F, b, Q, chol_Q), attached by loop.DynamicsThetaStep -- the sweeps then read chain c's own transition
         if delta is not None:
             self.set_delta(delta)
 
@@ -407,8 +408,51 @@ class CsmcChains:
         return a.to_host()
 
 
+class ChainDynamics:
+    """Per-chain linear-Gaussian transitions of resident cSMC chains (auxssm_csmc_sweep_chain_dynamics): the LIVE quadruple F (C, d, d), b (C, d), Q (C, d, d),
+    chol_Q (C, d, d) the sweep reads, the STAGING buffers F_new, b_new, Q_new a conjugate draw is written into, the draw's step_flags and the commit's flags
+    (auxssm_csmc_dynamics_commit moves a chain's staging values into the live ones, or leaves them and says why).  All start as C copies of (F, b, Q)."""
+
+    def __init__(self, handle, dtype, C, F, b, Q):
+        F, Q = (np.atleast_2d(np.asarray(a, np.float64)) for a in (F, Q))
+        d = F.shape[0]
+        b = np.asarray(b, np.float64).reshape(d)
+        Qr = Q.astype(dtype).astype(np.float64)  # the factor of Q as the live buffer holds it, as the commit forms it
+        host = dict(F=F, b=b, Q=Q, chol_Q=np.linalg.cholesky(Qr), F_new=F, b_new=b, Q_new=Q)
+        for name, a in host.items():
+            setattr(self, name, handle.to_device(np.repeat(a[None], C, axis=0), dtype))
+        self.step_flags, self.flags = handle.zeros((C,), np.int32), handle.zeros((C,), np.int32)
+        self.handle, self.dtype, self.C, self.dx = handle, np.dtype(dtype), int(C), d
+
+    def struct(self):
+        return _lib.FkChainDynamics(self.F.ptr.value, self.b.ptr.value, self.chol_Q.ptr.value)
+
+    def commit(self):
+        self.handle.csmc_dynamics_commit(self.F_new, self.b_new, self.Q_new, self.step_flags, self.F, self.b, self.Q, self.chol_Q, self.flags)
+
+
+def _check_chain_dynamics(fk, chains):
+    """why a description cannot run on the per-chain transitions of chains.dynamics (ValueError), or nothing"""
+    dyn = chains.dynamics
+    why = None
+    if fk.user is not None:
+        why = "user-defined models (DevicePotential / DeviceGaussianDynamics) are compiled for chain-shared transitions"
+    elif fk.proposal == _lib.PROP_AUX_GUIDED:
+        why = "guided proposals run chain-shared transitions (their K_t / chol Lambda_t tables would be per chain and step)"
+    elif fk.dx > 4:
+        why = f"dx={fk.dx}: the wide-state kernels (dx > 4) read one chain-shared transition"
+    elif fk.transition != _lib.TRANS_LINEAR:
+        why = "Lorenz63Dynamics has no (F, b, Q) to replace"
+    elif fk.tv is not None:
+        why = "the description's transitions vary in time; per-chain dynamics are time-invariant"
+    elif (dyn.C, dyn.dx) != (chains.C, chains.dx) or dyn.handle is not chains.handle or dyn.dtype != chains.dtype:
+        why = f"they were attached for {dyn.C} chains of dx={dyn.dx} ({dyn.dtype}), the chains are {chains.C} of dx={chains.dx} ({chains.dtype})"
+    if why is not None:
+        raise ValueError(f"these chains carry per-chain dynamics (CsmcChains.dynamics, attached by a DynamicsThetaStep), which this kernel cannot read: {why}")
+
+
 def sweep_resident(fk, chains, N, backward, key):
-    """One Threefry-keyed auxssm_csmc_sweep on resident chains.  Asynchronous."""
+    """One Threefry-keyed auxssm_csmc_sweep on resident chains -- auxssm_csmc_sweep_chain_dynamics when the chains carry per-chain dynamics.  Asynchronous."""
     _no_jax_resident()
     handle, d = chains.handle, chains.dx
     if d != fk.dx:
@@ -420,14 +464,23 @@ def sweep_resident(fk, chains, N, backward, key):
             raise ValueError("delta is required")
         shd = chains.sqrt_half_delta
     nz, _ = _noise(handle, chains.dtype, chains.C, key)
-    _csmc_call(handle, fk, chains.dtype, m, chains.C, chains.T, N, backward, shd, chains.x, nz, chains.ancestors, None, None, None)
+    dyn = None
+    if chains.dynamics is not None:
+        _check_chain_dynamics(fk, chains)
+        dyn = chains.dynamics.struct()
+    _csmc_call(handle, fk, chains.dtype, m, chains.C, chains.T, N, backward, shd, chains.x, nz, chains.ancestors, None, None, None, dyn)
 
 
-def _csmc_call(handle, fk, dtype, m, Cn, T, N, backward, shd, xd, nz, anc, xs, lws, As):
-    """auxssm_csmc_sweep, or auxssm_csmc_sweep_program for a model with device-code parts"""
+def _csmc_call(handle, fk, dtype, m, Cn, T, N, backward, shd, xd, nz, anc, xs, lws, As, dyn=None):
+    """auxssm_csmc_sweep, auxssm_csmc_sweep_chain_dynamics with per-chain transitions (dyn: an FkChainDynamics), or auxssm_csmc_sweep_program for a model with
+    device-code parts"""
     args = (Cn, T, N, int(bool(backward)), shd.ptr if shd is not None else None, xd.ptr, C.byref(nz), anc.ptr,
             xs.ptr if xs else None, lws.ptr if lws else None, As.ptr if As else None)
-    if fk.user is None:
+    if dyn is not None:
+        if fk.user is not None:
+            raise ValueError("per-chain dynamics: user-defined models are compiled for chain-shared transitions")
+        _lib.check(handle.lib.auxssm_csmc_sweep_chain_dynamics(handle.h, _lib.dtype_code(dtype), C.byref(m), C.byref(dyn), *args))
+    elif fk.user is None:
         _lib.check(handle.lib.auxssm_csmc_sweep(handle.h, _lib.dtype_code(dtype), C.byref(m), *args))
     else:
         u = fk.user.struct(handle, dtype, T)
@@ -439,6 +492,9 @@ def pit_sweep_resident(fk, chains, N, key):
     _no_jax_resident()
     handle = chains.handle
     _no_user_pit(fk)
+    if chains.dynamics is not None:
+        raise ValueError("these chains carry per-chain dynamics (CsmcChains.dynamics, attached by a DynamicsThetaStep): the parallel-in-time kernels read one "
+                         "chain-shared transition and would ignore them; run the sequential sweep (parallel=False)")
     if chains.dx != fk.dx:
         raise ValueError(f"state dimension {chains.dx} != model dimension {fk.dx}")
     if chains.sqrt_half_delta is None:
@@ -480,8 +536,9 @@ def pit_sweep(fk, x, N, *, key=None, noise=None, delta=None, handle=None):
     return (xo[0], ao[0]) if single else (xo, ao)
 
 
-def sweep(fk, x, N, backward, *, key=None, noise=None, delta=None, handle=None, want_history=False):
+def sweep(fk, x, N, backward, *, key=None, noise=None, delta=None, handle=None, want_history=False, chain_dynamics=None):
     """x: (T, d) one chain or (C, T, d).  noise: dict of explicit arrays (eps_prop, u_res, u_bwd[, eps_aux]) or None -> Threefry(key).
+    chain_dynamics: (F (C, d, d), b (C, d), chol_Q (C, d, d)) host arrays -> auxssm_csmc_sweep_chain_dynamics, chain c on its own transition.
     Returns (x_new, ancestors, history dict or None)."""
     handle = handle or _lib.default_handle()
     x = np.asarray(x)
@@ -511,7 +568,11 @@ def sweep(fk, x, N, backward, *, key=None, noise=None, delta=None, handle=None, 
         xs = handle.empty((Cn, T, N, d), dtype)
         lws = handle.empty((Cn, T, N), dtype)
         As = handle.zeros((Cn, max(T - 1, 1), N), np.int32)
-    _csmc_call(handle, fk, dtype, m, Cn, T, N, backward, shd, xd, nz, anc, xs, lws, As)
+    dyn = None
+    if chain_dynamics is not None:
+        dbuf = [handle.to_device(np.asarray(a, np.float64).reshape(shp), dtype) for a, shp in zip(chain_dynamics, ((Cn, d, d), (Cn, d), (Cn, d, d)))]
+        dyn = _lib.FkChainDynamics(*(a.ptr.value for a in dbuf))
+    _csmc_call(handle, fk, dtype, m, Cn, T, N, backward, shd, xd, nz, anc, xs, lws, As, dyn)
     xo, ao = xd.to_host(), anc.to_host()
     if want_history:
         hist = dict(xs=xs.to_host(), log_ws=lws.to_host(), As=As.to_host()[:, :T - 1])

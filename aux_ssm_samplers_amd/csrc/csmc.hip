@@ -101,20 +101,8 @@ __global__ void __launch_bounds__(1024) k_systematic(int M, int N, const R* __re
     }
 }
 
-// dynamic LDS of the forward / backward pass (csmc_sweep.h: k_csmc_fwd, k_csmc_bwd) for TB lanes
-static size_t fwd_lds(int TB, int D, size_t sR) { return (size_t)2 * (cpad(TB) + TB * D) * sR + 48 * sR + 64; }
-static size_t bwd_lds(int TB, int D, size_t sR) { return (size_t)2 * TB * sR + 64 * sR + (size_t)2 * TB * D * sR + 2 * sR + 64; }
-
-// the workgroup shapes with instantiations of their own (NW of k_csmc_fwd / k_csmc_bwd): sixteen full waves, eight full waves, 0 = any N
-static int nw_class(int N) { return N == 1024 ? 16 : (N == 512 ? 8 : 0); }
-// f(std::true_type / std::false_type) for b; f(std::integral_constant<int, nw>) for an nw_class
-template <typename F> static auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
-template <typename F> static auto with_nw(int nw, F&& f) {
-    return nw == 16 ? f(std::integral_constant<int, 16>{}) : (nw == 8 ? f(std::integral_constant<int, 8>{}) : f(std::integral_constant<int, 0>{}));
-}
-
-// a pass of the built-in family, as run_csmc launches it
-template <typename R> using SweepKernel = void (*)(CsmcArgs, FkDev<R>);
+// (the passes' LDS sizes, the workgroup classes and the kernel-pointer type -- fwd_lds / bwd_lds, nw_class, with_bool / with_nw, SweepKernel -- are csmc_host.h's:
+// csmc_chain.hip launches the same passes on per-chain transitions)
 
 // config C3's shape: the one instantiation with the model kinds folded at compile time (SP = 1, csmc_sweep.h)
 template <typename R, int D> static bool c3_shape(const FkDev<R>& m, const CsmcArgs& a, int nw) {
@@ -243,6 +231,7 @@ static int run_csmc_program(auxssm_ctx* h, const auxssm_fk_program_s* prog, cons
 
 namespace ax {
 int run_csmc_wide(auxssm_ctx* h, int dtype, const auxssm_fk_model* fk, CsmcArgs& a, void* ctt);  // csmc_wide.hip
+int run_csmc_chain(auxssm_ctx* h, int dtype, const auxssm_fk_model* fk, const auxssm_fk_chain_dynamics* dyn, CsmcArgs& a, void* ctt);  // csmc_chain.hip
 }
 using namespace ax;
 
@@ -296,8 +285,10 @@ extern "C" int auxssm_systematic_resample(auxssm_handle h, int dtype, int32_t ro
     return AUXSSM_OK;
 }
 
-// auxssm_csmc_sweep (prog == nullptr) and auxssm_csmc_sweep_program: one validation, one workspace plan, one chain batching
-static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk, const auxssm_fk_program_s* prog, const auxssm_fk_user* user, int32_t C,
+// auxssm_csmc_sweep (prog == nullptr), auxssm_csmc_sweep_program and auxssm_csmc_sweep_chain_dynamics (dyn != nullptr: per-chain transitions, csmc_chain.hip):
+// one validation, one workspace plan, one chain batching
+static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk, const auxssm_fk_program_s* prog, const auxssm_fk_user* user,
+                           const auxssm_fk_chain_dynamics* dyn, int32_t C,
                            int32_t T, int32_t N, int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise, int32_t* ancestors,
                            void* xs_out, void* log_ws_out, int32_t* As_out) {
     AX_NEED_H(h);
@@ -313,6 +304,28 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
     const int D = fk->dx;
     const bool wide = D > CS_MAXD;  // csmc_wide.hip: one wave per chain, particles' components in LDS rows
     const bool ug = prog && (prog->flags & AUXSSM_FK_USER_POTENTIAL), um = prog && (prog->flags & AUXSSM_FK_USER_MEAN);
+    if (dyn) {  // per-chain transitions: the register kernels' independent and bootstrap proposals on linear, time-invariant dynamics
+        if (!dyn->F || !dyn->b || !dyn->chol_Q) {
+            set_error("dyn->%s is NULL: per-chain dynamics need the device arrays F (C,dx,dx), b (C,dx) and chol_Q (C,dx,dx)", !dyn->F ? "F" : (!dyn->b ? "b" : "chol_Q"));
+            return AUXSSM_ERR_ARG;
+        }
+        if (D > CS_MAXD) {
+            set_error("dx=%d: per-chain dynamics run the register sweep kernels, dx <= %d (the wide-state kernels read one shared transition)", D, CS_MAXD);
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+        if (fk->proposal == AUXSSM_PROP_AUX_GUIDED) {
+            set_error("guided proposals run chain-shared transitions: with per-chain dynamics their K_t / chol Lambda_t tables would be per chain and step");
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+        if (fk->transition != AUXSSM_TRANS_LINEAR) {
+            set_error("per-chain dynamics are linear-Gaussian (F, b, chol_Q): AUXSSM_TRANS_LORENZ63_EM has none to replace");
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+        if (fk->F_t || fk->b_t || fk->chol_Q_t) {
+            set_error("per-chain dynamics are time-invariant: F_t / b_t / chol_Q_t must be NULL (one transition per chain, not per chain and step)");
+            return AUXSSM_ERR_UNSUPPORTED;
+        }
+    }
     if (prog) {
         if (!user) {
             set_error("user must be non-NULL");
@@ -423,6 +436,7 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
     ws.add(a.u, CT * D * sR);
     if (fk->gradient) ws.add(a.grad, CT * D * sR);
     if (fk->F_t) ws.add(ctt, (size_t)T * (1 + D) * sR);  // constants + reciprocal diagonals of the T - 1 transitions
+    if (dyn) ws.add(ctt, (size_t)C * (1 + D) * sR);      // ... of the C per-chain transitions
     if (!xs_out) ws.add(a.xs, CBT * N * D * sR);
     if (!log_ws_out) ws.add(a.lws, CBT * N * sR);
     if (!As_out && !backward) ws.add(a.As, (size_t)cb * T1 * N * 4);
@@ -466,6 +480,7 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
         a.eps_prop = pe;
         a.u_res = pu;
     }
+    if (dyn) return run_csmc_chain(h, dtype, fk, dyn, a, ctt);
     if (wide) return run_csmc_wide(h, dtype, fk, a, ctt);
     return csmc_dispatch(dtype, D, [&](auto r, auto d) {
         using R = decltype(r);
@@ -477,7 +492,7 @@ static int csmc_sweep_impl(auxssm_handle h, int dtype, const auxssm_fk_model* fk
 extern "C" int auxssm_csmc_sweep(auxssm_handle h, int dtype, const auxssm_fk_model* fk, int32_t C, int32_t T, int32_t N,
                                  int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise,
                                  int32_t* ancestors, void* xs_out, void* log_ws_out, int32_t* As_out) {
-    return csmc_sweep_impl(h, dtype, fk, nullptr, nullptr, C, T, N, backward, sqrt_half_delta, x, noise, ancestors, xs_out, log_ws_out, As_out);
+    return csmc_sweep_impl(h, dtype, fk, nullptr, nullptr, nullptr, C, T, N, backward, sqrt_half_delta, x, noise, ancestors, xs_out, log_ws_out, As_out);
 }
 
 extern "C" int auxssm_csmc_sweep_program(auxssm_handle h, auxssm_fk_program prog, int dtype, const auxssm_fk_model* fk, const auxssm_fk_user* user,
@@ -487,5 +502,15 @@ extern "C" int auxssm_csmc_sweep_program(auxssm_handle h, auxssm_fk_program prog
         set_error("program is NULL");
         return AUXSSM_ERR_ARG;
     }
-    return csmc_sweep_impl(h, dtype, fk, prog, user, C, T, N, backward, sqrt_half_delta, x, noise, ancestors, xs_out, log_ws_out, As_out);
+    return csmc_sweep_impl(h, dtype, fk, prog, user, nullptr, C, T, N, backward, sqrt_half_delta, x, noise, ancestors, xs_out, log_ws_out, As_out);
+}
+
+extern "C" int auxssm_csmc_sweep_chain_dynamics(auxssm_handle h, int dtype, const auxssm_fk_model* fk, const auxssm_fk_chain_dynamics* dyn, int32_t C, int32_t T,
+                                                int32_t N, int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise,
+                                                int32_t* ancestors, void* xs_out, void* log_ws_out, int32_t* As_out) {
+    if (!dyn) {
+        set_error("dyn is NULL (the chain-shared sweep is auxssm_csmc_sweep)");
+        return AUXSSM_ERR_ARG;
+    }
+    return csmc_sweep_impl(h, dtype, fk, nullptr, nullptr, dyn, C, T, N, backward, sqrt_half_delta, x, noise, ancestors, xs_out, log_ws_out, As_out);
 }

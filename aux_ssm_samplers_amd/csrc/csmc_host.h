@@ -270,6 +270,22 @@ static int csmc_prologue(auxssm_ctx* h, const auxssm_fk_model* fk, const CsmcArg
     return m.gradient ? grad() : AUXSSM_OK;
 }
 
+// ---- what the launchers of the sequential passes share (csmc.hip::run_csmc / run_csmc_program, csmc_chain.hip::run_csmc_chain) ----
+// dynamic LDS of the forward / backward pass (csmc_sweep.h: k_csmc_fwd, k_csmc_bwd) for TB lanes
+static size_t fwd_lds(int TB, int D, size_t sR) { return (size_t)2 * (cpad(TB) + TB * D) * sR + 48 * sR + 64; }
+static size_t bwd_lds(int TB, int D, size_t sR) { return (size_t)2 * TB * sR + 64 * sR + (size_t)2 * TB * D * sR + 2 * sR + 64; }
+
+// the workgroup shapes with instantiations of their own (NW of k_csmc_fwd / k_csmc_bwd): sixteen full waves, eight full waves, 0 = any N
+static int nw_class(int N) { return N == 1024 ? 16 : (N == 512 ? 8 : 0); }
+// f(std::true_type / std::false_type) for b; f(std::integral_constant<int, nw>) for an nw_class
+template <typename F> static auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <typename F> static auto with_nw(int nw, F&& f) {
+    return nw == 16 ? f(std::integral_constant<int, 16>{}) : (nw == 8 ? f(std::integral_constant<int, 8>{}) : f(std::integral_constant<int, 0>{}));
+}
+
+// a pass of the built-in family, as run_csmc launches it
+template <typename R> using SweepKernel = void (*)(CsmcArgs, FkDev<R>);
+
 // the arguments of the batch [c0, c0 + cb) of chains (CsmcArgs::c0)
 static CsmcArgs csmc_batch(const CsmcArgs& a, int c0, int cb) {
     CsmcArgs ab = a;

@@ -17,7 +17,8 @@ template <typename R> struct FkDev {
     R m0[CS_MAXD], LP0[CS_MAXD * CS_MAXD], F[CS_MAXD * CS_MAXD], b[CS_MAXD], LQ[CS_MAXD * CS_MAXD];
     R c_init, c_trans, c_obs, inv_sig_y;  // additive constants: -sum log L_kk - D/2 log 2pi, etc.
     R iLP0[CS_MAXD], iLQ[CS_MAXD];        // reciprocal diagonals of LP0 / LQ: the log-densities multiply by them (sweep contract v3)
-    // time-varying linear transitions (device arrays, row t = transition t -> t+1; null: the invariant F / b / LQ above)
+    // time-varying linear transitions (device arrays, row t = transition t -> t+1; null: the invariant F / b / LQ above); under a ChainDyn policy (below) the
+    // same five pointers hold PER-CHAIN rows instead, row c = chain c's time-invariant transition: (C, D, D), (C, D), (C, D, D), (C), (C, D)
     const R* Ft;   // (T-1, D, D)
     const R* bt;   // (T-1, D)
     const R* LQt;  // (T-1, D, D) lower
@@ -48,6 +49,41 @@ template <typename R, int D, bool TV> __device__ __forceinline__ TransT<R> trans
     if constexpr (TV) return TransT<R>{m.Ft + t * D * D, m.bt + t * D, m.LQt + t * D * D, D, m.ctt[t], m.idt + t * D};
     else return TransT<R>{m.F, m.b, m.LQ, CS_MAXD, m.c_trans, m.iLQ};
 }
+// ---- per-chain, time-invariant transitions (auxssm_csmc_sweep_chain_dynamics: particle Gibbs over (x, F, b, Q)) ----------------------------------------------
+// The third source of a TransT: row c of PER-CHAIN device arrays, c the GLOBAL chain.  The model's five pointers then hold F (C, D, D), b (C, D), chol_Q (C, D, D)
+// lower, the constants (C) and the reciprocal diagonals (C, D) -- the layout of the time-varying rows with the chain in the place of the time step (the constants
+// come from the same k_csmc_ctrans, run over C rows), so that FkDev and every kernel argument keep their layout.  The mode belongs to the model POLICY of a kernel
+// (ChainDyn<P>::value, a compile-time constant: FkBuiltinChain below, the built-in family only), never to a run-time test: the kernels of every other policy keep
+// their code.  A one-thread-per-(chain, step) kernel reads its row through pointers (trans_chain); a persistent sweep kernel, whose chain is its workgroup, copies
+// the row ONCE, before its time loop, into scalar registers (TransC::load: every load is wave-uniform and independent of t), and hands the loop a TransT of that
+// copy -- the loop then costs what the shared-parameter kernels' does, not a row of loads per step.
+template <typename P> struct ChainDyn { static constexpr bool value = false; };
+template <typename R, int D> __device__ __forceinline__ TransT<R> trans_chain(const FkDev<R>& m, long long c) {
+    return TransT<R>{m.Ft + c * D * D, m.bt + c * D, m.LQt + c * D * D, D, m.ctt[c], m.idt + c * D};
+}
+// v, which the caller knows to be the same in every lane, as a scalar-register value
+__device__ __forceinline__ float uniform_(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ double uniform_(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+template <typename R, int D> struct TransC {
+    R F[D * D], b[D], LQ[D * D], iL[D], c_trans;  // (leading dimension D; the strict upper triangle of LQ is never read and stays unset)
+    __device__ __forceinline__ void load(const FkDev<R>& m, long long c) {
+        const TransT<R> g = trans_chain<R, D>(m, c);
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            b[k] = uniform_(g.b[k]);
+            iL[k] = uniform_(g.iL[k]);
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                F[k * D + j] = uniform_(g.F[k * D + j]);
+                if (j <= k) LQ[k * D + j] = uniform_(g.LQ[k * D + j]);
+            }
+        }
+        c_trans = uniform_(g.c_trans);
+    }
+    __device__ __forceinline__ TransT<R> trans() const { return TransT<R>{F, b, LQ, D, c_trans, iL}; }
+};
 
 struct CsmcArgs {
     int C, T, N, backward;
@@ -803,6 +839,9 @@ template <typename R, int D, PotV V = PotV::SEP> struct FkBuiltin {
         trans_mean_vjp_t<R, D>(m, tr, xp, v, out);
     }
 };
+// the built-in family on per-chain transitions (ChainDyn above): the same two model functions, the transition record from row `chain` of the per-chain arrays
+template <typename R, int D, PotV V = PotV::SEP> struct FkBuiltinChain : FkBuiltin<R, D, V> {};
+template <typename R, int D, PotV V> struct ChainDyn<FkBuiltinChain<R, D, V>> { static constexpr bool value = true; };
 
 // gradient at u of  log M0(u_0) + G0(u_0) + sum_t [log Mt(u_{t+1} | u_t) + Gt(u_{t+1}, u_t)]  (csmc/independent.py:121-134, jax.grad there), one thread per
 // (chain, time step):  d_x log G_t(u_t, u_{t-1}) [+ d_xprev log G_{t+1}(u_{t+1}, u_t)] - Q^-1 (u_t - mean_t(u_{t-1})) + J_{t+1}(u_t)^T Q^-1 (u_{t+1} - mean_{t+1}(u_t))
@@ -810,6 +849,7 @@ template <typename R, int D, PotV V = PotV::SEP> struct FkBuiltin {
 // added to the d_x term before anything else: a potential that leaves it at zero gives the built-in gradient bit for bit.
 template <typename R, int D, typename P = FkBuiltin<R, D>, typename... PA> __global__ void k_csmc_grad(CsmcArgs a, FkDev<R> m, PA... pa) {
     const P pol{pa...};
+    constexpr bool PC = ChainDyn<P>::value;  // per-chain transitions: this thread's chain is g / T (a.C counts all chains here: the gradient is not batched)
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)a.C * a.T) return;
     const long long t = g % a.T;
@@ -847,7 +887,7 @@ template <typename R, int D, typename P = FkBuiltin<R, D>, typename... PA> __glo
         for (int k = 0; k < D; ++k) r[k] = ut[k] - m.m0[k];
         cho_solve_fixed<R, D>(m.LP0, CS_MAXD, r, w);
     } else {
-        const TransT<R> tr = trans_at<R, D>(m, t - 1);
+        const TransT<R> tr = PC ? trans_chain<R, D>(m, g / a.T) : trans_at<R, D>(m, t - 1);
         pol.mean(m, tr, (int)t, u - D, mu);
 #pragma unroll
         for (int k = 0; k < D; ++k) r[k] = ut[k] - mu[k];
@@ -857,7 +897,7 @@ template <typename R, int D, typename P = FkBuiltin<R, D>, typename... PA> __glo
     for (int k = 0; k < D; ++k) gr[k] = gr[k] - w[k];
     // density of u_{t+1} given u_t:  J(u_t)^T Q^-1 (u_{t+1} - mean(u_t))
     if (t + 1 < a.T) {
-        const TransT<R> tr = trans_at<R, D>(m, t);
+        const TransT<R> tr = PC ? trans_chain<R, D>(m, g / a.T) : trans_at<R, D>(m, t);
         pol.mean(m, tr, (int)t + 1, ut, mu);
 #pragma unroll
         for (int k = 0; k < D; ++k) r[k] = u[D + k] - mu[k];
@@ -878,6 +918,8 @@ template <typename R, int D, typename P = FkBuiltin<R, D>, typename... PA> __glo
 // SP = 2: the guided proposals (GuidedT above; time-invariant transitions, GRAD = the proposal mean reads the shifted u of CsmcArgs::grad): a compile-time variant, so
 // that the instantiations of the other proposals hold none of its code; its weights have no reduction-free bound (CsmcArgs::gb is null: exact maxima)
 // P: the model policy (above); PA: its kernel arguments (none for the built-in family, so the built-in kernels take exactly (CsmcArgs, FkDev) as before)
+// ChainDyn<P>: per-chain transitions (FkBuiltinChain; csmc_chain.hip) -- TV = false, SP = 0 or 1: the chain's row is copied into scalar registers before the loop
+// and every step reads that copy; the backward pass and k_csmc_grad (one thread per (chain, step): its row through pointers) follow the same switch
 template <typename R, int D, bool TV, bool GRAD, int NW, int SP = 0, typename P = FkBuiltin<R, D>, typename... PA>
 __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA... pa) {
     const P pol{pa...};
@@ -898,6 +940,10 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
     R* xbuf = cbuf + 2 * CP;            // [2][TB][D]
     R* red = xbuf + 2 * TB * D;         // [48]
     const int ch = a.c0 + blockIdx.x;
+    constexpr bool PC = ChainDyn<P>::value;  // per-chain transitions: the chain's row, read once into scalar registers (TransC); untouched otherwise
+    static_assert(!(PC && TV) && !(PC && SP == 2), "per-chain transitions are time-invariant and have no guided tables");
+    TransC<R, D> trc;
+    if constexpr (PC) trc.load(m, ch);
     const bool live = NW > 0 ? true : tid < N;
     if (tid < 16) red[32 + tid] = 0;  // totals of absent groups: +0 (totals_prefix reads all 16 slots; ordered by the first barrier below)
     const R* xstar = (const R*)a.x + (long long)ch * T * D;
@@ -1030,7 +1076,7 @@ __global__ void __launch_bounds__(1024) k_csmc_fwd(CsmcArgs a, FkDev<R> m, PA...
 #pragma unroll
         for (int k = 0; k < D; ++k) xp[k] = xprev[idx * D + k];
         // propagate (csmc.py:91-92); the transition t - 1 -> t (time-varying: row t - 1 of the device arrays)
-        const TransT<R> tr = trans_at_c<R, D, TV>(m, t - 1);
+        const TransT<R> tr = PC ? trc.trans() : trans_at_c<R, D, TV>(m, t - 1);
         if constexpr (SP == 2) {  // guided: pred = the parent's transition mean, P = Q
             R mu[D], ut[D];
             pol.mean(m, tr, t, xp, mu);
@@ -1112,6 +1158,10 @@ __global__ void __launch_bounds__(1024) k_csmc_bwd(CsmcArgs a, FkDev<R> m, PA...
     R* xpub = red + 64;              // [2][TB][D] candidate particles of the step, by step parity
     R* ubuf = xpub + 2 * TB * D;     // [2] the step's uniform, by step parity
     const int ch = a.c0 + blockIdx.x;
+    constexpr bool PC = ChainDyn<P>::value;  // per-chain transitions, as in the forward pass
+    static_assert(!(PC && TV), "per-chain transitions are time-invariant");
+    TransC<R, D> trc;
+    if constexpr (PC) trc.load(m, ch);
     const bool live = NW > 0 ? true : tid < N;
     if (tid < 16) red[32 + tid] = 0, red[48 + tid] = 0;  // totals of absent groups: +0 (totals_prefix)
     const R* xs = (const R*)a.xs + (long long)ch * T * N * D;
@@ -1189,7 +1239,7 @@ __global__ void __launch_bounds__(1024) k_csmc_bwd(CsmcArgs a, FkDev<R> m, PA...
             if (tid == 0) un_nx = ((const R*)a.u_bwd)[ub_base + (t - 1)];
         }
         R lw = ninf;
-        const TransT<R> tr = trans_at_c<R, D, TV>(m, t);  // Pt.logpdf(x_{t+1}, xs_t, params_t) (csmc.py:136)
+        const TransT<R> tr = PC ? trc.trans() : trans_at_c<R, D, TV>(m, t);  // Pt.logpdf(x_{t+1}, xs_t, params_t) (csmc.py:136)
         if (live) {
             R mu[D];
             pol.mean(m, tr, t + 1, xi, mu);

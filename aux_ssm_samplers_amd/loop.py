@@ -40,6 +40,9 @@ class LorenzThetaStep:
         self._eps = None
 
     def __call__(self, key, chains):
+        from .kalman.generic import DeviceChains
+        if not isinstance(chains, DeviceChains):
+            raise ValueError("LorenzThetaStep: the step writes the parameter rows of the Kalman sampler's LORENZ63_EXT sweep; it needs kalman.DeviceChains")
         handle = chains.handle
         par = self.model.par_device(handle, chains.dtype, chains.C)
         if self._eps is None or self._eps.handle is not handle or self._eps.shape != (chains.C, 3) or self._eps.dtype != chains.dtype:
@@ -115,10 +118,27 @@ class DynamicsThetaStep:
     (nu_n - i) / 2 (the update doubles them to chi-squares), the two normal buffers are filled, the update runs on chains.x in chains.layout; no host synchronisation.
     A chain whose posterior cannot be factorised keeps its parameters and raises its flag (flags(chains)).
     Keys: the call's key is split by random.split, which is jax.random.split under random.set_compat("jax") -- as loop() splits its own; the three fills are the
-    package's Threefry streams in either mode (the reference has no such step, so there are no jax.random draws to reproduce)."""
+    package's Threefry streams in either mode (the reference has no such step, so there are no jax.random draws to reproduce).
+
+    Particle Gibbs: model may instead be the csmc.LinearGaussianDynamics of a conditional-SMC kernel (time-invariant, dx <= 4) -- the step then serves
+    csmc.CsmcChains, and loop(..., theta_step=step) alternates x | theta, y by cSMC with theta | x by this draw:
+
+        Mt = csmc.LinearGaussianDynamics(F, b, Q);   init, kernel = csmc.get_independent_kernel(M0, G0, Mt, Gt, N=..., backward=True, Pt=Mt)
+        step = DynamicsThetaStep(Mt, MNIWPrior(M0, K0, nu0, Psi0));   loop(key, delta, state, kernel, None, n_iter, theta_step=step)
+
+    On its first call it attaches per-chain buffers to the chains (chains.dynamics, a csmc._device.ChainDynamics: the live F, b, Q, chol_Q, staging copies and
+    flags, all starting from the model's values); from then on the sequential sweep reads chain c's own transition (auxssm_csmc_sweep_chain_dynamics; kernels that
+    cannot -- guided, parallel in time, user programs, dx > 4 -- refuse such chains).  Every call: the same three key splits and fills, the update on chains.x into
+    the STAGING buffers, then auxssm_csmc_dynamics_commit, which factors each chain's new Q as rounded to the chains' dtype and moves the whole quadruple into the live
+    buffers, or leaves it and raises the chain's flag (1 - 4 the update's codes, 5: Q is not positive definite once rounded).  No host synchronisation."""
 
     def __init__(self, model, prior):
         from .kalman import models as M
+        from .csmc import models as CM
+        self._csmc = isinstance(model, (CM.LinearGaussianDynamics, CM.Lorenz63Dynamics, CM.DeviceGaussianDynamics))
+        if self._csmc:
+            self._init_csmc(model, prior)
+            return
         who = type(model).__name__
         if isinstance(model, M.LorenzModel):
             raise ValueError("DynamicsThetaStep: LorenzModel is parameterised by its drift (theta, dt), not by (F, b, Q): use LorenzThetaStep")
@@ -143,6 +163,57 @@ class DynamicsThetaStep:
         self._shapes = [0.5 * (prior.nu0 + model.T - 1 - i) for i in range(model.dx)]
         self._work = {}
 
+    def _init_csmc(self, model, prior):
+        from .csmc import models as CM
+        if isinstance(model, CM.Lorenz63Dynamics):
+            raise ValueError("DynamicsThetaStep: Lorenz63Dynamics is parameterised by its drift (theta, dt), not by (F, b, Q): there is nothing for the step to draw")
+        if isinstance(model, CM.DeviceGaussianDynamics):
+            raise ValueError("DynamicsThetaStep: DeviceGaussianDynamics has a user-defined transition mean (device code), not (F, b): the step covers "
+                             "csmc.LinearGaussianDynamics")
+        if not isinstance(prior, MNIWPrior):
+            raise ValueError("DynamicsThetaStep: prior must be an MNIWPrior")
+        if model.time_varying:
+            raise ValueError("DynamicsThetaStep: the LinearGaussianDynamics varies in time (F is (T - 1, d, d)); the step draws ONE (F, b, Q) per chain")
+        F, Q = (np.atleast_2d(np.asarray(a, np.float64)) for a in (model.F, model.Q))
+        d = F.shape[0]
+        if d > 4:
+            raise ValueError(f"DynamicsThetaStep: per-chain dynamics run the cSMC kernels of dx <= 4 (the model has dx = {d})")
+        if F.shape != (d, d) or Q.shape != (d, d) or np.size(model.b) != d:
+            raise ValueError(f"DynamicsThetaStep: need F (d, d), b (d,), Q (d, d); got {F.shape}, {np.shape(model.b)}, {Q.shape}")
+        if prior.d != d:
+            raise ValueError(f"DynamicsThetaStep: the prior is for d = {prior.d}, the model has dx = {d}")
+        self.model, self.prior, self.dx = model, prior, d
+        self._prior_c = prior.struct(2.0)
+        self._work = {}
+
+    def _dynamics(self, chains):
+        """-> the chains' ChainDynamics, attached (from the model's F, b, Q) on first use"""
+        from .csmc._device import ChainDynamics
+        if chains.dynamics is None:
+            chains.dynamics = ChainDynamics(chains.handle, chains.dtype, chains.C, self.model.F, self.model.b, self.model.Q)
+        dyn = chains.dynamics
+        if (dyn.C, dyn.dx) != (chains.C, self.dx):
+            raise ValueError(f"DynamicsThetaStep: the chains hold per-chain parameters of {dyn.C} chains of dx = {dyn.dx}, the step is for {chains.C} of dx = {self.dx}")
+        return dyn
+
+    def _call_csmc(self, key, chains):
+        handle, dtype, Cn, d = chains.handle, chains.dtype, chains.C, self.dx
+        dyn = self._dynamics(chains)
+        wk = (id(handle), np.dtype(dtype).str, Cn)
+        work = self._work.get(wk)
+        if work is None:
+            self._work.clear()
+            work = self._work[wk] = (handle.empty((Cn, d), dtype), handle.empty((Cn, d, d), dtype), handle.empty((Cn, d, d + 1), dtype))
+        chi, eps_w, eps_a = work
+        k_chi, k_w, k_a = _random.split(key, 3)
+        handle.rng_gamma_into(k_chi, 0, [0.5 * (self.prior.nu0 + chains.T - 1 - i) for i in range(d)], chi)
+        handle.rng_normal_into(k_w, 0, eps_w)
+        handle.rng_normal_into(k_a, 0, eps_a)
+        sc = 1 if Cn > 1 else 0
+        handle.dynamics_theta_update(chains.x, self._prior_c, chi, eps_w, eps_a, dyn.F_new.arr(sc * d * d, 0, 0), dyn.b_new.arr(sc * d, 0, 0),
+                                     dyn.Q_new.arr(sc * d * d, 0, 0), dyn.step_flags)
+        dyn.commit()
+
     # ---- the model's per-chain parameter buffers ----
     def _params(self, handle, dtype, C):
         """-> (F (C, d, d), b (C, d), Q (C, d, d)) DeviceArrays the device model points at, made per-chain on first use"""
@@ -162,13 +233,26 @@ class DynamicsThetaStep:
 
     def _check_chains(self, chains):
         from .kalman.generic import DeviceChains
+        if self._csmc:
+            from .csmc._device import CsmcChains
+            if not isinstance(chains, CsmcChains):
+                raise ValueError("DynamicsThetaStep: the step was built on a csmc.LinearGaussianDynamics and needs csmc.CsmcChains; for kalman.DeviceChains build "
+                                 "it on the Kalman-sampler model")
+            if chains.dx != self.dx:
+                raise ValueError(f"DynamicsThetaStep: the chains have dx = {chains.dx}, the model {self.dx}")
+            if chains.T < 2:
+                raise ValueError("DynamicsThetaStep: the chains have no transition (T < 2)")
+            return
         if not isinstance(chains, DeviceChains):
-            raise ValueError("DynamicsThetaStep: cSMC chains carry their transition parameters in the Feynman-Kac model; the step needs kalman.DeviceChains")
+            raise ValueError("DynamicsThetaStep: cSMC chains carry their transition parameters in the Feynman-Kac model; the step needs kalman.DeviceChains "
+                             "(for csmc.CsmcChains build it on the kernel's csmc.LinearGaussianDynamics)")
         if (chains.T, chains.dx) != (self.model.T, self.model.dx):
             raise ValueError(f"DynamicsThetaStep: the chains are (T, dx) = ({chains.T}, {chains.dx}), the model ({self.model.T}, {self.model.dx})")
 
     def __call__(self, key, chains):
         self._check_chains(chains)
+        if self._csmc:
+            return self._call_csmc(key, chains)
         handle, dtype, Cn, d = chains.handle, chains.dtype, chains.C, self.model.dx
         F, b, Q = self._params(handle, dtype, Cn)
         wk = (id(handle), np.dtype(dtype).str, Cn)
@@ -190,11 +274,17 @@ class DynamicsThetaStep:
     def params(self, chains):
         """-> (F (C, d, d), b (C, d), Q (C, d, d)) as host arrays (synchronises)"""
         self._check_chains(chains)
+        if self._csmc:
+            dyn = self._dynamics(chains)
+            return dyn.F.to_host(), dyn.b.to_host(), dyn.Q.to_host()
         F, b, Q = self._params(chains.handle, chains.dtype, chains.C)
         return F.to_host(), b.to_host(), Q.to_host()
 
     def flags(self, chains):
-        """-> (C,) int32: 0, or why the last call left chain c unchanged (include/auxssm.h: auxssm_dynamics_theta_update)"""
+        """-> (C,) int32: 0, or why the last call left chain c unchanged (include/auxssm.h: auxssm_dynamics_theta_update; cSMC chains: auxssm_csmc_dynamics_commit,
+        which adds 5 -- Q not positive definite once rounded to the chains' dtype)"""
+        if self._csmc:
+            return chains.dynamics.flags.to_host() if getattr(chains, "dynamics", None) is not None else np.zeros(chains.C, np.int32)
         work = self._work.get((id(chains.handle), np.dtype(chains.dtype).str, chains.C))
         return work[3].to_host() if work is not None else np.zeros(chains.C, np.int32)
 
@@ -378,10 +468,11 @@ class ThetaSteps:
 def loop(key, init_delta, init_state, kernel_fn, delta_fn, n_iter, target_alpha=None, lr=None, beta=0.01, theta_step=None,
          callback=None):
     """See module docstring.  init_state.x: DeviceChains (kernel_fn(key, state, delta) from kalman.get_kernel) or CsmcChains (from
-    csmc.get_kernel / get_independent_kernel).  theta_step: called as theta_step(key, chains) after every sweep (Kalman chains) with the second child of the sweep's key -- a LorenzThetaStep (the Lorenz drift
+    csmc.get_kernel / get_independent_kernel).  theta_step: called as theta_step(key, chains) after every sweep (and, on cSMC chains, after the sweep's moments are folded) with the second child of the sweep's key -- a LorenzThetaStep (the Lorenz drift
     parameters), a DynamicsThetaStep ((F, b, Q) of linear-Gaussian dynamics under an MNIWPrior: a Gibbs sampler over (x, F, b, Q)), an ObservationThetaStep
     ((H, c, R) of an LGConcatModel's observation model under an ObsMNIWPrior) or a ThetaSteps of several (both of the latter: a Gibbs sampler over
-    (x, F, b, Q, H, c, R)); all write the model's device parameters in place, one set per chain, without a host synchronisation.
+    (x, F, b, Q, H, c, R)); all write the model's device parameters in place, one set per chain, without a host synchronisation.  On cSMC chains: a
+    DynamicsThetaStep built on the kernel's csmc.LinearGaussianDynamics (particle Gibbs over (x, F, b, Q)); a step built for the other kind of chains raises ValueError.
     callback(i, state) is called after every sweep (e.g. to keep thinned samples; it may synchronise).
 
     Returns (n_iter, stats, state, delta, window_avg_acceptance, avg_acceptance): stats = (sq_jump, mean, sq_mean) as DeviceArrays
@@ -396,8 +487,6 @@ def loop(key, init_delta, init_state, kernel_fn, delta_fn, n_iter, target_alpha=
         raise ValueError("loop() runs on resident chains: init_state.x must be a kalman.DeviceChains or a csmc.CsmcChains")
     if delta_fn is not None and (target_alpha is None or lr is None):
         raise ValueError("target_alpha and lr are required with delta_fn")
-    if theta_step is not None and not kalman:
-        raise ValueError("theta_step needs Kalman chains")
     handle, dtype = chains.handle, chains.dtype
     split = _random.jax_split if _random.compat() == "jax" else _random.split   # (experiment.py:90: keys = jax.random.split(key, n_iter))
     keys = split(key, n_iter)
@@ -433,9 +522,12 @@ def loop(key, init_delta, init_state, kernel_fn, delta_fn, n_iter, target_alpha=
                 if theta_step is not None:
                     theta_step(k_theta, chains)
             else:
+                k_sweep, k_theta = (keys[i], None) if theta_step is None else split(keys[i], 2)
                 x_prev.copy_from(chains.x)
-                state = kernel_fn(keys[i], state, None)
+                state = kernel_fn(k_sweep, state, None)
                 handle.stats_update(i, x_prev, chains.x, stats)
+                if theta_step is not None:   # particle Gibbs: theta | x on the trajectory the sweep has just drawn
+                    theta_step(k_theta, chains)
             handle.accept_update(i, beta, flags, avg, window)
             if delta_fn is not None:
                 lr_i = (n_iter - i) * lr / n_iter

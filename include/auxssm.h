@@ -511,6 +511,39 @@ int auxssm_csmc_sweep_program(auxssm_handle h, auxssm_fk_program prog, int dtype
                               int32_t T, int32_t N, int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise,
                               int32_t* ancestors, void* xs_out, void* log_ws_out, int32_t* As_out);
 
+/* ---- particle Gibbs over (x, F, b, Q): the sequential sweep on PER-CHAIN transitions (csrc/csmc_chain.hip) -----------------------------------------
+ * auxssm_csmc_sweep_chain_dynamics: auxssm_csmc_sweep -- the same validation, workspace plan, chain batching, noise and outputs, the arguments from C on
+ * exactly its own -- with chain c's linear-Gaussian transition x_{t+1} | x_t ~ N(F_c x_t + b_c, chol_Q_c chol_Q_c^T) taken from row c of `dyn`, DEVICE arrays
+ * of `dtype` that the caller owns: F (C,dx,dx), b (C,dx), chol_Q (C,dx,dx) lower (the strict upper triangle is not read).  c is the global chain, whatever
+ * the batching.  The model's host F / b / chol_Q must still be valid (they are checked) and take no part in the transition; m0 / chol_P0 and the potential
+ * are shared by the chains as before.  A chain's sweep is bit for bit the one-chain auxssm_csmc_sweep whose time-varying rows F_t / b_t / chol_Q_t repeat
+ * that chain's row T - 1 times, on the chain's slices of the noise (Threefry: on the explicit arrays its streams stand for).  The kernels copy the row into
+ * scalar registers once, before their time loop: the sweep costs what the chain-shared one does.
+ * Covered: dx <= 4; AUXSSM_PROP_BOOTSTRAP_LG and AUXSSM_PROP_AUX_INDEPENDENT with every gradient mode; the eight potentials; ancestor tracing and backward
+ * sampling; fp32 and fp64; both noise modes.  AUXSSM_ERR_UNSUPPORTED before anything is enqueued, with the limit in the message: dx > 4 (the wide-state
+ * kernels), AUXSSM_PROP_AUX_GUIDED (its K_t / chol Lambda_t tables would be per chain and step), AUXSSM_TRANS_LORENZ63_EM, F_t / b_t / chol_Q_t set.  User
+ * programs and the parallel-in-time sweep have no such entry point.  AUXSSM_ERR_ARG: dyn or one of its arrays NULL, and whatever auxssm_csmc_sweep refuses.
+ *
+ * auxssm_csmc_dynamics_commit: one launch between auxssm_dynamics_theta_update, which has written its draw of (F, b, Q) | x into STAGING buffers F_new (C,dx,dx),
+ * b_new (C,dx), Q_new (C,dx,dx) (chain strides dx dx, dx, dx dx; time stride 0) and its codes into step_flags (C), and the next sweep.  For each chain, in one
+ * lane (csrc/chain_dynamics.h, which a host compiler runs too): factor Q_new in double from its values AS ROUNDED TO `dtype` (auxssm_dynamics_theta_update's
+ * pivot rule), round the factor to `dtype`, and write the whole quadruple into the live buffers F, b, Q, chol_Q (dyn points at F, b, chol_Q) -- only if the update
+ * left the chain unflagged, the factor exists, and every entry of the quadruple is finite in `dtype` with a positive factor diagonal.  Otherwise the live
+ * quadruple is untouched and flags[c] holds the update's code (1 - 4) or 5: Q is not positive definite once rounded to `dtype`.  flags[c] = 0 for a committed
+ * chain; flags may be step_flags itself.  A sweep therefore never reads a non-finite factor, or an F of one draw beside a Q of another.
+ * Refused before anything is enqueued: C < 1, dx < 1, a NULL argument (named), a live buffer that is its own staging buffer (AUXSSM_ERR_ARG); dx > 4
+ * (AUXSSM_ERR_UNSUPPORTED). */
+typedef struct {
+    const void* F;      /* device (C,dx,dx) */
+    const void* b;      /* device (C,dx) */
+    const void* chol_Q; /* device (C,dx,dx) lower */
+} auxssm_fk_chain_dynamics;
+int auxssm_csmc_sweep_chain_dynamics(auxssm_handle h, int dtype, const auxssm_fk_model* model, const auxssm_fk_chain_dynamics* dyn, int32_t C, int32_t T,
+                                     int32_t N, int32_t backward, const void* sqrt_half_delta, void* x, const auxssm_csmc_noise* noise,
+                                     int32_t* ancestors, void* xs_out, void* log_ws_out, int32_t* As_out);
+int auxssm_csmc_dynamics_commit(auxssm_handle h, int dtype, int32_t C, int32_t dx, const void* F_new, const void* b_new, const void* Q_new,
+                                const int32_t* step_flags, void* F, void* b, void* Q, void* chol_Q, int32_t* flags);
+
 /* ---- parallel-in-time conditional SMC (conditional dSMC) ------------------------------------------------------------
  * == kernel(key, state, delta) of aux_samplers.csmc.get_independent_kernel(..., parallel=True), classical branch
  * (csmc/independent.py:78-118 on _primitives/csmc/pit/csmc.py:69-114, operator.py, dc_map.py), for C chains at once: all T x N

@@ -29,6 +29,8 @@
                    model, the statistics entry alone in both layouts, auxssm_dynamics_stats on the same state and a device copy: dynamics_theta's four rows
    dynamics_theta  the conjugate step on (F, b, Q) (loop.DynamicsThetaStep) beside one keyed sweep of the same LGConcatModel with per-chain parameters: C2's shape
              (T = 65536, d = 4, fp64) at 1 / 16 / 256 chains and T = 16384, d = 1, fp32 at 1024 chains; the statistics pass alone as bytes/s beside a device copy
+   csmc_theta  per-chain dynamics in the sequential cSMC sweep (particle Gibbs over (x, F, b, Q)): the chain-shared, per-chain and time-varying sweeps of the same
+             values in one process, then loop.DynamicsThetaStep + auxssm_csmc_dynamics_commit on the CsmcChains: C3's shape and SV d = 4, N = 64, 256 chains, fp32
    em   one EM iteration of a time-invariant LGSSM (_primitives.kalman.fit_em's four calls: filter, smoother, auxssm_kalman_smooth_stats, auxssm_lgssm_em_mstep)
              beside the statistics entry alone, filter + smoother alone and a device copy of the bytes the statistics pass reads: C2's shape (T = 65536, dx = dy = 4,
              fp64) at 1 and 16 sequences, and T = 16384, d = 1, fp32 at 64 sequences
@@ -974,6 +976,62 @@ def dynamics_theta(runs=5):
             del chains, spare, state, step, model
 
 
+def csmc_theta(chains=256, runs=3):
+    """Per-chain dynamics in the sequential cSMC sweep (auxssm_csmc_sweep_chain_dynamics) beside the sweeps it must be judged against, in ONE process in alternating
+    batches (alternating_batches; best batch): the chain-shared sweep, the per-chain sweep on C copies of the same (F, b, Q), and the time-varying sweep whose
+    T - 1 rows repeat them -- the same arithmetic on the same values three ways -- then loop.DynamicsThetaStep on the CsmcChains (three fills, the conjugate
+    update into staging, auxssm_csmc_dynamics_commit).  Independent proposals, backward sampling, fp32, resident chains: config C3's shape (SV d = 1, T = 65536,
+    N = 1024) and SV d = 4, T = 4096, N = 64.  per_chain_over_shared should sit at 1 (the chain's row is read once, into scalar registers); a per-chain sweep
+    slower than the time-varying one, which reloads a row every step, would mean the loads are still inside the time loop."""
+    import bench
+    from aux_ssm_samplers_amd.csmc import CsmcChains, CSMCState, GaussianInit, LinearGaussianDynamics, SVPotential, get_independent_kernel
+    from aux_ssm_samplers_amd.csmc._device import ChainDynamics
+    from aux_ssm_samplers_amd.loop import DynamicsThetaStep, MNIWPrior
+    from aux_ssm_samplers_amd.workloads import sv_setup
+    h = _lib.default_handle()
+    T3 = 65536
+    phi, q, xsv, ysv = bench.sv_data(T3, 0)
+    y4, x4, (m0, P0, F, Q, b) = sv_setup(4096, 4)
+    shapes = (("C3 shape SV d=1 T=65536 N=1024", np.zeros(1), np.array([[q]]), np.array([[phi]]), np.zeros(1), np.array([[q]]), ysv.reshape(T3, 1),
+               xsv.reshape(T3, 1), 1024, 0.5),
+              ("SV d=4 T=4096 N=64", m0, P0, F, b, Q, y4, x4, 64, 0.05))
+    for label, m0_, P0_, F_, b_, Q_, y, x, N, delta in shapes:
+        T, d = x.shape
+        M0 = GaussianInit(m0=m0_, P0=P0_)
+        Mt = LinearGaussianDynamics(F=F_, b=b_, Q=Q_)
+        Mtv = LinearGaussianDynamics(F=np.broadcast_to(F_, (T - 1, d, d)), b=np.broadcast_to(b_, (T - 1, d)), Q=np.broadcast_to(Q_, (T - 1, d, d)))
+        G0, Gt = SVPotential(y=y[0]), SVPotential(params=y[1:])
+        _, k_shared = get_independent_kernel(M0, G0, Mt, Gt, N, backward=True, Pt=Mt)
+        _, k_tv = get_independent_kernel(M0, G0, Mtv, Gt, N, backward=True, Pt=Mtv)
+        x0 = np.repeat(x[None], chains, axis=0).astype(np.float32)
+        states = []
+        for per_chain in (False, True, False):
+            cc = CsmcChains(h, x0, delta=delta)
+            if per_chain:
+                cc.dynamics = ChainDynamics(h, cc.dtype, chains, F_, b_, Q_)
+            states.append(CSMCState(x=cc, updated=None))
+        del x0
+        it = [0]
+
+        def sweep(kernel, st):
+            def f():
+                it[0] += 1
+                kernel(it[0], st, None)
+            return f
+
+        sh, pc, tv = alternating_batches(h, [sweep(k_shared, states[0]), sweep(k_shared, states[1]), sweep(k_tv, states[2])], runs)
+        step = DynamicsThetaStep(Mt, MNIWPrior(np.zeros((d, d + 1)), np.eye(d + 1), d + 2.0, np.eye(d)))
+        keys = R.split(R.PRNGKey(3), 64)
+        st, = alternating_batches(h, [lambda: step(keys[it[0] % 64], states[1].x)], runs)
+        print(json.dumps(dict(config=f"{label}, aux-cSMC independent proposals + backward sampling, fp32, resident chains: shared / per-chain / time-varying "
+                                     "transitions of the same values, then the (F, b, Q) step + commit", chains=chains, shared_ms=round(sh[0], 3),
+                              shared_ms_median=round(sh[1], 3), per_chain_ms=round(pc[0], 3), per_chain_ms_median=round(pc[1], 3), time_varying_ms=round(tv[0], 3),
+                              time_varying_ms_median=round(tv[1], 3), per_chain_over_shared=round(pc[0] / sh[0], 4), per_chain_over_time_varying=round(pc[0] / tv[0], 4),
+                              step_commit_ms=round(st[0], 4), step_commit_ms_median=round(st[1], 4), step_over_sweep=round(st[0] / pc[0], 5),
+                              flagged=int(step.flags(states[1].x).any()))), flush=True)
+        del states, step
+
+
 def observation_theta(runs=5):
     """loop.ObservationThetaStep (gamma + two normal fills + statistics, reduce and finish kernels) beside one keyed sweep of the same LGConcatModel once its
     observation model is per-chain (the dense general path, one concatenated record per chain), auxssm_observation_stats alone (on the dense state the step runs
@@ -1091,6 +1149,8 @@ if __name__ == "__main__":
         dynamics_theta()
     if "observation_theta" in which:
         observation_theta()
+    if "csmc_theta" in which:
+        csmc_theta()
     if "em" in which:
         em()
     if "poisson_kalman" in which:

@@ -7,7 +7,7 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "aux_ssm_samplers_amd", "csrc")
-NO_CONTRACT = ("csmc.hip", "csmc_wide.hip", "pit.hip", "pit_wide.hip", "loop.hip", "dynamics_theta.hip", "observation_theta.hip", "lgssm_em.hip")  # the units csrc/Makefile builds with -ffp-contract=off
+NO_CONTRACT = ("csmc.hip", "csmc_chain.hip", "csmc_wide.hip", "pit.hip", "pit_wide.hip", "loop.hip", "dynamics_theta.hip", "observation_theta.hip", "lgssm_em.hip")  # the units csrc/Makefile builds with -ffp-contract=off
 KEYS = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]")
 
 
